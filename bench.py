@@ -9,7 +9,13 @@ starts; the token ids come back through a pinned buffer and step k's text is bui
 
 ``--gpus N`` with N > 1 launches the N ranks itself (``python -m torch.distributed.run``, one process per GPU) unless it is
 already running under such a launcher (WORLD_SIZE set, as the driver does); a WORLD_SIZE that disagrees with ``--gpus`` is an
-error.  Rank 0 prints ONE JSON line (contract in the task statement) with these additions:
+error.  Rank 0 prints ONE JSON line (contract in the task statement).
+
+A plain run sets up, warms up, times the ``--steps`` steps and prints the line (``metric``, ``value``, ``ms_per_step``, ... and
+``config``); nothing else runs.  ``--dump-outputs DIR`` writes what the last timed step computed -- the hypotheses every rank's
+batch received (rank 0 holds them all) -- as DIR/tokens.npy (token ids, -1 past a row's count), DIR/token_counts.npy and
+DIR/scores.npy, float32; the inputs are seeded, so two builds can be compared output for output.
+``--full`` measures everything else as well and adds to the line:
   roofline      the fused FFN kernel: algorithmic FLOPs / HIP-event time of its launches inside the timed region
   value_host_to_host  SURVEY 8(d) / BASELINE.md's definition of the metric (pinned host PCM -> ... -> text on the host); ``value``
                 follows the task contract (inputs resident in HBM when the timed region starts, the PCIe-inclusive rate never
@@ -78,6 +84,13 @@ def flush_c_stdio():
         ctypes.CDLL(None).fflush(None)
     except Exception:                                                   # noqa: BLE001  (cosmetic)
         pass
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: ``arrays`` (name -> array) as DIR/<name>.npy in float32"""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def log(msg):
@@ -399,6 +412,15 @@ class ContractStep:
             self.host[slot].copy_(rows, non_blocking=True)
             self.last_host_slot = slot
 
+    def last_outputs(self):
+        """the hypotheses of the last finished step as a caller receives them (rank 0: every rank's rows): token ids (-1 past
+        a row's count), token counts, scores"""
+        if self.events[self.last_host_slot] is not None:
+            self.events[self.last_host_slot].synchronize()
+        tok, nt, score = self.parallel.unpack_hypothesis_rows(self.host[self.last_host_slot].numpy())
+        tok = np.where(np.arange(tok.shape[1])[None, :] < nt[:, None], tok, -1)
+        return {'tokens': tok, 'token_counts': nt.copy(), 'scores': score.copy()}
+
     def ranks_seen(self):
         """ranks whose hypothesis rows arrived through the LAST step's all-gather: every rank's batch is seeded 1234 + rank, so
         rank r's block of the gathered payload must equal what rank r alone produces -- here checked the cheap way: each rank
@@ -481,19 +503,46 @@ def run_contract(args, rank, world, local):
         eng.profile_select(args.profile_kind)
         eng.profile_read(reset=True)
 
-    dt, dt_local = parallel.timed_region(lambda i: cs.step(i, 'full'), args.steps, args.warmup, after_warmup=prof_on,
-                                         flush=cs.flush, return_local=True)
+    dt, dt_local = parallel.timed_region(lambda i: cs.step(i, 'full'), args.steps, args.warmup,
+                                         after_warmup=prof_on if args.full else None, flush=cs.flush, return_local=True)
     # evidence that the step's exchange really spanned the job: the ranks whose hypothesis rows arrived through the all-gather of
     # the timed region's last step (ContractStep.ranks_seen), and every rank's own time for the region
     per_rank_ms = parallel.gather_floats([dt_local * 1e3 / args.steps])
     ranks_seen = cs.ranks_seen()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cs.last_outputs())
+    n_texts, sample_text = cs.n_texts, (cs.texts[0] if cs.texts else '')
+    log(f'rank {rank}: timed region done: {dt * 1e3 / args.steps:.3f} ms/step')
+    flush_c_stdio()
+    audio_step = world * BATCH * (N_SAMPLES / 16000.0)
+    per = lambda t: {'value': round(audio_step * args.steps / t, 1), 'ms_per_step': round(t * 1e3 / args.steps, 3)}
+    res = None
+    if rank == 0:
+        res = {'metric': 'audio-seconds/sec (RTF^-1), conformer_streaming_fbank b32x10s, PCM->fbank->encoder->ctc_greedy->text',
+               'value': per(dt)['value'], 'unit': 'audio-seconds/sec', 'n_gpus': world, 'steps': args.steps,
+               'warmup': args.warmup, 'ms_per_step': per(dt)['ms_per_step'], 'higher_is_better': True,
+               'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': data_tag(),
+               'config': {'workload': 'configs[1]: conformer.yml streaming fbank, batch=32 synthetic 16 kHz 10 s '
+                                      'utterances per GPU, ctc_greedy, random-init weights V=4233',
+                          'global_batch': world * BATCH, 'audio_seconds_per_step': audio_step,
+                          'parallelism': f'dp{world}', 'world_size_observed': parallel.world_info()[1],
+                          'backend': torch.distributed.get_backend() if torch.distributed.is_initialized() else 'none',
+                          'rccl_ranks_seen': ranks_seen,
+                          'ms_per_step_per_rank': {'min': round(min(per_rank_ms), 3), 'max': round(max(per_rank_ms), 3)},
+                          'algorithmic_gflop_per_step_per_gpu': GFLOP_PER_STEP,
+                          'normalisation': 'use_db_normalization = 2 (masr_transcribe_rows): mean squares on the device in numpy\'s '
+                                           'summation order, gain = the reference\'s scalar numpy expressions on this host -- the '
+                                           'int16 samples are the reference\'s bit for bit; the round trip of step k+1 runs under '
+                                           'step k and is recomputed every step',
+                          'timed_region': 'int16 PCM resident in HBM -> mean squares -> host gains -> masr_transcribe_rows (mode 2) '
+                                          '-> packed hypothesis rows -> (all-gather) -> D2H -> text on host; '
+                                          f'{n_texts} transcripts built inside it, e.g. {sample_text[:12]!r}'}}
+    if not args.full:
+        return eng, res
     prof_ms, prof_n, prof_flops = eng.profile_read(reset=True)
     eng.profile_select(0)
     if hasattr(eng, 'lib'):
         eng.lib.masr_debug_set(eng.h, 16, 1)
-    n_texts, sample_text = cs.n_texts, (cs.texts[0] if cs.texts else '')
-    log(f'rank {rank}: timed region done: {dt * 1e3 / args.steps:.3f} ms/step')
-    flush_c_stdio()
     # (three untimed steps each: the host mode creates its copy stream, device buffers and events in its first steps -- with one
     #  warm-up step ~4 ms of one-time work sat in its 20 timed steps: 6.70 against 6.45-6.47 ms per step, tools/h2h_ab.py)
     dt_dev = parallel.timed_region(lambda i: cs.step(i, 'device'), args.steps, 3)
@@ -516,9 +565,7 @@ def run_contract(args, rank, world, local):
             others.append({'kernel': desc, 'rocprof_name': frag, 'achieved': round(ach, 2), 'frac': round(ach / PEAK_F32_MFMA_TFLOPS, 4),
                            'launches': int(n), 'avg_us': round(ms * 1e3 / n, 2), 'flops_per_launch': fl / n})
     eng.profile_select(0)
-    res = None
     if rank == 0:
-        audio_step = world * BATCH * (N_SAMPLES / 16000.0)
         roofline = None
         if prof_n > 0 and prof_ms > 0:
             achieved = prof_flops / (prof_ms * 1e-3) / 1e12
@@ -533,32 +580,12 @@ def run_contract(args, rank, world, local):
                         'launches': int(prof_n), 'sampling': f'every {PROF_STRIDE}th launch of the timed region bracketed by HIP events',
                         'avg_us': round(prof_ms * 1e3 / prof_n, 2),
                         'flops_per_launch': prof_flops / prof_n, 'other_kernels': others}
-        per = lambda t: {'value': round(audio_step * args.steps / t, 1), 'ms_per_step': round(t * 1e3 / args.steps, 3)}
-        res = {'metric': 'audio-seconds/sec (RTF^-1), conformer_streaming_fbank b32x10s, PCM->fbank->encoder->ctc_greedy->text',
-               'value': per(dt)['value'], 'unit': 'audio-seconds/sec', 'n_gpus': world, 'steps': args.steps,
-               'warmup': args.warmup, 'ms_per_step': per(dt)['ms_per_step'], 'higher_is_better': True,
-               'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': data_tag(),
-               'config': {'workload': 'configs[1]: conformer.yml streaming fbank, batch=32 synthetic 16 kHz 10 s '
-                                      'utterances per GPU, ctc_greedy, random-init weights V=4233',
-                          'global_batch': world * BATCH, 'audio_seconds_per_step': audio_step,
-                          'parallelism': f'dp{world}', 'world_size_observed': parallel.world_info()[1],
-                          'backend': torch.distributed.get_backend() if torch.distributed.is_initialized() else 'none',
-                          'rccl_ranks_seen': ranks_seen,
-                          'ms_per_step_per_rank': {'min': round(min(per_rank_ms), 3), 'max': round(max(per_rank_ms), 3)},
-                          'algorithmic_gflop_per_step_per_gpu': GFLOP_PER_STEP,
-                          'normalisation': 'use_db_normalization = 2 (masr_transcribe_rows): mean squares on the device in numpy\'s '
-                                           'summation order, gain = the reference\'s scalar numpy expressions on this host -- the '
-                                           'int16 samples are the reference\'s bit for bit; the round trip of step k+1 runs under '
-                                           'step k and is recomputed every step',
-                          'timed_region': 'int16 PCM resident in HBM -> mean squares -> host gains -> masr_transcribe_rows (mode 2) '
-                                          '-> packed hypothesis rows -> (all-gather) -> D2H -> text on host; '
-                                          f'{n_texts} transcripts built inside it, e.g. {sample_text[:12]!r}'},
-               'value_definition': 'task contract: inputs resident in HBM when the timed region starts; SURVEY 8(d)\'s host-to-host '
-                                   'rate of the same route is value_host_to_host',
-               'value_host_to_host': per(dt_host)['value'],
-               'roofline': roofline,
-               'timing': {'device_only': dict(per(dt_dev), note='PCM in HBM -> packed hypothesis rows in HBM; the host waits only for the (earlier) mean squares'),
-                          'host_to_host': dict(per(dt_host), note='pinned host int16 PCM -> H2D (copy stream, under the previous step) -> ... -> D2H -> text on host')}}
+        res.update({'value_definition': 'task contract: inputs resident in HBM when the timed region starts; SURVEY 8(d)\'s '
+                                        'host-to-host rate of the same route is value_host_to_host',
+                    'value_host_to_host': per(dt_host)['value'],
+                    'roofline': roofline,
+                    'timing': {'device_only': dict(per(dt_dev), note='PCM in HBM -> packed hypothesis rows in HBM; the host waits only for the (earlier) mean squares'),
+                               'host_to_host': dict(per(dt_host), note='pinned host int16 PCM -> H2D (copy stream, under the previous step) -> ... -> D2H -> text on host')}})
     return eng, res
 
 
@@ -1155,8 +1182,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: roofline and per-kernel figures, the device-only and host-to-host timings, the '
+                         'secondary workloads (extra) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the hypotheses of the last timed step as DIR/<name>.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baseline')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: leave out the secondary workloads')
     ap.add_argument('--workload', default='conformer_b32',
                     help='conformer_b32 (BASELINE configs[1], the contract line, default) | efficient_b256 | stream128 | '
                          'squeezeformer_b64_beam | squeezeformer_b64_beam_nolm  (one secondary workload only, own JSON line)')
@@ -1177,6 +1209,8 @@ def main():
 
     line = None
     if args.workload != 'conformer_b32':
+        if args.dump_outputs:
+            raise SystemExit('bench.py: --dump-outputs writes the outputs of the contract workload (conformer_b32)')
         fn = {'efficient_b256': extra_efficient_b256, 'stream128': extra_stream128, 'bf16x3': extra_bf16x3,
               'conformer_b32_two_lanes': extra_contract_two_lanes,
               'squeezeformer_b64_beam': extra_squeezeformer_beam,
@@ -1192,7 +1226,7 @@ def main():
         eng, res = run_contract(args, rank, world, local)
         eng.close()
         extra = None
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             partial = {}
             dog = ExtrasWatchdog(rank, res, partial)
             extra = run_extras(args, rank, world, local, partial)
@@ -1205,7 +1239,7 @@ def main():
                     # the same step with consecutive steps side by side on the engine's two lanes: beside `value`, never instead of it
                     # (`value` / `roofline` are measured on ONE lane: a kernel bracketed by HIP events must have the CUs to itself)
                     res['value_two_lanes'] = two['value']
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 try:
                     res['cpu_baseline'] = cpu_baseline()
                 except Exception as exc:                                # noqa: BLE001  (the measured line must still print)

@@ -18,7 +18,10 @@ Fixtures (all inputs are either stored or re-derivable from seeds):
 * ``predictor.npz``    reference MASRPredictor(use_gpu=False) on TorchScript export of the
                        synthetic model: predict(test.wav) and every predict_stream partial.
 * ``greedy.npz``       reference greedy_decoder / greedy_decoder_chunk outputs on seeded probs.
+* ``normalize.npz``    reference AudioSegment.normalize on 200 seeded utterances (``normalize_cases``): the mean square it
+                       starts from and a SHA-256 digest of the samples it leaves (``python -m oracle.make_golden --only-normalize``).
 """
+import hashlib
 import json
 import os
 import tempfile
@@ -278,10 +281,40 @@ def features_fixture(tmp):
     np.savez_compressed(os.path.join(OUT, 'features.npz'), **out)
 
 
+def normalize_cases():
+    """(utterance, target_db) pairs of the normalize fixture: 200 seeded float32 utterances of 400 - 40000 samples over four
+    decades of level, integer and fractional targets"""
+    rng = np.random.default_rng(11)
+    for k in range(200):
+        n = int(rng.integers(400, 40000))
+        x = (rng.normal(0, 10 ** rng.uniform(-4, -0.3), n)).astype(np.float32)
+        yield x, (int(rng.integers(-30, -9)) if k % 2 else float(rng.uniform(-30, -10)))
+
+
+def samples_digest(a):
+    """SHA-256 of an array's dtype and bytes: equal digests = the same samples bit for bit"""
+    return hashlib.sha256(a.dtype.str.encode() + np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def normalize_fixture():
+    """reference AudioSegment.normalize (audio.py:287-304) on ``normalize_cases``"""
+    from masr.data_utils.audio import AudioSegment
+    ms, digest = [], []
+    for x, target in normalize_cases():
+        seg = AudioSegment.from_ndarray(x.copy(), 16000)
+        ms.append(np.mean(seg.samples ** 2))
+        seg.normalize(target_db=target)
+        digest.append(samples_digest(seg.samples))
+    np.savez_compressed(os.path.join(OUT, 'normalize.npz'), mean_square=np.array(ms, np.float32), digest=np.array(digest))
+
+
 def main():
     import sys
     shims.install()
     os.makedirs(OUT, exist_ok=True)
+    if '--only-normalize' in sys.argv:
+        normalize_fixture()
+        return
     tmp = tempfile.mkdtemp()
     torch.set_grad_enabled(False)
     if '--only-efficient' in sys.argv:
@@ -446,6 +479,7 @@ def main():
         ct.append(tx)
     np.savez_compressed(os.path.join(OUT, 'greedy.npz'), probs=p, score=np.array(s, np.float64), text=np.array(t),
                         chunk_scores=np.array(cs, np.float64), chunk_texts=np.array(ct))
+    normalize_fixture()
     print('golden fixtures written to', OUT)
     for f in sorted(os.listdir(OUT)):
         print(' ', f, os.path.getsize(os.path.join(OUT, f)))

@@ -257,15 +257,19 @@ def test_bench_contract_step_world2():
     assert n0 == 3 * 64 and n1 == 3 * 32 and dt0 == dt1      # max-over-ranks time is the same number everywhere
 
 
-def test_bench_cli_launches_ranks_and_rejects_mismatch():
-    """--gpus 2 outside a launcher starts 2 ranks itself (the CLI the driver calls); a WORLD_SIZE that disagrees is an error"""
+def test_bench_cli_launches_ranks_and_rejects_mismatch(tmp_path):
+    """--gpus 2 outside a launcher starts 2 ranks itself (the CLI the driver calls); a WORLD_SIZE that disagrees is an error;
+    a plain run prints the headline alone and --dump-outputs writes the last timed step's hypotheses"""
     import json
     import subprocess
     import sys
-    env = dict(os.environ, MASR_BENCH_ENGINE_FACTORY='tests.fake_engine:make', PYTHONPATH=ROOT)
+    # the stand-in ranks are host processes on gloo: a GPU of the machine stays hidden from them (invalid index = no device)
+    env = dict(os.environ, MASR_BENCH_ENGINE_FACTORY='tests.fake_engine:make', PYTHONPATH=ROOT, HIP_VISIBLE_DEVICES='-1',
+               CUDA_VISIBLE_DEVICES='-1')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-extra', '--no-cpu-baseline']
+    plain = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1']
+    cmd = plain + ['--full', '--no-extra', '--no-cpu-baseline']
     p = subprocess.run(cmd + ['--gpus', '2'], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
@@ -278,9 +282,14 @@ def test_bench_cli_launches_ranks_and_rejects_mismatch():
     assert r['config']['rccl_ranks_seen'] == [0, 1]
     assert 0 < r['config']['ms_per_step_per_rank']['min'] <= r['config']['ms_per_step_per_rank']['max'] <= r['ms_per_step'] * 1.001
     assert 'use_db_normalization = 2' in r['config']['normalisation'] and 'mode 2' in r['config']['timed_region']
-    p1 = subprocess.run(cmd + ['--gpus', '1'], env=env, capture_output=True, text=True, timeout=600)
+    p1 = subprocess.run(plain + ['--gpus', '1', '--dump-outputs', str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
     r1 = json.loads([ln for ln in p1.stdout.splitlines() if ln.startswith('{')][0])
     assert r1['n_gpus'] == 1 and r1['config']['global_batch'] == 32
+    assert r1['steps'] == 2 and r1['ms_per_step'] > 0 and not {'timing', 'roofline', 'extra', 'cpu_baseline'} & set(r1)
+    import numpy as np
+    tok, nt, sc = (np.load(os.path.join(tmp_path, f'{n}.npy')) for n in ('tokens', 'token_counts', 'scores'))
+    assert tok.dtype == nt.dtype == sc.dtype == np.float32 and tok.shape[0] == nt.shape[0] == sc.shape[0] == 32
+    assert all((tok[i, :int(nt[i])] >= 0).all() and (tok[i, int(nt[i]):] == -1).all() for i in range(32))
     bad = subprocess.run(cmd + ['--gpus', '2'], env=dict(env, WORLD_SIZE='4', RANK='0'), capture_output=True, text=True, timeout=120)
     assert bad.returncode != 0 and 'WORLD_SIZE=4' in (bad.stderr + bad.stdout)
     # configs[3] as its own workload on 2 ranks: 256 utterances sharded 128 / 128, gathered, 256 transcripts on rank 0

@@ -6,10 +6,10 @@
 D=${1:-gpurun_out/measure}; mkdir -p $D
 R=$PWD
 python -m pytest tests -m gpu -q 2>&1 | tail -40 > $D/gputests_tail.txt; grep -E "passed|failed|error" $D/gputests_tail.txt | tail -3 > $D/gputests.txt; cat $D/gputests.txt
-python bench.py > $D/bench.json 2> $D/bench.err; tail -1 $D/bench.err
+python bench.py --full > $D/bench.json 2> $D/bench.err; tail -1 $D/bench.err
 export TMPDIR=/tmp
-B="python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra"
-B2="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra"
+B="python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra"
+B2="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra"
 MF="SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $R/$D/kt -o r2 -- $B > $R/$D/kt.log 2>&1
@@ -51,7 +51,7 @@ python tools/stream_host_profile.py 128 3 2>&1 | grep -E "streams:|masr_pool_ste
 python tools/stream_host_profile.py 16 3 2>&1 | grep -E "streams:|masr_pool_step" >> $D/pool_host.txt
 python tools/facade_profile.py 2>&1 | grep -v amdgpu > $D/facade_profile.txt
 python tools/b1_ab.py 2>&1 | grep -v amdgpu > $D/b1_ab.txt
-MASR_FORCE_DIST=1 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra > $D/rccl_single_rank.json 2> $D/rccl_single_rank.err
+MASR_FORCE_DIST=1 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra > $D/rccl_single_rank.json 2> $D/rccl_single_rank.err
 python profiles/summarize_rocpd.py $(find $D/ktg -name "*.db") > $D/squeezeformer_greedy_kernel_stats.txt
 python profiles/summarize_rocpd.py $(find $D/ktd -name "*.db") > $D/deepspeech2_kernel_stats.txt
 python profiles/summarize_mfma.py $(find $D/pmg -name "*.db") $D/squeezeformer_greedy_mfma_util.json > $D/squeezeformer_greedy_mfma.txt 2>&1
