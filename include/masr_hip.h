@@ -384,6 +384,7 @@ int masr_select_lane(masr_engine* e, int32_t lane);
  *  24  1 = the full FFN launches run two accumulator chains per wave (ffn_dual.hip) instead of one (ffn_pc.hip; bit-identical)
  *  25  0 = the offline out-proj + pw1 chain kernel and the CTC head stream their weights through LDS slabs instead of reading
  *      packed copies with buffer loads (bit-identical)
+ *  39  0 = the full packed FFN launches run the 32-row kernel instead of the 16-row one (two workgroups per CU; bit-identical)
  *  20  1 = EXPLORATORY split-bf16 precision mode (not the reference's fp32 arithmetic, never the contract path): conv2, the embed
  *      projection and the other launches of the generic GEMM in the offline forward as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on
  *      the bf16 matrix pipe, fp32 accumulation (csrc/gemm_bf16x3.hip); 3 = also the FFN, unfused (slower than the fused fp32 FFN) */
@@ -394,6 +395,12 @@ int masr_debug_set(masr_engine* e, int32_t key, int32_t value);
  * masr_profile_read synchronises the events and returns total ms / launch count / flops since reset. */
 int masr_profile_select(masr_engine* e, int32_t kind);
 int masr_profile_read(masr_engine* e, double* total_ms, int64_t* launches, double* flops, int32_t reset);
+
+/* Summation-order probe (no engine): c32_dev, c16_dev [16][16] = a_dev [16][k] . b_dev [16][k]^T as a chain of 32x32x2 MFMAs in the
+ * fused FFN kernels' k order and as a chain of 16x16x4 MFMAs whose lanes take, in group g of 8 k, the k values 8g + perm[0..3]
+ * (first MFMA, lane groups 0..3) and 8g + perm[4..7] (second MFMA).  k a multiple of 8. */
+int masr_mfma_order_probe(const float* a_dev, const float* b_dev, float* c32_dev, float* c16_dev, int32_t k, const int32_t* perm,
+                          void* stream);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,7 @@ SIGNATURES = {
     'masr_select_lane': [_P, _I],
     'masr_stage_rows': [_P, C.c_int64, _P, _P, _I, _I, _I],
     'masr_debug_set': [_P, _I, _I],
+    'masr_mfma_order_probe': [_P, _P, _P, _P, _I, _P, _P],
     'masr_profile_select': [_P, _I],
     'masr_profile_read': [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), _I],
 }

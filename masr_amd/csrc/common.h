@@ -264,6 +264,11 @@ int launch_ffn_fused(float* x, const float* lnw, const float* lnb, const float* 
                      const FfnHead* head = nullptr, bool packed = false);
 void launch_pack_ffn_pc(const float* w1, const float* w2, float* p1, float* p2, int dff, hipStream_t s);
 void launch_pack_rows_pc(const float* w, float* p, int N, hipStream_t s, int n_src = -1);   // weights [n_src, 256] -> N % 256 == 0 packed rows (rows >= n_src zero)
+// 16-row fused FFN stages (ffn_pc.hip ffn16_kernel, two workgroups per CU): full-d_ff launches only, packed weights of its own order
+int launch_ffn16(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2, const float* b2, int M,
+                 int dff, float eps, float scale, hipStream_t s, const FfnTail* tail, const FfnHead* head);
+void launch_pack_ffn16(const float* w1, const float* w2, float* p1, float* p2, int dff, hipStream_t s);
+void launch_pack_rows16(const float* w, float* p, int N, hipStream_t s, int n_src = -1);
 // sqz_layer.hip: one Squeezeformer (post-LN) half-layer per launch on the workgroup's own 32 rows --
 //   stage 0 "mid": x <- LN_a(x + att . head_w^T + head_b);  x <- LN_b(x + FFN(ffn_s * x + ffn_b));
 //                  glu_out <- GLU(pw1(mask(tail_s * x + tail_sb)))        (tail_n = 512, padded layout of the depthwise conv)

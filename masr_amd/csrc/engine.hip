@@ -307,6 +307,7 @@ struct masr_engine : EngineWs {
     std::map<const float*, std::pair<DevBuf, DevBuf>> ffn_packed;  // fp32 FFN weights in fragment order (ffn_pc.hip VAR == 2), per W1 pointer
     std::map<const float*, std::pair<DevBuf, DevBuf>> ffn_dual_packed;  // the same in the two-chain order of ffn_dual.hip (and its QKV tail weights)
     std::map<const float*, std::pair<DevBuf, DevBuf>> x3_packed;   // exploratory split-bf16 FFN: packed weights per FFN (W1 pointer)
+    std::map<const float*, std::pair<DevBuf, DevBuf>> ffn16_packed;  // the same in the 16-row kernel's order (ffn_pc.hip ffn16_kernel), per W1 / tail / head pointer
     long long* beam_prof = nullptr;                                             // debug: phase cycle counters (masr_debug_set key 2)                                               // GPU beam search scratch                               // DeepSpeech2 workspaces
     float *preln_w = nullptr, *preln_b = nullptr, *tr_dw_w = nullptr, *tr_dw_b = nullptr, *tr_pw_w = nullptr,
           *tr_pw_b = nullptr, *rec_w = nullptr, *rec_b = nullptr;
@@ -394,7 +395,9 @@ struct CallGuard {
     masr_engine* e;
     hipStream_t s;
     size_t n0;
-    static size_t packed_count(const masr_engine* e) { return e->ffn_packed.size() + e->ffn_dual_packed.size() + e->x3_packed.size(); }
+    static size_t packed_count(const masr_engine* e) {
+        return e->ffn_packed.size() + e->ffn_dual_packed.size() + e->x3_packed.size() + e->ffn16_packed.size();
+    }
     CallGuard(masr_engine* e_, hipStream_t s_) : e(e_), s(s_), n0(packed_count(e_)) {
         if (!e->pack_pending) return;
         if (hipEventQuery(e->pack_ev) == hipSuccess) {
@@ -417,6 +420,7 @@ struct CallGuard {
 
 static int g_ffn_dual = 0;         // masr_debug_set key 24: 0 = the full FFN launches run ffn_pc.hip (one accumulator chain per wave) instead of ffn_dual.hip (A/B)
 static int g_ffn_packed = 2;       // masr_debug_set key 23: 0 = the full FFN launches stream their weights through the wave-private LDS slabs (A/B)
+static int g_ffn16 = 1;            // masr_debug_set key 39: 0 = the full packed FFN launches run the 32-row kernel instead of the 16-row one (A/B)
 // masr_debug_set key 20 -- EXPLORATORY precision mode, never the contract path: the big offline GEMMs (conv2, embed projection,
 // the two FFN GEMMs, unfused) run as split-bf16 products on the bf16 matrix pipe (gemm_bf16x3.hip)
 static int g_bf16x3 = 0;
@@ -732,6 +736,10 @@ void masr_destroy(masr_engine* e) {
         kv.second.first.release();
         kv.second.second.release();
     }
+    for (auto& kv : e->ffn16_packed) {
+        kv.second.first.release();
+        kv.second.second.release();
+    }
     for (auto& ev : e->prof_events) {
         (void)hipEventDestroy(ev.first);
         (void)hipEventDestroy(ev.second);
@@ -739,15 +747,15 @@ void masr_destroy(masr_engine* e) {
     delete e;
 }
 
-// The fragment-ordered weight copies (ffn_packed / ffn_dual_packed / x3_packed) are built on first use and keyed by the device
+// The fragment-ordered weight copies (ffn_packed / ffn_dual_packed / x3_packed / ffn16_packed) are built on first use and keyed by the device
 // pointer of the weights they were packed from.  A reload (masr_load_tensor on a finalized engine, then masr_finalize) re-uploads
 // into the SAME device buffers when the sizes are unchanged, so the keys would still match while the copies hold the old
 // values: every reload drops them (after the device has drained: launches in flight may still read them).
 static void drop_packed_weights(masr_engine* e) {
-    if (e->ffn_packed.empty() && e->ffn_dual_packed.empty() && e->x3_packed.empty()) return;
+    if (e->ffn_packed.empty() && e->ffn_dual_packed.empty() && e->x3_packed.empty() && e->ffn16_packed.empty()) return;
     (void)hipSetDevice(e->cfg.device_id);
     (void)hipDeviceSynchronize();
-    for (auto* m : {&e->ffn_packed, &e->ffn_dual_packed, &e->x3_packed}) {
+    for (auto* m : {&e->ffn_packed, &e->ffn_dual_packed, &e->x3_packed, &e->ffn16_packed}) {
         for (auto& kv : *m) {
             kv.second.first.release();
             kv.second.second.release();
@@ -1048,7 +1056,11 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
     // full launches stream PACKED weight copies straight into registers (ffn_pc.hip VAR == 2; built on first use, + 4 MB per FFN)
     const float *kw1 = w1, *kw2 = w2;
     const bool packed = g_ffn_packed && (nsplit == 1 || g_ffn_packed >= 2) && d == 256;      // (key 23 = 2: the d_ff-split launches of small M too)
-    if (packed) {
+    // 16-row blocks, two workgroups per CU (ffn_pc.hip ffn16_kernel): every full-d_ff launch of packed weights it covers; it reads
+    // copies of its own order, so the 32-row copies are not built for it
+    const bool use16 = packed && nsplit == 1 && g_ffn16 && !affine && dff % 128 == 0 && !(want_tail && tail->N % 256) &&
+                       !(want_head && head->ktaps != 15 && head->ktaps != 7);
+    if (packed && !use16) {
         auto it = e->ffn_packed.find(w1);
         if (it == e->ffn_packed.end()) {
             std::pair<DevBuf, DevBuf> pk;
@@ -1102,6 +1114,42 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
         const int done = launch_ffn_dual(e->x.as<float>(), lnw, lnb, it->second.first.as<float>(), b1, it->second.second.as<float>(),
                                          b2, M, dff, 1e-5f, scale, affine, s, want_tail ? &ptail : nullptr, want_head ? &phead : nullptr);
         if (done < 0) return fail("ffn(): the two-chain FFN kernel rejected the launch");
+        if (want_head && done != 4) return fail("ffn(): head stage was not launched");
+        if (tail_done) *tail_done = done == 2;
+        if (post_y) launch_layernorm(e->x.as<float>(), post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
+        return 0;
+    }
+    if (use16) {
+        auto p16 = [&](const float* W, int N, const float** out) -> int {
+            auto it = e->ffn16_packed.find(W);
+            if (it == e->ffn16_packed.end()) {
+                std::pair<DevBuf, DevBuf> pk;
+                CHK(pk.first.ensure((size_t)N * d * sizeof(float)));
+                launch_pack_rows16(W, pk.first.as<float>(), N, s);
+                it = e->ffn16_packed.emplace(W, pk).first;
+            }
+            *out = it->second.first.as<float>();
+            return 0;
+        };
+        auto it = e->ffn16_packed.find(w1);
+        if (it == e->ffn16_packed.end()) {
+            std::pair<DevBuf, DevBuf> pk;
+            CHK(pk.first.ensure((size_t)dff * d * sizeof(float)));
+            CHK(pk.second.ensure((size_t)dff * d * sizeof(float)));
+            launch_pack_ffn16(w1, w2, pk.first.as<float>(), pk.second.as<float>(), dff, s);
+            it = e->ffn16_packed.emplace(w1, pk).first;
+        }
+        if (want_tail) {
+            ptail = *tail;
+            CHK(p16(tail->W, tail->N, &ptail.W));
+        }
+        if (want_head) {
+            phead = *head;
+            CHK(p16(head->W, d, &phead.W));
+        }
+        const int done = launch_ffn16(e->x.as<float>(), lnw, lnb, it->second.first.as<float>(), b1, it->second.second.as<float>(), b2, M,
+                                      dff, 1e-5f, scale, s, want_tail ? &ptail : nullptr, want_head ? &phead : nullptr);
+        if (done < 0) return fail("ffn(): the 16-row FFN kernel rejected the launch");
         if (want_head && done != 4) return fail("ffn(): head stage was not launched");
         if (tail_done) *tail_done = done == 2;
         if (post_y) launch_layernorm(e->x.as<float>(), post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
@@ -3051,6 +3099,7 @@ int masr_debug_set(masr_engine* e, int32_t key, int32_t value) {
     else if (key == 36) g_sqz_fused_blocks = value;
     else if (key == 37) g_beam_narrow = value;
     else if (key == 38) e->skip_padding = value;
+    else if (key == 39) g_ffn16 = value;
     else if (key == 17) set_gemm_waves(value);
     else if (key == 18) set_conv1_nt(value);
     else if (key == 16) { e->prof_stride = value > 1 ? value : 1; e->prof_seen = 0; }

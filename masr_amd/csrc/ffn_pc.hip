@@ -608,6 +608,486 @@ __global__ __launch_bounds__(512) void ffn_pc_kernel(float* x, const float* __re
 }
 
 
+// ======================================================================================================================
+// 16-row variant (ffn16_kernel): the same stages on 16-row blocks with v_mfma_f32_16x16x4_f32, sized so that TWO workgroups share
+// a CU (<= 128 VGPRs at 8 waves, 33.5 KB of LDS, no wave-private slabs).  At M = 7 936 the 32-row kernel has one workgroup per CU
+// (248 on 256 CUs) and the matrix pipes idle through every phase that is not the d_ff main loop (conv-module head, LayerNorm
+// prologue, pipeline fill and drain, residual epilogue, tail LayerNorm, stores); with 496 16-row blocks resident in one round, one
+// block's phases run under the other block's MFMAs.  Bit-identical to the 32-row kernel: every dot product is the same fmaf chain --
+// in 8-wide k group g the 32x32x2 chain adds (8g, 8g+4), (8g+1, 8g+5), (8g+2, 8g+6), (8g+3, 8g+7); a 16x16x4 MFMA adds four k in
+// lane-group order, so lane group kk takes k = 8g + p16_k0(kk) in the group's first MFMA and that + 2 in its second
+// (tests/test_gpu_mfma_order.py checks the equivalence on the device).  Weight fragments (1 KB per wave, four MFMAs) come from packed
+// copies in consumption order (launch_pack_ffn16 / launch_pack_rows16) through raw buffer loads into a ring of P16_RING fragments:
+// tools/studies/mfma16_study.hip measured a 16x16x4 stream at 4 waves / SIMD with 1 KB per four MFMAs at 138-139 TF with a ring of 8
+// (130-133 TF with 4; the 32x32x2 stream of the 32-row kernel: 136-141 TF).
+//   producer p (0..3): h[16 rows, 32 units] (two 16-column tiles), fragment f = k group f: (tile 0, 1) x (first, second MFMA)
+//   consumer c (0..3): acc2[16 rows, 64 cols] (four tiles), fragment f = k group f >> 1, MFMA f & 1, one MFMA per tile
+//   head (HEADK) / tail (TAIL): all 8 waves, 32 output columns each, in the producer's fragment order
+static constexpr int P16_BM = 16;
+static constexpr int P16_RING = 8;
+__host__ __device__ constexpr int p16_k0(int kk) { return (kk & 1) * 4 + (kk >> 1); }
+
+template <int TAIL, int HEADK>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void ffn16_kernel(
+    float* x, const float* __restrict__ lnw, const float* __restrict__ lnb, const float* __restrict__ w1, const float* __restrict__ b1,
+    const float* __restrict__ w2, const float* __restrict__ b2, int M, int dff, float eps, float scale, FfnTail tail, FfnHead head) {
+    extern __shared__ __align__(16) float sm[];
+    float* xn = sm;                              // [16][260]   LayerNorm(x) tile (A operand of GEMM1, the head and the tail)
+    float* hs = xn + P16_BM * PC_XLD;            // [2][16][132] hidden tile (A operand of GEMM2), double-buffered
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int role = wave >> 2, idx = wave & 3;
+    const int row0 = blockIdx.x * P16_BM;
+    const int fr = lane & 15, kk = lane >> 4, ko = p16_k0(kk);
+    const unsigned lane16 = lane * 16;
+    f32x4 pre[P16_RING];
+    const float* xa = xn + fr * PC_XLD + ko;     // A values of lane (fr, kk): xa[8g], xa[8g + 2]
+
+    f32x4 gw_head = {0.f, 0.f, 0.f, 0.f}, gb_head = gw_head;
+    if (HEADK > 0) {
+        // ---- head 1: depthwise conv of my 16 rows -> xn tile (thread = (channel c, 8-row half); the window is reloaded where a
+        // new sequence starts inside the block and on padded rows, exactly as in the 32-row kernel)
+        {
+            constexpr int KT = HEADK > 0 ? HEADK : 1, pad = KT - 1;
+            const int c = tid & 255, half = tid >> 8;
+            float w[KT], win[KT], nw[8];
+#pragma unroll
+            for (int j = 0; j < KT; ++j) w[j] = head.dw_w[j * 256 + c];
+            const float bv = head.dw_b[c];
+            const float gc = head.gconst ? head.gconst[c] : 0.f;
+            const bool has_gc = head.gconst != nullptr;
+            const int hb0 = row0 / head.seq_t, ht0 = row0 - hb0 * head.seq_t, lr_last = M - 1 - row0;
+#pragma unroll
+            for (int rr = 0; rr < 8; ++rr) {
+                const SeqRow q = seq_row(hb0, ht0, head.seq_t, min(half * 8 + rr, lr_last));
+                nw[rr] = head.glu[((size_t)q.b * (pad + head.seq_t) + q.t + pad) * 256 + c];
+            }
+#pragma unroll
+            for (int j = 0; j < KT; ++j) win[j] = 0.f;
+#pragma unroll
+            for (int rr = 0; rr < 8; ++rr) {
+                const int lr = half * 8 + rr;
+                const SeqRow q = seq_row(hb0, ht0, head.seq_t, min(lr, lr_last));
+                const int b = q.b, t = q.t;
+                if (rr == 0 || t == 0 || row0 + lr >= M) {
+                    const float* gin = head.glu + ((size_t)b * (pad + head.seq_t) + t) * 256 + c;
+#pragma unroll
+                    for (int j = 0; j < pad; ++j) win[j + 1] = (has_gc && t + j < pad) ? gc : gin[(size_t)j * 256];
+                }
+#pragma unroll
+                for (int j = 0; j < pad; ++j) win[j] = win[j + 1];
+                win[pad] = nw[rr];
+                float acc = bv;
+#pragma unroll
+                for (int j = 0; j < KT; ++j) acc = fmaf(w[j], win[j], acc);
+                xn[lr * PC_XLD + c] = acc;
+            }
+        }
+        // ---- head 2: LayerNorm + SiLU per row (wave w: rows 2w, 2w+1), in place
+        {
+            const f32x4 ww = *reinterpret_cast<const f32x4*>(head.lnw + lane * 4);
+            const f32x4 bb = *reinterpret_cast<const f32x4*>(head.lnb + lane * 4);
+            __syncthreads();
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr) {
+                const int lr = wave * 2 + rr;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(&xn[lr * PC_XLD + lane * 4]);
+                const float mean = pc_wsum(v[0] + v[1] + v[2] + v[3]) * (1.0f / 256.0f);
+                const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
+                const float var = pc_wsum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.0f / 256.0f);
+                const float rstd = 1.0f / sqrtf(var + eps);
+                f32x4 o;
+                o[0] = d0 * rstd * ww[0] + bb[0];
+                o[1] = d1 * rstd * ww[1] + bb[1];
+                o[2] = d2 * rstd * ww[2] + bb[2];
+                o[3] = d3 * rstd * ww[3] + bb[3];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] = o[i] / (1.0f + expf(-o[i]));
+                *reinterpret_cast<f32x4*>(&xn[lr * PC_XLD + lane * 4]) = o;
+            }
+        }
+        // ---- head 3: pointwise_conv2 on all 8 waves (wave w: output channels 32w .. 32w+31), + bias, pad mask, residual -> x and,
+        // raw, back into the xn tile.  head.W: launch_pack_rows16 copy
+        const __amdgpu_buffer_rsrc_t hrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(head.W), 0, PC_D * PC_D * 4, 0x00020000);
+        auto hld = [&](int f) -> f32x4 { return pc_bufld(hrs, lane16, (unsigned)(wave * 32 + f) * 256u); };
+#pragma unroll
+        for (int k = 0; k < P16_RING; ++k) pre[k] = hld(k);
+        __syncthreads();                                  // A tile complete
+        {
+            float bv[2], res[8];
+            unsigned padded = 0;                          // bit 4 nt + r: element (tile nt, row 4 kk + r) is a padded frame
+            const int mb0 = row0 / head.seq_t, mt0 = row0 - mb0 * head.seq_t;
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                const int col = wave * 32 + 16 * nt + fr;
+                bv[nt] = head.bias[col];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int lrc = min(4 * kk + r, M - 1 - row0);
+                    res[4 * nt + r] = x[(size_t)(row0 + lrc) * PC_D + col];
+                    if (head.lens) {
+                        const SeqRow q = seq_row(mb0, mt0, head.seq_t, lrc);
+                        if (head.mstride * q.t >= head.lens[q.b]) padded |= 1u << (4 * nt + r);
+                    }
+                }
+            }
+            gw_head = *reinterpret_cast<const f32x4*>(lnw + lane * 4);
+            gb_head = *reinterpret_cast<const f32x4*>(lnb + lane * 4);
+            f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            float a0 = xa[0], a1 = xa[2];
+#pragma unroll
+            for (int g = 0; g < 32; ++g) {
+                float n0 = 0.f, n1 = 0.f;
+                if (g + 1 < 32) { n0 = xa[8 * (g + 1)]; n1 = xa[8 * (g + 1) + 2]; }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    acc[q & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(q < 2 ? a0 : a1, pre[g % P16_RING][q], acc[q & 1], 0, 0, 0);
+                    if (q == 3 && g + P16_RING < 32) pre[g % P16_RING] = hld(g + P16_RING);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                a0 = n0;
+                a1 = n1;
+            }
+            __syncthreads();                              // every wave has read its A values: the tile may be overwritten
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                const int col = wave * 32 + 16 * nt + fr;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int lr = 4 * kk + r;
+                    float v = acc[nt][r] + bv[nt];
+                    if (padded & (1u << (4 * nt + r))) v = 0.f;
+                    v = res[4 * nt + r] + v;
+                    if (row0 + lr < M) x[(size_t)(row0 + lr) * PC_D + col] = v;
+                    xn[lr * PC_XLD + col] = v;
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- LayerNorm prologue: wave w normalises rows 2w, 2w+1 ----------------------------------------
+    {
+        const f32x4 gw = HEADK > 0 ? gw_head : *reinterpret_cast<const f32x4*>(lnw + lane * 4);
+        const f32x4 gb = HEADK > 0 ? gb_head : *reinterpret_cast<const f32x4*>(lnb + lane * 4);
+        f32x4 v4[2];
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int row = min(row0 + wave * 2 + rr, M - 1);
+            v4[rr] = HEADK > 0 ? *reinterpret_cast<const f32x4*>(&xn[(wave * 2 + rr) * PC_XLD + lane * 4])
+                               : *reinterpret_cast<const f32x4*>(x + (size_t)row * PC_D + lane * 4);
+        }
+        if (TAIL && tail.pre_lnw) {
+            const f32x4 pw = *reinterpret_cast<const f32x4*>(tail.pre_lnw + lane * 4);
+            const f32x4 pb = *reinterpret_cast<const f32x4*>(tail.pre_lnb + lane * 4);
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr) {
+                const f32x4 v = v4[rr];
+                const float mean = pc_wsum(v[0] + v[1] + v[2] + v[3]) * (1.0f / 256.0f);
+                const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
+                const float var = pc_wsum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.0f / 256.0f);
+                const float rstd = 1.0f / sqrtf(var + eps);
+                f32x4 o;
+                o[0] = d0 * rstd * pw[0] + pb[0];
+                o[1] = d1 * rstd * pw[1] + pb[1];
+                o[2] = d2 * rstd * pw[2] + pb[2];
+                o[3] = d3 * rstd * pw[3] + pb[3];
+                v4[rr] = o;
+                const int row = row0 + wave * 2 + rr;
+                if (row < M) *reinterpret_cast<f32x4*>(x + (size_t)row * PC_D + lane * 4) = o;
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int lr = wave * 2 + rr;
+            const f32x4 v = v4[rr];
+            const float mean = pc_wsum(v[0] + v[1] + v[2] + v[3]) * (1.0f / 256.0f);
+            const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
+            const float var = pc_wsum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.0f / 256.0f);
+            const float rstd = 1.0f / sqrtf(var + eps);
+            f32x4 o;
+            o[0] = d0 * rstd * gw[0] + gb[0];
+            o[1] = d1 * rstd * gw[1] + gb[1];
+            o[2] = d2 * rstd * gw[2] + gb[2];
+            o[3] = d3 * rstd * gw[3] + gb[3];
+            if (row0 + lr >= M) o = f32x4{0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(&xn[lr * PC_XLD + lane * 4]) = o;
+        }
+    }
+
+    // ---- main loops: w1 / w2 are launch_pack_ffn16 copies [chunk][wave idx][fragment f][lane][4] ------------------------------
+    const int nchunk = dff / PC_CH, nlast = nchunk - 1;
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(role == 0 ? w1 : w2), 0, dff * PC_D * 4, 0x00020000);
+    auto pld = [&](int chunk, int f) -> f32x4 { return pc_bufld(wrs, lane16, (unsigned)((chunk * 4 + idx) * 32 + f) * 256u); };
+#pragma unroll
+    for (int k = 0; k < P16_RING; ++k) pre[k] = pld(0, k);
+    __syncthreads();                                 // xn tile complete
+
+    // phase p (one workgroup barrier each): producers chunk p (p < nchunk) with the bias + SiLU of chunk p - 1 in between;
+    // consumers chunk p - 2
+    if (role == 0) {
+        f32x4 accp[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};    // raw sums of the previous chunk
+        float bvp[2] = {0.f, 0.f};
+        f32x4 resx[4];
+        for (int phase = 0; phase <= nchunk + 1; ++phase) {
+            float* hprev = hs + ((phase + 1) & 1) * P16_BM * PC_HLD + idx * 32 + fr;     // buffer (phase-1) & 1
+            auto finish = [&](int e) {     // element e = 4 nt + r: row 4 kk + r, unit 16 nt + fr
+                const int nt = e >> 2, r = e & 3;
+                const float v = accp[nt][r] + bvp[nt];
+                hprev[(4 * kk + r) * PC_HLD + 16 * nt] = v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+            };
+            if (phase < nchunk) {
+                const int chunk = phase;
+                const float bv0 = b1[chunk * PC_CH + idx * 32 + fr], bv1 = b1[chunk * PC_CH + idx * 32 + 16 + fr];
+                f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+                float a0 = xa[0], a1 = xa[2];
+#pragma unroll
+                for (int g = 0; g < 32; ++g) {
+                    float n0 = 0.f, n1 = 0.f;
+                    if (g + 1 < 32) { n0 = xa[8 * (g + 1)]; n1 = xa[8 * (g + 1) + 2]; }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        acc[q & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(q < 2 ? a0 : a1, pre[g % P16_RING][q], acc[q & 1], 0, 0, 0);
+                        if (q == 3) pre[g % P16_RING] = pld(min(chunk + (g + P16_RING) / 32, nlast), (g + P16_RING) & 31);
+                        if (phase > 0 && q == 1 && (g & 3) == 1) finish(g >> 2);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    a0 = n0;
+                    a1 = n1;
+                }
+                accp[0] = acc[0];
+                accp[1] = acc[1];
+                bvp[0] = bv0;
+                bvp[1] = bv1;
+            } else if (phase == nchunk) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) finish(e);
+                // drain: the producers bring the raw residual rows (row 4 idx + i) back into the LayerNorm tile, read by the epilogue
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int row = min(row0 + idx * 4 + i, M - 1);
+                    resx[i] = *reinterpret_cast<const f32x4*>(x + (size_t)row * PC_D + lane * 4);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(&xn[(idx * 4 + i) * PC_XLD + lane * 4]) = resx[i];
+            }
+            __syncthreads();
+        }
+    } else {
+        f32x4 acc2[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc2[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+        float bv2n[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) bv2n[n] = b2[idx * 64 + 16 * n + fr];
+        for (int phase = 0; phase <= nchunk + 1; ++phase) {
+            if (phase >= 2) {
+                const int chunk = phase - 2;
+                const float* ha = hs + (phase & 1) * P16_BM * PC_HLD + fr * PC_HLD + ko;       // buffer (phase-2) & 1
+                float a = ha[0];
+#pragma unroll
+                for (int f = 0; f < 32; ++f) {
+                    const float an = f + 1 < 32 ? ha[8 * ((f + 1) >> 1) + 2 * ((f + 1) & 1)] : 0.f;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        acc2[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, pre[f % P16_RING][q], acc2[q], 0, 0, 0);
+                        if (q == 3) pre[f % P16_RING] = pld(min(chunk + (f + P16_RING) / 32, nlast), (f + P16_RING) & 31);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    a = an;
+                }
+            }
+            __syncthreads();
+        }
+        // ---- epilogue (consumers): x <- x + scale * (acc2 + b2) ---------------------------------------------------
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const int col = idx * 64 + 16 * n + fr;
+            const float bv2 = bv2n[n];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int lr = 4 * kk + r;
+                const float v = xn[lr * PC_XLD + col] + scale * (acc2[n][r] + bv2);
+                if (row0 + lr < M) x[(size_t)(row0 + lr) * PC_D + col] = v;
+                if (TAIL) xn[lr * PC_XLD + col] = v;
+            }
+        }
+    }
+    if (!TAIL) return;
+
+    // ---- tail stage: out[16 rows, tail.N] = LayerNorm_tail(x_new) . Wt^T + bt, all 8 waves (tail.W: launch_pack_rows16 copy) ----
+    {
+        const f32x4 gw = *reinterpret_cast<const f32x4*>(tail.lnw + lane * 4);
+        const f32x4 gb = *reinterpret_cast<const f32x4*>(tail.lnb + lane * 4);
+        __syncthreads();
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int lr = wave * 2 + rr;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(&xn[lr * PC_XLD + lane * 4]);
+            const float mean = pc_wsum(v[0] + v[1] + v[2] + v[3]) * (1.0f / 256.0f);
+            const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
+            const float var = pc_wsum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.0f / 256.0f);
+            const float rstd = 1.0f / sqrtf(var + eps);
+            f32x4 o;
+            o[0] = d0 * rstd * gw[0] + gb[0];
+            o[1] = d1 * rstd * gw[1] + gb[1];
+            o[2] = d2 * rstd * gw[2] + gb[2];
+            o[3] = d3 * rstd * gw[3] + gb[3];
+            if (row0 + lr >= M) o = f32x4{0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(&xn[lr * PC_XLD + lane * 4]) = o;
+        }
+    }
+    const int ntile = (tail.N + 255) / 256;
+    const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(tail.W), 0, ntile * 256 * PC_D * 4, 0x00020000);
+    auto tld = [&](int t, int f) -> f32x4 { return pc_bufld(trs, lane16, (unsigned)((min(t, ntile - 1) * 8 + wave) * 32 + f) * 256u); };
+#pragma unroll
+    for (int k = 0; k < P16_RING; ++k) pre[k] = tld(0, k);
+    __syncthreads();                                  // normalised tile complete
+    for (int t = 0; t < ntile; ++t) {
+        float bv[2];
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) bv[nt] = tail.bias[min(t * 256 + wave * 32 + 16 * nt + fr, tail.N - 1)];
+        f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        float a0 = xa[0], a1 = xa[2];
+#pragma unroll
+        for (int g = 0; g < 32; ++g) {
+            float n0 = 0.f, n1 = 0.f;
+            if (g + 1 < 32) { n0 = xa[8 * (g + 1)]; n1 = xa[8 * (g + 1) + 2]; }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                acc[q & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(q < 2 ? a0 : a1, pre[g % P16_RING][q], acc[q & 1], 0, 0, 0);
+                if (q == 3) pre[g % P16_RING] = tld(t + (g + P16_RING) / 32, (g + P16_RING) & 31);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            a0 = n0;
+            a1 = n1;
+        }
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const int col = t * 256 + wave * 32 + 16 * nt + fr;
+            if (col >= tail.N) continue;
+            if (tail.plane_stride > 0) {
+                float* plane = tail.out + (size_t)t * tail.plane_stride + wave * 32 + 16 * nt + fr;
+                const int pb0 = row0 / tail.seq_t, pt0 = row0 - pb0 * tail.seq_t;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int lr = 4 * kk + r;
+                    const SeqRow q = seq_row(pb0, pt0, tail.seq_t, lr);
+                    if (row0 + lr < M) plane[((size_t)q.b * (tail.seq_t + tail.pad_t) + q.t) * 256] = acc[nt][r] + bv[nt];
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = row0 + 4 * kk + r;
+                    if (row < M) tail.out[(size_t)row * tail.ldo + col] = acc[nt][r] + bv[nt];
+                }
+            }
+        }
+    }
+}
+
+// W1 [dff, 256], W2 [256, dff] -> ffn16_kernel's layout [chunk][idx][fragment f][lane][4] (kk = lane >> 4, fr = lane & 15):
+//   p1: W1[chunk*128 + 32 idx + 16 (q & 1) + fr][8 f + p16_k0(kk) + 2 (q >> 1)]
+//   p2: W2[64 idx + 16 q + fr][chunk*128 + 8 (f >> 1) + p16_k0(kk) + 2 (f & 1)]
+__global__ __launch_bounds__(256) void pack_ffn16_kernel(const float* __restrict__ w1, const float* __restrict__ w2,
+                                                         float* __restrict__ p1, float* __restrict__ p2, int dff) {
+    const size_t n = (size_t)dff * PC_D;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= 2 * n) return;
+    const bool second = t >= n;
+    const size_t e = second ? t - n : t;
+    const int q = (int)(e & 3), lane = (int)((e >> 2) & 63), f = (int)((e >> 8) & 31), idx = (int)((e >> 13) & 3), chunk = (int)(e >> 15);
+    const int fr = lane & 15, ko = p16_k0(lane >> 4);
+    if (!second) p1[e] = w1[(size_t)(chunk * PC_CH + 32 * idx + 16 * (q & 1) + fr) * PC_D + 8 * f + ko + 2 * (q >> 1)];
+    else p2[e] = w2[(size_t)(64 * idx + 16 * q + fr) * dff + chunk * PC_CH + 8 * (f >> 1) + ko + 2 * (f & 1)];
+}
+// W [N, 256] (N a multiple of 256: the fused QKV weights, pointwise_conv2) -> [tile t][wave][fragment f][lane][4]:
+//   P = W[t*256 + 32 wave + 16 (q & 1) + fr][8 f + p16_k0(kk) + 2 (q >> 1)]       (rows >= n_src packed as zeros)
+__global__ __launch_bounds__(256) void pack_rows16_kernel(const float* __restrict__ w, float* __restrict__ p, int N, int n_src) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)N * PC_D) return;
+    const int q = (int)(e & 3), lane = (int)((e >> 2) & 63), f = (int)((e >> 8) & 31), wave = (int)((e >> 13) & 7), t = (int)(e >> 16);
+    const int row = t * 256 + 32 * wave + 16 * (q & 1) + (lane & 15);
+    p[e] = row < n_src ? w[(size_t)row * PC_D + 8 * f + p16_k0(lane >> 4) + 2 * (q >> 1)] : 0.f;
+}
+void launch_pack_ffn16(const float* w1, const float* w2, float* p1, float* p2, int dff, hipStream_t s) {
+    const size_t n = (size_t)2 * dff * PC_D;
+    hipLaunchKernelGGL(pack_ffn16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w1, w2, p1, p2, dff);
+}
+void launch_pack_rows16(const float* w, float* p, int N, hipStream_t s, int n_src) {
+    const size_t n = (size_t)N * PC_D;
+    hipLaunchKernelGGL(pack_rows16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, p, N, n_src < 0 ? N : n_src);
+}
+
+// full-d_ff launch of the 16-row kernel (w1 / w2: launch_pack_ffn16 copies; tail->W, head->W: launch_pack_rows16 copies).
+// Returns 2 when the tail stage ran, 4 when the head stage ran, 0 otherwise, -1 for what this kernel does not cover (the caller
+// checks first: d_model 256, d_ff a multiple of 128, tail N a multiple of 256, head with 15 or 7 taps, never both).
+int launch_ffn16(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2, const float* b2, int M,
+                 int dff, float eps, float scale, hipStream_t s, const FfnTail* tail, const FfnHead* head) {
+    if (M <= 0) return 0;
+    if (dff % PC_CH || dff <= 0 || (tail && tail->out && head && head->glu)) return -1;
+    const size_t lds = (size_t)(P16_BM * PC_XLD + 2 * P16_BM * PC_HLD) * sizeof(float);
+    const dim3 grid((M + P16_BM - 1) / P16_BM);
+    if (head && head->glu) {
+        if (head->ktaps == 15)
+            hipLaunchKernelGGL((ffn16_kernel<0, 15>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, *head);
+        else if (head->ktaps == 7)
+            hipLaunchKernelGGL((ffn16_kernel<0, 7>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, *head);
+        else
+            return -1;
+        return 4;
+    }
+    if (tail && tail->out) {
+        if (tail->N % 256) return -1;
+        hipLaunchKernelGGL((ffn16_kernel<1, 0>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, *tail, FfnHead{});
+        return 2;
+    }
+    hipLaunchKernelGGL((ffn16_kernel<0, 0>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, FfnHead{});
+    return 0;
+}
+
+// Summation-order probe (tests/test_gpu_mfma_order.py): C[16][16] = A[16][K] . B[16][K]^T two ways, one wave.
+//   c32: a chain of v_mfma_f32_32x32x2_f32 in the fused kernels' k order (group g of 8 k, MFMA q takes k = 8g + q and 8g + 4 + q),
+//        A and B zero-padded to 32 rows
+//   c16: a chain of v_mfma_f32_16x16x4_f32; in group g, MFMA m (0, 1) gives lane (l >> 4) = kk the k value 8g + perm[4m + kk]
+// A 16-row kernel can only replace the 32-row one bit for bit if some perm makes c16 == c32 for all inputs.
+__global__ __launch_bounds__(64) void mfma_order_probe_kernel(const float* __restrict__ a, const float* __restrict__ b, float* c32,
+                                                              float* c16, int K, int4 p0, int4 p1) {
+    const int lane = threadIdx.x;
+    {
+        const int frow = lane & 31, fh = lane >> 5;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int g = 0; g < K / 8; ++g)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int k = 8 * g + 4 * fh + q;
+                const float av = frow < 16 ? a[frow * K + k] : 0.f, bv = frow < 16 ? b[frow * K + k] : 0.f;
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+            }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * fh;
+            if (row < 16 && frow < 16) c32[row * 16 + frow] = acc[r];
+        }
+    }
+    {
+        const int fr = lane & 15, kk = lane >> 4;
+        const int o0 = kk == 0 ? p0.x : kk == 1 ? p0.y : kk == 2 ? p0.z : p0.w;
+        const int o1 = kk == 0 ? p1.x : kk == 1 ? p1.y : kk == 2 ? p1.z : p1.w;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < K / 8; ++g) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[fr * K + 8 * g + o0], b[fr * K + 8 * g + o0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[fr * K + 8 * g + o1], b[fr * K + 8 * g + o1], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) c16[(4 * kk + r) * 16 + fr] = acc[r];
+    }
+}
+
 // W1 [dff, 256], W2 [256, dff] -> the VAR == 2 layout [chunk][idx][slab j][group g][lane][4]:
 //   p1: W1[chunk*128 + 32 idx + (lane & 31)][32 j + 8 g + 4 (lane >> 5) + q]
 //   p2: W2[64 idx + 32 (j & 1) + (lane & 31)][chunk*128 + 32 (j >> 1) + 8 g + 4 (lane >> 5) + q]
@@ -718,3 +1198,13 @@ int launch_ffn_pc(float* x, const float* lnw, const float* lnb, const float* w1,
 }
 
 }  // namespace masr
+
+extern "C" int masr_mfma_order_probe(const float* a_dev, const float* b_dev, float* c32_dev, float* c16_dev, int32_t k,
+                                     const int32_t* perm, void* stream) {
+    if (!a_dev || !b_dev || !c32_dev || !c16_dev || !perm || k <= 0 || k % 8) return 1;
+    for (int i = 0; i < 8; ++i)
+        if (perm[i] < 0 || perm[i] > 7) return 1;
+    hipLaunchKernelGGL(masr::mfma_order_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a_dev, b_dev, c32_dev, c16_dev, (int)k,
+                       make_int4(perm[0], perm[1], perm[2], perm[3]), make_int4(perm[4], perm[5], perm[6], perm[7]));
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
