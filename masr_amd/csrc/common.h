@@ -85,11 +85,15 @@ struct GemmArgs {
     // skip_rps > 0 (with lens): row r belongs to sequence r / skip_rps at frame (r % skip_rps) / skip_div; a tile whose rows all lie in
     // ONE sequence at frames with 4 * frame >= lens[sequence] (padding) is not computed -- its output rows keep what they held
     int skip_rps, skip_div;
+    // A_CONV2, N = 256: launch_pack_conv2_rows copy of W -- launch_gemm then runs the full-width row-block kernel where it would run
+    // 128x128 tiles (nullptr: never)
+    const float* Wp;
 };
 
 void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s);
 void set_conv2_mid_fill(int pct);     // diagnostics (masr_debug_set key 33)
 void set_gemm_waves(int n);          // diagnostics (masr_debug_set key 17): waves per workgroup of the large conv2 launch, 8 (default) or 4
+void launch_pack_conv2_rows(const float* w, float* p, int K, hipStream_t s);    // W [256, K] -> GemmArgs::Wp layout
 // deep-K, few-row GEMM: split K over workgroups into `partial` [nsplit][M][N], then reduce + epilogue into a.C
 void launch_gemm_splitk(const GemmArgs& a, float* partial, int nsplit, hipStream_t s, int amode = A_PLAIN);
 // exploratory split-bf16 variant (gemm_bf16x3.hip; masr_debug_set key 20): standard epilogue only; false = not taken

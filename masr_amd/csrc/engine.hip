@@ -308,6 +308,7 @@ struct masr_engine : EngineWs {
     std::map<const float*, std::pair<DevBuf, DevBuf>> ffn_dual_packed;  // the same in the two-chain order of ffn_dual.hip (and its QKV tail weights)
     std::map<const float*, std::pair<DevBuf, DevBuf>> x3_packed;   // exploratory split-bf16 FFN: packed weights per FFN (W1 pointer)
     std::map<const float*, std::pair<DevBuf, DevBuf>> ffn16_packed;  // the same in the 16-row kernel's order (ffn_pc.hip ffn16_kernel), per W1 / tail / head pointer
+    std::map<const float*, std::pair<DevBuf, DevBuf>> conv2_packed;  // conv2 weights in the row-block kernel's order (gemm_f32.hip conv2_rows_kernel)
     long long* beam_prof = nullptr;                                             // debug: phase cycle counters (masr_debug_set key 2)                                               // GPU beam search scratch                               // DeepSpeech2 workspaces
     float *preln_w = nullptr, *preln_b = nullptr, *tr_dw_w = nullptr, *tr_dw_b = nullptr, *tr_pw_w = nullptr,
           *tr_pw_b = nullptr, *rec_w = nullptr, *rec_b = nullptr;
@@ -396,7 +397,7 @@ struct CallGuard {
     hipStream_t s;
     size_t n0;
     static size_t packed_count(const masr_engine* e) {
-        return e->ffn_packed.size() + e->ffn_dual_packed.size() + e->x3_packed.size() + e->ffn16_packed.size();
+        return e->ffn_packed.size() + e->ffn_dual_packed.size() + e->x3_packed.size() + e->ffn16_packed.size() + e->conv2_packed.size();
     }
     CallGuard(masr_engine* e_, hipStream_t s_) : e(e_), s(s_), n0(packed_count(e_)) {
         if (!e->pack_pending) return;
@@ -421,6 +422,7 @@ struct CallGuard {
 static int g_ffn_dual = 0;         // masr_debug_set key 24: 0 = the full FFN launches run ffn_pc.hip (one accumulator chain per wave) instead of ffn_dual.hip (A/B)
 static int g_ffn_packed = 2;       // masr_debug_set key 23: 0 = the full FFN launches stream their weights through the wave-private LDS slabs (A/B)
 static int g_ffn16 = 1;            // masr_debug_set key 39: 0 = the full packed FFN launches run the 32-row kernel instead of the 16-row one (A/B)
+static int g_conv2_rows = 1;       // masr_debug_set key 40: 0 = the offline conv2 runs on 128x128 tiles instead of full-width 64-row blocks (A/B)
 // masr_debug_set key 20 -- EXPLORATORY precision mode, never the contract path: the big offline GEMMs (conv2, embed projection,
 // the two FFN GEMMs, unfused) run as split-bf16 products on the bf16 matrix pipe (gemm_bf16x3.hip)
 static int g_bf16x3 = 0;
@@ -740,6 +742,10 @@ void masr_destroy(masr_engine* e) {
         kv.second.first.release();
         kv.second.second.release();
     }
+    for (auto& kv : e->conv2_packed) {
+        kv.second.first.release();
+        kv.second.second.release();
+    }
     for (auto& ev : e->prof_events) {
         (void)hipEventDestroy(ev.first);
         (void)hipEventDestroy(ev.second);
@@ -747,15 +753,16 @@ void masr_destroy(masr_engine* e) {
     delete e;
 }
 
-// The fragment-ordered weight copies (ffn_packed / ffn_dual_packed / x3_packed / ffn16_packed) are built on first use and keyed by the device
+// The fragment-ordered weight copies (ffn_packed / ffn_dual_packed / x3_packed / ffn16_packed / conv2_packed) are built on first use and keyed by the device
 // pointer of the weights they were packed from.  A reload (masr_load_tensor on a finalized engine, then masr_finalize) re-uploads
 // into the SAME device buffers when the sizes are unchanged, so the keys would still match while the copies hold the old
 // values: every reload drops them (after the device has drained: launches in flight may still read them).
 static void drop_packed_weights(masr_engine* e) {
-    if (e->ffn_packed.empty() && e->ffn_dual_packed.empty() && e->x3_packed.empty() && e->ffn16_packed.empty()) return;
+    if (e->ffn_packed.empty() && e->ffn_dual_packed.empty() && e->x3_packed.empty() && e->ffn16_packed.empty() && e->conv2_packed.empty())
+        return;
     (void)hipSetDevice(e->cfg.device_id);
     (void)hipDeviceSynchronize();
-    for (auto* m : {&e->ffn_packed, &e->ffn_dual_packed, &e->x3_packed, &e->ffn16_packed}) {
+    for (auto* m : {&e->ffn_packed, &e->ffn_dual_packed, &e->x3_packed, &e->ffn16_packed, &e->conv2_packed}) {
         for (auto& kv : *m) {
             kv.second.first.release();
             kv.second.second.release();
@@ -1208,6 +1215,16 @@ int embed(masr_engine* e, hipStream_t s, const float* feats, int nseq, int T, in
             CHK(e->ffpart.ensure((size_t)nsplit * a.M * a.N * sizeof(float)));
             launch_gemm_splitk(a, e->ffpart.as<float>(), nsplit, s, A_CONV2);
         } else {
+            if (g_conv2_rows && a.N == 256) {     // full-width row blocks: the weights in the kernel's fragment order, packed at first use
+                auto it = e->conv2_packed.find(e->conv2_w);
+                if (it == e->conv2_packed.end()) {
+                    std::pair<DevBuf, DevBuf> pk;
+                    CHK(pk.first.ensure((size_t)a.N * a.K * sizeof(float)));
+                    launch_pack_conv2_rows(e->conv2_w, pk.first.as<float>(), a.K, s);
+                    it = e->conv2_packed.emplace(e->conv2_w, pk).first;
+                }
+                a.Wp = it->second.first.as<float>();
+            }
             launch_gemm(a, A_CONV2, EPI_STD, s);
         }
     }
@@ -3100,6 +3117,7 @@ int masr_debug_set(masr_engine* e, int32_t key, int32_t value) {
     else if (key == 37) g_beam_narrow = value;
     else if (key == 38) e->skip_padding = value;
     else if (key == 39) g_ffn16 = value;
+    else if (key == 40) g_conv2_rows = value;
     else if (key == 17) set_gemm_waves(value);
     else if (key == 18) set_conv1_nt(value);
     else if (key == 16) { e->prof_stride = value > 1 ? value : 1; e->prof_seen = 0; }

@@ -13,7 +13,7 @@
 //   [32-channel block][kh][kw][channel] so that overlapping window columns are re-read while still cached.
 // * Epilogue: bias, ReLU/SiLU, alpha, residual, row masking.  (The K = 256 projections of the layers use
 //   rowgemm.hip, the FFN ffn_pc.hip; this kernel serves conv2, the embed projection, the positional-key
-//   precompute and the full-probability CTC head.)
+//   precompute and the full-probability CTC head; the large offline conv2 runs on conv2_rows_kernel below.)
 #include "common.h"
 
 namespace masr {
@@ -214,6 +214,162 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(GemmArgs p) {
     }
 }
 
+// Offline conv2 on full-width row blocks (N = 256): a workgroup owns 64 output rows x all 256 channels, 8 waves, wave w the
+// columns 32w .. 32w+31 of all 64 rows (two 32x32 accumulators).  The implicit-GEMM A slab (64 rows x 32 k) is gathered ONCE per
+// block into double-buffered LDS (one dwordx4 load + one ds_write_b128 per thread and slab, one barrier per slab) and shared by all
+// 8 waves; the 128x128-tile launch staged every A element twice (once per column tile) and every weight element through LDS.  The
+// weights come from a packed copy in consumption order (launch_pack_conv2_rows: [wave][kt][g][lane][4]) through raw buffer loads
+// straight into MFMA operand registers, a ring of RB_RING fragments (two slabs ahead); each 1 KB fragment feeds 8 MFMAs (4 k steps
+// x 2 row tiles).  Per 32 MFMAs and wave: 2 staging + 8 A fragment reads + 4 weight loads (the 128x128 tile: 8 + 12).
+// 92 VGPRs and 18 KB of LDS: two workgroups per CU.  (Two slabs per barrier, 36 KB of LDS: 1 412 against 1 375 us; not kept.)
+// Bit-identical to gemm_f32_kernel: every output element sees the same MFMA chain (kt -> g -> s, k = 8g + s and 8g + 4 + s in
+// MFMA s) from zero, then the same epilogue.
+static constexpr int RB_BM = 64;
+static constexpr int RB_N = 256;
+static constexpr int RB_RING = 8;
+
+__device__ __forceinline__ f32x4 rb_bufld(__amdgpu_buffer_rsrc_t rs, unsigned lane16, unsigned frag) {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, frag * 1024u, 0));
+}
+
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void conv2_rows_kernel(GemmArgs p) {
+    __shared__ __align__(16) float As[2][RB_BM * LDP];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nbm = (p.M + RB_BM - 1) / RB_BM;
+    int bid = blockIdx.x;
+    if (p.skip_rps <= 0) {          // XCD-aware block order as in gemm_f32_kernel
+        const int q = nbm / 8, r = nbm % 8, xcd = bid % 8, idx = bid / 8;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    }
+    const int bm = bid * RB_BM;
+    if (p.skip_rps > 0 && p.lens) {         // a block of padded frames only (whole workgroup, before any barrier)
+        const int span = min(bm + RB_BM, p.M) - 1 - bm;
+        const int b0 = bm / p.skip_rps, r0 = bm - b0 * p.skip_rps;
+        if (r0 + span < p.skip_rps && 4 * (r0 / p.skip_div) >= p.lens[b0]) return;
+    }
+
+    // ---- A gather: thread = (row tid >> 3, 4 k values), one float4 per slab ----------------------------------------------
+    const int lrow = tid >> 3, lc4 = (tid & 7) * 4;
+    const float* aptr;
+    const bool aok = bm + lrow < p.M;
+    {
+        const int mm = aok ? bm + lrow : 0;
+        const int f2 = mm % p.F2, bt = mm / p.F2, t2 = bt % p.T2, b = bt / p.T2;
+        aptr = p.A + (((size_t)b * p.T1 + 2 * t2) * p.F1 + 2 * f2) * p.Cc + lc4;
+    }
+    auto load_a = [&](int kt) -> f32x4 {
+        const int cb = kt / 9, pos = kt - 9 * cb;       // K order [channel block of 32][kh][kw][32 channels]
+        const int kh = pos / 3, kw = pos - 3 * kh;
+        const size_t aoff = ((size_t)kh * p.F1 + kw) * p.Cc + (size_t)cb * BK;
+        return aok ? *reinterpret_cast<const f32x4*>(aptr + aoff) : f32x4{0.f, 0.f, 0.f, 0.f};
+    };
+    float* const adst = &As[0][lrow * LDP + lc4];
+
+    // ---- weights: fragment (kt, g) of wave w at ((w * KT + kt) * 4 + g) KB -----------------------------------------------
+    const int KT = p.K / BK;
+    const __amdgpu_buffer_rsrc_t wrs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Wp), 0, RB_N * p.K * (int)sizeof(float), 0x00020000);
+    const unsigned lane16 = lane * 16;
+    const unsigned wfrag0 = (unsigned)(wave * KT) * 4u;
+    auto bld = [&](int kt, int g) -> f32x4 { return rb_bufld(wrs, lane16, wfrag0 + (unsigned)min(kt, KT - 1) * 4u + g); };
+
+    f32x4 pre[RB_RING];
+#pragma unroll
+    for (int i = 0; i < RB_RING; ++i) pre[i] = bld(i >> 2, i & 3);
+    f32x16 acc[2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+
+    *reinterpret_cast<f32x4*>(adst) = load_a(0);
+    __syncthreads();
+
+    const int frow = lane & 31, fcol = (lane >> 5) * 4;
+    const float* afrag = &As[0][frow * LDP + fcol];
+    for (int kt0 = 0; kt0 < KT; kt0 += 2) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {           // slab kt = kt0 + j lives in LDS buffer j, its fragments in ring slots 4j .. 4j+3
+            const int kt = kt0 + j;
+            if (j == 1 && kt >= KT) break;
+            f32x4 areg;
+            if (kt + 1 < KT) areg = load_a(kt + 1);
+            const float* Ab = afrag + j * RB_BM * LDP;
+            f32x4 af[2] = {*reinterpret_cast<const f32x4*>(Ab), *reinterpret_cast<const f32x4*>(Ab + 32 * LDP)};
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int g = 0; g < BK / 8; ++g) {
+                f32x4 an[2];
+                if (g + 1 < BK / 8) {
+                    an[0] = *reinterpret_cast<const f32x4*>(Ab + (g + 1) * 8);
+                    an[1] = *reinterpret_cast<const f32x4*>(Ab + 32 * LDP + (g + 1) * 8);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int m = 0; m < 2; ++m)
+                        acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[m][s], pre[4 * j + g][s], acc[m], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                pre[4 * j + g] = bld(kt + 2, g);
+                __builtin_amdgcn_sched_barrier(0);
+                if (g + 1 < BK / 8) {
+                    af[0] = an[0];
+                    af[1] = an[1];
+                }
+            }
+            if (kt + 1 < KT) *reinterpret_cast<f32x4*>(adst + (j ^ 1) * RB_BM * LDP) = areg;
+            __syncthreads();
+        }
+    }
+
+    // ---- epilogue (gemm_f32_kernel EPI_STD with TM = 2, TN = 1) ---------------------------------------------------------
+    const int ccol = lane & 31;
+    const int rbase = 4 * (lane >> 5);
+    const int col = wave * 32 + ccol;
+    const float bv = p.bias ? p.bias[col] : 0.f;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        float res[16];   // residual loads before the stores (R may alias C)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = min(bm + m * 32 + (r & 3) + 8 * (r >> 2) + rbase, p.M - 1);
+            res[r] = p.R ? p.R[(size_t)row * p.ldr + col] : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = bm + m * 32 + (r & 3) + 8 * (r >> 2) + rbase;
+            float v = acc[m][r] + (p.bias_after_alpha ? 0.f : bv);
+            if (p.act == ACT_RELU) v = fmaxf(v, 0.f);
+            else if (p.act == ACT_SILU) v = silu_f(v);
+            if (p.mask_tp > 0) {
+                const int rc = min(row, p.M - 1);
+                const int b = rc / p.mask_tp, t = rc - b * p.mask_tp;
+                if (4 * t >= p.lens[b]) v = 0.f;
+            }
+            v = res[r] + v * p.alpha + (p.bias_after_alpha ? bv : 0.f);
+            if (row < p.M) p.C[(size_t)row * p.ldc + col] = v;
+        }
+    }
+}
+
+// W [256, K] (K order of the implicit GEMM) -> conv2_rows_kernel's layout [wave][kt][g][lane][4]:
+//   P = W[32 wave + (lane & 31)][32 kt + 8 g + 4 (lane >> 5) + q]
+__global__ __launch_bounds__(256) void pack_conv2_rows_kernel(const float* __restrict__ w, float* __restrict__ p, int K) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)RB_N * K) return;
+    const int KT = K / BK;
+    const int q = (int)(e & 3), lane = (int)((e >> 2) & 63);
+    const size_t frag = e >> 8;
+    const int g = (int)(frag & 3), kt = (int)((frag >> 2) % KT), wave = (int)((frag >> 2) / KT);
+    p[e] = w[(size_t)(32 * wave + (lane & 31)) * K + kt * BK + 8 * g + 4 * (lane >> 5) + q];
+}
+void launch_pack_conv2_rows(const float* w, float* p, int K, hipStream_t s) {
+    const size_t n = (size_t)RB_N * K;
+    hipLaunchKernelGGL(pack_conv2_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, p, K);
+}
+
 // waves per workgroup of the conv2 implicit GEMM on 128x128 tiles: 8 (default) or 4 (masr_debug_set key 17).  In one kernel
 // trace with both shapes alternating (tools/gemm_waves_trace.py): 1 467 vs 1 486 us on average, 1 437 vs 1 480 us at best.
 static int g_gemm_waves = 8;
@@ -266,6 +422,10 @@ void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s) {
         // 8 waves (2 x 4 grid, 64 x 32 per wave) on the 128x128 tile: two workgroups per CU = four waves per SIMD cover each
         // other's slab barriers; 1 494 -> 1 457 us at B = 32 x 10 s by HIP events.  (4 x 2 grid: 1 488 us; 16 waves as a 4 x 4 grid: 1 624 us; 128x256 /
         // 256x128 tiles with 8 waves, one workgroup per CU: 1 540 us.)
+        // full-width 64-row blocks with packed weights in registers when the caller supplies the packed copy (a.Wp: offline conv2,
+        // masr_debug_set key 40)
+        else if (a.Wp && a.N == RB_N && a.K % BK == 0)
+            hipLaunchKernelGGL(conv2_rows_kernel, dim3((unsigned)((a.M + RB_BM - 1) / RB_BM)), dim3(512), 0, s, a);
         else if (g_gemm_waves == 8) launch_t<128, 128, 2, 4, A_CONV2, EPI_STD>(a, s);
         else launch_t<128, 128, 2, 2, A_CONV2, EPI_STD>(a, s);
         return;
