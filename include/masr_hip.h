@@ -386,6 +386,10 @@ int masr_select_lane(masr_engine* e, int32_t lane);
  *      packed copies with buffer loads (bit-identical)
  *  39  0 = the full packed FFN launches run the 32-row kernel instead of the 16-row one (two workgroups per CU; bit-identical)
  *  40  0 = the offline conv2 runs on 128x128 tiles instead of full-width 64-row blocks with packed weights (bit-identical)
+ *  41  0 = conv1 runs as its own launch (writing its output to a workspace) instead of inside the A gather of the row-block
+ *      conv2 (key 40; bit-identical)
+ *  42  0 = the K quarters of the offline embed projection run on 128x128 tiles instead of full-width 64-row blocks with packed
+ *      weights (bit-identical)
  *  20  1 = EXPLORATORY split-bf16 precision mode (not the reference's fp32 arithmetic, never the contract path): conv2, the embed
  *      projection and the other launches of the generic GEMM in the offline forward as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on
  *      the bf16 matrix pipe, fp32 accumulation (csrc/gemm_bf16x3.hip); 3 = also the FFN, unfused (slower than the fused fp32 FFN) */

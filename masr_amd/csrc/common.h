@@ -88,12 +88,17 @@ struct GemmArgs {
     // A_CONV2, N = 256: launch_pack_conv2_rows copy of W -- launch_gemm then runs the full-width row-block kernel where it would run
     // 128x128 tiles (nullptr: never)
     const float* Wp;
+    // conv2_rows_kernel only, with Wp: conv1 computed inside the A gather (masr_debug_set key 41) from the features
+    // feats [B, Tin, Fin] through CMVN (mean, istd) and the conv1 weights c1w [9][256], c1b [256]; A is not read (nullptr: from A)
+    const float *feats, *mean, *istd, *c1w, *c1b;
+    int Tin, Fin;
 };
 
 void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s);
 void set_conv2_mid_fill(int pct);     // diagnostics (masr_debug_set key 33)
 void set_gemm_waves(int n);          // diagnostics (masr_debug_set key 17): waves per workgroup of the large conv2 launch, 8 (default) or 4
 void launch_pack_conv2_rows(const float* w, float* p, int K, hipStream_t s);    // W [256, K] -> GemmArgs::Wp layout
+bool gemm_conv2_rows(const GemmArgs& a);    // launch_gemm(a, A_CONV2, EPI_STD) runs conv2_rows_kernel (needs a.Wp)
 // deep-K, few-row GEMM: split K over workgroups into `partial` [nsplit][M][N], then reduce + epilogue into a.C
 void launch_gemm_splitk(const GemmArgs& a, float* partial, int nsplit, hipStream_t s, int amode = A_PLAIN);
 // exploratory split-bf16 variant (gemm_bf16x3.hip; masr_debug_set key 20): standard epilogue only; false = not taken

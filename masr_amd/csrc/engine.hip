@@ -308,7 +308,7 @@ struct masr_engine : EngineWs {
     std::map<const float*, std::pair<DevBuf, DevBuf>> ffn_dual_packed;  // the same in the two-chain order of ffn_dual.hip (and its QKV tail weights)
     std::map<const float*, std::pair<DevBuf, DevBuf>> x3_packed;   // exploratory split-bf16 FFN: packed weights per FFN (W1 pointer)
     std::map<const float*, std::pair<DevBuf, DevBuf>> ffn16_packed;  // the same in the 16-row kernel's order (ffn_pc.hip ffn16_kernel), per W1 / tail / head pointer
-    std::map<const float*, std::pair<DevBuf, DevBuf>> conv2_packed;  // conv2 weights in the row-block kernel's order (gemm_f32.hip conv2_rows_kernel)
+    std::map<const float*, std::pair<DevBuf, DevBuf>> conv2_packed;  // conv2 and embed projection weights in the row-block kernel's order (gemm_f32.hip conv2_rows_kernel)
     long long* beam_prof = nullptr;                                             // debug: phase cycle counters (masr_debug_set key 2)                                               // GPU beam search scratch                               // DeepSpeech2 workspaces
     float *preln_w = nullptr, *preln_b = nullptr, *tr_dw_w = nullptr, *tr_dw_b = nullptr, *tr_pw_w = nullptr,
           *tr_pw_b = nullptr, *rec_w = nullptr, *rec_b = nullptr;
@@ -423,6 +423,8 @@ static int g_ffn_dual = 0;         // masr_debug_set key 24: 0 = the full FFN la
 static int g_ffn_packed = 2;       // masr_debug_set key 23: 0 = the full FFN launches stream their weights through the wave-private LDS slabs (A/B)
 static int g_ffn16 = 1;            // masr_debug_set key 39: 0 = the full packed FFN launches run the 32-row kernel instead of the 16-row one (A/B)
 static int g_conv2_rows = 1;       // masr_debug_set key 40: 0 = the offline conv2 runs on 128x128 tiles instead of full-width 64-row blocks (A/B)
+static int g_conv1_fused = 1;      // masr_debug_set key 41: 0 = conv1 runs as its own launch in front of the row-block conv2 (A/B)
+static int g_embed_rows = 1;       // masr_debug_set key 42: 0 = the offline embed projection's K quarters run on 128x128 tiles (A/B)
 // masr_debug_set key 20 -- EXPLORATORY precision mode, never the contract path: the big offline GEMMs (conv2, embed projection,
 // the two FFN GEMMs, unfused) run as split-bf16 products on the bf16 matrix pipe (gemm_bf16x3.hip)
 static int g_bf16x3 = 0;
@@ -1194,18 +1196,35 @@ int embed(masr_engine* e, hipStream_t s, const float* feats, int nseq, int T, in
     const int T1 = (T - 1) / 2, Tq = (T1 - 1) / 2;
     if (T < 7 || Tq <= 0) return fail("input too short for Conv2dSubsampling4 (need >= 7 frames)");
     const int M = nseq * Tq;
-    CHK(e->x1.ensure((size_t)nseq * T1 * F1 * d * sizeof(float)));
     CHK(e->x2.ensure((size_t)M * F2 * d * sizeof(float)));
     CHK(e->x.ensure((size_t)M * d * sizeof(float)));
-    launch_conv1(feats, e->cmvn_mean, e->cmvn_istd, e->conv1_w, e->conv1_b, e->x1.as<float>(), nseq, T, F, d, s);
     {
         GemmArgs a{};
-        a.A = e->x1.as<float>(); a.W = e->conv2_w; a.bias = e->conv2_b; a.C = e->x2.as<float>();
+        a.W = e->conv2_w; a.bias = e->conv2_b; a.C = e->x2.as<float>();
         a.M = M * F2; a.N = d; a.K = 9 * d; a.ldc = d; a.act = ACT_RELU; a.alpha = 1.f;
         a.T1 = T1; a.F1 = F1; a.T2 = Tq; a.F2 = F2; a.Cc = d;
         if (skip_lens) { a.lens = skip_lens; a.skip_rps = Tq * F2; a.skip_div = F2; }      // tiles of padded frames only: not computed
-        ProfScope ps(e, s, PROF_CONV2, 2.0 * a.M * (double)a.N * a.K);
         const int tiles = ((a.M + 63) / 64) * ((a.N + 63) / 64);
+        if (tiles >= 640 && g_conv2_rows && a.N == 256) {   // full-width row blocks: the weights in the kernel's fragment order, packed at first use
+            auto it = e->conv2_packed.find(e->conv2_w);
+            if (it == e->conv2_packed.end()) {
+                std::pair<DevBuf, DevBuf> pk;
+                CHK(pk.first.ensure((size_t)a.N * a.K * sizeof(float)));
+                launch_pack_conv2_rows(e->conv2_w, pk.first.as<float>(), a.K, s);
+                it = e->conv2_packed.emplace(e->conv2_w, pk).first;
+            }
+            a.Wp = it->second.first.as<float>();
+            if (g_conv1_fused && !g_bf16x3 && gemm_conv2_rows(a)) {    // conv1 computed in the row blocks' A gather: no x1, no conv1 launch
+                a.feats = feats; a.mean = e->cmvn_mean; a.istd = e->cmvn_istd; a.c1w = e->conv1_w; a.c1b = e->conv1_b;
+                a.Tin = T; a.Fin = F;
+            }
+        }
+        if (!a.feats) {
+            CHK(e->x1.ensure((size_t)nseq * T1 * F1 * d * sizeof(float)));
+            launch_conv1(feats, e->cmvn_mean, e->cmvn_istd, e->conv1_w, e->conv1_b, e->x1.as<float>(), nseq, T, F, d, s);
+            a.A = e->x1.as<float>();
+        }
+        ProfScope ps(e, s, PROF_CONV2, 2.0 * a.M * (double)a.N * a.K);
         if (g_bf16x3 && tiles >= 640 && launch_gemm_bf16x3(a, A_CONV2, s)) {
             // exploratory split-bf16 mode
         } else if (tiles < 640) {
@@ -1215,16 +1234,6 @@ int embed(masr_engine* e, hipStream_t s, const float* feats, int nseq, int T, in
             CHK(e->ffpart.ensure((size_t)nsplit * a.M * a.N * sizeof(float)));
             launch_gemm_splitk(a, e->ffpart.as<float>(), nsplit, s, A_CONV2);
         } else {
-            if (g_conv2_rows && a.N == 256) {     // full-width row blocks: the weights in the kernel's fragment order, packed at first use
-                auto it = e->conv2_packed.find(e->conv2_w);
-                if (it == e->conv2_packed.end()) {
-                    std::pair<DevBuf, DevBuf> pk;
-                    CHK(pk.first.ensure((size_t)a.N * a.K * sizeof(float)));
-                    launch_pack_conv2_rows(e->conv2_w, pk.first.as<float>(), a.K, s);
-                    it = e->conv2_packed.emplace(e->conv2_w, pk).first;
-                }
-                a.Wp = it->second.first.as<float>();
-            }
             launch_gemm(a, A_CONV2, EPI_STD, s);
         }
     }
@@ -1243,6 +1252,17 @@ int embed(masr_engine* e, hipStream_t s, const float* feats, int nseq, int T, in
         } else if (g_embed_split && tiles >= 128 && t128 >= 100 && t128 <= 128) {
             // B = 32 x 10 s: 124 tiles of 128x128 -- four K quarters on 8-wave workgroups = 496 workgroups, two per CU, four
             // waves per SIMD: 163 + 11 us (GEMM + reduction) against 180 + 9 us for two K halves on 64x128 tiles and 203 us unsplit
+            // (full-width 64-row blocks with the weights packed at first use, the same K quarters: 124 x 4 = 496 workgroups, key 42)
+            if (g_embed_rows && d == 256 && (F2 * d) % 32 == 0) {
+                auto it = e->conv2_packed.find(e->embed_w);
+                if (it == e->conv2_packed.end()) {
+                    std::pair<DevBuf, DevBuf> pk;
+                    CHK(pk.first.ensure((size_t)a.N * a.K * sizeof(float)));
+                    launch_pack_conv2_rows(e->embed_w, pk.first.as<float>(), a.K, s);
+                    it = e->conv2_packed.emplace(e->embed_w, pk).first;
+                }
+                a.Wp = it->second.first.as<float>();
+            }
             CHK(e->ffpart.ensure((size_t)4 * M * d * sizeof(float)));
             launch_gemm_splitk(a, e->ffpart.as<float>(), 4, s);
         } else if (g_embed_split && tiles >= 128 && wide >= 200 && wide <= 320) {
@@ -3118,6 +3138,8 @@ int masr_debug_set(masr_engine* e, int32_t key, int32_t value) {
     else if (key == 38) e->skip_padding = value;
     else if (key == 39) g_ffn16 = value;
     else if (key == 40) g_conv2_rows = value;
+    else if (key == 41) g_conv1_fused = value;
+    else if (key == 42) g_embed_rows = value;
     else if (key == 17) set_gemm_waves(value);
     else if (key == 18) set_conv1_nt(value);
     else if (key == 16) { e->prof_stride = value > 1 ? value : 1; e->prof_seen = 0; }

@@ -224,16 +224,35 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(GemmArgs p) {
 // 92 VGPRs and 18 KB of LDS: two workgroups per CU.  (Two slabs per barrier, 36 KB of LDS: 1 412 against 1 375 us; not kept.)
 // Bit-identical to gemm_f32_kernel: every output element sees the same MFMA chain (kt -> g -> s, k = 8g + s and 8g + 4 + s in
 // MFMA s) from zero, then the same epilogue.
+//
+// A operand modes (template AM):
+// * RB_X1: the implicit-GEMM gather from the conv1 output x1 [B, T1, F1, 256] (written by conv1_kernel, elementwise.hip).
+// * RB_FUSED (masr_debug_set key 41): conv1 is computed in the gather, and x1 never exists.  At block start the CMVN-normalised
+//   7 x 7 feature patch of every row (frames 4 t2 .. 4 t2 + 6, mel bins 4 f2 .. 4 f2 + 6) and the conv1 weights + bias go to LDS
+//   (12.25 + 10 KB).  Thread (row lrow, channels 32 cb + lc4 .. + 3) computes slab (cb, kh, kw) as the conv1 output at
+//   t1 = 2 t2 + kh, f1 = 2 f2 + kw: bias, then 9 fmaf in conv1_kernel's tap order, then ReLU, so every value is bit-identical to
+//   conv1_kernel's.  Its taps are spread over the MFMA groups of the slab before (LDS reads ahead of the group's MFMAs, the fmaf
+//   behind them), and one ds_write_b128 replaces the global load.
+// * RB_PLAIN: row-major A (lda), K split into gridDim.y ranges of p.ksplit slabs, raw partials stored as EPI_SPLITK
+//   (splitk_reduce_kernel applies the epilogue): the offline embed projection (masr_debug_set key 42).
 static constexpr int RB_BM = 64;
 static constexpr int RB_N = 256;
 static constexpr int RB_RING = 8;
+static constexpr int RB_PP = 49;     // RB_FUSED: 7 x 7 feature patch per row (odd pitch: the 8 rows of a wave on 8 banks)
+enum { RB_X1 = 0, RB_FUSED = 1, RB_PLAIN = 2 };
 
 __device__ __forceinline__ f32x4 rb_bufld(__amdgpu_buffer_rsrc_t rs, unsigned lane16, unsigned frag) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, frag * 1024u, 0));
 }
 
+// RB_FUSED: first conv1 tap of MFMA group g (taps [rb_tap(g), rb_tap(g + 1)) follow group g's MFMAs)
+__device__ constexpr int rb_tap(int g) { return g == 0 ? 0 : g == 1 ? 2 : g == 2 ? 4 : g == 3 ? 6 : 9; }
+
+template <int AM>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void conv2_rows_kernel(GemmArgs p) {
+    constexpr int XS = AM == RB_FUSED ? 10 * RB_N + RB_BM * RB_PP : 4;      // conv1 weights [9][256] + bias [256], patches [64][49]
     __shared__ __align__(16) float As[2][RB_BM * LDP];
+    __shared__ __align__(16) float Xs[XS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nbm = (p.M + RB_BM - 1) / RB_BM;
@@ -248,26 +267,35 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
         const int b0 = bm / p.skip_rps, r0 = bm - b0 * p.skip_rps;
         if (r0 + span < p.skip_rps && 4 * (r0 / p.skip_div) >= p.lens[b0]) return;
     }
+    const int KT = p.K / BK;
+    const int kt_lo = AM == RB_PLAIN ? (int)blockIdx.y * p.ksplit : 0;
+    const int kt_hi = AM == RB_PLAIN ? min(kt_lo + p.ksplit, KT) : KT;
 
     // ---- A gather: thread = (row tid >> 3, 4 k values), one float4 per slab ----------------------------------------------
     const int lrow = tid >> 3, lc4 = (tid & 7) * 4;
-    const float* aptr;
+    const float* aptr = nullptr;
     const bool aok = bm + lrow < p.M;
-    {
+    if (AM == RB_X1) {
         const int mm = aok ? bm + lrow : 0;
         const int f2 = mm % p.F2, bt = mm / p.F2, t2 = bt % p.T2, b = bt / p.T2;
         aptr = p.A + (((size_t)b * p.T1 + 2 * t2) * p.F1 + 2 * f2) * p.Cc + lc4;
+    } else if (AM == RB_PLAIN) {
+        aptr = p.A + (size_t)(aok ? bm + lrow : 0) * p.lda + lc4;
     }
     auto load_a = [&](int kt) -> f32x4 {
-        const int cb = kt / 9, pos = kt - 9 * cb;       // K order [channel block of 32][kh][kw][32 channels]
-        const int kh = pos / 3, kw = pos - 3 * kh;
-        const size_t aoff = ((size_t)kh * p.F1 + kw) * p.Cc + (size_t)cb * BK;
+        size_t aoff;
+        if (AM == RB_PLAIN) {
+            aoff = (size_t)kt * BK;
+        } else {
+            const int cb = kt / 9, pos = kt - 9 * cb;       // K order [channel block of 32][kh][kw][32 channels]
+            const int kh = pos / 3, kw = pos - 3 * kh;
+            aoff = ((size_t)kh * p.F1 + kw) * p.Cc + (size_t)cb * BK;
+        }
         return aok ? *reinterpret_cast<const f32x4*>(aptr + aoff) : f32x4{0.f, 0.f, 0.f, 0.f};
     };
     float* const adst = &As[0][lrow * LDP + lc4];
 
     // ---- weights: fragment (kt, g) of wave w at ((w * KT + kt) * 4 + g) KB -----------------------------------------------
-    const int KT = p.K / BK;
     const __amdgpu_buffer_rsrc_t wrs =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Wp), 0, RB_N * p.K * (int)sizeof(float), 0x00020000);
     const unsigned lane16 = lane * 16;
@@ -276,25 +304,76 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
 
     f32x4 pre[RB_RING];
 #pragma unroll
-    for (int i = 0; i < RB_RING; ++i) pre[i] = bld(i >> 2, i & 3);
+    for (int i = 0; i < RB_RING; ++i) pre[i] = bld(kt_lo + (i >> 2), i & 3);
+    __builtin_amdgcn_sched_barrier(0);       // (RB_FUSED: issued ahead of the staging loads)
+
+    // ---- RB_FUSED: conv1 weights and the rows' feature patches in LDS ----------------------------------------------------
+    // (rows >= M take row M - 1's patch: defined values, never stored)
+    const float* const w1s = Xs;                        // [10][256]: taps 0..8, bias
+    const float* const xrow = Xs + 10 * RB_N + lrow * RB_PP;
+    if (AM == RB_FUSED) {
+        for (int i = tid; i < 9 * RB_N; i += 512) Xs[i] = p.c1w[i];
+        if (tid < RB_N) Xs[9 * RB_N + tid] = p.c1b[tid];
+        // the 8 threads of row lrow stage its patch (one row decomposition per thread)
+        const int m = min(bm + lrow, p.M - 1);
+        const int f2 = m % p.F2, bt = m / p.F2, t2 = bt % p.T2, b = bt / p.T2;
+        const float* src = p.feats + ((size_t)b * p.Tin + 4 * t2) * p.Fin + 4 * f2;
+        for (int q = tid & 7; q < RB_PP; q += 8) {
+            const int dt = q / 7, df = q - 7 * dt, f = 4 * f2 + df;
+            Xs[10 * RB_N + lrow * RB_PP + q] = (src[dt * p.Fin + df] - p.mean[f]) * p.istd[f];
+        }
+    }
+    // conv1 taps [t0, t1) of slab kt into c (tap = 3 kh' + kw': feature (2 kh + kh', 2 kw + kw') of the row's patch); the LDS
+    // reads (rd) and the fmaf (fma) are separate so that the reads can be issued ahead of an MFMA group
+    auto c1_rd = [&](int kt, int t, f32x4& w, float& x) {
+        const int cb = kt / 9, pos = kt - 9 * cb, kh = pos / 3, kw = pos - 3 * kh;
+        x = xrow[2 * kh * 7 + 2 * kw + (t / 3) * 7 + t % 3];
+        w = *reinterpret_cast<const f32x4*>(w1s + t * RB_N + 32 * cb + lc4);
+    };
+    auto c1_fma = [&](f32x4& c, const f32x4& w, float x) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) c[q] = fmaf(w[q], x, c[q]);
+    };
+    auto c1_bias = [&](int kt) -> f32x4 { return *reinterpret_cast<const f32x4*>(w1s + 9 * RB_N + 32 * (kt / 9) + lc4); };
+    auto c1_relu = [&](f32x4& c) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) c[q] = fmaxf(c[q], 0.f);
+    };
+
+    if (AM == RB_FUSED) {       // slab 0 (the weight ring loads in flight behind the staging)
+        __syncthreads();
+        f32x4 c = c1_bias(0);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            f32x4 w;
+            float x;
+            c1_rd(0, t, w, x);
+            c1_fma(c, w, x);
+        }
+        c1_relu(c);
+        *reinterpret_cast<f32x4*>(adst) = c;
+    }
     f32x16 acc[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
 
-    *reinterpret_cast<f32x4*>(adst) = load_a(0);
+    if (AM != RB_FUSED) *reinterpret_cast<f32x4*>(adst) = load_a(kt_lo);
     __syncthreads();
 
     const int frow = lane & 31, fcol = (lane >> 5) * 4;
     const float* afrag = &As[0][frow * LDP + fcol];
-    for (int kt0 = 0; kt0 < KT; kt0 += 2) {
+    for (int kt0 = kt_lo; kt0 < kt_hi; kt0 += 2) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {           // slab kt = kt0 + j lives in LDS buffer j, its fragments in ring slots 4j .. 4j+3
             const int kt = kt0 + j;
-            if (j == 1 && kt >= KT) break;
+            if (j == 1 && kt >= kt_hi) break;
+            const bool next = kt + 1 < kt_hi;
+            const int ktn = min(kt + 1, kt_hi - 1);     // RB_FUSED: the slab computed behind this one's MFMAs
             f32x4 areg;
-            if (kt + 1 < KT) areg = load_a(kt + 1);
+            if (AM == RB_FUSED) areg = c1_bias(ktn);
+            else if (next) areg = load_a(kt + 1);
             const float* Ab = afrag + j * RB_BM * LDP;
             f32x4 af[2] = {*reinterpret_cast<const f32x4*>(Ab), *reinterpret_cast<const f32x4*>(Ab + 32 * LDP)};
             __builtin_amdgcn_sched_barrier(0);
@@ -305,6 +384,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
                     an[0] = *reinterpret_cast<const f32x4*>(Ab + (g + 1) * 8);
                     an[1] = *reinterpret_cast<const f32x4*>(Ab + 32 * LDP + (g + 1) * 8);
                 }
+                constexpr int NTAP = 3;
+                f32x4 cw[NTAP];
+                float cx[NTAP];
+                if (AM == RB_FUSED) {
+#pragma unroll
+                    for (int t = rb_tap(g); t < rb_tap(g + 1); ++t) c1_rd(ktn, t, cw[t - rb_tap(g)], cx[t - rb_tap(g)]);
+                }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
@@ -314,20 +400,36 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
                 __builtin_amdgcn_sched_barrier(0);
                 pre[4 * j + g] = bld(kt + 2, g);
                 __builtin_amdgcn_sched_barrier(0);
+                if (AM == RB_FUSED) {
+#pragma unroll
+                    for (int t = rb_tap(g); t < rb_tap(g + 1); ++t) c1_fma(areg, cw[t - rb_tap(g)], cx[t - rb_tap(g)]);
+                }
                 if (g + 1 < BK / 8) {
                     af[0] = an[0];
                     af[1] = an[1];
                 }
             }
-            if (kt + 1 < KT) *reinterpret_cast<f32x4*>(adst + (j ^ 1) * RB_BM * LDP) = areg;
+            if (AM == RB_FUSED) c1_relu(areg);
+            if (next) *reinterpret_cast<f32x4*>(adst + (j ^ 1) * RB_BM * LDP) = areg;
             __syncthreads();
         }
     }
 
-    // ---- epilogue (gemm_f32_kernel EPI_STD with TM = 2, TN = 1) ---------------------------------------------------------
     const int ccol = lane & 31;
     const int rbase = 4 * (lane >> 5);
     const int col = wave * 32 + ccol;
+    if (AM == RB_PLAIN) {       // ---- raw partial of K range blockIdx.y (gemm_f32_kernel EPI_SPLITK) ----------------------
+        float* cp = p.C + (size_t)blockIdx.y * p.M * p.ldc;
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = bm + m * 32 + (r & 3) + 8 * (r >> 2) + rbase;
+                if (row < p.M) cp[(size_t)row * p.ldc + col] = acc[m][r];
+            }
+        return;
+    }
+    // ---- epilogue (gemm_f32_kernel EPI_STD with TM = 2, TN = 1) ---------------------------------------------------------
     const float bv = p.bias ? p.bias[col] : 0.f;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -402,6 +504,23 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs p, const fl
     out[(size_t)row * p.ldc + col] = r + v * p.alpha + (p.bias_after_alpha ? bv : 0.f);
 }
 
+// the conv2 tile choice of launch_gemm below (A_CONV2, EPI_STD): few rows -> 64x64, a thin last round -> 64x128, else 128x128
+// tiles or, given a.Wp, the row blocks
+static int conv2_tiles(const GemmArgs& a) {
+    // few output rows (streaming chunk steps): 64x64 tiles so that the grid still covers the chip
+    const long t128c = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
+    // mid sizes (the 128-stream chunk step: 608 tiles of 128x128 on 512 resident slots = two rounds, the second at 19 %):
+    // 128x64 tiles (four waves, the tile count doubles) when the last round of the 128x128 grid would be under g_conv2_mid_fill
+    // percent full (masr_debug_set key 33; 0 = never)
+    const long rounds = (t128c + 511) / 512;
+    const bool thin_tail = g_conv2_mid_fill > 0 && t128c >= 200 && t128c <= 1024 &&
+                           (t128c - (rounds - 1) * 512) * 100 < (long)g_conv2_mid_fill * 512;
+    if (t128c < 200) return 64;
+    if (thin_tail) return 128;
+    return a.Wp && a.N == RB_N && a.K % BK == 0 ? 0 : 256;
+}
+bool gemm_conv2_rows(const GemmArgs& a) { return a.M > 0 && conv2_tiles(a) == 0; }
+
 void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) return;
     if (amode == A_CONV2 && epi == EPI_SPLITK) {      // caller set a.C = partial buffer, a.nsplit, a.ksplit
@@ -409,28 +528,30 @@ void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s) {
         return;
     }
     if (amode == A_CONV2) {
-        // few output rows (streaming chunk steps): 64x64 tiles so that the grid still covers the chip
-        const long t128c = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-        // mid sizes (the 128-stream chunk step: 608 tiles of 128x128 on 512 resident slots = two rounds, the second at 19 %):
-        // 128x64 tiles (four waves, the tile count doubles) when the last round of the 128x128 grid would be under g_conv2_mid_fill
-        // percent full (masr_debug_set key 33; 0 = never)
-        const long rounds = (t128c + 511) / 512;
-        const bool thin_tail = g_conv2_mid_fill > 0 && t128c >= 200 && t128c <= 1024 &&
-                               (t128c - (rounds - 1) * 512) * 100 < (long)g_conv2_mid_fill * 512;
-        if (t128c < 200) launch_t<64, 64, 2, 2, A_CONV2, EPI_STD>(a, s);
-        else if (thin_tail) launch_t<64, 128, 2, 2, A_CONV2, EPI_STD>(a, s);
+        const int tiles = conv2_tiles(a);
+        if (tiles == 64) launch_t<64, 64, 2, 2, A_CONV2, EPI_STD>(a, s);
+        else if (tiles == 128) launch_t<64, 128, 2, 2, A_CONV2, EPI_STD>(a, s);
         // 8 waves (2 x 4 grid, 64 x 32 per wave) on the 128x128 tile: two workgroups per CU = four waves per SIMD cover each
         // other's slab barriers; 1 494 -> 1 457 us at B = 32 x 10 s by HIP events.  (4 x 2 grid: 1 488 us; 16 waves as a 4 x 4 grid: 1 624 us; 128x256 /
         // 256x128 tiles with 8 waves, one workgroup per CU: 1 540 us.)
         // full-width 64-row blocks with packed weights in registers when the caller supplies the packed copy (a.Wp: offline conv2,
-        // masr_debug_set key 40)
-        else if (a.Wp && a.N == RB_N && a.K % BK == 0)
-            hipLaunchKernelGGL(conv2_rows_kernel, dim3((unsigned)((a.M + RB_BM - 1) / RB_BM)), dim3(512), 0, s, a);
-        else if (g_gemm_waves == 8) launch_t<128, 128, 2, 4, A_CONV2, EPI_STD>(a, s);
+        // masr_debug_set key 40), conv1 computed in the gather when it supplies the features (a.feats: masr_debug_set key 41)
+        else if (a.Wp && a.N == RB_N && a.K % BK == 0) {
+            const dim3 grid((unsigned)((a.M + RB_BM - 1) / RB_BM));
+            if (a.feats) hipLaunchKernelGGL(conv2_rows_kernel<RB_FUSED>, grid, dim3(512), 0, s, a);
+            else hipLaunchKernelGGL(conv2_rows_kernel<RB_X1>, grid, dim3(512), 0, s, a);
+        } else if (g_gemm_waves == 8) launch_t<128, 128, 2, 4, A_CONV2, EPI_STD>(a, s);
         else launch_t<128, 128, 2, 2, A_CONV2, EPI_STD>(a, s);
         return;
     }
     if (epi == EPI_SPLITK) {            // caller set a.C = partial buffer, a.nsplit, a.ksplit
+        // full-width 64-row blocks with packed weights in registers when the caller supplies the packed copy (a.Wp: the offline
+        // embed projection, masr_debug_set key 42)
+        if (a.Wp && a.N == RB_N && a.K % BK == 0) {
+            hipLaunchKernelGGL(conv2_rows_kernel<RB_PLAIN>, dim3((unsigned)((a.M + RB_BM - 1) / RB_BM), (unsigned)a.nsplit), dim3(512),
+                               0, s, a);
+            return;
+        }
         // many rows (the offline embed projection: 248 tiles of 64x128 = one 4-wave workgroup per CU): the wide tile, so that
         // the split doubles the waves per SIMD instead of the LDS traffic per MFMA
         // (four waves: as a 2 x 4 grid of eight waves, 32 x 32 per wave, this launch is slower -- 183.6 vs 177.4 us in one
