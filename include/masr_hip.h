@@ -38,7 +38,9 @@ typedef struct masr_config {
     int32_t max_pos;         /* positional table length (reference max_len = 5000, embedding.py:14)  */
     int32_t device_id;
     int32_t reserved[5];     /* squeezeformer: [0] reduce_idx, [1] recover_idx; efficient_conformer: [0] stride layer, [1] grouped layers,
-                                [2] group size; conformer: [0] = 1 -> cnn_module_norm: batch_norm (convolution.py:60-67; full-context only) */
+                                [2] group size; conformer: [0] = 1 -> cnn_module_norm: batch_norm (convolution.py:60-67; full-context only);
+                                conformer and efficient_conformer: [3] input_layer, 0 = conv2d (x4), 1 = conv2d6 (x6), 2 = conv2d8 (x8)
+                                (conformer/subsampling.py:65-211) */
 } masr_config;
 
 const char* masr_last_error(void);
@@ -102,7 +104,8 @@ int masr_linear_batch(masr_engine* e, const void* samples_dev, int32_t sample_fo
  * ConformerModel.get_encoder_out (masr/model_utils/conformer/model.py:152-167, encoder.py:305-346).
  *   feats_dev [B, T, n_mels] f32 (zero padded), feat_lens_dev [B] int32 (frames)
  *   decoding_chunk_size: -1 = full attention (get_encoder_out), >0 = chunk mask (encoder.forward(..., c, -1))
- *   enc_out_dev [B, T', d_model] f32, T' = ((T-1)/2-1)/2 */
+ *   enc_out_dev [B, T', d_model] f32, T' = ((T-1)/2-1)/2 (conv2d), ((T-1)/2-2)/3 (conv2d6), (((T-1)/2-1)/2-1)/2 (conv2d8);
+ *   the Efficient Conformer's stride layer halves T' once more, (T'+1)/2 -- masr_encoder_frames gives it for any model */
 int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat_lens_dev, int32_t B, int32_t T,
                      int32_t decoding_chunk_size, float* enc_out_dev, void* stream);
 
@@ -293,7 +296,7 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
 /* diagnostics: host time of masr_pool_step per phase, accumulated over `steps` calls (ms): assemble the samples | upload + mean
  * squares + wait | gains | features + frame bookkeeping | windows (lock-step chunk steps enqueued) | collapse + copy back + wait */
 int masr_pool_profile(masr_pool* p, double* phase_ms, int64_t* steps, int32_t reset);
-/* encoder frames that T feature frames give (Conv2dSubsampling4, subsampling.py:65-112; halved once more behind the Efficient
+/* encoder frames that T feature frames give (Conv2dSubsampling4 / 6 / 8 by masr_config.reserved[3], subsampling.py:65-211; halved once more behind the Efficient
  * Conformer's stride layer) and the engine's geometry -- what a host needs to size the buffers above */
 int masr_encoder_frames(masr_engine* e, int32_t feature_frames, int32_t* encoder_frames);
 int masr_engine_info(masr_engine* e, int32_t* device_id, int32_t* n_mels, int32_t* vocab_size);

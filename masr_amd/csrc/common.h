@@ -61,13 +61,30 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 #endif
 
 
+// ---- subsampling front-end geometry (encoder_conf.input_layer, masr_config.reserved[3]) ----------------------------
+// 0 = conv2d (Conv2dSubsampling4), 1 = conv2d6, 2 = conv2d8 (reference conformer/subsampling.py:65-211).  Every conv has no
+// padding: conv1 is 3x3 stride 2, then 3x3 stride 2 (conv2d), 5x5 stride 3 (conv2d6) or 3x3 stride 2 twice (conv2d8).  The
+// subsampled mask keeps input frame rate * t (x_mask[:-2:2][:-2:2], [:-2:2][:-4:3], [:-2:2] x 3), so encoder frame t of an
+// utterance of len feature frames is valid iff rate * t < len.
+enum InputLayer { IL_CONV2D = 0, IL_CONV2D6 = 1, IL_CONV2D8 = 2 };
+__host__ __device__ inline int sub_rate(int il) { return il == IL_CONV2D6 ? 6 : il == IL_CONV2D8 ? 8 : 4; }
+__host__ __device__ inline int sub_min_frames(int il) { return il == IL_CONV2D6 ? 11 : il == IL_CONV2D8 ? 15 : 7; }
+// size of one spatial axis (time or frequency) behind the convs after the first: n1 = (n - 1) / 2 comes out of conv1
+__host__ __device__ inline int sub_after_conv1(int il, int n1) {
+    return il == IL_CONV2D6 ? (n1 - 2) / 3 : il == IL_CONV2D8 ? ((n1 - 1) / 2 - 1) / 2 : (n1 - 1) / 2;
+}
+// encoder frames T' for T feature frames (0 below the minimum)
+__host__ __device__ inline int sub_frames(int il, int T) { return T < sub_min_frames(il) ? 0 : sub_after_conv1(il, (T - 1) / 2); }
+// frequency bins behind the last conv (80 mel bins: 19 / 12 / 9)
+__host__ __device__ inline int sub_bins(int il, int F) { return sub_after_conv1(il, (F - 1) / 2); }
+
 // ---- GEMM: C[M,N] = epilogue(A[M,K] * W[N,K]^T) on v_mfma_f32_32x32x2_f32 ----------------
 enum GemmAct { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2 };
-enum GemmAMode { A_PLAIN = 0, A_CONV2 = 1 };
+enum GemmAMode { A_PLAIN = 0, A_CONV2 = 1, A_CONV5 = 2 };     // A_CONV5: the 5x5 stride-3 gather of conv2d6 (A_CONV2 geometry)
 enum GemmEpi { EPI_STD = 0, EPI_GLU = 1, EPI_SPLITK = 2 };
 
 struct GemmArgs {
-    const float* A;      // [M, lda] row-major (A_PLAIN) or conv1 activations [B,T1,F1,C] (A_CONV2)
+    const float* A;      // [M, lda] row-major (A_PLAIN) or conv activations [B,T1,F1,C] (A_CONV2 / A_CONV5)
     const float* W;      // [N, K] row-major (K contiguous) -- torch Linear.weight layout
     const float* bias;   // [N] or nullptr
     float* C;            // [M, ldc]
@@ -79,7 +96,7 @@ struct GemmArgs {
     float alpha;         // out = R + alpha * act(acc + bias)
     int mask_tp;         // >0: row r -> (b = r / mask_tp, t = r % mask_tp); rows with 4*t >= lens[b] give act(..)=0
     int bias_after_alpha; // 1: out = R + alpha*act(acc) + bias  (Squeezeformer input_proj: scaling precedes the Linear)
-    // A_CONV2 geometry: row m -> (b, t2, f2) with m = (b*T2 + t2)*F2 + f2 ; k -> (kh, kw*C + c)
+    // A_CONV2 / A_CONV5 geometry: row m -> (b, t2, f2) with m = (b*T2 + t2)*F2 + f2 ; k -> (c / 32, kh, kw, c % 32)
     int T1, F1, T2, F2, Cc;
     int nsplit, ksplit;  // EPI_SPLITK: number of K ranges (gridDim.y) and BK-slabs per range
     // skip_rps > 0 (with lens): row r belongs to sequence r / skip_rps at frame (r % skip_rps) / skip_div; a tile whose rows all lie in
@@ -167,7 +184,9 @@ void launch_ctc_collapse_rows(const int* idx, const float* maxp, const int* nfra
 void launch_topk_prune(const float* probs, int M, int V, int top_n, float cutoff_prob, int* out_idx, float* out_logp,
                        int* out_cnt, int blank, float* out_blank_lp, hipStream_t s);
 void launch_argmax_rows(const float* probs, int M, int V, int* idx, float* maxp, hipStream_t s);
-void launch_frame_counts(const int* nsamp, int B, int* nfr, int* nenc, int halve, hipStream_t s);
+void launch_frame_counts(const int* nsamp, int B, int* nfr, int* nenc, int halve, hipStream_t s, int input_layer = IL_CONV2D);
+// lens [B] feature frames -> out [B] = 4 * ceil(lens / rate): the conv2d-unit lengths of a rate-6 / rate-8 front-end
+void launch_sub_lens(const int* lens, int B, int rate, int* out, hipStream_t s);
 void launch_export_att(const float* cache, float* out, int L, int H, int cap, int t, int dk, hipStream_t s, int rate = 1,
                        int shift = 0);   // rate 2: half-rate cache, entry (j + shift) / 2 (the reference repeat-interleaves)
 struct PlaneCopy { const float* src_k; const float* src_v; float* dst_k; float* dst_v; };

@@ -557,21 +557,31 @@ void launch_argmax_rows(const float* probs, int M, int V, int* idx, float* maxp,
 }
 
 // samples -> fbank frames (snip_edges) -> encoder frames (two 3x3/stride-2 convs)
-__global__ void frame_counts_kernel(const int* __restrict__ nsamp, int B, int* nfr, int* nenc, int halve) {
+__global__ void frame_counts_kernel(const int* __restrict__ nsamp, int B, int* nfr, int* nenc, int halve, int il) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const int n = nsamp[b];
     const int T = n >= 400 ? 1 + (n - 400) / 160 : 0;
     if (nfr) nfr[b] = T;
     if (nenc) {
-        const int n4 = T >= 7 ? ((T - 1) / 2 - 1) / 2 : 0;
+        const int n4 = sub_frames(il, T);
         nenc[b] = halve ? (n4 + 1) / 2 : n4;
     }
 }
 
-void launch_frame_counts(const int* nsamp, int B, int* nfr, int* nenc, int halve, hipStream_t s) {
+void launch_frame_counts(const int* nsamp, int B, int* nfr, int* nenc, int halve, hipStream_t s, int input_layer) {
     if (B <= 0) return;
-    hipLaunchKernelGGL(frame_counts_kernel, dim3((B + 63) / 64), dim3(64), 0, s, nsamp, B, nfr, nenc, halve);
+    hipLaunchKernelGGL(frame_counts_kernel, dim3((B + 63) / 64), dim3(64), 0, s, nsamp, B, nfr, nenc, halve, input_layer);
+}
+
+// feature lengths -> lengths in conv2d units for a front-end of subsampling rate r: 4 * ceil(len / r) (engine.hip sub_lens)
+__global__ void sub_lens_kernel(const int* __restrict__ lens, int B, int rate, int* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) out[b] = 4 * ((max(lens[b], 0) + rate - 1) / rate);
+}
+void launch_sub_lens(const int* lens, int B, int rate, int* out, hipStream_t s) {
+    if (B <= 0) return;
+    hipLaunchKernelGGL(sub_lens_kernel, dim3((B + 63) / 64), dim3(64), 0, s, lens, B, rate, out);
 }
 
 // stream caches -> reference layouts (encoder.py:404-419): att [L,H,t,2dk], cnn [L,1,d,pad]

@@ -258,10 +258,11 @@ struct EngineWs {
     DevBuf fb_scratch;
     DevBuf x1, x2, x, ln, hid, qkv, att, lnpad, glu, dwo, logits, feats, enc, idx, maxp, attseq, gain, nframes, lens, xsave,
         xred, xh;      // xh: rows updated by the head stage of a d_ff-split FFN launch (few rows)
+    DevBuf x3, sublens;   // conv2d8: the third subsampling conv's output; conv2d6 / conv2d8: the lengths in conv2d units (sub_lens)
     void release_all() {
         for (DevBuf* b : {&gx, &rnn_out, &hstate, &cstate, &ds2_lens, &qplanes, &attp, &cnnptrs, &ffpart, &fb_scratch, &x1, &x2, &x,
                           &ln, &hid, &qkv, &att, &lnpad, &glu, &dwo, &logits, &feats, &enc, &idx, &maxp, &attseq, &gain, &nframes,
-                          &lens, &xsave, &xred, &xh})
+                          &lens, &xsave, &xred, &xh, &x3, &sublens})
             b->release();
         stage.release();
     }
@@ -287,7 +288,7 @@ struct masr_engine : EngineWs {
     std::vector<void*> owned;   // device weight allocations
     // weights
     float *cmvn_mean = nullptr, *cmvn_istd = nullptr, *conv1_w = nullptr, *conv1_b = nullptr, *conv2_w = nullptr,
-          *conv2_b = nullptr, *embed_w = nullptr, *embed_b = nullptr, *after_w = nullptr, *after_b = nullptr,
+          *conv2_b = nullptr, *conv3_w = nullptr, *conv3_b = nullptr, *embed_w = nullptr, *embed_b = nullptr, *after_w = nullptr, *after_b = nullptr,
           *ctc_w = nullptr, *ctc_b = nullptr, *pe = nullptr;
     std::vector<LayerW> layers;
     std::vector<SqLayerW> sq_layers;
@@ -314,6 +315,7 @@ struct masr_engine : EngineWs {
           *tr_pw_b = nullptr, *rec_w = nullptr, *rec_b = nullptr;
     int reduce_idx = -1, recover_idx = -1;
     int stride_idx = -1, n_group_layers = 0, group_size = 3;   // Efficient-Conformer (model_kind 2)
+    int input_layer = IL_CONV2D;     // Conformer / Efficient-Conformer subsampling front-end (cfg.reserved[3], common.h InputLayer)
     bool conv_bn = false;            // Conformer with cnn_module_norm: batch_norm (cfg.reserved[0] = 1): LayerW::cln_w / cln_b hold the folded scale / shift
     // fbank tables
     float *window = nullptr, *melwt = nullptr, *tw512 = nullptr, *twr4 = nullptr;
@@ -653,6 +655,11 @@ static int side_streams_of(int dev, SideStreams** out) {
     return 0;
 }
 
+namespace masr {
+// frames behind the subsampling front-end (before the Efficient-Conformer's stride layer): the unit of a stream's cap and offset
+int subsampled_frames(const masr_engine* e, int feature_frames) { return sub_frames(e->input_layer, feature_frames); }
+}  // namespace masr
+
 extern "C" {
 
 const char* masr_last_error(void) { return g_err.c_str(); }
@@ -692,6 +699,13 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
     e->reduce_idx = cfg->model_kind == 1 ? cfg->reserved[0] : -1;
     e->conv_bn = cfg->model_kind == 0 && cfg->reserved[0] == 1;
     e->recover_idx = cfg->model_kind == 1 ? cfg->reserved[1] : -1;
+    if (cfg->model_kind == 0 || cfg->model_kind == 2) {
+        if (cfg->reserved[3] < IL_CONV2D || cfg->reserved[3] > IL_CONV2D8) {
+            delete e;
+            return fail("input_layer (masr_config.reserved[3]) must be 0 = conv2d, 1 = conv2d6 or 2 = conv2d8");
+        }
+        e->input_layer = cfg->reserved[3];
+    }
     if (cfg->model_kind == 2) {
         e->stride_idx = cfg->reserved[0];
         e->n_group_layers = cfg->reserved[1];
@@ -808,7 +822,7 @@ int masr_finalize(masr_engine* e, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(e->cfg.device_id));
     const int d = e->cfg.d_model, dff = e->cfg.d_ff, L = e->cfg.num_blocks, V = e->cfg.vocab_size, F = e->cfg.n_mels;
-    const int F1 = (F - 1) / 2, F2 = (F1 - 1) / 2, K = e->cfg.cnn_kernel, H = e->cfg.heads, dk = d / H;
+    const int il = e->input_layer, F2 = sub_bins(il, F), K = e->cfg.cnn_kernel, H = e->cfg.heads, dk = d / H;
     const HostTensor* t;
     CHK(up(e, "encoder.global_cmvn.mean", {F}, &e->cmvn_mean));
     CHK(up(e, "encoder.global_cmvn.istd", {F}, &e->cmvn_istd));
@@ -820,26 +834,38 @@ int masr_finalize(masr_engine* e, void* stream) {
         CHK(upload(e, w, &e->conv1_w));
         CHK(up(e, "encoder.embed.conv.0.bias", {d}, &e->conv1_b));
     }
-    {   // conv2 [co,ci,3,3] -> [co][ci / 32][kh*3+kw][ci % 32]: the implicit GEMM walks the nine window positions of one
-        // 32-channel block in consecutive K slabs, so the overlapping input columns of neighbouring positions (kw = 2 of one
-        // output, kw = 0 of the next) are re-read a slab or two later -- out of L1 / L2 instead of HBM
-        CHK(get(e, "encoder.embed.conv.2.weight", {d, d, 3, 3}, &t));
-        std::vector<float> w((size_t)d * 9 * d);
+    // conv2 (and conv2d8's conv3) [co,ci,KS,KS] -> [co][ci / 32][kh*KS+kw][ci % 32]: the implicit GEMM walks the KS^2 window
+    // positions of one 32-channel block in consecutive K slabs, so the overlapping input columns of neighbouring positions (kw = 2
+    // of one output, kw = 0 of the next) are re-read a slab or two later -- out of L1 / L2 instead of HBM
+    auto conv_kxk = [&](const char* wname, const char* bname, int ks, float** wd, float** bd) -> int {
+        const int kk = ks * ks;
+        CHK(get(e, wname, {d, d, ks, ks}, &t));
+        std::vector<float> w((size_t)d * kk * d);
         for (int co = 0; co < d; ++co)
             for (int ci = 0; ci < d; ++ci)
-                for (int k = 0; k < 9; ++k)
-                    w[(size_t)co * 9 * d + (size_t)(ci / 32) * 9 * 32 + k * 32 + ci % 32] = t->v[((size_t)co * d + ci) * 9 + k];
-        CHK(upload(e, w, &e->conv2_w));
-        CHK(up(e, "encoder.embed.conv.2.bias", {d}, &e->conv2_b));
-    }
-    {   // embed.out.0 [d][c*F2+f] -> [d][f*d + c]   (subsampling.py:110 flattens channel-major)
-        CHK(get(e, "encoder.embed.out.0.weight", {d, (int64_t)d * F2}, &t));
+                for (int k = 0; k < kk; ++k)
+                    w[(size_t)co * kk * d + (size_t)(ci / 32) * kk * 32 + k * 32 + ci % 32] = t->v[((size_t)co * d + ci) * kk + k];
+        CHK(upload(e, w, wd));
+        return up(e, bname, {d}, bd);
+    };
+    CHK(conv_kxk("encoder.embed.conv.2.weight", "encoder.embed.conv.2.bias", il == IL_CONV2D6 ? 5 : 3, &e->conv2_w, &e->conv2_b));
+    if (il == IL_CONV2D8) CHK(conv_kxk("encoder.embed.conv.4.weight", "encoder.embed.conv.4.bias", 3, &e->conv3_w, &e->conv3_b));
+    {   // embed.out.0 (conv2d) / embed.linear (conv2d6, conv2d8) [d][c*F2+f] -> [d][f*d + c]   (subsampling.py:110, 151, 206
+        // flatten channel-major)
+        const std::string lin = il == IL_CONV2D ? "encoder.embed.out.0" : "encoder.embed.linear";
+        if (il != IL_CONV2D && e->host.count("encoder.embed.out.0.weight"))
+            return fail("input_layer conv2d6 / conv2d8 but the checkpoint holds encoder.embed.out.0 (a conv2d front-end)");
+        if (il == IL_CONV2D && e->host.count("encoder.embed.linear.weight"))
+            return fail("input_layer conv2d but the checkpoint holds encoder.embed.linear (a conv2d6 / conv2d8 front-end)");
+        if (il != IL_CONV2D8 && e->host.count("encoder.embed.conv.4.weight"))
+            return fail("the checkpoint holds a third subsampling conv (encoder.embed.conv.4, conv2d8) but input_layer is not conv2d8");
+        CHK(get(e, lin + ".weight", {d, (int64_t)d * F2}, &t));
         std::vector<float> w((size_t)d * d * F2);
         for (int o = 0; o < d; ++o)
             for (int c = 0; c < d; ++c)
                 for (int f = 0; f < F2; ++f) w[(size_t)o * d * F2 + f * d + c] = t->v[(size_t)o * d * F2 + c * F2 + f];
         CHK(upload(e, w, &e->embed_w));
-        CHK(up(e, "encoder.embed.out.0.bias", {d}, &e->embed_b));
+        CHK(up(e, lin + ".bias", {d}, &e->embed_b));
     }
     {   // positional table (conformer/embedding.py:31-37)
         auto it = e->host.find("__pos_table__");
@@ -1190,56 +1216,96 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
 
 static int g_hot_weights = 0;      // masr_debug_set key 19 (timing experiment only): every chunk-step layer runs on layer 0's weights
 static int g_embed_split = 1;      // masr_debug_set key 15: 0 = the offline embed projection never splits K
-// feats [nseq, T, 80] -> x [nseq*Tq, d] (embed incl. x*sqrt(d))
-int embed(masr_engine* e, hipStream_t s, const float* feats, int nseq, int T, int* Tq_out, const int* skip_lens = nullptr) {
-    const int d = e->cfg.d_model, F = e->cfg.n_mels, F1 = (F - 1) / 2, F2 = (F1 - 1) / 2;
-    const int T1 = (T - 1) / 2, Tq = (T1 - 1) / 2;
-    if (T < 7 || Tq <= 0) return fail("input too short for Conv2dSubsampling4 (need >= 7 frames)");
-    const int M = nseq * Tq;
-    CHK(e->x2.ensure((size_t)M * F2 * d * sizeof(float)));
-    CHK(e->x.ensure((size_t)M * d * sizeof(float)));
-    {
-        GemmArgs a{};
-        a.W = e->conv2_w; a.bias = e->conv2_b; a.C = e->x2.as<float>();
-        a.M = M * F2; a.N = d; a.K = 9 * d; a.ldc = d; a.act = ACT_RELU; a.alpha = 1.f;
-        a.T1 = T1; a.F1 = F1; a.T2 = Tq; a.F2 = F2; a.Cc = d;
-        if (skip_lens) { a.lens = skip_lens; a.skip_rps = Tq * F2; a.skip_div = F2; }      // tiles of padded frames only: not computed
-        const int tiles = ((a.M + 63) / 64) * ((a.N + 63) / 64);
-        if (tiles >= 640 && g_conv2_rows && a.N == 256) {   // full-width row blocks: the weights in the kernel's fragment order, packed at first use
-            auto it = e->conv2_packed.find(e->conv2_w);
-            if (it == e->conv2_packed.end()) {
-                std::pair<DevBuf, DevBuf> pk;
-                CHK(pk.first.ensure((size_t)a.N * a.K * sizeof(float)));
-                launch_pack_conv2_rows(e->conv2_w, pk.first.as<float>(), a.K, s);
-                it = e->conv2_packed.emplace(e->conv2_w, pk).first;
-            }
-            a.Wp = it->second.first.as<float>();
-            if (g_conv1_fused && !g_bf16x3 && gemm_conv2_rows(a)) {    // conv1 computed in the row blocks' A gather: no x1, no conv1 launch
-                a.feats = feats; a.mean = e->cmvn_mean; a.istd = e->cmvn_istd; a.c1w = e->conv1_w; a.c1b = e->conv1_b;
-                a.Tin = T; a.Fin = F;
-            }
+// one subsampling conv over channels-last activations as an implicit GEMM (a: geometry, C, lens; amode A_CONV2 / A_CONV5):
+// full-width row blocks with the weights packed at first use, split K for few rows.  feats [nseq, a.Tin, n_mels] given: the
+// conv reads conv1's output (computed in the row blocks' gather, or by conv1 into x1 first); else it reads x_in.
+static int subsampling_conv(masr_engine* e, hipStream_t s, GemmArgs a, int amode, int nseq, const float* feats, const float* x_in) {
+    const int d = e->cfg.d_model;
+    const int tiles = ((a.M + 63) / 64) * ((a.N + 63) / 64);
+    if (tiles >= 640 && g_conv2_rows && a.N == 256) {   // full-width row blocks: the weights in the kernel's fragment order, packed at first use
+        auto it = e->conv2_packed.find(a.W);
+        if (it == e->conv2_packed.end()) {
+            std::pair<DevBuf, DevBuf> pk;
+            CHK(pk.first.ensure((size_t)a.N * a.K * sizeof(float)));
+            launch_pack_conv2_rows(a.W, pk.first.as<float>(), a.K, s);
+            it = e->conv2_packed.emplace(a.W, pk).first;
         }
-        if (!a.feats) {
-            CHK(e->x1.ensure((size_t)nseq * T1 * F1 * d * sizeof(float)));
-            launch_conv1(feats, e->cmvn_mean, e->cmvn_istd, e->conv1_w, e->conv1_b, e->x1.as<float>(), nseq, T, F, d, s);
-            a.A = e->x1.as<float>();
-        }
-        ProfScope ps(e, s, PROF_CONV2, 2.0 * a.M * (double)a.N * a.K);
-        if (g_bf16x3 && tiles >= 640 && launch_gemm_bf16x3(a, A_CONV2, s)) {
-            // exploratory split-bf16 mode
-        } else if (tiles < 640) {
-            // streaming chunk steps: ~1 workgroup of 4 waves per CU leaves the load -> LDS -> MFMA chain of every 32-wide K slab
-            // exposed (2.5 us per slab, 72 slabs); split K so that ~4-5 workgroups per CU overlap each other's latencies
-            const int nsplit = std::min(8, std::max(2, 1280 / tiles));
-            CHK(e->ffpart.ensure((size_t)nsplit * a.M * a.N * sizeof(float)));
-            launch_gemm_splitk(a, e->ffpart.as<float>(), nsplit, s, A_CONV2);
-        } else {
-            launch_gemm(a, A_CONV2, EPI_STD, s);
+        a.Wp = it->second.first.as<float>();
+        if (feats && amode == A_CONV2 && g_conv1_fused && !g_bf16x3 && gemm_conv2_rows(a)) {    // conv1 computed in the row blocks' A gather: no x1, no conv1 launch
+            a.feats = feats; a.mean = e->cmvn_mean; a.istd = e->cmvn_istd; a.c1w = e->conv1_w; a.c1b = e->conv1_b;
+            a.Fin = e->cfg.n_mels;
         }
     }
+    if (!a.feats) {
+        if (feats) {        // conv1 as its own launch into x1
+            CHK(e->x1.ensure((size_t)nseq * a.T1 * a.F1 * d * sizeof(float)));
+            launch_conv1(feats, e->cmvn_mean, e->cmvn_istd, e->conv1_w, e->conv1_b, e->x1.as<float>(), nseq, a.Tin, e->cfg.n_mels,
+                         d, s);
+            a.A = e->x1.as<float>();
+        } else {
+            a.A = x_in;
+        }
+    }
+    ProfScope ps(e, s, PROF_CONV2, 2.0 * a.M * (double)a.N * a.K);
+    if (g_bf16x3 && amode == A_CONV2 && tiles >= 640 && launch_gemm_bf16x3(a, A_CONV2, s)) {
+        // exploratory split-bf16 mode
+    } else if (tiles < 640) {
+        // streaming chunk steps: ~1 workgroup of 4 waves per CU leaves the load -> LDS -> MFMA chain of every 32-wide K slab
+        // exposed (2.5 us per slab, 72 slabs); split K so that ~4-5 workgroups per CU overlap each other's latencies
+        const int nsplit = std::min(8, std::max(2, 1280 / tiles));
+        CHK(e->ffpart.ensure((size_t)nsplit * a.M * a.N * sizeof(float)));
+        launch_gemm_splitk(a, e->ffpart.as<float>(), nsplit, s, amode);
+    } else {
+        launch_gemm(a, amode, EPI_STD, s);
+    }
+    return 0;
+}
+
+// device lengths in conv2d units for the conv2d6 / conv2d8 front-ends (nullptr in, or conv2d: lens itself).  The encoder's kernels
+// treat frame t of a sequence as padding when mstride * t >= lens (mstride 4 at the conv2d rate); with rate r the reference keeps
+// frame t iff r * t < len, i.e. iff t < ceil(len / r) -- the same test on 4 * ceil(len / r)
+static const int* sub_lens(masr_engine* e, hipStream_t s, const int* lens, int B) {
+    if (!lens || e->input_layer == IL_CONV2D || B <= 0) return lens;
+    if (e->sublens.ensure(sizeof(int) * B)) return nullptr;
+    launch_sub_lens(lens, B, sub_rate(e->input_layer), e->sublens.as<int>(), s);
+    return e->sublens.as<int>();
+}
+
+// feats [nseq, T, 80] -> x [nseq*Tq, d] (embed incl. x*sqrt(d)).  skip_lens: lengths in conv2d units (sub_lens)
+int embed(masr_engine* e, hipStream_t s, const float* feats, int nseq, int T, int* Tq_out, const int* skip_lens = nullptr) {
+    const int il = e->input_layer, d = e->cfg.d_model, F = e->cfg.n_mels, F1 = (F - 1) / 2, F2 = sub_bins(il, F);
+    const int T1 = (T - 1) / 2, Tq = sub_frames(il, T);
+    if (T < sub_min_frames(il) || Tq <= 0)
+        return fail("input too short for the subsampling front-end (need >= " + std::to_string(sub_min_frames(il)) + " frames)");
+    // conv2d8: the second conv runs as conv2d's (19 bins, T1 -> (T1 - 1) / 2 frames), the third on its output
+    const int Fc = il == IL_CONV2D8 ? (F1 - 1) / 2 : F2, Tc = il == IL_CONV2D8 ? (T1 - 1) / 2 : Tq;
+    const int M = nseq * Tq;
+    CHK(e->x2.ensure((size_t)nseq * Tc * Fc * d * sizeof(float)));
+    CHK(e->x.ensure((size_t)M * d * sizeof(float)));
+    {
+        const int ks = il == IL_CONV2D6 ? 5 : 3;
+        GemmArgs a{};
+        a.W = e->conv2_w; a.bias = e->conv2_b; a.C = e->x2.as<float>();
+        a.M = nseq * Tc * Fc; a.N = d; a.K = ks * ks * d; a.ldc = d; a.act = ACT_RELU; a.alpha = 1.f;
+        a.T1 = T1; a.F1 = F1; a.T2 = Tc; a.F2 = Fc; a.Cc = d; a.Tin = T;
+        // tiles of padded frames only: not computed (conv2d8: on the last conv only -- the padding of its input is read).  Only the
+        // Squeezeformer passes skip_lens today, always conv2d: the conv2d6 / conv2d8 cases are kept exact but are not reached
+        if (skip_lens && il != IL_CONV2D8) { a.lens = skip_lens; a.skip_rps = Tc * Fc; a.skip_div = Fc; }
+        CHK(subsampling_conv(e, s, a, il == IL_CONV2D6 ? A_CONV5 : A_CONV2, nseq, feats, nullptr));
+    }
+    if (il == IL_CONV2D8) {     // third conv: 3x3 stride 2 over the second one's output [nseq, Tc, 19, d]
+        CHK(e->x3.ensure((size_t)M * F2 * d * sizeof(float)));
+        GemmArgs a{};
+        a.W = e->conv3_w; a.bias = e->conv3_b; a.C = e->x3.as<float>();
+        a.M = M * F2; a.N = d; a.K = 9 * d; a.ldc = d; a.act = ACT_RELU; a.alpha = 1.f;
+        a.T1 = Tc; a.F1 = Fc; a.T2 = Tq; a.F2 = F2; a.Cc = d;
+        if (skip_lens) { a.lens = skip_lens; a.skip_rps = Tq * F2; a.skip_div = F2; }
+        CHK(subsampling_conv(e, s, a, A_CONV2, nseq, nullptr, e->x2.as<float>()));
+    }
+    const float* const xs = il == IL_CONV2D8 ? e->x3.as<float>() : e->x2.as<float>();
     {   // Conformer: (W.x + b) * sqrt(d)  (embedding.py:97);  Squeezeformer: W.(x * sqrt(d)) + b  (subsampling.py:72-75)
         GemmArgs a{};
-        a.A = e->x2.as<float>(); a.lda = F2 * d; a.W = e->embed_w; a.bias = e->embed_b; a.C = e->x.as<float>(); a.ldc = d;
+        a.A = xs; a.lda = F2 * d; a.W = e->embed_w; a.bias = e->embed_b; a.C = e->x.as<float>(); a.ldc = d;
         a.M = M; a.N = d; a.K = F2 * d; a.act = ACT_NONE; a.alpha = sqrtf((float)d);
         a.bias_after_alpha = e->cfg.model_kind == 1 ? 1 : 0;
         if (skip_lens) { a.lens = skip_lens; a.skip_rps = Tq; a.skip_div = 1; }
@@ -1979,6 +2045,9 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
     // decoding_chunk_size > 0 limits the attention to chunks in the streaming-trained builds only (use_dynamic_chunk follows
     // `streaming`, model.py of every family; utils/mask.py:117-143 ignores it otherwise)
     const int chunk = (decoding_chunk_size > 0 && e->cfg.causal) ? decoding_chunk_size : 0;
+    // conv2d6 / conv2d8: every mask below tests 4 * t against the lengths in conv2d units
+    if (feat_lens_dev && e->input_layer != IL_CONV2D && !(feat_lens_dev = sub_lens(e, s, feat_lens_dev, B)))
+        return fail("out of device memory (subsampled lengths)");
     if (e->cfg.model_kind == 1) return encode_full_squeezeformer(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
     if (e->cfg.model_kind == 2) return encode_full_efficient(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
     const int d = e->cfg.d_model, H = e->cfg.heads, pad = e->cfg.cnn_kernel - 1;
@@ -2434,7 +2503,7 @@ static int transcribe_impl(masr_engine* e, const void* samples_dev, int32_t fmt,
     if (n_max < 400) return fail("n_max < 400 samples: no frame");
     hipStream_t s = (hipStream_t)stream;
     const int d = enc_dim(e), F = e->cfg.n_mels;
-    const int T = 1 + (n_max - 400) / 160, T1 = (T - 1) / 2, Tsub = (T1 - 1) / 2;
+    const int T = 1 + (n_max - 400) / 160, Tsub = sub_frames(e->input_layer, T);
     const bool halved = e->cfg.model_kind == 2 && e->stride_idx >= 0;      // efficient conformer: one more stride-2 stage
     const int Tq = halved ? (Tsub + 1) / 2 : Tsub;
     if (Tsub <= 0) return fail("utterances too short");
@@ -2449,7 +2518,7 @@ static int transcribe_impl(masr_engine* e, const void* samples_dev, int32_t fmt,
     CHK(masr_fbank_batch(e, samples_dev, fmt, n_samples_dev, B, n_max, use_db_normalization, target_db,
                          e->feats.as<float>(), nullptr, nullptr, use_db_normalization == 2 ? const_cast<float*>(gain_dev) : nullptr,
                          stream));
-    launch_frame_counts(n_samples_dev, B, nfr, nenc, halved ? 1 : 0, s);
+    launch_frame_counts(n_samples_dev, B, nfr, nenc, halved ? 1 : 0, s, e->input_layer);
     {
         // decode_all_frames: the padded frames are decoded too (the reference's batch evaluation, trainer.py:340) -- then they
         // must be computed, whatever masr_debug_set key 38 says
@@ -2581,9 +2650,9 @@ int masr_stream_set_history(masr_engine* e, int32_t stream_id, int32_t required_
 
 int masr_encoder_frames(masr_engine* e, int32_t feature_frames, int32_t* encoder_frames) {
     if (!e || !encoder_frames) return fail("null argument");
-    const int T1 = (feature_frames - 1) / 2, Tsub = (T1 - 1) / 2;
+    const int Tsub = sub_frames(e->input_layer, feature_frames);
     const bool halved = e->cfg.model_kind == 2 && e->stride_idx >= 0;
-    *encoder_frames = feature_frames < 7 ? 0 : (halved ? (Tsub + 1) / 2 : Tsub);
+    *encoder_frames = halved ? (Tsub + 1) / 2 : Tsub;
     return 0;
 }
 
@@ -2776,6 +2845,13 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
                                   float* probs_dev, int32_t* argmax_dev, float* maxprob_dev) {
     const int n = (int)st.size();
     const int d = e->cfg.d_model, H = e->cfg.heads, L = e->cfg.num_blocks, G = e->group_size;
+    // conv2d8 gives 7 frames per 67-frame window: the half-rate layers' caches of an odd chunk do not line up with the next
+    // chunk's positions, and the reference's chunk forward fails there (a size mismatch in the attention scores).  conv2d keeps
+    // its behaviour (only a short last chunk is odd); conv2d6 gives 10 frames per window.
+    for (int i = 0; i < n; ++i)
+        if (e->input_layer != IL_CONV2D && st[i]->offset % 2 != 0)
+            return fail("efficient_conformer: a chunk after one of an odd number of encoder frames (conv2d8: 7 per 67-frame window) "
+                        "is not defined by the reference; use conv2d or conv2d6 for chunked streaming");
     int T0 = 0;
     CHK(embed(e, s, feats, n, Tc, &T0));
     const int T2 = (T0 + 1) / 2, Tg = (T0 + G - 1) / G, Tpad = Tg * G;

@@ -8,9 +8,9 @@
 //   (row = lane&31, 16-byte column = lane>>5) are bank-conflict free (row stride 144 B = 9 slots).
 // * Fragment trick: MFMA sums over k in any order, so lane half h=(lane>>5) takes the 4 consecutive
 //   k values {8g+4h .. 8g+4h+3} of each 8-wide k group with ONE 16-byte LDS read for A and for W.
-// * A operand modes: plain row-major, or implicit-GEMM gather for the 3x3/stride-2 subsampling
-//   conv over channels-last activations (reference conformer/subsampling.py:86-110), K ordered
-//   [32-channel block][kh][kw][channel] so that overlapping window columns are re-read while still cached.
+// * A operand modes: plain row-major, or implicit-GEMM gather for the subsampling convs over channels-last
+//   activations (reference conformer/subsampling.py:86-211): 3x3 stride 2 (A_CONV2) or 5x5 stride 3 (A_CONV5, conv2d6),
+//   K ordered [32-channel block][kh][kw][channel] so that overlapping window columns are re-read while still cached.
 // * Epilogue: bias, ReLU/SiLU, alpha, residual, row masking.  (The K = 256 projections of the layers use
 //   rowgemm.hip, the FFN ffn_pc.hip; this kernel serves conv2, the embed projection, the positional-key
 //   precompute and the full-probability CTC head; the large offline conv2 runs on conv2_rows_kernel below.)
@@ -27,9 +27,14 @@ __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf
 // EPI_SPLITK: blockIdx.y owns a contiguous range of K slabs and stores its raw partial tile to p.C + blockIdx.y*M*ldc
 // (p.ksplit slabs per range); splitk_reduce_kernel applies the epilogue.  For M so small that the tile grid cannot fill
 // the chip while K is deep (embed projection of a streaming chunk step: M = 256, K = 4864).
+// implicit-GEMM window of an A mode: KS x KS taps at stride S (A_CONV2: 3x3 stride 2, A_CONV5: 5x5 stride 3)
+__host__ __device__ constexpr int conv_ks(int amode) { return amode == A_CONV5 ? 5 : 3; }
+__host__ __device__ constexpr int conv_stride(int amode) { return amode == A_CONV5 ? 3 : 2; }
+
 template <int BM, int BN, int WM, int WN, int AMODE, int EPI>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(GemmArgs p) {
     static_assert(WM * WN == 4 || WM * WN == 8, "4 or 8 waves");
+    constexpr int KS = conv_ks(AMODE), S = conv_stride(AMODE);
     constexpr int NT = 64 * WM * WN;
     constexpr int RPP = NT / 8;   // slab rows staged per pass of the workgroup (8 threads x float4 per 32-wide row)
     constexpr int TM = BM / WM / 32;
@@ -80,7 +85,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(GemmArgs p) {
             const int bt = mm / p.F2;
             const int t2 = bt % p.T2;
             const int b = bt / p.T2;
-            aptr[i] = p.A + (((size_t)b * p.T1 + 2 * t2) * p.F1 + 2 * f2) * p.Cc + lc4;
+            aptr[i] = p.A + (((size_t)b * p.T1 + S * t2) * p.F1 + S * f2) * p.Cc + lc4;
         }
     }
     const float* wptr[WL];
@@ -99,9 +104,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(GemmArgs p) {
             aoff = (size_t)kt * BK;
         } else {
             // K is ordered [channel block of 32][kh][kw][32 channels] (weights re-laid out at load): slab kt = window position
-            // kt % 9 of channel block kt / 9
-            const int cb = kt / 9, pos = kt - 9 * cb;
-            const int kh = pos / 3, kw = pos - 3 * kh;
+            // kt % KS^2 of channel block kt / KS^2
+            const int cb = kt / (KS * KS), pos = kt - KS * KS * cb;
+            const int kh = pos / KS, kw = pos - KS * kh;
             aoff = ((size_t)kh * p.F1 + kw) * p.Cc + (size_t)cb * BK;
         }
 #pragma unroll
@@ -226,7 +231,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(GemmArgs p) {
 // MFMA s) from zero, then the same epilogue.
 //
 // A operand modes (template AM):
-// * RB_X1: the implicit-GEMM gather from the conv1 output x1 [B, T1, F1, 256] (written by conv1_kernel, elementwise.hip).
+// * RB_X1: the implicit-GEMM gather from the conv1 output x1 [B, T1, F1, 256] (written by conv1_kernel, elementwise.hip), or
+//   from any channels-last [B, T1, F1, 256] activation: KS x KS window at stride S (template <KS, S>: <3, 2> for conv2 and
+//   conv2d8's third conv, <5, 3> for conv2d6's second conv), slab kt = window position kt % KS^2 of channel block kt / KS^2.
 // * RB_FUSED (masr_debug_set key 41): conv1 is computed in the gather, and x1 never exists.  At block start the CMVN-normalised
 //   7 x 7 feature patch of every row (frames 4 t2 .. 4 t2 + 6, mel bins 4 f2 .. 4 f2 + 6) and the conv1 weights + bias go to LDS
 //   (12.25 + 10 KB).  Thread (row lrow, channels 32 cb + lc4 .. + 3) computes slab (cb, kh, kw) as the conv1 output at
@@ -248,8 +255,9 @@ __device__ __forceinline__ f32x4 rb_bufld(__amdgpu_buffer_rsrc_t rs, unsigned la
 // RB_FUSED: first conv1 tap of MFMA group g (taps [rb_tap(g), rb_tap(g + 1)) follow group g's MFMAs)
 __device__ constexpr int rb_tap(int g) { return g == 0 ? 0 : g == 1 ? 2 : g == 2 ? 4 : g == 3 ? 6 : 9; }
 
-template <int AM>
+template <int AM, int KS = 3, int S = 2>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void conv2_rows_kernel(GemmArgs p) {
+    static_assert(AM != RB_FUSED || (KS == 3 && S == 2), "conv1 in the gather: 3x3 stride 2 only");
     constexpr int XS = AM == RB_FUSED ? 10 * RB_N + RB_BM * RB_PP : 4;      // conv1 weights [9][256] + bias [256], patches [64][49]
     __shared__ __align__(16) float As[2][RB_BM * LDP];
     __shared__ __align__(16) float Xs[XS];
@@ -278,7 +286,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
     if (AM == RB_X1) {
         const int mm = aok ? bm + lrow : 0;
         const int f2 = mm % p.F2, bt = mm / p.F2, t2 = bt % p.T2, b = bt / p.T2;
-        aptr = p.A + (((size_t)b * p.T1 + 2 * t2) * p.F1 + 2 * f2) * p.Cc + lc4;
+        aptr = p.A + (((size_t)b * p.T1 + S * t2) * p.F1 + S * f2) * p.Cc + lc4;
     } else if (AM == RB_PLAIN) {
         aptr = p.A + (size_t)(aok ? bm + lrow : 0) * p.lda + lc4;
     }
@@ -287,8 +295,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
         if (AM == RB_PLAIN) {
             aoff = (size_t)kt * BK;
         } else {
-            const int cb = kt / 9, pos = kt - 9 * cb;       // K order [channel block of 32][kh][kw][32 channels]
-            const int kh = pos / 3, kw = pos - 3 * kh;
+            const int cb = kt / (KS * KS), pos = kt - KS * KS * cb;       // K order [channel block of 32][kh][kw][32 channels]
+            const int kh = pos / KS, kw = pos - KS * kh;
             aoff = ((size_t)kh * p.F1 + kw) * p.Cc + (size_t)cb * BK;
         }
         return aok ? *reinterpret_cast<const f32x4*>(aptr + aoff) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -456,7 +464,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
     }
 }
 
-// W [256, K] (K order of the implicit GEMM) -> conv2_rows_kernel's layout [wave][kt][g][lane][4]:
+// W [256, K] (K order of the implicit GEMM, any window: K = KS^2 * 256 or a plain K) -> conv2_rows_kernel's layout [wave][kt][g][lane][4]:
 //   P = W[32 wave + (lane & 31)][32 kt + 8 g + 4 (lane >> 5) + q]
 __global__ __launch_bounds__(256) void pack_conv2_rows_kernel(const float* __restrict__ w, float* __restrict__ p, int K) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -525,6 +533,15 @@ void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) return;
     if (amode == A_CONV2 && epi == EPI_SPLITK) {      // caller set a.C = partial buffer, a.nsplit, a.ksplit
         launch_t<64, 64, 2, 2, A_CONV2, EPI_SPLITK>(a, s);
+        return;
+    }
+    if (amode == A_CONV5) {       // conv2d6's 5x5 stride-3 conv: the conv2 launch shapes with the wider window (never conv1 in the gather)
+        if (epi == EPI_SPLITK) launch_t<64, 64, 2, 2, A_CONV5, EPI_SPLITK>(a, s);
+        else if (conv2_tiles(a) == 64) launch_t<64, 64, 2, 2, A_CONV5, EPI_STD>(a, s);
+        else if (conv2_tiles(a) == 128) launch_t<64, 128, 2, 2, A_CONV5, EPI_STD>(a, s);
+        else if (conv2_tiles(a) == 0)
+            hipLaunchKernelGGL((conv2_rows_kernel<RB_X1, 5, 3>), dim3((unsigned)((a.M + RB_BM - 1) / RB_BM)), dim3(512), 0, s, a);
+        else launch_t<128, 128, 2, 4, A_CONV5, EPI_STD>(a, s);
         return;
     }
     if (amode == A_CONV2) {

@@ -26,6 +26,7 @@
 
 using namespace masr;
 namespace masr {
+int subsampled_frames(const masr_engine* e, int feature_frames);     // engine.hip: frames behind the subsampling front-end
 int engine_fail(const std::string& m);
 }
 
@@ -334,7 +335,7 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
                 const int left = end_flag[i] ? kContext : kWindow;
                 for (int cur = 0; cur <= nfr - left; cur += kStride) {
                     const int len = std::min(cur + kWindow, nfr) - cur;
-                    emit += ((len - 1) / 2 - 1) / 2;
+                    emit += subsampled_frames(p->e, len);       // (the unit of masr_stream_room: before any stride layer)
                 }
             }
             int32_t room = 0;
@@ -547,7 +548,11 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
             const PoolSeg *dg = nullptr, *ds = nullptr;
             PCHK(push_segments(gat, &dg));
             launch_copy_segments(p->feat.as<float>(), p->win.as<float>(), nullptr, nullptr, dg, m, len, p->F, s);
-            PCHK(masr_encode_chunk(p->e, ids.data(), m, p->win.as<float>(), len, nullptr, p->idx.as<int32_t>(), p->mp.as<float>(), stream));
+            // (a last window shorter than the front-end's minimum -- 8-14 frames under conv2d8, 7-10 under conv2d6 -- gives no
+            // encoder frame: nothing to run, where the reference's conv would refuse the input)
+            if (tq > 0)
+                PCHK(masr_encode_chunk(p->e, ids.data(), m, p->win.as<float>(), len, nullptr, p->idx.as<int32_t>(), p->mp.as<float>(),
+                                       stream));
             if (tq > 0) {
                 PCHK(push_segments(sca, &ds));
                 launch_copy_segments(reinterpret_cast<const float*>(p->idx.p), p->hist_idx.as<float>(), p->mp.as<float>(),

@@ -28,8 +28,21 @@ def positional_table(max_len, d):
     return pe
 
 
-def subsampled_len(t):
-    return ((t - 1) // 2 - 1) // 2
+# encoder_conf.input_layer -> masr_config.reserved[3] (include/masr_hip.h): Conv2dSubsampling4 / 6 / 8 (conformer/subsampling.py)
+INPUT_LAYERS = {'conv2d': 0, 'conv2d6': 1, 'conv2d8': 2}
+# the fewest feature frames that give one encoder frame
+MIN_FRAMES = {'conv2d': 7, 'conv2d6': 11, 'conv2d8': 15}
+
+
+def subsampled_len(t, input_layer='conv2d'):
+    """encoder frames for t feature frames (int, array or tensor): conv1 3x3 stride 2, then 3x3 stride 2 (conv2d), 5x5 stride 3
+    (conv2d6) or 3x3 stride 2 twice (conv2d8), none padded.  Below the minimum the result is <= 0."""
+    t1 = (t - 1) // 2
+    if input_layer == 'conv2d6':
+        return (t1 - 2) // 3
+    if input_layer == 'conv2d8':
+        return ((t1 - 1) // 2 - 1) // 2
+    return (t1 - 1) // 2
 
 
 def reference_gains_scalar(mean_square, target_db, max_gain_db=300.0):
@@ -90,7 +103,7 @@ def _validate_encoder_conf(use_model, enc, state_dict):
         want('normalize_before', (True,), True)
         want('use_cnn_module', (True,), True)
         want('macaron_style', (True,), True)
-        want('input_layer', ('conv2d',), 'conv2d')
+        want('input_layer', tuple(INPUT_LAYERS), 'conv2d')
         want('pos_enc_layer_type', ('rel_pos',), 'rel_pos')
         has_bn = state_dict is not None and any(k.endswith('conv_module.norm.running_mean') for k in state_dict)
         is_bn = enc.get('cnn_module_norm', 'layer_norm') == 'batch_norm'
@@ -126,6 +139,8 @@ class HipEngine:
         self.device = torch.device('cuda', device)
         torch.cuda.set_device(self.device)
         _validate_encoder_conf(use_model, enc, state_dict)
+        # subsampling front-end (Conformer / Efficient Conformer; the other models have their own)
+        self.input_layer = enc.get('input_layer', 'conv2d') if use_model in ('conformer', 'efficient_conformer') else 'conv2d'
         if use_model == 'conformer':
             cfg = MasrConfig(model_kind=0, d_model=int(enc.get('output_size', 256)),
                              heads=int(enc.get('attention_heads', 4)), d_ff=int(enc.get('linear_units', 2048)),
@@ -134,6 +149,7 @@ class HipEngine:
                              vocab_size=int(vocab_size), causal=1 if streaming else 0, max_pos=max_pos,
                              device_id=device)
             cfg.reserved[0] = 1 if enc.get('cnn_module_norm', 'layer_norm') == 'batch_norm' else 0
+            cfg.reserved[3] = INPUT_LAYERS[self.input_layer]
         elif use_model == 'squeezeformer':
             # configs/squeezeformer.yml: encoder_dim, feed_forward_expansion_factor, reduce_idx / recover_idx
             dim = int(enc.get('encoder_dim', 256))
@@ -166,6 +182,7 @@ class HipEngine:
             cfg.reserved[0] = int(stride_idx[0])
             cfg.reserved[1] = len(groups)
             cfg.reserved[2] = int(eff.get('group_size', 3))
+            cfg.reserved[3] = INPUT_LAYERS[self.input_layer]
         elif use_model == 'deepspeech2':
             # configs/deepspeech2.yml encoder_conf: rnn_size, num_rnn_layers; streaming <=> uni-directional LSTMs
             # (deepspeech2/encoder.py:14-19: rnn_direction = 'forward' if streaming else 'bidirect')
@@ -370,13 +387,18 @@ class HipEngine:
 
     def out_frames(self, T):
         """encoder output frames for T feature frames (the Efficient Conformer halves the rate once more)."""
-        Tp = subsampled_len(T)
+        Tp = subsampled_len(T, getattr(self, 'input_layer', 'conv2d'))
         return (Tp + 1) // 2 if getattr(self, 'use_model', 'conformer') == 'efficient_conformer' else Tp
+
+    @property
+    def min_frames(self):
+        """the fewest feature frames that give one encoder frame (7 / 11 / 15 for conv2d / conv2d6 / conv2d8)"""
+        return MIN_FRAMES[getattr(self, 'input_layer', 'conv2d')]
 
     def enc_frames(self, feat_frames):
         """valid encoder frames per utterance for its feature frames (tensor or array; mirrors launch_frame_counts in
-        elementwise.hip: Conv2dSubsampling4, once more halved with ceil by the Efficient Conformer's stride layer)."""
-        n4 = ((feat_frames - 1) // 2 - 1) // 2
+        elementwise.hip: Conv2dSubsampling4 / 6 / 8, once more halved with ceil by the Efficient Conformer's stride layer)."""
+        n4 = subsampled_len(feat_frames, getattr(self, 'input_layer', 'conv2d'))
         n4 = n4.clamp(min=0) if torch.is_tensor(n4) else np.maximum(n4, 0)
         return (n4 + 1) // 2 if self.use_model == 'efficient_conformer' else n4
 

@@ -279,8 +279,9 @@ class MASRPredictor:
         for s in segs:
             if s.sample_rate != rate:
                 s.resample(rate)
-        # 7 feature frames is the least Conv2dSubsampling4 accepts (subsampling.py:65-112)
-        ok = [i for i, s in enumerate(segs) if s.num_samples >= min_samples + 6 * 160]
+        # 7 / 11 / 15 feature frames is the least Conv2dSubsampling4 / 6 / 8 accepts (subsampling.py:65-211)
+        min_frames = getattr(self.predictor.engine, 'min_frames', 7)
+        ok = [i for i, s in enumerate(segs) if s.num_samples >= min_samples + (min_frames - 1) * 160]
         live = [segs[i] for i in ok]
         n = np.array([s.num_samples for s in live], np.int32)
         return {'count': len(segs), 'ok': ok, 'n': n, 'min_samples': min_samples,

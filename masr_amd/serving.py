@@ -91,7 +91,7 @@ class _HostStage:
 
 
 class _Session:
-    __slots__ = ('sid', 'remained', 'fresh', 'f0', 'nf', 'row', 'frames', 'result', 'decoder', 'tokens')
+    __slots__ = ('sid', 'remained', 'fresh', 'f0', 'nf', 'row', 'frames', 'result', 'decoder', 'tokens', 'beam_last')
 
     def __init__(self, sid, row, decoder=None):
         self.sid = sid
@@ -104,6 +104,7 @@ class _Session:
         self.result = None
         self.decoder = decoder        # ctc_beam_search: this session's own search state
         self.tokens = []              # token ids of the last partial result
+        self.beam_last = None         # beam search: the last decode_chunk result (what a step without a window returns)
 
 
 class StreamPool:
@@ -455,6 +456,11 @@ class StreamPool:
                 if k < len(p):
                     groups.setdefault(p[k][1] - p[k][0], []).append((s, p[k]))
             for length, items in groups.items():          # full windows together; a short last window on its own
+                if eng.out_frames(length) <= 0:           # a last window below the front-end's minimum (conv2d6 / conv2d8): no frame
+                    if self.beam:                         # nothing new to decode: the transcript so far (greedy re-collapses below)
+                        for s, _ in items:
+                            s.result = s.beam_last
+                    continue
                 # the windows are gathered from the device-resident feature pool: [items, length] flat frame indices
                 base = np.array([s.row * self._feat_cap + s.f0 + a for s, (a, _) in items], np.int64)
                 x = self._feat.view(-1, self.feat_dim)[self._dev_index(base[:, None] + np.arange(length)[None, :])]
@@ -464,7 +470,7 @@ class StreamPool:
                     for i, (s, _) in enumerate(items):
                         score, text = s.decoder.decode_chunk(probs=probs[i:i + 1], logits_lens=[probs.shape[1]])
                         s.frames += probs.shape[1]
-                        s.result = {'text': text, 'score': score}
+                        s.result = s.beam_last = {'text': text, 'score': score}
                         s.tokens = list(s.decoder.last_tokens)
                     continue
                 _, idx, mp = eng.encode_chunk(sids, x, want_probs=False, want_argmax=True)

@@ -22,12 +22,15 @@ def _uniform(seed, name, shape, bound):
 
 
 def conformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, d_ff=2048, num_blocks=12,
-                         kernel=15, n_mels=80, ctc_gain=6.0, cnn_module_norm='layer_norm'):
+                         kernel=15, n_mels=80, ctc_gain=6.0, cnn_module_norm='layer_norm', input_layer='conv2d'):
     """Keys/shapes == reference ``encoder.*`` + ``ctc.*`` entries (attention-decoder
     ``decoder.*`` entries are never used by get_encoder_out*, model.py:152-190).  ``cnn_module_norm='batch_norm'``
-    (conformer/convolution.py:60-67): the conv module's norm carries running statistics (same weight / bias shapes)."""
+    (conformer/convolution.py:60-67): the conv module's norm carries running statistics (same weight / bias shapes).
+    ``input_layer`` 'conv2d6' / 'conv2d8' (conformer/subsampling.py:115-211): a 5x5 second conv, or a third 3x3 conv
+    (``embed.conv.4``), and the projection under ``embed.linear``."""
     sd = {}
-    f2 = ((n_mels - 1) // 2 - 1) // 2
+    f1 = (n_mels - 1) // 2
+    f2 = {'conv2d6': (f1 - 2) // 3, 'conv2d8': ((f1 - 1) // 2 - 1) // 2}.get(input_layer, (f1 - 1) // 2)
 
     def lin(name, out_f, in_f, bias=True, gain=1.0):
         b = gain / math.sqrt(in_f)
@@ -43,9 +46,15 @@ def conformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, d_ff=2048, num
     sd['encoder.global_cmvn.istd'] = 0.3 + _uniform(seed, 'cmvn.istd', (n_mels,), 0.05)
     sd['encoder.embed.conv.0.weight'] = _uniform(seed, 'conv0.w', (d, 1, 3, 3), math.sqrt(3.0 / 9))
     sd['encoder.embed.conv.0.bias'] = _uniform(seed, 'conv0.b', (d,), 0.1)
-    sd['encoder.embed.conv.2.weight'] = _uniform(seed, 'conv2.w', (d, d, 3, 3), math.sqrt(3.0 / (9 * d)))
+    if input_layer == 'conv2d6':
+        sd['encoder.embed.conv.2.weight'] = _uniform(seed, 'conv2.w5', (d, d, 5, 5), math.sqrt(3.0 / (25 * d)))
+    else:
+        sd['encoder.embed.conv.2.weight'] = _uniform(seed, 'conv2.w', (d, d, 3, 3), math.sqrt(3.0 / (9 * d)))
     sd['encoder.embed.conv.2.bias'] = _uniform(seed, 'conv2.b', (d,), 0.1)
-    lin('encoder.embed.out.0', d, d * f2)
+    if input_layer == 'conv2d8':
+        sd['encoder.embed.conv.4.weight'] = _uniform(seed, 'conv4.w', (d, d, 3, 3), math.sqrt(3.0 / (9 * d)))
+        sd['encoder.embed.conv.4.bias'] = _uniform(seed, 'conv4.b', (d,), 0.1)
+    lin('encoder.embed.out.0' if input_layer == 'conv2d' else 'encoder.embed.linear', d, d * f2)
     for i in range(num_blocks):
         p = f'encoder.encoders.{i}.'
         for q in ('linear_q', 'linear_k', 'linear_v', 'linear_out'):
@@ -162,11 +171,11 @@ def squeezeformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, ff_factor=
 
 def efficient_conformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, d_ff=2048, num_blocks=12, kernel=15,
                                    n_mels=80, ctc_gain=6.0, stride_layer_idx=(3,), stride=(2,),
-                                   group_layer_idx=(0, 1, 2, 3), group_size=3):
+                                   group_layer_idx=(0, 1, 2, 3), group_size=3, input_layer='conv2d'):
     """Keys/shapes == reference EfficientConformerModel ``encoder.*`` + ``ctc.*``
     (configs/efficient_conformer.yml: streaming, layer_norm conv module, grouped attention in blocks 0-3,
     strided depthwise conv in block 3, kernel 15 -> 7 afterwards; masr/model_utils/efficient_conformer/)."""
-    sd = conformer_state_dict(seed, vocab_size, d, heads, d_ff, num_blocks, kernel, n_mels, ctc_gain)
+    sd = conformer_state_dict(seed, vocab_size, d, heads, d_ff, num_blocks, kernel, n_mels, ctc_gain, input_layer=input_layer)
     k = kernel
     for i in range(num_blocks):
         p = f'encoder.encoders.{i}.'
