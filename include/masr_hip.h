@@ -40,7 +40,8 @@ typedef struct masr_config {
     int32_t reserved[5];     /* squeezeformer: [0] reduce_idx, [1] recover_idx; efficient_conformer: [0] stride layer, [1] grouped layers,
                                 [2] group size; conformer: [0] = 1 -> cnn_module_norm: batch_norm (convolution.py:60-67; full-context only);
                                 conformer and efficient_conformer: [3] input_layer, 0 = conv2d (x4), 1 = conv2d6 (x6), 2 = conv2d8 (x8)
-                                (conformer/subsampling.py:65-211) */
+                                (conformer/subsampling.py:65-211); deepspeech2 (model_kind 3): [0] recurrent cell, 0 = LSTM,
+                                1 = GRU (encoder_conf.use_gru, deepspeech2/encoder.py:21-33), any other value is refused */
 } masr_config;
 
 const char* masr_last_error(void);
@@ -341,7 +342,8 @@ int masr_resample_f32(const float* x, int64_t n_orig, double ratio, const double
 int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc,
                       float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, void* stream);
 /* Read back a stream's caches in the reference layout (for parity tests):
- * att [L, H, t, 2*dk], cnn [L, 1, d, kernel-1] -- device pointers, t = current offset. */
+ * att [L, H, t, 2*dk], cnn [L, 1, d, kernel-1] -- device pointers, t = current offset.  DeepSpeech2: att <- h [L, rnn_size],
+ * cnn <- c [L, rnn_size]; a GRU stream returns h in both (deepspeech2/gru.py: final_state_c = final_state_h). */
 int masr_stream_export_cache(masr_engine* e, int32_t stream_id, float* att_dev, float* cnn_dev, void* stream);
 
 /* Single kernels, exposed for unit tests and profiling. */

@@ -212,6 +212,7 @@ struct SqLayerW {   // Squeezeformer block (post-LN, adaptive scale/bias, BatchN
 
 struct Ds2LayerW {  // DeepSpeech2 RNN layer: input projection of both directions stacked, recurrent weights, LayerNorm
     float *wih, *bih, *whh, *ln_w, *ln_b;
+    float* bhn = nullptr;   // use_gru: b_hn [ndir][H] (inside the reset-gate product, not folded into bih)
     int kin;
 };
 
@@ -230,7 +231,7 @@ struct Stream {
     int first_half = 0; // half-rate layers (Squeezeformer between reduction and recovery, Efficient-Conformer behind the stride
                         // layer): index of their first kept cache entry (advances by next_cache_start // 2 per step)
     DevBuf att;  // [L][cap][2*d]  (k | v per row)
-    DevBuf cnn;  // [L][kernel-1][d]   (DeepSpeech2: LSTM state [L][2 (h, c)][rnn_size])
+    DevBuf cnn;  // [L][kernel-1][d]   (DeepSpeech2: LSTM state [L][2 (h, c)][rnn_size]; GRU: h in both)
     DevBuf cnn2; // Conformer / Squeezeformer: second half of the double-buffered cnn cache (a chunk step reads `cnn`, writes
                  // `cnn2`, then the two are swapped -- lets one kernel read the history and write the new cache without ordering)
 };
@@ -317,6 +318,7 @@ struct masr_engine : EngineWs {
     int stride_idx = -1, n_group_layers = 0, group_size = 3;   // Efficient-Conformer (model_kind 2)
     int input_layer = IL_CONV2D;     // Conformer / Efficient-Conformer subsampling front-end (cfg.reserved[3], common.h InputLayer)
     bool conv_bn = false;            // Conformer with cnn_module_norm: batch_norm (cfg.reserved[0] = 1): LayerW::cln_w / cln_b hold the folded scale / shift
+    bool ds2_gru = false;            // DeepSpeech2 with use_gru: True (cfg.reserved[0] = 1): nn.GRU recurrent layers (gru.hip)
     // fbank tables
     float *window = nullptr, *melwt = nullptr, *tw512 = nullptr, *twr4 = nullptr;
     FbankTables fbank_tables() const { return FbankTables{window, melwt, tw512, twr4, mel_lo}; }
@@ -674,6 +676,8 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
     if (cfg->model_kind == 3) {
         if (cfg->d_model != 1024) return fail("deepspeech2: the LSTM step kernel is specialised for rnn_size=1024");
         if (cfg->num_blocks <= 0) return fail("deepspeech2: num_rnn_layers must be positive");
+        if (cfg->reserved[0] != 0 && cfg->reserved[0] != 1)
+            return fail("deepspeech2: the recurrent cell (masr_config.reserved[0], encoder_conf.use_gru) must be 0 = LSTM or 1 = GRU");
     } else if (cfg->d_model != 256 || cfg->heads != 4) {
         return fail("kernels are specialised for d_model=256, heads=4");
     } else if (cfg->d_ff % 128) {
@@ -698,6 +702,7 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
     if (e->cfg.max_pos <= 0) e->cfg.max_pos = 5000;
     e->reduce_idx = cfg->model_kind == 1 ? cfg->reserved[0] : -1;
     e->conv_bn = cfg->model_kind == 0 && cfg->reserved[0] == 1;
+    e->ds2_gru = cfg->model_kind == 3 && cfg->reserved[0] == 1;
     e->recover_idx = cfg->model_kind == 1 ? cfg->reserved[1] : -1;
     if (cfg->model_kind == 0 || cfg->model_kind == 2) {
         if (cfg->reserved[3] < IL_CONV2D || cfg->reserved[3] > IL_CONV2D8) {
@@ -1922,34 +1927,50 @@ static int finalize_ds2(masr_engine* e) {
         CHK(upload(e, w, &e->conv2_w));
     }
     CHK(up(e, "encoder.conv.conv.2.bias", {C}, &e->conv2_b));
+    // use_gru: True wraps nn.GRU in the reference's own GRU module (deepspeech2/gru.py): one more ".rnn" in every key
+    const bool gru = e->ds2_gru;
+    const int G = gru ? 3 : 4;                        // gates per unit: r, z, n  |  i, f, g, o
+    const std::string cell = gru ? "rnn.rnn." : "rnn.";
+    {
+        const bool has_gru = e->host.count("encoder.rnns.0.rnn.rnn.weight_ih_l0") > 0;
+        const bool has_lstm = e->host.count("encoder.rnns.0.rnn.weight_ih_l0") > 0;
+        if (gru && !has_gru && has_lstm)
+            return fail("deepspeech2: encoder_conf.use_gru is True but the checkpoint holds LSTM layers (encoder.rnns.0.rnn.weight_ih_l0)");
+        if (!gru && has_gru)
+            return fail("deepspeech2: encoder_conf.use_gru is False but the checkpoint holds GRU layers (encoder.rnns.0.rnn.rnn.weight_ih_l0)");
+    }
     e->ds2_layers.assign(L, Ds2LayerW{});
     for (int i = 0; i < L; ++i) {
         Ds2LayerW& w = e->ds2_layers[i];
         const std::string p = "encoder.rnns." + std::to_string(i) + ".";
         const int kin = i == 0 ? C * F2 : D;
         w.kin = kin;
-        std::vector<float> wih((size_t)ndir * 4 * H * kin), bih((size_t)ndir * 4 * H), whh((size_t)ndir * 4 * H * H);
+        std::vector<float> wih((size_t)ndir * G * H * kin), bih((size_t)ndir * G * H), whh((size_t)ndir * G * H * H);
+        std::vector<float> bhn(gru ? (size_t)ndir * H : 0);
         for (int dir = 0; dir < ndir; ++dir) {
             const std::string suf = dir ? "_reverse" : "";
             const HostTensor *a, *b, *c, *d;
-            CHK(get(e, p + "rnn.weight_ih_l0" + suf, {4 * H, kin}, &a));
-            CHK(get(e, p + "rnn.weight_hh_l0" + suf, {4 * H, H}, &b));
-            CHK(get(e, p + "rnn.bias_ih_l0" + suf, {4 * H}, &c));
-            CHK(get(e, p + "rnn.bias_hh_l0" + suf, {4 * H}, &d));
-            float* dst = wih.data() + (size_t)dir * 4 * H * kin;
+            CHK(get(e, p + cell + "weight_ih_l0" + suf, {G * H, kin}, &a));
+            CHK(get(e, p + cell + "weight_hh_l0" + suf, {G * H, H}, &b));
+            CHK(get(e, p + cell + "bias_ih_l0" + suf, {G * H}, &c));
+            CHK(get(e, p + cell + "bias_hh_l0" + suf, {G * H}, &d));
+            float* dst = wih.data() + (size_t)dir * G * H * kin;
             if (i == 0) {   // conv output is channels-last here: column f*32 + c  <-  reference column c*F2 + f (conv.py:20)
-                for (int r = 0; r < 4 * H; ++r)
+                for (int r = 0; r < G * H; ++r)
                     for (int c2 = 0; c2 < C; ++c2)
                         for (int f = 0; f < F2; ++f) dst[(size_t)r * kin + f * C + c2] = a->v[(size_t)r * kin + c2 * F2 + f];
             } else {
                 std::copy(a->v.begin(), a->v.end(), dst);
             }
-            std::copy(b->v.begin(), b->v.end(), whh.begin() + (size_t)dir * 4 * H * H);
-            for (int r = 0; r < 4 * H; ++r) bih[(size_t)dir * 4 * H + r] = c->v[r] + d->v[r];
+            std::copy(b->v.begin(), b->v.end(), whh.begin() + (size_t)dir * G * H * H);
+            // GRU: b_hr and b_hz fold into the input projection, b_hn stays with the recurrent product (r * (W_hn h + b_hn))
+            for (int r = 0; r < G * H; ++r) bih[(size_t)dir * G * H + r] = c->v[r] + (gru && r >= 2 * H ? 0.f : d->v[r]);
+            if (gru) std::copy(d->v.begin() + 2 * H, d->v.end(), bhn.begin() + (size_t)dir * H);
         }
         CHK(upload(e, wih, &w.wih));
         CHK(upload(e, bih, &w.bih));
         CHK(upload(e, whh, &w.whh));
+        if (gru) CHK(upload(e, bhn, &w.bhn));
         CHK(up(e, p + "layer_norm.weight", {D}, &w.ln_w));
         CHK(up(e, p + "layer_norm.bias", {D}, &w.ln_b));
     }
@@ -1970,9 +1991,11 @@ static int ds2_forward(masr_engine* e, hipStream_t s, const float* feats, const 
     if (T < 7 || Tq <= 0) return fail("input too short for Conv2dSubsampling4Pure (need >= 7 frames)");
     if (st && ndir != 1) return fail("deepspeech2: stateful chunks need the uni-directional (streaming) model");
     const int M = nseq * Tq;
+    const bool gru = e->ds2_gru;
+    const int G = gru ? 3 : 4;                        // gates per unit
     CHK(e->x1.ensure((size_t)nseq * T1 * F1 * C * sizeof(float)));
     CHK(e->x2.ensure((size_t)M * F2 * C * sizeof(float)));
-    CHK(e->gx.ensure((size_t)M * ndir * 4 * H * sizeof(float)));
+    CHK(e->gx.ensure((size_t)M * ndir * G * H * sizeof(float)));
     CHK(e->rnn_out.ensure((size_t)M * D * sizeof(float)));
     CHK(e->ln.ensure((size_t)M * D * sizeof(float)));
     CHK(e->hstate.ensure((size_t)2 * ndir * nseq * H * sizeof(float)));
@@ -1998,29 +2021,32 @@ static int ds2_forward(masr_engine* e, hipStream_t s, const float* feats, const 
     float* cbuf = e->cstate.as<float>();
     for (int l = 0; l < L; ++l) {
         const Ds2LayerW& w = e->ds2_layers[l];
-        gemm(e, s, in, w.kin, w.wih, w.bih, e->gx.as<float>(), ndir * 4 * H, M, ndir * 4 * H, w.kin, ACT_NONE, 1.f, nullptr, 0);
+        gemm(e, s, in, w.kin, w.wih, w.bih, e->gx.as<float>(), ndir * G * H, M, ndir * G * H, w.kin, ACT_NONE, 1.f, nullptr, 0);
         if (st) {
             for (int i = 0; i < nseq; ++i) {
                 const float* hc = st[i]->cnn.as<float>() + (size_t)l * 2 * H;
                 HIPCHK(hipMemcpyAsync(hbuf + (size_t)i * H, hc, sizeof(float) * H, hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync(cbuf + (size_t)i * H, hc + H, sizeof(float) * H, hipMemcpyDeviceToDevice, s));
+                if (!gru) HIPCHK(hipMemcpyAsync(cbuf + (size_t)i * H, hc + H, sizeof(float) * H, hipMemcpyDeviceToDevice, s));
             }
         } else {
             HIPCHK(hipMemsetAsync(hbuf, 0, sizeof(float) * hsz, s));
-            HIPCHK(hipMemsetAsync(cbuf, 0, sizeof(float) * hsz, s));
+            if (!gru) HIPCHK(hipMemsetAsync(cbuf, 0, sizeof(float) * hsz, s));
         }
         // (the whole sequence of a layer as one cooperative launch with W_hh resident in registers and a barrier in global memory
         //  per step was built and measured in round 6: 10.0 against 6.0 ms at B = 1, 26.4 against 25.7 ms at B = 32 --
         //  tools/studies/lstm_seq_study.hip)
-        for (int step = 0; step < Tq; ++step)
-            launch_lstm_step(e->gx.as<float>(), w.whh, hbuf + (size_t)(step & 1) * hsz, hbuf + (size_t)((step + 1) & 1) * hsz,
-                             cbuf, e->rnn_out.as<float>(), xl, nseq, Tq, H, step, ndir, s);
-        if (st) {
+        for (int step = 0; step < Tq; ++step) {
+            const float* hp = hbuf + (size_t)(step & 1) * hsz;
+            float* hn = hbuf + (size_t)((step + 1) & 1) * hsz;
+            if (gru) launch_gru_step(e->gx.as<float>(), w.whh, w.bhn, hp, hn, e->rnn_out.as<float>(), xl, nseq, Tq, H, step, ndir, s);
+            else launch_lstm_step(e->gx.as<float>(), w.whh, hp, hn, cbuf, e->rnn_out.as<float>(), xl, nseq, Tq, H, step, ndir, s);
+        }
+        if (st) {     // GRU: the reference returns final_state_c = final_state_h (gru.py), so h goes to both slots
             const float* hfin = hbuf + (size_t)(Tq & 1) * hsz;
             for (int i = 0; i < nseq; ++i) {
                 float* hc = st[i]->cnn.as<float>() + (size_t)l * 2 * H;
                 HIPCHK(hipMemcpyAsync(hc, hfin + (size_t)i * H, sizeof(float) * H, hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync(hc + H, cbuf + (size_t)i * H, sizeof(float) * H, hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(hc + H, (gru ? hfin : cbuf) + (size_t)i * H, sizeof(float) * H, hipMemcpyDeviceToDevice, s));
             }
         }
         float* out = l == L - 1 ? enc_out : e->ln.as<float>();
@@ -2579,7 +2605,7 @@ int masr_stream_open(masr_engine* e, int32_t max_frames_out, int32_t* stream_id)
     Stream& st = e->streams[id];
     const int d = e->cfg.d_model, L = e->cfg.num_blocks, pad = e->cfg.cnn_kernel - 1;
     st.cap = max_frames_out;
-    if (e->cfg.model_kind == 3) {      // LSTM state (h, c) per layer; no attention cache, no frame limit
+    if (e->cfg.model_kind == 3) {      // recurrent state (h, c) per layer; no attention cache, no frame limit
         st.cap = 1 << 30;
         CHK(st.cnn.ensure((size_t)L * 2 * d * sizeof(float)));
         CHK(clear_sync(st.cnn.p, 0, (size_t)L * 2 * d * sizeof(float)));
@@ -3089,7 +3115,7 @@ int masr_stream_export_cache(masr_engine* e, int32_t stream_id, float* att_dev, 
     ENTER(e);
     hipStream_t s = (hipStream_t)stream;
     const int d = e->cfg.d_model, L = e->cfg.num_blocks, pad = e->cfg.cnn_kernel - 1, H = e->cfg.heads;
-    if (e->cfg.model_kind == 3) {       // att_dev <- h [L][rnn_size], cnn_dev <- c [L][rnn_size]
+    if (e->cfg.model_kind == 3) {       // att_dev <- h [L][rnn_size], cnn_dev <- c [L][rnn_size] (GRU: h again)
         for (int l = 0; l < L; ++l) {
             const float* hc = st->cnn.as<float>() + (size_t)l * 2 * d;
             if (att_dev) HIPCHK(hipMemcpyAsync(att_dev + (size_t)l * d, hc, sizeof(float) * d, hipMemcpyDeviceToDevice, s));
@@ -3216,6 +3242,7 @@ int masr_debug_set(masr_engine* e, int32_t key, int32_t value) {
     else if (key == 40) g_conv2_rows = value;
     else if (key == 41) g_conv1_fused = value;
     else if (key == 42) g_embed_rows = value;
+    else if (key == 43) set_gru_mfma_units(value);
     else if (key == 17) set_gemm_waves(value);
     else if (key == 18) set_conv1_nt(value);
     else if (key == 16) { e->prof_stride = value > 1 ? value : 1; e->prof_seen = 0; }

@@ -117,6 +117,15 @@ def _validate_encoder_conf(use_model, enc, state_dict):
         want('pos_enc_layer_type', ('rel_pos',), 'rel_pos')
         want('adaptive_scale', (True,), True)
         want('dw_stride', (False,), False)
+    elif use_model == 'deepspeech2':
+        # use_gru (deepspeech2/encoder.py:21-33): nn.GRU inside the reference's own GRU module, so its keys carry one more '.rnn'
+        want('use_gru', (False, True), False)
+        has_gru = state_dict is not None and 'encoder.rnns.0.rnn.rnn.weight_ih_l0' in state_dict
+        is_gru = bool(enc.get('use_gru', False))
+        if has_gru != is_gru and state_dict is not None:
+            raise _lib.MasrError(f'{use_model}: encoder_conf.use_gru={is_gru!r} but the checkpoint holds '
+                                 f'{"GRU" if has_gru else "LSTM"} layers ({"encoder.rnns.0.rnn.rnn" if has_gru else "encoder.rnns.0.rnn"}'
+                                 f'.weight_ih_l0)')
 
 
 class HipEngine:
@@ -184,12 +193,13 @@ class HipEngine:
             cfg.reserved[2] = int(eff.get('group_size', 3))
             cfg.reserved[3] = INPUT_LAYERS[self.input_layer]
         elif use_model == 'deepspeech2':
-            # configs/deepspeech2.yml encoder_conf: rnn_size, num_rnn_layers; streaming <=> uni-directional LSTMs
-            # (deepspeech2/encoder.py:14-19: rnn_direction = 'forward' if streaming else 'bidirect')
+            # configs/deepspeech2.yml encoder_conf: rnn_size, num_rnn_layers, use_gru; streaming <=> uni-directional recurrent
+            # layers (deepspeech2/encoder.py:14-19: rnn_direction = 'forward' if streaming else 'bidirect')
             cfg = MasrConfig(model_kind=3, d_model=int(enc.get('rnn_size', 1024)), heads=0, d_ff=0,
                              num_blocks=int(enc.get('num_rnn_layers', 5)), cnn_kernel=0, n_mels=n_mels,
                              vocab_size=int(vocab_size), causal=1 if streaming else 0, max_pos=max_pos,
                              device_id=device)
+            cfg.reserved[0] = int(enc.get('use_gru', False))          # 0 = LSTM, 1 = GRU (checked above)
         else:
             raise _lib.MasrError(f'use_model={use_model}: conformer, squeezeformer, efficient_conformer, deepspeech2 '
                                  f'are implemented')

@@ -69,7 +69,7 @@ class InferencePredictor:
     def predict_chunk_deepspeech(self, x_chunk):
         if not (self.use_model == 'deepspeech2' and self.streaming):
             raise Exception(f'当前模型不支持该方法，当前模型为：{self.use_model}，参数streaming为：{self.streaming}')
-        # inference_predictor.py:66-78: the (h, c) state of every LSTM layer lives in the engine's stream
+        # inference_predictor.py:66-78: the (h, c) state of every recurrent layer lives in the engine's stream (GRU: h, h)
         if self._sid is None:
             self._sid = self.engine.stream_open(0)
         x = torch.as_tensor(np.asarray(x_chunk), dtype=torch.float32).to(self.device).contiguous()

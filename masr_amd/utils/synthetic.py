@@ -190,9 +190,11 @@ def efficient_conformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, d_ff
 
 
 def deepspeech2_state_dict(seed=0, vocab_size=4233, rnn_size=1024, num_rnn_layers=5, bidirectional=True, n_mels=80,
-                           ctc_gain=2.0):
+                           ctc_gain=2.0, use_gru=False):
     """Keys/shapes == reference DeepSpeech2Model state_dict (masr/model_utils/deepspeech2/): conv front-end
-    1->32->32, ``num_rnn_layers`` x (LSTM(rnn_size) [+ reverse] + LayerNorm), CTC head under ``decoder.ctc_lo``."""
+    1->32->32, ``num_rnn_layers`` x (LSTM(rnn_size) [+ reverse] + LayerNorm), CTC head under ``decoder.ctc_lo``.
+    ``use_gru=True`` (encoder.py:21-28): nn.GRU layers inside the reference's GRU module, keys ``encoder.rnns.{i}.rnn.rnn.*``
+    with 3 gate blocks; their draws are named apart from the LSTM's, which stay exactly as they were."""
     sd = {}
     f2 = ((n_mels - 1) // 2 - 1) // 2
     sd['encoder.global_cmvn.mean'] = 13.5 + _uniform(seed, 'cmvn.mean', (n_mels,), 1.0)
@@ -206,11 +208,12 @@ def deepspeech2_state_dict(seed=0, vocab_size=4233, rnn_size=1024, num_rnn_layer
     for i in range(num_rnn_layers):
         isz = 32 * f2 if i == 0 else out
         for suf in ([''] + (['_reverse'] if bidirectional else [])):
-            p = f'encoder.rnns.{i}.rnn.'
-            sd[p + 'weight_ih_l0' + suf] = _uniform(seed, p + 'wih' + suf, (4 * rnn_size, isz), math.sqrt(3.0 / isz))
-            sd[p + 'weight_hh_l0' + suf] = _uniform(seed, p + 'whh' + suf, (4 * rnn_size, rnn_size), math.sqrt(3.0 / rnn_size))
-            sd[p + 'bias_ih_l0' + suf] = _uniform(seed, p + 'bih' + suf, (4 * rnn_size,), 0.1)
-            sd[p + 'bias_hh_l0' + suf] = _uniform(seed, p + 'bhh' + suf, (4 * rnn_size,), 0.1)
+            p = f'encoder.rnns.{i}.rnn.' + ('rnn.' if use_gru else '')
+            g = 3 if use_gru else 4
+            sd[p + 'weight_ih_l0' + suf] = _uniform(seed, p + 'wih' + suf, (g * rnn_size, isz), math.sqrt(3.0 / isz))
+            sd[p + 'weight_hh_l0' + suf] = _uniform(seed, p + 'whh' + suf, (g * rnn_size, rnn_size), math.sqrt(3.0 / rnn_size))
+            sd[p + 'bias_ih_l0' + suf] = _uniform(seed, p + 'bih' + suf, (g * rnn_size,), 0.1)
+            sd[p + 'bias_hh_l0' + suf] = _uniform(seed, p + 'bhh' + suf, (g * rnn_size,), 0.1)
         sd[f'encoder.rnns.{i}.layer_norm.weight'] = 1.0 + _uniform(seed, f'ds2.ln{i}.w', (out,), 0.2)
         sd[f'encoder.rnns.{i}.layer_norm.bias'] = _uniform(seed, f'ds2.ln{i}.b', (out,), 0.1)
     b = ctc_gain / math.sqrt(out)
