@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY -- torch-CPU fp32 restatement of the reference
+"""TEST INFRASTRUCTURE ONLY -- torch-CPU restatement (float32, or float64 when the ``state_dict`` and the inputs are: oracle/f64.py) of the reference
 Conformer inference forward (full-context and chunked streaming) + CTC head.
 
 Written from the reference's algorithm, driven directly by a ``state_dict`` with
@@ -13,14 +13,15 @@ import torch
 import torch.nn.functional as F
 
 
-def positional_table(max_len, d):
-    """conformer/embedding.py:31-37 -- sin on even, cos on odd feature indices."""
+def positional_table(max_len, d, dtype=torch.float32):
+    """conformer/embedding.py:31-37 -- sin on even, cos on odd feature indices.  Built in float32 (the table the engine
+    uploads as ``__pos_table__``) and cast to ``dtype`` afterwards."""
     pe = torch.zeros(max_len, d)
     pos = torch.arange(0, max_len, dtype=torch.float32).unsqueeze(1)
     div = torch.exp(torch.arange(0, d, 2, dtype=torch.float32) * -(math.log(10000.0) / d))
     pe[:, 0::2] = torch.sin(pos * div)
     pe[:, 1::2] = torch.cos(pos * div)
-    return pe
+    return pe.to(dtype)
 
 
 def subsampled_len(t):
@@ -140,7 +141,7 @@ def encoder_full(sd, feats, lens, decoding_chunk_size=-1, heads=4, kernel=15, st
     x = embed(sd, feats)
     Tp = x.shape[1]
     pad_s = pad[:, :-2:2][:, :-2:2]                                     # subsampling.py:112
-    pos_emb = positional_table(5000, x.shape[-1])[:Tp].unsqueeze(0)
+    pos_emb = positional_table(5000, x.shape[-1], x.dtype)[:Tp].unsqueeze(0)
     idx = torch.arange(Tp)
     if decoding_chunk_size < 0:
         chunk = torch.ones(Tp, Tp, dtype=torch.bool)
@@ -180,7 +181,7 @@ def get_encoder_out_chunk(sd, feats, offset, required_cache_size, att_cache, cnn
     cache_t1 = att_cache.shape[2] if have else 0
     chunk = x.shape[1]
     key_size = cache_t1 + chunk
-    pos_emb = positional_table(5000, x.shape[-1])[offset - cache_t1: offset - cache_t1 + key_size].unsqueeze(0)
+    pos_emb = positional_table(5000, x.shape[-1], x.dtype)[offset - cache_t1: offset - cache_t1 + key_size].unsqueeze(0)
     if required_cache_size < 0:
         start = 0
     elif required_cache_size == 0:

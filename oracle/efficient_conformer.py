@@ -69,7 +69,7 @@ def encoder_full(sd, feats, lens, heads=4, stride_layer_idx=(3,), stride=(2,), g
     x = oc.embed(sd, feats)
     Tp = x.shape[1]
     pad_s = pad[:, :-2:2][:, :-2:2]
-    pos_emb = oc.positional_table(5000, x.shape[-1])[:Tp].unsqueeze(0)
+    pos_emb = oc.positional_table(5000, x.shape[-1], x.dtype)[:Tp].unsqueeze(0)
     att = None
     if streaming and decoding_chunk_size > 0:
         idx = torch.arange(Tp)
@@ -168,7 +168,7 @@ def get_encoder_out_chunk(sd, feats, offset, required_cache_size, att_cache, cnn
     cache_t1 = att_cache.shape[2] if have else 0
     chunk = x.shape[1]
     key_size = cache_t1 + chunk
-    pos_emb = oc.positional_table(5000, x.shape[-1])[offset - cache_t1: offset - cache_t1 + key_size].unsqueeze(0)
+    pos_emb = oc.positional_table(5000, x.shape[-1], x.dtype)[offset - cache_t1: offset - cache_t1 + key_size].unsqueeze(0)
     if required_cache_size < 0:
         start = 0
     elif required_cache_size == 0:

@@ -102,7 +102,7 @@ def _time_reduce(sd, x, pad_mask):
     if L - T < 0:
         y = y[:, :L - T, :].contiguous()
     else:
-        y = torch.cat([y, torch.zeros(y.shape[0], L - T, y.shape[2])], dim=1)
+        y = torch.cat([y, torch.zeros(y.shape[0], L - T, y.shape[2], dtype=y.dtype)], dim=1)
     return y, pm
 
 
@@ -120,7 +120,7 @@ def encoder_full(sd, feats, lens, heads=4, kernel=31, reduce_idx=5, recover_idx=
     x = embed(sd, feats)
     Tp = x.shape[1]
     pad_s = pad[:, :-2:2][:, :-2:2]
-    pos_emb = positional_table(5000, x.shape[-1])[:Tp].unsqueeze(0)
+    pos_emb = positional_table(5000, x.shape[-1], x.dtype)[:Tp].unsqueeze(0)
     x = _ln(sd, 'encoder.preln', x)
     att = None
     if causal and decoding_chunk_size > 0:
@@ -200,7 +200,7 @@ def get_encoder_out_chunk(sd, feats, offset, required_cache_size, att_cache, cnn
     cache_t1 = att_cache.shape[2] if have else 0
     chunk = x.shape[1]
     key_size = cache_t1 + chunk
-    pos_emb = positional_table(5000, x.shape[-1])[offset - cache_t1: offset - cache_t1 + key_size].unsqueeze(0)
+    pos_emb = positional_table(5000, x.shape[-1], x.dtype)[offset - cache_t1: offset - cache_t1 + key_size].unsqueeze(0)
     if required_cache_size < 0:
         start = 0
     elif required_cache_size == 0:

@@ -48,7 +48,7 @@ def encoder_full_il(sd, feats, lens, il, streaming, decoding_chunk_size=-1, head
     x = embed_il(sd, feats, il)
     Tp = x.shape[1]
     pad_s = mask_il(torch.arange(T)[None, :] < lens[:, None], il)
-    pos_emb = oc.positional_table(5000, x.shape[-1])[:Tp].unsqueeze(0)
+    pos_emb = oc.positional_table(5000, x.shape[-1], x.dtype)[:Tp].unsqueeze(0)
     idx = torch.arange(Tp)
     if decoding_chunk_size < 0:
         chunk = torch.ones(Tp, Tp, dtype=torch.bool)
