@@ -339,6 +339,22 @@ int masr_stage_rows(void* dst, int64_t row_bytes, const void* const* src, const 
  * y [n_out] with n_out = (int)(n_orig * ratio).  No engine, no GPU: an input-format step in front of the hot path. */
 int masr_resample_f32(const float* x, int64_t n_orig, double ratio, const double* win, const double* dwin, int64_t nwin,
                       int32_t num_table, float* y, int64_t n_out);
+/* The same resampling on the device, for the rows of ONE source rate of a device pass.  Replaces, per row, resampy.resample behind
+ * AudioSegment.resample (masr/data_utils/audio.py:306-317) with the arithmetic of masr_resample_f32, operation for operation (one
+ * thread per output sample; no fused multiply-add, denormals kept): every row comes out bit for bit as the host entry makes it
+ * (third-party algorithm restated, parity unpinned, as above).
+ *   src_dev    [R, src_stride] int16 PCM (sample_format 0, scaled by 2^-15 in the kernel) or float32 (1), at the source rate
+ *   rows_host / rows_dev [R][3] int32, the same table in host and in device memory: samples in | samples out = (int)(samples in *
+ *              ratio), computed by the caller | destination row.  The host copy is read during the call only
+ *   table_dev  [nwin][2] float64: (win[k], dwin[k]) pairs of the filter as masr_resample_f32 takes them (scaled by ratio when
+ *              ratio < 1); NULL with ratio == 1: the rows are at the target rate already and are converted and copied
+ *   dst_dev    [dst_rows, dst_stride] float32: row rows[i][2] receives the resampled row i and zeros from its length to dst_stride
+ * Returns non-zero (masr_last_error) where masr_resample_f32 returns 1 -- a ratio that is not positive, index_step <= 0, a row whose
+ * last output would read at or beyond its input (n >= n_orig) -- and for rows that do not fit their buffers; nothing is launched
+ * then.  Launches on `stream`, never synchronises. */
+int masr_resample_rows(masr_engine* e, const void* src_dev, int32_t sample_format, int64_t src_stride, const int32_t* rows_host,
+                       const int32_t* rows_dev, int32_t R, double ratio, const double* table_dev, int64_t nwin, int32_t num_table,
+                       float* dst_dev, int32_t dst_rows, int64_t dst_stride, void* stream);
 int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc,
                       float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, void* stream);
 /* Read back a stream's caches in the reference layout (for parity tests):

@@ -95,6 +95,7 @@ SIGNATURES = {
     'masr_stream_cache_len': [_P, _I, C.POINTER(_I)],
     'masr_stream_room': [_P, _I, C.POINTER(_I)],
     'masr_resample_f32': [_P, C.c_int64, C.c_double, _P, _P, C.c_int64, _I, _P, C.c_int64],
+    'masr_resample_rows': [_P, _P, _I, C.c_int64, _P, _P, _I, C.c_double, _P, C.c_int64, _I, _P, _I, C.c_int64, _P],
     'masr_stream_set_history': [_P, _I, _I],
     'masr_encode_chunk': [_P, C.POINTER(_I), _I, _P, _I, _P, _P, _P, _P],
     'masr_stream_export_cache': [_P, _I, _P, _P, _P],

@@ -12,7 +12,7 @@ LIB_DIR = os.path.join(ROOT, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libmasr_hip.so')
 SOURCES = ['gemm_f32.hip', 'ffn_reduce.hip', 'ffn_pc.hip', 'sqz_layer.hip', 'rowgemm.hip', 'rowgemm_small.hip', 'elementwise.hip',
            'attention.hip', 'lstm.hip', 'gru.hip', 'beam_gpu.hip', 'lm_scorer.cpp', 'fbank.hip', 'silero.hip', 'engine.hip', 'pool.hip',
-           'beam_search.cpp', 'stage.cpp', 'resample.cpp']
+           'beam_search.cpp', 'stage.cpp', 'resample.cpp', 'resample.hip']
 # MASR_BUILD_EXPERIMENTS=1: the measured-and-rejected kernels of earlier rounds (A/B material behind masr_debug_set keys 20 / 24 /
 # 30 / 34 / 35) are compiled in as well; the default library holds the product kernels only
 EXPERIMENTS = os.environ.get('MASR_BUILD_EXPERIMENTS') == '1'
@@ -22,6 +22,9 @@ if EXPERIMENTS:
 HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'lm_scorer.h'),
            os.path.join(os.path.dirname(ROOT), 'include', 'masr_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value'] + (['-DMASR_EXPERIMENTS=1'] if EXPERIMENTS else [])
+# resample.hip reproduces the host loop of resample.cpp bit for bit: a multiply and the add behind it must round separately (no
+# fused multiply-add) and float32 denormals must survive (tests/test_gpu_resample.py pins both)
+FILE_FLAGS = {'resample.hip': ['-ffp-contract=off', '-fno-gpu-flush-denormals-to-zero']}
 STAMP = os.path.join(LIB_DIR, '.build_flavour')
 
 
@@ -37,7 +40,10 @@ def _sources():
 
 
 def _obj(src):
-    return os.path.join(LIB_DIR, os.path.splitext(src)[0] + '.o')
+    stem, ext = os.path.splitext(src)
+    if sum(os.path.splitext(s)[0] == stem for s in SOURCES) > 1:      # resample.cpp (host) and resample.hip (device)
+        stem += '_' + ext[1:]
+    return os.path.join(LIB_DIR, stem + '.o')
 
 
 def _stale(src):
@@ -76,7 +82,7 @@ def build(force=False, verbose=False):
     todo = [s for s in _sources() if force or _stale(s)]
 
     def compile_one(src):
-        cmd = [_hipcc()] + FLAGS + ['-c', os.path.join(CSRC, src), '-o', _obj(src)]
+        cmd = [_hipcc()] + FLAGS + FILE_FLAGS.get(src, []) + ['-c', os.path.join(CSRC, src), '-o', _obj(src)]
         if verbose:
             print(' '.join(cmd), flush=True)
         subprocess.run(cmd, check=True)

@@ -479,5 +479,10 @@ void launch_linear_spec(const void* pcm, int sample_format, const int* nsamp, in
                         const double* win /*[320]*/, const double* tw /*[320][2]*/, double scale, float* feats /*[B][T_max][161]*/,
                         int T_max, hipStream_t s);
 void launch_linear_frame_counts(const int* nsamp, int B, int* nfr, hipStream_t s);
+// resample.hip: rows of one source rate -> float32 rows at ratio x that rate, scattered into dst [.., dst_stride] and zero-filled
+// behind their own length.  rows_dev [R][3] int32 = samples in | samples out | destination row; table [nwin][2] double = (win[k],
+// dwin[k]) pairs, nullptr = the rows are at the target rate already (converted and copied)
+void launch_resample_rows(const void* src, int sample_format /*0 int16, 1 float32*/, long src_stride, const int* rows_dev, int R,
+                          double ratio, const double* table, int nwin, int num_table, float* dst, long dst_stride, hipStream_t s);
 
 }  // namespace masr

@@ -2442,6 +2442,38 @@ int masr_mean_square(masr_engine* e, const void* samples_dev, int32_t sample_for
     return 0;
 }
 
+// Device form of masr_resample_f32 for the rows of one source rate (resample.hip).  What the host loop refuses is refused here, before
+// anything is launched: the host copy of the row table says which outputs every row has.
+int masr_resample_rows(masr_engine* e, const void* src_dev, int32_t sample_format, int64_t src_stride, const int32_t* rows_host,
+                       const int32_t* rows_dev, int32_t R, double ratio, const double* table_dev, int64_t nwin, int32_t num_table,
+                       float* dst_dev, int32_t dst_rows, int64_t dst_stride, void* stream) {
+    if (!e || !src_dev || !rows_host || !rows_dev || !dst_dev) return fail("masr_resample_rows: null argument");
+    ENTER(e);
+    if (sample_format != 0 && sample_format != 1) return fail("sample_format must be 0 (int16) or 1 (float32)");
+    if (R < 0 || dst_rows <= 0 || dst_stride <= 0 || src_stride <= 0) return fail("masr_resample_rows: bad geometry");
+    if (!(ratio > 0.0)) return fail("masr_resample_rows: ratio must be positive");
+    if (!table_dev && ratio != 1.0) return fail("masr_resample_rows: no filter table for a ratio other than 1");
+    double time_increment = 1.0;
+    if (table_dev) {
+        if (nwin <= 0 || nwin > (1 << 30) || num_table <= 0) return fail("masr_resample_rows: bad filter table");
+        const double scale = ratio < 1.0 ? ratio : 1.0;
+        if ((int64_t)(scale * (double)num_table) <= 0) return fail("masr_resample_rows: index_step <= 0 (ratio too small for the table)");
+        time_increment = 1.0 / ratio;
+    }
+    for (int32_t i = 0; i < R; ++i) {
+        const int64_t n_in = rows_host[3 * i], n_out = rows_host[3 * i + 1], row = rows_host[3 * i + 2];
+        if (n_in <= 0 || n_in > src_stride || n_out < 0 || n_out > dst_stride || row < 0 || row >= dst_rows)
+            return fail("masr_resample_rows: row " + std::to_string(i) + " does not fit its buffers");
+        // the source index of an output grows with the output: the last one decides (resample.cpp: n >= n_orig)
+        if (n_out > 0 && (int64_t)((double)(n_out - 1) * time_increment) >= n_in)
+            return fail("masr_resample_rows: row " + std::to_string(i) + " asks for outputs beyond its input (n >= n_orig)");
+    }
+    launch_resample_rows(src_dev, sample_format, (long)src_stride, rows_dev, R, ratio, table_dev, (int)nwin, num_table, dst_dev,
+                         (long)dst_stride, (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
 // kaldi.mfcc(num_mel_bins=80, num_ceps=n_ceps) on top of the fbank front-end (audio_featurizer.py:98-117).  The DCT / lifter
 // tables follow torchaudio's float32 construction (functional.create_dct(norm='ortho') with column 0 = sqrt(1/80), transposed;
 // lifter 1 + 0.5 * 22 * sin(pi * i / 22)).

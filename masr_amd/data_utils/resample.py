@@ -79,6 +79,43 @@ def resample(x, sr_orig, sr_new, filter='kaiser_best'):
     return y
 
 
+def resampled_length(n, sr_orig, sr_new):
+    """samples that ``n`` samples at ``sr_orig`` give at ``sr_new``: ``int(n * ratio)`` with ``ratio = float(sr_new) / sr_orig``
+    exactly as :func:`resample` evaluates it (NOT ``n * sr_new // sr_orig``: the float product may round across an integer);
+    raises like :func:`resample` for bad rates and for a row too short to give one output sample"""
+    if sr_orig <= 0 or sr_new <= 0:
+        raise ValueError('Invalid sample rate')
+    n_out = int(int(n) * (float(sr_new) / sr_orig))
+    if n_out < 1:
+        raise ValueError(f'Input signal length={int(n)} is too small to resample from {sr_orig}->{sr_new}')
+    return n_out
+
+
+def plan_rows(lengths, rates, target_rate):
+    """host-side plan of a device pass whose rows come at their own sample rates: ``(n_out, groups)`` -- ``n_out[i]`` samples of
+    row i at ``target_rate`` (its own length when it is there already, :func:`resampled_length` otherwise, raising like the host
+    resampler), ``groups`` = {source rate: [row indices, ascending]} in order of first appearance: one device launch each"""
+    if len(lengths) != len(rates):
+        raise ValueError('plan_rows: one rate per row expected')
+    n_out, groups = [], {}
+    for i, (n, sr) in enumerate(zip(lengths, rates)):
+        n_out.append(int(n) if sr == target_rate else resampled_length(n, sr, target_rate))
+        groups.setdefault(sr, []).append(i)
+    return n_out, groups
+
+
+def device_table(sr_orig, sr_new, filter='kaiser_best'):
+    """the filter as the device kernel reads it: ``(pairs [nwin, 2] float64 = (win[k], dwin[k]), num_table)``, prepared exactly
+    as :func:`resample_native` prepares win / dwin (float64, scaled by the ratio when it is below 1, dwin = diff(win))"""
+    ratio = float(sr_new) / sr_orig
+    win, num_table = filter_table(filter)
+    if ratio < 1:
+        win = ratio * win
+    win = np.ascontiguousarray(win, dtype=np.float64)
+    dwin = np.diff(win, append=win[-1])
+    return np.ascontiguousarray(np.stack([win, dwin], axis=1)), num_table
+
+
 def resample_native(x, sr_orig, sr_new, filter='kaiser_best'):
     """the same algorithm through ``masr_resample_f32`` of libmasr_hip.so (host C++, operation for operation the arithmetic of
     :func:`resample`: bit-identical output, ~40x faster than the numpy tap loop); float32 in, float32 out"""

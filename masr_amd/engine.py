@@ -253,6 +253,42 @@ class HipEngine:
         check(self.lib.masr_mean_square(self.h, _ptr(samples), fmt, _ptr(n_samples), B, n_max, _ptr(ms), _stream()))
         return ms
 
+    def resample_table(self, sr_orig, sr_new, filter='kaiser_best'):
+        """(win, dwin) pairs of ``filter`` for ``sr_orig -> sr_new`` on the device (``data_utils.resample.device_table``),
+        uploaded once per (ratio, filter) and kept on the engine -> (tensor [nwin, 2] float64, num_table)"""
+        from .data_utils.resample import device_table
+        cache = self.__dict__.setdefault('_resample_tables', {})
+        key = (float(sr_new) / sr_orig, filter)
+        if key not in cache:
+            pairs, num_table = device_table(sr_orig, sr_new, filter)
+            cache[key] = (torch.from_numpy(pairs).to(self.device), num_table)
+        return cache[key]
+
+    def resample_rows(self, src, n_in, sr_orig, sr_new, filter='kaiser_best', out=None, dst_rows=None):
+        """masr_resample_rows: the rows of ONE source rate -- ``src`` [R, m] int16 PCM or float32 (device), ``n_in`` [R] their
+        lengths (host) -- resampled to ``sr_new`` on the current stream, bit for bit the samples of ``AudioSegment.resample``
+        (audio.py:306-317).  Row i goes to row ``dst_rows[i]`` (default i) of ``out`` [B, n_max] float32 (default: a new
+        [R, longest output] buffer), zeros behind its own ``int(n_in[i] * ratio)`` samples.  ``sr_orig == sr_new``: the rows
+        are converted and copied.  -> (out, output lengths [R] int32 numpy); raises like the host resampler for a row too
+        short to give one sample."""
+        from .data_utils.resample import resampled_length
+        R = src.shape[0]
+        fmt = {torch.int16: 0, torch.float32: 1}[src.dtype]
+        n_in = np.asarray(n_in, np.int64).reshape(-1)
+        if n_in.shape[0] != R or not src.is_contiguous():
+            raise ValueError('resample_rows: src [R, m] contiguous and one length per row expected')
+        same = sr_orig == sr_new
+        n_out = n_in if same else np.array([resampled_length(n, sr_orig, sr_new) for n in n_in], np.int64)
+        if out is None:
+            out = torch.empty(R, int(n_out.max(initial=1)), dtype=torch.float32, device=self.device)
+        rows = np.stack([n_in, n_out, np.arange(R) if dst_rows is None else np.asarray(dst_rows, np.int64)], axis=1).astype(np.int32)
+        table, num_table = (None, 0) if same else self.resample_table(sr_orig, sr_new, filter)
+        rows_dev = self.to_device(rows)
+        check(self.lib.masr_resample_rows(self.h, _ptr(src), fmt, src.shape[1], rows.ctypes.data_as(C.c_void_p), _ptr(rows_dev), R,
+                                          float(sr_new) / sr_orig, _ptr(table), 0 if same else table.shape[0], num_table,
+                                          _ptr(out), out.shape[0], out.shape[1], _stream()))
+        return out, n_out.astype(np.int32)
+
     def side_stream(self, kind):
         """a side stream of THIS DEVICE owned by libmasr_hip.so (masr_side_stream; kind 0 / 1: prefix searches of consecutive
         passes, 2: per-pass preparation, 3: copies, 4: encoder passes of lane 1), as a torch stream.  One set per device, created

@@ -24,6 +24,7 @@ import yaml
 from masr_amd import SUPPORT_MODEL, parallel
 from masr_amd._lib import check
 from masr_amd.data_utils.audio import AudioSegment
+from masr_amd.data_utils.resample import plan_rows
 from masr_amd.data_utils.featurizer.audio_featurizer import AudioFeaturizer
 from masr_amd.data_utils.featurizer.text_featurizer import TextFeaturizer
 from masr_amd.decoders.ctc_greedy_decoder import greedy_decoder
@@ -143,7 +144,13 @@ class MASRPredictor:
         self.init_vad(vad_predictor)
         audio_segment = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
         if audio_segment.sample_rate != self.configs.preprocess_conf.sample_rate:
-            audio_segment.resample(self.configs.preprocess_conf.sample_rate)
+            if self._device_resample():
+                # the recording as ONE long row through the resampling kernel (the samples AudioSegment.resample makes) and back
+                # to the host, where the VAD and the segmentation read it
+                rate = self.configs.preprocess_conf.sample_rate
+                audio_segment = AudioSegment.from_ndarray(self._resample_long(audio_segment, rate), rate)
+            else:
+                audio_segment.resample(self.configs.preprocess_conf.sample_rate)
         samples = audio_segment.samples
         stamps = self.vad_predictor.get_speech_timestamps(samples, audio_segment.sample_rate)
         pieces = [samples[t['start']: t['end']] for t in stamps]
@@ -219,14 +226,74 @@ class MASRPredictor:
         ring['events'][k] = ev
         return xs, ns
 
-    def _prepare_begin(self, live, n, use_db):
+    @staticmethod
+    def _device_resample():
+        """MASR_DEVICE_RESAMPLE=0 (A/B): off-rate utterances are resampled on the host, one after the other, as before"""
+        return os.environ.get('MASR_DEVICE_RESAMPLE', '1') != '0'
+
+    def _stage_native(self, segs):
+        """the rows of ONE source rate at that rate into a pinned buffer [R, longest] (int16 when all of them still are the PCM
+        they were loaded from) -> (pinned rows, their lengths, done): the discipline of ``_stage_fill`` -- buffers take turns and
+        each waits for the event of its own last upload, which ``done()`` records on the current stream once the copy is queued.
+        Four buffers per sample type: a pass takes one per distinct rate, and two passes are prepared ahead."""
+        as_pcm = all(s._pcm16 is not None for s in segs)
+        dt = torch.int16 if as_pcm else torch.float32
+        rows = [np.ascontiguousarray(s._pcm16 if as_pcm else s._samples, np.int16 if as_pcm else np.float32) for s in segs]
+        m32 = np.array([r.shape[0] for r in rows], np.int32)
+        m_max = int(m32.max())
+        need = len(rows) * m_max
+        ring = self.__dict__.setdefault('_native_stage', {}).setdefault(dt, {'bufs': [None] * 4, 'events': [None] * 4, 'turn': 0})
+        k = ring['turn']
+        ring['turn'] = (k + 1) % 4
+        if ring['events'][k] is not None:
+            ring['events'][k].synchronize()
+        if ring['bufs'][k] is None or ring['bufs'][k].numel() < need:
+            ring['bufs'][k] = torch.zeros(need + need // 4, dtype=dt, pin_memory=True)
+        stage = ring['bufs'][k][:need].view(len(rows), m_max)
+        ptrs = (C.c_void_p * len(rows))(*[r.ctypes.data for r in rows])
+        check(self.predictor.engine.lib.masr_stage_rows(C.c_void_p(stage.data_ptr()), m_max * stage.element_size(), ptrs,
+                                                       m32.ctypes.data_as(C.c_void_p), len(rows), stage.element_size(), 4))
+
+        def done():
+            ev = torch.cuda.Event()
+            ev.record()
+            ring['events'][k] = ev
+        return stage, m32, done
+
+    def _stage_resampled(self, live, n, groups):
+        """``_stage_batch`` of a pass with rows off the model's rate, on the CURRENT stream: every distinct source rate's rows are
+        staged and uploaded at that rate (PCM as int16) and ONE launch per rate resamples them into their rows of the pass's
+        float32 input [B, n_max] -- the samples ``AudioSegment.resample`` makes, zeros behind each row's own length.  Rows at
+        the model's rate are one more group, converted and copied by the same call."""
+        eng = self.predictor.engine
+        rate = int(self.configs.preprocess_conf.get('sample_rate', 16000))
+        xs = torch.empty(len(live), int(n.max()), dtype=torch.float32, device=eng.device)
+        for src_rate, rows in groups.items():
+            stage, m32, done = self._stage_native([live[j] for j in rows])
+            src = stage.to(eng.device, non_blocking=True)
+            done()
+            _, n_out = eng.resample_rows(src, m32, src_rate, rate, out=xs, dst_rows=rows)
+            assert np.array_equal(n_out, n[rows])
+        return xs, eng.to_device(np.ascontiguousarray(n, np.int32))
+
+    def _resample_long(self, seg, rate):
+        """one recording -> its float32 samples at ``rate``, resampled on the device as a single row (``predict_long``)"""
+        eng = self.predictor.engine
+        stage, m32, done = self._stage_native([seg])
+        src = stage.to(eng.device, non_blocking=True)
+        done()
+        out, n_out = eng.resample_rows(src, m32, seg.sample_rate, rate)
+        return eng.to_host(out[0, :int(n_out[0])])
+
+    def _prepare_begin(self, live, n, use_db, groups=None):
         """first half of a pass's preparation, nothing waited for: staging + upload + (bit-exact normalisation route) the mean
         squares on their way back to a pinned slot, all on the preparation stream.  With two lanes it is issued for pass k + 1
         BEFORE the encoder of pass k is launched: issued beside a running encoder pass, the upload and the mean squares start
-        4 - 6 ms late (round 6; whichever side stream, 4 or 8 hardware queues)."""
+        4 - 6 ms late (round 6; whichever side stream, 4 or 8 hardware queues).  ``groups`` (a pass with rows off the model's
+        rate, ``_begin_pass``): the rows go up at their own rates and are resampled on the device, ``_stage_resampled``."""
         eng = self.predictor.engine
         with torch.cuda.stream(self._prep_stream()):
-            xs, ns = self._stage_upload(self._stage_fill(live, n))
+            xs, ns = self._stage_upload(self._stage_fill(live, n)) if groups is None else self._stage_resampled(live, n, groups)
             ms_host = None
             if use_db:
                 ring = self.__dict__.setdefault('_ms_ring', {'bufs': [None] * 4, 'turn': 0})
@@ -276,16 +343,25 @@ class MASRPredictor:
         pc = self.configs.preprocess_conf
         rate = int(pc.get('sample_rate', 16000))
         min_samples = 320 if pc.get('feature_method', 'fbank') == 'linear' else 400
-        for s in segs:
-            if s.sample_rate != rate:
-                s.resample(rate)
+        off_rate = any(s.sample_rate != rate for s in segs)
+        if off_rate and not self._device_resample():
+            for s in segs:
+                if s.sample_rate != rate:
+                    s.resample(rate)
+            off_rate = False
+        # lengths at the model's rate: what the host resampler would give, int(n * ratio), computed here -- the rows themselves
+        # are resampled on the device behind their upload (``_stage_resampled``); a row too short for that raises as it did
+        lengths = plan_rows([s.num_samples for s in segs], [s.sample_rate for s in segs], rate)[0] if off_rate else \
+            [s.num_samples for s in segs]
         # 7 / 11 / 15 feature frames is the least Conv2dSubsampling4 / 6 / 8 accepts (subsampling.py:65-211)
         min_frames = getattr(self.predictor.engine, 'min_frames', 7)
-        ok = [i for i, s in enumerate(segs) if s.num_samples >= min_samples + (min_frames - 1) * 160]
+        ok = [i for i, m in enumerate(lengths) if m >= min_samples + (min_frames - 1) * 160]
         live = [segs[i] for i in ok]
-        n = np.array([s.num_samples for s in live], np.int32)
+        n = np.array([lengths[i] for i in ok], np.int32)
+        # one launch per distinct source rate among the rows that take part (row indices within ``live``)
+        groups = plan_rows([s.num_samples for s in live], [s.sample_rate for s in live], rate)[1] if off_rate else None
         return {'count': len(segs), 'ok': ok, 'n': n, 'min_samples': min_samples,
-                'prep': self._prepare_begin(live, n, pc.use_dB_normalization) if ok else None}
+                'prep': self._prepare_begin(live, n, pc.use_dB_normalization, groups) if ok else None}
 
     def _predict_local(self, segs, decode_all_frames=False, as_tokens=False, defer=False, hold_search=False, began=None):
         """AudioSegments -> [{'text','score'}] on THIS rank's engine.  Utterances too short for one feature frame decode to
