@@ -294,6 +294,29 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
                    const int64_t* feed_n, const int32_t* feed_format, const int32_t* feed_is_end, masr_gain_fn gain_fn,
                    void* gain_user, int32_t* n_sessions, const int32_t** handles_out, const int32_t** state_out,
                    const int32_t** rows_host, int32_t* row_width, int32_t** rows_dev, void* stream);
+/* Sessions fed OFF the model's sample rate (8 kHz telephony, 44.1 / 48 kHz recordings): the step resamples their feeds on the
+ * device.  Replaces the per-chunk AudioSegment.resample of the stream facade (masr/predict.py:260-281 ->
+ * masr/data_utils/audio.py:306-317) that a caller of masr_pool_step runs on the host, one chunk at a time.
+ *   masr_pool_set_rate:   registers a source rate once per pool -> *slot.  ratio = model rate / sr_orig, table_host [nwin][2]
+ *                         float64 (win, dwin) pairs as masr_resample_rows takes them, uploaded here with synchronous copies: the
+ *                         first feed of a new source rate blocks on the device once (at most 64 rates per pool).  The pool
+ *                         does not know the model's rate: a ratio that is not model rate / sr_orig is the caller's mistake.
+ *                         Idempotent per sr_orig: a second call returns the slot of the first and ignores its other arguments.
+ *   masr_pool_step_rates: masr_pool_step with feed_rate_slot[k]: -1 = the feed is at the model's rate (handled exactly as by
+ *                         masr_pool_step, which is this call with feed_rate_slot == NULL); a slot = feed_samples[k] are feed_n[k]
+ *                         samples AT THE SOURCE RATE, staged raw; the feed gives (int)(feed_n * ratio) samples (every length of
+ *                         the step's bookkeeping is known on the host), resampled on its own (no filter state across feeds, like
+ *                         the reference) by ONE masr_resample_feeds launch for all off-rate feeds of the step, behind the upload
+ *                         and ahead of the mean squares, with no additional synchronisation; the carried-over samples of such a
+ *                         session return through pinned memory.  Refused before any state changes, on top of masr_pool_step's
+ *                         checks: an unknown slot, a feed too short to give one sample. */
+int masr_pool_set_rate(masr_pool* p, int32_t sr_orig, double ratio, const double* table_host, int64_t nwin, int32_t num_table,
+                       int32_t* slot);
+int masr_pool_step_rates(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, const void* const* feed_samples,
+                         const int64_t* feed_n, const int32_t* feed_format, const int32_t* feed_is_end,
+                         const int32_t* feed_rate_slot, masr_gain_fn gain_fn, void* gain_user, int32_t* n_sessions,
+                         const int32_t** handles_out, const int32_t** state_out, const int32_t** rows_host, int32_t* row_width,
+                         int32_t** rows_dev, void* stream);
 /* diagnostics: host time of masr_pool_step per phase, accumulated over `steps` calls (ms): assemble the samples | upload + mean
  * squares + wait | gains | features + frame bookkeeping | windows (lock-step chunk steps enqueued) | collapse + copy back + wait */
 int masr_pool_profile(masr_pool* p, double* phase_ms, int64_t* steps, int32_t reset);
@@ -355,6 +378,48 @@ int masr_resample_f32(const float* x, int64_t n_orig, double ratio, const double
 int masr_resample_rows(masr_engine* e, const void* src_dev, int32_t sample_format, int64_t src_stride, const int32_t* rows_host,
                        const int32_t* rows_dev, int32_t R, double ratio, const double* table_dev, int64_t nwin, int32_t num_table,
                        float* dst_dev, int32_t dst_rows, int64_t dst_stride, void* stream);
+/* The same resampling for MANY SHORT FEEDS OF MIXED RATES in one launch: the chunks a streaming pool was fed since its last step
+ * (8 kHz telephony next to 44.1 / 48 kHz recordings), each landing at its own offset inside a session's row.  Replaces, per feed,
+ * the resample of the stream facade (masr/predict.py:260-281 -> AudioSegment.resample, masr/data_utils/audio.py:306-317): every
+ * feed is resampled on its own, no filter state carried from chunk to chunk, bit for bit as masr_resample_f32 makes it.
+ *   masr_resample_feed  one feed: src_offset (bytes into src_dev; 2-byte aligned for int16 PCM, 4-byte for float32), format
+ *                       (0 int16 PCM, scaled by 2^-15 in the kernel / 1 float32), n_in samples at the source rate, n_out =
+ *                       (int)(n_in * ratio) samples written to dst[dst_row][dst_offset .. dst_offset + n_out) and NOTHING else
+ *                       (no zero tails), rate_slot = index into the rate table
+ *   masr_resample_rate  one source rate: what masr_resample_rows derives per call, derived once by masr_resample_rate_fill from
+ *                       (ratio, table_dev [nwin][2] float64 (win, dwin) pairs, nwin, num_table)
+ *   tiles               [n_tiles][2] int32 = (feed, first output): a workgroup owns up to 256 consecutive outputs of one feed, so
+ *                       a short feed costs one workgroup, whatever the longest feed.  masr_resample_plan (host only, no engine, no
+ *                       GPU) validates the feeds and builds the list: tiles == NULL counts (n_tiles), else at most tiles_cap
+ *                       entries are written.  It returns 0, or non-zero with *bad_feed (-1: not about one feed) and *why (static
+ *                       text) for: an unknown rate slot, a rate that masr_resample_rate_fill did not make, a bad format, an
+ *                       unaligned or out-of-range source, n_out != (int)(n_in * ratio), a last output that would read at or beyond
+ *                       its input (n >= n_orig), a destination range outside its row.
+ *   masr_resample_feeds feeds / rates / tiles in host AND device memory (the same tables; the host copies are read during the call
+ *                       only).  Everything is validated (masr_resample_plan, and tiles_host against the list it builds) before
+ *                       anything is launched.  ONE launch on `stream`, never synchronises. */
+typedef struct masr_resample_feed {
+    int64_t src_offset;
+    int32_t format, n_in, n_out, dst_row, dst_offset, rate_slot;
+} masr_resample_feed;
+typedef struct masr_resample_rate {
+    double ratio, time_increment, scale;
+    const double* table_dev;
+    int32_t index_step, nwin, num_table, reserved;
+} masr_resample_rate;
+#define MASR_RESAMPLE_TILE 256          /* outputs per workgroup */
+#define MASR_RESAMPLE_LDS_FLOATS 16000 /* a tile's inputs are staged in LDS up to this span, read from global memory beyond */
+int masr_resample_rate_fill(double ratio, const double* table_dev, int64_t nwin, int32_t num_table, masr_resample_rate* out);
+/* input samples one tile of a rate can touch (its span / ratio + both filter wings): what the launcher compares with
+ * MASR_RESAMPLE_LDS_FLOATS */
+int64_t masr_resample_tile_span(const masr_resample_rate* rate);
+int masr_resample_plan(const masr_resample_feed* feeds, int32_t n_feeds, const masr_resample_rate* rates, int32_t n_rates,
+                       int64_t src_bytes, int32_t dst_rows, int64_t dst_stride, int32_t* tiles, int64_t tiles_cap, int64_t* n_tiles,
+                       int32_t* bad_feed, const char** why);
+int masr_resample_feeds(masr_engine* e, const void* src_dev, int64_t src_bytes, const masr_resample_feed* feeds_host,
+                        const masr_resample_feed* feeds_dev, int32_t n_feeds, const masr_resample_rate* rates_host,
+                        const masr_resample_rate* rates_dev, int32_t n_rates, const int32_t* tiles_host, const int32_t* tiles_dev,
+                        int64_t n_tiles, float* dst_dev, int32_t dst_rows, int64_t dst_stride, void* stream);
 int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc,
                       float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, void* stream);
 /* Read back a stream's caches in the reference layout (for parity tests):

@@ -6,6 +6,8 @@ module raises, and so does everything that imports it.
 import ctypes as C
 import os
 
+import numpy as _np
+
 from .build import LIB_PATH
 
 _lib = None
@@ -96,6 +98,14 @@ SIGNATURES = {
     'masr_stream_room': [_P, _I, C.POINTER(_I)],
     'masr_resample_f32': [_P, C.c_int64, C.c_double, _P, _P, C.c_int64, _I, _P, C.c_int64],
     'masr_resample_rows': [_P, _P, _I, C.c_int64, _P, _P, _I, C.c_double, _P, C.c_int64, _I, _P, _I, C.c_int64, _P],
+    'masr_resample_rate_fill': [C.c_double, _P, C.c_int64, _I, _P],
+    'masr_resample_tile_span': [_P],
+    'masr_resample_plan': [_P, _I, _P, _I, C.c_int64, _I, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_I),
+                           C.POINTER(C.c_char_p)],
+    'masr_resample_feeds': [_P, _P, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, C.c_int64, _P, _I, C.c_int64, _P],
+    'masr_pool_set_rate': [_P, _I, C.c_double, _P, C.c_int64, _I, C.POINTER(_I)],
+    'masr_pool_step_rates': [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_I), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                             C.POINTER(_I), C.POINTER(_P), _P],
     'masr_stream_set_history': [_P, _I, _I],
     'masr_encode_chunk': [_P, C.POINTER(_I), _I, _P, _I, _P, _P, _P, _P],
     'masr_stream_export_cache': [_P, _I, _P, _P, _P],
@@ -110,7 +120,15 @@ SIGNATURES = {
     'masr_profile_read': [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), _I],
 }
 _RESTYPE = {'masr_last_error': C.c_char_p, 'masr_destroy': None, 'masr_beam_destroy': None, 'masr_lm_destroy': None,
-            'masr_lm_last_error': C.c_char_p, 'masr_vad_last_error': C.c_char_p, 'masr_vad_destroy': None, 'masr_pool_destroy': None}
+            'masr_lm_last_error': C.c_char_p, 'masr_vad_last_error': C.c_char_p, 'masr_vad_destroy': None, 'masr_pool_destroy': None,
+            'masr_resample_tile_span': C.c_int64}
+
+# masr_resample_feed / masr_resample_rate of include/masr_hip.h as numpy record layouts (32 / 48 bytes)
+RESAMPLE_FEED = _np.dtype([('src_offset', '<i8'), ('format', '<i4'), ('n_in', '<i4'), ('n_out', '<i4'), ('dst_row', '<i4'),
+                           ('dst_offset', '<i4'), ('rate_slot', '<i4')])
+RESAMPLE_RATE = _np.dtype([('ratio', '<f8'), ('time_increment', '<f8'), ('scale', '<f8'), ('table_dev', '<u8'), ('index_step', '<i4'),
+                           ('nwin', '<i4'), ('num_table', '<i4'), ('reserved', '<i4')])
+RESAMPLE_TILE, RESAMPLE_LDS_FLOATS = 256, 16000
 
 
 # int gain_fn(const float* mean_square, int32 n, float target_db, float* gain_out, void* user)

@@ -6,6 +6,9 @@
 
 #include "lm_scorer.h"
 
+struct masr_resample_feed;      // include/masr_hip.h
+struct masr_resample_rate;
+
 // MASR_EXPERIMENTS = 1 (MASR_BUILD_EXPERIMENTS=1 at build time): the measured-and-rejected kernels of earlier rounds are compiled
 // in and reachable through their masr_debug_set keys (ffn_dual.hip, ffn_coop.hip, ffn_x3.hip, gemm_bf16x3.hip, attn_chain_kernel,
 // the head stage on d_ff-split launches).  The default build holds the product kernels only; those keys then fail loudly.
@@ -484,5 +487,9 @@ void launch_linear_frame_counts(const int* nsamp, int B, int* nfr, hipStream_t s
 // dwin[k]) pairs, nullptr = the rows are at the target rate already (converted and copied)
 void launch_resample_rows(const void* src, int sample_format /*0 int16, 1 float32*/, long src_stride, const int* rows_dev, int R,
                           double ratio, const double* table, int nwin, int num_table, float* dst, long dst_stride, hipStream_t s);
+// resample.hip: the off-rate feeds of a streaming step in ONE launch over tiles_dev [n_tiles][2] = (feed, first output); every feed
+// writes dst[dst_row][dst_offset .. + n_out) only.  Descriptors: masr_hip.h; lds_floats: the dynamic LDS that stages a tile's inputs
+void launch_resample_feeds(const void* src, const ::masr_resample_feed* feeds_dev, int n_feeds, const ::masr_resample_rate* rates_dev,
+                           const int* tiles_dev, long n_tiles, int lds_floats, float* dst, long dst_stride, hipStream_t s);
 
 }  // namespace masr

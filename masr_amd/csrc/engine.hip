@@ -2474,6 +2474,40 @@ int masr_resample_rows(masr_engine* e, const void* src_dev, int32_t sample_forma
     return 0;
 }
 
+// The off-rate feeds of a streaming step in one launch (resample.hip resample_feeds_kernel): per feed the resample of the stream
+// facade (masr/predict.py:260-281 -> AudioSegment.resample, masr/data_utils/audio.py:306-317).  masr_resample_plan (resample.cpp)
+// refuses what the host loop refuses and what does not fit its buffers; the tile list the kernel indexes the feeds by is compared
+// with the one the plan builds.  Nothing is launched for a refused call.
+int masr_resample_feeds(masr_engine* e, const void* src_dev, int64_t src_bytes, const masr_resample_feed* feeds_host,
+                        const masr_resample_feed* feeds_dev, int32_t n_feeds, const masr_resample_rate* rates_host,
+                        const masr_resample_rate* rates_dev, int32_t n_rates, const int32_t* tiles_host, const int32_t* tiles_dev,
+                        int64_t n_tiles, float* dst_dev, int32_t dst_rows, int64_t dst_stride, void* stream) {
+    if (!e) return fail("null engine");
+    ENTER(e);
+    if (n_feeds == 0 && n_tiles == 0) return 0;
+    if (!src_dev || !feeds_host || !feeds_dev || !rates_host || !rates_dev || !tiles_host || !tiles_dev || !dst_dev)
+        return fail("masr_resample_feeds: null argument");
+    int32_t bad = -1;
+    const char* why = nullptr;
+    int64_t want_tiles = 0;
+    if (masr_resample_plan(feeds_host, n_feeds, rates_host, n_rates, src_bytes, dst_rows, dst_stride, nullptr, 0, &want_tiles, &bad, &why))
+        return fail("masr_resample_feeds: " + (bad >= 0 ? "feed " + std::to_string(bad) + ": " : std::string()) + (why ? why : "refused"));
+    if (want_tiles != n_tiles || n_tiles > 0x7fffffff) return fail("masr_resample_feeds: tile list is not the one masr_resample_plan builds (count)");
+    int64_t at = 0;
+    long lds = 0;
+    for (int32_t k = 0; k < n_feeds; ++k) {
+        for (int64_t t0 = 0; t0 < feeds_host[k].n_out; t0 += MASR_RESAMPLE_TILE, ++at)
+            if (tiles_host[2 * at] != k || tiles_host[2 * at + 1] != (int32_t)t0)
+                return fail("masr_resample_feeds: tile list is not the one masr_resample_plan builds (tile " + std::to_string(at) + ")");
+        const long span = (long)masr_resample_tile_span(&rates_host[feeds_host[k].rate_slot]);
+        if (span <= MASR_RESAMPLE_LDS_FLOATS && span > lds) lds = span;
+    }
+    launch_resample_feeds(src_dev, feeds_dev, n_feeds, rates_dev, tiles_dev, (long)n_tiles, (int)lds, dst_dev, (long)dst_stride,
+                          (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
 // kaldi.mfcc(num_mel_bins=80, num_ceps=n_ceps) on top of the fbank front-end (audio_featurizer.py:98-117).  The DCT / lifter
 // tables follow torchaudio's float32 construction (functional.create_dct(norm='ortho') with column 0 = sqrt(1/80), transposed;
 // lifter 1 + 0.5 * 22 * sin(pi * i / 22)).

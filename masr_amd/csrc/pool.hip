@@ -11,6 +11,9 @@
 //   that advanced -> ONE copy back of the packed rows [tokens | count | score bits].
 // Round 3 did this framing in python (masr_amd/serving.py: 1.4 of the 4.4 ms of a 128-stream step); the python class keeps the
 // sessions' handles and builds the text.  Greedy sessions only (beam-search sessions keep their per-session python path).
+// Sessions fed off the model's sample rate (masr_pool_set_rate, masr_pool_step_rates): their feeds are staged RAW, their rows are
+// assembled with holes, and one masr_resample_feeds launch behind the upload fills the holes -- where the facade resamples every
+// chunk on the host (predict.py:260-281 -> data_utils/audio.py:306-317).  Lengths are (int)(n * ratio): known without the device.
 // Host-side only: the kernels are the engine's (masr_hip.h entry points) plus two copy / collapse launches in elementwise.hip.
 #include <string.h>
 
@@ -121,6 +124,16 @@ struct Session {
     int frames = 0;               // encoder frames decoded so far
 };
 
+struct Tail {                    // carried-over samples of a session with off-rate feeds: on their way back through pinned memory
+    int sid;
+    const float* src;            // (in the pool's pinned area: valid until the next step resets it)
+    size_t n;
+    float gain;
+    bool scaled;
+};
+
+constexpr int kMaxRates = 64;    // source rates per pool
+
 }  // namespace
 
 struct masr_pool {
@@ -138,6 +151,13 @@ struct masr_pool {
     int hist_rows = 0, hist_cap = 0;
     // per-step work buffers
     Dev samples, lens, ms, gains, feats, win, idx, mp, segs, meta, rows_out;
+    // off-rate feeds: rate slots (host copy + device table, filter tables), the step's raw bytes + descriptors, the tails
+    std::vector<masr_resample_rate> rates;
+    std::map<int, int> rate_of;   // sr_orig -> slot
+    std::vector<void*> rate_tables;
+    masr_resample_rate* rates_dev = nullptr;
+    Dev raw, tails_dev;
+    std::vector<Tail> tails;      // not yet copied into their sessions
     Pinned pin;
     hipEvent_t ev = nullptr;      // the previous step's copies out of `pin`
     bool pending = false;
@@ -195,6 +215,36 @@ int widen_feat(masr_pool* p, int cap, hipStream_t s) {
     return 0;
 }
 
+// the carried-over samples that came back from the device (the stream has been waited for since their copy was queued)
+void settle_tails(masr_pool* p) {
+    for (const Tail& t : p->tails) {
+        auto it = p->sessions.find(t.sid);
+        if (it == p->sessions.end() || it->second.remained.size() != t.n) continue;
+        std::vector<float>& r = it->second.remained;
+        if (t.n) memcpy(r.data(), t.src, t.n * 4);
+        if (t.scaled)
+            for (float& v : r) v *= t.gain;
+    }
+    p->tails.clear();
+}
+
+void drop_tails(masr_pool* p, int sid) {
+    p->tails.erase(std::remove_if(p->tails.begin(), p->tails.end(), [sid](const Tail& t) { return t.sid == sid; }), p->tails.end());
+}
+
+// A step that fails after it has queued tails (their sessions hold placeholders) must not leave them to be read before their copy
+// has landed: on any exit but the regular one the stream is waited for and the tails are settled.
+struct TailGuard {
+    masr_pool* p;
+    hipStream_t s;
+    bool done = false;
+    ~TailGuard() {
+        if (done || p->tails.empty()) return;
+        (void)hipStreamSynchronize(s);
+        settle_tails(p);
+    }
+};
+
 int upload(masr_pool* p, Dev& dst, const void* host_in_pin, size_t n, hipStream_t s) {
     PCHK(dst.ensure(n, 0, s));
     PHIP(hipMemcpyAsync(dst.p, host_in_pin, n, hipMemcpyHostToDevice, s));
@@ -234,8 +284,10 @@ void masr_pool_destroy(masr_pool* p) {
     (void)hipDeviceSynchronize();
     for (auto& kv : p->sessions) (void)masr_stream_close(p->e, kv.second.sid);
     for (Dev* d : {&p->feat, &p->hist_idx, &p->hist_mp, &p->samples, &p->lens, &p->ms, &p->gains, &p->feats, &p->win, &p->idx,
-                   &p->mp, &p->segs, &p->meta, &p->rows_out})
+                   &p->mp, &p->segs, &p->meta, &p->rows_out, &p->raw, &p->tails_dev})
         d->release();
+    for (void* t : p->rate_tables) (void)hipFree(t);
+    if (p->rates_dev) (void)hipFree(p->rates_dev);
     p->pin.release();
     if (p->ev) (void)hipEventDestroy(p->ev);
     delete p;
@@ -263,6 +315,7 @@ int masr_pool_close(masr_pool* p, int32_t handle) {
     auto it = p->sessions.find(handle);
     if (it == p->sessions.end()) PFAIL("masr_pool_close: unknown handle");
     PCHK(masr_stream_close(p->e, handle));
+    drop_tails(p, handle);
     p->free_rows.push_back(it->second.row);
     p->sessions.erase(it);
     return 0;
@@ -274,8 +327,48 @@ int masr_pool_reset(masr_pool* p, int32_t handle) {
     if (it == p->sessions.end()) PFAIL("masr_pool_reset: unknown handle");
     PCHK(masr_stream_reset(p->e, handle));
     Session& s = it->second;
+    drop_tails(p, handle);
     s.remained.clear();
     s.f0 = s.nf = s.frames = 0;
+    return 0;
+}
+
+int masr_pool_set_rate(masr_pool* p, int32_t sr_orig, double ratio, const double* table_host, int64_t nwin, int32_t num_table,
+                       int32_t* slot) {
+    if (!p || !slot || !table_host) PFAIL("masr_pool_set_rate: null argument");
+    if (sr_orig <= 0) PFAIL("masr_pool_set_rate: Invalid sample rate");
+    auto it = p->rate_of.find(sr_orig);
+    if (it != p->rate_of.end()) {
+        *slot = it->second;
+        return 0;
+    }
+    if ((int)p->rates.size() >= kMaxRates) PFAIL("masr_pool_set_rate: at most 64 source rates per pool");
+    if (!(ratio > 0.0) || nwin <= 0 || nwin > (1 << 30) || num_table <= 0) PFAIL("masr_pool_set_rate: ratio must be positive, with a filter table");
+    PHIP(hipSetDevice(p->device));
+    void* table = nullptr;
+    PHIP(hipMalloc(&table, (size_t)nwin * 16));
+    masr_resample_rate r;
+    if (masr_resample_rate_fill(ratio, (const double*)table, nwin, num_table, &r)) {
+        (void)hipFree(table);
+        PFAIL("masr_pool_set_rate: index_step <= 0 (ratio too small for the table)");
+    }
+    if (!p->rates_dev) {
+        const hipError_t err = hipMalloc((void**)&p->rates_dev, kMaxRates * sizeof(masr_resample_rate));
+        if (err != hipSuccess) {
+            (void)hipFree(table);
+            PFAIL(std::string("masr_pool_set_rate: hipMalloc: ") + hipGetErrorString(err));
+        }
+    }
+    // (synchronous copies: a registration, not a step; the slot is new, so no launch in flight reads it)
+    hipError_t err = hipMemcpy(table, table_host, (size_t)nwin * 16, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(p->rates_dev + p->rates.size(), &r, sizeof(r), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        (void)hipFree(table);
+        PFAIL(std::string("masr_pool_set_rate: hipMemcpy: ") + hipGetErrorString(err));
+    }
+    p->rate_tables.push_back(table);
+    p->rates.push_back(r);
+    *slot = p->rate_of[sr_orig] = (int)p->rates.size() - 1;
     return 0;
 }
 
@@ -283,6 +376,15 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
                    const int64_t* feed_n, const int32_t* feed_format, const int32_t* feed_is_end, masr_gain_fn gain_fn,
                    void* gain_user, int32_t* n_sessions, const int32_t** handles_out, const int32_t** state_out,
                    const int32_t** rows_host, int32_t* row_width, int32_t** rows_dev, void* stream) {
+    return masr_pool_step_rates(p, n_feeds, feed_handle, feed_samples, feed_n, feed_format, feed_is_end, nullptr, gain_fn, gain_user,
+                                n_sessions, handles_out, state_out, rows_host, row_width, rows_dev, stream);
+}
+
+int masr_pool_step_rates(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, const void* const* feed_samples,
+                         const int64_t* feed_n, const int32_t* feed_format, const int32_t* feed_is_end,
+                         const int32_t* feed_rate_slot, masr_gain_fn gain_fn, void* gain_user, int32_t* n_sessions,
+                         const int32_t** handles_out, const int32_t** state_out, const int32_t** rows_host, int32_t* row_width,
+                         int32_t** rows_dev, void* stream) {
     if (!p || !n_sessions) PFAIL("null argument");
     PHIP(hipSetDevice(p->device));
     hipStream_t s = (hipStream_t)stream;
@@ -300,6 +402,21 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
         if (feed_format[k] != 0 && feed_format[k] != 1) PFAIL("masr_pool_step: sample format 0 = int16 PCM, 1 = float32");
         if (feed_n[k] < 0 || feed_n[k] > kMaxFeedSamples) PFAIL("masr_pool_step: feed_n out of range (0 .. 2^28 samples)");
         if (feed_n[k] > 0 && !feed_samples[k]) PFAIL("masr_pool_step: null sample pointer with feed_n > 0");
+    }
+    // samples every feed gives at the model's rate: its own count, or (int)(n * ratio) of an off-rate feed (resample.cpp)
+    std::vector<int64_t> out_n(feed_n, feed_n + n_feeds);
+    int n_off = 0;
+    for (int k = 0; feed_rate_slot && k < n_feeds; ++k) {
+        const int slot = feed_rate_slot[k];
+        if (slot == -1) continue;
+        if (slot < 0 || slot >= (int)p->rates.size()) PFAIL("masr_pool_step: unknown rate slot (masr_pool_set_rate)");
+        const masr_resample_rate& r = p->rates[slot];
+        const int64_t m = (int64_t)((double)feed_n[k] * r.ratio);
+        if (m < 1 || m > kMaxFeedSamples) PFAIL("masr_pool_step: feed " + std::to_string(k) + " is too small to resample (or gives more than 2^28 samples)");
+        if ((int64_t)((double)(m - 1) * r.time_increment) >= feed_n[k])
+            PFAIL("masr_pool_step: feed " + std::to_string(k) + " asks for outputs beyond its input (n >= n_orig)");
+        out_n[k] = m;
+        ++n_off;
     }
     // ---- sessions of this step, in the order they were first fed ------------------------------------------------------
     std::vector<Session*> sess;
@@ -328,7 +445,7 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
         std::vector<std::vector<int>> keep_f;
         for (size_t i = 0; i < sess.size(); ++i) {
             long tot = (long)sess[i]->remained.size();
-            for (int k : feeds_of[i]) tot += feed_n[k];
+            for (int k : feeds_of[i]) tot += out_n[k];
             const int nfr = sess[i]->nf + feature_frames(p, tot);
             long emit = 0;
             if (!((nfr < kWindow && !end_flag[i]) || nfr < kContext)) {
@@ -374,6 +491,7 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
         p->pending = false;
     }
     if (!p->ev) PHIP(hipEventCreateWithFlags(&p->ev, hipEventDisableTiming));
+    settle_tails(p);                                 // (a step that ended without a wait left its tails in the pinned area)
     PCHK(p->pin.reset());
     int max_row = 0;
     for (Session* q : sess) max_row = std::max(max_row, q->row);
@@ -384,10 +502,24 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
     long n_max = p->min_samples;
     for (int i = 0; i < n; ++i) {
         long tot = (long)sess[i]->remained.size();
-        for (int k : feeds_of[i]) tot += feed_n[k];
+        for (int k : feeds_of[i]) tot += out_n[k];
         L[i] = tot;
         n_max = std::max(n_max, tot);
     }
+    // off-rate feeds of the sessions that take part: their raw bytes are staged in pinned memory as fed, 4-byte aligned
+    std::vector<masr_resample_feed> rs_feeds;
+    std::vector<char> off_sess(n, 0);
+    size_t raw_bytes = 0;
+    if (n_off)
+        for (int i = 0; i < n; ++i)
+            for (int k : feeds_of[i])
+                if (feed_rate_slot[k] >= 0) {
+                    raw_bytes = ((raw_bytes + 3) & ~(size_t)3) + (size_t)feed_n[k] * (feed_format[k] ? 4 : 2);
+                    off_sess[i] = 1;
+                }
+    char* raw_h = nullptr;
+    if (raw_bytes) PCHK(p->pin.take(raw_bytes, (void**)&raw_h));
+    size_t raw_at = 0;
     float* buf = nullptr;
     int32_t* lens_h = nullptr;
     PCHK(p->pin.take((size_t)n * n_max * 4, (void**)&buf));
@@ -398,6 +530,16 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
         if (at) memcpy(row, sess[i]->remained.data(), at * 4);
         for (int k : feeds_of[i]) {
             const long m = feed_n[k];
+            if (feed_rate_slot && feed_rate_slot[k] >= 0) {      // staged raw; its samples are a hole the device fills
+                raw_at = (raw_at + 3) & ~(size_t)3;
+                const size_t bytes = (size_t)m * (feed_format[k] ? 4 : 2);
+                memcpy(raw_h + raw_at, feed_samples[k], bytes);
+                rs_feeds.push_back(masr_resample_feed{(int64_t)raw_at, feed_format[k], (int32_t)m, (int32_t)out_n[k], i, (int32_t)at,
+                                                      feed_rate_slot[k]});
+                raw_at += bytes;
+                at += (size_t)out_n[k];
+                continue;
+            }
             if (feed_format[k] == 1) {
                 memcpy(row + at, feed_samples[k], (size_t)m * 4);
             } else {                                  // int16 PCM: x / 2^15 in float32 (buf_to_float, data_utils/utils.py:382-411)
@@ -412,6 +554,60 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
     lap(0);
     PCHK(upload(p, p->samples, buf, (size_t)n * n_max * 4, s));
     PCHK(upload(p, p->lens, lens_h, (size_t)n * 4, s));
+    // ---- off-rate feeds: ONE launch fills their holes; the tails of their sessions come back behind it ----------------------
+    std::vector<int> fresh(n);
+    for (int i = 0; i < n; ++i) fresh[i] = feature_frames(p, L[i]);
+    std::vector<const float*> tail_h(n, nullptr);
+    if (!rs_feeds.empty()) {
+        const int nf = (int)rs_feeds.size();
+        int64_t n_tiles = 0;                           // (what the plan will count: one tile per 256 outputs of a feed)
+        for (const masr_resample_feed& f : rs_feeds) n_tiles += (f.n_out + MASR_RESAMPLE_TILE - 1) / MASR_RESAMPLE_TILE;
+        int32_t bad = -1;
+        const char* why = nullptr;
+        std::vector<PoolSeg> tsegs;
+        long tail_total = 0;
+        int tail_max = 0;
+        for (int i = 0; i < n; ++i)
+            if (off_sess[i]) {
+                const long from = 160L * fresh[i], len = L[i] - from;
+                if (len > 0) {
+                    tsegs.push_back(PoolSeg{(long)i * n_max + from, tail_total, (int)len, i});
+                    tail_max = std::max(tail_max, (int)len);
+                }
+                tail_total += len;
+            }
+        // block: feeds | tiles | tail segments (descriptors; the raw bytes are their own copy: they may be large)
+        const size_t o_tiles = (size_t)nf * sizeof(masr_resample_feed), o_segs = o_tiles + (size_t)n_tiles * 8;
+        const size_t block = o_segs + tsegs.size() * sizeof(PoolSeg);
+        char* blk = nullptr;
+        PCHK(p->pin.take(block, (void**)&blk));
+        memcpy(blk, rs_feeds.data(), o_tiles);
+        int64_t planned = 0;
+        if (masr_resample_plan(rs_feeds.data(), nf, p->rates.data(), (int)p->rates.size(), (int64_t)raw_bytes, n, n_max,
+                               (int32_t*)(blk + o_tiles), n_tiles, &planned, &bad, &why) || planned != n_tiles)
+            PFAIL(std::string("masr_pool_step: off-rate feed: ") + (why ? why : "tile count"));
+        float* tails_h = nullptr;
+        if (tail_total) PCHK(p->pin.take((size_t)tail_total * 4, (void**)&tails_h));
+        for (PoolSeg& g : tsegs) {
+            tail_h[g.pad_] = tails_h + g.dst;
+            g.pad_ = 0;
+        }
+        if (!tsegs.empty()) memcpy(blk + o_segs, tsegs.data(), tsegs.size() * sizeof(PoolSeg));
+        const size_t dev_raw = (raw_bytes + 63) & ~(size_t)63;
+        PCHK(p->raw.ensure(dev_raw + block, 0, s));
+        char* raw_d = p->raw.as<char>();
+        PHIP(hipMemcpyAsync(raw_d, raw_h, raw_bytes, hipMemcpyHostToDevice, s));
+        PHIP(hipMemcpyAsync(raw_d + dev_raw, blk, block, hipMemcpyHostToDevice, s));
+        PCHK(masr_resample_feeds(p->e, raw_d, (int64_t)raw_bytes, rs_feeds.data(), (const masr_resample_feed*)(raw_d + dev_raw), nf,
+                                 p->rates.data(), p->rates_dev, (int)p->rates.size(), (const int32_t*)(blk + o_tiles),
+                                 (const int32_t*)(raw_d + dev_raw + o_tiles), n_tiles, p->samples.as<float>(), n, n_max, stream));
+        if (tail_total) {
+            PCHK(p->tails_dev.ensure((size_t)tail_total * 4, 0, s));
+            launch_copy_segments(p->samples.as<float>(), p->tails_dev.as<float>(), nullptr, nullptr,
+                                 (const PoolSeg*)(raw_d + dev_raw + o_segs), (int)tsegs.size(), tail_max, 1, s);
+            PHIP(hipMemcpyAsync(tails_h, p->tails_dev.p, (size_t)tail_total * 4, hipMemcpyDeviceToHost, s));
+        }
+    }
 
     // ---- gains: mean squares from the device, the scalar expressions of AudioSegment.normalize on the host ------------------
     float* gains_h = nullptr;
@@ -452,22 +648,24 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
                                nullptr, p->gains.as<float>(), stream));
 
     // ---- bookkeeping: carried-over samples, new frames appended to the sessions' rows of the frame pool --------------------
-    std::vector<int> fresh(n);
     int need = 0;
-    for (int i = 0; i < n; ++i) {
-        fresh[i] = feature_frames(p, L[i]);
-        need = std::max(need, sess[i]->nf + fresh[i]);
-    }
+    for (int i = 0; i < n; ++i) need = std::max(need, sess[i]->nf + fresh[i]);
     if (need > p->feat_cap) PCHK(widen_feat(p, std::max(need, 2 * p->feat_cap), s));
     std::vector<PoolSeg> seg_h;
     int seg_rows = 0;
+    TailGuard tail_guard{p, s};
     for (int i = 0; i < n; ++i) {
         Session& q = *sess[i];
         const float* row = buf + (size_t)i * n_max;
         const long from = 160L * fresh[i];
-        q.remained.assign(row + from, row + L[i]);                   // normalised in place, like AudioSegment.normalize
-        if (p->use_db && L[i] > 0)
-            for (float& v : q.remained) v *= gains_h[i];
+        if (off_sess[i]) {                                            // the device has the row: its tail is on its way back
+            q.remained.assign((size_t)(L[i] - from), 0.f);
+            p->tails.push_back(Tail{q.sid, tail_h[i], (size_t)(L[i] - from), p->use_db ? gains_h[i] : 1.f, p->use_db && L[i] > 0});
+        } else {
+            q.remained.assign(row + from, row + L[i]);               // normalised in place, like AudioSegment.normalize
+            if (p->use_db && L[i] > 0)
+                for (float& v : q.remained) v *= gains_h[i];
+        }
         if (q.f0 + q.nf + fresh[i] > p->feat_cap) {                   // make room: the live frames move to the front of the row
             float* base = p->feat.as<float>() + (size_t)q.row * p->feat_cap * p->F;
             PCHK(p->win.ensure((size_t)q.nf * p->F * 4, 0, s));
@@ -592,6 +790,8 @@ int masr_pool_step(masr_pool* p, int32_t n_feeds, const int32_t* feed_handle, co
     PHIP(hipEventRecord(p->ev, s));
     p->pending = true;
     if (na) PHIP(hipStreamSynchronize(s));
+    if (na || p->use_db) settle_tails(p);            // (waited for above, or with the mean squares; else: at the next step)
+    tail_guard.done = true;
     lap(5);
     ++p->prof_steps;
     // ---- results + the windows' bookkeeping (predict.py:329: keep the overlap frames) -----------------------------------------

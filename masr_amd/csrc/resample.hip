@@ -11,6 +11,7 @@
 // table is read as one 16-byte (win[k], dwin[k]) pair per tap; at tap i every output of the workgroup reads inside the window
 // [i * index_step, (i + 1) * index_step] of it, so the pairs come out of the vector cache.  The chain through the float32
 // accumulator is inherent in the rounding; it is hidden by the waves in flight, never by reordering the sum.
+#include "../../include/masr_hip.h"
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -122,6 +123,93 @@ __global__ __launch_bounds__(RS_TILE) void resample_copy_kernel(const void* __re
     dst[(long)r.dst_row * dst_stride + t] = t < r.n_out ? rs_sample(row, fmt, t) : 0.f;
 }
 
+// ---- many short feeds of mixed rates in one launch (a streaming pool's step) ------------------------------------------------------
+// The chunks of a step are 0.1 - 0.64 s each, at their own rates and formats, each landing at its own offset of a session's row.
+// One flat grid over tiles: tiles[b] = (feed, first output); the workgroup reads its feed's descriptor and its rate's slot (time
+// increment, scale, index step, table: what the row kernel gets as launch arguments) from device memory, then does what the row
+// kernel does -- the same staging, the same per-output loop, operation for operation.  It writes its own outputs and nothing else.
+static_assert(sizeof(masr_resample_feed) == 32 && sizeof(masr_resample_rate) == 48, "descriptor layout (masr_hip.h)");
+static_assert(RS_TILE == MASR_RESAMPLE_TILE, "tile (masr_hip.h)");
+
+__global__ __launch_bounds__(RS_TILE) void resample_feeds_kernel(const char* __restrict__ src, const masr_resample_feed* __restrict__ feeds,
+                                                                 int n_feeds, const masr_resample_rate* __restrict__ rates,
+                                                                 const int2* __restrict__ tiles, int lds_cap, float* __restrict__ dst,
+                                                                 long dst_stride) {
+    extern __shared__ float xs[];
+    const int2 tile = tiles[blockIdx.x];
+    if (tile.x < 0 || tile.x >= n_feeds) return;           // (uniform; the entry point has checked the list)
+    const masr_resample_feed f = feeds[tile.x];
+    const masr_resample_rate r = rates[f.rate_slot];
+    const int fmt = f.format, index_step = r.index_step, nwin = r.nwin, num_table = r.num_table;
+    const double time_increment = r.time_increment, scale = r.scale;
+    const double2* table = reinterpret_cast<const double2*>(r.table_dev);
+    const long t0 = tile.y;
+    const long t = t0 + threadIdx.x;
+    const char* row = src + f.src_offset;
+    float* out = dst + (long)f.dst_row * dst_stride + f.dst_offset;
+    // inputs of the tile: [n(first output) - wing + 1, n(last output) + wing], clipped to the feed
+    const long wing = nwin / index_step;
+    const long t_last = (t0 + RS_TILE < f.n_out ? t0 + RS_TILE : (long)f.n_out) - 1;
+    long base = (long)((double)t0 * time_increment) - wing + 1;
+    long end = (long)((double)t_last * time_increment) + wing + 1;
+    base = base < 0 ? 0 : base;
+    end = end > f.n_in ? f.n_in : end;
+    const bool staged = end - base <= lds_cap;             // (uniform)
+    if (staged) {
+        for (long j = base + threadIdx.x; j < end; j += RS_TILE) xs[j - base] = rs_sample(row, fmt, j);
+        __syncthreads();
+    }
+    if (t >= f.n_out) return;
+    const double time_register = (double)t * time_increment;
+    const long n = (long)time_register;
+    float acc = 0.f;
+    if (n < f.n_in) {                                      // (the entry point has refused feeds where this fails)
+        double frac = scale * (time_register - (double)n);
+        double index_frac = frac * (double)num_table;
+        long offset = (long)index_frac;
+        double eta = index_frac - (double)offset;
+        long lim = (nwin - offset) / index_step;
+        const int i_max = (int)(n + 1 < lim ? n + 1 : lim);
+        const double2* tp = table + offset;
+        if (staged) {
+            const float* xp = xs + (n - base);
+            for (int i = 0; i < i_max; ++i) {
+                const double2 w = tp[(long)i * index_step];
+                const double weight = w.x + eta * w.y;
+                acc = (float)((double)acc + weight * (double)xp[-i]);
+            }
+        } else {
+            for (int i = 0; i < i_max; ++i) {
+                const double2 w = tp[(long)i * index_step];
+                const double weight = w.x + eta * w.y;
+                acc = (float)((double)acc + weight * (double)rs_sample(row, fmt, n - i));
+            }
+        }
+        frac = scale - frac;
+        index_frac = frac * (double)num_table;
+        offset = (long)index_frac;
+        eta = index_frac - (double)offset;
+        lim = (nwin - offset) / index_step;
+        const int k_max = (int)(f.n_in - n - 1 < lim ? f.n_in - n - 1 : lim);
+        tp = table + offset;
+        if (staged) {
+            const float* xp = xs + (n + 1 - base);
+            for (int i = 0; i < k_max; ++i) {
+                const double2 w = tp[(long)i * index_step];
+                const double weight = w.x + eta * w.y;
+                acc = (float)((double)acc + weight * (double)xp[i]);
+            }
+        } else {
+            for (int i = 0; i < k_max; ++i) {
+                const double2 w = tp[(long)i * index_step];
+                const double weight = w.x + eta * w.y;
+                acc = (float)((double)acc + weight * (double)rs_sample(row, fmt, n + 1 + i));
+            }
+        }
+    }
+    out[t] = acc;
+}
+
 }  // namespace
 
 // floats of LDS that hold the inputs of one tile whatever its position: the tile's own span + both wings (+ rounding slack)
@@ -148,6 +236,16 @@ void launch_resample_rows(const void* src, int sample_format, long src_stride, c
     hipLaunchKernelGGL(resample_rows_kernel, grid, dim3(RS_TILE), (size_t)cap * sizeof(float), s, src, sample_format, src_stride,
                        rows, time_increment, scale, index_step, reinterpret_cast<const double2*>(table), nwin, num_table, (int)cap,
                        dst, dst_stride);
+}
+
+// lds_floats: the largest tile span among the rates in use that fits MASR_RESAMPLE_LDS_FLOATS (the caller's, from
+// masr_resample_tile_span); a rate whose tiles span more reads global memory
+void launch_resample_feeds(const void* src, const masr_resample_feed* feeds_dev, int n_feeds, const masr_resample_rate* rates_dev,
+                           const int* tiles_dev, long n_tiles, int lds_floats, float* dst, long dst_stride, hipStream_t s) {
+    if (n_tiles <= 0 || n_feeds <= 0) return;
+    hipLaunchKernelGGL(resample_feeds_kernel, dim3((unsigned)n_tiles), dim3(RS_TILE), (size_t)lds_floats * sizeof(float), s,
+                       reinterpret_cast<const char*>(src), feeds_dev, n_feeds, rates_dev, reinterpret_cast<const int2*>(tiles_dev),
+                       lds_floats, dst, dst_stride);
 }
 
 }  // namespace masr

@@ -289,6 +289,47 @@ class HipEngine:
                                           _ptr(out), out.shape[0], out.shape[1], _stream()))
         return out, n_out.astype(np.int32)
 
+    def resample_rate(self, sr_orig, sr_new, filter='kaiser_best'):
+        """one ``masr_resample_rate`` record (``_lib.RESAMPLE_RATE``) for ``sr_orig -> sr_new``: the table of
+        :meth:`resample_table` and what ``masr_resample_rate_fill`` derives from the ratio"""
+        from ._lib import RESAMPLE_RATE
+        table, num_table = self.resample_table(sr_orig, sr_new, filter)
+        rec = np.zeros(1, RESAMPLE_RATE)
+        if self.lib.masr_resample_rate_fill(float(sr_new) / sr_orig, _ptr(table), table.shape[0], num_table,
+                                            rec.ctypes.data_as(C.c_void_p)) != 0:
+            raise ValueError(f'cannot resample from {sr_orig}->{sr_new}: ratio too small for the filter table')
+        return rec[0]
+
+    def resample_plan(self, feeds, rates, src_bytes, dst_rows, dst_stride):
+        """masr_resample_plan (host only): validates ``feeds`` (``_lib.RESAMPLE_FEED`` records) against ``rates``
+        (``_lib.RESAMPLE_RATE`` records) and the buffers -> the tile list [n_tiles, 2] int32 = (feed, first output); raises
+        ValueError with the reason for a refused feed"""
+        feeds, rates = np.ascontiguousarray(feeds), np.ascontiguousarray(rates)
+        n, bad, why = C.c_int64(), C.c_int32(), C.c_char_p()
+        args = (feeds.ctypes.data_as(C.c_void_p), feeds.shape[0], rates.ctypes.data_as(C.c_void_p), rates.shape[0], int(src_bytes),
+                int(dst_rows), int(dst_stride))
+        if self.lib.masr_resample_plan(*args, None, 0, C.byref(n), C.byref(bad), C.byref(why)) != 0:
+            raise ValueError(f'resample_plan: feed {bad.value}: {(why.value or b"refused").decode()}')
+        tiles = np.zeros((n.value, 2), np.int32)
+        self.lib.masr_resample_plan(*args, tiles.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(bad), C.byref(why))
+        return tiles
+
+    def resample_feeds(self, src, feeds, rates, tiles, out):
+        """masr_resample_feeds: many short feeds of mixed rates and formats in ONE launch on the current stream.  ``src``: the
+        feeds' raw bytes, one ragged uint8 device buffer; ``feeds`` / ``rates`` / ``tiles``: the host tables (uploaded here);
+        feed k writes ``out[dst_row, dst_offset : dst_offset + n_out]`` (float32 device, contiguous) and nothing else, bit for
+        bit the samples ``AudioSegment.resample`` makes of it on its own (predict.py:260-281 -> audio.py:306-317).  Raises
+        MasrError, with nothing launched, for what ``masr_resample_plan`` refuses."""
+        feeds, rates, tiles = np.ascontiguousarray(feeds), np.ascontiguousarray(rates), np.ascontiguousarray(tiles, np.int32)
+        if src.dtype != torch.uint8 or out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or not src.is_contiguous():
+            raise ValueError('resample_feeds: src uint8 and out [rows, stride] float32, both contiguous, expected')
+        up = [self.to_device(a.view(np.uint8)) for a in (feeds, rates, tiles)]
+        check(self.lib.masr_resample_feeds(self.h, _ptr(src), src.numel(), feeds.ctypes.data_as(C.c_void_p), _ptr(up[0]), feeds.shape[0],
+                                           rates.ctypes.data_as(C.c_void_p), _ptr(up[1]), rates.shape[0],
+                                           tiles.ctypes.data_as(C.c_void_p), _ptr(up[2]), tiles.shape[0], _ptr(out), out.shape[0],
+                                           out.shape[1], _stream()))
+        return out
+
     def side_stream(self, kind):
         """a side stream of THIS DEVICE owned by libmasr_hip.so (masr_side_stream; kind 0 / 1: prefix searches of consecutive
         passes, 2: per-pass preparation, 3: copies, 4: encoder passes of lane 1), as a torch stream.  One set per device, created

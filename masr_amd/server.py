@@ -51,7 +51,7 @@ class EngineWorker(object):
         self._cv = threading.Condition()
         self._offline = []          # (arrival time, audio, future)
         self._calls = []            # (fn, args, future): run on the worker thread as they are (stream open/close, predict_long)
-        self._feeds = []            # (handle, pcm bytes, is_end, future)
+        self._feeds = []            # (handle, pcm bytes, is_end, future, sample rate)
         self._stop = False
         self.stats = {'batches': 0, 'utterances': 0, 'steps': 0, 'chunks': 0}
         self._busy = 0              # requests taken off the queues and not finished yet
@@ -84,11 +84,13 @@ class EngineWorker(object):
     def stream_close(self, handle):
         return self.call(self.pool.close, handle)
 
-    def stream_feed(self, handle, pcm_bytes, is_end=False):
-        """queue one chunk of a session -> Future of {'text', 'score'} or None (not enough audio for a window yet)"""
+    def stream_feed(self, handle, pcm_bytes, is_end=False, sample_rate=16000):
+        """queue one chunk of a session -> Future of {'text', 'score'} or None (not enough audio for a window yet).
+        ``sample_rate``: the rate of the chunk's mono 16-bit PCM; off the model's rate (8 kHz telephony) the pool's step
+        resamples it on the device"""
         fut = Future()
         with self._cv:
-            self._feeds.append((handle, pcm_bytes, bool(is_end), fut))
+            self._feeds.append((handle, pcm_bytes, bool(is_end), fut, int(sample_rate)))
             self._cv.notify()
         return fut
 
@@ -234,11 +236,16 @@ class EngineWorker(object):
                 (later if item[0] in seen else now).append(item)
                 seen.add(item[0])
             live = []
-            for handle, data, is_end, fut in now:
+            for handle, data, is_end, fut, rate in now:
                 if not fut.set_running_or_notify_cancel():
                     continue
                 try:
-                    self.pool.feed(handle, data, is_end=is_end)
+                    # (a chunk at the pool's own rate, and an EMPTY one -- a client's final b'end' alone, which no resampler
+                    # takes -- are fed as they always were; the keyword goes to pools that are told another rate)
+                    if rate == getattr(self.pool, 'sample_rate', 16000) or len(data) == 0:
+                        self.pool.feed(handle, data, is_end=is_end)
+                    else:
+                        self.pool.feed(handle, data, is_end=is_end, sample_rate=rate)
                     live.append((handle, fut))
                 except BaseException as e:
                     fut.set_exception(e)
@@ -313,8 +320,8 @@ class WorkerRouter(object):
         inner.add_done_callback(done)
         return out
 
-    def stream_feed(self, handle, pcm_bytes, is_end=False):
-        return self.workers[handle % self.n].stream_feed(handle // self.n, pcm_bytes, is_end)
+    def stream_feed(self, handle, pcm_bytes, is_end=False, sample_rate=16000):
+        return self.workers[handle % self.n].stream_feed(handle // self.n, pcm_bytes, is_end, sample_rate)
 
     def stream_close(self, handle):
         return self.workers[handle % self.n].stream_close(handle // self.n)
@@ -335,12 +342,14 @@ def _multipart_file(content_type, body, field='audio'):
     raise ValueError(f'multipart field {field!r} missing')
 
 
-def create_app(predictor=None, max_batch=32, max_wait_ms=10.0, max_frames_out=0, pool=None, predictors=None, pools=None):
+def create_app(predictor=None, max_batch=32, max_wait_ms=10.0, max_frames_out=0, pool=None, predictors=None, pools=None,
+               stream_sample_rate=16000):
     """FastAPI application speaking the reference server's protocol on top of an EngineWorker -- or, with
     ``predictors=[one MASRPredictor per GPU]``, on a ``WorkerRouter`` over one worker per GPU (sticky websocket sessions,
     least-loaded offline requests).  ``app.state.worker`` is the worker / router (``.stats`` counts batches / utterances /
     steps / chunks).  ``pool`` / ``pools``: the StreamPool(s) of the websocket sessions (default: one is built per streaming
-    ctc_greedy predictor)."""
+    ctc_greedy predictor).  ``stream_sample_rate``: the rate of the mono 16-bit PCM the websocket clients send (the reference's
+    protocol carries none and means 16000); a telephony deployment declares 8000 and the pool resamples on the device."""
     from fastapi import FastAPI, Request, WebSocket
     from starlette.websockets import WebSocketDisconnect
 
@@ -404,7 +413,7 @@ def create_app(predictor=None, max_batch=32, max_wait_ms=10.0, max_frames_out=0,
                 if is_end:
                     data = data[:-3]
                 try:
-                    res = await asyncio.wrap_future(worker.stream_feed(handle, data, is_end))
+                    res = await asyncio.wrap_future(worker.stream_feed(handle, data, is_end, stream_sample_rate))
                     if res is not None:
                         text = res['text']
                     await websocket.send_json({'code': 0, 'result': text})

@@ -40,6 +40,40 @@ STRIDE = SUBSAMPLING * DECODING_CHUNK                      # 64
 OVERLAP = CONTEXT - SUBSAMPLING                            # 3 frames carried over
 
 
+def device_resample_enabled():
+    """MASR_DEVICE_RESAMPLE=0 (A/B): off-rate audio is resampled on the host, chunk by chunk, as before"""
+    return os.environ.get('MASR_DEVICE_RESAMPLE', '1') != '0'
+
+
+def route_feed(audio_data, channels, samp_width, sample_rate, target_rate, c_framing, device_resample):
+    """where one ``StreamPool.feed`` goes -> ``('wire', int16 array)``: mono 16-bit PCM bytes at the model's rate, kept as they
+    are; ``('raw', samples, format, n_out)``: OFF-RATE audio the C framing hands to the device resampler as fed -- mono 16-bit
+    PCM bytes or an int16 vector (format 0), any other int / float array as the float32 mono samples ``AudioSegment`` makes of
+    it (format 1) -- with ``n_out = resampled_length(n, sample_rate, target_rate)`` samples at the model's rate (raises the host
+    resampler's ValueError for a chunk too short to give one); ``('host',)``: everything else -- multi-channel or non-16-bit
+    bytes, audio at the model's rate that is not wire PCM, the python framing (beam search, MASR_POOL_PY=1) and
+    MASR_DEVICE_RESAMPLE=0 -- through ``AudioSegment`` on the host, as before."""
+    from masr_amd.data_utils.resample import resampled_length
+    is_bytes = isinstance(audio_data, (bytes, bytearray, memoryview))
+    pcm = is_bytes and samp_width == 2 and channels == 1
+    if pcm and sample_rate == target_rate:
+        return ('wire', np.frombuffer(bytes(audio_data) if isinstance(audio_data, bytearray) else audio_data, '<i2'))
+    if not (c_framing and device_resample) or sample_rate == target_rate:
+        return ('host',)
+    if pcm:
+        x, fmt = np.frombuffer(bytes(audio_data) if isinstance(audio_data, bytearray) else audio_data, '<i2'), 0
+    elif isinstance(audio_data, np.ndarray):
+        if audio_data.dtype == np.int16 and audio_data.ndim == 1:
+            x, fmt = np.ascontiguousarray(audio_data), 0
+        else:
+            x, fmt = np.ascontiguousarray(AudioSegment._to_float(audio_data), np.float32), 1
+        if x.ndim != 1:
+            return ('host',)
+    else:
+        return ('host',)
+    return ('raw', x, fmt, resampled_length(x.shape[0], sample_rate, target_rate))
+
+
 class _HostStage:
     """Pinned host memory for the per-call uploads of a pool (pending samples, lengths, index arrays): a bump allocator whose
     copies to the device are asynchronous on the current stream, so the host never waits for the device between the launches
@@ -146,6 +180,8 @@ class StreamPool:
         self._c = None
         self._feeds = []
         self._packed = None
+        self._rate_slots = {}         # source rate -> slot of masr_pool_set_rate
+        self.device_resampled = 0     # off-rate feeds handed to the device resampler (masr_pool_step_rates) so far
         if not self.beam and not os.environ.get('MASR_POOL_PY'):
             self._lib = _lib.lib()
             h = C.c_void_p()
@@ -262,22 +298,38 @@ class StreamPool:
         self.sessions[handle] = _Session(handle, old.row, old.decoder)
         self._fed.pop(handle, None)
 
+    def _rate_slot(self, sample_rate):
+        """the pool's slot for a source rate: registered once (masr_pool_set_rate uploads the filter table)"""
+        slot = self._rate_slots.get(sample_rate)
+        if slot is None:
+            from masr_amd.data_utils.resample import device_table
+            pairs, num_table = device_table(sample_rate, self.sample_rate)
+            out = C.c_int32()
+            _lib.check(self._lib.masr_pool_set_rate(self._c, int(sample_rate), float(self.sample_rate) / sample_rate,
+                                                    pairs.ctypes.data_as(C.c_void_p), pairs.shape[0], num_table, C.byref(out)))
+            slot = self._rate_slots[sample_rate] = out.value
+        return slot
+
     def feed(self, handle, audio_data, is_end=False, channels=1, samp_width=2, sample_rate=16000):
         """queue raw PCM bytes (or a float / int numpy array) for a session (predict.py:260-272); processed by the next
-        ``step()``"""
+        ``step()``.  Audio off the model's rate is queued as fed, with its rate: the step resamples it on the device
+        (``route_feed``; MASR_DEVICE_RESAMPLE=0: on the host, here)."""
         self._alive()
         s = self.sessions[handle]
-        wire = isinstance(audio_data, (bytes, bytearray, memoryview)) and samp_width == 2 and channels == 1 and \
-            sample_rate == self.sample_rate
+        route = route_feed(audio_data, channels, samp_width, sample_rate, self.sample_rate, self._c is not None,
+                           device_resample_enabled())
+        wire = route[0] == 'wire'
         if wire and self._c is not None:
             # (the buffer is handed to masr_pool_step as it is: the array keeps the caller's bytes alive until the step has run)
-            self._feeds.append((handle, np.frombuffer(bytes(audio_data) if isinstance(audio_data, bytearray) else audio_data, '<i2'),
-                                0, bool(is_end)))
+            self._feeds.append((handle, route[1], 0, bool(is_end), -1))
+            return
+        if route[0] == 'raw':
+            self._feeds.append((handle, route[1], route[2], bool(is_end), self._rate_slot(sample_rate)))
             return
         if wire:
             # the common wire format: kept as int16 (a view of the caller's bytes); x / 2^15 -- the float32 value
             # from_pcm_bytes produces -- happens when the step stages the samples for the device
-            s.fresh.append(np.frombuffer(bytes(audio_data) if isinstance(audio_data, bytearray) else audio_data, '<i2'))
+            s.fresh.append(route[1])
         else:
             if isinstance(audio_data, np.ndarray):
                 seg = AudioSegment.from_ndarray(audio_data, sample_rate)
@@ -289,7 +341,7 @@ class StreamPool:
             if seg.sample_rate != self.sample_rate:
                 seg.resample(self.sample_rate)
             if self._c is not None:
-                self._feeds.append((handle, np.ascontiguousarray(seg.samples, np.float32), 1, bool(is_end)))
+                self._feeds.append((handle, np.ascontiguousarray(seg.samples, np.float32), 1, bool(is_end), -1))
                 return
             s.fresh.append(seg.samples)
         self._fed[handle] = bool(is_end) or self._fed.get(handle, False)
@@ -388,13 +440,19 @@ class StreamPool:
         ns, width = C.c_int32(), C.c_int32()
         h_out, st_out, rows_h, rows_d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         self._gain_error = None
-        rc = self._lib.masr_pool_step(self._c, n, handles.ctypes.data, ptrs.ctypes.data, counts.ctypes.data, fmts.ctypes.data,
-                                      ends.ctypes.data, C.cast(self._gain_cb, C.c_void_p), None, C.byref(ns), C.byref(h_out),
-                                      C.byref(st_out), C.byref(rows_h), C.byref(width), C.byref(rows_d),
-                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        slots = np.fromiter((f[4] for f in feeds), np.int32, n)
+        n_off = int((slots >= 0).sum())
+        tail = (C.cast(self._gain_cb, C.c_void_p), None, C.byref(ns), C.byref(h_out), C.byref(st_out), C.byref(rows_h), C.byref(width),
+                C.byref(rows_d), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        head = (self._c, n, handles.ctypes.data, ptrs.ctypes.data, counts.ctypes.data, fmts.ctypes.data, ends.ctypes.data)
+        if n_off:                                              # off-rate feeds: resampled on the device inside the step
+            rc = self._lib.masr_pool_step_rates(*head, slots.ctypes.data, *tail)
+        else:
+            rc = self._lib.masr_pool_step(*head, *tail)
         if self._gain_error is not None:
             raise self._gain_error
         _lib.check(rc)
+        self.device_resampled += n_off
         m, w = ns.value, width.value
         hs = np.ctypeslib.as_array(C.cast(h_out, C.POINTER(C.c_int32)), (m,))
         st = np.ctypeslib.as_array(C.cast(st_out, C.POINTER(C.c_int32)), (m,))
