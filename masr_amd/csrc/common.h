@@ -357,6 +357,20 @@ void launch_ffn_reduce(float* x, const float* partial, const float* b2, int M, i
                        const FfnPostLn* post, const float* xin = nullptr);
 void set_ffn_variant(int v);   // diagnostic ablations of the fused FFN kernel (0 = production)
 
+// Fragment-ordered weight copies, one layout per packing routine: the engine keeps every copy it has built under
+// (layout, device pointer of the source weights) -- engine.hip packed_of()
+enum PackLayout {
+    PACK_FFN_PC,        // launch_pack_ffn_pc: W1 | W2 of an FFN, keyed by W1
+    PACK_ROWS_PC,       // launch_pack_rows_pc: [N, 256] rows, N rounded up to a multiple of 256
+    PACK_FFN16,         // launch_pack_ffn16: W1 | W2 in the 16-row kernel's order, keyed by W1
+    PACK_ROWS16,        // launch_pack_rows16
+    PACK_CONV2_ROWS,    // launch_pack_conv2_rows: subsampling conv / embed projection weights [256, K]
+    PACK_FFN_DUAL,      // launch_pack_ffn_dual: W1 | W2 in the two-chain order, keyed by W1
+    PACK_ROWS_DUAL,     // launch_pack_rows_dual: the 768-row QKV tail of the two-chain kernel
+    PACK_FFN_COOP_W1,   // launch_pack_ffn_coop_w1: W1 as 16 x 16 x 4 fragments (W2: the PACK_FFN_PC copy)
+    PACK_FFN_X3,        // launch_pack_ffn_x3: (hi, lo) bf16 pieces of W1 | W2, keyed by W1
+};
+
 // ---- CTC prefix beam search on the GPU (beam_gpu.hip) ---------------------------------------------
 struct BeamGpuArgs {
     const int* cidx;       // [B * T_stride, K]

@@ -143,6 +143,15 @@ struct DevBuf {
     }
 };
 
+// one packed weight copy (masr_engine::packed): `a` alone, or the W1 | W2 pair of an FFN
+struct PackedW {
+    DevBuf a, b;
+    void release() {
+        a.release();
+        b.release();
+    }
+};
+
 // Pinned host staging for the per-call descriptor tables (AttSeq rows, cache pointers) of the streaming chunk step: the
 // copies to the device are truly asynchronous, so the chunk step does not stall the host on the work queued before it.
 // One call owns the area at a time: `begin` waits for the previous call's copies (normally long done).
@@ -306,11 +315,8 @@ struct masr_engine : EngineWs {
     int skip_padding = 7;            // masr_debug_set key 38: the offline Squeezeformer launches skip the all-padding row blocks of a batch
     void* beam_first_stream = nullptr;
     bool beam_first_set = false;
-    std::map<const float*, std::pair<DevBuf, DevBuf>> ffn_packed;  // fp32 FFN weights in fragment order (ffn_pc.hip VAR == 2), per W1 pointer
-    std::map<const float*, std::pair<DevBuf, DevBuf>> ffn_dual_packed;  // the same in the two-chain order of ffn_dual.hip (and its QKV tail weights)
-    std::map<const float*, std::pair<DevBuf, DevBuf>> x3_packed;   // exploratory split-bf16 FFN: packed weights per FFN (W1 pointer)
-    std::map<const float*, std::pair<DevBuf, DevBuf>> ffn16_packed;  // the same in the 16-row kernel's order (ffn_pc.hip ffn16_kernel), per W1 / tail / head pointer
-    std::map<const float*, std::pair<DevBuf, DevBuf>> conv2_packed;  // conv2 and embed projection weights in the row-block kernel's order (gemm_f32.hip conv2_rows_kernel)
+    // every fragment-ordered weight copy, built on first use by packed_of(): (common.h PackLayout, source device pointer) -> copy
+    std::map<std::pair<int, const float*>, PackedW> packed;
     long long* beam_prof = nullptr;                                             // debug: phase cycle counters (masr_debug_set key 2)                                               // GPU beam search scratch                               // DeepSpeech2 workspaces
     float *preln_w = nullptr, *preln_b = nullptr, *tr_dw_w = nullptr, *tr_dw_b = nullptr, *tr_pw_w = nullptr,
           *tr_pw_b = nullptr, *rec_w = nullptr, *rec_b = nullptr;
@@ -394,16 +400,13 @@ struct ProfScope {
 };
 
 // Packed weight copies are built on first use by whatever call needs them first, on that call's stream.  With two lanes a call
-// on ANOTHER stream may find the copy in the map while the packing launch is still queued: the call that packed records an event
-// behind itself, and calls on other streams wait for that event until it has completed.
+// on ANOTHER stream may find the copy in the cache while the packing launch is still queued: the call that packed (the cache has
+// grown under it) records an event behind itself, and calls on other streams wait for that event until it has completed.
 struct CallGuard {
     masr_engine* e;
     hipStream_t s;
     size_t n0;
-    static size_t packed_count(const masr_engine* e) {
-        return e->ffn_packed.size() + e->ffn_dual_packed.size() + e->x3_packed.size() + e->ffn16_packed.size() + e->conv2_packed.size();
-    }
-    CallGuard(masr_engine* e_, hipStream_t s_) : e(e_), s(s_), n0(packed_count(e_)) {
+    CallGuard(masr_engine* e_, hipStream_t s_) : e(e_), s(s_), n0(e_->packed.size()) {
         if (!e->pack_pending) return;
         if (hipEventQuery(e->pack_ev) == hipSuccess) {
             e->pack_pending = false;
@@ -413,7 +416,7 @@ struct CallGuard {
         }
     }
     ~CallGuard() {
-        if (packed_count(e) == n0) return;
+        if (e->packed.size() == n0) return;
         if (!e->pack_ev && hipEventCreateWithFlags(&e->pack_ev, hipEventDisableTiming) != hipSuccess) return;
         // (a pending event of another stream: this call waited for it at its start, so the new record covers it)
         if (hipEventRecord(e->pack_ev, s) == hipSuccess) {
@@ -446,32 +449,48 @@ void gemm(masr_engine* e, hipStream_t s, const float* A, int lda, const float* W
 }
 
 static int g_rowgemm_packed = 1;   // masr_debug_set key 25: 0 = the offline out-proj + pw1 chain and the CTC head stream their weights through LDS slabs (A/B)
-// fragment-ordered copy of a [N, 256] weight matrix (rows padded to a multiple of 256 with zeros), built on first use and kept
-const float* packed_rows_of(masr_engine* e, const float* W, int N, hipStream_t s) {
-    auto it = e->ffn_packed.find(W);
-    if (it == e->ffn_packed.end()) {
-        const int Np = (N + 255) / 256 * 256;
-        std::pair<DevBuf, DevBuf> pk;
-        if (pk.first.ensure((size_t)Np * 256 * sizeof(float))) return nullptr;
-        launch_pack_rows_pc(W, pk.first.as<float>(), Np, s, N);
-        it = e->ffn_packed.emplace(W, pk).first;
+// The packed copy of `src` in `layout`, built on first use and kept: buffers of bytes_a (and bytes_b, 0 = none), filled by
+// pack(copy, s), which issues the packing launch on the caller's stream.  nullptr = an allocation failed (masr_last_error says
+// which): what was allocated is freed and nothing is cached.
+template <class Pack>
+const PackedW* packed_of(masr_engine* e, PackLayout layout, const float* src, size_t bytes_a, size_t bytes_b, hipStream_t s,
+                         Pack&& pack) {
+    const std::pair<int, const float*> key(layout, src);
+    auto it = e->packed.find(key);
+    if (it == e->packed.end()) {
+        PackedW pk;
+        if (pk.a.ensure(bytes_a) || pk.b.ensure(bytes_b)) {
+            pk.release();
+            return nullptr;
+        }
+        pack(pk, s);
+        it = e->packed.emplace(key, pk).first;
     }
-    return it->second.first.as<float>();
+    return &it->second;
 }
 
-// fragment-order copies of an FFN's two weight matrices (ffn_pc.hip layout), cached per W1 pointer
-int packed_ffn_of(masr_engine* e, const float* w1, const float* w2, hipStream_t s, const float** p1, const float** p2) {
-    const int d = e->cfg.d_model;
-    auto it = e->ffn_packed.find(w1);
-    if (it == e->ffn_packed.end()) {
-        std::pair<DevBuf, DevBuf> pk;
-        CHK(pk.first.ensure((size_t)e->cfg.d_ff * d * sizeof(float)));
-        CHK(pk.second.ensure((size_t)e->cfg.d_ff * d * sizeof(float)));
-        launch_pack_ffn_pc(w1, w2, pk.first.as<float>(), pk.second.as<float>(), e->cfg.d_ff, s);
-        it = e->ffn_packed.emplace(w1, pk).first;
-    }
-    *p1 = it->second.first.as<float>();
-    *p2 = it->second.second.as<float>();
+// fragment-ordered copy of a [N, 256] weight matrix (rows padded to a multiple of 256 with zeros): launch_pack_rows_pc's order,
+// or launch_pack_rows16's (PACK_ROWS16)
+const float* packed_rows_of(masr_engine* e, const float* W, int N, hipStream_t s, PackLayout layout = PACK_ROWS_PC) {
+    const int Np = (N + 255) / 256 * 256;
+    const PackedW* pk = packed_of(e, layout, W, (size_t)Np * 256 * sizeof(float), 0, s, [&](const PackedW& p, hipStream_t st) {
+        (layout == PACK_ROWS16 ? launch_pack_rows16 : launch_pack_rows_pc)(W, p.a.as<float>(), Np, st, N);
+    });
+    return pk ? pk->a.as<float>() : nullptr;
+}
+
+// fragment-order copies of an FFN's two weight matrices, cached per W1 pointer: ffn_pc.hip's layout (PACK_FFN_PC,
+// launch_pack_ffn_pc), the 16-row kernel's (PACK_FFN16, launch_pack_ffn16) or the two-chain kernel's (PACK_FFN_DUAL, launch_pack_ffn_dual)
+typedef void (*PackFfnFn)(const float*, const float*, float*, float*, int, hipStream_t);
+int packed_ffn_of(masr_engine* e, const float* w1, const float* w2, hipStream_t s, const float** p1, const float** p2,
+                  PackLayout layout = PACK_FFN_PC, PackFfnFn pack = launch_pack_ffn_pc) {
+    const size_t bytes = (size_t)e->cfg.d_ff * e->cfg.d_model * sizeof(float);
+    const PackedW* pk = packed_of(e, layout, w1, bytes, bytes, s, [&](const PackedW& p, hipStream_t st) {
+        pack(w1, w2, p.a.as<float>(), p.b.as<float>(), e->cfg.d_ff, st);
+    });
+    if (!pk) return 1;
+    *p1 = pk->a.as<float>();
+    *p2 = pk->b.as<float>();
     return 0;
 }
 // the fused Squeezeformer stages cover these sizes (launch_sqz_stage's own checks, sqz_layer.hip): anything else takes the separate launches
@@ -480,23 +499,19 @@ static bool sqz_stage_supported(const masr_engine* e) {
     return e->cfg.d_model == 256 && e->cfg.d_ff % 128 == 0 && e->cfg.d_ff >= 256 && (K == 31 || K == 15);
 }
 
-void rowgemm(masr_engine* e, hipStream_t s, int pro, int epi, const float* A, int lda, const float* lnw,
-             const float* lnb, const float* W, const float* bias, float* C, int ldc, int M, int N, const float* R,
-             int ldr, float alpha, const int* lens, int mask_tp, int seq_t, int pad, int* out_idx, float* out_maxp,
-             int kind = PROF_GEMM, int mstride = 4, int out_seq_t = 0, int out_pad_l = 0, int out_pad_tot = 0,
-             int plane_cols = 0, long plane_stride = 0, int a_seq_t = 0, int a_seq_stride = 0, const AttSeq* kv_seqs = nullptr,
-             int kv_tq = 0) {
+// the common prefix of a row-block launch, C[M, N] = A[M, 256] . W[N, 256]^T + bias, with the defaults every launch but the odd one
+// takes (alpha 1, LayerNorm eps 1e-5, 4 feature frames per encoder frame in the pad masks); the rest is filled in by field name
+RowGemmArgs rg_args(const float* A, int lda, const float* W, const float* bias, float* C, int ldc, int M, int N) {
     RowGemmArgs a{};
-    a.A = A; a.lda = lda; a.lnw = lnw; a.lnb = lnb; a.W = W; a.bias = bias; a.C = C; a.ldc = ldc; a.M = M; a.N = N;
-    a.R = R; a.ldr = ldr; a.alpha = alpha; a.lens = lens; a.mask_tp = mask_tp; a.seq_t = seq_t; a.pad = pad;
-    a.out_idx = out_idx; a.out_maxp = out_maxp; a.eps = 1e-5f; a.mstride = mstride;
-    a.out_seq_t = out_seq_t; a.out_pad_l = out_pad_l; a.out_pad_tot = out_pad_tot;
-    a.plane_cols = plane_cols; a.plane_stride = plane_stride; a.a_seq_t = a_seq_t; a.a_seq_stride = a_seq_stride;
-    a.kv_seqs = kv_seqs; a.kv_tq = kv_tq;
+    a.A = A; a.lda = lda; a.W = W; a.bias = bias; a.C = C; a.ldc = ldc; a.M = M; a.N = N;
+    a.alpha = 1.f; a.eps = 1e-5f; a.mstride = 4;
+    return a;
+}
+void rowgemm(masr_engine* e, hipStream_t s, int pro, int epi, RowGemmArgs a, int kind = PROF_GEMM) {
     // full row-block launches (the K-split kernel of few row blocks reads W itself) take the packed copy of their weights
-    if (g_rowgemm_packed && M >= 112 * 32 && pro != RG_PRO_HIST && pro != RG_PRO_DWCONV && (epi == RG_EPI_CTC || N % 256 == 0))
-        a.Wp = packed_rows_of(e, W, N, s);
-    ProfScope ps(e, s, kind, 2.0 * M * (double)N * 256);
+    if (g_rowgemm_packed && a.M >= 112 * 32 && pro != RG_PRO_HIST && pro != RG_PRO_DWCONV && (epi == RG_EPI_CTC || a.N % 256 == 0))
+        a.Wp = packed_rows_of(e, a.W, a.N, s);
+    ProfScope ps(e, s, kind, 2.0 * a.M * (double)a.N * 256);
     launch_rowgemm(a, pro, epi, s);
 }
 
@@ -747,26 +762,7 @@ void masr_destroy(masr_engine* e) {
         kv.second.second.release();
     }
     for (auto& kv : e->ms_ws) kv.second.release();
-    for (auto& kv : e->x3_packed) {
-        kv.second.first.release();
-        kv.second.second.release();
-    }
-    for (auto& kv : e->ffn_packed) {
-        kv.second.first.release();
-        kv.second.second.release();
-    }
-    for (auto& kv : e->ffn_dual_packed) {
-        kv.second.first.release();
-        kv.second.second.release();
-    }
-    for (auto& kv : e->ffn16_packed) {
-        kv.second.first.release();
-        kv.second.second.release();
-    }
-    for (auto& kv : e->conv2_packed) {
-        kv.second.first.release();
-        kv.second.second.release();
-    }
+    for (auto& kv : e->packed) kv.second.release();
     for (auto& ev : e->prof_events) {
         (void)hipEventDestroy(ev.first);
         (void)hipEventDestroy(ev.second);
@@ -774,22 +770,16 @@ void masr_destroy(masr_engine* e) {
     delete e;
 }
 
-// The fragment-ordered weight copies (ffn_packed / ffn_dual_packed / x3_packed / ffn16_packed / conv2_packed) are built on first use and keyed by the device
-// pointer of the weights they were packed from.  A reload (masr_load_tensor on a finalized engine, then masr_finalize) re-uploads
-// into the SAME device buffers when the sizes are unchanged, so the keys would still match while the copies hold the old
-// values: every reload drops them (after the device has drained: launches in flight may still read them).
+// The fragment-ordered weight copies (masr_engine::packed) are built on first use and keyed by the device pointer of the weights
+// they were packed from.  A reload (masr_load_tensor on a finalized engine, then masr_finalize) replaces those weights: every
+// reload drops the copies (after the device has drained: launches in flight may still read them), so that no key can outlive
+// the values it was packed from, whichever device buffers the new upload lands in (tests/test_gpu_ffn_packed.py).
 static void drop_packed_weights(masr_engine* e) {
-    if (e->ffn_packed.empty() && e->ffn_dual_packed.empty() && e->x3_packed.empty() && e->ffn16_packed.empty() && e->conv2_packed.empty())
-        return;
+    if (e->packed.empty()) return;
     (void)hipSetDevice(e->cfg.device_id);
     (void)hipDeviceSynchronize();
-    for (auto* m : {&e->ffn_packed, &e->ffn_dual_packed, &e->x3_packed, &e->ffn16_packed, &e->conv2_packed}) {
-        for (auto& kv : *m) {
-            kv.second.first.release();
-            kv.second.second.release();
-        }
-        m->clear();
-    }
+    for (auto& kv : e->packed) kv.second.release();
+    e->packed.clear();
 }
 
 int masr_load_tensor(masr_engine* e, const char* name, const float* host, const int64_t* shape, int32_t ndim) {
@@ -1040,187 +1030,117 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
         launch_dwconv_ln_silu(head->glu, head->dw_w, head->dw_b, head->lnw, head->lnb, e->dwo.as<float>(), M / head->seq_t,
                               head->seq_t, head->ktaps, 1e-5f, s, head->gconst);
         float* x = e->x.as<float>();
-        rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->dwo.as<float>(), d, nullptr, nullptr, head->W, head->bias, x, d, M, d, x, d,
-                1.f, head->lens, head->lens ? head->seq_t : 0, 0, 0, nullptr, nullptr, PROF_GEMM, head->mstride);
+        {
+            RowGemmArgs g = rg_args(e->dwo.as<float>(), d, head->W, head->bias, x, d, M, d);
+            g.R = x; g.ldr = d; g.lens = head->lens; g.mask_tp = head->lens ? head->seq_t : 0; g.mstride = head->mstride;
+            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
+        }
     }
     if (tail && tail->pre_lnw && !want_tail)          // the deferred LayerNorm of the previous layer, as its own launch
         launch_layernorm(e->x.as<float>(), tail->pre_lnw, tail->pre_lnb, e->x.as<float>(), M, 1e-5f, 0, 0, nullptr, s);
+    float* x = e->x.as<float>();
     if (x3) {
-        // packed (hi, lo) weights of this FFN, built on first use and kept (keyed by the W1 pointer): + 4 MB per FFN
-        auto it = e->x3_packed.find(w1);
-        if (it == e->x3_packed.end()) {
-            std::pair<DevBuf, DevBuf> pk;
-            CHK(pk.first.ensure(ffn_x3_packed_elems(dff) * sizeof(unsigned short)));
-            CHK(pk.second.ensure(ffn_x3_packed_elems(dff) * sizeof(unsigned short)));
-            launch_pack_ffn_x3(w1, w2, pk.first.as<unsigned short>(), pk.second.as<unsigned short>(), dff, s);
-            it = e->x3_packed.emplace(w1, pk).first;
-        }
-        float* x = e->x.as<float>();
+        // packed (hi, lo) weights of this FFN: + 4 MB per FFN
+        const size_t bytes = ffn_x3_packed_elems(dff) * sizeof(unsigned short);
+        const PackedW* pk = packed_of(e, PACK_FFN_X3, w1, bytes, bytes, s, [&](const PackedW& p, hipStream_t st) {
+            launch_pack_ffn_x3(w1, w2, p.a.as<unsigned short>(), p.b.as<unsigned short>(), dff, st);
+        });
+        if (!pk) return 1;
         {
             ProfScope ps(e, s, PROF_FFN1, 4.0 * M * (double)dff * d);
-            if (!launch_ffn_x3(x, lnw, lnb, it->second.first.as<unsigned short>(), b1, it->second.second.as<unsigned short>(), b2, M,
-                               dff, 1e-5f, scale, s))
+            if (!launch_ffn_x3(x, lnw, lnb, pk->a.as<unsigned short>(), b1, pk->b.as<unsigned short>(), b2, M, dff, 1e-5f, scale, s))
                 return fail("ffn(): the split-bf16 FFN kernel rejected the sizes");
         }
         if (tail_done) *tail_done = false;
         if (post_y) launch_layernorm(x, post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
         return 0;
     }
+    const float *kw1 = w1, *kw2 = w2;
     // few rows, one chunk of 128 hidden units per workgroup: the kernel in which all eight waves work on both products (key 35)
     if (g_ffn_coop && nsplit > 1 && nsplit == dff / 128 && !want_head && !x3 && d == 256) {
-        // packed copies: ffn_pc.hip's (W2 is shared with it) + the 16 x 16 x 4 fragment order of W1 (its own map: keyed by W1)
-        auto it = e->ffn_packed.find(w1);
-        if (it == e->ffn_packed.end()) {
-            std::pair<DevBuf, DevBuf> pk;
-            CHK(pk.first.ensure((size_t)dff * d * sizeof(float)));
-            CHK(pk.second.ensure((size_t)dff * d * sizeof(float)));
-            launch_pack_ffn_pc(w1, w2, pk.first.as<float>(), pk.second.as<float>(), dff, s);
-            it = e->ffn_packed.emplace(w1, pk).first;
-        }
-        auto ic = e->ffn_dual_packed.find(w1 + 1);            // (+ 1: a key of its own next to ffn_dual.hip's entries for the same W1)
-        if (ic == e->ffn_dual_packed.end()) {
-            std::pair<DevBuf, DevBuf> pk;
-            CHK(pk.first.ensure((size_t)dff * d * sizeof(float)));
-            launch_pack_ffn_coop_w1(w1, pk.first.as<float>(), dff, s);
-            ic = e->ffn_dual_packed.emplace(w1 + 1, pk).first;
-        }
+        // packed copies: ffn_pc.hip's (W2 is shared with it) + the 16 x 16 x 4 fragment order of W1
+        CHK(packed_ffn_of(e, w1, w2, s, &kw1, &kw2));
+        const PackedW* pc = packed_of(e, PACK_FFN_COOP_W1, w1, (size_t)dff * d * sizeof(float), 0, s,
+                                      [&](const PackedW& p, hipStream_t st) { launch_pack_ffn_coop_w1(w1, p.a.as<float>(), dff, st); });
+        if (!pc) return 1;
         ProfScope psc(e, s, PROF_FFN1, 4.0 * M * (double)dff * d);
-        launch_ffn_coop(e->x.as<float>(), lnw, lnb, ic->second.first.as<float>(), b1, it->second.second.as<float>(), M, dff, 1e-5f,
-                        affine, e->ffpart.as<float>(), s);
-        launch_ffn_reduce(e->x.as<float>(), e->ffpart.as<float>(), b2, M, nsplit, scale, s, post_y ? &post : nullptr);
+        launch_ffn_coop(x, lnw, lnb, pc->a.as<float>(), b1, kw2, M, dff, 1e-5f, affine, e->ffpart.as<float>(), s);
+        launch_ffn_reduce(x, e->ffpart.as<float>(), b2, M, nsplit, scale, s, post_y ? &post : nullptr);
         if (tail_done) *tail_done = false;
         return 0;
     }
     ProfScope ps(e, s, want_tail ? PROF_FFN_TAIL : want_head ? PROF_FFN_HEAD : PROF_FFN1,
                  4.0 * M * (double)dff * d + (want_tail ? 2.0 * M * (double)tail->N * d : 0.0) + (want_head ? 2.0 * M * (double)d * d : 0.0));
     // full launches stream PACKED weight copies straight into registers (ffn_pc.hip VAR == 2; built on first use, + 4 MB per FFN)
-    const float *kw1 = w1, *kw2 = w2;
     const bool packed = g_ffn_packed && (nsplit == 1 || g_ffn_packed >= 2) && d == 256;      // (key 23 = 2: the d_ff-split launches of small M too)
     // 16-row blocks, two workgroups per CU (ffn_pc.hip ffn16_kernel): every full-d_ff launch of packed weights it covers; it reads
     // copies of its own order, so the 32-row copies are not built for it
     const bool use16 = packed && nsplit == 1 && g_ffn16 && !affine && dff % 128 == 0 && !(want_tail && tail->N % 256) &&
                        !(want_head && head->ktaps != 15 && head->ktaps != 7);
-    if (packed && !use16) {
-        auto it = e->ffn_packed.find(w1);
-        if (it == e->ffn_packed.end()) {
-            std::pair<DevBuf, DevBuf> pk;
-            CHK(pk.first.ensure((size_t)dff * d * sizeof(float)));
-            CHK(pk.second.ensure((size_t)dff * d * sizeof(float)));
-            launch_pack_ffn_pc(w1, w2, pk.first.as<float>(), pk.second.as<float>(), dff, s);
-            it = e->ffn_packed.emplace(w1, pk).first;
-        }
-        kw1 = it->second.first.as<float>();
-        kw2 = it->second.second.as<float>();
-    }
-    // ... and so do the row-local stages that ride on the launch (QKV tail, pointwise_conv2 head)
-    FfnTail ptail{};
-    FfnHead phead{};
-    auto packed_rows = [&](const float* W, int N, const float** out) -> int {
-        auto it = e->ffn_packed.find(W);
-        if (it == e->ffn_packed.end()) {
-            std::pair<DevBuf, DevBuf> pk;
-            CHK(pk.first.ensure((size_t)N * d * sizeof(float)));
-            launch_pack_rows_pc(W, pk.first.as<float>(), N, s);
-            it = e->ffn_packed.emplace(W, pk).first;
-        }
-        *out = it->second.first.as<float>();
-        return 0;
-    };
+    if (packed && !use16) CHK(packed_ffn_of(e, w1, w2, s, &kw1, &kw2));
+    // ... and so do the row-local stages that ride on the launch (QKV tail, pointwise_conv2 head): copies of the stage descriptors
+    // whose W is the packed copy in the chosen kernel's order
+    FfnTail ptail = tail ? *tail : FfnTail{};
+    FfnHead phead = head ? *head : FfnHead{};
     // two accumulator chains per wave (ffn_dual.hip): same arithmetic in the same order, its own packing order
     if (packed && nsplit == 1 && g_ffn_dual && dff % 256 == 0 && dff >= 512 && !(want_tail && tail->N != 768) && !(affine && (want_tail || want_head))) {
-        auto it = e->ffn_dual_packed.find(w1);
-        if (it == e->ffn_dual_packed.end()) {
-            std::pair<DevBuf, DevBuf> pk;
-            CHK(pk.first.ensure((size_t)dff * d * sizeof(float)));
-            CHK(pk.second.ensure((size_t)dff * d * sizeof(float)));
-            launch_pack_ffn_dual(w1, w2, pk.first.as<float>(), pk.second.as<float>(), dff, s);
-            it = e->ffn_dual_packed.emplace(w1, pk).first;
-        }
+        const float *p1, *p2;
+        CHK(packed_ffn_of(e, w1, w2, s, &p1, &p2, PACK_FFN_DUAL, launch_pack_ffn_dual));
         if (want_tail) {
-            ptail = *tail;
-            auto tw = e->ffn_dual_packed.find(tail->W);
-            if (tw == e->ffn_dual_packed.end()) {
-                std::pair<DevBuf, DevBuf> pk;
-                CHK(pk.first.ensure((size_t)768 * d * sizeof(float)));
-                launch_pack_rows_dual(tail->W, pk.first.as<float>(), s);
-                tw = e->ffn_dual_packed.emplace(tail->W, pk).first;
-            }
-            ptail.W = tw->second.first.as<float>();
+            const PackedW* tw = packed_of(e, PACK_ROWS_DUAL, tail->W, (size_t)768 * d * sizeof(float), 0, s,
+                                          [&](const PackedW& p, hipStream_t st) { launch_pack_rows_dual(tail->W, p.a.as<float>(), st); });
+            if (!tw) return 1;
+            ptail.W = tw->a.as<float>();
         }
-        if (want_head) {
-            phead = *head;
-            CHK(packed_rows(head->W, d, &phead.W));
-        }
-        const int done = launch_ffn_dual(e->x.as<float>(), lnw, lnb, it->second.first.as<float>(), b1, it->second.second.as<float>(),
-                                         b2, M, dff, 1e-5f, scale, affine, s, want_tail ? &ptail : nullptr, want_head ? &phead : nullptr);
+        if (want_head && !(phead.W = packed_rows_of(e, head->W, d, s))) return 1;
+        const int done = launch_ffn_dual(x, lnw, lnb, p1, b1, p2, b2, M, dff, 1e-5f, scale, affine, s, want_tail ? &ptail : nullptr,
+                                         want_head ? &phead : nullptr);
         if (done < 0) return fail("ffn(): the two-chain FFN kernel rejected the launch");
         if (want_head && done != 4) return fail("ffn(): head stage was not launched");
         if (tail_done) *tail_done = done == 2;
-        if (post_y) launch_layernorm(e->x.as<float>(), post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
+        if (post_y) launch_layernorm(x, post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
         return 0;
     }
     if (use16) {
-        auto p16 = [&](const float* W, int N, const float** out) -> int {
-            auto it = e->ffn16_packed.find(W);
-            if (it == e->ffn16_packed.end()) {
-                std::pair<DevBuf, DevBuf> pk;
-                CHK(pk.first.ensure((size_t)N * d * sizeof(float)));
-                launch_pack_rows16(W, pk.first.as<float>(), N, s);
-                it = e->ffn16_packed.emplace(W, pk).first;
-            }
-            *out = it->second.first.as<float>();
-            return 0;
-        };
-        auto it = e->ffn16_packed.find(w1);
-        if (it == e->ffn16_packed.end()) {
-            std::pair<DevBuf, DevBuf> pk;
-            CHK(pk.first.ensure((size_t)dff * d * sizeof(float)));
-            CHK(pk.second.ensure((size_t)dff * d * sizeof(float)));
-            launch_pack_ffn16(w1, w2, pk.first.as<float>(), pk.second.as<float>(), dff, s);
-            it = e->ffn16_packed.emplace(w1, pk).first;
-        }
-        if (want_tail) {
-            ptail = *tail;
-            CHK(p16(tail->W, tail->N, &ptail.W));
-        }
-        if (want_head) {
-            phead = *head;
-            CHK(p16(head->W, d, &phead.W));
-        }
-        const int done = launch_ffn16(e->x.as<float>(), lnw, lnb, it->second.first.as<float>(), b1, it->second.second.as<float>(), b2, M,
-                                      dff, 1e-5f, scale, s, want_tail ? &ptail : nullptr, want_head ? &phead : nullptr);
+        const float *p1, *p2;
+        CHK(packed_ffn_of(e, w1, w2, s, &p1, &p2, PACK_FFN16, launch_pack_ffn16));
+        if (want_tail && !(ptail.W = packed_rows_of(e, tail->W, tail->N, s, PACK_ROWS16))) return 1;
+        if (want_head && !(phead.W = packed_rows_of(e, head->W, d, s, PACK_ROWS16))) return 1;
+        const int done = launch_ffn16(x, lnw, lnb, p1, b1, p2, b2, M, dff, 1e-5f, scale, s, want_tail ? &ptail : nullptr,
+                                      want_head ? &phead : nullptr);
         if (done < 0) return fail("ffn(): the 16-row FFN kernel rejected the launch");
         if (want_head && done != 4) return fail("ffn(): head stage was not launched");
         if (tail_done) *tail_done = done == 2;
-        if (post_y) launch_layernorm(e->x.as<float>(), post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
+        if (post_y) launch_layernorm(x, post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
         return 0;
     }
-    if (packed && want_tail && tail->N % 256 == 0) {
-        ptail = *tail;
-        CHK(packed_rows(tail->W, tail->N, &ptail.W));
-        tail = &ptail;
-    }
+    if (packed && want_tail && tail->N % 256 == 0 && !(ptail.W = packed_rows_of(e, tail->W, tail->N, s))) return 1;
     if (packed && want_head) {
-        phead = *head;
-        CHK(packed_rows(head->W, d, &phead.W));
+        if (!(phead.W = packed_rows_of(e, head->W, d, s))) return 1;
         if (split_head) {
             CHK(e->xh.ensure((size_t)M * d * sizeof(float)));
             phead.xout = e->xh.as<float>();
         }
-        head = &phead;
     }
-    const int done = launch_ffn_fused(e->x.as<float>(), lnw, lnb, kw1, b1, kw2, b2, M, dff, 1e-5f, scale, affine,
+    const int done = launch_ffn_fused(x, lnw, lnb, kw1, b1, kw2, b2, M, dff, 1e-5f, scale, affine,
                                       nsplit > 1 ? e->ffpart.as<float>() : nullptr, nsplit, s, post_y ? &post : nullptr,
-                                      want_tail ? tail : nullptr, want_head ? head : nullptr, packed);
+                                      want_tail ? &ptail : nullptr, want_head ? &phead : nullptr, packed);
     if (done < 0) return fail("ffn(): launch rejected");
     if (want_head && !(done & 4)) return fail("ffn(): head stage was not launched");
     if (tail_done) *tail_done = done == 2;
-    if (post_y && !(done & 1)) launch_layernorm(e->x.as<float>(), post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
+    if (post_y && !(done & 1)) launch_layernorm(x, post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
     return 0;
 }
 
 static int g_hot_weights = 0;      // masr_debug_set key 19 (timing experiment only): every chunk-step layer runs on layer 0's weights
 static int g_embed_split = 1;      // masr_debug_set key 15: 0 = the offline embed projection never splits K
+// W [N = 256, K] in the row-block kernel's fragment order (gemm_f32.hip conv2_rows_kernel): the subsampling convs and the embed projection
+static const float* packed_conv2_rows_of(masr_engine* e, const float* W, int N, int K, hipStream_t s) {
+    const PackedW* pk = packed_of(e, PACK_CONV2_ROWS, W, (size_t)N * K * sizeof(float), 0, s,
+                                  [&](const PackedW& p, hipStream_t st) { launch_pack_conv2_rows(W, p.a.as<float>(), K, st); });
+    return pk ? pk->a.as<float>() : nullptr;
+}
+
 // one subsampling conv over channels-last activations as an implicit GEMM (a: geometry, C, lens; amode A_CONV2 / A_CONV5):
 // full-width row blocks with the weights packed at first use, split K for few rows.  feats [nseq, a.Tin, n_mels] given: the
 // conv reads conv1's output (computed in the row blocks' gather, or by conv1 into x1 first); else it reads x_in.
@@ -1228,14 +1148,7 @@ static int subsampling_conv(masr_engine* e, hipStream_t s, GemmArgs a, int amode
     const int d = e->cfg.d_model;
     const int tiles = ((a.M + 63) / 64) * ((a.N + 63) / 64);
     if (tiles >= 640 && g_conv2_rows && a.N == 256) {   // full-width row blocks: the weights in the kernel's fragment order, packed at first use
-        auto it = e->conv2_packed.find(a.W);
-        if (it == e->conv2_packed.end()) {
-            std::pair<DevBuf, DevBuf> pk;
-            CHK(pk.first.ensure((size_t)a.N * a.K * sizeof(float)));
-            launch_pack_conv2_rows(a.W, pk.first.as<float>(), a.K, s);
-            it = e->conv2_packed.emplace(a.W, pk).first;
-        }
-        a.Wp = it->second.first.as<float>();
+        if (!(a.Wp = packed_conv2_rows_of(e, a.W, a.N, a.K, s))) return 1;
         if (feats && amode == A_CONV2 && g_conv1_fused && !g_bf16x3 && gemm_conv2_rows(a)) {    // conv1 computed in the row blocks' A gather: no x1, no conv1 launch
             a.feats = feats; a.mean = e->cmvn_mean; a.istd = e->cmvn_istd; a.c1w = e->conv1_w; a.c1b = e->conv1_b;
             a.Fin = e->cfg.n_mels;
@@ -1324,16 +1237,7 @@ int embed(masr_engine* e, hipStream_t s, const float* feats, int nseq, int T, in
             // B = 32 x 10 s: 124 tiles of 128x128 -- four K quarters on 8-wave workgroups = 496 workgroups, two per CU, four
             // waves per SIMD: 163 + 11 us (GEMM + reduction) against 180 + 9 us for two K halves on 64x128 tiles and 203 us unsplit
             // (full-width 64-row blocks with the weights packed at first use, the same K quarters: 124 x 4 = 496 workgroups, key 42)
-            if (g_embed_rows && d == 256 && (F2 * d) % 32 == 0) {
-                auto it = e->conv2_packed.find(e->embed_w);
-                if (it == e->conv2_packed.end()) {
-                    std::pair<DevBuf, DevBuf> pk;
-                    CHK(pk.first.ensure((size_t)a.N * a.K * sizeof(float)));
-                    launch_pack_conv2_rows(e->embed_w, pk.first.as<float>(), a.K, s);
-                    it = e->conv2_packed.emplace(e->embed_w, pk).first;
-                }
-                a.Wp = it->second.first.as<float>();
-            }
+            if (g_embed_rows && d == 256 && (F2 * d) % 32 == 0 && !(a.Wp = packed_conv2_rows_of(e, e->embed_w, a.N, a.K, s))) return 1;
             CHK(e->ffpart.ensure((size_t)4 * M * d * sizeof(float)));
             launch_gemm_splitk(a, e->ffpart.as<float>(), 4, s);
         } else if (g_embed_split && tiles >= 128 && wide >= 200 && wide <= 320) {
@@ -1379,16 +1283,19 @@ int conv_module(masr_engine* e, hipStream_t s, const LayerW& w, const EncodeCtx&
         // glu buffer already filled by mhsa_out_pw1 (fused out-projection -> LayerNorm -> pointwise_conv1 -> GLU)
     } else if (hist) {
         launch_layernorm(x, w.ln_conv_w, w.ln_conv_b, e->lnpad.as<float>(), M, 1e-5f, c.Tq, pad, c.lens, s);
-        rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_GLU, e->lnpad.as<float>(), d, nullptr, nullptr, w.pw1_w, w.pw1_b,
-                e->glu.as<float>(), d, Mp, 2 * d, nullptr, 0, 1.f, nullptr, 0, 0, 0, nullptr, nullptr);
+        rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_GLU,
+                rg_args(e->lnpad.as<float>(), d, w.pw1_w, w.pw1_b, e->glu.as<float>(), d, Mp, 2 * d));
     } else {
         // only the real rows go through the GEMM (M = nseq*Tq: 248 workgroups at B=32 x 10 s, one per CU); they land in the
         // padded layout, whose history rows are the constant glu(bias) that the depthwise kernel substitutes itself
         // (non-causal build, streaming: False: the depthwise Conv1d pads the GLU output with (K-1)/2 zero rows on both sides --
         //  those rows of the glu buffer are zeroed once per call by the caller)
-        rowgemm(e, s, RG_PRO_LN_PAD, RG_EPI_GLU, x, d, w.ln_conv_w, w.ln_conv_b, w.pw1_w, w.pw1_b, e->glu.as<float>(), d,
-                M, 2 * d, nullptr, 0, 1.f, c.lens, 0, c.Tq, 0, nullptr, nullptr, PROF_GEMM, mstride, c.Tq,
-                e->cfg.causal ? pad : pad / 2, pad);
+        {
+            RowGemmArgs g = rg_args(x, d, w.pw1_w, w.pw1_b, e->glu.as<float>(), d, M, 2 * d);
+            g.lnw = w.ln_conv_w; g.lnb = w.ln_conv_b; g.lens = c.lens; g.seq_t = c.Tq; g.mstride = mstride; g.out_seq_t = c.Tq;
+            g.out_pad_l = e->cfg.causal ? pad : pad / 2; g.out_pad_tot = pad;
+            rowgemm(e, s, RG_PRO_LN_PAD, RG_EPI_GLU, g);
+        }
     }
     if (pw2_later) return 0;       // the rest of the module is the head stage of the FFN launch that follows
     const float* gconst = (hist || !e->cfg.causal) ? nullptr : w.gconst;
@@ -1407,8 +1314,11 @@ int conv_module(masr_engine* e, hipStream_t s, const LayerW& w, const EncodeCtx&
     else
         launch_dwconv_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), c.nseq, c.Tq, K,
                               1e-5f, s, gconst);
-    rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->dwo.as<float>(), d, nullptr, nullptr, w.pw2_w, w.pw2_b, x, d, M, d, x, d,
-            1.f, c.lens, c.lens ? c.Tq : 0, 0, 0, nullptr, nullptr, PROF_GEMM, mstride);
+    {
+        RowGemmArgs g = rg_args(e->dwo.as<float>(), d, w.pw2_w, w.pw2_b, x, d, M, d);
+        g.R = x; g.ldr = d; g.lens = c.lens; g.mask_tp = c.lens ? c.Tq : 0; g.mstride = mstride;
+        rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
+    }
     return 0;
 }
 
@@ -1454,14 +1364,16 @@ int conv_module_stream(masr_engine* e, hipStream_t s, const LayerW& w, int n, in
 // kv_seqs (streaming): the k | v columns are appended to the streams' caches by the projection itself
 void mhsa(masr_engine* e, hipStream_t s, const LayerW& w, int M, const AttSeq* kv_seqs = nullptr, int kv_tq = 0) {
     const int d = e->cfg.d_model;
-    rowgemm(e, s, RG_PRO_LN, RG_EPI_STORE, e->x.as<float>(), d, w.ln_mha_w, w.ln_mha_b, w.wqkv, w.bqkv, e->qkv.as<float>(),
-            3 * d, M, 3 * d, nullptr, 0, 1.f, nullptr, 0, 0, 0, nullptr, nullptr, PROF_GEMM, 4, 0, 0, 0, 0, 0, 0, 0, kv_seqs, kv_tq);
+    RowGemmArgs g = rg_args(e->x.as<float>(), d, w.wqkv, w.bqkv, e->qkv.as<float>(), 3 * d, M, 3 * d);
+    g.lnw = w.ln_mha_w; g.lnb = w.ln_mha_b; g.kv_seqs = kv_seqs; g.kv_tq = kv_tq;
+    rowgemm(e, s, RG_PRO_LN, RG_EPI_STORE, g);
 }
 void mhsa_out(masr_engine* e, hipStream_t s, const LayerW& w, int M) {
     const int d = e->cfg.d_model;
     float* x = e->x.as<float>();
-    rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->att.as<float>(), d, nullptr, nullptr, w.wo, w.bo, x, d, M, d, x, d, 1.f,
-            nullptr, 0, 0, 0, nullptr, nullptr);
+    RowGemmArgs g = rg_args(e->att.as<float>(), d, w.wo, w.bo, x, d, M, d);
+    g.R = x; g.ldr = d;
+    rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
 }
 
 // offline conformer layer: attention out-projection + residual and the conv module's LayerNorm + pointwise_conv1 + GLU in ONE
@@ -1698,15 +1610,13 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
             HIPCHK(hipMemcpyAsync(e->xsave.p, x, (size_t)B * Tq * d * sizeof(float), hipMemcpyDeviceToDevice, s));
             launch_time_reduce_dw(x, e->tr_dw_w, e->tr_dw_b, lens, e->xred.as<float>(), B, Tq, mstride, s);
             const int Lr = (Tq + 1) / 2;
-            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_STORE, e->xred.as<float>(), d, nullptr, nullptr, e->tr_pw_w, e->tr_pw_b, x, d,
-                    B * Lr, d, nullptr, 0, 1.f, nullptr, 0, 0, 0, nullptr, nullptr);
+            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_STORE, rg_args(e->xred.as<float>(), d, e->tr_pw_w, e->tr_pw_b, x, d, B * Lr, d));
             Tq = Lr; mstride = 8; pstride = 2;
             CHK(new_resolution());
         }
         if (i == e->recover_idx && e->reduce_idx >= 0) {
             // x = saved + Linear(repeat_interleave(x, 2))[:, :T0]   (encoder.py:199-205)
-            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_STORE, x, d, nullptr, nullptr, e->rec_w, e->rec_b, e->xred.as<float>(), d,
-                    B * Tq, d, nullptr, 0, 1.f, nullptr, 0, 0, 0, nullptr, nullptr);
+            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_STORE, rg_args(x, d, e->rec_w, e->rec_b, e->xred.as<float>(), d, B * Tq, d));
             launch_recover_add(e->xsave.as<float>(), e->xred.as<float>(), x, B, T0, Tq, s);
             Tq = T0; mstride = 4; pstride = 1;
             CHK(new_resolution());
@@ -1717,8 +1627,11 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
         const bool fused = g_sqz_fused_blocks > 0 && (M + 31) / 32 >= g_sqz_fused_blocks && sqz_stage_supported(e);
         // x = LN1(x + MHSA(ada(x)))
         if (!qkv_ready)
-            rowgemm(e, s, RG_PRO_AFFINE, RG_EPI_STORE, x, d, w.att_s, w.att_b, w.wqkv, w.bqkv, e->qkv.as<float>(), 3 * d, M,
-                    3 * d, nullptr, 0, 1.f, nullptr, 0, 0, 0, nullptr, nullptr);
+            {
+                RowGemmArgs g = rg_args(x, d, w.wqkv, w.bqkv, e->qkv.as<float>(), 3 * d, M, 3 * d);
+                g.lnw = w.att_s; g.lnb = w.att_b;
+                rowgemm(e, s, RG_PRO_AFFINE, RG_EPI_STORE, g);
+            }
         qkv_ready = false;
         {
             ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * B);
@@ -1766,19 +1679,29 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
             qkv_ready = next_same;
             continue;
         }
-        rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->att.as<float>(), d, nullptr, nullptr, w.wo, w.bo, x, d, M, d, x, d, 1.f,
-                nullptr, 0, 0, 0, nullptr, nullptr);
+        {
+            RowGemmArgs g = rg_args(e->att.as<float>(), d, w.wo, w.bo, x, d, M, d);
+            g.R = x; g.ldr = d;
+            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
+        }
         launch_layernorm(x, w.ln1_w, w.ln1_b, x, M, 1e-5f, 0, 0, nullptr, s);
         // x = LN2(x + FFN1(ada(x)))   (the post-LayerNorm rides on the d_ff-split reduction where the block runs split: few row
         // blocks, i.e. exactly the launches that take this branch by default; otherwise ffn() launches it)
         CHK(ffn(e, s, M, w.f1_s, w.f1_b, w.f1_w1, w.f1_b1, w.f1_w2, w.f1_b2, 1.0f, 1, w.ln2_w, w.ln2_b, x));
         // x = LN3(x + Conv(ada(x)))   symmetric depthwise conv: (K-1)/2 zero rows on both sides of the GLU output
-        rowgemm(e, s, RG_PRO_AFFINE, RG_EPI_GLU, x, d, w.cv_s, w.cv_b, w.pw1_w, w.pw1_b, e->glu.as<float>(), d, M, 2 * d,
-                nullptr, 0, 1.f, lens, 0, Tq, 0, nullptr, nullptr, PROF_GEMM, mstride, Tq, pad_l, 2 * half);
+        {
+            RowGemmArgs g = rg_args(x, d, w.pw1_w, w.pw1_b, e->glu.as<float>(), d, M, 2 * d);
+            g.lnw = w.cv_s; g.lnb = w.cv_b; g.lens = lens; g.seq_t = Tq; g.mstride = mstride; g.out_seq_t = Tq;
+            g.out_pad_l = pad_l; g.out_pad_tot = 2 * half;
+            rowgemm(e, s, RG_PRO_AFFINE, RG_EPI_GLU, g);
+        }
         launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.bn_scale, w.bn_shift, e->dwo.as<float>(), B, Tq, K, s,
                               causal ? w.gconst : nullptr);
-        rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->dwo.as<float>(), d, nullptr, nullptr, w.pw2_w, w.pw2_b, x, d, M, d, x,
-                d, 1.f, lens, Tq, 0, 0, nullptr, nullptr, PROF_GEMM, mstride);
+        {
+            RowGemmArgs g = rg_args(e->dwo.as<float>(), d, w.pw2_w, w.pw2_b, x, d, M, d);
+            g.R = x; g.ldr = d; g.lens = lens; g.mask_tp = Tq; g.mstride = mstride;
+            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
+        }
         launch_layernorm(x, w.ln3_w, w.ln3_b, x, M, 1e-5f, 0, 0, nullptr, s);
         // x = LN4(x + FFN2(ada(x)))
         CHK(ffn(e, s, M, w.f2_s, w.f2_b, w.f2_w1, w.f2_b1, w.f2_w2, w.f2_b2, 1.0f, 1, w.ln4_w, w.ln4_b, i == L - 1 ? enc_out : x));
@@ -1839,16 +1762,23 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
             if (Tq != T0) return fail("grouped attention after the stride layer is not supported");
             // q | k | v -> planar, time-padded buffers; attention over T/3 positions with d_k' = 192
             if (!qkv_done)
-                rowgemm(e, s, RG_PRO_LN, RG_EPI_STORE, x, d, w.ln_mha_w, w.ln_mha_b, w.wqkv, w.bqkv, qp, d, M, 3 * d, nullptr,
-                        0, 1.f, nullptr, 0, 0, 0, nullptr, nullptr, PROF_GEMM, mstride, Tq, 0, Tpad - Tq, d, (long)plane);
+                {
+                    RowGemmArgs g = rg_args(x, d, w.wqkv, w.bqkv, qp, d, M, 3 * d);
+                    g.lnw = w.ln_mha_w; g.lnb = w.ln_mha_b; g.mstride = mstride; g.out_seq_t = Tq; g.out_pad_tot = Tpad - Tq;
+                    g.plane_cols = d; g.plane_stride = (long)plane;
+                    rowgemm(e, s, RG_PRO_LN, RG_EPI_STORE, g);
+                }
             {
                 ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * B / G);
                 launch_attention_grouped(seq_g, B, Tg, H, G, w.ptab, Tq, w.pos_u, w.pos_v, s, chunk);
             }
             if (fused) mhsa_out_pw1(e, s, w, ctx0, mstride, Ki, e->attp.as<float>(), Tq, Tpad);
             else
-                rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->attp.as<float>(), d, nullptr, nullptr, w.wo, w.bo, x, d, M, d, x, d,
-                        1.f, nullptr, 0, 0, 0, nullptr, nullptr, PROF_GEMM, mstride, 0, 0, 0, 0, 0, Tq, Tpad);
+                {
+                    RowGemmArgs g = rg_args(e->attp.as<float>(), d, w.wo, w.bo, x, d, M, d);
+                    g.R = x; g.ldr = d; g.mstride = mstride; g.a_seq_t = Tq; g.a_seq_stride = Tpad;
+                    rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
+                }
         } else {
             if (!qkv_done) mhsa(e, s, w, M);
             {
@@ -1873,19 +1803,29 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
             // StrideConformerEncoderLayer (encoder.py:454-545): x = AvgPool(x) + conv_module_stride2(LN(x))
             const int K = layer_kernel(e, i), pad = K - 1, T2 = (Tq + 1) / 2;
             if (causal)      // the K - 1 history rows go through pointwise_conv1 + GLU like the reference's left padding
-                rowgemm(e, s, RG_PRO_LN_PAD, RG_EPI_GLU, x, d, w.ln_conv_w, w.ln_conv_b, w.pw1_w, w.pw1_b, e->glu.as<float>(), d,
-                        B * (Tq + pad), 2 * d, nullptr, 0, 1.f, lens, 0, Tq, pad, nullptr, nullptr, PROF_GEMM, mstride);
+                {
+                    RowGemmArgs g = rg_args(x, d, w.pw1_w, w.pw1_b, e->glu.as<float>(), d, B * (Tq + pad), 2 * d);
+                    g.lnw = w.ln_conv_w; g.lnb = w.ln_conv_b; g.lens = lens; g.seq_t = Tq; g.pad = pad; g.mstride = mstride;
+                    rowgemm(e, s, RG_PRO_LN_PAD, RG_EPI_GLU, g);
+                }
             else             // symmetric: the real rows land between (K - 1) / 2 zero rows on either side (same stride-2 window sum)
-                rowgemm(e, s, RG_PRO_LN_PAD, RG_EPI_GLU, x, d, w.ln_conv_w, w.ln_conv_b, w.pw1_w, w.pw1_b, e->glu.as<float>(), d,
-                        M, 2 * d, nullptr, 0, 1.f, lens, 0, Tq, 0, nullptr, nullptr, PROF_GEMM, mstride, Tq, pad / 2, pad);
+                {
+                    RowGemmArgs g = rg_args(x, d, w.pw1_w, w.pw1_b, e->glu.as<float>(), d, M, 2 * d);
+                    g.lnw = w.ln_conv_w; g.lnb = w.ln_conv_b; g.lens = lens; g.seq_t = Tq; g.mstride = mstride;
+                    g.out_seq_t = Tq; g.out_pad_l = pad / 2; g.out_pad_tot = pad;
+                    rowgemm(e, s, RG_PRO_LN_PAD, RG_EPI_GLU, g);
+                }
             launch_dwconv_stride2_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), B, Tq, K,
                                           1e-5f, s);
             launch_avgpool2(x, e->xsave.as<float>(), B, Tq, s);
             Tq = T2; mstride *= 2; pstride *= 2; M = B * Tq;
             if (!causal)     // half rate, kernel 7 from here on: a new padded layout
                 HIPCHK(hipMemsetAsync(e->glu.p, 0, (size_t)B * (Tq + layer_kernel(e, i + 1) - 1) * d * sizeof(float), s));
-            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->dwo.as<float>(), d, nullptr, nullptr, w.pw2_w, w.pw2_b, x, d, M, d,
-                    e->xsave.as<float>(), d, 1.f, lens, Tq, 0, 0, nullptr, nullptr, PROF_GEMM, mstride);
+            {
+                RowGemmArgs g = rg_args(e->dwo.as<float>(), d, w.pw2_w, w.pw2_b, x, d, M, d);
+                g.R = e->xsave.as<float>(); g.ldr = d; g.lens = lens; g.mask_tp = Tq; g.mstride = mstride;
+                rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
+            }
             launch_attseq_full(seq_r, e->qkv.as<float>(), e->att.as<float>(), lens, B, Tq, mstride, s);
         } else {
             CHK(conv_module(e, s, w, ctx, false, layer_kernel(e, i), mstride));
@@ -2187,8 +2127,11 @@ int masr_ctc_greedy_frames(masr_engine* e, const float* enc_dev, int32_t M, int3
     // through the tiled GEMM (vocabulary spread over the CUs) into a workspace and the softmax statistics are a second launch
     if ((M + 31) / 32 < g_ctc_fused_blocks) return ctc_head(e, enc_dev, M, nullptr, 0, argmax_dev, maxprob_dev, (hipStream_t)stream);
     // fused: logits GEMM + online softmax statistics + argmax, nothing but (idx, prob) leaves the chip
-    rowgemm(e, (hipStream_t)stream, RG_PRO_PLAIN, RG_EPI_CTC, enc_dev, e->cfg.d_model, nullptr, nullptr, e->ctc_w,
-            e->ctc_b, nullptr, 0, M, e->cfg.vocab_size, nullptr, 0, 1.f, nullptr, 0, 0, 0, argmax_dev, maxprob_dev);
+    {
+        RowGemmArgs g = rg_args(enc_dev, e->cfg.d_model, e->ctc_w, e->ctc_b, nullptr, 0, M, e->cfg.vocab_size);
+        g.out_idx = argmax_dev; g.out_maxp = maxprob_dev;
+        rowgemm(e, (hipStream_t)stream, RG_PRO_PLAIN, RG_EPI_CTC, g);
+    }
     LAUNCHCHK();
     return 0;
 }
@@ -2876,23 +2819,27 @@ static int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector
         if (l == e->reduce_idx) {
             HIPCHK(hipMemcpyAsync(e->xsave.p, x, (size_t)n * T0 * d * sizeof(float), hipMemcpyDeviceToDevice, s));
             launch_time_reduce_dw(x, e->tr_dw_w, e->tr_dw_b, nullptr, e->xred.as<float>(), n, T0, 4, s);
-            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_STORE, e->xred.as<float>(), d, nullptr, nullptr, e->tr_pw_w, e->tr_pw_b, x, d,
-                    n * Tr, d, nullptr, 0, 1.f, nullptr, 0, 0, 0, nullptr, nullptr);
+            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_STORE, rg_args(e->xred.as<float>(), d, e->tr_pw_w, e->tr_pw_b, x, d, n * Tr, d));
             Tq = Tr;
         }
         if (l == e->recover_idx && e->reduce_idx >= 0) {
-            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_STORE, x, d, nullptr, nullptr, e->rec_w, e->rec_b, e->xred.as<float>(), d,
-                    n * Tq, d, nullptr, 0, 1.f, nullptr, 0, 0, 0, nullptr, nullptr);
+            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_STORE, rg_args(x, d, e->rec_w, e->rec_b, e->xred.as<float>(), d, n * Tq, d));
             launch_recover_add(e->xsave.as<float>(), e->xred.as<float>(), x, n, T0, Tq, s);
             Tq = T0;
         }
         const int M = n * Tq;
         const AttSeq* seqs = e->attseq.as<AttSeq>() + (size_t)l * n;
-        rowgemm(e, s, RG_PRO_AFFINE, RG_EPI_STORE, x, d, w.att_s, w.att_b, w.wqkv, w.bqkv, e->qkv.as<float>(), 3 * d, M,
-                3 * d, nullptr, 0, 1.f, nullptr, 0, 0, 0, nullptr, nullptr, PROF_GEMM, 4, 0, 0, 0, 0, 0, 0, 0, seqs, Tq);
+        {
+            RowGemmArgs g = rg_args(x, d, w.wqkv, w.bqkv, e->qkv.as<float>(), 3 * d, M, 3 * d);
+            g.lnw = w.att_s; g.lnb = w.att_b; g.kv_seqs = seqs; g.kv_tq = Tq;
+            rowgemm(e, s, RG_PRO_AFFINE, RG_EPI_STORE, g);
+        }
         launch_attention(seqs, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, reduced(l) ? 2 : 1, s);
-        rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->att.as<float>(), d, nullptr, nullptr, w.wo, w.bo, x, d, M, d, x, d, 1.f,
-                nullptr, 0, 0, 0, nullptr, nullptr);
+        {
+            RowGemmArgs g = rg_args(e->att.as<float>(), d, w.wo, w.bo, x, d, M, d);
+            g.R = x; g.ldr = d;
+            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
+        }
         launch_layernorm(x, w.ln1_w, w.ln1_b, x, M, 1e-5f, 0, 0, nullptr, s);
         CHK(ffn(e, s, M, w.f1_s, w.f1_b, w.f1_w1, w.f1_b1, w.f1_w2, w.f1_b2, 1.0f, 1, w.ln2_w, w.ln2_b, x));
         // conv module: [cnn cache | ada(x)] -> pointwise_conv1 + GLU -> causal depthwise + BatchNorm + SiLU -> pointwise_conv2
@@ -2911,8 +2858,11 @@ static int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector
             }
         }
         launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.bn_scale, w.bn_shift, e->dwo.as<float>(), n, Tq, K, s);
-        rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->dwo.as<float>(), d, nullptr, nullptr, w.pw2_w, w.pw2_b, x, d, M, d, x,
-                d, 1.f, nullptr, 0, 0, 0, nullptr, nullptr);
+        {
+            RowGemmArgs g = rg_args(e->dwo.as<float>(), d, w.pw2_w, w.pw2_b, x, d, M, d);
+            g.R = x; g.ldr = d;
+            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
+        }
         launch_layernorm(x, w.ln3_w, w.ln3_b, x, M, 1e-5f, 0, 0, nullptr, s);
         CHK(ffn(e, s, M, w.f2_s, w.f2_b, w.f2_w1, w.f2_b1, w.f2_w2, w.f2_b2, 1.0f, 1, w.ln4_w, w.ln4_b,
                 l == L - 1 ? e->enc.as<float>() : x));
@@ -3028,12 +2978,19 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
         const AttSeq* seqs = e->attseq.as<AttSeq>() + (size_t)l * n;
         CHK(ffn(e, s, M, w.ln_ffm_w, w.ln_ffm_b, w.ffm_w1, w.ffm_b1, w.ffm_w2, w.ffm_b2));
         if (layer_grouped(e, l)) {
-            rowgemm(e, s, RG_PRO_LN, RG_EPI_STORE, x, d, w.ln_mha_w, w.ln_mha_b, w.wqkv, w.bqkv, qp, d, M, 3 * d, nullptr, 0,
-                    1.f, nullptr, 0, 0, 0, nullptr, nullptr, PROF_GEMM, 4, Tq, 0, Tpad - Tq, d, (long)plane);
+            {
+                RowGemmArgs g = rg_args(x, d, w.wqkv, w.bqkv, qp, d, M, 3 * d);
+                g.lnw = w.ln_mha_w; g.lnb = w.ln_mha_b; g.out_seq_t = Tq; g.out_pad_tot = Tpad - Tq; g.plane_cols = d;
+                g.plane_stride = (long)plane;
+                rowgemm(e, s, RG_PRO_LN, RG_EPI_STORE, g);
+            }
             launch_kv_append_planar(pc_dev + (size_t)l * n, n, Tq, s);
             launch_attention_grouped(seqs, n, Tg, H, G, w.ptab, 0, w.pos_u, w.pos_v, s);
-            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->attp.as<float>(), d, nullptr, nullptr, w.wo, w.bo, x, d, M, d, x, d,
-                    1.f, nullptr, 0, 0, 0, nullptr, nullptr, PROF_GEMM, 4, 0, 0, 0, 0, 0, Tq, Tpad);
+            {
+                RowGemmArgs g = rg_args(e->attp.as<float>(), d, w.wo, w.bo, x, d, M, d);
+                g.R = x; g.ldr = d; g.a_seq_t = Tq; g.a_seq_stride = Tpad;
+                rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
+            }
         } else {
             mhsa(e, s, w, M, seqs, Tq);                 // k | v rows go straight to the streams' caches
             launch_attention(seqs, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, rate(l), s);
@@ -3045,15 +3002,18 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
             launch_cnn_cache_move(cptr, e->lnpad.as<float>(), n, Tq, pad, 0, s);
             // StrideConformerEncoderLayer (encoder.py:454-545): x = AvgPool(x) + conv_module_stride2([cache | LN(x)])
             launch_layernorm(x, w.ln_conv_w, w.ln_conv_b, e->lnpad.as<float>(), M, 1e-5f, Tq, pad, nullptr, s);
-            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_GLU, e->lnpad.as<float>(), d, nullptr, nullptr, w.pw1_w, w.pw1_b,
-                    e->glu.as<float>(), d, n * (Tq + pad), 2 * d, nullptr, 0, 1.f, nullptr, 0, 0, 0, nullptr, nullptr);
+            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_GLU,
+                    rg_args(e->lnpad.as<float>(), d, w.pw1_w, w.pw1_b, e->glu.as<float>(), d, n * (Tq + pad), 2 * d));
             launch_cnn_cache_move(cptr + (size_t)L * n, e->lnpad.as<float>(), n, Tq, pad, 1, s);
             launch_dwconv_stride2_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K,
                                           1e-5f, s);
             launch_avgpool2(x, e->xsave.as<float>(), n, Tq, s);
             M = n * T2;
-            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, e->dwo.as<float>(), d, nullptr, nullptr, w.pw2_w, w.pw2_b, x, d, M, d,
-                    e->xsave.as<float>(), d, 1.f, nullptr, 0, 0, 0, nullptr, nullptr);
+            {
+                RowGemmArgs g = rg_args(e->dwo.as<float>(), d, w.pw2_w, w.pw2_b, x, d, M, d);
+                g.R = e->xsave.as<float>(); g.ldr = d;
+                rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
+            }
         } else {
             CHK(conv_module_stream(e, s, w, n, Tq, cptr, cptr + (size_t)L * n, K));
         }

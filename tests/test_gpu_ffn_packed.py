@@ -33,7 +33,7 @@ def test_packed_weights_are_bit_identical_to_the_slab_pipeline(kind, streaming):
             probs = eng.ctc_probs(out[v])
             out[('p', v)] = probs.clone()
     finally:
-        eng.lib.masr_debug_set(eng.h, 23, 1)
+        eng.lib.masr_debug_set(eng.h, 23, 2)               # (the default: the d_ff-split launches of few rows read packed copies too)
     torch.cuda.synchronize()
     assert torch.equal(out[0], out[1]) and torch.equal(out[('p', 0)], out[('p', 1)])
     assert float(out[1].abs().max()) > 0
@@ -66,7 +66,7 @@ def test_two_chain_ffn_is_bit_identical_to_the_single_chain_kernel(kind, streami
             out[v] = eng.encode_full(feats, frames, -1).clone()
             out[('p', v)] = eng.ctc_probs(out[v]).clone()
     finally:
-        eng.lib.masr_debug_set(eng.h, 24, 1)
+        eng.lib.masr_debug_set(eng.h, 24, 0)               # (the default: the single-chain kernel)
     torch.cuda.synchronize()
     assert torch.isfinite(out[1]).all() and float(out[1].abs().max()) > 0
     assert torch.equal(out[0], out[1]), float((out[0] - out[1]).abs().max())
@@ -107,6 +107,54 @@ def test_packed_row_block_projections_are_bit_identical_to_the_slab_pipeline(kin
     for a, b in zip(out[0], out[1]):
         assert torch.equal(a, b)
     eng.close()
+
+
+def test_reloaded_weights_replace_every_packed_copy():
+    """The packed copies are keyed by the device pointer of their source weights and built on first use; a reload
+    (masr_load_tensor for every tensor of a finalized engine, then masr_finalize) drops every one of them, so none can outlive
+    the weights it was packed from.  Offline (32 x 6-10 s, every packed path) and one streaming chunk step of 4 sessions (the
+    d_ff-split packed launches): a reloaded engine computes exactly what a fresh one does, and not what it did before."""
+    from masr_amd.engine import HipEngine, _stream, check, positional_table
+    from masr_amd.utils import synthetic
+    V = 512
+    sds = [synthetic.conformer_state_dict(seed, V) for seed in (0, 1)]
+    rng = np.random.default_rng(3)
+    lens = rng.integers(96000, 160001, 32).astype(np.int32)
+    pcm = synthetic.synthetic_pcm(32, 160000, seed=9)
+    for i, l in enumerate(lens):
+        pcm[i, l:] = 0
+    pcm, lens = torch.from_numpy(pcm).cuda(), torch.from_numpy(lens).cuda()
+    chunk = (torch.randn(4, 67, 80, generator=torch.Generator().manual_seed(4)) * 3 + 13).cuda()
+
+    def offline(eng):
+        feats, frames = eng.fbank_batch(pcm, lens)
+        enc = eng.encode_full(feats, frames, -1)
+        return enc.clone(), eng.ctc_probs(enc).clone()
+
+    def chunk_step(eng):
+        sids = [eng.stream_open(200) for _ in range(4)]
+        probs, idx, mp = eng.encode_chunk(sids, chunk, want_probs=True, want_argmax=True)
+        for sid in sids:
+            eng.stream_close(sid)
+        return probs.clone(), mp.clone()
+
+    for streaming, run in ((False, offline), (True, chunk_step)):
+        eng = HipEngine(sds[0], vocab_size=V, streaming=streaming)
+        fresh = HipEngine(sds[1], vocab_size=V, streaming=streaming)
+        try:
+            first = run(eng)
+            for name, t in sds[1].items():
+                eng._load(name, t)
+            eng._load('__pos_table__', positional_table(5000, eng.d_model))
+            check(eng.lib.masr_finalize(eng.h, _stream()))
+            again, want = run(eng), run(fresh)
+            torch.cuda.synchronize()
+            for a, b, c in zip(again, want, first):
+                assert torch.isfinite(a).all() and torch.equal(a, b)
+                assert not torch.equal(a, c)
+        finally:
+            eng.close()
+            fresh.close()
 
 
 @needs_experiments()
