@@ -27,7 +27,8 @@ typedef struct masr_engine masr_engine;
  * + vocabulary size (masr/trainer.py:174-203 builds the model from exactly these). */
 typedef struct masr_config {
     int32_t model_kind;      /* 0 = conformer                                                   */
-    int32_t d_model;         /* encoder_conf.output_size        (256)                           */
+    int32_t d_model;         /* encoder_conf.output_size        (256); deepspeech2: encoder_conf.rnn_size, a multiple of
+                              * 256 in [256, 2048] (1024 in configs/deepspeech2.yml)           */
     int32_t heads;           /* encoder_conf.attention_heads    (4)                             */
     int32_t d_ff;            /* encoder_conf.linear_units       (2048)                          */
     int32_t num_blocks;      /* encoder_conf.num_blocks         (12)                            */
@@ -476,13 +477,18 @@ int masr_select_lane(masr_engine* e, int32_t lane);
  *      conv2 (key 40; bit-identical)
  *  42  0 = the K quarters of the offline embed projection run on 128x128 tiles instead of full-width 64-row blocks with packed
  *      weights (bit-identical)
+ *  43  hidden units per workgroup of the DeepSpeech2 matrix-core recurrent step (4 < B <= 32): 8 = production (4 units at rnn_size
+ *      <= 512, 8 above); 16 = 16 units (GRU at rnn_size 1024 only); -8 = 8 units at every size (bit-identical: a column's dot
+ *      product does not depend on the grouping).  PROCESS-WIDE, unlike the other keys: it holds for every engine of the process,
+ *      whichever handle sets it
  *  20  1 = EXPLORATORY split-bf16 precision mode (not the reference's fp32 arithmetic, never the contract path): conv2, the embed
  *      projection and the other launches of the generic GEMM in the offline forward as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on
  *      the bf16 matrix pipe, fp32 accumulation (csrc/gemm_bf16x3.hip); 3 = also the FFN, unfused (slower than the fused fp32 FFN) */
 int masr_debug_set(masr_engine* e, int32_t key, int32_t value);
 
 /* Profiling: time every launch of one kernel class with HIP events on the launch stream.
- * kind: 0 none, 1 gemm (all), 2 ffn-w1 gemm, 3 conv2 gemm, 4 attention, 5 fbank.
+ * kind: 0 none, 1 gemm (all), 2 ffn-w1 gemm, 3 conv2 gemm, 4 attention, 5 fbank, 8 the step loop of a DeepSpeech2 recurrent
+ * layer (one "launch" = the T' step launches of one layer).
  * masr_profile_read synchronises the events and returns total ms / launch count / flops since reset. */
 int masr_profile_select(masr_engine* e, int32_t kind);
 int masr_profile_read(masr_engine* e, double* total_ms, int64_t* launches, double* flops, int32_t reset);

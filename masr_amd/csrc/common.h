@@ -408,14 +408,16 @@ size_t beam_gpu_lds_bytes(int beam, int K, bool use_lm);
 int launch_beam_search(const BeamGpuArgs& a, int B, hipStream_t s);   // 1: sizes not supported
 
 // ---- DeepSpeech2 (lstm.hip, gru.hip) ------------------------------------------------------
-void launch_lstm_step(const float* gx, const float* whh, const float* h_prev, float* h_next, float* c, float* out,
-                      const int* lens, int B, int T, int H, int step, int ndir, hipStream_t s);
+// step launchers: H = every multiple of 256 in [256, 2048]; 1 (and nothing launched) for any other H
+int launch_lstm_step(const float* gx, const float* whh, const float* h_prev, float* h_next, float* c, float* out,
+                     const int* lens, int B, int T, int H, int step, int ndir, hipStream_t s);
+void set_lstm_mfma_units(int u);
 void launch_layernorm_generic(const float* x, const float* w, const float* b, float* y, int M, int N, float eps,
                               hipStream_t s);
 void launch_ds2_lens(const int* lens, int B, int Tq, int* out, hipStream_t s);
 // use_gru: True (gru.hip): gx [B*T][ndir*3H] holds W_ih x + b_ih + [b_hr, b_hz, 0]; bhn [ndir][H]
-void launch_gru_step(const float* gx, const float* whh, const float* bhn, const float* h_prev, float* h_next, float* out,
-                     const int* lens, int B, int T, int H, int step, int ndir, hipStream_t s);
+int launch_gru_step(const float* gx, const float* whh, const float* bhn, const float* h_prev, float* h_next, float* out,
+                    const int* lens, int B, int T, int H, int step, int ndir, hipStream_t s);
 void set_gru_mfma_units(int u);
 
 // ---- attention ---------------------------------------------------------------------------

@@ -254,7 +254,7 @@ struct GBeam {        // device-resident streaming CTC prefix beam search (masr_
 };
 
 enum ProfKind { PROF_NONE = 0, PROF_GEMM = 1, PROF_FFN1 = 2, PROF_CONV2 = 3, PROF_ATT = 4, PROF_FBANK = 5,
-                PROF_FFN_TAIL = 6, PROF_FFN_HEAD = 7 };     // 2 = the plain fused FFN kernel; 6 = its variant with the QKV tail stage, 7 = with the conv-module head stage (own kernel names)
+                PROF_FFN_TAIL = 6, PROF_FFN_HEAD = 7, PROF_RNN = 8 };     // 2 = the plain fused FFN kernel; 6 = its variant with the QKV tail stage, 7 = with the conv-module head stage (own kernel names)
 
 }  // namespace
 
@@ -689,7 +689,9 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
     // n_mels = input feature size of the model: 80 (fbank), n_mfcc (mfcc) or 161 (linear) -- audio_featurizer.py:141-154
     if (cfg->n_mels < 7 || cfg->n_mels > 512) return fail("input feature size (n_mels) must be in [7, 512]");
     if (cfg->model_kind == 3) {
-        if (cfg->d_model != 1024) return fail("deepspeech2: the LSTM step kernel is specialised for rnn_size=1024");
+        if (cfg->d_model < 256 || cfg->d_model > 2048 || cfg->d_model % 256)
+            return fail("deepspeech2: rnn_size (masr_config.d_model) must be a multiple of 256 in [256, 2048], got " +
+                        std::to_string(cfg->d_model));
         if (cfg->num_blocks <= 0) return fail("deepspeech2: num_rnn_layers must be positive");
         if (cfg->reserved[0] != 0 && cfg->reserved[0] != 1)
             return fail("deepspeech2: the recurrent cell (masr_config.reserved[0], encoder_conf.use_gru) must be 0 = LSTM or 1 = GRU");
@@ -1975,11 +1977,15 @@ static int ds2_forward(masr_engine* e, hipStream_t s, const float* feats, const 
         // (the whole sequence of a layer as one cooperative launch with W_hh resident in registers and a barrier in global memory
         //  per step was built and measured in round 6: 10.0 against 6.0 ms at B = 1, 26.4 against 25.7 ms at B = 32 --
         //  tools/studies/lstm_seq_study.hip)
-        for (int step = 0; step < Tq; ++step) {
-            const float* hp = hbuf + (size_t)(step & 1) * hsz;
-            float* hn = hbuf + (size_t)((step + 1) & 1) * hsz;
-            if (gru) launch_gru_step(e->gx.as<float>(), w.whh, w.bhn, hp, hn, e->rnn_out.as<float>(), xl, nseq, Tq, H, step, ndir, s);
-            else launch_lstm_step(e->gx.as<float>(), w.whh, hp, hn, cbuf, e->rnn_out.as<float>(), xl, nseq, Tq, H, step, ndir, s);
+        {   // PROF_RNN times exactly the Tq step launches of this layer
+            ProfScope ps(e, s, PROF_RNN, 2.0 * nseq * (double)Tq * ndir * G * H * H);    // the step loop of one layer (Tq launches)
+            for (int step = 0; step < Tq; ++step) {
+                const float* hp = hbuf + (size_t)(step & 1) * hsz;
+                float* hn = hbuf + (size_t)((step + 1) & 1) * hsz;
+                const int miss = gru ? launch_gru_step(e->gx.as<float>(), w.whh, w.bhn, hp, hn, e->rnn_out.as<float>(), xl, nseq, Tq, H, step, ndir, s)
+                                     : launch_lstm_step(e->gx.as<float>(), w.whh, hp, hn, cbuf, e->rnn_out.as<float>(), xl, nseq, Tq, H, step, ndir, s);
+                if (miss) return fail("deepspeech2: no recurrent step kernel for rnn_size=" + std::to_string(H));
+            }
         }
         if (st) {     // GRU: the reference returns final_state_c = final_state_h (gru.py), so h goes to both slots
             const float* hfin = hbuf + (size_t)(Tq & 1) * hsz;
@@ -3268,7 +3274,7 @@ int masr_debug_set(masr_engine* e, int32_t key, int32_t value) {
     else if (key == 40) g_conv2_rows = value;
     else if (key == 41) g_conv1_fused = value;
     else if (key == 42) g_embed_rows = value;
-    else if (key == 43) set_gru_mfma_units(value);
+    else if (key == 43) { set_gru_mfma_units(value); set_lstm_mfma_units(value); }
     else if (key == 17) set_gemm_waves(value);
     else if (key == 18) set_conv1_nt(value);
     else if (key == 16) { e->prof_stride = value > 1 ? value : 1; e->prof_seen = 0; }

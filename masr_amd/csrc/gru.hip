@@ -31,7 +31,8 @@ static __device__ __forceinline__ void gru_cell(const float* __restrict__ gx, co
 }
 
 // Wave-per-unit form (B <= 4 and B > 32): a wave owns ONE hidden unit, its 3 gate rows of W_hh stay in registers (48 values
-// per lane), and walks over the batch; 1024 units / 4 waves = 256 workgroups per direction.
+// per lane at rnn_size 1024, 3 H / 64 in general), and walks over the batch; H units / 4 waves = H / 4 workgroups per direction.
+// H is instantiated for every multiple of 256 from 256 to 2048, as for the LSTM (lstm.hip).
 template <int H>
 __global__ __launch_bounds__(256) void gru_step_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
                                                        const float* __restrict__ bhn, const float* __restrict__ h_prev,
@@ -80,7 +81,8 @@ __global__ __launch_bounds__(256) void gru_step_kernel(const float* __restrict__
 // Matrix-core form (4 < B <= 32): U hidden units x 3 gates of a workgroup against the h_{t-1} rows of 16 * BT sequences
 // (v_mfma_f32_16x16x4_f32: D[16 sequences, 16 columns] += h[16, 4] . W^T[4, 16]).  Column c of the workgroup's 3U columns is
 // gate c / U of unit c % U, in NT = ceil(3U / 16) tiles of 16; U = 8 leaves the last 8 columns of the second tile empty (their
-// lanes load nothing), U = 16 fills three tiles exactly but gives half as many workgroups.  8 waves split K = 1024 (128 each),
+// lanes load nothing), U = 16 fills three tiles exactly but gives half as many workgroups, U = 4 is 12 columns of one tile and
+// twice as many workgroups.  H / U workgroups per direction.  8 waves split K = H (H / 8 each, in steps of 16: H % 128 == 0),
 // partial tiles are summed through LDS, then one thread per (sequence, unit) applies the gates.  Operand fetch as in
 // lstm_step_mfma_kernel: 16-byte vectors along k, element i of every lane's vector feeds MFMA i of a group of four.
 template <int H, int U, int BT>
@@ -156,29 +158,48 @@ __global__ __launch_bounds__(512) void gru_step_mfma_kernel(const float* __restr
     }
 }
 
-static int g_gru_units = 8;       // masr_debug_set key 43: hidden units per workgroup of the matrix-core form (8 or 16)
-void set_gru_mfma_units(int u) { g_gru_units = u == 16 ? 16 : 8; }
+// masr_debug_set key 43: hidden units per workgroup of the matrix-core form.  8 = the product's choice (4 units at rnn_size <= 512,
+// where 8 leave most CUs without a workgroup: measured 10 - 16 % per step, docs/LAB_NOTES.md 18; 8 units above), 16 = 16 units at
+// rnn_size 1024, -8 = 8 units at every size (the A/B side of the small sizes; the same bits)
+static int g_gru_units = 8;
+void set_gru_mfma_units(int u) { g_gru_units = u == 16 || u == -8 ? u : 8; }
 
-template <int U>
+template <int H, int U>
 static void launch_gru_mfma(const float* gx, const float* whh, const float* bhn, const float* h_prev, float* h_next, float* out,
                             const int* lens, int B, int T, int step, int ndir, hipStream_t s) {
-    const dim3 grid(1024 / U, ndir), blk(512);
+    const dim3 grid(H / U, ndir), blk(512);
     if (B <= 16)
-        hipLaunchKernelGGL((gru_step_mfma_kernel<1024, U, 1>), grid, blk, 0, s, gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir);
+        hipLaunchKernelGGL((gru_step_mfma_kernel<H, U, 1>), grid, blk, 0, s, gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir);
     else
-        hipLaunchKernelGGL((gru_step_mfma_kernel<1024, U, 2>), grid, blk, 0, s, gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir);
+        hipLaunchKernelGGL((gru_step_mfma_kernel<H, U, 2>), grid, blk, 0, s, gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir);
 }
 
-void launch_gru_step(const float* gx, const float* whh, const float* bhn, const float* h_prev, float* h_next, float* out,
-                     const int* lens, int B, int T, int H, int step, int ndir, hipStream_t s) {
-    if (H != 1024) return;
+template <int H>
+static void launch_gru_step_h(const float* gx, const float* whh, const float* bhn, const float* h_prev, float* h_next, float* out,
+                              const int* lens, int B, int T, int step, int ndir, hipStream_t s) {
     if (B > 4 && B <= 32) {           // matrix-core form: U units per workgroup, 16 * BT sequences
-        if (g_gru_units == 16) launch_gru_mfma<16>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s);
-        else launch_gru_mfma<8>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s);
-        return;
+        if constexpr (H == 1024) {
+            if (g_gru_units == 16) return launch_gru_mfma<H, 16>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s);
+        }
+        if constexpr (H <= 512) {
+            if (g_gru_units != -8) return launch_gru_mfma<H, 4>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s);
+        }
+        return launch_gru_mfma<H, 8>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s);
     }
-    hipLaunchKernelGGL(gru_step_kernel<1024>, dim3(H / 4, ndir), dim3(256), 0, s, gx, whh, bhn, h_prev, h_next, out, lens, B, T,
+    hipLaunchKernelGGL(gru_step_kernel<H>, dim3(H / 4, ndir), dim3(256), 0, s, gx, whh, bhn, h_prev, h_next, out, lens, B, T,
                        step, ndir);
+}
+
+// 0: launched; 1: no step kernel is instantiated for this H (nothing was written)
+int launch_gru_step(const float* gx, const float* whh, const float* bhn, const float* h_prev, float* h_next, float* out,
+                    const int* lens, int B, int T, int H, int step, int ndir, hipStream_t s) {
+    switch (H) {
+#define MASR_GRU_H(N) case N: launch_gru_step_h<N>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s); return 0;
+        MASR_GRU_H(256) MASR_GRU_H(512) MASR_GRU_H(768) MASR_GRU_H(1024)
+        MASR_GRU_H(1280) MASR_GRU_H(1536) MASR_GRU_H(1792) MASR_GRU_H(2048)
+#undef MASR_GRU_H
+    }
+    return 1;
 }
 
 }  // namespace masr

@@ -5,9 +5,12 @@
 // left is the recurrence  gates_t = Gx_t + W_hh . h_{t-1}  (PyTorch gate order i, f, g, o),
 // c_t = sigma(f) c_{t-1} + sigma(i) tanh(g),  h_t = sigma(o) tanh(c_t).  One launch per timestep, both
 // directions in it (blockIdx.y): a wave owns ONE hidden unit (its 4 gate rows of W_hh stay in registers,
-// 16 values per lane) and walks over the batch; 1024 units / 4 waves = 256 workgroups = one per CU.
-// W_hh (16 MB per direction) is re-streamed from L2 / Infinity Cache every step -- the recurrence is
-// HBM/L2-bound by construction at batch 1; a persistent cross-CU kernel is the next step.
+// H / 64 values per lane and gate: 16 at rnn_size 1024, 32 at 2048) and walks over the batch; H units / 4 waves = H / 4
+// workgroups per direction (256 = one per CU at 1024).  H is a template parameter, instantiated for every multiple of 256
+// from 256 to 2048 (the lane's slice is read as 16-byte vectors, so H % 256 == 0).
+// W_hh (4 H^2 floats per direction: 16 MB at 1024, 67 MB at 2048) is re-streamed from L2 / Infinity Cache every step --
+// the recurrence is cache-bandwidth-bound by construction at batch 1; at 2048 W_hh no longer fits the
+// aggregate L2 and comes from the Infinity Cache.  The persistent cross-CU form was measured and rejected.
 // pack_padded_sequence semantics: a sequence advances only while t < len (the reverse direction therefore
 // starts at its own last frame), padded outputs are zero.
 #include "common.h"
@@ -80,39 +83,43 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const float* __restrict_
     }
 }
 
-// Batched form of the step (B > 4): 8 hidden units x 4 gates of a workgroup against the h_{t-1} rows of 16 * BT sequences on
-// the matrix cores (v_mfma_f32_16x16x4_f32: D[16 sequences, 16 columns] += h[16, 4] . W^T[4, 16]; the 16 columns of tile p are
-// gate 2p of the 8 units followed by gate 2p+1 of the same units).  1024 / 8 units x directions = 256 workgroups at two
-// directions, one per CU, so the whole chip pulls W_hh.  8 waves split K = 1024 (128 each), partial tiles are summed through
-// LDS, then one thread per (sequence, unit) applies the gate non-linearities.  Both operands are fetched as 16-byte vectors
-// along k (lane l: row/col l % 16, k block 4 * (l / 16)); the k order inside an MFMA sum is free, so element i of every lane's
-// vector feeds MFMA i of a group of four.
-template <int H, int BT>
+// Batched form of the step (4 < B <= 32): U hidden units x 4 gates of a workgroup against the h_{t-1} rows of 16 * BT sequences
+// on the matrix cores (v_mfma_f32_16x16x4_f32: D[16 sequences, 16 columns] += h[16, 4] . W^T[4, 16]).  Column c of the
+// workgroup's 4U columns is gate c / U of unit c % U, in NT = U / 4 tiles of 16 (U = 8: tile p holds gate 2p of the 8 units
+// followed by gate 2p+1 of the same units).  H / U workgroups per direction: 256 at rnn_size 1024 with two directions, one per
+// CU, so the whole chip pulls W_hh.  8 waves split K = H (H / 8 each, walked in steps of 16, so H % 128 == 0), partial tiles
+// are summed through LDS, then one thread per (sequence, unit) applies the gate non-linearities.  Both operands are fetched as
+// 16-byte vectors along k (lane l: row/col l % 16, k block 4 * (l / 16)); the k order inside an MFMA sum is free, so element i
+// of every lane's vector feeds MFMA i of a group of four.  A column's dot product does not depend on U (same waves, same k
+// order), so every U gives the same bits.
+template <int H, int U, int BT>
 __global__ __launch_bounds__(512) void lstm_step_mfma_kernel(const float* __restrict__ gx, const float* __restrict__ whh,
                                                              const float* __restrict__ h_prev, float* __restrict__ h_next,
                                                              float* __restrict__ c, float* __restrict__ out,
                                                              const int* __restrict__ lens, int B, int T, int step, int ndir) {
     typedef float f32x4v __attribute__((ext_vector_type(4)));
-    __shared__ float red[8][BT * 2 * 4][64];          // [wave][sequence tile, gate pair, acc reg][lane]
+    static_assert(U % 4 == 0 && 16 % U == 0 && H % 128 == 0 && H % U == 0, "whole 16-column tiles of whole gates, whole k steps");
+    constexpr int NT = U / 4;
+    __shared__ float red[8][BT * NT * 4][64];         // [wave][sequence tile, column tile, acc reg][lane]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int dir = blockIdx.y;
-    const int j0 = blockIdx.x * 8;
+    const int j0 = blockIdx.x * U;
     const int t = dir ? T - 1 - step : step;
     const int col = lane & 15, q = lane >> 4;
     const int k0 = wave * (H / 8);
-    f32x4v acc[BT][2];
+    f32x4v acc[BT][NT];
 #pragma unroll
     for (int bt = 0; bt < BT; ++bt)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) acc[bt][p] = f32x4v{0.f, 0.f, 0.f, 0.f};
-    // column `col` of gate-pair tile p: gate 2p + (col >> 3), unit j0 + (col & 7)
-    const float* wbase = whh + ((size_t)dir * 4 * H + (size_t)(col >> 3) * H + j0 + (col & 7)) * H + k0 + 4 * q;
+        for (int p = 0; p < NT; ++p) acc[bt][p] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    // column `col` of tile p: gate (16p + col) / U = p * (16 / U) + col / U, unit j0 + col % U
+    const float* wbase = whh + ((size_t)dir * 4 * H + (size_t)(col / U) * H + j0 + col % U) * H + k0 + 4 * q;
     const float* hbase = h_prev + (size_t)dir * B * H + k0 + 4 * q;
 #pragma unroll
-    for (int kb = 0; kb < H / 8; kb += 16) {      // fully unrolled: all 8 x (2 + BT) vector loads can be in flight at once
-        f32x4 wv[2], hv[BT];
+    for (int kb = 0; kb < H / 8; kb += 16) {      // fully unrolled: all H / 128 x (NT + BT) vector loads can be in flight at once
+        f32x4 wv[NT], hv[BT];
 #pragma unroll
-        for (int p = 0; p < 2; ++p) wv[p] = *reinterpret_cast<const f32x4*>(wbase + (size_t)(2 * p) * H * H + kb);
+        for (int p = 0; p < NT; ++p) wv[p] = *reinterpret_cast<const f32x4*>(wbase + (size_t)(p * (16 / U)) * H * H + kb);
 #pragma unroll
         for (int bt = 0; bt < BT; ++bt) {
             const int b = min(bt * 16 + col, B - 1);
@@ -123,28 +130,29 @@ __global__ __launch_bounds__(512) void lstm_step_mfma_kernel(const float* __rest
 #pragma unroll
             for (int bt = 0; bt < BT; ++bt)
 #pragma unroll
-                for (int p = 0; p < 2; ++p)
+                for (int p = 0; p < NT; ++p)
                     acc[bt][p] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[bt][i], wv[p][i], acc[bt][p], 0, 0, 0);
     }
 #pragma unroll
     for (int bt = 0; bt < BT; ++bt)
 #pragma unroll
-        for (int p = 0; p < 2; ++p)
+        for (int p = 0; p < NT; ++p)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) red[wave][(bt * 2 + p) * 4 + r][lane] = acc[bt][p][r];
+            for (int r = 0; r < 4; ++r) red[wave][(bt * NT + p) * 4 + r][lane] = acc[bt][p][r];
     __syncthreads();
     // D layout of the 16x16 tile: lane l, register r -> row (sequence) 4 * (l / 16) + r, column l % 16
-    for (int e = threadIdx.x; e < BT * 16 * 8; e += 512) {       // one thread per (sequence, unit)
-        const int b = e >> 3, u = e & 7;
+    for (int e = threadIdx.x; e < BT * 16 * U; e += 512) {       // one thread per (sequence, unit)
+        const int b = e / U, u = e % U;
         if (b >= B) continue;
         const int bt = b >> 4, r = b & 3, lq = (b >> 2) & 3;      // b = 16 bt + 4 lq + r
         float dot[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const int l = lq * 16 + (g & 1) * 8 + u;              // lane that holds column (gate g & 1, unit u) of tile g >> 1
+            const int cc = g * U + u;
+            const int l = lq * 16 + (cc & 15);                    // lane that holds column cc & 15 of tile cc >> 4
             float a = 0.f;
 #pragma unroll
-            for (int w = 0; w < 8; ++w) a += red[w][(bt * 2 + (g >> 1)) * 4 + r][l];
+            for (int w = 0; w < 8; ++w) a += red[w][(bt * NT + (cc >> 4)) * 4 + r][l];
             dot[g] = a;
         }
         const int j = j0 + u;
@@ -167,17 +175,43 @@ __global__ __launch_bounds__(512) void lstm_step_mfma_kernel(const float* __rest
     }
 }
 
-void launch_lstm_step(const float* gx, const float* whh, const float* h_prev, float* h_next, float* c, float* out,
-                      const int* lens, int B, int T, int H, int step, int ndir, hipStream_t s) {
-    if (H != 1024) return;
-    if (B > 4 && B <= 32) {           // matrix-core form: 8 units per workgroup, 16 * BT sequences
-        const dim3 grid(H / 8, ndir), blk(512);
-        if (B <= 16) hipLaunchKernelGGL((lstm_step_mfma_kernel<1024, 1>), grid, blk, 0, s, gx, whh, h_prev, h_next, c, out, lens, B, T, step, ndir);
-        else hipLaunchKernelGGL((lstm_step_mfma_kernel<1024, 2>), grid, blk, 0, s, gx, whh, h_prev, h_next, c, out, lens, B, T, step, ndir);
-        return;
+// Units per workgroup of the matrix-core form: 4 at rnn_size <= 512, where 8 leave most CUs without a workgroup (H / 8 x ndir = 32
+// to 128 workgroups on 256 CUs; measured 10 - 17 % per step, docs/LAB_NOTES.md 18), 8 above.  masr_debug_set key 43 = -8 runs 8
+// units at every size (the A/B side; the same bits).
+static bool g_lstm_units8 = false;
+void set_lstm_mfma_units(int u) { g_lstm_units8 = u == -8; }
+
+template <int H, int U>
+static void launch_lstm_mfma(const float* gx, const float* whh, const float* h_prev, float* h_next, float* c, float* out,
+                             const int* lens, int B, int T, int step, int ndir, hipStream_t s) {
+    const dim3 grid(H / U, ndir), blk(512);
+    if (B <= 16) hipLaunchKernelGGL((lstm_step_mfma_kernel<H, U, 1>), grid, blk, 0, s, gx, whh, h_prev, h_next, c, out, lens, B, T, step, ndir);
+    else hipLaunchKernelGGL((lstm_step_mfma_kernel<H, U, 2>), grid, blk, 0, s, gx, whh, h_prev, h_next, c, out, lens, B, T, step, ndir);
+}
+
+template <int H>
+static void launch_lstm_step_h(const float* gx, const float* whh, const float* h_prev, float* h_next, float* c, float* out,
+                               const int* lens, int B, int T, int step, int ndir, hipStream_t s) {
+    if (B > 4 && B <= 32) {           // matrix-core form: U units per workgroup, 16 * BT sequences
+        if constexpr (H <= 512) {
+            if (!g_lstm_units8) return launch_lstm_mfma<H, 4>(gx, whh, h_prev, h_next, c, out, lens, B, T, step, ndir, s);
+        }
+        return launch_lstm_mfma<H, 8>(gx, whh, h_prev, h_next, c, out, lens, B, T, step, ndir, s);
     }
-    hipLaunchKernelGGL(lstm_step_kernel<1024>, dim3(H / 4, ndir), dim3(256), 0, s, gx, whh, h_prev, h_next, c, out, lens, B,
+    hipLaunchKernelGGL(lstm_step_kernel<H>, dim3(H / 4, ndir), dim3(256), 0, s, gx, whh, h_prev, h_next, c, out, lens, B,
                        T, step, ndir);
+}
+
+// 0: launched; 1: no step kernel is instantiated for this H (nothing was written)
+int launch_lstm_step(const float* gx, const float* whh, const float* h_prev, float* h_next, float* c, float* out,
+                     const int* lens, int B, int T, int H, int step, int ndir, hipStream_t s) {
+    switch (H) {
+#define MASR_LSTM_H(N) case N: launch_lstm_step_h<N>(gx, whh, h_prev, h_next, c, out, lens, B, T, step, ndir, s); return 0;
+        MASR_LSTM_H(256) MASR_LSTM_H(512) MASR_LSTM_H(768) MASR_LSTM_H(1024)
+        MASR_LSTM_H(1280) MASR_LSTM_H(1536) MASR_LSTM_H(1792) MASR_LSTM_H(2048)
+#undef MASR_LSTM_H
+    }
+    return 1;
 }
 
 // LayerNorm over rows of arbitrary width N <= 8192 (deepspeech2/encoder.py:33,44): one workgroup per row

@@ -128,6 +128,26 @@ def _validate_encoder_conf(use_model, enc, state_dict):
                                  f'.weight_ih_l0)')
 
 
+RNN_SIZES = tuple(range(256, 2049, 256))
+
+
+def _validate_rnn_size(enc, state_dict):
+    """DeepSpeech2 ``encoder_conf.rnn_size`` (configs/deepspeech2.yml): the recurrent step kernels (lstm.hip, gru.hip) are
+    instantiated for every multiple of 256 from 256 to 2048, and the value has to be the checkpoint's own hidden size."""
+    size = enc.get('rnn_size', 1024)
+    if isinstance(size, bool) or not isinstance(size, int) or size not in RNN_SIZES:
+        raise _lib.MasrError(f'deepspeech2: encoder_conf.rnn_size={size!r} is not supported: multiples of 256 from 256 to 2048 '
+                             f'are ({", ".join(map(str, RNN_SIZES))})')
+    if state_dict is None:
+        return
+    for key in ('encoder.rnns.0.rnn.weight_hh_l0', 'encoder.rnns.0.rnn.rnn.weight_hh_l0'):
+        if key in state_dict:
+            have = int(state_dict[key].shape[1])
+            if have != size:
+                raise _lib.MasrError(f'deepspeech2: encoder_conf.rnn_size={size} but the checkpoint was trained with rnn_size={have} '
+                                     f'({key} is {list(state_dict[key].shape)})')
+
+
 class HipEngine:
     """One engine per GPU rank.  ``state_dict`` uses the reference key names
     (``encoder.*`` / ``ctc.*``; extra keys are ignored); ``state_dict=None`` gives a weight-less
@@ -148,6 +168,8 @@ class HipEngine:
         self.device = torch.device('cuda', device)
         torch.cuda.set_device(self.device)
         _validate_encoder_conf(use_model, enc, state_dict)
+        if use_model == 'deepspeech2':
+            _validate_rnn_size(enc, state_dict)
         # subsampling front-end (Conformer / Efficient Conformer; the other models have their own)
         self.input_layer = enc.get('input_layer', 'conv2d') if use_model in ('conformer', 'efficient_conformer') else 'conv2d'
         if use_model == 'conformer':
