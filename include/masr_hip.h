@@ -457,34 +457,63 @@ int masr_side_stream(masr_engine* e, int32_t kind, void** stream_out);
 int masr_select_lane(masr_engine* e, int32_t lane);
 
 /* Diagnostics: A/B switches of the kernels, for in-process measurements (tools/ *_ab.py); production = the defaults.
- *   1  fused-FFN variant (0 production, 1 without weight loads)      2  beam-search phase profile of workgroup 0
- *   5  1 = no out-proj + pw1 chain kernel                            6  0 = no K-split projection kernel
- *   7  0 = always the query-tiled attention kernel                   8  1 = no QKV tail stage on the first FFN
- *   9  1 = no conv-module head stage on the second FFN              12  row blocks below which the K-split projection kernel runs
- *  13  row blocks below which the FFN splits d_ff                   14  0 = two-term attention scores (no positional-key fold)
- *  15  0 = the offline embed projection never splits K              16  time every n-th matching launch (masr_profile_*)
- *  17  waves per workgroup of the offline conv2 launch (8 | 4)   18  0 = conv1 writes with plain instead of streaming stores
- *  19  timing experiment: every chunk-step layer on layer 0's weights
- *  21  waves per workgroup of the split-bf16 conv2 launch (8 | 4)   22  0 = no per-workgroup chunk rotation in the split-bf16 FFN
- *  23  0 = the full FFN launches stream their weights through the wave-private LDS slabs instead of reading the packed copies
- *      straight into registers (bit-identical either way)
- *  24  1 = the full FFN launches run two accumulator chains per wave (ffn_dual.hip) instead of one (ffn_pc.hip; bit-identical)
- *  25  0 = the offline out-proj + pw1 chain kernel and the CTC head stream their weights through LDS slabs instead of reading
- *      packed copies with buffer loads (bit-identical)
- *  39  0 = the full packed FFN launches run the 32-row kernel instead of the 16-row one (two workgroups per CU; bit-identical)
- *  40  0 = the offline conv2 runs on 128x128 tiles instead of full-width 64-row blocks with packed weights (bit-identical)
- *  41  0 = conv1 runs as its own launch (writing its output to a workspace) instead of inside the A gather of the row-block
- *      conv2 (key 40; bit-identical)
- *  42  0 = the K quarters of the offline embed projection run on 128x128 tiles instead of full-width 64-row blocks with packed
- *      weights (bit-identical)
- *  43  hidden units per workgroup of the DeepSpeech2 matrix-core recurrent step (4 < B <= 32): 8 = production (4 units at rnn_size
- *      <= 512, 8 above); 16 = 16 units (GRU at rnn_size 1024 only); -8 = 8 units at every size (bit-identical: a column's dot
- *      product does not depend on the grouping).  PROCESS-WIDE, unlike the other keys: it holds for every engine of the process,
- *      whichever handle sets it
- *  20  1 = EXPLORATORY split-bf16 precision mode (not the reference's fp32 arithmetic, never the contract path): conv2, the embed
- *      projection and the other launches of the generic GEMM in the offline forward as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on
- *      the bf16 matrix pipe, fp32 accumulation (csrc/gemm_bf16x3.hip); 3 = also the FFN, unfused (slower than the fused fp32 FFN) */
+ * SCOPE: every key but 2, 16 and 38 is PROCESS-WIDE -- it holds for every engine of the process, whichever handle sets it; keys 2, 16
+ * and 38 belong to the engine whose handle sets them.  key, name (masr_debug_key_info), meaning:
+ *   1  ffn_variant: fused-FFN variant (0 production, 81 without weight loads)
+ *   2  beam-search phase profile of workgroup 0 (per engine)
+ *   5  no_chain: 1 = no out-proj + pw1 chain kernel                  6  rowgemm_small: 0 = no K-split projection kernel
+ *   7  attention_fewq: 0 = always the query-tiled attention kernel   8  no_ffn_tail: 1 = no QKV tail stage on the first FFN
+ *   9  no_ffn_head: 1 = no conv-module head stage on the second FFN
+ *  12  rowgemm_small_blocks: row blocks below which the K-split projection kernel runs
+ *  13  ffn_split_blocks: row blocks below which the FFN splits d_ff
+ *  14  attention_fold: 0 = two-term attention scores (no positional-key fold)
+ *  15  embed_split: 0 = the offline embed projection never splits K
+ *  16  time every n-th matching launch (masr_profile_*; per engine)
+ *  17  gemm_waves: waves per workgroup of the offline conv2 launch (8 | 4)
+ *  18  conv1_nt: 0 = conv1 writes with plain instead of streaming stores
+ *  19  hot_weights: timing experiment: every chunk-step layer on layer 0's weights
+ *  20  bf16x3: 1 = EXPLORATORY split-bf16 precision mode (not the reference's fp32 arithmetic, never the contract path): conv2, the
+ *      embed projection and the other launches of the generic GEMM in the offline forward as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on
+ *      the bf16 matrix pipe, fp32 accumulation (csrc/gemm_bf16x3.hip); 3 = also the FFN, unfused (slower than the fused fp32 FFN)
+ *  21  gemm_bf16x3_waves: waves per workgroup of the split-bf16 conv2 launch (8 | 4)
+ *  22  ffn_x3_rotation: 0 = no per-workgroup chunk rotation in the split-bf16 FFN
+ *  23  ffn_packed: 0 = the full FFN launches stream their weights through the wave-private LDS slabs instead of reading the packed
+ *      copies straight into registers (bit-identical either way); 2 (default) = the d_ff-split launches read packed copies too
+ *  24  ffn_dual: 1 = the full FFN launches run two accumulator chains per wave (ffn_dual.hip) instead of one (ffn_pc.hip;
+ *      bit-identical)
+ *  25  rowgemm_packed: 0 = the offline out-proj + pw1 chain kernel and the CTC head stream their weights through LDS slabs instead
+ *      of reading packed copies with buffer loads (bit-identical)
+ *  26  attention_grouped_fold: 0 = the two-wave, two-term grouped attention kernel
+ *  27  ctc_fused_blocks: row blocks from which the fused CTC head runs
+ *  28  attention_fewq_wgs: offline launches with fewer attention workgroups than this take the key-split kernel
+ *  29  few_rows_path: 0 = offline Conformer layers of few row blocks keep the row-block chain kernel
+ *  30  split_head: 1 = few rows: the conv-module head stage rides on the d_ff-split FFN launch
+ *  31  efficient_fused: 0 = Efficient-Conformer layers keep separate out-proj / pw1 / dwconv / pw2 launches
+ *  32  beam_lm_cache: 0 = the GPU prefix search probes the scorer once per (prefix, candidate) pair
+ *  33  conv2_mid_fill: percent below which a thin last round of the 128x128 conv2 grid switches to 128x64 tiles (0 = never)
+ *  34  attn_chain: 1 = offline Conformer layers run attention and the out-proj + pw1 chain as one launch
+ *  35  ffn_coop: 1 = one-chunk d_ff slices of few rows run ffn_coop.hip
+ *  36  sqz_fused_blocks: row blocks from which a full-context Squeezeformer layer runs the fused stage kernels (0 = never)
+ *  37  beam_narrow: 0 = every frame of the GPU prefix search on the wide (1024-thread) step
+ *  38  the offline Squeezeformer launches skip the all-padding row blocks of a batch (per engine; bits: 1 stage kernels, 2 conv2 +
+ *      input projection, 4 attention; default 7, 0 = the padded frames are computed too)
+ *  39  ffn16: 0 = the full packed FFN launches run the 32-row kernel instead of the 16-row one (two workgroups per CU; bit-identical)
+ *  40  conv2_rows: 0 = the offline conv2 runs on 128x128 tiles instead of full-width 64-row blocks with packed weights
+ *      (bit-identical)
+ *  41  conv1_fused: 0 = conv1 runs as its own launch (writing its output to a workspace) instead of inside the A gather of the
+ *      row-block conv2 (key 40; bit-identical)
+ *  42  embed_rows: 0 = the K quarters of the offline embed projection run on 128x128 tiles instead of full-width 64-row blocks with
+ *      packed weights (bit-identical)
+ *  43  rnn_mfma_units: hidden units per workgroup of the DeepSpeech2 matrix-core recurrent step (4 < B <= 32): 8 = production (4
+ *      units at rnn_size <= 512, 8 above); 16 = 16 units (GRU at rnn_size 1024 only); -8 = 8 units at every size (bit-identical: a
+ *      column's dot product does not depend on the grouping)
+ * Keys 20, 21, 22, 24, 30, 34 and 35 select experimental kernels: a build without MASR_BUILD_EXPERIMENTS=1 refuses a non-zero value.
+ * masr_debug_reset puts every process-wide switch back to its default, and this engine's keys 16 and 38 (1 and 7); key 2 is left
+ * alone.  masr_debug_key_info (no engine) describes row `index` of the table of process-wide switches -- its key, default,
+ * whether it is experimental, and its name (a static string) -- and returns non-zero past the last row; null outputs are skipped. */
 int masr_debug_set(masr_engine* e, int32_t key, int32_t value);
+int masr_debug_reset(masr_engine* e);
+int masr_debug_key_info(int32_t index, int32_t* key, int32_t* default_value, int32_t* experimental, const char** name);
 
 /* Profiling: time every launch of one kernel class with HIP events on the launch stream.
  * kind: 0 none, 1 gemm (all), 2 ffn-w1 gemm, 3 conv2 gemm, 4 attention, 5 fbank, 8 the step loop of a DeepSpeech2 recurrent

@@ -3,6 +3,7 @@
 The product path has NO CPU fallback: if the HIP library is missing or cannot be loaded this
 module raises, and so does everything that imports it.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -115,6 +116,8 @@ SIGNATURES = {
     'masr_select_lane': [_P, _I],
     'masr_stage_rows': [_P, C.c_int64, _P, _P, _I, _I, _I],
     'masr_debug_set': [_P, _I, _I],
+    'masr_debug_reset': [_P],
+    'masr_debug_key_info': [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_char_p)],
     'masr_mfma_order_probe': [_P, _P, _P, _P, _I, _P, _P],
     'masr_profile_select': [_P, _I],
     'masr_profile_read': [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), _I],
@@ -158,3 +161,33 @@ def lib():
 def check(rc):
     if rc != 0:
         raise MasrError(lib().masr_last_error().decode('utf-8', 'replace'))
+
+
+# the three per-engine keys of masr_debug_set (include/masr_hip.h); every other key is a row of masr_debug_key_info
+_ENGINE_KEYS = {'beam_profile': 2, 'prof_stride': 16, 'skip_padding': 38}
+
+
+def debug_key_table():
+    """[(key, name, default, experimental)]: the process-wide masr_debug_set switches, as masr_debug_key_info lists them"""
+    rows = []
+    key, default, experimental, name = _I(), _I(), _I(), C.c_char_p()
+    while lib().masr_debug_key_info(len(rows), C.byref(key), C.byref(default), C.byref(experimental), C.byref(name)) == 0:
+        rows.append((key.value, name.value.decode(), default.value, bool(experimental.value)))
+    return rows
+
+
+@contextlib.contextmanager
+def debug_keys(eng, by_name=None, **more):
+    """Set masr_debug_set switches by name for the body -- debug_keys(eng, ffn16=0) or debug_keys(eng, {'ffn16': 0}); a key of the
+    dict may also be the switch's number.  Raises MasrError when the library refuses a key (unknown, or experimental in a product
+    build).  On exit masr_debug_reset puts EVERY process-wide switch, and this engine's prof_stride and skip_padding, back to the
+    default -- not to what held before -- so blocks do not nest: give all the keys of one measurement to one block."""
+    numbers = dict(_ENGINE_KEYS, **{name: key for key, name, _, _ in debug_key_table()})
+    try:
+        for name, value in dict(by_name or {}, **more).items():
+            if not isinstance(name, int) and name not in numbers:
+                raise MasrError(f'debug_keys: no switch is named {name!r}')
+            check(lib().masr_debug_set(eng.h, name if isinstance(name, int) else numbers[name], int(value)))
+        yield
+    finally:
+        check(lib().masr_debug_reset(eng.h))

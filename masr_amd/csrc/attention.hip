@@ -498,12 +498,6 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
     }
 }
 
-static int g_fewq = 1, g_fold = 1;
-static int g_fewq_wgs = 48;       // masr_debug_set key 28: offline launches with fewer attention_kernel workgroups than this take the key-split kernel
-void set_attention_fewq_wgs(int n) { g_fewq_wgs = n; }
-void set_attention_fewq(int on) { g_fewq = on; }
-void set_attention_fold(int on) { g_fold = on; }
-
 void launch_attention(const AttSeq* seqs, int nseq, int max_nq, int heads, int q_stride, int kv_stride,
                       const float* ptab, const float* bias_u, const float* bias_v, int chunk_size, int pos_stride,
                       hipStream_t s) {
@@ -512,15 +506,16 @@ void launch_attention(const AttSeq* seqs, int nseq, int max_nq, int heads, int q
     // the key-split kernel (eight waves share 32 queries and split the key tiles) also takes short offline batches, one
     // workgroup per (head, sequence, 32 queries): attention_kernel would give such a batch nqb * heads * nseq workgroups that each
     // walk ALL key tiles in pairs (one 8.4 s utterance: 8 workgroups, 22 us; here 28 workgroups of one tile per wave)
-    if (g_fewq && (max_nq <= 32 || nqb * heads * nseq < g_fewq_wgs)) {
+    if (knobs().attention_fewq && (max_nq <= 32 || nqb * heads * nseq < knobs().attention_fewq_wgs)) {
         hipLaunchKernelGGL(attention_fewq_kernel, dim3(heads, nseq, (max_nq + 31) / 32), dim3(512), 0, s, seqs, q_stride, kv_stride,
                            ptab, bias_u, bias_v, chunk_size, pos_stride);
         return;
     }
-    if (g_fold && ATT_XCD_MAP)
+    const int fold = knobs().attention_fold;
+    if (fold && ATT_XCD_MAP)
         hipLaunchKernelGGL(attention_kernel<1>, dim3(8 * nqb * ((heads * nseq + 7) / 8)), dim3(512), 0, s, seqs, q_stride,
                            kv_stride, ptab, bias_u, bias_v, chunk_size, pos_stride, nqb, heads, nseq);
-    else if (g_fold)
+    else if (fold)
         hipLaunchKernelGGL(attention_kernel<1>, dim3(nqb, heads, nseq), dim3(512), 0, s, seqs, q_stride,
                            kv_stride, ptab, bias_u, bias_v, chunk_size, pos_stride, 0, heads, nseq);
     else
@@ -1168,13 +1163,10 @@ __global__ __launch_bounds__(384) void attention_grouped_fold_kernel(const AttSe
     }
 }
 
-static int g_att_grouped_fold = 1;      // masr_debug_set key 26: 0 = the two-wave, two-term grouped kernel (A/B)
-void set_attention_grouped_fold(int on) { g_att_grouped_fold = on; }
-
 void launch_attention_grouped(const AttSeq* seqs, int nseq, int max_nq, int heads, int group, const float* ptab,
                               int t_true, const float* bias_u, const float* bias_v, hipStream_t s, int chunk_size) {
     if (nseq <= 0 || max_nq <= 0 || group != 3) return;
-    if (g_att_grouped_fold) {
+    if (knobs().attention_grouped_fold) {
         constexpr int DKG = 192;
         const size_t lds = (size_t)(2 * 2 * 32 * (DKG + 4) + 64) * sizeof(float);
         static LdsAttr attr;

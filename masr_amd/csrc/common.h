@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "knobs.h"
 #include "lm_scorer.h"
 
 struct masr_resample_feed;      // include/masr_hip.h
@@ -115,8 +116,6 @@ struct GemmArgs {
 };
 
 void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s);
-void set_conv2_mid_fill(int pct);     // diagnostics (masr_debug_set key 33)
-void set_gemm_waves(int n);          // diagnostics (masr_debug_set key 17): waves per workgroup of the large conv2 launch, 8 (default) or 4
 void launch_pack_conv2_rows(const float* w, float* p, int K, hipStream_t s);    // W [256, K] -> GemmArgs::Wp layout
 bool gemm_conv2_rows(const GemmArgs& a);    // launch_gemm(a, A_CONV2, EPI_STD) runs conv2_rows_kernel (needs a.Wp)
 // deep-K, few-row GEMM: split K over workgroups into `partial` [nsplit][M][N], then reduce + epilogue into a.C
@@ -124,18 +123,14 @@ void launch_gemm_splitk(const GemmArgs& a, float* partial, int nsplit, hipStream
 // exploratory split-bf16 variant (gemm_bf16x3.hip; masr_debug_set key 20): standard epilogue only; false = not taken
 #if MASR_EXPERIMENTS
 bool launch_gemm_bf16x3(const GemmArgs& a, int amode, hipStream_t s);
-void set_gemm_bf16x3_waves(int n);
 // fused split-bf16 FFN (ffn_x3.hip): weights packed once per FFN (hi / lo pieces in fragment order)
 size_t ffn_x3_packed_elems(int dff);
-void set_ffn_x3_rotation(int on);
 void launch_pack_ffn_x3(const float* w1, const float* w2, unsigned short* p1, unsigned short* p2, int dff, hipStream_t s);
 bool launch_ffn_x3(float* x, const float* lnw, const float* lnb, const unsigned short* p1, const float* b1,
                    const unsigned short* p2, const float* b2, int M, int dff, float eps, float scale, hipStream_t s);
 #else
 inline bool launch_gemm_bf16x3(const GemmArgs&, int, hipStream_t) { return false; }
-inline void set_gemm_bf16x3_waves(int) {}
 inline size_t ffn_x3_packed_elems(int) { return 0; }
-inline void set_ffn_x3_rotation(int) {}
 inline void launch_pack_ffn_x3(const float*, const float*, unsigned short*, unsigned short*, int, hipStream_t) {}
 inline bool launch_ffn_x3(float*, const float*, const float*, const unsigned short*, const float*, const unsigned short*, const float*,
                           int, int, float, float, hipStream_t) { return false; }
@@ -147,7 +142,6 @@ inline bool launch_ffn_x3(float*, const float*, const float*, const unsigned sho
 void launch_layernorm(const float* x, const float* w, const float* b, float* y, int M, float eps,
                       int seq_t, int pad, const int* lens, hipStream_t s);
 // CMVN + Conv2d(1->C,3x3,s2) + ReLU, output channels-last [B,T1,F1,C]
-void set_conv1_nt(int on);           // diagnostics (masr_debug_set key 18): 0 = conv1 writes its output with plain stores
 void launch_conv1(const float* feats, const float* mean, const float* istd, const float* w9c, const float* bias,
                   float* out, int B, int T, int F, int C, hipStream_t s);
 // depthwise causal conv (k taps) + LayerNorm(C=256) + SiLU on padded layout [nseq, pad+Tq, 256] -> [nseq*Tq, 256]
@@ -241,8 +235,6 @@ struct RowGemmArgs {
 };
 bool launch_rowgemm(const RowGemmArgs& a, int pro, int epi, hipStream_t s);   // false: not applicable, nothing launched (HIST / DWCONV)
 bool launch_rowgemm_small(const RowGemmArgs& a, int pro, int epi, hipStream_t s);   // rowgemm_small.hip; false = not applicable
-void set_rowgemm_small_blocks(int n);                                                // tuning (masr_debug_set key 12)
-void set_rowgemm_small(int on);                                                      // diagnostics (masr_debug_set key 6)
 
 // Fused FFN block, in place: x <- x + scale * (W2 . silu(W1 . LN(x) + b1) + b2)   (ffn_pc.hip; launched through launch_ffn_fused in ffn_reduce.hip)
 // partial/nsplit: split-d_ff mode for small M (streaming).  post: LayerNorm that follows the block in the layer; it is fused into
@@ -355,7 +347,6 @@ inline void launch_ffn_coop(const float*, const float*, const float*, const floa
 #endif
 void launch_ffn_reduce(float* x, const float* partial, const float* b2, int M, int nsplit, float scale, hipStream_t s,
                        const FfnPostLn* post, const float* xin = nullptr);
-void set_ffn_variant(int v);   // diagnostic ablations of the fused FFN kernel (0 = production)
 
 // Fragment-ordered weight copies, one layout per packing routine: the engine keeps every copy it has built under
 // (layout, device pointer of the source weights) -- engine.hip packed_of()
@@ -411,14 +402,12 @@ int launch_beam_search(const BeamGpuArgs& a, int B, hipStream_t s);   // 1: size
 // step launchers: H = every multiple of 256 in [256, 2048]; 1 (and nothing launched) for any other H
 int launch_lstm_step(const float* gx, const float* whh, const float* h_prev, float* h_next, float* c, float* out,
                      const int* lens, int B, int T, int H, int step, int ndir, hipStream_t s);
-void set_lstm_mfma_units(int u);
 void launch_layernorm_generic(const float* x, const float* w, const float* b, float* y, int M, int N, float eps,
                               hipStream_t s);
 void launch_ds2_lens(const int* lens, int B, int Tq, int* out, hipStream_t s);
 // use_gru: True (gru.hip): gx [B*T][ndir*3H] holds W_ih x + b_ih + [b_hr, b_hz, 0]; bhn [ndir][H]
 int launch_gru_step(const float* gx, const float* whh, const float* bhn, const float* h_prev, float* h_next, float* out,
                     const int* lens, int B, int T, int H, int step, int ndir, hipStream_t s);
-void set_gru_mfma_units(int u);
 
 // ---- attention ---------------------------------------------------------------------------
 struct AttSeq {            // one per sequence, device memory
@@ -460,11 +449,6 @@ inline bool launch_attn_chain(const AttnChainArgs&, int, hipStream_t) { return f
 void launch_attention(const AttSeq* seqs, int nseq, int max_nq, int heads, int q_stride, int kv_stride,
                       const float* ptab /*[max_pos,256]*/, const float* bias_u, const float* bias_v,
                       int chunk_size, int pos_stride, hipStream_t s);
-void set_attention_grouped_fold(int on);   // key 26: 0 = the two-wave two-term grouped attention kernel (A/B)
-int rowgemm_small_blocks();                // row blocks below which the K-split projection kernel takes a launch
-void set_attention_fewq_wgs(int n);        // key 28
-void set_attention_fold(int on);     // diagnostics (masr_debug_set key 14): 0 = two-term score contraction in attention_kernel
-void set_attention_fewq(int on);     // diagnostics (masr_debug_set key 7): 0 = always the query-tiled kernel
 void launch_attention_grouped(const AttSeq* seqs, int nseq, int max_nq, int heads, int group, const float* ptab,
                               int t_true, const float* bias_u, const float* bias_v, hipStream_t s, int chunk_size = 0);
 void launch_attseq_grouped(AttSeq* seqs, const float* q, const float* k, const float* v, float* out, const int* lens,

@@ -117,16 +117,11 @@ __global__ __launch_bounds__(256) void conv1_kernel(const float* __restrict__ fe
     }
 }
 
-// the 636 MB of conv1 output (B = 32 x 10 s) are written once and read back from HBM by conv2 whatever the caches do: streaming
-// (non-temporal) stores, 135.3 -> 125.6 us in one kernel trace with both forms alternating, conv2 behind it unchanged
-static int g_conv1_nt = 1;
-void set_conv1_nt(int on) { g_conv1_nt = on; }
-
 void launch_conv1(const float* feats, const float* mean, const float* istd, const float* w9c, const float* bias,
                   float* out, int B, int T, int F, int C, hipStream_t s) {
     const int T1 = (T - 1) / 2, F1 = (F - 1) / 2;
     if (B * T1 <= 0) return;
-    if (g_conv1_nt)
+    if (knobs().conv1_nt)
         hipLaunchKernelGGL(conv1_kernel<1>, dim3(B * T1), dim3(256), 3 * F * sizeof(float), s, feats, mean, istd, w9c, bias,
                            out, T, F, T1, F1, C);
     else

@@ -75,44 +75,6 @@ void ensure_dynamic_lds(const void* fn, size_t bytes, LdsAttr& st) {
 // device != 0 may be driven from a worker thread whose current device is still 0)
 #define ENTER(e) HIPCHK(hipSetDevice((e)->cfg.device_id))
 
-static int g_no_ffn_tail = 0;     // masr_debug_set key 8: 1 = the QKV projection as its own launch after the first FFN (A/B)
-// row blocks below which the FFN splits d_ff across workgroups (masr_debug_set key 13): up to 191 row blocks the split (256 /
-// rowblocks ways) + its reduction beat one full-d_ff workgroup per row block on a quarter to three quarters of the CUs
-// (128 streams: chunk call 5.34 -> 3.16 ms, 256 streams 6.52 -> 4.99 ms; tools/chunk_step_ab.py)
-static int g_ffn_split_blocks = 192;
-static int g_no_ffn_head = 0;     // masr_debug_set key 9: 1 = depthwise conv and pointwise_conv2 as their own launches before the second FFN (A/B)
-// masr_debug_set key 30: 1 = few rows: [depthwise conv -> LN -> SiLU -> pointwise_conv2 + residual] as the head stage of the d_ff-split
-// FFN launch (every slice repeats it on its row block's rows; slice 0 publishes them).  Built in round 4 because round 3 priced
-// it at -3.4 us per layer; MEASURED (tools/chunk_lat.py, MASR_AB=30:0,30:1,30:0,30:1, one process, one box): 16 streams 1.177 /
-// 1.162 ms per chunk call without it, 1.199 / 1.170 ms with it; 128 streams 3.011 / 3.017 vs 3.037 / 3.042 ms -- the 128
-// dependent MFMAs + the window loads it adds to EVERY slice's critical path cost what the removed 11 us launch (whose columns
-// spread over 32 workgroups) cost.  Off by default; identical frame decisions either way.
-static int g_split_head = 0;
-static int g_efficient_fused = 1;   // masr_debug_set key 31: 0 = Efficient-Conformer layers keep separate out-proj / pw1 / dwconv / pw2 launches (A/B)
-// masr_debug_set key 34: 1 = offline Conformer layers run attention AND the [out-proj -> LN -> pw1 -> GLU] chain as ONE launch
-// (attention.hip attn_chain_kernel: 32 queries x all four heads per workgroup, context rows in LDS).  Built in round 4 (verdict
-// item 6, priced at -0.13 ms per step in round 3), bit-identical to the two launches -- and MEASURED no faster: 58.3 us per launch
-// against 25.9 + 32.7 us (rocprofv3, one trace), 6.428 vs 6.412 ms per 32 x 10 s pass (tools/attn_chain_ab.py): a workgroup that
-// owns 32 queries of all four heads stages four heads' K' / V tiles per 64 MFMAs per wave where attention_kernel's 128 queries of
-// one head stage one -- the saved prologue / epilogue / att round trip is paid back in staging.  Off by default.
-static int g_attn_chain = 0;
-// masr_debug_set key 35: 1 = one-chunk d_ff slices of few rows (<= 8 row blocks) run ffn_coop.hip -- all eight waves on both products
-// (GEMM 1 as 16 x 16 x 4 tiles without a K split, GEMM 2 as 32 x 32 x 2), every weight fragment from packed copies, all loads in
-// flight before the LayerNorm -- instead of the producer / consumer kernel, whose two roles run one after the other when a
-// workgroup owns ONE chunk.  Built in round 4 on the estimate of 2 x 1.7 us of matrix pipe saved per launch; MEASURED slower:
-// 16 streams 1.167 / 1.195 ms per chunk call against 1.135 / 1.109 ms (tools/chunk_lat.py MASR_AB=35:0,35:1,35:0,35:1; with the
-// weights read from the row-major matrices: 1.33 ms -- 16 / 32 cache lines per load instruction).  The launch is bound by its
-// dependent memory round trips (rows written by another XCD, LayerNorm, LDS exchange, partial store), not by the 256 MFMAs.  Off.
-static int g_ffn_coop = 0;
-static int g_few_rows_path = 1;   // masr_debug_set key 29: 0 = offline Conformer layers of few row blocks keep the row-block chain kernel (A/B)
-// masr_debug_set key 36: row blocks from which a full-context Squeezeformer layer runs as attention + the two fused stage kernels of
-// sqz_layer.hip (0 = never: the twelve separate launches, kept for A/B and the bit-identity test).  128 since round 6: the half-rate
-// layers of BASELINE configs[2]'s second pass (144 row blocks, 100 of them valid) are 0.4 ms per call faster fused, on one lane
-// and on two (17.5 -> 17.0 / 19.2 -> 18.8 ms); passes of ~120 half-rate row blocks (32 x 10 s) stay on the d_ff-split launches
-// (fused from 96: 21.2 against 18.9 ms per call of three such passes, round 5)
-static int g_sqz_fused_blocks = 128;
-static int g_no_chain = 0;   // masr_debug_set key 5: 1 = separate out-projection and pointwise_conv1 kernels (A/B)
-
 namespace {
 
 struct DevBuf {
@@ -426,16 +388,6 @@ struct CallGuard {
     }
 };
 
-static int g_ffn_dual = 0;         // masr_debug_set key 24: 0 = the full FFN launches run ffn_pc.hip (one accumulator chain per wave) instead of ffn_dual.hip (A/B)
-static int g_ffn_packed = 2;       // masr_debug_set key 23: 0 = the full FFN launches stream their weights through the wave-private LDS slabs (A/B)
-static int g_ffn16 = 1;            // masr_debug_set key 39: 0 = the full packed FFN launches run the 32-row kernel instead of the 16-row one (A/B)
-static int g_conv2_rows = 1;       // masr_debug_set key 40: 0 = the offline conv2 runs on 128x128 tiles instead of full-width 64-row blocks (A/B)
-static int g_conv1_fused = 1;      // masr_debug_set key 41: 0 = conv1 runs as its own launch in front of the row-block conv2 (A/B)
-static int g_embed_rows = 1;       // masr_debug_set key 42: 0 = the offline embed projection's K quarters run on 128x128 tiles (A/B)
-// masr_debug_set key 20 -- EXPLORATORY precision mode, never the contract path: the big offline GEMMs (conv2, embed projection,
-// the two FFN GEMMs, unfused) run as split-bf16 products on the bf16 matrix pipe (gemm_bf16x3.hip)
-static int g_bf16x3 = 0;
-
 void gemm(masr_engine* e, hipStream_t s, const float* A, int lda, const float* W, const float* bias, float* C, int ldc,
           int M, int N, int K, int act, float alpha, const float* R, int ldr, int kind = PROF_GEMM,
           const int* lens = nullptr, int mask_tp = 0) {
@@ -444,11 +396,10 @@ void gemm(masr_engine* e, hipStream_t s, const float* A, int lda, const float* W
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr;
     a.act = act; a.alpha = alpha; a.mask_tp = mask_tp;
     ProfScope ps(e, s, kind, 2.0 * M * (double)N * K);
-    if (g_bf16x3 && launch_gemm_bf16x3(a, A_PLAIN, s)) return;
+    if (knobs().bf16x3 && launch_gemm_bf16x3(a, A_PLAIN, s)) return;
     launch_gemm(a, A_PLAIN, EPI_STD, s);
 }
 
-static int g_rowgemm_packed = 1;   // masr_debug_set key 25: 0 = the offline out-proj + pw1 chain and the CTC head stream their weights through LDS slabs (A/B)
 // The packed copy of `src` in `layout`, built on first use and kept: buffers of bytes_a (and bytes_b, 0 = none), filled by
 // pack(copy, s), which issues the packing launch on the caller's stream.  nullptr = an allocation failed (masr_last_error says
 // which): what was allocated is freed and nothing is cached.
@@ -509,7 +460,7 @@ RowGemmArgs rg_args(const float* A, int lda, const float* W, const float* bias, 
 }
 void rowgemm(masr_engine* e, hipStream_t s, int pro, int epi, RowGemmArgs a, int kind = PROF_GEMM) {
     // full row-block launches (the K-split kernel of few row blocks reads W itself) take the packed copy of their weights
-    if (g_rowgemm_packed && a.M >= 112 * 32 && pro != RG_PRO_HIST && pro != RG_PRO_DWCONV && (epi == RG_EPI_CTC || a.N % 256 == 0))
+    if (knobs().rowgemm_packed && a.M >= 112 * 32 && pro != RG_PRO_HIST && pro != RG_PRO_DWCONV && (epi == RG_EPI_CTC || a.N % 256 == 0))
         a.Wp = packed_rows_of(e, a.W, a.N, s);
     ProfScope ps(e, s, kind, 2.0 * a.M * (double)a.N * 256);
     launch_rowgemm(a, pro, epi, s);
@@ -1011,19 +962,19 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
     int nsplit = 1;
     const int rowblocks = (M + 31) / 32;
     const FfnPostLn post{post_w, post_b, post_y, 1e-5f};
-    if (rowblocks < g_ffn_split_blocks) {
+    if (rowblocks < knobs().ffn_split_blocks) {
         nsplit = std::min(dff / 128, std::max(1, (rowblocks < 64 ? 128 : 256) / rowblocks));
         CHK(e->ffpart.ensure((size_t)nsplit * M * d * sizeof(float)));
     }
     // exploratory, bit 2 of key 20: the fused split-bf16 FFN (ffn_x3.hip).  (An unfused version -- LayerNorm, then two split-bf16
     // GEMMs with the hidden tensor in HBM -- measured 44 + 82 + 6 us against the 144 us of the fused exact-fp32 kernel at
     // B = 32 x 10 s: the 65 MB round trip of the hidden tensor ate what the bf16 pipe saved.)
-    const bool x3 = (g_bf16x3 & 2) && nsplit == 1 && !affine && d == 256 && dff % 128 == 0;
-    const bool want_tail = tail && nsplit == 1 && !g_no_ffn_tail && !x3;
+    const bool x3 = (knobs().bf16x3 & 2) && nsplit == 1 && !affine && d == 256 && dff % 128 == 0;
+    const bool want_tail = tail && nsplit == 1 && !knobs().no_ffn_tail && !x3;
     // (few rows: the head stage rides on the d_ff-split launch, every slice repeating it on the row block's rows -- key 30)
-    const bool split_head = head && head->glu && nsplit > 1 && g_split_head && !affine && !x3 && head->ktaps == 15 && d == 256 &&
-                            g_ffn_packed >= 2;
-    const bool want_head = head && head->glu && ((nsplit == 1 && !want_tail && !g_no_ffn_head && !affine && !x3 &&
+    const bool split_head = head && head->glu && nsplit > 1 && knobs().split_head && !affine && !x3 && head->ktaps == 15 && d == 256 &&
+                            knobs().ffn_packed >= 2;
+    const bool want_head = head && head->glu && ((nsplit == 1 && !want_tail && !knobs().no_ffn_head && !affine && !x3 &&
                                                   (head->ktaps == 15 || head->ktaps == 7)) || split_head);
     if (head_done) *head_done = want_head;
     if (head && head->glu && !want_head) {
@@ -1059,7 +1010,7 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
     }
     const float *kw1 = w1, *kw2 = w2;
     // few rows, one chunk of 128 hidden units per workgroup: the kernel in which all eight waves work on both products (key 35)
-    if (g_ffn_coop && nsplit > 1 && nsplit == dff / 128 && !want_head && !x3 && d == 256) {
+    if (knobs().ffn_coop && nsplit > 1 && nsplit == dff / 128 && !want_head && !x3 && d == 256) {
         // packed copies: ffn_pc.hip's (W2 is shared with it) + the 16 x 16 x 4 fragment order of W1
         CHK(packed_ffn_of(e, w1, w2, s, &kw1, &kw2));
         const PackedW* pc = packed_of(e, PACK_FFN_COOP_W1, w1, (size_t)dff * d * sizeof(float), 0, s,
@@ -1074,10 +1025,10 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
     ProfScope ps(e, s, want_tail ? PROF_FFN_TAIL : want_head ? PROF_FFN_HEAD : PROF_FFN1,
                  4.0 * M * (double)dff * d + (want_tail ? 2.0 * M * (double)tail->N * d : 0.0) + (want_head ? 2.0 * M * (double)d * d : 0.0));
     // full launches stream PACKED weight copies straight into registers (ffn_pc.hip VAR == 2; built on first use, + 4 MB per FFN)
-    const bool packed = g_ffn_packed && (nsplit == 1 || g_ffn_packed >= 2) && d == 256;      // (key 23 = 2: the d_ff-split launches of small M too)
+    const bool packed = knobs().ffn_packed && (nsplit == 1 || knobs().ffn_packed >= 2) && d == 256;      // (key 23 = 2: the d_ff-split launches of small M too)
     // 16-row blocks, two workgroups per CU (ffn_pc.hip ffn16_kernel): every full-d_ff launch of packed weights it covers; it reads
     // copies of its own order, so the 32-row copies are not built for it
-    const bool use16 = packed && nsplit == 1 && g_ffn16 && !affine && dff % 128 == 0 && !(want_tail && tail->N % 256) &&
+    const bool use16 = packed && nsplit == 1 && knobs().ffn16 && !affine && dff % 128 == 0 && !(want_tail && tail->N % 256) &&
                        !(want_head && head->ktaps != 15 && head->ktaps != 7);
     if (packed && !use16) CHK(packed_ffn_of(e, w1, w2, s, &kw1, &kw2));
     // ... and so do the row-local stages that ride on the launch (QKV tail, pointwise_conv2 head): copies of the stage descriptors
@@ -1085,7 +1036,7 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
     FfnTail ptail = tail ? *tail : FfnTail{};
     FfnHead phead = head ? *head : FfnHead{};
     // two accumulator chains per wave (ffn_dual.hip): same arithmetic in the same order, its own packing order
-    if (packed && nsplit == 1 && g_ffn_dual && dff % 256 == 0 && dff >= 512 && !(want_tail && tail->N != 768) && !(affine && (want_tail || want_head))) {
+    if (packed && nsplit == 1 && knobs().ffn_dual && dff % 256 == 0 && dff >= 512 && !(want_tail && tail->N != 768) && !(affine && (want_tail || want_head))) {
         const float *p1, *p2;
         CHK(packed_ffn_of(e, w1, w2, s, &p1, &p2, PACK_FFN_DUAL, launch_pack_ffn_dual));
         if (want_tail) {
@@ -1134,8 +1085,6 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
     return 0;
 }
 
-static int g_hot_weights = 0;      // masr_debug_set key 19 (timing experiment only): every chunk-step layer runs on layer 0's weights
-static int g_embed_split = 1;      // masr_debug_set key 15: 0 = the offline embed projection never splits K
 // W [N = 256, K] in the row-block kernel's fragment order (gemm_f32.hip conv2_rows_kernel): the subsampling convs and the embed projection
 static const float* packed_conv2_rows_of(masr_engine* e, const float* W, int N, int K, hipStream_t s) {
     const PackedW* pk = packed_of(e, PACK_CONV2_ROWS, W, (size_t)N * K * sizeof(float), 0, s,
@@ -1149,9 +1098,9 @@ static const float* packed_conv2_rows_of(masr_engine* e, const float* W, int N, 
 static int subsampling_conv(masr_engine* e, hipStream_t s, GemmArgs a, int amode, int nseq, const float* feats, const float* x_in) {
     const int d = e->cfg.d_model;
     const int tiles = ((a.M + 63) / 64) * ((a.N + 63) / 64);
-    if (tiles >= 640 && g_conv2_rows && a.N == 256) {   // full-width row blocks: the weights in the kernel's fragment order, packed at first use
+    if (tiles >= 640 && knobs().conv2_rows && a.N == 256) {   // full-width row blocks: the weights in the kernel's fragment order, packed at first use
         if (!(a.Wp = packed_conv2_rows_of(e, a.W, a.N, a.K, s))) return 1;
-        if (feats && amode == A_CONV2 && g_conv1_fused && !g_bf16x3 && gemm_conv2_rows(a)) {    // conv1 computed in the row blocks' A gather: no x1, no conv1 launch
+        if (feats && amode == A_CONV2 && knobs().conv1_fused && !knobs().bf16x3 && gemm_conv2_rows(a)) {    // conv1 computed in the row blocks' A gather: no x1, no conv1 launch
             a.feats = feats; a.mean = e->cmvn_mean; a.istd = e->cmvn_istd; a.c1w = e->conv1_w; a.c1b = e->conv1_b;
             a.Fin = e->cfg.n_mels;
         }
@@ -1167,7 +1116,7 @@ static int subsampling_conv(masr_engine* e, hipStream_t s, GemmArgs a, int amode
         }
     }
     ProfScope ps(e, s, PROF_CONV2, 2.0 * a.M * (double)a.N * a.K);
-    if (g_bf16x3 && amode == A_CONV2 && tiles >= 640 && launch_gemm_bf16x3(a, A_CONV2, s)) {
+    if (knobs().bf16x3 && amode == A_CONV2 && tiles >= 640 && launch_gemm_bf16x3(a, A_CONV2, s)) {
         // exploratory split-bf16 mode
     } else if (tiles < 640) {
         // streaming chunk steps: ~1 workgroup of 4 waves per CU leaves the load -> LDS -> MFMA chain of every 32-wide K slab
@@ -1233,16 +1182,16 @@ int embed(masr_engine* e, hipStream_t s, const float* feats, int nseq, int T, in
         const int tiles = ((M + 63) / 64) * ((d + 63) / 64);
         const long wide = (long)((M + 63) / 64) * ((d + 127) / 128);      // 64x128 tiles of the unsplit launch
         const long t128 = (long)((M + 127) / 128) * ((d + 127) / 128);
-        if (g_bf16x3 && tiles >= 128 && launch_gemm_bf16x3(a, A_PLAIN, s)) {
+        if (knobs().bf16x3 && tiles >= 128 && launch_gemm_bf16x3(a, A_PLAIN, s)) {
             // exploratory split-bf16 mode: 5x less matrix-pipe time, no K split needed
-        } else if (g_embed_split && tiles >= 128 && t128 >= 100 && t128 <= 128) {
+        } else if (knobs().embed_split && tiles >= 128 && t128 >= 100 && t128 <= 128) {
             // B = 32 x 10 s: 124 tiles of 128x128 -- four K quarters on 8-wave workgroups = 496 workgroups, two per CU, four
             // waves per SIMD: 163 + 11 us (GEMM + reduction) against 180 + 9 us for two K halves on 64x128 tiles and 203 us unsplit
             // (full-width 64-row blocks with the weights packed at first use, the same K quarters: 124 x 4 = 496 workgroups, key 42)
-            if (g_embed_rows && d == 256 && (F2 * d) % 32 == 0 && !(a.Wp = packed_conv2_rows_of(e, e->embed_w, a.N, a.K, s))) return 1;
+            if (knobs().embed_rows && d == 256 && (F2 * d) % 32 == 0 && !(a.Wp = packed_conv2_rows_of(e, e->embed_w, a.N, a.K, s))) return 1;
             CHK(e->ffpart.ensure((size_t)4 * M * d * sizeof(float)));
             launch_gemm_splitk(a, e->ffpart.as<float>(), 4, s);
-        } else if (g_embed_split && tiles >= 128 && wide >= 200 && wide <= 320) {
+        } else if (knobs().embed_split && tiles >= 128 && wide >= 200 && wide <= 320) {
             // about one 4-wave workgroup per CU: two K halves put two waves on every SIMD
             CHK(e->ffpart.ensure((size_t)2 * M * d * sizeof(float)));
             launch_gemm_splitk(a, e->ffpart.as<float>(), 2, s);
@@ -1309,7 +1258,7 @@ int conv_module(masr_engine* e, hipStream_t s, const LayerW& w, const EncodeCtx&
         a.W = w.pw2_w; a.bias = w.pw2_b; a.C = x; a.ldc = d; a.R = x; a.ldr = d; a.M = M; a.N = d; a.alpha = 1.f; a.eps = 1e-5f;
         a.mstride = mstride; a.seq_t = c.Tq; a.pad = pad; a.lens = c.lens; a.mask_tp = c.lens ? c.Tq : 0;
         ProfScope ps(e, s, PROF_GEMM, 2.0 * M * (double)d * d);
-        if (!e->conv_bn && g_few_rows_path && launch_rowgemm(a, RG_PRO_DWCONV, RG_EPI_RESID, s)) return 0;
+        if (!e->conv_bn && knobs().few_rows_path && launch_rowgemm(a, RG_PRO_DWCONV, RG_EPI_RESID, s)) return 0;
     }
     if (e->conv_bn)        // BatchNorm build: the depthwise kernel's BN variant (the Squeezeformer's), then pointwise_conv2
         launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), c.nseq, c.Tq, K, s, gconst);
@@ -1391,7 +1340,7 @@ void mhsa_out_pw1(masr_engine* e, hipStream_t s, const LayerW& w, const EncodeCt
     a.C = e->glu.as<float>(); a.ldc = d; a.M = M; a.N = 3 * d; a.R = x; a.R2 = x; a.ldr = d; a.alpha = 1.f;
     a.lens = c.lens; a.seq_t = c.Tq; a.mstride = mstride; a.eps = 1e-5f;
     a.out_seq_t = c.Tq; a.out_pad_l = e->cfg.causal ? pad : pad / 2; a.out_pad_tot = pad;
-    if (g_rowgemm_packed) a.Wp = packed_rows_of(e, w.chain_w, 3 * d, s);
+    if (knobs().rowgemm_packed) a.Wp = packed_rows_of(e, w.chain_w, 3 * d, s);
     ProfScope ps(e, s, PROF_GEMM, 2.0 * M * (double)(3 * d) * d);
     launch_rowgemm(a, RG_PRO_PLAIN, RG_EPI_CHAIN, s);
 }
@@ -1626,7 +1575,7 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
         const int M = B * Tq;
         // Fused layer (sqz_layer.hip): attention + two row-block kernels.  Taken when the row blocks fill the chip (below that the
         // d_ff-split FFN and the K-split projections of the unfused sequence are the faster launches); bit-identical either way.
-        const bool fused = g_sqz_fused_blocks > 0 && (M + 31) / 32 >= g_sqz_fused_blocks && sqz_stage_supported(e);
+        const bool fused = knobs().sqz_fused_blocks > 0 && (M + 31) / 32 >= knobs().sqz_fused_blocks && sqz_stage_supported(e);
         // x = LN1(x + MHSA(ada(x)))
         if (!qkv_ready)
             {
@@ -1748,8 +1697,8 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
         int M = B * Tq;
         const int Ki = layer_kernel(e, i);
         // enough row blocks for the full (non d_ff-split) FFN launch: the Conformer's fused launches (key 31 = 0: separate ones)
-        const bool fused = g_efficient_fused && !g_no_chain && !g_no_ffn_head && i != e->stride_idx &&
-                           (M + 31) / 32 >= g_ffn_split_blocks && (Ki == 15 || Ki == 7) && d == 256;
+        const bool fused = knobs().efficient_fused && !knobs().no_chain && !knobs().no_ffn_head && i != e->stride_idx &&
+                           (M + 31) / 32 >= knobs().ffn_split_blocks && (Ki == 15 || Ki == 7) && d == 256;
         const EncodeCtx ctx0{B, Tq, lens};
         // regular layers: LayerNorm + fused QKV projection ride on the first FFN kernel (tail stage), like the Conformer
         const FfnTail tail{w.ln_mha_w, w.ln_mha_b, w.wqkv, w.bqkv, e->qkv.as<float>(), 3 * d, 3 * d, nullptr, nullptr};
@@ -1757,7 +1706,7 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
         // grouped layers: the same tail stage writes q | k | v PLANAR into the time-padded buffers of the grouped attention
         // (round 4; ffn_pc.hip only -- the two-chain kernel keeps the separate projection)
         const FfnTail gtail{w.ln_mha_w, w.ln_mha_b, w.wqkv, w.bqkv, qp, 3 * d, d, nullptr, nullptr, (long)plane, Tq, Tpad - Tq};
-        const bool planar_tail = layer_grouped(e, i) && g_efficient_fused && !g_ffn_dual;
+        const bool planar_tail = layer_grouped(e, i) && knobs().efficient_fused && !knobs().ffn_dual;
         CHK(ffn(e, s, M, w.ln_ffm_w, w.ln_ffm_b, w.ffm_w1, w.ffm_b1, w.ffm_w2, w.ffm_b2, 0.5f, 0, nullptr, nullptr, nullptr,
                 layer_grouped(e, i) ? (planar_tail ? &gtail : nullptr) : &tail, &qkv_done));
         if (layer_grouped(e, i)) {
@@ -2035,7 +1984,7 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
     if (!e->cfg.causal)     // symmetric conv: the (K-1)/2 pad rows on both sides of every sequence stay zero for all layers
         HIPCHK(hipMemsetAsync(e->glu.p, 0, (size_t)B * (Tq + pad) * d * sizeof(float), s));
     const LayerW* prev = nullptr;                 // layer whose norm_final is still pending (it rides on the next FFN launch)
-    const bool few_rows = g_few_rows_path && (M + 31) / 32 < std::min(rowgemm_small_blocks(), g_ffn_split_blocks);
+    const bool few_rows = knobs().few_rows_path && (M + 31) / 32 < std::min(knobs().rowgemm_small_blocks, knobs().ffn_split_blocks);
     for (const LayerW& w : e->layers) {
         // first macaron FFN with the attention block's LayerNorm + fused QKV projection as its tail stage (full kernel only)
         const FfnTail tail{w.ln_mha_w, w.ln_mha_b, w.wqkv, w.bqkv, e->qkv.as<float>(), 3 * d, 3 * d,
@@ -2045,7 +1994,7 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
                 &qkv_done));
         if (!qkv_done) mhsa(e, s, w, M);
         // attention and the chain kernel behind it as ONE launch (32 queries x all four heads per workgroup; key 34 = 0: two launches)
-        const bool fuse_ac = g_attn_chain && !few_rows && !g_no_chain && !e->conv_bn && H == 4 && d == 256 && g_rowgemm_packed;
+        const bool fuse_ac = knobs().attn_chain && !few_rows && !knobs().no_chain && !e->conv_bn && H == 4 && d == 256 && knobs().rowgemm_packed;
         if (fuse_ac) {
             AttnChainArgs a{};
             a.seqs = e->attseq.as<AttSeq>(); a.nseq = B; a.q_stride = 3 * d; a.kv_stride = 3 * d;
@@ -2068,14 +2017,14 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
             // 7.4 + 7.7 us for the two K-split launches whose columns spread over the chip); norm_final rides on the split
             // FFN's reduction
             mhsa_out(e, s, w, M);
-            const bool fuse = g_split_head && e->cfg.cnn_kernel == 15 && g_ffn_packed >= 2 && !g_no_ffn_head && !e->conv_bn;
+            const bool fuse = knobs().split_head && e->cfg.cnn_kernel == 15 && knobs().ffn_packed >= 2 && !knobs().no_ffn_head && !e->conv_bn;
             CHK(conv_module(e, s, w, ctx, false, 0, 4, false, fuse));
             const FfnHead head{e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->cfg.causal ? w.gconst : nullptr,
                                w.pw2_w, w.pw2_b, feat_lens_dev, Tq, e->cfg.cnn_kernel, 4, nullptr};
             CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2, 0.5f, 0, w.ln_fin_w, w.ln_fin_b, x, nullptr,
                     nullptr, fuse ? &head : nullptr));
             continue;                              // (prev stays null: nothing deferred)
-        } else if (g_no_chain || e->conv_bn) {      // (BatchNorm build: the fused head stage carries the LayerNorm variant only)
+        } else if (knobs().no_chain || e->conv_bn) {      // (BatchNorm build: the fused head stage carries the LayerNorm variant only)
             mhsa_out(e, s, w, M);
             CHK(conv_module(e, s, w, ctx, false));
             CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2));
@@ -2096,7 +2045,6 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
     return 0;
 }
 
-static int g_ctc_fused_blocks = 160;     // masr_debug_set key 27: row blocks from which the fused CTC head (rowgemm EPI_CTC) runs
 static int ctc_head(masr_engine* e, const float* enc_dev, int M, float* probs_dev, int write_probs, int32_t* argmax_dev,
                     float* maxprob_dev, hipStream_t s) {
     const int d = enc_dim(e), V = e->cfg.vocab_size;
@@ -2129,9 +2077,9 @@ int masr_ctc_greedy_frames(masr_engine* e, const float* enc_dev, int32_t M, int3
     if (e->cfg.model_kind == 3)      // K = 1024 / 2048 rows: generic GEMM + softmax statistics (logits stay in a workspace)
         return ctc_head(e, enc_dev, M, nullptr, 0, argmax_dev, maxprob_dev, (hipStream_t)stream);
     // few row blocks (one utterance: 7; the Efficient Conformer's half-rate output at 32 x 10 s: 124): the fused head gives a
-    // workgroup 32 rows x the WHOLE vocabulary (165 us whether 7 or 248 row blocks run); below g_ctc_fused_blocks the logits go
+    // workgroup 32 rows x the WHOLE vocabulary (165 us whether 7 or 248 row blocks run); below knobs().ctc_fused_blocks the logits go
     // through the tiled GEMM (vocabulary spread over the CUs) into a workspace and the softmax statistics are a second launch
-    if ((M + 31) / 32 < g_ctc_fused_blocks) return ctc_head(e, enc_dev, M, nullptr, 0, argmax_dev, maxprob_dev, (hipStream_t)stream);
+    if ((M + 31) / 32 < knobs().ctc_fused_blocks) return ctc_head(e, enc_dev, M, nullptr, 0, argmax_dev, maxprob_dev, (hipStream_t)stream);
     // fused: logits GEMM + online softmax statistics + argmax, nothing but (idx, prob) leaves the chip
     {
         RowGemmArgs g = rg_args(enc_dev, e->cfg.d_model, e->ctc_w, e->ctc_b, nullptr, 0, M, e->cfg.vocab_size);
@@ -2188,12 +2136,10 @@ int masr_ctc_topk_blank(masr_engine* e, const float* probs_dev, int32_t M, int32
     return 0;
 }
 
-static int g_beam_narrow = 1;      // masr_debug_set key 37: 0 = every frame of the GPU prefix search on the wide (1024-thread) step (A/B, tests)
-static int g_beam_lm_cache = 1;    // masr_debug_set key 32: 0 = the GPU prefix search probes the scorer once per (prefix, candidate) pair (A/B)
 static int bind_lm(BeamGpuArgs& a, masr_lm* lm, float alpha, float beta) {
     a.use_lm = 0;
-    a.lm_cache = g_beam_lm_cache;
-    a.narrow = g_beam_narrow;
+    a.lm_cache = knobs().beam_lm_cache;
+    a.narrow = knobs().beam_narrow;
     a.alpha = alpha;
     a.beta = beta;
     if (!lm) return 0;
@@ -3114,7 +3060,7 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
     float* x = e->x.as<float>();
     EncodeCtx ctx{n, Tq, nullptr};
     for (int l = 0; l < L; ++l) {
-        const LayerW& w = e->layers[g_hot_weights ? 0 : l];
+        const LayerW& w = e->layers[knobs().hot_weights ? 0 : l];
         CHK(ffn(e, s, M, w.ln_ffm_w, w.ln_ffm_b, w.ffm_w1, w.ffm_b1, w.ffm_w2, w.ffm_b2));
         mhsa(e, s, w, M, e->attseq.as<AttSeq>() + (size_t)l * n, Tq);     // q -> qkv buffer, k|v rows -> the streams' caches
         launch_attention(e->attseq.as<AttSeq>() + (size_t)l * n, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, 1, s);
@@ -3122,7 +3068,7 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
         float* const* cptr = e->cnnptrs.as<float*>() + (size_t)l * n;
         // [depthwise conv -> LN -> SiLU -> pointwise_conv2 + residual] rides on the second FFN launch as its head stage (on the
         // d_ff-split launch of few streams every slice repeats it on the row block's rows; one launch less on the step's chain)
-        const bool fuse = g_split_head && e->cfg.cnn_kernel == 15 && g_ffn_packed >= 2 && !g_no_ffn_head;
+        const bool fuse = knobs().split_head && e->cfg.cnn_kernel == 15 && knobs().ffn_packed >= 2 && !knobs().no_ffn_head;
         CHK(conv_module_stream(e, s, w, n, Tq, cptr, cptr + (size_t)L * n, e->cfg.cnn_kernel, fuse));
         const FfnHead head{e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, nullptr, w.pw2_w, w.pw2_b, nullptr, Tq,
                            e->cfg.cnn_kernel, 4, nullptr};
@@ -3240,48 +3186,13 @@ int masr_side_stream(masr_engine* e, int32_t kind, void** stream_out) {
 
 int masr_debug_set(masr_engine* e, int32_t key, int32_t value) {
     if (!e) return fail("null engine");
-#if !MASR_EXPERIMENTS
-    if (value != 0 && (key == 20 || key == 21 || key == 22 || key == 24 || key == 30 || key == 34 || key == 35))
-        return fail("masr_debug_set: this key selects an experimental kernel that is not in this build (MASR_BUILD_EXPERIMENTS=1)");
-#endif
-    if (key == 1) set_ffn_variant(value);
-    else if (key == 5) g_no_chain = value;
-    else if (key == 6) set_rowgemm_small(value);
-    else if (key == 7) set_attention_fewq(value);
-    else if (key == 14) set_attention_fold(value);
-    else if (key == 15) g_embed_split = value;
-    else if (key == 19) g_hot_weights = value;
-    else if (key == 20) g_bf16x3 = value;
-    else if (key == 21) set_gemm_bf16x3_waves(value);
-    else if (key == 22) set_ffn_x3_rotation(value);
-    else if (key == 23) g_ffn_packed = value;
-    else if (key == 24) g_ffn_dual = value;
-    else if (key == 25) g_rowgemm_packed = value;
-    else if (key == 26) set_attention_grouped_fold(value);
-    else if (key == 27) g_ctc_fused_blocks = value;
-    else if (key == 28) set_attention_fewq_wgs(value);
-    else if (key == 29) g_few_rows_path = value;
-    else if (key == 30) g_split_head = value;
-    else if (key == 31) g_efficient_fused = value;
-    else if (key == 32) g_beam_lm_cache = value;
-    else if (key == 33) set_conv2_mid_fill(value);
-    else if (key == 34) g_attn_chain = value;
-    else if (key == 35) g_ffn_coop = value;
-    else if (key == 36) g_sqz_fused_blocks = value;
-    else if (key == 37) g_beam_narrow = value;
-    else if (key == 38) e->skip_padding = value;
-    else if (key == 39) g_ffn16 = value;
-    else if (key == 40) g_conv2_rows = value;
-    else if (key == 41) g_conv1_fused = value;
-    else if (key == 42) g_embed_rows = value;
-    else if (key == 43) { set_gru_mfma_units(value); set_lstm_mfma_units(value); }
-    else if (key == 17) set_gemm_waves(value);
-    else if (key == 18) set_conv1_nt(value);
+    const KnobInfo* k = knob_find(key);
+    if (k) {
+        if (!MASR_EXPERIMENTS && k->experimental && value != 0)
+            return fail("masr_debug_set: this key selects an experimental kernel that is not in this build (MASR_BUILD_EXPERIMENTS=1)");
+        knob_set(key, value);
+    } else if (key == 38) e->skip_padding = value;
     else if (key == 16) { e->prof_stride = value > 1 ? value : 1; e->prof_seen = 0; }
-    else if (key == 8) g_no_ffn_tail = value;
-    else if (key == 9) g_no_ffn_head = value;
-    else if (key == 12) set_rowgemm_small_blocks(value);
-    else if (key == 13) g_ffn_split_blocks = value;
     else if (key == 2) {            // beam search phase profile of workgroup 0: value 1 = on, 0 = print + off
         if (value) {
             if (!e->beam_prof) {
@@ -3302,6 +3213,25 @@ int masr_debug_set(masr_engine* e, int32_t key, int32_t value) {
         }
     }
     else return fail("unknown debug key");
+    return 0;
+}
+
+int masr_debug_reset(masr_engine* e) {
+    if (!e) return fail("null engine");
+    knobs_reset();
+    e->skip_padding = 7;
+    e->prof_stride = 1;
+    e->prof_seen = 0;
+    return 0;
+}
+
+int masr_debug_key_info(int32_t index, int32_t* key, int32_t* default_value, int32_t* experimental, const char** name) {
+    const KnobInfo* k = knob_info(index);
+    if (!k) return 1;
+    if (key) *key = k->key;
+    if (default_value) *default_value = knob_default(*k);
+    if (experimental) *experimental = k->experimental;
+    if (name) *name = k->name;
     return 0;
 }
 

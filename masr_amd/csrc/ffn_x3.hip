@@ -255,9 +255,6 @@ __global__ __launch_bounds__(512) void ffn_x3_kernel(float* __restrict__ x, cons
 
 }  // namespace
 
-static int g_x3_rot = 1;
-void set_ffn_x3_rotation(int on) { g_x3_rot = on; }
-
 size_t ffn_x3_packed_elems(int dff) { return (size_t)2 * dff * FX_D; }      // bf16 elements per packed matrix (hi + lo)
 
 void launch_pack_ffn_x3(const float* w1, const float* w2, unsigned short* p1, unsigned short* p2, int dff, hipStream_t s) {
@@ -270,7 +267,7 @@ bool launch_ffn_x3(float* x, const float* lnw, const float* lnb, const unsigned 
                    const unsigned short* p2, const float* b2, int M, int dff, float eps, float scale, hipStream_t s) {
     if (M <= 0 || dff % FX_CH != 0 || dff / FX_CH < 1) return false;
     hipLaunchKernelGGL(ffn_x3_kernel, dim3((M + 31) / 32), dim3(512), 0, s, x, lnw, lnb, p1, b1, p2, b2, M, dff, eps, scale,
-                       g_x3_rot);
+                       knobs().ffn_x3_rotation);
     return true;
 }
 

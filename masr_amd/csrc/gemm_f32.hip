@@ -480,13 +480,6 @@ void launch_pack_conv2_rows(const float* w, float* p, int K, hipStream_t s) {
     hipLaunchKernelGGL(pack_conv2_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, p, K);
 }
 
-// waves per workgroup of the conv2 implicit GEMM on 128x128 tiles: 8 (default) or 4 (masr_debug_set key 17).  In one kernel
-// trace with both shapes alternating (tools/gemm_waves_trace.py): 1 467 vs 1 486 us on average, 1 437 vs 1 480 us at best.
-static int g_gemm_waves = 8;
-static int g_conv2_mid_fill = 50;     // 128 streams: 3.26 -> 3.19 ms per chunk call (tools/chunk_lat.py MASR_AB=33:0,33:50)
-void set_conv2_mid_fill(int pct) { g_conv2_mid_fill = pct; }
-void set_gemm_waves(int n) { g_gemm_waves = n; }
-
 template <int BM, int BN, int WM, int WN, int AMODE, int EPI>
 static void launch_t(const GemmArgs& a, hipStream_t s) {
     const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
@@ -518,11 +511,12 @@ static int conv2_tiles(const GemmArgs& a) {
     // few output rows (streaming chunk steps): 64x64 tiles so that the grid still covers the chip
     const long t128c = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
     // mid sizes (the 128-stream chunk step: 608 tiles of 128x128 on 512 resident slots = two rounds, the second at 19 %):
-    // 128x64 tiles (four waves, the tile count doubles) when the last round of the 128x128 grid would be under g_conv2_mid_fill
+    // 128x64 tiles (four waves, the tile count doubles) when the last round of the 128x128 grid would be under conv2_mid_fill
     // percent full (masr_debug_set key 33; 0 = never)
     const long rounds = (t128c + 511) / 512;
-    const bool thin_tail = g_conv2_mid_fill > 0 && t128c >= 200 && t128c <= 1024 &&
-                           (t128c - (rounds - 1) * 512) * 100 < (long)g_conv2_mid_fill * 512;
+    const int mid_fill = knobs().conv2_mid_fill;
+    const bool thin_tail = mid_fill > 0 && t128c >= 200 && t128c <= 1024 &&
+                           (t128c - (rounds - 1) * 512) * 100 < (long)mid_fill * 512;
     if (t128c < 200) return 64;
     if (thin_tail) return 128;
     return a.Wp && a.N == RB_N && a.K % BK == 0 ? 0 : 256;
@@ -557,7 +551,7 @@ void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s) {
             const dim3 grid((unsigned)((a.M + RB_BM - 1) / RB_BM));
             if (a.feats) hipLaunchKernelGGL(conv2_rows_kernel<RB_FUSED>, grid, dim3(512), 0, s, a);
             else hipLaunchKernelGGL(conv2_rows_kernel<RB_X1>, grid, dim3(512), 0, s, a);
-        } else if (g_gemm_waves == 8) launch_t<128, 128, 2, 4, A_CONV2, EPI_STD>(a, s);
+        } else if (knobs().gemm_waves == 8) launch_t<128, 128, 2, 4, A_CONV2, EPI_STD>(a, s);
         else launch_t<128, 128, 2, 2, A_CONV2, EPI_STD>(a, s);
         return;
     }

@@ -158,11 +158,11 @@ __global__ __launch_bounds__(512) void gru_step_mfma_kernel(const float* __restr
     }
 }
 
-// masr_debug_set key 43: hidden units per workgroup of the matrix-core form.  8 = the product's choice (4 units at rnn_size <= 512,
-// where 8 leave most CUs without a workgroup: measured 10 - 16 % per step, docs/LAB_NOTES.md 18; 8 units above), 16 = 16 units at
-// rnn_size 1024, -8 = 8 units at every size (the A/B side of the small sizes; the same bits)
-static int g_gru_units = 8;
-void set_gru_mfma_units(int u) { g_gru_units = u == 16 || u == -8 ? u : 8; }
+// masr_debug_set key 43 (knobs.h rnn_mfma_units): hidden units per workgroup of the matrix-core form; any value but 16 and -8 is 8
+static int gru_units() {
+    const int u = knobs().rnn_mfma_units;
+    return u == 16 || u == -8 ? u : 8;
+}
 
 template <int H, int U>
 static void launch_gru_mfma(const float* gx, const float* whh, const float* bhn, const float* h_prev, float* h_next, float* out,
@@ -179,10 +179,10 @@ static void launch_gru_step_h(const float* gx, const float* whh, const float* bh
                               const int* lens, int B, int T, int step, int ndir, hipStream_t s) {
     if (B > 4 && B <= 32) {           // matrix-core form: U units per workgroup, 16 * BT sequences
         if constexpr (H == 1024) {
-            if (g_gru_units == 16) return launch_gru_mfma<H, 16>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s);
+            if (gru_units() == 16) return launch_gru_mfma<H, 16>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s);
         }
         if constexpr (H <= 512) {
-            if (g_gru_units != -8) return launch_gru_mfma<H, 4>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s);
+            if (gru_units() != -8) return launch_gru_mfma<H, 4>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s);
         }
         return launch_gru_mfma<H, 8>(gx, whh, bhn, h_prev, h_next, out, lens, B, T, step, ndir, s);
     }

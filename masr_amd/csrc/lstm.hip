@@ -178,8 +178,6 @@ __global__ __launch_bounds__(512) void lstm_step_mfma_kernel(const float* __rest
 // Units per workgroup of the matrix-core form: 4 at rnn_size <= 512, where 8 leave most CUs without a workgroup (H / 8 x ndir = 32
 // to 128 workgroups on 256 CUs; measured 10 - 17 % per step, docs/LAB_NOTES.md 18), 8 above.  masr_debug_set key 43 = -8 runs 8
 // units at every size (the A/B side; the same bits).
-static bool g_lstm_units8 = false;
-void set_lstm_mfma_units(int u) { g_lstm_units8 = u == -8; }
 
 template <int H, int U>
 static void launch_lstm_mfma(const float* gx, const float* whh, const float* h_prev, float* h_next, float* c, float* out,
@@ -194,7 +192,7 @@ static void launch_lstm_step_h(const float* gx, const float* whh, const float* h
                                const int* lens, int B, int T, int step, int ndir, hipStream_t s) {
     if (B > 4 && B <= 32) {           // matrix-core form: U units per workgroup, 16 * BT sequences
         if constexpr (H <= 512) {
-            if (!g_lstm_units8) return launch_lstm_mfma<H, 4>(gx, whh, h_prev, h_next, c, out, lens, B, T, step, ndir, s);
+            if (knobs().rnn_mfma_units != -8) return launch_lstm_mfma<H, 4>(gx, whh, h_prev, h_next, c, out, lens, B, T, step, ndir, s);
         }
         return launch_lstm_mfma<H, 8>(gx, whh, h_prev, h_next, c, out, lens, B, T, step, ndir, s);
     }

@@ -458,15 +458,12 @@ static void launch_rowgemm_big(const RowGemmArgs& a, int pro, int epi, hipStream
     else if (pro == RG_PRO_PLAIN && epi == RG_EPI_CHAIN) launch_rg<RG_PRO_PLAIN, RG_EPI_CHAIN>(a, s);
 }
 
-static int g_small = 1;
-void set_rowgemm_small(int on) { g_small = on; }
-
 // false: nothing was launched (the fused streaming prologues HIST / DWCONV exist in the small-M kernel only; the caller then
 // runs the unfused sequence)
 bool launch_rowgemm(const RowGemmArgs& a, int pro, int epi, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) return true;
     // few row blocks (streaming chunk steps, short utterances): K-split kernel with 4x more, 4x shorter workgroups
-    if (g_small && launch_rowgemm_small(a, pro, epi, s)) return true;
+    if (knobs().rowgemm_small && launch_rowgemm_small(a, pro, epi, s)) return true;
     if (pro == RG_PRO_HIST || pro == RG_PRO_DWCONV) return false;
     launch_rowgemm_big(a, pro, epi, s);
     // the big kernel stores all QKV columns to C; the streams' cache append is then its own launch

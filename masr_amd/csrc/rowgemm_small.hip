@@ -343,20 +343,13 @@ static void launch_rs(const RowGemmArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((rowgemm_small_kernel<PRO, EPI>), dim3(ny, rowblocks), dim3(512), 0, s, a);
 }
 
-// true when the small-M kernel took the launch
-// row blocks (of 32 rows) below which the K-split kernel takes the projection: 4x more, 4x shorter workgroups fill the chip
-// where a 32-row x N workgroup per row block leaves CUs idle (128 lock-step streams = 64 row blocks: chunk call 5.75 -> 5.34 ms;
-// tools/chunk_step_ab.py).  At 124 row blocks (16 x 10 s; the Efficient Conformer's half-rate layers at 32 x 10 s) the row-block
-// kernel is ahead again: 4.56 -> 4.42 ms per forward, 6.11 -> 6.04 ms per Efficient-Conformer pass (tools/offline_size_ab.py,
-// tools/efficient_size_ab.py); 93 row blocks are indifferent
-static int g_small_blocks = 112;
-void set_rowgemm_small_blocks(int n) { g_small_blocks = n; }
-int rowgemm_small_blocks() { return g_small_blocks; }
+// true when the small-M kernel took the launch (below knobs().rowgemm_small_blocks row blocks of 32 rows)
 bool launch_rowgemm_small(const RowGemmArgs& a, int pro, int epi, hipStream_t s) {
     // (the streaming conv module's fused prologues exist only here: where this kernel declines, the caller runs an extra launch in
     //  front of the row-block kernel -- 128 streams = 120 padded row blocks of pointwise_conv1: 3.26 -> 3.18 ms per chunk call with
     //  the limit at 160 for those two prologues, tools/chunk_lat.py MASR_AB=12:112,12:128)
-    const int limit = (pro == RG_PRO_HIST || pro == RG_PRO_DWCONV) ? std::max(g_small_blocks, 160) : g_small_blocks;
+    const int small_blocks = knobs().rowgemm_small_blocks;
+    const int limit = (pro == RG_PRO_HIST || pro == RG_PRO_DWCONV) ? std::max(small_blocks, 160) : small_blocks;
     if (a.M <= 0 || a.M >= limit * 32) return false;
     if (epi == RG_EPI_GLU ? a.N != 512 : (a.N % 64) != 0) return false;
     if (pro == RG_PRO_AFFINE && a.lens && a.seq_t > 0) return false;       // pad masking in the prologue: big kernel only

@@ -376,6 +376,7 @@ def test_gpu_narrow_step_equals_wide_step_on_the_same_frames(tmp_path, lm_order,
     frame on the wide step.  Same candidates, same frames: transcripts AND scores must be identical (not close), offline and
     through the streaming state; both equal the host search."""
     from masr_amd import runtime
+    from masr_amd._lib import debug_keys
     from masr_amd.decoders.beam_search_decoder import BeamSearchDecoder
     rng = np.random.default_rng(77 + beam)
     probs = [_mixed_posteriors(rng, V, T, sharp_every=se) for T, se in ((90, 3), (61, 1000), (40, 2), (17, 1))]
@@ -387,9 +388,8 @@ def test_gpu_narrow_step_equals_wide_step_on_the_same_frames(tmp_path, lm_order,
         dec = BeamSearchDecoder(0, 0, beam, 0.99, 40, vocab, num_processes=4, language_model_path=None)
     eng = runtime.aux_engine()
     out = {}
-    try:
-        for mode in (1, 0):
-            assert eng.lib.masr_debug_set(eng.h, 37, mode) == 0
+    for mode in (1, 0):
+        with debug_keys(eng, beam_narrow=mode):
             dec.use_gpu_search = True
             off = dec._batch(probs)
             dec.reset_decoder()
@@ -398,8 +398,6 @@ def test_gpu_narrow_step_equals_wide_step_on_the_same_frames(tmp_path, lm_order,
                 chunks.append(dec.decode_chunk(probs[0][None, lo:lo + 16], [min(16, 90 - lo)]))
             dec.reset_decoder()
             out[mode] = (off, chunks)
-    finally:
-        eng.lib.masr_debug_set(eng.h, 37, 1)
     assert out[1] == out[0]
     assert out[1][1][-1][1] == out[1][0][0][1] and abs(out[1][1][-1][0] - out[1][0][0][0]) < 1e-3 * max(1.0, abs(out[1][0][0][0]))
     dec.use_gpu_search = False

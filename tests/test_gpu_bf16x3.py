@@ -15,20 +15,10 @@ pytestmark = [pytest.mark.gpu, needs_experiments()]
 
 @pytest.fixture()
 def x3():
-    """switches the mode on for one test and off again whatever happens (the switch is process-wide)"""
-    from masr_amd import _lib
-    lib = _lib.lib()
-    engines = []
-
-    def on(eng, value=3):                 # 3 = every kernel of the mode, the unfused split-bf16 FFN included
-        engines.append(eng)
-        lib.masr_debug_set(eng.h, 20, value)
-
-    def off(eng):
-        lib.masr_debug_set(eng.h, 20, 0)
-    yield on, off
-    for e in engines:
-        lib.masr_debug_set(e.h, 20, 0)
+    """x3(eng) switches the mode on for a block and every switch back to its default behind it, whatever happens (the switch is
+    process-wide); value 3 = every kernel of the mode, the unfused split-bf16 FFN included"""
+    from masr_amd._lib import debug_keys
+    return lambda eng, value=3: debug_keys(eng, bf16x3=value)
 
 
 def _op_gemm(eng, a, w, bias, res, act, alpha):
@@ -47,7 +37,6 @@ def _op_gemm(eng, a, w, bias, res, act, alpha):
                                                       (65, 4233, 256, 0, 1.0, False)])
 def test_split_bf16_gemm_against_float64(x3, M, N, K, act, alpha, with_res):
     from masr_amd import runtime
-    on, off = x3
     eng = runtime.aux_engine()
     g = torch.Generator(device='cpu').manual_seed(M + N + K)
     a = (torch.randn(M, K, generator=g) * 2.0 + 0.5).cuda()
@@ -61,9 +50,8 @@ def test_split_bf16_gemm_against_float64(x3, M, N, K, act, alpha, with_res):
         ref = ref * torch.sigmoid(ref)
     ref = ref * alpha + (res.double() if with_res else 0.0)
     f32 = _op_gemm(eng, a, w, bias, res, act, alpha)
-    on(eng)
-    b3 = _op_gemm(eng, a, w, bias, res, act, alpha)
-    off(eng)
+    with x3(eng):
+        b3 = _op_gemm(eng, a, w, bias, res, act, alpha)
     torch.cuda.synchronize()
     scale = float(ref.abs().max())
     e32 = float((f32.double() - ref).abs().max()) / scale
@@ -79,7 +67,6 @@ def test_conformer_forward_in_split_bf16_mode_keeps_the_parity_bars(x3):
     from masr_amd.engine import HipEngine
     from masr_amd.utils import synthetic
     from oracle import conformer as oc
-    on, off = x3
     V = 512
     sd = synthetic.conformer_state_dict(0, V)
     eng = HipEngine(sd, vocab_size=V)
@@ -93,11 +80,10 @@ def test_conformer_forward_in_split_bf16_mode_keeps_the_parity_bars(x3):
     feats, frames = eng.fbank_batch(pcm_d, n_d)
     enc32 = eng.encode_full(feats, frames, -1).clone()
     tok32, nt32, sc32 = [t.clone() for t in eng.transcribe_batch(pcm_d, n_d)]
-    on(eng)
-    enc3 = eng.encode_full(feats, frames, -1).clone()
-    probs3 = eng.ctc_probs(enc3).clone()
-    tok3, nt3, sc3 = [t.clone() for t in eng.transcribe_batch(pcm_d, n_d)]
-    off(eng)
+    with x3(eng):
+        enc3 = eng.encode_full(feats, frames, -1).clone()
+        probs3 = eng.ctc_probs(enc3).clone()
+        tok3, nt3, sc3 = [t.clone() for t in eng.transcribe_batch(pcm_d, n_d)]
     torch.cuda.synchronize()
     assert not torch.equal(enc32, enc3)
     assert float((enc32 - enc3).abs().max()) < 2e-4
@@ -108,15 +94,14 @@ def test_conformer_forward_in_split_bf16_mode_keeps_the_parity_bars(x3):
             f = feats[i:i + 1, :int(frames[i])].cpu()
             ref = oc.encoder_full(sd, f, frames[i:i + 1].cpu().long(), -1)
             t = ref.shape[1]
-            single = eng_forward_single(eng, on, off, f)
+            single = eng_forward_single(eng, x3, f)
             assert float((single[0, :t] - ref[0]).abs().max()) < 1e-3
     eng.close()
 
 
-def eng_forward_single(eng, on, off, feats_cpu):
-    on(eng)
-    out = eng.encode_full(feats_cpu.cuda(), torch.tensor([feats_cpu.shape[1]], dtype=torch.int32).cuda(), -1).cpu()
-    off(eng)
+def eng_forward_single(eng, x3, feats_cpu):
+    with x3(eng):
+        out = eng.encode_full(feats_cpu.cuda(), torch.tensor([feats_cpu.shape[1]], dtype=torch.int32).cuda(), -1).cpu()
     return out
 
 
@@ -124,7 +109,6 @@ def eng_forward_single(eng, on, off, feats_cpu):
 def test_sibling_encoders_in_split_bf16_mode(x3, kind):
     from masr_amd.engine import HipEngine
     from masr_amd.utils import synthetic
-    on, off = x3
     V = 512
     sd = getattr(synthetic, kind + '_state_dict')(0, V)
     eng = HipEngine(sd, vocab_size=V, use_model=kind, streaming=(kind != 'squeezeformer'))
@@ -132,9 +116,8 @@ def test_sibling_encoders_in_split_bf16_mode(x3, kind):
     n = torch.full((8,), 120000, dtype=torch.int32).cuda()
     feats, frames = eng.fbank_batch(pcm, n)
     a = eng.encode_full(feats, frames, -1).clone()
-    on(eng)
-    b = eng.encode_full(feats, frames, -1).clone()
-    off(eng)
+    with x3(eng):
+        b = eng.encode_full(feats, frames, -1).clone()
     torch.cuda.synchronize()
     assert not torch.equal(a, b) and float((a - b).abs().max()) < 3e-4
     eng.close()
@@ -145,15 +128,13 @@ def test_reference_facade_transcript_identical_in_split_bf16_mode(x3, tmp_path):
     normalisation off -- identical with the mode on (text ==, score to 1e-3); the streaming path keeps the fp32 kernels"""
     import os
     from tests.test_gpu_identity import GOLDEN, _predictor
-    on, off = x3
     pred = _predictor(str(tmp_path), False)
     z = np.load(os.path.join(GOLDEN, 'predictor_nonorm.npz'), allow_pickle=True)
     pcm = np.load(os.path.join(GOLDEN, 'testwav.npz'))['pcm']
     base = pred.predict(audio_data=pcm.copy())
-    on(pred.predictor.engine)
-    got = pred.predict(audio_data=pcm.copy())
-    batch = pred.predict_batch([pcm.copy(), pcm[:70000].copy(), pcm.copy()])
-    off(pred.predictor.engine)
+    with x3(pred.predictor.engine):
+        got = pred.predict(audio_data=pcm.copy())
+        batch = pred.predict_batch([pcm.copy(), pcm[:70000].copy(), pcm.copy()])
     assert got['text'] == base['text'] == str(z['offline_text'])
     assert abs(got['score'] - float(z['offline_score'])) < 1e-3 * max(1.0, abs(float(z['offline_score'])))
     assert batch[0]['text'] == batch[2]['text'] == got['text']

@@ -21,15 +21,13 @@ def _takes_row_blocks(nseq, T):
     return M, t128 > 1024 or (t128 >= 200 and (t128 - (rounds - 1) * 512) * 100 >= 50 * 512)
 
 
-def _both(eng, feats, lens):
+def _both(eng, feats, lens, **keys):
+    from masr_amd._lib import debug_keys
     out = {}
-    try:
-        for v in (1, 0, 1):
-            assert eng.lib.masr_debug_set(eng.h, 40, v) == 0
+    for v in (1, 0, 1):
+        with debug_keys(eng, conv2_rows=v, **keys):
             enc = eng.encode_full(feats, lens, -1).clone()
             out[v] = (enc, eng.ctc_probs(enc).clone())
-    finally:
-        eng.lib.masr_debug_set(eng.h, 40, 1)
     torch.cuda.synchronize()
     return out
 
@@ -103,10 +101,6 @@ def test_squeezeformer_skipped_padding():
         feats, n = _feats(nseq, T, lens, 11)
         valid = eng.enc_frames(np.array(lens))
         _assert_same(_both(eng, feats, n), valid)
-        assert eng.lib.masr_debug_set(eng.h, 38, 0) == 0
-        try:
-            _assert_same(_both(eng, feats, n))
-        finally:
-            eng.lib.masr_debug_set(eng.h, 38, 7)
+        _assert_same(_both(eng, feats, n, skip_padding=0))
     finally:
         eng.close()

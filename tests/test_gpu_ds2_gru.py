@@ -79,27 +79,24 @@ def test_gru_against_reference_fixture(gru_engines):
 # units = 16: the matrix-core form on three full 16-column tiles (masr_debug_set key 43) instead of the default 8 units.
 @pytest.mark.parametrize('B,units', [(1, 8), (3, 8), (8, 8), (20, 8), (40, 8), (8, 16), (20, 16)])
 def test_gru_step_forms_ragged_against_torch_gru(gru_engines, B, units):
-    from masr_amd._lib import check
+    from masr_amd._lib import debug_keys
     e_bi, e_uni, sd_bi, sd_uni = gru_engines
     torch.manual_seed(100 + B)
     T = 131
     lens = torch.randint(40, T + 1, (B,))
     lens[B // 2] = T
     x = (torch.randn(B, T, 80) * 3 + 13) * (torch.arange(T)[None, :, None] < lens[:, None, None])
-    try:
-        for e, sd in ((e_bi, sd_bi), (e_uni, sd_uni)):
-            check(e.lib.masr_debug_set(e.h, 43, units))
+    for e, sd in ((e_bi, sd_bi), (e_uni, sd_uni)):
+        with debug_keys(e, rnn_mfma_units=units):
             probs = e.ctc_probs(e.encode_full(dev(x), dev(lens, torch.int32))).cpu()
-            ref, xl = cpu_probs(sd, x, lens)
-            n = ref.shape[1]                                       # pad_packed_sequence trims to the longest sequence
-            assert probs.shape[0] == B and probs.shape[1] >= n
-            err = (probs[:, :n] - ref).abs().max().item()
-            assert err < 1e-3, (B, units, err)
-            for b in range(B):
-                k = int(xl[b])
-                assert (probs[b, :k].argmax(-1) == ref[b, :k].argmax(-1)).float().mean().item() > 0.995
-    finally:
-        check(e_bi.lib.masr_debug_set(e_bi.h, 43, 8))
+        ref, xl = cpu_probs(sd, x, lens)
+        n = ref.shape[1]                                       # pad_packed_sequence trims to the longest sequence
+        assert probs.shape[0] == B and probs.shape[1] >= n
+        err = (probs[:, :n] - ref).abs().max().item()
+        assert err < 1e-3, (B, units, err)
+        for b in range(B):
+            k = int(xl[b])
+            assert (probs[b, :k].argmax(-1) == ref[b, :k].argmax(-1)).float().mean().item() > 0.995
 
 
 def test_gru_stream_chunks_against_reference_fixture(gru_engines):

@@ -107,15 +107,12 @@ def test_step_forms_ragged_against_torch(engines, H, gru, B):
 @pytest.mark.parametrize('B', [8, 20])
 @pytest.mark.parametrize('gru', [False, True], ids=['lstm', 'gru'])
 def test_units_per_workgroup_give_the_same_bits(engines, gru, B):
-    from masr_amd._lib import check
+    from masr_amd._lib import debug_keys
     x, lens = ragged(B)
     for streaming in (False, True):
         e, sd = engines(512, gru, streaming)
-        try:
-            check(e.lib.masr_debug_set(e.h, 43, -8))
+        with debug_keys(e, rnn_mfma_units=-8):
             eight = e.encode_full(dev(x), dev(lens, torch.int32)).clone()
-        finally:
-            check(e.lib.masr_debug_set(e.h, 43, 8))
         four = e.encode_full(dev(x), dev(lens, torch.int32))
         assert torch.equal(four, eight)
         ref, _ = cpu_probs(sd, x, lens)

@@ -20,13 +20,9 @@ def _engine(streaming=True):
     return HipEngine(sd, vocab_size=V, streaming=streaming), sd
 
 
-def _set(eng, conf):
-    for k, v in conf.items():
-        eng.lib.masr_debug_set(eng.h, k, v)
-
-
-OLD = {27: 0, 28: 0, 29: 0, 30: 0}
-NEW = {27: 160, 28: 48, 29: 1, 30: 0}
+OLD = {'ctc_fused_blocks': 0, 'attention_fewq_wgs': 0, 'few_rows_path': 0}
+NEW = {}                        # the defaults
+HEAD = {'split_head': 1}        # an experimental kernel: the product build refuses the key
 
 
 @pytest.mark.parametrize('streaming', [True, False])
@@ -34,6 +30,8 @@ NEW = {27: 160, 28: 48, 29: 1, 30: 0}
 def test_few_row_block_path_against_oracle_and_previous_kernels(streaming, B, T):
     """B x T feature frames, ragged, frames per utterance NOT a multiple of 4 (the depthwise prologue's clamped last group):
     streaming-trained (causal conv, unmaterialised history rows) and streaming: False (symmetric conv) builds"""
+    from masr_amd import build
+    from masr_amd._lib import debug_keys
     from oracle import conformer as oc
     eng, sd = _engine(streaming)
     gen = torch.Generator().manual_seed(B * 1000 + T)
@@ -47,19 +45,18 @@ def test_few_row_block_path_against_oracle_and_previous_kernels(streaming, B, T)
     keep = (torch.arange(ref.shape[1])[None, :] < eng.enc_frames(lens)[:, None])[:, :, None]
     out = {}
     try:
-        for name, conf in (('old', OLD), ('new', NEW), ('head', {**NEW, 30: 1})):
-            _set(eng, conf)
-            enc = eng.encode_full(feats.cuda(), lens.to(torch.int32).cuda(), -1)
-            idx, mp = eng.ctc_greedy_frames(enc)
+        for name, conf in (('old', OLD), ('new', NEW)) + ((('head', HEAD),) if build.has_experiments() else ()):
+            with debug_keys(eng, conf):
+                enc = eng.encode_full(feats.cuda(), lens.to(torch.int32).cuda(), -1)
+                idx, mp = eng.ctc_greedy_frames(enc)
             out[name] = (enc.cpu(), idx.cpu(), mp.cpu())
     finally:
-        _set(eng, NEW)
         eng.close()
     for name, (enc, idx, mp) in out.items():
         err = ((enc - ref).abs() * keep).max().item()
         print(f'{name}: B = {B}, T = {T}, streaming = {streaming}: max |enc - oracle| = {err:.3e}')
         assert err < 1e-3, (name, err)
-    for name in ('new', 'head'):
+    for name in set(out) - {'old'}:
         d = ((out[name][0] - out['old'][0]).abs() * keep).max().item()
         assert d < 2e-5, (name, d)
         same = ((out[name][1] == out['old'][1]) | ~keep[:, :, 0])
@@ -71,6 +68,7 @@ def test_few_row_block_path_against_oracle_and_previous_kernels(streaming, B, T)
 def test_chunk_steps_with_the_head_stage_on_the_split_ffn_launch():
     """masr_debug_set key 30 (off by default: measured no faster): the conv module's second half as the head stage of the second
     FFN's d_ff-split launch -- 3 and 40 lock-step streams over six chunks, frame decisions identical, probabilities within 1e-5"""
+    from masr_amd._lib import debug_keys
     eng, _ = _engine(True)
     try:
         for n in (3, 40):
@@ -78,20 +76,19 @@ def test_chunk_steps_with_the_head_stage_on_the_split_ffn_launch():
             feats = (torch.randn(n, 67 + 5 * 64, 80, generator=gen) * 3 + 13).cuda()
             res = {}
             for key30 in (0, 1):
-                eng.lib.masr_debug_set(eng.h, 30, key30)
-                sids = [eng.stream_open(200) for _ in range(n)]
-                outs = []
-                for cur in range(0, feats.shape[1] - 67 + 1, 64):
-                    probs, idx, mp = eng.encode_chunk(sids, feats[:, cur:cur + 67].contiguous(), want_probs=True, want_argmax=True)
-                    outs.append((probs.cpu(), idx.cpu()))
-                for sid in sids:
-                    eng.stream_close(sid)
+                with debug_keys(eng, split_head=key30):
+                    sids = [eng.stream_open(200) for _ in range(n)]
+                    outs = []
+                    for cur in range(0, feats.shape[1] - 67 + 1, 64):
+                        probs, idx, mp = eng.encode_chunk(sids, feats[:, cur:cur + 67].contiguous(), want_probs=True, want_argmax=True)
+                        outs.append((probs.cpu(), idx.cpu()))
+                    for sid in sids:
+                        eng.stream_close(sid)
                 res[key30] = outs
             for (p0, i0), (p1, i1) in zip(res[0], res[1]):
                 assert torch.equal(i0, i1)
                 assert (p0 - p1).abs().max().item() < 1e-5
     finally:
-        eng.lib.masr_debug_set(eng.h, 30, 0)
         eng.close()
 
 

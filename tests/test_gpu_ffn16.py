@@ -5,7 +5,7 @@ head (offline Conformer, streaming True and False), the Efficient Conformer (pla
 block is partial and whose sequences start inside blocks, and M on both sides of the cut-overs of ffn() in engine.hip.
 
 Full launches (nsplit = 1) need >= 129 32-row blocks: below that ffn() splits d_ff (nsplit = min(d_ff / 128, 256 / blocks) > 1).
-The conv-module head rides on the FFN launch from g_ffn_split_blocks = 192 blocks (masr_debug_set key 13) on."""
+The conv-module head rides on the FFN launch from ffn_split_blocks = 192 blocks (masr_debug_set key 13) on."""
 import numpy as np
 import pytest
 import torch
@@ -13,15 +13,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _both(eng, feats, lens):
+def _both(eng, feats, lens, **keys):
+    from masr_amd._lib import debug_keys
     out = {}
-    try:
-        for v in (1, 0, 1):
-            assert eng.lib.masr_debug_set(eng.h, 39, v) == 0
+    for v in (1, 0, 1):
+        with debug_keys(eng, ffn16=v, **keys):
             enc = eng.encode_full(feats, lens, -1).clone()
             out[v] = (enc, eng.ctc_probs(enc).clone())
-    finally:
-        eng.lib.masr_debug_set(eng.h, 39, 1)
     torch.cuda.synchronize()
     return out
 
@@ -75,11 +73,7 @@ def test_ragged_batch_with_partial_blocks(streaming):
     eng = HipEngine(sd, vocab_size=512, streaming=streaming)
     try:
         feats, lens = _feats(9, 1003, [1003, 990, 700, 1003, 512, 333, 1003, 801, 67], 21)
-        assert eng.lib.masr_debug_set(eng.h, 13, 0) == 0
-        try:
-            out = _both(eng, feats, lens)
-        finally:
-            eng.lib.masr_debug_set(eng.h, 13, 192)
+        out = _both(eng, feats, lens, ffn_split_blocks=0)
         assert out[1][0].shape == (9, 250, 256)
         _assert_same(out)
     finally:

@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize('kind,streaming', [('conformer', True), ('conformer', False), ('squeezeformer', False),
                                             ('efficient_conformer', True)])
 def test_packed_weights_are_bit_identical_to_the_slab_pipeline(kind, streaming):
+    from masr_amd._lib import debug_keys
     from masr_amd.engine import HipEngine
     from masr_amd.utils import synthetic
     V = 512
@@ -26,14 +27,11 @@ def test_packed_weights_are_bit_identical_to_the_slab_pipeline(kind, streaming):
         pcm[i, l:] = 0
     feats, frames = eng.fbank_batch(torch.from_numpy(pcm).cuda(), torch.from_numpy(lens).cuda())
     out = {}
-    try:
-        for v in (1, 0, 1):
-            eng.lib.masr_debug_set(eng.h, 23, v)
+    for v in (1, 0, 1):
+        with debug_keys(eng, ffn_packed=v):
             out[v] = eng.encode_full(feats, frames, -1).clone()
             probs = eng.ctc_probs(out[v])
             out[('p', v)] = probs.clone()
-    finally:
-        eng.lib.masr_debug_set(eng.h, 23, 2)               # (the default: the d_ff-split launches of few rows read packed copies too)
     torch.cuda.synchronize()
     assert torch.equal(out[0], out[1]) and torch.equal(out[('p', 0)], out[('p', 1)])
     assert float(out[1].abs().max()) > 0
@@ -47,6 +45,7 @@ def test_two_chain_ffn_is_bit_identical_to_the_single_chain_kernel(kind, streami
     """ffn_dual.hip (two independent accumulator chains per wave over chunks of 256 hidden units, three in the QKV tail stage)
     sums every accumulator's k in the same ascending order as ffn_pc.hip: encoder output and probabilities BIT-identical with
     masr_debug_set key 24 on and off; ragged batch with a partial last row block."""
+    from masr_amd._lib import debug_keys
     from masr_amd.engine import HipEngine
     from masr_amd.utils import synthetic
     V = 512
@@ -60,13 +59,10 @@ def test_two_chain_ffn_is_bit_identical_to_the_single_chain_kernel(kind, streami
         pcm[i, l:] = 0
     feats, frames = eng.fbank_batch(torch.from_numpy(pcm).cuda(), torch.from_numpy(lens).cuda())
     out = {}
-    try:
-        for v in (1, 0, 1):
-            eng.lib.masr_debug_set(eng.h, 24, v)
+    for v in (1, 0, 1):
+        with debug_keys(eng, ffn_dual=v):
             out[v] = eng.encode_full(feats, frames, -1).clone()
             out[('p', v)] = eng.ctc_probs(out[v]).clone()
-    finally:
-        eng.lib.masr_debug_set(eng.h, 24, 0)               # (the default: the single-chain kernel)
     torch.cuda.synchronize()
     assert torch.isfinite(out[1]).all() and float(out[1].abs().max()) > 0
     assert torch.equal(out[0], out[1]), float((out[0] - out[1]).abs().max())
@@ -81,6 +77,7 @@ def test_packed_row_block_projections_are_bit_identical_to_the_slab_pipeline(kin
     fused CTC head) reads a packed copy of its weights with buffer loads (masr_debug_set key 25, default on) instead of staging
     them through wave-private LDS slabs: same operands in the same MFMA order, so encoder output, frame argmax and frame
     probability are BIT-identical with the switch on and off -- for every family, ragged batch, partial last row block."""
+    from masr_amd._lib import debug_keys
     from masr_amd.engine import HipEngine
     from masr_amd.utils import synthetic
     V = 600                                    # not a multiple of 256: the packed CTC weights are zero-padded to 768 rows
@@ -94,14 +91,11 @@ def test_packed_row_block_projections_are_bit_identical_to_the_slab_pipeline(kin
         pcm[i, l:] = 0
     feats, frames = eng.fbank_batch(torch.from_numpy(pcm).cuda(), torch.from_numpy(lens).cuda())
     out = {}
-    try:
-        for v in (1, 0, 1):
-            eng.lib.masr_debug_set(eng.h, 25, v)
+    for v in (1, 0, 1):
+        with debug_keys(eng, rowgemm_packed=v):
             enc = eng.encode_full(feats, frames, -1).clone()
             idx, mp = eng.ctc_greedy_frames(enc)
             out[v] = (enc, idx.clone(), mp.clone())
-    finally:
-        eng.lib.masr_debug_set(eng.h, 25, 1)
     torch.cuda.synchronize()
     assert torch.isfinite(out[1][0]).all() and float(out[1][0].abs().max()) > 0
     for a, b in zip(out[0], out[1]):
@@ -164,6 +158,7 @@ def test_attention_chain_kernel_is_bit_identical_to_the_two_launches(streaming, 
     x all four heads per workgroup, the context rows stay in LDS) performs the operations of attention_kernel<1> and of the
     EPI_CHAIN rowgemm in the same order: encoder output and probabilities BIT-identical with masr_debug_set key 34 on and off --
     ragged batch (pad masks, a partial last query block per sequence), causal and symmetric conv builds, chunk-masked attention."""
+    from masr_amd._lib import debug_keys
     from masr_amd.engine import HipEngine
     from masr_amd.utils import synthetic
     V = 512
@@ -177,13 +172,10 @@ def test_attention_chain_kernel_is_bit_identical_to_the_two_launches(streaming, 
         pcm[i, l:] = 0
     feats, frames = eng.fbank_batch(torch.from_numpy(pcm).cuda(), torch.from_numpy(lens).cuda())
     out = {}
-    try:
-        for v in (1, 0, 1):
-            eng.lib.masr_debug_set(eng.h, 34, v)
+    for v in (1, 0, 1):
+        with debug_keys(eng, attn_chain=v):
             out[v] = eng.encode_full(feats, frames, chunk).clone()
             out[('p', v)] = eng.ctc_probs(out[v]).clone()
-    finally:
-        eng.lib.masr_debug_set(eng.h, 34, 0)               # (the default: measured no faster than the two launches)
     torch.cuda.synchronize()
     assert torch.equal(out[0], out[1]) and torch.equal(out[('p', 0)], out[('p', 1)])
     assert float(out[1].abs().max()) > 0 and bool(torch.isfinite(out[1]).all())

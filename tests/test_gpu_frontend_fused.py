@@ -24,17 +24,13 @@ def _takes_row_blocks(nseq, T):
     return M, t128 > 1024 or (t128 >= 200 and (t128 - (rounds - 1) * 512) * 100 >= 50 * 512)
 
 
-def _all(eng, feats, lens):
+def _all(eng, feats, lens, **keys):
+    from masr_amd._lib import debug_keys
     out = []
-    try:
-        for k41, k42 in SETTINGS:
-            assert eng.lib.masr_debug_set(eng.h, 41, k41) == 0
-            assert eng.lib.masr_debug_set(eng.h, 42, k42) == 0
+    for k41, k42 in SETTINGS:
+        with debug_keys(eng, conv1_fused=k41, embed_rows=k42, **keys):
             enc = eng.encode_full(feats, lens, -1).clone()
             out.append((enc, eng.ctc_probs(enc).clone()))
-    finally:
-        eng.lib.masr_debug_set(eng.h, 41, 1)
-        eng.lib.masr_debug_set(eng.h, 42, 1)
     torch.cuda.synchronize()
     return out
 
@@ -110,10 +106,6 @@ def test_squeezeformer_skipped_padding():
         feats, n = _feats(nseq, T, lens, 12)
         valid = eng.enc_frames(np.array(lens))
         _assert_same(_all(eng, feats, n), valid)
-        assert eng.lib.masr_debug_set(eng.h, 38, 0) == 0
-        try:
-            _assert_same(_all(eng, feats, n))
-        finally:
-            eng.lib.masr_debug_set(eng.h, 38, 7)
+        _assert_same(_all(eng, feats, n, skip_padding=0))
     finally:
         eng.close()

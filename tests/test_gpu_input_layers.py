@@ -214,6 +214,7 @@ def test_chunks_over_facade_windows_against_restatement(il):
 def test_batch_32x10s_against_restatement(il):
     """B = 32 x 10 s (998 frames): M = 5 280 / 3 936 encoder rows; the row-block front-end (conv1 fused into conv2's gather
     under conv2d8, masr_debug_set key 41 -- bit-identical on and off) against the restatement"""
+    from masr_amd._lib import debug_keys
     eng, sd = _engine(il, False, num_blocks=1)
     try:
         B, T = 32, 998
@@ -221,11 +222,8 @@ def test_batch_32x10s_against_restatement(il):
         lens = torch.full((B,), T, dtype=torch.int32)
         enc = eng.encode_full(feats.cuda(), lens.cuda(), -1).clone()
         assert enc.shape[0] * enc.shape[1] == {'conv2d6': 5280, 'conv2d8': 3936}[il]
-        try:
-            assert eng.lib.masr_debug_set(eng.h, 41, 0) == 0
+        with debug_keys(eng, conv1_fused=0):
             enc0 = eng.encode_full(feats.cuda(), lens.cuda(), -1).clone()
-        finally:
-            eng.lib.masr_debug_set(eng.h, 41, 1)
         assert torch.equal(enc, enc0)
         with torch.no_grad():
             ref = encoder_full_il(sd, feats, lens.long(), il, False)

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from masr_amd._lib import debug_keys
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(__file__), 'golden')
@@ -62,17 +64,9 @@ def valid_frames(a, lens, rate=4):
     return a
 
 
-class computing_padded_frames:
+def computing_padded_frames(e, **keys):
     """with computing_padded_frames(engine): the padded frames are computed like the reference computes them (key 38 = 0)"""
-    def __init__(self, e):
-        self.e = e
-
-    def __enter__(self):
-        assert self.e.lib.masr_debug_set(self.e.h, 38, 0) == 0
-
-    def __exit__(self, *exc):
-        self.e.lib.masr_debug_set(self.e.h, 38, 7)
-
+    return debug_keys(e, skip_padding=0, **keys)
 
 
 def acceptable_texts(probs, vocab, od, margin=2e-3, limit=12):
@@ -510,11 +504,8 @@ def test_squeezeformer_against_reference_fixture(sq512, oracle_mods):
         v = min(got.shape[1], -(-int(lens[b]) // 4))
         err = np.abs(got[b, :v] - z['enc'][b, :v]).max()
         assert err < 1e-3, f'squeezeformer encoder_out max err {err} on the valid frames of utterance {b}'
-    assert e.lib.masr_debug_set(e.h, 38, 0) == 0
-    try:
+    with computing_padded_frames(e):
         full = e.encode_full(dev(feats), dev(lens, torch.int32), -1)
-    finally:
-        e.lib.masr_debug_set(e.h, 38, 7)
     err = np.abs(full.cpu().numpy() - z['enc']).max()
     assert err < 1e-3, f'squeezeformer encoder_out max err {err}'
     for b in range(got.shape[0]):       # skipping changes nothing on a valid frame: identical bits
@@ -645,9 +636,8 @@ def test_squeezeformer_fused_layer_is_bit_identical_to_the_separate_launches(ora
         skipping = e.encode_full(xd, ld).cpu()                      # default: row blocks of padded frames are not computed
         with computing_padded_frames(e):
             fused = e.encode_full(xd, ld).cpu()
-            assert e.lib.masr_debug_set(e.h, 36, 0) == 0
+        with computing_padded_frames(e, sqz_fused_blocks=0):
             plain = e.encode_full(xd, ld).cpu()
-            assert e.lib.masr_debug_set(e.h, 36, 128) == 0
         assert torch.isfinite(fused).all() and torch.isfinite(skipping).all()
         assert torch.equal(fused, plain), f'max |fused - separate| = {(fused - plain).abs().max().item():.3e}'
         # skipping the padded row blocks changes no bit of a valid frame, and the padded frames of the output read zero
@@ -1059,11 +1049,8 @@ def test_ffn_tail_stage_matches_separate_launches(eng512):
     feats = feats * (torch.arange(1003)[None, :, None] < lens[:, None, None])
     x, n = dev(feats), dev(lens)
     fused = e.encode_full(x, n, -1).clone()
-    e.lib.masr_debug_set(e.h, 8, 1)
-    try:
+    with debug_keys(e, no_ffn_tail=1):
         plain = e.encode_full(x, n, -1).clone()
-    finally:
-        e.lib.masr_debug_set(e.h, 8, 0)
     assert fused.shape == (9, 250, 256)
     assert torch.equal(fused, plain)
     assert torch.isfinite(fused).all()
@@ -1086,11 +1073,8 @@ def test_ffn_head_stage_matches_separate_launches(oracle_mods, streaming):
         feats = feats * (torch.arange(1003)[None, :, None] < lens[:, None, None])
         x, n = dev(feats), dev(lens)
         fused = e.encode_full(x, n, -1).clone()
-        e.lib.masr_debug_set(e.h, 9, 1)
-        try:
+        with debug_keys(e, no_ffn_head=1):
             plain = e.encode_full(x, n, -1).clone()
-        finally:
-            e.lib.masr_debug_set(e.h, 9, 0)
         assert fused.shape == (9, 250, 256) and torch.isfinite(fused).all()
         assert torch.equal(fused, plain), (fused - plain).abs().max().item()
         oc = oracle_mods[0]
@@ -1117,11 +1101,8 @@ def test_attention_folded_positional_keys_match_two_term_scores(oracle_mods, chu
         feats = feats * (torch.arange(1003)[None, :, None] < lens[:, None, None])
         x, n = dev(feats), dev(lens)
         folded = e.encode_full(x, n, chunk).clone()
-        e.lib.masr_debug_set(e.h, 14, 0)
-        try:
+        with debug_keys(e, attention_fold=0):
             two_term = e.encode_full(x, n, chunk).clone()
-        finally:
-            e.lib.masr_debug_set(e.h, 14, 1)
         diff = (folded - two_term).abs().max().item()
         print(f'attention fold vs two-term (chunk {chunk}): max |enc| diff {diff:.2e}')
         assert torch.isfinite(folded).all() and diff < 5e-5

@@ -8,6 +8,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from masr_amd._lib import debug_keys  # noqa: E402
 from masr_amd.engine import HipEngine  # noqa: E402
 from masr_amd.utils import synthetic  # noqa: E402
 
@@ -36,22 +37,17 @@ if len(sys.argv) > 1 and sys.argv[1] == 'trace':
     print(f'{gpu_ms(30):.3f} ms')
     sys.exit(0)
 feats, frames = e.fbank_batch(xs, ns, gain_in=gain)
-OLD = {27: 0, 28: 0, 29: 0}
-NEW = {27: 160, 28: 48, 29: 1}
+OLD = {'ctc_fused_blocks': 0, 'attention_fewq_wgs': 0, 'few_rows_path': 0}
 for rep in range(2):
     out = []
-    for name, conf in (('round 3 kernels', OLD), ('+ tiled CTC head', {**OLD, 27: 160}), ('+ key-split attention', {**OLD, 27: 160, 28: 48}),
-                       ('+ latency-cut layer (default)', NEW)):
-        for k, v in conf.items():
-            e.lib.masr_debug_set(e.h, k, v)
-        out.append(f'{name}: {gpu_ms():.3f} ms')
+    for name, back in (('round 3 kernels', ()), ('+ tiled CTC head', ('ctc_fused_blocks',)),
+                       ('+ key-split attention', ('ctc_fused_blocks', 'attention_fewq_wgs')), ('+ latency-cut layer (default)', tuple(OLD))):
+        with debug_keys(e, {k: v for k, v in OLD.items() if k not in back}):      # (the keys in `back` at their defaults)
+            out.append(f'{name}: {gpu_ms():.3f} ms')
     print('   '.join(out))
-for k, v in OLD.items():
-    e.lib.masr_debug_set(e.h, k, v)
-enc_old = e.encode_full(feats, frames, -1).clone()
-rows_old = e.transcribe_rows(xs, ns, True, -20.0, gain_in=gain).clone()
-for k, v in NEW.items():
-    e.lib.masr_debug_set(e.h, k, v)
+with debug_keys(e, OLD):
+    enc_old = e.encode_full(feats, frames, -1).clone()
+    rows_old = e.transcribe_rows(xs, ns, True, -20.0, gain_in=gain).clone()
 enc_new = e.encode_full(feats, frames, -1).clone()
 rows_new = e.transcribe_rows(xs, ns, True, -20.0, gain_in=gain).clone()
 tp = rows_old.shape[1] - 2

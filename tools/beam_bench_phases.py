@@ -11,11 +11,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import bench  # noqa: E402
 from masr_amd import runtime  # noqa: E402
+from masr_amd._lib import debug_keys  # noqa: E402
 
 sharp = len(sys.argv) > 1 and sys.argv[1] == '1'
 eng = runtime.aux_engine()
-eng.lib.masr_debug_set(eng.h, 2, 1)
-r = bench.extra_squeezeformer_beam(types.SimpleNamespace(steps=2, warmup=1), 0, 1, 0, sharp=sharp)
-torch.cuda.synchronize()
-eng.lib.masr_debug_set(eng.h, 2, 0)          # prints the counters
+with debug_keys(eng, beam_profile=1):
+    r = bench.extra_squeezeformer_beam(types.SimpleNamespace(steps=2, warmup=1), 0, 1, 0, sharp=sharp)
+    torch.cuda.synchronize()
+with debug_keys(eng, beam_profile=0):          # prints the counters (masr_debug_reset leaves key 2 alone)
+    pass
 print(f"{'sharpened head' if sharp else 'flat posteriors'}: {r['ms_per_step']} ms per call")

@@ -13,6 +13,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from masr_amd import runtime
+from masr_amd._lib import debug_keys
 from masr_amd.decoders.beam_search_decoder import BeamSearchDecoder
 from masr_amd.decoders.lm_scorer import write_synthetic_arpa
 
@@ -34,22 +35,22 @@ dec = BeamSearchDecoder(2.2 if order else 0, 4.3 if order else 0, beam, 0.99, 40
 dec.prune_min_cutoff = bool(prune)
 eng = runtime.aux_engine()
 cache = int(sys.argv[6]) if len(sys.argv) > 6 else 1
-eng.lib.masr_debug_set(eng.h, 32, cache)
-eng.lib.masr_debug_set(eng.h, 37, int(os.environ.get('BEAM_PROFILE_NARROW', '1')))      # 0: every frame on the wide step; 3: narrow step on, the wide step's pass skipping off
-cand = dec._candidates(probs[0], to_host=False)[2].float().mean().item()
-print(f'logit scale {scale}: {cand:.1f} candidates per frame')
-ref = dec._batch([probs[i] for i in range(NB)])
+narrow = int(os.environ.get('BEAM_PROFILE_NARROW', '1'))      # 0: every frame on the wide step; 3: narrow step on, the wide step's pass skipping off
+with debug_keys(eng, beam_lm_cache=cache, beam_narrow=narrow):
+    cand = dec._candidates(probs[0], to_host=False)[2].float().mean().item()
+    print(f'logit scale {scale}: {cand:.1f} candidates per frame')
+    ref = dec._batch([probs[i] for i in range(NB)])
 if cache and order:                    # the table must not change a score: same transcripts and scores as per-pair probing
-    eng.lib.masr_debug_set(eng.h, 32, 0)
-    base = dec._batch([probs[i] for i in range(NB)])
-    eng.lib.masr_debug_set(eng.h, 32, 1)
+    with debug_keys(eng, beam_lm_cache=0, beam_narrow=narrow):
+        base = dec._batch([probs[i] for i in range(NB)])
     assert base == ref, 'scorer table changed the search result'
     print('identical transcripts and scores with and without the per-frame scorer table')
 torch.cuda.synchronize()
-eng.lib.masr_debug_set(eng.h, 2, 1)
-t0 = time.perf_counter()
-dec._batch([probs[i] for i in range(NB)])
-torch.cuda.synchronize()
-dt = time.perf_counter() - t0
+with debug_keys(eng, beam_lm_cache=cache, beam_narrow=narrow, beam_profile=1):
+    t0 = time.perf_counter()
+    dec._batch([probs[i] for i in range(NB)])
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
 print(f'batch of {NB} x {T} frames, LM order {order}, scorer table {cache}: {1e3 * dt:.2f} ms  ({1e6 * dt / T:.1f} us per frame step incl. pruning)')
-eng.lib.masr_debug_set(eng.h, 2, 0)
+with debug_keys(eng, beam_profile=0):          # prints the counters (masr_debug_reset leaves key 2 alone)
+    pass

@@ -7,6 +7,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from masr_amd._lib import debug_keys  # noqa: E402
 from masr_amd.engine import HipEngine  # noqa: E402
 from masr_amd.utils import synthetic  # noqa: E402
 
@@ -15,10 +16,10 @@ e = HipEngine(synthetic.conformer_state_dict(0, 4233), vocab_size=4233)
 line = f'{label:8s}'
 # optional A/B inside one process: MASR_AB='30:0,30:1' runs the sizes once per setting of debug key 30
 settings = [tuple(int(v) for v in kv.split(':')) for kv in os.environ.get('MASR_AB', '').split(',') if kv] or [None]
-for ns, ab in [(n, a) for a in settings for n in (16, 128)]:
-    if ab is not None:
-        e.lib.masr_debug_set(e.h, ab[0], ab[1])
-        line += f' | key {ab[0]} = {ab[1]}'
+
+
+
+def measure(ns):
     feats = torch.randn(ns, 998, 80, device='cuda', generator=torch.Generator('cuda').manual_seed(3)) * 3 + 13
     sids = [e.stream_open(300) for _ in range(ns)]
 
@@ -38,7 +39,15 @@ for ns, ab in [(n, a) for a in settings for n in (16, 128)]:
     for _ in range(5):
         l, chk = run()
         lat += l
-    line += f' | {ns} streams: p50 {np.percentile(lat, 50) * 1e3:.3f} ms p95 {np.percentile(lat, 95) * 1e3:.3f} ms (sum of frame ids {chk})'
     for sid in sids:
         e.stream_close(sid)
+    return f' | {ns} streams: p50 {np.percentile(lat, 50) * 1e3:.3f} ms p95 {np.percentile(lat, 95) * 1e3:.3f} ms (sum of frame ids {chk})'
+
+
+for ab in settings:
+    with debug_keys(e, {ab[0]: ab[1]} if ab else {}):
+        if ab:
+            line += f' | key {ab[0]} = {ab[1]}'
+        for ns in (16, 128):
+            line += measure(ns)
 print(line)

@@ -21,7 +21,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from masr_amd._lib import check            # noqa: E402
+from masr_amd._lib import debug_keys       # noqa: E402
 from masr_amd.engine import HipEngine      # noqa: E402
 from masr_amd.utils import synthetic       # noqa: E402
 
@@ -84,12 +84,11 @@ def main():
         order = names[r % len(names):] + names[:r % len(names)]
         for name in order:
             eng = engines['gru' if name.startswith('gru') else 'lstm']
-            check(eng.lib.masr_debug_set(eng.h, 43, 16 if name == 'gru_u16' else 8))
-            if 'b1' in workloads:
-                res[('b1', name)].append(time_b1(eng, xs, ns))
-            if 'b32' in workloads:
-                res[('b32', name)].append(time_b32(eng, pcm, n))
-    check(eng.lib.masr_debug_set(eng.h, 43, 8))
+            with debug_keys(eng, {'rnn_mfma_units': 16} if name == 'gru_u16' else {}):
+                if 'b1' in workloads:
+                    res[('b1', name)].append(time_b1(eng, xs, ns))
+                if 'b32' in workloads:
+                    res[('b32', name)].append(time_b32(eng, pcm, n))
     lines = []
     for (w, name), ms in res.items():
         med = float(np.median(ms))

@@ -37,10 +37,10 @@ BATCHES = (1, 16, 32)
 
 def imports(root):
     sys.path.insert(0, root)
-    from masr_amd._lib import check
+    from masr_amd import _lib
     from masr_amd.engine import HipEngine
     from masr_amd.utils import synthetic
-    return check, HipEngine, synthetic
+    return _lib, HipEngine, synthetic
 
 
 def make(HipEngine, synthetic, H, gru, streaming, layers=1, V=50):
@@ -94,7 +94,7 @@ def point(kind, H, gru, streaming, B, vals, unit, **extra):
 
 
 def run_step(mods, sizes, rounds, calls, emit):
-    check, HipEngine, synthetic = mods
+    _lib, HipEngine, synthetic = mods
     for H in sizes:
         for gru in (False, True):
             for streaming in (True, False):
@@ -110,7 +110,7 @@ def run_step(mods, sizes, rounds, calls, emit):
 
 
 def run_units(mods, sizes, rounds, calls, emit):
-    check, HipEngine, synthetic = mods
+    _lib, HipEngine, synthetic = mods
     for H in [h for h in sizes if h <= 512]:
         for gru in (False, True):
             for streaming in (True, False):
@@ -120,10 +120,9 @@ def run_units(mods, sizes, rounds, calls, emit):
                     vals, outs = {4: [], 8: []}, {}
                     for r in range(rounds):
                         for u in ((4, 8) if r % 2 == 0 else (8, 4)):
-                            check(eng.lib.masr_debug_set(eng.h, 43, -8 if u == 8 else 8))
-                            vals[u].append(step_us(eng, x, lens, calls))
-                            outs[u] = eng.encode_full(x, lens).clone()
-                    check(eng.lib.masr_debug_set(eng.h, 43, 8))
+                            with _lib.debug_keys(eng, {'rnn_mfma_units': -8} if u == 8 else {}):
+                                vals[u].append(step_us(eng, x, lens, calls))
+                                outs[u] = eng.encode_full(x, lens).clone()
                     for u in (8, 4):
                         emit(point('units', H, gru, streaming, B, vals[u], 'us/step', units=u,
                                    workgroups=H // u * (1 if streaming else 2), equal_bits=bool(torch.equal(outs[4], outs[8]))))
@@ -131,7 +130,7 @@ def run_units(mods, sizes, rounds, calls, emit):
 
 
 def run_e2e(mods, sizes, rounds, emit):
-    check, HipEngine, synthetic = mods
+    _lib, HipEngine, synthetic = mods
     wav = np.load(os.path.join(ROOT, 'tests', 'golden', 'testwav.npz'))['pcm']
     for H in sizes:
         for gru in (False, True):
@@ -158,7 +157,7 @@ def run_e2e(mods, sizes, rounds, emit):
 
 def run_encode(mods, calls, emit, tag):
     """one pass over the 1024 shapes; the parent process alternates trees and gathers the rounds"""
-    check, HipEngine, synthetic = mods
+    _lib, HipEngine, synthetic = mods
     for gru in (False, True):
         for streaming in (True, False):
             eng = make(HipEngine, synthetic, 1024, gru, streaming)

@@ -10,6 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import bench  # noqa: E402
+from masr_amd._lib import debug_keys  # noqa: E402
 from masr_amd.utils import synthetic  # noqa: E402
 
 rng = np.random.default_rng(1234)
@@ -21,18 +22,18 @@ eng = pred.predictor.engine
 ref = None
 ONLY = os.environ.get('SQZ_AB_ONLY')          # e.g. '1:64' -> one configuration (for a rocprofv3 trace)
 for skip in ((int(ONLY.split(":")[0]),) if ONLY else (7, 0)):
-    eng.lib.masr_debug_set(eng.h, 38, skip)
-    for mode in ((int(ONLY.split(':')[1]),) if ONLY else ('balanced', 32, 64)):
-        for _ in range(2):
-            res = pred.predict_batch(audio, batch_size=mode)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(10):
-            res = pred.predict_batch(audio, batch_size=mode)
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / 10
-        texts = [r['text'] for r in res]
-        if ref is None:
-            ref = texts
-        same = sum(a == b for a, b in zip(ref, texts))
-        print(f'skip padded blocks {skip}, passes {mode}: {1e3 * dt:.2f} ms per call, {same}/64 transcripts equal to the first run')
+    with debug_keys(eng, skip_padding=skip):
+        for mode in ((int(ONLY.split(':')[1]),) if ONLY else ('balanced', 32, 64)):
+            for _ in range(2):
+                res = pred.predict_batch(audio, batch_size=mode)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(10):
+                res = pred.predict_batch(audio, batch_size=mode)
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) / 10
+            texts = [r['text'] for r in res]
+            if ref is None:
+                ref = texts
+            same = sum(a == b for a, b in zip(ref, texts))
+            print(f'skip padded blocks {skip}, passes {mode}: {1e3 * dt:.2f} ms per call, {same}/64 transcripts equal to the first run')
