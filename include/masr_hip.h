@@ -39,7 +39,8 @@ typedef struct masr_config {
     int32_t max_pos;         /* positional table length (reference max_len = 5000, embedding.py:14)  */
     int32_t device_id;
     int32_t reserved[5];     /* squeezeformer: [0] reduce_idx, [1] recover_idx; efficient_conformer: [0] stride layer, [1] grouped layers,
-                                [2] group size; conformer: [0] = 1 -> cnn_module_norm: batch_norm (convolution.py:60-67; full-context only);
+                                [2] group size, [4] = 1 -> cnn_module_norm: batch_norm (full-context and chunked; [0] is taken by the
+                                stride layer); conformer: [0] = 1 -> cnn_module_norm: batch_norm (convolution.py:60-67; full-context only);
                                 conformer and efficient_conformer: [3] input_layer, 0 = conv2d (x4), 1 = conv2d6 (x6), 2 = conv2d8 (x8)
                                 (conformer/subsampling.py:65-211); deepspeech2 (model_kind 3): [0] recurrent cell, 0 = LSTM,
                                 1 = GRU (encoder_conf.use_gru, deepspeech2/encoder.py:21-33), any other value is refused */

@@ -157,6 +157,9 @@ void launch_dwconv_bn_silu(const float* g, const float* wkc, const float* bias, 
 // [nseq][ktaps-1 + Tin][256] -> [nseq * ceil(Tin/2), 256]; and the AvgPool1d(2, ceil_mode) residual path
 void launch_dwconv_stride2_ln_silu(const float* g, const float* wkc, const float* bias, const float* lnw,
                                    const float* lnb, float* out, int nseq, int Tin, int ktaps, float eps, hipStream_t s);
+// same with an eval-mode BatchNorm folded into a per-channel scale/shift instead of the LayerNorm (cnn_module_norm: batch_norm)
+void launch_dwconv_stride2_bn_silu(const float* g, const float* wkc, const float* bias, const float* scale,
+                                   const float* shift, float* out, int nseq, int Tin, int ktaps, hipStream_t s);
 void launch_avgpool2(const float* x, float* out, int B, int T, hipStream_t s);
 // Squeezeformer TimeReductionLayer1D depthwise part: k=5, stride 2, padding 3, pad-masked input -> [B, ceil(T/2), 256]
 void launch_time_reduce_dw(const float* x, const float* w5c, const float* bias, const int* lens, float* out, int B, int T,
@@ -264,13 +267,14 @@ struct FfnTail {
 };
 // head: the rest of the conv module in front of the block, on the workgroup's own 32 rows, before the block's LayerNorm:
 //   x <- x + mask(pointwise_conv2(SiLU(LayerNorm(depthwise_conv(glu)))))       (convolution.py:120-131, encoder.py:137-148)
+// norm = 1 (cnn_module_norm: batch_norm): the eval-mode BatchNorm1d folded into a per-channel scale / shift instead of the LayerNorm
 // the depthwise conv reads the GLU rows of the padded layout [nseq][pad + seq_t][256] (ktaps - 1 = pad history rows in front,
 // gconst: constant history rows that are not materialised).  Return value bit 2 (4) = done by the kernel.
 struct FfnHead {
     const float* glu;          // nullptr: no head stage
     const float* dw_w;         // [ktaps][256]
     const float* dw_b;
-    const float* lnw;          // the conv module's LayerNorm
+    const float* lnw;          // the conv module's LayerNorm (norm = 1: the folded BatchNorm's scale / shift)
     const float* lnb;
     const float* gconst;       // [256] or nullptr
     const float* W;            // pointwise_conv2 [256, 256]
@@ -280,6 +284,7 @@ struct FfnHead {
     float* xout;               // d_ff-split launches (few rows) only: where the rows updated by the head stage go -- every d_ff
                                // slice of a row block runs the head on the SAME old rows of x, so x itself must stay untouched
                                // until the split reduction, which then reads xout and writes x
+    int norm;                  // 0 = LayerNorm, 1 = folded BatchNorm: y = silu(conv * lnw[c] + lnb[c]), no row statistics
 };
 int launch_ffn_fused(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2,
                      const float* b2, int M, int dff, float eps, float scale, int affine_prologue, float* partial,

@@ -229,6 +229,7 @@ void launch_dwconv_bn_silu(const float* g, const float* wkc, const float* bias, 
     const dim3 grid(nseq * tiles), blk(256);
     if (ktaps == 31) hipLaunchKernelGGL((dwconv_ln_silu_kernel<31, 1>), grid, blk, 0, s, g, wkc, bias, scale, shift, out, Tq, 0.f, gconst);
     else if (ktaps == 15) hipLaunchKernelGGL((dwconv_ln_silu_kernel<15, 1>), grid, blk, 0, s, g, wkc, bias, scale, shift, out, Tq, 0.f, gconst);
+    else if (ktaps == 7) hipLaunchKernelGGL((dwconv_ln_silu_kernel<7, 1>), grid, blk, 0, s, g, wkc, bias, scale, shift, out, Tq, 0.f, gconst);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -291,6 +292,44 @@ void launch_dwconv_stride2_ln_silu(const float* g, const float* wkc, const float
     const int tiles = (Tout + DW_TT - 1) / DW_TT;
     hipLaunchKernelGGL(dwconv_stride2_ln_silu_kernel<15>, dim3(nseq * tiles), dim3(256), 0, s, g, wkc, bias, lnw, lnb, out,
                        Tin, Tout, eps);
+}
+
+// The stride layer with cnn_module_norm: batch_norm: the eval-mode BatchNorm1d is a per-channel scale / shift, so the thread that
+// owns channel c finishes its own elements -- same tap order as above, no LDS tile, no barrier, no row reduction.
+template <int KT>
+__global__ __launch_bounds__(256) void dwconv_stride2_bn_silu_kernel(const float* __restrict__ g,
+                                                                     const float* __restrict__ wkc,
+                                                                     const float* __restrict__ bias,
+                                                                     const float* __restrict__ scale,
+                                                                     const float* __restrict__ shift,
+                                                                     float* __restrict__ out, int Tin, int Tout) {
+    const int tiles = (Tout + DW_TT - 1) / DW_TT;
+    const int seq = blockIdx.x / tiles;
+    const int t0 = (blockIdx.x % tiles) * DW_TT;
+    const int c = threadIdx.x;
+    const float* gin = g + ((size_t)seq * (KT - 1 + Tin)) * 256 + c;
+    float w[KT];
+#pragma unroll
+    for (int j = 0; j < KT; ++j) w[j] = wkc[j * 256 + c];
+    const float bv = bias[c], sc = scale[c], sh = shift[c];
+    const int nrows = min(DW_TT, Tout - t0);
+    for (int r = 0; r < nrows; ++r) {
+        float acc = bv;
+        const float* gp = gin + (size_t)(2 * (t0 + r)) * 256;
+#pragma unroll
+        for (int j = 0; j < KT; ++j) acc = fmaf(w[j], gp[(size_t)j * 256], acc);
+        acc = fmaf(acc, sc, sh);
+        out[((size_t)seq * Tout + t0 + r) * 256 + c] = acc / (1.0f + expf(-acc));
+    }
+}
+
+void launch_dwconv_stride2_bn_silu(const float* g, const float* wkc, const float* bias, const float* scale,
+                                   const float* shift, float* out, int nseq, int Tin, int ktaps, hipStream_t s) {
+    const int Tout = (Tin + 1) / 2;
+    if (nseq * Tout <= 0 || ktaps != 15) return;
+    const int tiles = (Tout + DW_TT - 1) / DW_TT;
+    hipLaunchKernelGGL(dwconv_stride2_bn_silu_kernel<15>, dim3(nseq * tiles), dim3(256), 0, s, g, wkc, bias, scale, shift, out,
+                       Tin, Tout);
 }
 
 __global__ __launch_bounds__(256) void avgpool2_kernel(const float* __restrict__ x, float* __restrict__ out, int T,

@@ -285,7 +285,7 @@ struct masr_engine : EngineWs {
     int reduce_idx = -1, recover_idx = -1;
     int stride_idx = -1, n_group_layers = 0, group_size = 3;   // Efficient-Conformer (model_kind 2)
     int input_layer = IL_CONV2D;     // Conformer / Efficient-Conformer subsampling front-end (cfg.reserved[3], common.h InputLayer)
-    bool conv_bn = false;            // Conformer with cnn_module_norm: batch_norm (cfg.reserved[0] = 1): LayerW::cln_w / cln_b hold the folded scale / shift
+    bool conv_bn = false;            // cnn_module_norm: batch_norm (Conformer: cfg.reserved[0] = 1, Efficient Conformer: cfg.reserved[4] = 1): LayerW::cln_w / cln_b hold the folded scale / shift
     bool ds2_gru = false;            // DeepSpeech2 with use_gru: True (cfg.reserved[0] = 1): nn.GRU recurrent layers (gru.hip)
     // fbank tables
     float *window = nullptr, *melwt = nullptr, *tw512 = nullptr, *twr4 = nullptr;
@@ -669,7 +669,8 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
     e->cfg = *cfg;
     if (e->cfg.max_pos <= 0) e->cfg.max_pos = 5000;
     e->reduce_idx = cfg->model_kind == 1 ? cfg->reserved[0] : -1;
-    e->conv_bn = cfg->model_kind == 0 && cfg->reserved[0] == 1;
+    // (the Efficient Conformer's reserved[0] is its stride layer: its norm selector sits in reserved[4])
+    e->conv_bn = (cfg->model_kind == 0 && cfg->reserved[0] == 1) || (cfg->model_kind == 2 && cfg->reserved[4] == 1);
     e->ds2_gru = cfg->model_kind == 3 && cfg->reserved[0] == 1;
     e->recover_idx = cfg->model_kind == 1 ? cfg->reserved[1] : -1;
     if (cfg->model_kind == 0 || cfg->model_kind == 2) {
@@ -852,10 +853,13 @@ int masr_finalize(masr_engine* e, void* stream) {
             CHK(get(e, p + "conv_module.norm.bias", {d}, &tb));
             CHK(get(e, p + "conv_module.norm.running_mean", {d}, &tm));
             CHK(get(e, p + "conv_module.norm.running_var", {d}, &tv));
+            // (the reference's own float32 steps, so that y = fma(x, scale, shift) is its eval-mode batch_norm bit for bit:
+            //  invstd = 1 / sqrt(var + eps), scale = weight * invstd, shift = fma(-mean, scale, bias))
             std::vector<float> sc(d), sh(d);
             for (int c = 0; c < d; ++c) {
-                sc[c] = tw->v[c] / sqrtf(tv->v[c] + 1e-5f);
-                sh[c] = tb->v[c] - tm->v[c] * sc[c];
+                const float invstd = 1.0f / sqrtf(tv->v[c] + 1e-5f);
+                sc[c] = tw->v[c] * invstd;
+                sh[c] = fmaf(-tm->v[c], sc[c], tb->v[c]);
             }
             CHK(upload(e, sc, &w.cln_w));
             CHK(upload(e, sh, &w.cln_b));
@@ -980,8 +984,12 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
     if (head && head->glu && !want_head) {
         // the rest of the conv module as its own two launches: depthwise conv + LayerNorm + SiLU, pointwise_conv2 + mask + residual
         CHK(e->dwo.ensure((size_t)M * d * sizeof(float)));
-        launch_dwconv_ln_silu(head->glu, head->dw_w, head->dw_b, head->lnw, head->lnb, e->dwo.as<float>(), M / head->seq_t,
-                              head->seq_t, head->ktaps, 1e-5f, s, head->gconst);
+        if (head->norm == 1)
+            launch_dwconv_bn_silu(head->glu, head->dw_w, head->dw_b, head->lnw, head->lnb, e->dwo.as<float>(), M / head->seq_t,
+                                  head->seq_t, head->ktaps, s, head->gconst);
+        else
+            launch_dwconv_ln_silu(head->glu, head->dw_w, head->dw_b, head->lnw, head->lnb, e->dwo.as<float>(), M / head->seq_t,
+                                  head->seq_t, head->ktaps, 1e-5f, s, head->gconst);
         float* x = e->x.as<float>();
         {
             RowGemmArgs g = rg_args(e->dwo.as<float>(), d, head->W, head->bias, x, d, M, d);
@@ -1036,7 +1044,8 @@ int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb
     FfnTail ptail = tail ? *tail : FfnTail{};
     FfnHead phead = head ? *head : FfnHead{};
     // two accumulator chains per wave (ffn_dual.hip): same arithmetic in the same order, its own packing order
-    if (packed && nsplit == 1 && knobs().ffn_dual && dff % 256 == 0 && dff >= 512 && !(want_tail && tail->N != 768) && !(affine && (want_tail || want_head))) {
+    if (packed && nsplit == 1 && knobs().ffn_dual && dff % 256 == 0 && dff >= 512 && !(want_tail && tail->N != 768) && !(affine && (want_tail || want_head)) &&
+        !(want_head && head->norm)) {      // (the two-chain kernel's head stage carries the LayerNorm variant only)
         const float *p1, *p2;
         CHK(packed_ffn_of(e, w1, w2, s, &p1, &p2, PACK_FFN_DUAL, launch_pack_ffn_dual));
         if (want_tail) {
@@ -1301,9 +1310,14 @@ int conv_module_stream(masr_engine* e, hipStream_t s, const LayerW& w, int n, in
         a.W = w.pw2_w; a.bias = w.pw2_b; a.C = x; a.ldc = d; a.R = x; a.ldr = d; a.M = M; a.N = d; a.alpha = 1.f;
         a.eps = 1e-5f; a.mstride = 4; a.seq_t = Tq; a.pad = pad;
         ProfScope ps(e, s, PROF_GEMM, 2.0 * M * (double)d * d);
-        if (!launch_rowgemm(a, RG_PRO_DWCONV, RG_EPI_RESID, s)) {
-            launch_dwconv_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K, 1e-5f, s,
-                                  nullptr);
+        // (BatchNorm build: the small-M kernel's depthwise prologue carries the LayerNorm variant only -- the depthwise kernel's BN
+        //  variant, then pointwise_conv2 on the small-M kernel)
+        if (e->conv_bn || !launch_rowgemm(a, RG_PRO_DWCONV, RG_EPI_RESID, s)) {
+            if (e->conv_bn)
+                launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K, s, nullptr);
+            else
+                launch_dwconv_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K, 1e-5f, s,
+                                      nullptr);
             a.A = e->dwo.as<float>();
             launch_rowgemm(a, RG_PRO_PLAIN, RG_EPI_RESID, s);
         }
@@ -1744,7 +1758,7 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
             // like the offline Conformer layer: [out-proj + residual -> LN -> pw1 -> GLU] was one kernel; the rest of the conv
             // module is the head stage of the second FFN launch (15 taps before, 7 behind the stride layer)
             const FfnHead head{e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, causal ? w.gconst : nullptr,
-                               w.pw2_w, w.pw2_b, lens, Tq, Ki, mstride, nullptr};
+                               w.pw2_w, w.pw2_b, lens, Tq, Ki, mstride, nullptr, e->conv_bn ? 1 : 0};
             CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2, 0.5f, 0, nullptr, nullptr, nullptr, nullptr,
                     nullptr, &head));
             launch_layernorm(x, w.ln_fin_w, w.ln_fin_b, x, M, 1e-5f, 0, 0, nullptr, s);
@@ -1766,8 +1780,11 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
                     g.out_seq_t = Tq; g.out_pad_l = pad / 2; g.out_pad_tot = pad;
                     rowgemm(e, s, RG_PRO_LN_PAD, RG_EPI_GLU, g);
                 }
-            launch_dwconv_stride2_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), B, Tq, K,
-                                          1e-5f, s);
+            if (e->conv_bn)
+                launch_dwconv_stride2_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), B, Tq, K, s);
+            else
+                launch_dwconv_stride2_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), B, Tq, K,
+                                              1e-5f, s);
             launch_avgpool2(x, e->xsave.as<float>(), B, Tq, s);
             Tq = T2; mstride *= 2; pstride *= 2; M = B * Tq;
             if (!causal)     // half rate, kernel 7 from here on: a new padded layout
@@ -1994,7 +2011,7 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
                 &qkv_done));
         if (!qkv_done) mhsa(e, s, w, M);
         // attention and the chain kernel behind it as ONE launch (32 queries x all four heads per workgroup; key 34 = 0: two launches)
-        const bool fuse_ac = knobs().attn_chain && !few_rows && !knobs().no_chain && !e->conv_bn && H == 4 && d == 256 && knobs().rowgemm_packed;
+        const bool fuse_ac = knobs().attn_chain && !few_rows && !knobs().no_chain && H == 4 && d == 256 && knobs().rowgemm_packed;
         if (fuse_ac) {
             AttnChainArgs a{};
             a.seqs = e->attseq.as<AttSeq>(); a.nseq = B; a.q_stride = 3 * d; a.kv_stride = 3 * d;
@@ -2017,23 +2034,23 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
             // 7.4 + 7.7 us for the two K-split launches whose columns spread over the chip); norm_final rides on the split
             // FFN's reduction
             mhsa_out(e, s, w, M);
-            const bool fuse = knobs().split_head && e->cfg.cnn_kernel == 15 && knobs().ffn_packed >= 2 && !knobs().no_ffn_head && !e->conv_bn;
+            const bool fuse = knobs().split_head && e->cfg.cnn_kernel == 15 && knobs().ffn_packed >= 2 && !knobs().no_ffn_head;
             CHK(conv_module(e, s, w, ctx, false, 0, 4, false, fuse));
             const FfnHead head{e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->cfg.causal ? w.gconst : nullptr,
-                               w.pw2_w, w.pw2_b, feat_lens_dev, Tq, e->cfg.cnn_kernel, 4, nullptr};
+                               w.pw2_w, w.pw2_b, feat_lens_dev, Tq, e->cfg.cnn_kernel, 4, nullptr, e->conv_bn ? 1 : 0};
             CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2, 0.5f, 0, w.ln_fin_w, w.ln_fin_b, x, nullptr,
                     nullptr, fuse ? &head : nullptr));
             continue;                              // (prev stays null: nothing deferred)
-        } else if (knobs().no_chain || e->conv_bn) {      // (BatchNorm build: the fused head stage carries the LayerNorm variant only)
+        } else if (knobs().no_chain) {
             mhsa_out(e, s, w, M);
             CHK(conv_module(e, s, w, ctx, false));
             CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2));
         } else {
             // out-projection + residual + LayerNorm + pointwise_conv1 + GLU in one kernel; the rest of the conv module
-            // (depthwise conv, LayerNorm, SiLU, pointwise_conv2, residual) is the head stage of the second FFN kernel
+            // (depthwise conv, LayerNorm or folded BatchNorm, SiLU, pointwise_conv2, residual) is the head stage of the second FFN kernel
             if (!fuse_ac) mhsa_out_pw1(e, s, w, ctx);
             const FfnHead head{e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->cfg.causal ? w.gconst : nullptr,
-                               w.pw2_w, w.pw2_b, feat_lens_dev, Tq, e->cfg.cnn_kernel, 4, nullptr};
+                               w.pw2_w, w.pw2_b, feat_lens_dev, Tq, e->cfg.cnn_kernel, 4, nullptr, e->conv_bn ? 1 : 0};
             CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2, 0.5f, 0, nullptr, nullptr, nullptr, nullptr,
                     nullptr, &head));
         }
@@ -2554,7 +2571,7 @@ int masr_stream_open(masr_engine* e, int32_t max_frames_out, int32_t* stream_id)
     } else if (!e->cfg.causal) {
         return fail("chunked streaming needs the streaming-trained (causal conv) build");
     }
-    if (e->conv_bn) return fail("cnn_module_norm=batch_norm: only the full-context forward is implemented (the chunk-step kernels carry the LayerNorm variant)");
+    if (e->conv_bn && e->cfg.model_kind == 0) return fail("cnn_module_norm=batch_norm: only the full-context forward is implemented (the chunk-step kernels carry the LayerNorm variant)");
     if (max_frames_out <= 0 || max_frames_out > e->cfg.max_pos) max_frames_out = e->cfg.max_pos;
     int id = -1;
     for (size_t i = 0; i < e->streams.size(); ++i)
@@ -2957,8 +2974,11 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
             rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_GLU,
                     rg_args(e->lnpad.as<float>(), d, w.pw1_w, w.pw1_b, e->glu.as<float>(), d, n * (Tq + pad), 2 * d));
             launch_cnn_cache_move(cptr + (size_t)L * n, e->lnpad.as<float>(), n, Tq, pad, 1, s);
-            launch_dwconv_stride2_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K,
-                                          1e-5f, s);
+            if (e->conv_bn)
+                launch_dwconv_stride2_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K, s);
+            else
+                launch_dwconv_stride2_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K,
+                                              1e-5f, s);
             launch_avgpool2(x, e->xsave.as<float>(), n, Tq, s);
             M = n * T2;
             {

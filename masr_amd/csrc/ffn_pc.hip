@@ -55,7 +55,11 @@ __device__ __forceinline__ float pc_wsum(float v) {
 // pointwise_conv2 + residual run first, on the same 32 rows (FfnHead, common.h): the depthwise conv reads its HEADK - 1 earlier
 // GLU rows from the padded buffer the previous kernel wrote, everything behind it is row-local.  Replaces two launches
 // (dwconv_ln_silu_kernel, rowgemm PRO_PLAIN / EPI_RESID) with the same arithmetic in the same order (bit-identical).
-template <int AFFINE, int SPLIT, int VAR, int TAIL, int HEADK>
+// NORM = 1 (FfnHead::norm, cnn_module_norm: batch_norm): the conv module's norm is an eval-mode BatchNorm1d folded into a per-channel
+// scale / shift (head.lnw / head.lnb).  It needs no row statistics, so the thread that owns channel c applies it and the SiLU to its
+// own conv sums in head 1 (the arithmetic of dwconv_ln_silu_kernel<KT, 1>), and head 2 -- its barrier, LDS round trip and wave
+// reductions -- is not compiled.
+template <int AFFINE, int SPLIT, int VAR, int TAIL, int HEADK, int NORM = 0>
 __global__ __launch_bounds__(512) void ffn_pc_kernel(float* x, const float* __restrict__ lnw, const float* __restrict__ lnb,
                                                      const float* __restrict__ w1, const float* __restrict__ b1,
                                                      const float* __restrict__ w2, const float* __restrict__ b2, int M,
@@ -90,6 +94,7 @@ __global__ __launch_bounds__(512) void ffn_pc_kernel(float* x, const float* __re
             const float bv = head.dw_b[c];
             const float gc = head.gconst ? head.gconst[c] : 0.f;
             const bool has_gc = head.gconst != nullptr;
+            const float bn_sc = NORM == 1 ? head.lnw[c] : 0.f, bn_sh = NORM == 1 ? head.lnb[c] : 0.f;
             // the newest window element of every row (padded row t + pad) is requested up front: 16 loads in flight instead of
             // one exposed memory round trip per row of the sliding loop
             const int hb0 = row0 / head.seq_t, ht0 = row0 - hb0 * head.seq_t, lr_last = M - 1 - row0;
@@ -116,10 +121,15 @@ __global__ __launch_bounds__(512) void ffn_pc_kernel(float* x, const float* __re
                 float acc = bv;                       // out[t] = b + sum_j w[j] * gpad[t + j]
 #pragma unroll
                 for (int j = 0; j < KT; ++j) acc = fmaf(w[j], win[j], acc);
+                if (NORM == 1) {                      // folded BatchNorm + SiLU on the element itself
+                    acc = fmaf(acc, bn_sc, bn_sh);
+                    acc = acc / (1.0f + expf(-acc));
+                }
                 xn[lr * PC_XLD + c] = acc;
             }
         }
         // ---- head 2: LayerNorm + SiLU per row (wave w: rows 4w .. 4w+3), in place: the A tile of pointwise_conv2 ------------
+        if (NORM == 0)
         {
             const f32x4 ww = *reinterpret_cast<const f32x4*>(head.lnw + lane * 4);       // (requested before the barrier)
             const f32x4 bb = *reinterpret_cast<const f32x4*>(head.lnb + lane * 4);
@@ -627,7 +637,7 @@ static constexpr int P16_BM = 16;
 static constexpr int P16_RING = 8;
 __host__ __device__ constexpr int p16_k0(int kk) { return (kk & 1) * 4 + (kk >> 1); }
 
-template <int TAIL, int HEADK>
+template <int TAIL, int HEADK, int NORM = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void ffn16_kernel(
     float* x, const float* __restrict__ lnw, const float* __restrict__ lnb, const float* __restrict__ w1, const float* __restrict__ b1,
     const float* __restrict__ w2, const float* __restrict__ b2, int M, int dff, float eps, float scale, FfnTail tail, FfnHead head) {
@@ -657,6 +667,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void f
             const float bv = head.dw_b[c];
             const float gc = head.gconst ? head.gconst[c] : 0.f;
             const bool has_gc = head.gconst != nullptr;
+            const float bn_sc = NORM == 1 ? head.lnw[c] : 0.f, bn_sh = NORM == 1 ? head.lnb[c] : 0.f;
             const int hb0 = row0 / head.seq_t, ht0 = row0 - hb0 * head.seq_t, lr_last = M - 1 - row0;
 #pragma unroll
             for (int rr = 0; rr < 8; ++rr) {
@@ -681,10 +692,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void f
                 float acc = bv;
 #pragma unroll
                 for (int j = 0; j < KT; ++j) acc = fmaf(w[j], win[j], acc);
+                if (NORM == 1) {                      // folded BatchNorm + SiLU on the element itself
+                    acc = fmaf(acc, bn_sc, bn_sh);
+                    acc = acc / (1.0f + expf(-acc));
+                }
                 xn[lr * PC_XLD + c] = acc;
             }
         }
-        // ---- head 2: LayerNorm + SiLU per row (wave w: rows 2w, 2w+1), in place
+        // ---- head 2: LayerNorm + SiLU per row (wave w: rows 2w, 2w+1), in place (NORM = 1: done per element in head 1)
+        if (NORM == 0)
         {
             const f32x4 ww = *reinterpret_cast<const f32x4*>(head.lnw + lane * 4);
             const f32x4 bb = *reinterpret_cast<const f32x4*>(head.lnb + lane * 4);
@@ -1031,7 +1047,12 @@ int launch_ffn16(float* x, const float* lnw, const float* lnb, const float* w1, 
     const size_t lds = (size_t)(P16_BM * PC_XLD + 2 * P16_BM * PC_HLD) * sizeof(float);
     const dim3 grid((M + P16_BM - 1) / P16_BM);
     if (head && head->glu) {
-        if (head->ktaps == 15)
+        if (head->norm != 0 && head->norm != 1) return -1;
+        if (head->ktaps == 15 && head->norm == 1)
+            hipLaunchKernelGGL((ffn16_kernel<0, 15, 1>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, *head);
+        else if (head->ktaps == 7 && head->norm == 1)
+            hipLaunchKernelGGL((ffn16_kernel<0, 7, 1>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, *head);
+        else if (head->ktaps == 15)
             hipLaunchKernelGGL((ffn16_kernel<0, 15>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, *head);
         else if (head->ktaps == 7)
             hipLaunchKernelGGL((ffn16_kernel<0, 7>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, *head);
@@ -1124,12 +1145,12 @@ void launch_pack_ffn_pc(const float* w1, const float* w2, float* p1, float* p2, 
     hipLaunchKernelGGL(pack_ffn_pc_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w1, w2, p1, p2, dff);
 }
 
-template <int HEADK, int VAR>
+template <int HEADK, int VAR, int NORM = 0>
 static void launch_head_t(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2,
                           const float* b2, int M, int dff, float eps, float scale, hipStream_t s, const FfnHead& head, size_t lds) {
     static LdsAttr attr;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<0, 0, VAR, 0, HEADK>), lds, attr);
-    hipLaunchKernelGGL((ffn_pc_kernel<0, 0, VAR, 0, HEADK>), dim3((M + PC_BM - 1) / PC_BM), dim3(512), lds, s, x, lnw, lnb, w1, b1, w2,
+    ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<0, 0, VAR, 0, HEADK, NORM>), lds, attr);
+    hipLaunchKernelGGL((ffn_pc_kernel<0, 0, VAR, 0, HEADK, NORM>), dim3((M + PC_BM - 1) / PC_BM), dim3(512), lds, s, x, lnw, lnb, w1, b1, w2,
                        b2, M, dff, eps, scale, (float*)nullptr, 0, FfnTail{}, head);
 }
 
@@ -1157,10 +1178,16 @@ static int launch_pc_t(float* x, const float* lnw, const float* lnb, const float
         // head->xout and the reduction continues from there
 #if MASR_EXPERIMENTS
         if (head && head->glu && head->xout && head->ktaps == 15 && !AFFINE && SV == 2) {
-            static LdsAttr attr_split_h;
-            ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<0, 1, 2, 0, 15>), lds, attr_split_h);
-            hipLaunchKernelGGL((ffn_pc_kernel<0, 1, 2, 0, 15>), dim3((M + PC_BM - 1) / PC_BM, ny), dim3(512), lds, s, x, lnw, lnb, w1,
-                               b1, w2, b2, M, dff, eps, scale, partial, cpb, FfnTail{}, *head);
+            static LdsAttr attr_split_h, attr_split_hb;
+            if (head->norm == 1) {
+                ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<0, 1, 2, 0, 15, 1>), lds, attr_split_hb);
+                hipLaunchKernelGGL((ffn_pc_kernel<0, 1, 2, 0, 15, 1>), dim3((M + PC_BM - 1) / PC_BM, ny), dim3(512), lds, s, x, lnw, lnb,
+                                   w1, b1, w2, b2, M, dff, eps, scale, partial, cpb, FfnTail{}, *head);
+            } else {
+                ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<0, 1, 2, 0, 15>), lds, attr_split_h);
+                hipLaunchKernelGGL((ffn_pc_kernel<0, 1, 2, 0, 15>), dim3((M + PC_BM - 1) / PC_BM, ny), dim3(512), lds, s, x, lnw, lnb,
+                                   w1, b1, w2, b2, M, dff, eps, scale, partial, cpb, FfnTail{}, *head);
+            }
             launch_ffn_reduce(x, partial, b2, M, ny, scale, s, post, head->xout);
             return (post && post->y ? 1 : 0) | 4;
         }
@@ -1170,7 +1197,9 @@ static int launch_pc_t(float* x, const float* lnw, const float* lnb, const float
         launch_ffn_reduce(x, partial, b2, M, ny, scale, s, post);
         return post && post->y ? 1 : 0;
     } else if (head && head->glu && (head->ktaps == 15 || head->ktaps == 7) && !AFFINE && VAR != 1 && !(tail && tail->out)) {
-        if (head->ktaps == 15) launch_head_t<15, TV>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, s, *head, lds);
+        if (head->ktaps == 15 && head->norm == 1) launch_head_t<15, TV, 1>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, s, *head, lds);
+        else if (head->norm == 1) launch_head_t<7, TV, 1>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, s, *head, lds);
+        else if (head->ktaps == 15) launch_head_t<15, TV>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, s, *head, lds);
         else launch_head_t<7, TV>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, s, *head, lds);
         return 4;                                         // head stage done
     } else if (tail && tail->out && tail->N % 256 == 0 && !AFFINE && VAR != 1) {

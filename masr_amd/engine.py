@@ -97,8 +97,10 @@ def _validate_encoder_conf(use_model, enc, state_dict):
         if v not in allowed:
             raise _lib.MasrError(f'{use_model}: encoder_conf.{key}={v!r} is not implemented (supported: {allowed})')
     if use_model in ('conformer', 'efficient_conformer'):
-        # batch_norm (conformer/convolution.py:60-67): Conformer only, full-context forward only (eval-mode statistics folded)
-        want('cnn_module_norm', ('layer_norm', 'batch_norm') if use_model == 'conformer' else ('layer_norm',), 'layer_norm')
+        # batch_norm (conformer/convolution.py:60-67, eval-mode statistics folded into scale / shift): Conformer in the full-context
+        # forward only, Efficient Conformer full-context and chunked.  An absent key means layer_norm here for both families (the
+        # reference's EfficientConformerEncoder defaults to batch_norm; the shipped YAML sets layer_norm)
+        want('cnn_module_norm', ('layer_norm', 'batch_norm'), 'layer_norm')
         want('activation_type', ('swish',), 'swish')
         want('normalize_before', (True,), True)
         want('use_cnn_module', (True,), True)
@@ -213,6 +215,7 @@ class HipEngine:
             cfg.reserved[0] = int(stride_idx[0])
             cfg.reserved[1] = len(groups)
             cfg.reserved[2] = int(eff.get('group_size', 3))
+            cfg.reserved[4] = 1 if enc.get('cnn_module_norm', 'layer_norm') == 'batch_norm' else 0
             cfg.reserved[3] = INPUT_LAYERS[self.input_layer]
         elif use_model == 'deepspeech2':
             # configs/deepspeech2.yml encoder_conf: rnn_size, num_rnn_layers, use_gru; streaming <=> uni-directional recurrent

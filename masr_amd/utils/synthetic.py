@@ -171,11 +171,18 @@ def squeezeformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, ff_factor=
 
 def efficient_conformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, d_ff=2048, num_blocks=12, kernel=15,
                                    n_mels=80, ctc_gain=6.0, stride_layer_idx=(3,), stride=(2,),
-                                   group_layer_idx=(0, 1, 2, 3), group_size=3, input_layer='conv2d'):
+                                   group_layer_idx=(0, 1, 2, 3), group_size=3, input_layer='conv2d',
+                                   cnn_module_norm='layer_norm'):
     """Keys/shapes == reference EfficientConformerModel ``encoder.*`` + ``ctc.*``
     (configs/efficient_conformer.yml: streaming, layer_norm conv module, grouped attention in blocks 0-3,
-    strided depthwise conv in block 3, kernel 15 -> 7 afterwards; masr/model_utils/efficient_conformer/)."""
-    sd = conformer_state_dict(seed, vocab_size, d, heads, d_ff, num_blocks, kernel, n_mels, ctc_gain, input_layer=input_layer)
+    strided depthwise conv in block 3, kernel 15 -> 7 afterwards; masr/model_utils/efficient_conformer/).
+    ``cnn_module_norm='batch_norm'`` (the reference encoder's own default, efficient_conformer/encoder.py:48): the conv
+    module's norm carries running statistics and ``num_batches_tracked``, as in ``conformer_state_dict``."""
+    sd = conformer_state_dict(seed, vocab_size, d, heads, d_ff, num_blocks, kernel, n_mels, ctc_gain, input_layer=input_layer,
+                              cnn_module_norm=cnn_module_norm)
+    if cnn_module_norm == 'batch_norm':
+        for i in range(num_blocks):
+            sd[f'encoder.encoders.{i}.conv_module.norm.num_batches_tracked'] = torch.tensor(100, dtype=torch.long)
     k = kernel
     for i in range(num_blocks):
         p = f'encoder.encoders.{i}.'
