@@ -30,7 +30,9 @@ typedef struct masr_config {
     int32_t d_model;         /* encoder_conf.output_size        (256); deepspeech2: encoder_conf.rnn_size, a multiple of
                               * 256 in [256, 2048] (1024 in configs/deepspeech2.yml)           */
     int32_t heads;           /* encoder_conf.attention_heads    (4)                             */
-    int32_t d_ff;            /* encoder_conf.linear_units       (2048)                          */
+    int32_t d_ff;            /* encoder_conf.linear_units       (2048); squeezeformer: encoder_dim x
+                              * feed_forward_expansion_factor.  Model kinds 0-2: any positive multiple of 128;
+                              * masr_create refuses 0, negative values and non-multiples              */
     int32_t num_blocks;      /* encoder_conf.num_blocks         (12)                            */
     int32_t cnn_kernel;      /* encoder_conf.cnn_module_kernel  (15)                            */
     int32_t n_mels;          /* preprocess_conf.n_mels          (80)                            */

@@ -648,8 +648,9 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
             return fail("deepspeech2: the recurrent cell (masr_config.reserved[0], encoder_conf.use_gru) must be 0 = LSTM or 1 = GRU");
     } else if (cfg->d_model != 256 || cfg->heads != 4) {
         return fail("kernels are specialised for d_model=256, heads=4");
-    } else if (cfg->d_ff % 128) {
-        return fail("unsupported d_ff");
+    } else if (cfg->d_ff <= 0 || cfg->d_ff % 128) {
+        // (0 and the negative multiples pass the remainder test; ffn() would then launch the fused kernels with no chunks)
+        return fail("d_ff (linear_units) must be a positive multiple of 128, got " + std::to_string(cfg->d_ff));
     }
     if (cfg->model_kind == 3) {
     } else if (cfg->model_kind == 0 || cfg->model_kind == 2) {
