@@ -30,6 +30,13 @@ typedef struct masr_config {
     int32_t d_model;         /* encoder_conf.output_size        (256); deepspeech2: encoder_conf.rnn_size, a multiple of
                               * 256 in [256, 2048] (1024 in configs/deepspeech2.yml)           */
     int32_t heads;           /* encoder_conf.attention_heads    (4)                             */
+                             /* (d_model, heads): (256, 4) for model kinds 0-2; model kind 0 also (512, 8), with layer_norm
+                              * (reserved[0] = 0) and input_layer conv2d (reserved[3] = 0) only.  masr_create refuses every other
+                              * pair with a message that names output_size / attention_heads.  (512, 8) runs a width-generic path
+                              * of separate launches (csrc/wide.hip + the tiled GEMM): every entry point works as at 256 -- both
+                              * lanes, chunk steps, cache export [L, 8, t, 128] / [L, 1, 512, 14] -- but it builds no packed weight
+                              * copies and none of the fused row-block kernels run, so the masr_debug_set keys that choose between
+                              * them have no effect there; the attention keys (attention_fewq, attention_fold, ...) keep theirs */
     int32_t d_ff;            /* encoder_conf.linear_units       (2048); squeezeformer: encoder_dim x
                               * feed_forward_expansion_factor.  Model kinds 0-2: any positive multiple of 128;
                               * masr_create refuses 0, negative values and non-multiples              */
@@ -510,6 +517,8 @@ int masr_select_lane(masr_engine* e, int32_t lane);
  *  43  rnn_mfma_units: hidden units per workgroup of the DeepSpeech2 matrix-core recurrent step (4 < B <= 32): 8 = production (4
  *      units at rnn_size <= 512, 8 above); 16 = 16 units (GRU at rnn_size 1024 only); -8 = 8 units at every size (bit-identical: a
  *      column's dot product does not depend on the grouping)
+ * At d_model 512 (masr_config.d_model) only the attention keys (7, 14, 28) and the tile choice of the tiled GEMM change the launches: the fused
+ * FFN / row-block / chain keys select between kernels built for d_model 256.
  * Keys 20, 21, 22, 24, 30, 34 and 35 select experimental kernels: a build without MASR_BUILD_EXPERIMENTS=1 refuses a non-zero value.
  * masr_debug_reset puts every process-wide switch back to its default, and this engine's keys 16 and 38 (1 and 7); key 2 is left
  * alone.  masr_debug_key_info (no engine) describes row `index` of the table of process-wide switches -- its key, default,
@@ -520,7 +529,8 @@ int masr_debug_key_info(int32_t index, int32_t* key, int32_t* default_value, int
 
 /* Profiling: time every launch of one kernel class with HIP events on the launch stream.
  * kind: 0 none, 1 gemm (all), 2 ffn-w1 gemm, 3 conv2 gemm, 4 attention, 5 fbank, 8 the step loop of a DeepSpeech2 recurrent
- * layer (one "launch" = the T' step launches of one layer).
+ * layer (one "launch" = the T' step launches of one layer); the row kernels of the d_model 512 path (csrc/wide.hip): 9 LayerNorm,
+ * 10 GLU, 11 depthwise conv + LayerNorm + SiLU, 12 the streaming cache kernels (conv history, key / value append).
  * masr_profile_read synchronises the events and returns total ms / launch count / flops since reset. */
 int masr_profile_select(masr_engine* e, int32_t kind);
 int masr_profile_read(masr_engine* e, double* total_ms, int64_t* launches, double* flops, int32_t reset);

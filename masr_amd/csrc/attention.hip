@@ -77,7 +77,7 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
                                                         const float* __restrict__ ptab,
                                                         const float* __restrict__ bias_u,
                                                         const float* __restrict__ bias_v, int chunk_size,
-                                                        int pos_stride, int nqb_1d, int heads_1d, int nseq_1d) {
+                                                        int pos_stride, int nqb_1d, int heads_1d, int nseq_1d, int row_w) {
     __shared__ __align__(16) float lds_att[2 * 32 * KP_LD * 2 + 2 * 32 * V_LD + 64];
     float* Ks = lds_att;                       // [2 tiles][32][68]
     float* Ps = Ks + 2 * 32 * KP_LD;
@@ -155,10 +155,10 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
     // raw buffer loads: the sequence's key / value rows and its positional rows behind descriptors in SGPRs, this thread's row and
     // column as ONE constant byte offset per operand, the tile pair as a scalar offset -- no 64-bit address arithmetic per load
     // next to the MFMAs; rows past the last key are out of the descriptor's range and read as zero
-    const unsigned kv_row_bytes = (unsigned)kv_stride * 4u, p_row_bytes = (unsigned)pos_stride * 1024u;
+    const unsigned kv_row_bytes = (unsigned)kv_stride * 4u, p_row_bytes = (unsigned)(pos_stride * row_w) * 4u;
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sq.k), 0, (unsigned)sq.nk * kv_row_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sq.v), 0, (unsigned)sq.nk * kv_row_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptab + (size_t)sq.pos0 * 256), 0,
+    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptab + (size_t)sq.pos0 * row_w), 0,
                                                                          (unsigned)sq.nk * p_row_bytes, 0x00020000);
     unsigned kvo[2], po[2];
 #pragma unroll
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
             const int jc = min(j, sq.nk - 1);                      // clamped address, masked below
             pk[i] = *reinterpret_cast<const f32x4*>(sq.k + (size_t)jc * kv_stride + head * DK + sc4);
             pv[i] = *reinterpret_cast<const f32x4*>(sq.v + (size_t)jc * kv_stride + head * DK + sc4);
-            pp[i] = *reinterpret_cast<const f32x4*>(ptab + (size_t)(sq.pos0 + jc * pos_stride) * 256 + head * DK + sc4);
+            pp[i] = *reinterpret_cast<const f32x4*>(ptab + (size_t)(sq.pos0 + jc * pos_stride) * row_w + head * DK + sc4);
             if (j >= sq.nk) { pk[i] = f32x4{0.f, 0.f, 0.f, 0.f}; pv[i] = pk[i]; pp[i] = pk[i]; }
         }
     };
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
     // ---- normalise and store: lane owns query qi, dims d = (r&3) + 8(r>>2) + 4h (+32) -----------
     if (q_ok) {
         const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
-        float* orow = sq.out + (size_t)qi * 256 + head * DK;
+        float* orow = sq.out + (size_t)qi * row_w + head * DK;
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int d = 8 * rr + 4 * h;
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
                                                              const float* __restrict__ ptab,
                                                              const float* __restrict__ bias_u,
                                                              const float* __restrict__ bias_v, int chunk_size,
-                                                             int pos_stride) {
+                                                             int pos_stride, int row_w) {
     __shared__ float mg[8 * 34 * 64];          // [wave][m, l, o0[16], o1[16]][lane]
     const AttSeq sq = seqs[blockIdx.y];
     const int head = blockIdx.x;
@@ -379,10 +379,10 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
     // per-lane offset per operand, the tile (and, for the value rows, the key of accumulator register r) as a wave-uniform scalar
     // offset -- no per-load address arithmetic in a kernel whose time is its dependent chain; rows past the last key read as zero
     // (their keys are masked: probability 0 times 0)
-    const unsigned kv_row_bytes = (unsigned)kv_stride * 4u, p_row_bytes = (unsigned)pos_stride * 1024u;
+    const unsigned kv_row_bytes = (unsigned)kv_stride * 4u, p_row_bytes = (unsigned)(pos_stride * row_w) * 4u;
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sq.k), 0, (unsigned)sq.nk * kv_row_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sq.v), 0, (unsigned)sq.nk * kv_row_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptab + (size_t)sq.pos0 * 256), 0,
+    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptab + (size_t)sq.pos0 * row_w), 0,
                                                                          (unsigned)sq.nk * p_row_bytes, 0x00020000);
     const unsigned ko = (unsigned)(lane & 31) * kv_row_bytes + (unsigned)(head * DK + 4 * h) * 4u;
     const unsigned po = (unsigned)(lane & 31) * p_row_bytes + (unsigned)(head * DK + 4 * h) * 4u;
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
         // ---- all operand loads of this tile (clamped rows: masked keys get probability 0, times a finite value) ----------
         const int jr = min(j0 + (lane & 31), sq.nk - 1);
         const float* kp = sq.k + (size_t)jr * kv_stride + head * DK + 4 * h;
-        const float* pp = ptab + (size_t)(sq.pos0 + jr * pos_stride) * 256 + head * DK + 4 * h;
+        const float* pp = ptab + (size_t)(sq.pos0 + jr * pos_stride) * row_w + head * DK + 4 * h;
 #pragma unroll
         for (int g = 0; g < 8; ++g) kf[g] = *reinterpret_cast<const f32x4*>(kp + 8 * g);
 #pragma unroll
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
     }
     if (q_ok) {
         const float inv = l > 0.f ? 1.0f / l : 0.f;
-        float* orow = sq.out + (size_t)qi * 256 + head * DK + (wave >> 2) * 32 + 8 * (wave & 3) + 4 * h;
+        float* orow = sq.out + (size_t)qi * row_w + head * DK + (wave >> 2) * 32 + 8 * (wave & 3) + 4 * h;
 #pragma unroll
         for (int s = 0; s < 4; ++s) acc[s] *= inv;
         *reinterpret_cast<f32x4*>(orow) = acc;
@@ -500,7 +500,7 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
 
 void launch_attention(const AttSeq* seqs, int nseq, int max_nq, int heads, int q_stride, int kv_stride,
                       const float* ptab, const float* bias_u, const float* bias_v, int chunk_size, int pos_stride,
-                      hipStream_t s) {
+                      hipStream_t s, int row_w) {
     if (nseq <= 0 || max_nq <= 0) return;
     const int nqb = (max_nq + 127) / 128;
     // the key-split kernel (eight waves share 32 queries and split the key tiles) also takes short offline batches, one
@@ -508,19 +508,19 @@ void launch_attention(const AttSeq* seqs, int nseq, int max_nq, int heads, int q
     // walk ALL key tiles in pairs (one 8.4 s utterance: 8 workgroups, 22 us; here 28 workgroups of one tile per wave)
     if (knobs().attention_fewq && (max_nq <= 32 || nqb * heads * nseq < knobs().attention_fewq_wgs)) {
         hipLaunchKernelGGL(attention_fewq_kernel, dim3(heads, nseq, (max_nq + 31) / 32), dim3(512), 0, s, seqs, q_stride, kv_stride,
-                           ptab, bias_u, bias_v, chunk_size, pos_stride);
+                           ptab, bias_u, bias_v, chunk_size, pos_stride, row_w);
         return;
     }
     const int fold = knobs().attention_fold;
     if (fold && ATT_XCD_MAP)
         hipLaunchKernelGGL(attention_kernel<1>, dim3(8 * nqb * ((heads * nseq + 7) / 8)), dim3(512), 0, s, seqs, q_stride,
-                           kv_stride, ptab, bias_u, bias_v, chunk_size, pos_stride, nqb, heads, nseq);
+                           kv_stride, ptab, bias_u, bias_v, chunk_size, pos_stride, nqb, heads, nseq, row_w);
     else if (fold)
         hipLaunchKernelGGL(attention_kernel<1>, dim3(nqb, heads, nseq), dim3(512), 0, s, seqs, q_stride,
-                           kv_stride, ptab, bias_u, bias_v, chunk_size, pos_stride, 0, heads, nseq);
+                           kv_stride, ptab, bias_u, bias_v, chunk_size, pos_stride, 0, heads, nseq, row_w);
     else
         hipLaunchKernelGGL(attention_kernel<0>, dim3(nqb, heads, nseq), dim3(512), 0, s, seqs, q_stride,
-                           kv_stride, ptab, bias_u, bias_v, chunk_size, pos_stride, 0, heads, nseq);
+                           kv_stride, ptab, bias_u, bias_v, chunk_size, pos_stride, 0, heads, nseq, row_w);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -85,7 +85,9 @@ __host__ __device__ inline int sub_bins(int il, int F) { return sub_after_conv1(
 // ---- GEMM: C[M,N] = epilogue(A[M,K] * W[N,K]^T) on v_mfma_f32_32x32x2_f32 ----------------
 enum GemmAct { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2 };
 enum GemmAMode { A_PLAIN = 0, A_CONV2 = 1, A_CONV5 = 2 };     // A_CONV5: the 5x5 stride-3 gather of conv2d6 (A_CONV2 geometry)
-enum GemmEpi { EPI_STD = 0, EPI_GLU = 1, EPI_SPLITK = 2 };
+enum GemmEpi { EPI_STD = 0, EPI_GLU = 1, EPI_SPLITK = 2 };    // EPI_GLU is NOT implemented by launch_gemm (gemm_f32.hip has no GLU
+                                                                // epilogue; the number is kept so that EPI_SPLITK keeps its value): the
+                                                                // row-block kernels carry RG_EPI_GLU, the wide path runs launch_glu_wide
 
 struct GemmArgs {
     const float* A;      // [M, lda] row-major (A_PLAIN) or conv activations [B,T1,F1,C] (A_CONV2 / A_CONV5)
@@ -419,7 +421,7 @@ struct AttSeq {            // one per sequence, device memory
     const float* q;        // first query row of this sequence (row stride q_stride)
     const float* k;        // first key row   (row stride kv_stride)
     const float* v;        // first value row (row stride kv_stride)
-    float* out;            // first output row (row stride 256)
+    float* out;            // first output row (row stride heads * 64: launch_attention's row_w)
     int nq, nk;            // number of query rows / key rows
     int klen;              // keys j >= klen are masked (padding)
     int pos0;              // positional index of key 0
@@ -451,9 +453,10 @@ bool launch_attn_chain(const AttnChainArgs& a, int max_nq, hipStream_t s);
 #else
 inline bool launch_attn_chain(const AttnChainArgs&, int, hipStream_t) { return false; }
 #endif
+// row_w = heads * 64: the row stride of AttSeq::out and of ptab [max_pos, row_w] (256; the wide Conformer path: 512)
 void launch_attention(const AttSeq* seqs, int nseq, int max_nq, int heads, int q_stride, int kv_stride,
-                      const float* ptab /*[max_pos,256]*/, const float* bias_u, const float* bias_v,
-                      int chunk_size, int pos_stride, hipStream_t s);
+                      const float* ptab /*[max_pos,row_w]*/, const float* bias_u, const float* bias_v,
+                      int chunk_size, int pos_stride, hipStream_t s, int row_w);
 void launch_attention_grouped(const AttSeq* seqs, int nseq, int max_nq, int heads, int group, const float* ptab,
                               int t_true, const float* bias_u, const float* bias_v, hipStream_t s, int chunk_size = 0);
 void launch_attseq_grouped(AttSeq* seqs, const float* q, const float* k, const float* v, float* out, const int* lens,
@@ -465,6 +468,33 @@ void launch_conv_hist(const float* x, const float* w, const float* b, float* con
                       float* lnpad, int n, int Tq, int pad, int affine, float eps, hipStream_t s);
 void launch_attseq_full(AttSeq* seqs, const float* qkv, float* out, const int* lens, int B, int Tp, int mstride,
                         hipStream_t s, int valid_only = 0);     // valid_only: nq = nk = klen (padded queries / keys are not touched)
+
+// ---- width-generic Conformer path (wide.hip): counterparts of the 256-only row kernels, rows of width d ------------------------
+// wide_supported(d): the widths the templated kernels are instantiated for (512).  The bool launchers are those templated on the
+// width: false, with nothing launched, for any other d.  The void launchers (conv1, glu(bias), sequence descriptors) run plain
+// kernels that take d at run time and serve any width.
+bool wide_supported(int d);
+// launch_layernorm at width d (same remap into the padded layout and pad masking)
+bool launch_layernorm_wide(const float* x, const float* w, const float* b, float* y, int M, int d, float eps, int seq_t, int pad,
+                           const int* lens, hipStream_t s);
+// launch_conv1 for more than 256 output channels
+void launch_conv1_wide(const float* feats, const float* mean, const float* istd, const float* w9c, const float* bias, float* out,
+                       int B, int T, int F, int C, hipStream_t s);
+// out [M, d] = value * sigmoid(gate) of in [M, 2 d] (value | gate: a pointwise_conv1 output with its bias added)
+bool launch_glu_wide(const float* in, float* out, int M, int d, hipStream_t s);
+void launch_glu_const_wide(const float* bias2d, float* out, int d, hipStream_t s);      // launch_glu_const at width d
+// depthwise conv (ktaps = 15) + LayerNorm(d) + SiLU: g [nseq][in_pad + Tq][d] (in_pad materialised history rows) -> out [nseq * Tq, d];
+// tap j of output frame t reads input frame t + j - pad_l; frames in front of the materialised rows read gconst [d] (nullptr:
+// zero), frames behind the sequence read zero
+bool launch_dwconv_ln_silu_wide(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb, float* out,
+                                int nseq, int Tq, int d, int ktaps, int in_pad, int pad_l, float eps, const float* gconst,
+                                hipStream_t s);
+// launch_conv_hist (LayerNorm variant) at width d
+bool launch_conv_hist_wide(const float* x, const float* w, const float* b, float* const* cache_rd, float* const* cache_wr,
+                           float* lnpad, int n, int Tq, int pad, int d, float eps, hipStream_t s);
+bool launch_kv_append_wide(const AttSeq* seqs, const float* qkv, int n, int Tq, int d, hipStream_t s);   // qkv [n * Tq, 3 d]
+// launch_attseq_full over a [B * Tp, 3 d] q | k | v buffer and [B * Tp, d] output rows (conv2d rate: 4 feature frames per frame)
+void launch_attseq_full_wide(AttSeq* seqs, const float* qkv, float* out, const int* lens, int B, int Tp, int d, hipStream_t s);
 
 // ---- features ------------------------------------------------------------------------------
 size_t fbank_gain_scratch_floats(int B);   // size of gain_scratch ([B] gains + partial sums)

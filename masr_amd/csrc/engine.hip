@@ -216,7 +216,8 @@ struct GBeam {        // device-resident streaming CTC prefix beam search (masr_
 };
 
 enum ProfKind { PROF_NONE = 0, PROF_GEMM = 1, PROF_FFN1 = 2, PROF_CONV2 = 3, PROF_ATT = 4, PROF_FBANK = 5,
-                PROF_FFN_TAIL = 6, PROF_FFN_HEAD = 7, PROF_RNN = 8 };     // 2 = the plain fused FFN kernel; 6 = its variant with the QKV tail stage, 7 = with the conv-module head stage (own kernel names)
+                PROF_FFN_TAIL = 6, PROF_FFN_HEAD = 7, PROF_RNN = 8,
+                PROF_WIDE_LN = 9, PROF_WIDE_GLU = 10, PROF_WIDE_DWCONV = 11, PROF_WIDE_CACHE = 12 };   // 9-12: the row kernels of wide.hip (12 = conv_hist + kv_append)     // 2 = the plain fused FFN kernel; 6 = its variant with the QKV tail stage, 7 = with the conv-module head stage (own kernel names)
 
 }  // namespace
 
@@ -646,11 +647,20 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
         if (cfg->num_blocks <= 0) return fail("deepspeech2: num_rnn_layers must be positive");
         if (cfg->reserved[0] != 0 && cfg->reserved[0] != 1)
             return fail("deepspeech2: the recurrent cell (masr_config.reserved[0], encoder_conf.use_gru) must be 0 = LSTM or 1 = GRU");
-    } else if (cfg->d_model != 256 || cfg->heads != 4) {
-        return fail("kernels are specialised for d_model=256, heads=4");
+    } else if (!(cfg->d_model == 256 && cfg->heads == 4) && !(cfg->model_kind == 0 && cfg->d_model == 512 && cfg->heads == 8)) {
+        return fail("output_size / attention_heads (masr_config.d_model / heads) = " + std::to_string(cfg->d_model) + " / " +
+                    std::to_string(cfg->heads) + " is not supported: 256 / 4 for every family, 512 / 8 for the Conformer "
+                    "(model_kind 0) only");
     } else if (cfg->d_ff <= 0 || cfg->d_ff % 128) {
         // (0 and the negative multiples pass the remainder test; ffn() would then launch the fused kernels with no chunks)
         return fail("d_ff (linear_units) must be a positive multiple of 128, got " + std::to_string(cfg->d_ff));
+    } else if (cfg->d_model != 256) {
+        // the width-generic path (wide.hip) carries the shipped Conformer variant only
+        if (cfg->reserved[0] == 1)
+            return fail("output_size " + std::to_string(cfg->d_model) + ": cnn_module_norm: batch_norm is implemented at output_size 256 only");
+        if (cfg->reserved[3] != IL_CONV2D)
+            return fail("output_size " + std::to_string(cfg->d_model) + ": input_layer must be conv2d (conv2d6 / conv2d8 are implemented at "
+                        "output_size 256 only)");
     }
     if (cfg->model_kind == 3) {
     } else if (cfg->model_kind == 0 || cfg->model_kind == 2) {
@@ -895,7 +905,7 @@ int masr_finalize(masr_engine* e, void* stream) {
         CHK(up(e, p + "self_attn.pos_bias_v", {H, gk}, &w.pos_v));
         CHK(up(e, p + "conv_module.pointwise_conv1.weight", {2 * d, d, 1}, &w.pw1_w));   // rows: value c, gate d + c
         CHK(up(e, p + "conv_module.pointwise_conv1.bias", {2 * d}, &w.pw1_b));
-        {   // [Wo; W_pw1] and [bo; b_pw1]: one continuous weight stream for the fused kernel of the offline path
+        if (d == 256) {   // [Wo; W_pw1] and [bo; b_pw1]: one continuous weight stream for the fused kernel of the offline path
             const HostTensor *a, *b, *c2, *d2;
             CHK(get(e, p + "self_attn.linear_out.weight", {d, d}, &a));
             CHK(get(e, p + "self_attn.linear_out.bias", {d}, &b));
@@ -910,7 +920,8 @@ int masr_finalize(masr_engine* e, void* stream) {
         {   // glu(bias): what the zero left-padding of the causal conv turns into behind pointwise_conv1 + GLU
             std::vector<float> z(d, 0.f);
             CHK(upload(e, z, &w.gconst));
-            launch_glu_const(w.pw1_b, w.gconst, (hipStream_t)stream);
+            if (d == 256) launch_glu_const(w.pw1_b, w.gconst, (hipStream_t)stream);
+            else launch_glu_const_wide(w.pw1_b, w.gconst, d, (hipStream_t)stream);
         }
         {   // depthwise [d,1,K_i] -> [K_i][d]
             const int K = layer_kernel(e, i);
@@ -1118,8 +1129,9 @@ static int subsampling_conv(masr_engine* e, hipStream_t s, GemmArgs a, int amode
     if (!a.feats) {
         if (feats) {        // conv1 as its own launch into x1
             CHK(e->x1.ensure((size_t)nseq * a.T1 * a.F1 * d * sizeof(float)));
-            launch_conv1(feats, e->cmvn_mean, e->cmvn_istd, e->conv1_w, e->conv1_b, e->x1.as<float>(), nseq, a.Tin, e->cfg.n_mels,
-                         d, s);
+            // (conv1_kernel's thread = output channel: more than 256 channels take the wide kernel)
+            (d > 256 ? launch_conv1_wide : launch_conv1)(feats, e->cmvn_mean, e->cmvn_istd, e->conv1_w, e->conv1_b, e->x1.as<float>(),
+                                                         nseq, a.Tin, e->cfg.n_mels, d, s);
             a.A = e->x1.as<float>();
         } else {
             a.A = x_in;
@@ -1358,6 +1370,90 @@ void mhsa_out_pw1(masr_engine* e, hipStream_t s, const LayerW& w, const EncodeCt
     if (knobs().rowgemm_packed) a.Wp = packed_rows_of(e, w.chain_w, 3 * d, s);
     ProfScope ps(e, s, PROF_GEMM, 2.0 * M * (double)(3 * d) * d);
     launch_rowgemm(a, RG_PRO_PLAIN, RG_EPI_CHAIN, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Width-generic Conformer path (output_size 512, attention_heads 8; masr_create admits it for model_kind 0 only): the layer of
+// conformer/encoder.py:88-167 with every step as its own launch -- the row kernels of wide.hip, the tiled GEMM of gemm_f32.hip
+// for every product and the attention kernels with 8 heads of 64.  No packed weight copies, none of the fused row-block kernels
+// (they are built for K = 256), so none of their masr_debug_set switches applies here.
+// ------------------------------------------------------------------------------------------------
+bool is_wide(const masr_engine* e) { return e->cfg.model_kind == 0 && e->cfg.d_model != 256; }
+// a wide.hip launch under its profile class (masr_profile_select kinds 9-12); a width the kernels are not built for is an error
+#define WIDECHK(kind, launched)                                                                                      \
+    do {                                                                                                             \
+        ProfScope _ps(e, s, kind, 0.0);                                                                              \
+        if (!(launched)) return fail("no kernel for output_size " + std::to_string(e->cfg.d_model) + ": " #launched); \
+    } while (0)
+
+int ensure_wide_ws(masr_engine* e, int nseq, int Tq) {
+    CHK(ensure_layer_ws(e, nseq, Tq));
+    // hidden rows of an FFN [M, d_ff] or the value | gate rows of pointwise_conv1 over the padded layout [Mp, 2 d]
+    const size_t Mp = (size_t)nseq * (Tq + e->cfg.cnn_kernel - 1);
+    return e->hid.ensure(Mp * std::max(e->cfg.d_ff, 2 * e->cfg.d_model) * sizeof(float));
+}
+
+// x <- x + 0.5 * (W2 . silu(W1 . LayerNorm(x) + b1) + b2)
+int wide_ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb, const float* w1, const float* b1,
+             const float* w2, const float* b2) {
+    const int d = e->cfg.d_model, dff = e->cfg.d_ff;
+    float *x = e->x.as<float>(), *ln = e->ln.as<float>(), *hid = e->hid.as<float>();
+    WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, lnw, lnb, ln, M, d, 1e-5f, 0, 0, nullptr, s));
+    gemm(e, s, ln, d, w1, b1, hid, dff, M, dff, d, ACT_SILU, 1.f, nullptr, 0, PROF_FFN1);
+    gemm(e, s, hid, dff, w2, b2, x, d, M, d, dff, ACT_NONE, 0.5f, x, d, PROF_FFN1);
+    return 0;
+}
+
+// one layer on x [nseq * Tq, d] in place.  Offline (cache_rd == nullptr): seqs point into the qkv buffer, lens mask the padded
+// frames, the conv module's history is the constant glu(bias) row (causal build) or zero padding on both sides.  Chunk step: the
+// k | v columns are appended to the streams' caches, the conv module reads its history rows from cache_rd and writes cache_wr.
+int wide_layer(masr_engine* e, hipStream_t s, const LayerW& w, int nseq, int Tq, const int* lens, const AttSeq* seqs, int chunk,
+               float* const* cache_rd, float* const* cache_wr) {
+    const int d = e->cfg.d_model, H = e->cfg.heads, K = e->cfg.cnn_kernel, pad = K - 1, M = nseq * Tq;
+    const bool stream = cache_rd != nullptr;
+    float *x = e->x.as<float>(), *ln = e->ln.as<float>(), *hid = e->hid.as<float>(), *glu = e->glu.as<float>();
+    CHK(wide_ffn(e, s, M, w.ln_ffm_w, w.ln_ffm_b, w.ffm_w1, w.ffm_b1, w.ffm_w2, w.ffm_b2));
+    // self-attention: x <- x + Wo . att(LayerNorm(x))
+    WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, w.ln_mha_w, w.ln_mha_b, ln, M, d, 1e-5f, 0, 0, nullptr, s));
+    gemm(e, s, ln, d, w.wqkv, w.bqkv, e->qkv.as<float>(), 3 * d, M, 3 * d, d, ACT_NONE, 1.f, nullptr, 0);
+    if (stream) WIDECHK(PROF_WIDE_CACHE, launch_kv_append_wide(seqs, e->qkv.as<float>(), nseq, Tq, d, s));
+    {
+        ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * nseq);
+        launch_attention(seqs, nseq, Tq, H, 3 * d, stream ? 2 * d : 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, 1, s, d);
+    }
+    gemm(e, s, e->att.as<float>(), d, w.wo, w.bo, x, d, M, d, d, ACT_NONE, 1.f, x, d);
+    // conv module: x <- x + mask(pw2(SiLU(LayerNorm(dwconv(GLU(pw1(mask(LayerNorm(x)))))))))
+    const int in_pad = stream ? pad : 0, Mp = nseq * (Tq + in_pad);
+    if (stream) {
+        WIDECHK(PROF_WIDE_CACHE, launch_conv_hist_wide(x, w.ln_conv_w, w.ln_conv_b, cache_rd, cache_wr, e->lnpad.as<float>(), nseq, Tq, pad, d, 1e-5f, s));
+    } else {
+        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, w.ln_conv_w, w.ln_conv_b, ln, M, d, 1e-5f, Tq, 0, lens, s));
+    }
+    gemm(e, s, stream ? e->lnpad.as<float>() : ln, d, w.pw1_w, w.pw1_b, hid, 2 * d, Mp, 2 * d, d, ACT_NONE, 1.f, nullptr, 0);
+    WIDECHK(PROF_WIDE_GLU, launch_glu_wide(hid, glu, Mp, d, s));
+    WIDECHK(PROF_WIDE_DWCONV, launch_dwconv_ln_silu_wide(glu, w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), nseq, Tq, d, K, in_pad,
+                                       (stream || e->cfg.causal) ? pad : pad / 2, 1e-5f,
+                                       (!stream && e->cfg.causal) ? w.gconst : nullptr, s));
+    gemm(e, s, e->dwo.as<float>(), d, w.pw2_w, w.pw2_b, x, d, M, d, d, ACT_NONE, 1.f, x, d, PROF_GEMM, lens, lens ? Tq : 0);
+    CHK(wide_ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2));
+    WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, w.ln_fin_w, w.ln_fin_b, x, M, d, 1e-5f, 0, 0, nullptr, s));
+    return 0;
+}
+
+// ConformerEncoder.forward at output_size 512 (masr_encode_full): feats [B, T, n_mels] -> enc_out [B * T', d]
+int encode_full_wide(masr_engine* e, hipStream_t s, const float* feats, const int* lens, int B, int T, float* enc_out, int chunk) {
+    const int d = e->cfg.d_model;
+    if (!wide_supported(d)) return fail("no kernels for output_size " + std::to_string(d));
+    int Tq = 0;
+    CHK(embed(e, s, feats, B, T, &Tq));
+    if (Tq >= e->cfg.max_pos) return fail("sequence longer than max_pos");   // embedding.py:48-50 assert
+    CHK(ensure_wide_ws(e, B, Tq));
+    CHK(e->attseq.ensure(sizeof(AttSeq) * B));
+    launch_attseq_full_wide(e->attseq.as<AttSeq>(), e->qkv.as<float>(), e->att.as<float>(), lens, B, Tq, d, s);
+    for (const LayerW& w : e->layers) CHK(wide_layer(e, s, w, B, Tq, lens, e->attseq.as<AttSeq>(), chunk, nullptr, nullptr));
+    WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(e->x.as<float>(), e->after_w, e->after_b, enc_out, B * Tq, d, 1e-5f, 0, 0, nullptr, s));
+    LAUNCHCHK();
+    return 0;
 }
 
 }  // namespace
@@ -1602,7 +1698,7 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
         {
             ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * B);
             // (chunk > 0: decoding_chunk_size of the streaming-trained build; the kernel thins the mask by the layer's rate)
-            launch_attention(e->attseq.as<AttSeq>(), B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, pstride, s);
+            launch_attention(e->attseq.as<AttSeq>(), B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, pstride, s, 256);
         }
         if (fused) {
             // the next layer's QKV projection rides on this layer's last launch unless the frame rate changes in between
@@ -1749,7 +1845,7 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
             if (!qkv_done) mhsa(e, s, w, M);
             {
                 ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * B);
-                launch_attention(seq_r, B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, pstride, s);
+                launch_attention(seq_r, B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, pstride, s, 256);
             }
             if (fused) mhsa_out_pw1(e, s, w, ctx0, mstride, Ki);
             else mhsa_out(e, s, w, M);
@@ -1989,6 +2085,7 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
         return fail("out of device memory (subsampled lengths)");
     if (e->cfg.model_kind == 1) return encode_full_squeezeformer(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
     if (e->cfg.model_kind == 2) return encode_full_efficient(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
+    if (is_wide(e)) return encode_full_wide(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
     const int d = e->cfg.d_model, H = e->cfg.heads, pad = e->cfg.cnn_kernel - 1;
     int Tq = 0;
     CHK(embed(e, s, feats_dev, B, T, &Tq));
@@ -2027,7 +2124,7 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
         } else {
             ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * B);
             launch_attention(e->attseq.as<AttSeq>(), B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v,
-                             (decoding_chunk_size > 0 && e->cfg.causal) ? decoding_chunk_size : 0, 1, s);   // use_dynamic_chunk only in the streaming build
+                             (decoding_chunk_size > 0 && e->cfg.causal) ? decoding_chunk_size : 0, 1, s, 256);   // use_dynamic_chunk only in the streaming build
         }
         if (few_rows) {
             // few row blocks (one utterance, a handful of short ones): latency-cut kernels of the chunk steps -- the row-block
@@ -2092,7 +2189,7 @@ int masr_ctc_greedy_frames(masr_engine* e, const float* enc_dev, int32_t M, int3
     if (!e || !e->finalized) return fail("engine not finalized");
     ENTER(e);
     CallGuard call_guard(e, (hipStream_t)stream);
-    if (e->cfg.model_kind == 3)      // K = 1024 / 2048 rows: generic GEMM + softmax statistics (logits stay in a workspace)
+    if (e->cfg.model_kind == 3 || is_wide(e))      // K = 512 / 1024 / 2048 rows: generic GEMM + softmax statistics (logits stay in a workspace)
         return ctc_head(e, enc_dev, M, nullptr, 0, argmax_dev, maxprob_dev, (hipStream_t)stream);
     // few row blocks (one utterance: 7; the Efficient Conformer's half-rate output at 32 x 10 s: 124): the fused head gives a
     // workgroup 32 rows x the WHOLE vocabulary (165 us whether 7 or 248 row blocks run); below knobs().ctc_fused_blocks the logits go
@@ -2804,7 +2901,7 @@ static int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector
             g.lnw = w.att_s; g.lnb = w.att_b; g.kv_seqs = seqs; g.kv_tq = Tq;
             rowgemm(e, s, RG_PRO_AFFINE, RG_EPI_STORE, g);
         }
-        launch_attention(seqs, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, reduced(l) ? 2 : 1, s);
+        launch_attention(seqs, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, reduced(l) ? 2 : 1, s, 256);
         {
             RowGemmArgs g = rg_args(e->att.as<float>(), d, w.wo, w.bo, x, d, M, d);
             g.R = x; g.ldr = d;
@@ -2963,7 +3060,7 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
             }
         } else {
             mhsa(e, s, w, M, seqs, Tq);                 // k | v rows go straight to the streams' caches
-            launch_attention(seqs, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, rate(l), s);
+            launch_attention(seqs, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, rate(l), s, 256);
             mhsa_out(e, s, w, M);
         }
         const int K = layer_kernel(e, l), pad = K - 1;
@@ -3043,7 +3140,9 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
     for (int i = 0; i < n; ++i)
         if (st[i]->offset + Tq > st[i]->cap) return fail("stream exceeds its max_frames_out / max_pos");
     const int M = n * Tq;
-    CHK(ensure_layer_ws(e, n, Tq));
+    const bool wide = is_wide(e);        // output_size 512: the same descriptors and caches, every layer as separate launches
+    if (wide && !wide_supported(d)) return fail("no kernels for output_size " + std::to_string(d));
+    CHK(wide ? ensure_wide_ws(e, n, Tq) : ensure_layer_ws(e, n, Tq));
     CHK(e->attseq.ensure(sizeof(AttSeq) * (size_t)n * L));
     // descriptors for all layers in one H2D copy
     std::vector<AttSeq> hs((size_t)n * L);
@@ -3081,10 +3180,15 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
     float* x = e->x.as<float>();
     EncodeCtx ctx{n, Tq, nullptr};
     for (int l = 0; l < L; ++l) {
+        if (wide) {
+            float* const* cp = e->cnnptrs.as<float*>() + (size_t)l * n;
+            CHK(wide_layer(e, s, e->layers[l], n, Tq, nullptr, e->attseq.as<AttSeq>() + (size_t)l * n, 0, cp, cp + (size_t)L * n));
+            continue;
+        }
         const LayerW& w = e->layers[knobs().hot_weights ? 0 : l];
         CHK(ffn(e, s, M, w.ln_ffm_w, w.ln_ffm_b, w.ffm_w1, w.ffm_b1, w.ffm_w2, w.ffm_b2));
         mhsa(e, s, w, M, e->attseq.as<AttSeq>() + (size_t)l * n, Tq);     // q -> qkv buffer, k|v rows -> the streams' caches
-        launch_attention(e->attseq.as<AttSeq>() + (size_t)l * n, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, 1, s);
+        launch_attention(e->attseq.as<AttSeq>() + (size_t)l * n, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, 1, s, 256);
         mhsa_out(e, s, w, M);
         float* const* cptr = e->cnnptrs.as<float*>() + (size_t)l * n;
         // [depthwise conv -> LN -> SiLU -> pointwise_conv2 + residual] rides on the second FFN launch as its head stage (on the
@@ -3097,7 +3201,8 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
                 nullptr, fuse ? &head : nullptr));
     }
     CHK(e->enc.ensure((size_t)M * d * sizeof(float)));
-    launch_layernorm(x, e->after_w, e->after_b, e->enc.as<float>(), M, 1e-5f, 0, 0, nullptr, s);
+    if (wide) WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, e->after_w, e->after_b, e->enc.as<float>(), M, d, 1e-5f, 0, 0, nullptr, s));
+    else launch_layernorm(x, e->after_w, e->after_b, e->enc.as<float>(), M, 1e-5f, 0, 0, nullptr, s);
     if (e->cfg.vocab_size > 16384) return fail("vocab_size > 16384 is not supported by the softmax / pruning kernels (one 256-thread workgroup holds a row in registers)");
     CHK(ctc_head(e, e->enc.as<float>(), M, probs_dev, probs_dev ? 1 : 0, argmax_dev, maxprob_dev, s));
     for (int i = 0; i < n; ++i) {

@@ -96,6 +96,20 @@ def _validate_encoder_conf(use_model, enc, state_dict):
         v = enc.get(key, default)
         if v not in allowed:
             raise _lib.MasrError(f'{use_model}: encoder_conf.{key}={v!r} is not implemented (supported: {allowed})')
+    if use_model != 'deepspeech2':
+        # model width (masr_create repeats these checks): 256 / 4 for every family; the Conformer also 512 / 8, on the width-generic
+        # path (csrc/wide.hip), which carries layer_norm and the conv2d input layer only
+        width_key = 'encoder_dim' if use_model == 'squeezeformer' else 'output_size'
+        pair = (enc.get(width_key, 256), enc.get('attention_heads', 4))
+        if pair != (256, 4) and not (use_model == 'conformer' and pair == (512, 8)):
+            raise _lib.MasrError(f'{use_model}: encoder_conf.{width_key} / attention_heads = {pair[0]!r} / {pair[1]!r} is not '
+                                 f'supported: 256 / 4 for every family, 512 / 8 for the conformer only')
+        if pair[0] == 512:
+            if enc.get('cnn_module_norm', 'layer_norm') == 'batch_norm':
+                raise _lib.MasrError('conformer: encoder_conf.cnn_module_norm=\'batch_norm\' is implemented at output_size 256 only')
+            if enc.get('input_layer', 'conv2d') != 'conv2d':
+                raise _lib.MasrError(f'conformer: encoder_conf.input_layer={enc.get("input_layer")!r} is implemented at output_size '
+                                     f'256 only (output_size 512 takes conv2d)')
     if use_model in ('conformer', 'efficient_conformer'):
         # batch_norm (conformer/convolution.py:60-67, eval-mode statistics folded into scale / shift): Conformer in the full-context
         # forward only, Efficient Conformer full-context and chunked.  An absent key means layer_norm here for both families (the
