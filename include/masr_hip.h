@@ -527,6 +527,19 @@ int masr_debug_set(masr_engine* e, int32_t key, int32_t value);
 int masr_debug_reset(masr_engine* e);
 int masr_debug_key_info(int32_t index, int32_t* key, int32_t* default_value, int32_t* experimental, const char** name);
 
+/* Which kernel of the fused FFN family one FFN call on m rows launches, and how (csrc/ffn_plan.h: the function the engine itself
+ * evaluates on the process's switches).  No engine and no GPU: the plan is computed on the DEFAULTS of the process-wide switches
+ * with n_overrides (key, value) pairs from overrides [2 * n_overrides] applied to a local copy -- the process's switches are neither
+ * read nor written, and experimental keys are accepted in every build.
+ *   ask [5]:  affine prologue (Squeezeformer) | weight rows of the tail stage, 0 = none | 1 = planar tail output | depthwise taps
+ *             of the head stage, 0 = none | head norm (0 LayerNorm, 1 folded BatchNorm)
+ *   plan [9]: kernel (0 split-bf16, 1 cooperative split, 2 two-chain, 3 16-row, 4 32-row) | nsplit | chunks of 128 hidden units
+ *             per slice | slices launched | packed weights | tail stage in the kernel | head stage in the kernel | head stage on
+ *             the d_ff-split launch | masr_profile_select kind of the launch (2, 6 with tail, 7 with head)
+ * Non-zero: d_ff no positive multiple of 128, m <= 0, an unknown key, a null argument. */
+int masr_ffn_plan(int32_t d_model, int32_t d_ff, int32_t m, const int32_t* ask, const int32_t* overrides, int32_t n_overrides,
+                  int32_t* plan);
+
 /* Profiling: time every launch of one kernel class with HIP events on the launch stream.
  * kind: 0 none, 1 gemm (all), 2 ffn-w1 gemm, 3 conv2 gemm, 4 attention, 5 fbank, 8 the step loop of a DeepSpeech2 recurrent
  * layer (one "launch" = the T' step launches of one layer); the row kernels of the d_model 512 path (csrc/wide.hip): 9 LayerNorm,

@@ -3,6 +3,7 @@
 The product path has NO CPU fallback: if the HIP library is missing or cannot be loaded this
 module raises, and so does everything that imports it.
 """
+import collections
 import contextlib
 import ctypes as C
 import os
@@ -118,6 +119,7 @@ SIGNATURES = {
     'masr_debug_set': [_P, _I, _I],
     'masr_debug_reset': [_P],
     'masr_debug_key_info': [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_char_p)],
+    'masr_ffn_plan': [_I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I)],
     'masr_mfma_order_probe': [_P, _P, _P, _P, _I, _P, _P],
     'masr_profile_select': [_P, _I],
     'masr_profile_read': [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), _I],
@@ -174,6 +176,20 @@ def debug_key_table():
     while lib().masr_debug_key_info(len(rows), C.byref(key), C.byref(default), C.byref(experimental), C.byref(name)) == 0:
         rows.append((key.value, name.value.decode(), default.value, bool(experimental.value)))
     return rows
+
+
+FFN_KERNELS = ('X3', 'COOP', 'DUAL', 'ROWS16', 'PC')      # FfnKernel of csrc/ffn_plan.h
+FfnPlan = collections.namedtuple('FfnPlan', 'kernel nsplit cpb ny packed tail_in_kernel head_in_kernel split_head prof')
+
+
+def ffn_plan(d_ff, M, keys=None, d_model=256, affine=0, tail_n=0, tail_planar=0, head_ktaps=0, head_norm=0):
+    """masr_ffn_plan: the launch plan of one FFN call on M rows under the switch defaults with ``keys`` {key number: value} on top
+    (no engine, no GPU, process state untouched); ``kernel`` comes back as its name"""
+    ask = (_I * 5)(affine, tail_n, tail_planar, head_ktaps, head_norm)
+    flat = [int(v) for kv in (keys or {}).items() for v in kv]
+    out = (_I * 9)()
+    check(lib().masr_ffn_plan(d_model, d_ff, M, ask, (_I * max(1, len(flat)))(*flat), len(flat) // 2, out))
+    return FfnPlan(FFN_KERNELS[out[0]], *out[1:])
 
 
 @contextlib.contextmanager

@@ -122,20 +122,19 @@ void launch_pack_conv2_rows(const float* w, float* p, int K, hipStream_t s);    
 bool gemm_conv2_rows(const GemmArgs& a);    // launch_gemm(a, A_CONV2, EPI_STD) runs conv2_rows_kernel (needs a.Wp)
 // deep-K, few-row GEMM: split K over workgroups into `partial` [nsplit][M][N], then reduce + epilogue into a.C
 void launch_gemm_splitk(const GemmArgs& a, float* partial, int nsplit, hipStream_t s, int amode = A_PLAIN);
+struct FfnArgs;
 // exploratory split-bf16 variant (gemm_bf16x3.hip; masr_debug_set key 20): standard epilogue only; false = not taken
 #if MASR_EXPERIMENTS
 bool launch_gemm_bf16x3(const GemmArgs& a, int amode, hipStream_t s);
 // fused split-bf16 FFN (ffn_x3.hip): weights packed once per FFN (hi / lo pieces in fragment order)
 size_t ffn_x3_packed_elems(int dff);
 void launch_pack_ffn_x3(const float* w1, const float* w2, unsigned short* p1, unsigned short* p2, int dff, hipStream_t s);
-bool launch_ffn_x3(float* x, const float* lnw, const float* lnb, const unsigned short* p1, const float* b1,
-                   const unsigned short* p2, const float* b2, int M, int dff, float eps, float scale, hipStream_t s);
+bool launch_ffn_x3(const FfnArgs& a, hipStream_t s);      // w1 / w2: the packed (hi, lo) bf16 copies; false = sizes not covered
 #else
 inline bool launch_gemm_bf16x3(const GemmArgs&, int, hipStream_t) { return false; }
 inline size_t ffn_x3_packed_elems(int) { return 0; }
 inline void launch_pack_ffn_x3(const float*, const float*, unsigned short*, unsigned short*, int, hipStream_t) {}
-inline bool launch_ffn_x3(float*, const float*, const float*, const unsigned short*, const float*, const unsigned short*, const float*,
-                          int, int, float, float, hipStream_t) { return false; }
+inline bool launch_ffn_x3(const FfnArgs&, hipStream_t) { return false; }
 #endif
 
 // ---- elementwise / reductions ------------------------------------------------------------
@@ -241,14 +240,13 @@ struct RowGemmArgs {
 bool launch_rowgemm(const RowGemmArgs& a, int pro, int epi, hipStream_t s);   // false: not applicable, nothing launched (HIST / DWCONV)
 bool launch_rowgemm_small(const RowGemmArgs& a, int pro, int epi, hipStream_t s);   // rowgemm_small.hip; false = not applicable
 
-// Fused FFN block, in place: x <- x + scale * (W2 . silu(W1 . LN(x) + b1) + b2)   (ffn_pc.hip; launched through launch_ffn_fused in ffn_reduce.hip)
-// partial/nsplit: split-d_ff mode for small M (streaming).  post: LayerNorm that follows the block in the layer; it is fused into
-// the split-mode reduction (return value 1), otherwise the caller runs it (return value 0)
+// Fused FFN block, in place: x <- x + scale * (W2 . silu(W1 . LN(x) + b1) + b2)   (ffn_pc.hip and its kin; FfnArgs below)
+// post: LayerNorm that follows the block in the layer; it is fused into the split-mode reduction of small M
 struct FfnPostLn {
     const float* lnw;
     const float* lnb;
-    float* y;          // destination rows (may alias x)
-    float eps;
+    float* y;          // destination rows (may alias x); nullptr: no LayerNorm behind the block
+    float eps = 1e-5f;
 };
 // tail: a row-local stage appended to the full (non-split) kernel: out[M, N] = LayerNorm(x_new; lnw, lnb) . W[N, 256]^T + bias
 // (the fused QKV projection that follows the first macaron FFN).  Return value 2 = done by the kernel.
@@ -288,15 +286,34 @@ struct FfnHead {
                                // until the split reduction, which then reads xout and writes x
     int norm;                  // 0 = LayerNorm, 1 = folded BatchNorm: y = silu(conv * lnw[c] + lnb[c]), no row statistics
 };
-int launch_ffn_fused(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2,
-                     const float* b2, int M, int dff, float eps, float scale, int affine_prologue, float* partial,
-                     int nsplit, hipStream_t s, const FfnPostLn* post = nullptr, const FfnTail* tail = nullptr,
-                     const FfnHead* head = nullptr, bool packed = false);
+// One FFN call, from ffn()'s call sites (engine.hip) to the launchers.  ffn_plan.h chooses the launcher; ffn() hands it the weights
+// in that kernel's order (w1 / w2, tail.W, head.W) and only the stages the kernel is to run
+struct FfnArgs {
+    float* x = nullptr;           // rows [M, 256], updated in place (ffn(): the engine's residual stream)
+    int M = 0, dff = 0;           // rows / hidden units (ffn(): the model's d_ff)
+    const float* lnw = nullptr;   // the block's LayerNorm (affine = 1: per-channel scale / bias instead, Squeezeformer)
+    const float* lnb = nullptr;
+    const float* w1 = nullptr;    // [dff, 256]
+    const float* b1 = nullptr;
+    const float* w2 = nullptr;    // [256, dff]
+    const float* b2 = nullptr;
+    float scale = 0.5f;           // x <- x + scale * block(x)
+    int affine = 0;
+    float eps = 1e-5f;
+    FfnPostLn post{};             // the LayerNorm that follows the block; y == nullptr: none
+    FfnTail tail{};               // W == nullptr: none
+    FfnHead head{};               // glu == nullptr: none
+    float* partial = nullptr;     // split mode: [nsplit][M][256] partial sums
+    int nsplit = 1;               //             d_ff slices wished for (1: the full kernel)
+    bool packed = false;          // w1 / w2 are launch_pack_ffn_pc's copies (launch_ffn_fused)
+};
+// the fused block (ffn_pc.hip through ffn_reduce.hip): returns 1 when the post LayerNorm was applied (split-d_ff path), 2 when the
+// tail stage ran, 4 when the head stage ran (| 1 on a split launch), 0 when the caller still has to run whichever it asked for
+int launch_ffn_fused(const FfnArgs& a, hipStream_t s);
 void launch_pack_ffn_pc(const float* w1, const float* w2, float* p1, float* p2, int dff, hipStream_t s);
 void launch_pack_rows_pc(const float* w, float* p, int N, hipStream_t s, int n_src = -1);   // weights [n_src, 256] -> N % 256 == 0 packed rows (rows >= n_src zero)
 // 16-row fused FFN stages (ffn_pc.hip ffn16_kernel, two workgroups per CU): full-d_ff launches only, packed weights of its own order
-int launch_ffn16(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2, const float* b2, int M,
-                 int dff, float eps, float scale, hipStream_t s, const FfnTail* tail, const FfnHead* head);
+int launch_ffn16(const FfnArgs& a, hipStream_t s);
 void launch_pack_ffn16(const float* w1, const float* w2, float* p1, float* p2, int dff, hipStream_t s);
 void launch_pack_rows16(const float* w, float* p, int N, hipStream_t s, int n_src = -1);
 // sqz_layer.hip: one Squeezeformer (post-LN) half-layer per launch on the workgroup's own 32 rows --
@@ -329,14 +346,11 @@ bool launch_sqz_stage(const SqzStageArgs& a, int stage, hipStream_t s);
 // launch_pack_ffn_dual, tail->W from launch_pack_rows_dual (N = 768), head->W from launch_pack_rows_pc.
 // Returns 0 / 2 (tail done) / 4 (head done), -1 when the sizes are not covered
 #if MASR_EXPERIMENTS
-int launch_ffn_dual(float* x, const float* lnw, const float* lnb, const float* p1, const float* b1, const float* p2,
-                    const float* b2, int M, int dff, float eps, float scale, int affine_prologue, hipStream_t s,
-                    const FfnTail* tail, const FfnHead* head);
+int launch_ffn_dual(const FfnArgs& a, hipStream_t s);
 void launch_pack_ffn_dual(const float* w1, const float* w2, float* p1, float* p2, int dff, hipStream_t s);
 void launch_pack_rows_dual(const float* w, float* p, hipStream_t s);
 #else
-inline int launch_ffn_dual(float*, const float*, const float*, const float*, const float*, const float*, const float*, int, int, float,
-                           float, int, hipStream_t, const FfnTail*, const FfnHead*) { return -1; }
+inline int launch_ffn_dual(const FfnArgs&, hipStream_t) { return -1; }
 inline void launch_pack_ffn_dual(const float*, const float*, float*, float*, int, hipStream_t) {}
 inline void launch_pack_rows_dual(const float*, float*, hipStream_t) {}
 #endif
@@ -345,15 +359,14 @@ inline void launch_pack_rows_dual(const float*, float*, hipStream_t) {}
 // ffn_pc.hip's packed W2, partial [dff / 128][M][256]
 #if MASR_EXPERIMENTS
 void launch_pack_ffn_coop_w1(const float* w1, float* p, int dff, hipStream_t s);
-void launch_ffn_coop(const float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2, int M,
-                     int dff, float eps, int affine, float* partial, hipStream_t s);
+void launch_ffn_coop(const FfnArgs& a, hipStream_t s);      // the caller runs the reduction
 #else
 inline void launch_pack_ffn_coop_w1(const float*, float*, int, hipStream_t) {}
-inline void launch_ffn_coop(const float*, const float*, const float*, const float*, const float*, const float*, int, int, float, int,
-                            float*, hipStream_t) {}
+inline void launch_ffn_coop(const FfnArgs&, hipStream_t) {}
 #endif
-void launch_ffn_reduce(float* x, const float* partial, const float* b2, int M, int nsplit, float scale, hipStream_t s,
-                       const FfnPostLn* post, const float* xin = nullptr);
+// x <- xin + scale * (sum of a.nsplit partial sums + b2), then a.post (xin: the rows a head stage of the split launch updated;
+// nullptr: x)
+void launch_ffn_reduce(const FfnArgs& a, hipStream_t s, const float* xin = nullptr);
 
 // Fragment-ordered weight copies, one layout per packing routine: the engine keeps every copy it has built under
 // (layout, device pointer of the source weights) -- engine.hip packed_of()

@@ -13,6 +13,7 @@
 
 #include "../../include/masr_hip.h"
 #include "common.h"
+#include "ffn_plan.h"
 
 using namespace masr;
 namespace masr {
@@ -966,144 +967,149 @@ struct EncodeCtx {
     const int* lens; // device feature lengths for pad masking, or nullptr (streaming)
 };
 
-// post_*: the LayerNorm that follows the block (y <- LayerNorm(x), y may be x); fused into the split-mode reduction of small M
-// tail / tail_done: a row-local stage to run on the finished rows inside the same kernel (fused QKV projection, ffn_pc.hip TAIL);
-// *tail_done = true when the kernel did it, otherwise the caller launches it
-int ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb, const float* w1, const float* b1,
-        const float* w2, const float* b2, float scale = 0.5f, int affine = 0, const float* post_w = nullptr,
-        const float* post_b = nullptr, float* post_y = nullptr, const FfnTail* tail = nullptr, bool* tail_done = nullptr,
-        const FfnHead* head = nullptr, bool* head_done = nullptr) {
-    const int d = e->cfg.d_model, dff = e->cfg.d_ff;
-    // few rows (streaming chunk steps): split d_ff across workgroups so that >= ~128 CUs work on the block
-    int nsplit = 1;
-    const int rowblocks = (M + 31) / 32;
-    const FfnPostLn post{post_w, post_b, post_y, 1e-5f};
-    if (rowblocks < knobs().ffn_split_blocks) {
-        nsplit = std::min(dff / 128, std::max(1, (rowblocks < 64 ? 128 : 256) / rowblocks));
-        CHK(e->ffpart.ensure((size_t)nsplit * M * d * sizeof(float)));
-    }
-    // exploratory, bit 2 of key 20: the fused split-bf16 FFN (ffn_x3.hip).  (An unfused version -- LayerNorm, then two split-bf16
-    // GEMMs with the hidden tensor in HBM -- measured 44 + 82 + 6 us against the 144 us of the fused exact-fp32 kernel at
-    // B = 32 x 10 s: the 65 MB round trip of the hidden tensor ate what the bf16 pipe saved.)
-    const bool x3 = (knobs().bf16x3 & 2) && nsplit == 1 && !affine && d == 256 && dff % 128 == 0;
-    const bool want_tail = tail && nsplit == 1 && !knobs().no_ffn_tail && !x3;
-    // (few rows: the head stage rides on the d_ff-split launch, every slice repeating it on the row block's rows -- key 30)
-    const bool split_head = head && head->glu && nsplit > 1 && knobs().split_head && !affine && !x3 && head->ktaps == 15 && d == 256 &&
-                            knobs().ffn_packed >= 2;
-    const bool want_head = head && head->glu && ((nsplit == 1 && !want_tail && !knobs().no_ffn_head && !affine && !x3 &&
-                                                  (head->ktaps == 15 || head->ktaps == 7)) || split_head);
-    if (head_done) *head_done = want_head;
-    if (head && head->glu && !want_head) {
+// the FFNs of a layer as ffn() calls on M rows: a call site adds what it wants beside the block (post, tail, head)
+FfnArgs ffn_of(int M, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2, const float* b2) {
+    FfnArgs a;
+    a.M = M; a.lnw = lnw; a.lnb = lnb; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
+    return a;
+}
+FfnArgs ffn_macaron(const LayerW& w, int M) { return ffn_of(M, w.ln_ffm_w, w.ln_ffm_b, w.ffm_w1, w.ffm_b1, w.ffm_w2, w.ffm_b2); }
+// (y: where the layer's norm_final goes when it rides on this call -- a.post; nullptr: the caller runs or defers it)
+FfnArgs ffn_final(const LayerW& w, int M, float* y = nullptr) {
+    FfnArgs a = ffn_of(M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2);
+    a.post = {w.ln_fin_w, w.ln_fin_b, y};
+    return a;
+}
+// Squeezeformer (post-LN): adaptive scale / bias in front of the block, the whole block added, `post` = the LayerNorm behind it
+FfnArgs ffn_sqz(int M, const float* s, const float* b, const float* w1, const float* b1, const float* w2, const float* b2,
+                const float* post_w, const float* post_b, float* post_y) {
+    FfnArgs a = ffn_of(M, s, b, w1, b1, w2, b2);
+    a.scale = 1.0f; a.affine = 1; a.post = {post_w, post_b, post_y};
+    return a;
+}
+FfnArgs ffn_sqz1(const SqLayerW& w, int M, float* y) { return ffn_sqz(M, w.f1_s, w.f1_b, w.f1_w1, w.f1_b1, w.f1_w2, w.f1_b2, w.ln2_w, w.ln2_b, y); }
+FfnArgs ffn_sqz2(const SqLayerW& w, int M, float* y) { return ffn_sqz(M, w.f2_s, w.f2_b, w.f2_w1, w.f2_b1, w.f2_w2, w.f2_b2, w.ln4_w, w.ln4_b, y); }
+// tail stage of a layer's first FFN: the attention block's LayerNorm + fused QKV projection into out [M, ldo]
+FfnTail qkv_tail(const masr_engine* e, const LayerW& w, float* out, int ldo) {
+    FfnTail t{};
+    t.lnw = w.ln_mha_w; t.lnb = w.ln_mha_b; t.W = w.wqkv; t.bias = w.bqkv; t.out = out; t.N = 3 * e->cfg.d_model; t.ldo = ldo;
+    return t;
+}
+// head stage of a layer's second FFN: the conv module behind pointwise_conv1 + GLU, on the offline GLU buffer (whose causal
+// history rows are the constant glu(bias), not materialised)
+FfnHead conv_head(const masr_engine* e, const LayerW& w, const int* lens, int Tq, int ktaps, int mstride) {
+    FfnHead h{};
+    h.glu = e->glu.as<float>(); h.dw_w = w.dw_w; h.dw_b = w.dw_b; h.lnw = w.cln_w; h.lnb = w.cln_b;
+    h.gconst = e->cfg.causal ? w.gconst : nullptr; h.W = w.pw2_w; h.bias = w.pw2_b;
+    h.lens = lens; h.seq_t = Tq; h.ktaps = ktaps; h.mstride = mstride; h.norm = e->conv_bn ? 1 : 0;
+    return h;
+}
+
+// what ffn() did with the stages asked for; as an int: the error code (0 = launched)
+struct FfnDone {
+    int err;
+    bool tail_done = false;   // the kernel ran the tail stage; otherwise the caller launches it
+    bool head_done = false;   // the kernel ran the head stage; otherwise ffn() has launched it in front of the block
+    FfnDone(int err_ = 0) : err(err_) {}
+    operator int() const { return err; }
+};
+
+// The fused FFN block on the engine's residual stream e->x (a.x and a.dff are filled in here).  ffn_plan.h chooses the kernel;
+// a.post: fused into the split-mode reduction of small M, otherwise launched behind the block; a.tail (fused QKV projection,
+// ffn_pc.hip TAIL): see FfnDone; a.head: the kernel's head stage or two launches of its own in front of the block
+FfnDone ffn(masr_engine* e, hipStream_t s, FfnArgs a) {
+    const int d = e->cfg.d_model, M = a.M;
+    float* x = a.x = e->x.as<float>();
+    a.dff = e->cfg.d_ff;
+    const FfnTail tail = a.tail;          // as asked for: a.tail / a.head become what the kernel is to run, with W in its order
+    const FfnHead head = a.head;
+    const FfnPlan plan = ffn_plan(knobs(), d, a.dff, M, {a.affine, tail.W ? tail.N : 0, tail.plane_stride > 0, head.glu ? head.ktaps : 0, head.norm});
+    if (!plan.tail_in_kernel) a.tail = FfnTail{};
+    if (!plan.head_in_kernel) a.head = FfnHead{};
+    if (head.glu && !plan.head_in_kernel) {
         // the rest of the conv module as its own two launches: depthwise conv + LayerNorm + SiLU, pointwise_conv2 + mask + residual
         CHK(e->dwo.ensure((size_t)M * d * sizeof(float)));
-        if (head->norm == 1)
-            launch_dwconv_bn_silu(head->glu, head->dw_w, head->dw_b, head->lnw, head->lnb, e->dwo.as<float>(), M / head->seq_t,
-                                  head->seq_t, head->ktaps, s, head->gconst);
+        if (head.norm == 1)
+            launch_dwconv_bn_silu(head.glu, head.dw_w, head.dw_b, head.lnw, head.lnb, e->dwo.as<float>(), M / head.seq_t, head.seq_t,
+                                  head.ktaps, s, head.gconst);
         else
-            launch_dwconv_ln_silu(head->glu, head->dw_w, head->dw_b, head->lnw, head->lnb, e->dwo.as<float>(), M / head->seq_t,
-                                  head->seq_t, head->ktaps, 1e-5f, s, head->gconst);
-        float* x = e->x.as<float>();
-        {
-            RowGemmArgs g = rg_args(e->dwo.as<float>(), d, head->W, head->bias, x, d, M, d);
-            g.R = x; g.ldr = d; g.lens = head->lens; g.mask_tp = head->lens ? head->seq_t : 0; g.mstride = head->mstride;
-            rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
-        }
+            launch_dwconv_ln_silu(head.glu, head.dw_w, head.dw_b, head.lnw, head.lnb, e->dwo.as<float>(), M / head.seq_t, head.seq_t,
+                                  head.ktaps, 1e-5f, s, head.gconst);
+        RowGemmArgs g = rg_args(e->dwo.as<float>(), d, head.W, head.bias, x, d, M, d);
+        g.R = x; g.ldr = d; g.lens = head.lens; g.mask_tp = head.lens ? head.seq_t : 0; g.mstride = head.mstride;
+        rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
     }
-    if (tail && tail->pre_lnw && !want_tail)          // the deferred LayerNorm of the previous layer, as its own launch
-        launch_layernorm(e->x.as<float>(), tail->pre_lnw, tail->pre_lnb, e->x.as<float>(), M, 1e-5f, 0, 0, nullptr, s);
-    float* x = e->x.as<float>();
-    if (x3) {
-        // packed (hi, lo) weights of this FFN: + 4 MB per FFN
-        const size_t bytes = ffn_x3_packed_elems(dff) * sizeof(unsigned short);
+    if (tail.W && tail.pre_lnw && !plan.tail_in_kernel)          // the deferred LayerNorm of the previous layer, as its own launch
+        launch_layernorm(x, tail.pre_lnw, tail.pre_lnb, x, M, 1e-5f, 0, 0, nullptr, s);
+    if (plan.nsplit > 1) {
+        CHK(e->ffpart.ensure((size_t)plan.nsplit * M * d * sizeof(float)));
+        a.partial = e->ffpart.as<float>(); a.nsplit = plan.nsplit;
+    }
+    if (plan.split_head) {
+        CHK(e->xh.ensure((size_t)M * d * sizeof(float)));
+        a.head.xout = e->xh.as<float>();
+    }
+    ProfScope ps(e, s, plan.prof, 4.0 * M * (double)a.dff * d + (plan.tail_in_kernel ? 2.0 * M * (double)tail.N * d : 0.0) +
+                                      (plan.head_in_kernel ? 2.0 * M * (double)d * d : 0.0));
+    // each kernel reads fragment-ordered copies of its own (built on first use, + 4 MB per FFN), and so do the row-local stages
+    // that ride on the launch.  done: what the launcher says it ran -- 1 the post LayerNorm (split reduction), 2 the tail, 4 the head
+    int done = 0;
+    switch (plan.kernel) {
+    case FFN_X3: {
+        const size_t bytes = ffn_x3_packed_elems(a.dff) * sizeof(unsigned short);      // (hi, lo) pieces
+        const float *w1 = a.w1, *w2 = a.w2;
         const PackedW* pk = packed_of(e, PACK_FFN_X3, w1, bytes, bytes, s, [&](const PackedW& p, hipStream_t st) {
-            launch_pack_ffn_x3(w1, w2, p.a.as<unsigned short>(), p.b.as<unsigned short>(), dff, st);
+            launch_pack_ffn_x3(w1, w2, p.a.as<unsigned short>(), p.b.as<unsigned short>(), a.dff, st);
         });
         if (!pk) return 1;
-        {
-            ProfScope ps(e, s, PROF_FFN1, 4.0 * M * (double)dff * d);
-            if (!launch_ffn_x3(x, lnw, lnb, pk->a.as<unsigned short>(), b1, pk->b.as<unsigned short>(), b2, M, dff, 1e-5f, scale, s))
-                return fail("ffn(): the split-bf16 FFN kernel rejected the sizes");
-        }
-        if (tail_done) *tail_done = false;
-        if (post_y) launch_layernorm(x, post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
-        return 0;
+        a.w1 = pk->a.as<float>(); a.w2 = pk->b.as<float>();
+        if (!launch_ffn_x3(a, s)) return fail("ffn(): the split-bf16 FFN kernel rejected the sizes");
+        break;
     }
-    const float *kw1 = w1, *kw2 = w2;
-    // few rows, one chunk of 128 hidden units per workgroup: the kernel in which all eight waves work on both products (key 35)
-    if (knobs().ffn_coop && nsplit > 1 && nsplit == dff / 128 && !want_head && !x3 && d == 256) {
-        // packed copies: ffn_pc.hip's (W2 is shared with it) + the 16 x 16 x 4 fragment order of W1
-        CHK(packed_ffn_of(e, w1, w2, s, &kw1, &kw2));
-        const PackedW* pc = packed_of(e, PACK_FFN_COOP_W1, w1, (size_t)dff * d * sizeof(float), 0, s,
-                                      [&](const PackedW& p, hipStream_t st) { launch_pack_ffn_coop_w1(w1, p.a.as<float>(), dff, st); });
+    case FFN_COOP: {
+        // ffn_pc.hip's copies (W2 is shared with it) + the 16 x 16 x 4 fragment order of W1
+        const float* w1 = a.w1;
+        CHK(packed_ffn_of(e, w1, a.w2, s, &a.w1, &a.w2));
+        const PackedW* pc = packed_of(e, PACK_FFN_COOP_W1, w1, (size_t)a.dff * d * sizeof(float), 0, s,
+                                      [&](const PackedW& p, hipStream_t st) { launch_pack_ffn_coop_w1(w1, p.a.as<float>(), a.dff, st); });
         if (!pc) return 1;
-        ProfScope psc(e, s, PROF_FFN1, 4.0 * M * (double)dff * d);
-        launch_ffn_coop(x, lnw, lnb, pc->a.as<float>(), b1, kw2, M, dff, 1e-5f, affine, e->ffpart.as<float>(), s);
-        launch_ffn_reduce(x, e->ffpart.as<float>(), b2, M, nsplit, scale, s, post_y ? &post : nullptr);
-        if (tail_done) *tail_done = false;
-        return 0;
+        a.w1 = pc->a.as<float>();
+        launch_ffn_coop(a, s);
+        launch_ffn_reduce(a, s);
+        done = 1;
+        break;
     }
-    ProfScope ps(e, s, want_tail ? PROF_FFN_TAIL : want_head ? PROF_FFN_HEAD : PROF_FFN1,
-                 4.0 * M * (double)dff * d + (want_tail ? 2.0 * M * (double)tail->N * d : 0.0) + (want_head ? 2.0 * M * (double)d * d : 0.0));
-    // full launches stream PACKED weight copies straight into registers (ffn_pc.hip VAR == 2; built on first use, + 4 MB per FFN)
-    const bool packed = knobs().ffn_packed && (nsplit == 1 || knobs().ffn_packed >= 2) && d == 256;      // (key 23 = 2: the d_ff-split launches of small M too)
-    // 16-row blocks, two workgroups per CU (ffn_pc.hip ffn16_kernel): every full-d_ff launch of packed weights it covers; it reads
-    // copies of its own order, so the 32-row copies are not built for it
-    const bool use16 = packed && nsplit == 1 && knobs().ffn16 && !affine && dff % 128 == 0 && !(want_tail && tail->N % 256) &&
-                       !(want_head && head->ktaps != 15 && head->ktaps != 7);
-    if (packed && !use16) CHK(packed_ffn_of(e, w1, w2, s, &kw1, &kw2));
-    // ... and so do the row-local stages that ride on the launch (QKV tail, pointwise_conv2 head): copies of the stage descriptors
-    // whose W is the packed copy in the chosen kernel's order
-    FfnTail ptail = tail ? *tail : FfnTail{};
-    FfnHead phead = head ? *head : FfnHead{};
-    // two accumulator chains per wave (ffn_dual.hip): same arithmetic in the same order, its own packing order
-    if (packed && nsplit == 1 && knobs().ffn_dual && dff % 256 == 0 && dff >= 512 && !(want_tail && tail->N != 768) && !(affine && (want_tail || want_head)) &&
-        !(want_head && head->norm)) {      // (the two-chain kernel's head stage carries the LayerNorm variant only)
-        const float *p1, *p2;
-        CHK(packed_ffn_of(e, w1, w2, s, &p1, &p2, PACK_FFN_DUAL, launch_pack_ffn_dual));
-        if (want_tail) {
-            const PackedW* tw = packed_of(e, PACK_ROWS_DUAL, tail->W, (size_t)768 * d * sizeof(float), 0, s,
-                                          [&](const PackedW& p, hipStream_t st) { launch_pack_rows_dual(tail->W, p.a.as<float>(), st); });
+    case FFN_DUAL:
+        CHK(packed_ffn_of(e, a.w1, a.w2, s, &a.w1, &a.w2, PACK_FFN_DUAL, launch_pack_ffn_dual));
+        if (plan.tail_in_kernel) {
+            const PackedW* tw = packed_of(e, PACK_ROWS_DUAL, tail.W, (size_t)768 * d * sizeof(float), 0, s,
+                                          [&](const PackedW& p, hipStream_t st) { launch_pack_rows_dual(tail.W, p.a.as<float>(), st); });
             if (!tw) return 1;
-            ptail.W = tw->a.as<float>();
+            a.tail.W = tw->a.as<float>();
         }
-        if (want_head && !(phead.W = packed_rows_of(e, head->W, d, s))) return 1;
-        const int done = launch_ffn_dual(x, lnw, lnb, p1, b1, p2, b2, M, dff, 1e-5f, scale, affine, s, want_tail ? &ptail : nullptr,
-                                         want_head ? &phead : nullptr);
-        if (done < 0) return fail("ffn(): the two-chain FFN kernel rejected the launch");
-        if (want_head && done != 4) return fail("ffn(): head stage was not launched");
-        if (tail_done) *tail_done = done == 2;
-        if (post_y) launch_layernorm(x, post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
-        return 0;
-    }
-    if (use16) {
-        const float *p1, *p2;
-        CHK(packed_ffn_of(e, w1, w2, s, &p1, &p2, PACK_FFN16, launch_pack_ffn16));
-        if (want_tail && !(ptail.W = packed_rows_of(e, tail->W, tail->N, s, PACK_ROWS16))) return 1;
-        if (want_head && !(phead.W = packed_rows_of(e, head->W, d, s, PACK_ROWS16))) return 1;
-        const int done = launch_ffn16(x, lnw, lnb, p1, b1, p2, b2, M, dff, 1e-5f, scale, s, want_tail ? &ptail : nullptr,
-                                      want_head ? &phead : nullptr);
-        if (done < 0) return fail("ffn(): the 16-row FFN kernel rejected the launch");
-        if (want_head && done != 4) return fail("ffn(): head stage was not launched");
-        if (tail_done) *tail_done = done == 2;
-        if (post_y) launch_layernorm(x, post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
-        return 0;
-    }
-    if (packed && want_tail && tail->N % 256 == 0 && !(ptail.W = packed_rows_of(e, tail->W, tail->N, s))) return 1;
-    if (packed && want_head) {
-        if (!(phead.W = packed_rows_of(e, head->W, d, s))) return 1;
-        if (split_head) {
-            CHK(e->xh.ensure((size_t)M * d * sizeof(float)));
-            phead.xout = e->xh.as<float>();
+        if (plan.head_in_kernel && !(a.head.W = packed_rows_of(e, head.W, d, s))) return 1;
+        if ((done = launch_ffn_dual(a, s)) < 0) return fail("ffn(): the two-chain FFN kernel rejected the launch");
+        break;
+    case FFN_ROWS16:
+        CHK(packed_ffn_of(e, a.w1, a.w2, s, &a.w1, &a.w2, PACK_FFN16, launch_pack_ffn16));
+        if (plan.tail_in_kernel && !(a.tail.W = packed_rows_of(e, tail.W, tail.N, s, PACK_ROWS16))) return 1;
+        if (plan.head_in_kernel && !(a.head.W = packed_rows_of(e, head.W, d, s, PACK_ROWS16))) return 1;
+        if ((done = launch_ffn16(a, s)) < 0) return fail("ffn(): the 16-row FFN kernel rejected the launch");
+        break;
+    case FFN_PC:
+        if ((a.packed = plan.packed)) {
+            CHK(packed_ffn_of(e, a.w1, a.w2, s, &a.w1, &a.w2));
+            if (plan.tail_in_kernel && tail.N % 256 == 0 && !(a.tail.W = packed_rows_of(e, tail.W, tail.N, s))) return 1;
+            if (plan.head_in_kernel && !(a.head.W = packed_rows_of(e, head.W, d, s))) return 1;
         }
+        if ((done = launch_ffn_fused(a, s)) < 0) return fail("ffn(): launch rejected");
+        break;
     }
-    const int done = launch_ffn_fused(x, lnw, lnb, kw1, b1, kw2, b2, M, dff, 1e-5f, scale, affine,
-                                      nsplit > 1 ? e->ffpart.as<float>() : nullptr, nsplit, s, post_y ? &post : nullptr,
-                                      want_tail ? &ptail : nullptr, want_head ? &phead : nullptr, packed);
-    if (done < 0) return fail("ffn(): launch rejected");
-    if (want_head && !(done & 4)) return fail("ffn(): head stage was not launched");
-    if (tail_done) *tail_done = done == 2;
-    if (post_y && !(done & 1)) launch_layernorm(x, post_w, post_b, post_y, M, 1e-5f, 0, 0, nullptr, s);
-    return 0;
+    if (plan.head_in_kernel && !(done & 4)) return fail("ffn(): head stage was not launched");
+    if (a.post.y && !(done & 1)) launch_layernorm(x, a.post.lnw, a.post.lnb, a.post.y, M, 1e-5f, 0, 0, nullptr, s);
+    FfnDone r;
+    r.tail_done = done == 2; r.head_done = plan.head_in_kernel;
+    return r;
 }
 
 // W [N = 256, K] in the row-block kernel's fragment order (gemm_f32.hip conv2_rows_kernel): the subsampling convs and the embed projection
@@ -1747,9 +1753,9 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
             rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
         }
         launch_layernorm(x, w.ln1_w, w.ln1_b, x, M, 1e-5f, 0, 0, nullptr, s);
-        // x = LN2(x + FFN1(ada(x)))   (the post-LayerNorm rides on the d_ff-split reduction where the block runs split: few row
-        // blocks, i.e. exactly the launches that take this branch by default; otherwise ffn() launches it)
-        CHK(ffn(e, s, M, w.f1_s, w.f1_b, w.f1_w1, w.f1_b1, w.f1_w2, w.f1_b2, 1.0f, 1, w.ln2_w, w.ln2_b, x));
+        // x = LN2(x + FFN1(ada(x)))   (the post-LayerNorm rides on the d_ff-split reduction where ffn_plan.h runs the block split;
+        // otherwise ffn() launches it)
+        CHK(ffn(e, s, ffn_sqz1(w, M, x)));
         // x = LN3(x + Conv(ada(x)))   symmetric depthwise conv: (K-1)/2 zero rows on both sides of the GLU output
         {
             RowGemmArgs g = rg_args(x, d, w.pw1_w, w.pw1_b, e->glu.as<float>(), d, M, 2 * d);
@@ -1766,7 +1772,7 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
         }
         launch_layernorm(x, w.ln3_w, w.ln3_b, x, M, 1e-5f, 0, 0, nullptr, s);
         // x = LN4(x + FFN2(ada(x)))
-        CHK(ffn(e, s, M, w.f2_s, w.f2_b, w.f2_w1, w.f2_b1, w.f2_w2, w.f2_b2, 1.0f, 1, w.ln4_w, w.ln4_b, i == L - 1 ? enc_out : x));
+        CHK(ffn(e, s, ffn_sqz2(w, M, i == L - 1 ? enc_out : x)));
     }
     LAUNCHCHK();
     return 0;
@@ -1809,21 +1815,24 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
         const int Ki = layer_kernel(e, i);
         // enough row blocks for the full (non d_ff-split) FFN launch: the Conformer's fused launches (key 31 = 0: separate ones)
         const bool fused = knobs().efficient_fused && !knobs().no_chain && !knobs().no_ffn_head && i != e->stride_idx &&
-                           (M + 31) / 32 >= knobs().ffn_split_blocks && (Ki == 15 || Ki == 7) && d == 256;
+                           ffn_full_row_blocks(knobs(), M) && (Ki == 15 || Ki == 7) && d == 256;
         const EncodeCtx ctx0{B, Tq, lens};
         // regular layers: LayerNorm + fused QKV projection ride on the first FFN kernel (tail stage), like the Conformer
-        const FfnTail tail{w.ln_mha_w, w.ln_mha_b, w.wqkv, w.bqkv, e->qkv.as<float>(), 3 * d, 3 * d, nullptr, nullptr};
-        bool qkv_done = false;
-        // grouped layers: the same tail stage writes q | k | v PLANAR into the time-padded buffers of the grouped attention
-        // (round 4; ffn_pc.hip only -- the two-chain kernel keeps the separate projection)
-        const FfnTail gtail{w.ln_mha_w, w.ln_mha_b, w.wqkv, w.bqkv, qp, 3 * d, d, nullptr, nullptr, (long)plane, Tq, Tpad - Tq};
-        const bool planar_tail = layer_grouped(e, i) && knobs().efficient_fused && !knobs().ffn_dual;
-        CHK(ffn(e, s, M, w.ln_ffm_w, w.ln_ffm_b, w.ffm_w1, w.ffm_b1, w.ffm_w2, w.ffm_b2, 0.5f, 0, nullptr, nullptr, nullptr,
-                layer_grouped(e, i) ? (planar_tail ? &gtail : nullptr) : &tail, &qkv_done));
+        FfnArgs f1 = ffn_macaron(w, M);
+        if (!layer_grouped(e, i)) {
+            f1.tail = qkv_tail(e, w, e->qkv.as<float>(), 3 * d);
+        } else if (knobs().efficient_fused) {
+            // grouped layers: the same tail stage writes q | k | v PLANAR into the time-padded buffers of the grouped attention
+            // (round 4; ffn_pc.hip only -- ffn_plan.h keeps the separate projection where the two-chain kernel is switched on)
+            f1.tail = qkv_tail(e, w, qp, d);
+            f1.tail.plane_stride = (long)plane; f1.tail.seq_t = Tq; f1.tail.pad_t = Tpad - Tq;
+        }
+        const FfnDone r1 = ffn(e, s, f1);
+        CHK(r1);
         if (layer_grouped(e, i)) {
             if (Tq != T0) return fail("grouped attention after the stride layer is not supported");
             // q | k | v -> planar, time-padded buffers; attention over T/3 positions with d_k' = 192
-            if (!qkv_done)
+            if (!r1.tail_done)
                 {
                     RowGemmArgs g = rg_args(x, d, w.wqkv, w.bqkv, qp, d, M, 3 * d);
                     g.lnw = w.ln_mha_w; g.lnb = w.ln_mha_b; g.mstride = mstride; g.out_seq_t = Tq; g.out_pad_tot = Tpad - Tq;
@@ -1842,7 +1851,7 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
                     rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
                 }
         } else {
-            if (!qkv_done) mhsa(e, s, w, M);
+            if (!r1.tail_done) mhsa(e, s, w, M);
             {
                 ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * B);
                 launch_attention(seq_r, B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, pstride, s, 256);
@@ -1854,10 +1863,9 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
         if (fused) {
             // like the offline Conformer layer: [out-proj + residual -> LN -> pw1 -> GLU] was one kernel; the rest of the conv
             // module is the head stage of the second FFN launch (15 taps before, 7 behind the stride layer)
-            const FfnHead head{e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, causal ? w.gconst : nullptr,
-                               w.pw2_w, w.pw2_b, lens, Tq, Ki, mstride, nullptr, e->conv_bn ? 1 : 0};
-            CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2, 0.5f, 0, nullptr, nullptr, nullptr, nullptr,
-                    nullptr, &head));
+            FfnArgs f2 = ffn_final(w, M);
+            f2.head = conv_head(e, w, lens, Tq, Ki, mstride);
+            CHK(ffn(e, s, f2));
             launch_layernorm(x, w.ln_fin_w, w.ln_fin_b, x, M, 1e-5f, 0, 0, nullptr, s);
             continue;
         }
@@ -1895,7 +1903,7 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
         } else {
             CHK(conv_module(e, s, w, ctx, false, layer_kernel(e, i), mstride));
         }
-        CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2));
+        CHK(ffn(e, s, ffn_final(w, M)));
         launch_layernorm(x, w.ln_fin_w, w.ln_fin_b, x, M, 1e-5f, 0, 0, nullptr, s);
     }
     launch_layernorm(x, e->after_w, e->after_b, enc_out, B * Tq, 1e-5f, 0, 0, nullptr, s);
@@ -2099,15 +2107,15 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
     if (!e->cfg.causal)     // symmetric conv: the (K-1)/2 pad rows on both sides of every sequence stay zero for all layers
         HIPCHK(hipMemsetAsync(e->glu.p, 0, (size_t)B * (Tq + pad) * d * sizeof(float), s));
     const LayerW* prev = nullptr;                 // layer whose norm_final is still pending (it rides on the next FFN launch)
-    const bool few_rows = knobs().few_rows_path && (M + 31) / 32 < std::min(knobs().rowgemm_small_blocks, knobs().ffn_split_blocks);
+    const bool few_rows = few_row_blocks(knobs(), M);
     for (const LayerW& w : e->layers) {
         // first macaron FFN with the attention block's LayerNorm + fused QKV projection as its tail stage (full kernel only)
-        const FfnTail tail{w.ln_mha_w, w.ln_mha_b, w.wqkv, w.bqkv, e->qkv.as<float>(), 3 * d, 3 * d,
-                           prev ? prev->ln_fin_w : nullptr, prev ? prev->ln_fin_b : nullptr};
-        bool qkv_done = false;
-        CHK(ffn(e, s, M, w.ln_ffm_w, w.ln_ffm_b, w.ffm_w1, w.ffm_b1, w.ffm_w2, w.ffm_b2, 0.5f, 0, nullptr, nullptr, nullptr, &tail,
-                &qkv_done));
-        if (!qkv_done) mhsa(e, s, w, M);
+        FfnArgs f1 = ffn_macaron(w, M);
+        f1.tail = qkv_tail(e, w, e->qkv.as<float>(), 3 * d);
+        if (prev) { f1.tail.pre_lnw = prev->ln_fin_w; f1.tail.pre_lnb = prev->ln_fin_b; }
+        const FfnDone r1 = ffn(e, s, f1);
+        CHK(r1);
+        if (!r1.tail_done) mhsa(e, s, w, M);
         // attention and the chain kernel behind it as ONE launch (32 queries x all four heads per workgroup; key 34 = 0: two launches)
         const bool fuse_ac = knobs().attn_chain && !few_rows && !knobs().no_chain && H == 4 && d == 256 && knobs().rowgemm_packed;
         if (fuse_ac) {
@@ -2134,23 +2142,21 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
             mhsa_out(e, s, w, M);
             const bool fuse = knobs().split_head && e->cfg.cnn_kernel == 15 && knobs().ffn_packed >= 2 && !knobs().no_ffn_head;
             CHK(conv_module(e, s, w, ctx, false, 0, 4, false, fuse));
-            const FfnHead head{e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->cfg.causal ? w.gconst : nullptr,
-                               w.pw2_w, w.pw2_b, feat_lens_dev, Tq, e->cfg.cnn_kernel, 4, nullptr, e->conv_bn ? 1 : 0};
-            CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2, 0.5f, 0, w.ln_fin_w, w.ln_fin_b, x, nullptr,
-                    nullptr, fuse ? &head : nullptr));
+            FfnArgs f2 = ffn_final(w, M, x);
+            if (fuse) f2.head = conv_head(e, w, feat_lens_dev, Tq, e->cfg.cnn_kernel, 4);
+            CHK(ffn(e, s, f2));
             continue;                              // (prev stays null: nothing deferred)
         } else if (knobs().no_chain) {
             mhsa_out(e, s, w, M);
             CHK(conv_module(e, s, w, ctx, false));
-            CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2));
+            CHK(ffn(e, s, ffn_final(w, M)));
         } else {
             // out-projection + residual + LayerNorm + pointwise_conv1 + GLU in one kernel; the rest of the conv module
             // (depthwise conv, LayerNorm or folded BatchNorm, SiLU, pointwise_conv2, residual) is the head stage of the second FFN kernel
             if (!fuse_ac) mhsa_out_pw1(e, s, w, ctx);
-            const FfnHead head{e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->cfg.causal ? w.gconst : nullptr,
-                               w.pw2_w, w.pw2_b, feat_lens_dev, Tq, e->cfg.cnn_kernel, 4, nullptr, e->conv_bn ? 1 : 0};
-            CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2, 0.5f, 0, nullptr, nullptr, nullptr, nullptr,
-                    nullptr, &head));
+            FfnArgs f2 = ffn_final(w, M);
+            f2.head = conv_head(e, w, feat_lens_dev, Tq, e->cfg.cnn_kernel, 4);
+            CHK(ffn(e, s, f2));
         }
         prev = &w;                                 // norm_final deferred to the next layer's first FFN launch
     }
@@ -2908,7 +2914,7 @@ static int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector
             rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
         }
         launch_layernorm(x, w.ln1_w, w.ln1_b, x, M, 1e-5f, 0, 0, nullptr, s);
-        CHK(ffn(e, s, M, w.f1_s, w.f1_b, w.f1_w1, w.f1_b1, w.f1_w2, w.f1_b2, 1.0f, 1, w.ln2_w, w.ln2_b, x));
+        CHK(ffn(e, s, ffn_sqz1(w, M, x)));
         // conv module: [cnn cache | ada(x)] -> pointwise_conv1 + GLU -> causal depthwise + BatchNorm + SiLU -> pointwise_conv2
         float* const* cptr = e->cnnptrs.as<float*>() + (size_t)l * n;
         {   // [cnn cache | ada_scale * x + ada_bias] -> pointwise_conv1 + GLU (+ the new cache) in one launch where the small-M
@@ -2931,8 +2937,7 @@ static int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector
             rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
         }
         launch_layernorm(x, w.ln3_w, w.ln3_b, x, M, 1e-5f, 0, 0, nullptr, s);
-        CHK(ffn(e, s, M, w.f2_s, w.f2_b, w.f2_w1, w.f2_b1, w.f2_w2, w.f2_b2, 1.0f, 1, w.ln4_w, w.ln4_b,
-                l == L - 1 ? e->enc.as<float>() : x));
+        CHK(ffn(e, s, ffn_sqz2(w, M, l == L - 1 ? e->enc.as<float>() : x)));
     }
     if (e->cfg.vocab_size > 16384) return fail("vocab_size > 16384 is not supported by the softmax / pruning kernels (one 256-thread workgroup holds a row in registers)");
     CHK(ctc_head(e, e->enc.as<float>(), n * T0, probs_dev, probs_dev ? 1 : 0, argmax_dev, maxprob_dev, s));
@@ -3043,7 +3048,7 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
         const int Tq = rate(l) == 2 ? T2 : T0;
         int M = n * Tq;
         const AttSeq* seqs = e->attseq.as<AttSeq>() + (size_t)l * n;
-        CHK(ffn(e, s, M, w.ln_ffm_w, w.ln_ffm_b, w.ffm_w1, w.ffm_b1, w.ffm_w2, w.ffm_b2));
+        CHK(ffn(e, s, ffn_macaron(w, M)));
         if (layer_grouped(e, l)) {
             {
                 RowGemmArgs g = rg_args(x, d, w.wqkv, w.bqkv, qp, d, M, 3 * d);
@@ -3087,7 +3092,7 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
         } else {
             CHK(conv_module_stream(e, s, w, n, Tq, cptr, cptr + (size_t)L * n, K));
         }
-        CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2, 0.5f, 0, w.ln_fin_w, w.ln_fin_b, x));
+        CHK(ffn(e, s, ffn_final(w, M, x)));
     }
     CHK(e->enc.ensure((size_t)n * T2 * d * sizeof(float)));
     launch_layernorm(x, e->after_w, e->after_b, e->enc.as<float>(), n * T2, 1e-5f, 0, 0, nullptr, s);
@@ -3186,7 +3191,7 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
             continue;
         }
         const LayerW& w = e->layers[knobs().hot_weights ? 0 : l];
-        CHK(ffn(e, s, M, w.ln_ffm_w, w.ln_ffm_b, w.ffm_w1, w.ffm_b1, w.ffm_w2, w.ffm_b2));
+        CHK(ffn(e, s, ffn_macaron(w, M)));
         mhsa(e, s, w, M, e->attseq.as<AttSeq>() + (size_t)l * n, Tq);     // q -> qkv buffer, k|v rows -> the streams' caches
         launch_attention(e->attseq.as<AttSeq>() + (size_t)l * n, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, 1, s, 256);
         mhsa_out(e, s, w, M);
@@ -3195,10 +3200,12 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
         // d_ff-split launch of few streams every slice repeats it on the row block's rows; one launch less on the step's chain)
         const bool fuse = knobs().split_head && e->cfg.cnn_kernel == 15 && knobs().ffn_packed >= 2 && !knobs().no_ffn_head;
         CHK(conv_module_stream(e, s, w, n, Tq, cptr, cptr + (size_t)L * n, e->cfg.cnn_kernel, fuse));
-        const FfnHead head{e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, nullptr, w.pw2_w, w.pw2_b, nullptr, Tq,
-                           e->cfg.cnn_kernel, 4, nullptr};
-        CHK(ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2, 0.5f, 0, w.ln_fin_w, w.ln_fin_b, x, nullptr,
-                nullptr, fuse ? &head : nullptr));
+        FfnArgs f2 = ffn_final(w, M, x);
+        if (fuse) {
+            f2.head = conv_head(e, w, nullptr, Tq, e->cfg.cnn_kernel, 4);
+            f2.head.gconst = nullptr;      // the history rows are real here: the streams' cnn caches
+        }
+        CHK(ffn(e, s, f2));
     }
     CHK(e->enc.ensure((size_t)M * d * sizeof(float)));
     if (wide) WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, e->after_w, e->after_b, e->enc.as<float>(), M, d, 1e-5f, 0, 0, nullptr, s));
@@ -3358,6 +3365,20 @@ int masr_debug_key_info(int32_t index, int32_t* key, int32_t* default_value, int
     if (default_value) *default_value = knob_default(*k);
     if (experimental) *experimental = k->experimental;
     if (name) *name = k->name;
+    return 0;
+}
+
+int masr_ffn_plan(int32_t d_model, int32_t d_ff, int32_t m, const int32_t* ask, const int32_t* overrides, int32_t n_overrides,
+                  int32_t* plan) {
+    if (!ask || !plan || n_overrides < 0 || (n_overrides && !overrides)) return fail("masr_ffn_plan: null argument");
+    if (d_ff <= 0 || d_ff % 128 || m <= 0) return fail("masr_ffn_plan: d_ff must be a positive multiple of 128 and m positive");
+    Knobs k;                       // the defaults; the process's switches are neither read nor written
+    for (int i = 0; i < n_overrides; ++i)
+        if (!knob_set(overrides[2 * i], overrides[2 * i + 1], k))
+            return fail("masr_ffn_plan: no process-wide switch has key " + std::to_string(overrides[2 * i]));
+    const FfnPlan p = ffn_plan(k, d_model, d_ff, m, {ask[0], ask[1], ask[2], ask[3], ask[4]});
+    const int32_t out[9] = {p.kernel, p.nsplit, p.cpb, p.ny, p.packed, p.tail_in_kernel, p.head_in_kernel, p.split_head, p.prof};
+    std::copy(out, out + 9, plan);
     return 0;
 }
 

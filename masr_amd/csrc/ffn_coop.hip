@@ -154,12 +154,11 @@ void launch_pack_ffn_coop_w1(const float* w1, float* p, int dff, hipStream_t s) 
     hipLaunchKernelGGL(pack_ffn_coop_w1_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w1, p, dff);
 }
 
-// w1p: launch_pack_ffn_coop_w1's copy of W1; w2p: ffn_pc.hip's packed copy of W2 (launch_pack_ffn_pc); partial [dff / 128][M][256];
+// a.w1: launch_pack_ffn_coop_w1's copy of W1; a.w2: ffn_pc.hip's packed copy of W2 (launch_pack_ffn_pc); a.partial [dff / 128][M][256];
 // the caller runs the reduction
-void launch_ffn_coop(const float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2, int M,
-                     int dff, float eps, int affine, float* partial, hipStream_t s) {
-    hipLaunchKernelGGL(ffn_coop_kernel, dim3((M + 31) / 32, dff / 128), dim3(512), 0, s, x, lnw, lnb, w1, b1, w2, M, dff, eps, affine,
-                       partial);
+void launch_ffn_coop(const FfnArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(ffn_coop_kernel, dim3((a.M + 31) / 32, a.dff / 128), dim3(512), 0, s, (const float*)a.x, a.lnw, a.lnb, a.w1, a.b1,
+                       a.w2, a.M, a.dff, a.eps, a.affine, a.partial);
 }
 
 }  // namespace masr

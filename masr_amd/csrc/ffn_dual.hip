@@ -463,41 +463,38 @@ void launch_pack_rows_dual(const float* w, float* p, hipStream_t s) {
 }
 
 template <int AFFINE, int TAIL, int HEADK>
-static void launch_dual_t(float* x, const float* lnw, const float* lnb, const float* p1, const float* b1, const float* p2,
-                          const float* b2, int M, int dff, float eps, float scale, hipStream_t s, const FfnTail& tail,
-                          const FfnHead& head) {
+static void launch_dual_t(const FfnArgs& a, hipStream_t s, const FfnTail& tail, const FfnHead& head) {
     const size_t lds = (size_t)(DU_BM * DU_XLD + 2 * DU_BM * DU_HLD) * sizeof(float);
     static LdsAttr attr;
     ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_dual_kernel<AFFINE, TAIL, HEADK>), lds, attr);
-    hipLaunchKernelGGL((ffn_dual_kernel<AFFINE, TAIL, HEADK>), dim3((M + DU_BM - 1) / DU_BM), dim3(512), lds, s, x, lnw, lnb, p1, b1,
-                       p2, b2, M, dff, eps, scale, tail, head);
+    hipLaunchKernelGGL((ffn_dual_kernel<AFFINE, TAIL, HEADK>), dim3((a.M + DU_BM - 1) / DU_BM), dim3(512), lds, s, a.x, a.lnw, a.lnb, a.w1,
+                       a.b1, a.w2, a.b2, a.M, a.dff, a.eps, a.scale, tail, head);
 }
 
-// p1 / p2: packed copies of launch_pack_ffn_dual; tail->W: launch_pack_rows_dual (N = 768 only); head->W: launch_pack_rows_pc.
+// a.w1 / a.w2: packed copies of launch_pack_ffn_dual; tail.W: launch_pack_rows_dual (N = 768 only); head.W: launch_pack_rows_pc.
 // Returns 0 (block only), 2 (tail stage done), 4 (head stage done), -1 (sizes not covered: the caller uses ffn_pc.hip)
-int launch_ffn_dual(float* x, const float* lnw, const float* lnb, const float* p1, const float* b1, const float* p2,
-                    const float* b2, int M, int dff, float eps, float scale, int affine_prologue, hipStream_t s,
-                    const FfnTail* tail, const FfnHead* head) {
-    if (M <= 0) return 0;
-    if (dff % DU_CH != 0 || dff < 2 * DU_CH) return -1;
-    if (affine_prologue) {
+int launch_ffn_dual(const FfnArgs& a, hipStream_t s) {
+    if (a.M <= 0) return 0;
+    if (a.dff % DU_CH != 0 || a.dff < 2 * DU_CH) return -1;
+    const bool tail = a.tail.W != nullptr, head = a.head.glu != nullptr;
+    if (a.affine) {
         if (tail || head) return -1;
-        launch_dual_t<1, 0, 0>(x, lnw, lnb, p1, b1, p2, b2, M, dff, eps, scale, s, FfnTail{}, FfnHead{});
+        launch_dual_t<1, 0, 0>(a, s, FfnTail{}, FfnHead{});
         return 0;
     }
-    if (head && head->glu) {
+    if (head) {
         if (tail) return -1;
-        if (head->ktaps == 15) launch_dual_t<0, 0, 15>(x, lnw, lnb, p1, b1, p2, b2, M, dff, eps, scale, s, FfnTail{}, *head);
-        else if (head->ktaps == 7) launch_dual_t<0, 0, 7>(x, lnw, lnb, p1, b1, p2, b2, M, dff, eps, scale, s, FfnTail{}, *head);
+        if (a.head.ktaps == 15) launch_dual_t<0, 0, 15>(a, s, FfnTail{}, a.head);
+        else if (a.head.ktaps == 7) launch_dual_t<0, 0, 7>(a, s, FfnTail{}, a.head);
         else return -1;
         return 4;
     }
-    if (tail && tail->out) {
-        if (tail->N != 768) return -1;
-        launch_dual_t<0, 1, 0>(x, lnw, lnb, p1, b1, p2, b2, M, dff, eps, scale, s, *tail, FfnHead{});
+    if (tail && a.tail.out) {
+        if (a.tail.N != 768) return -1;
+        launch_dual_t<0, 1, 0>(a, s, a.tail, FfnHead{});
         return 2;
     }
-    launch_dual_t<0, 0, 0>(x, lnw, lnb, p1, b1, p2, b2, M, dff, eps, scale, s, FfnTail{}, FfnHead{});
+    launch_dual_t<0, 0, 0>(a, s, FfnTail{}, FfnHead{});
     return 0;
 }
 

@@ -19,6 +19,7 @@
 // wave; conformer/attention.py:53-79, encoder.py:123-131).  This replaces a separate launch whose ramp, row reload +
 // LayerNorm prologue and store tail cost about as much as its 20 us of matrix work.
 #include "common.h"
+#include "ffn_plan.h"
 
 namespace masr {
 
@@ -1037,35 +1038,35 @@ void launch_pack_rows16(const float* w, float* p, int N, hipStream_t s, int n_sr
     hipLaunchKernelGGL(pack_rows16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, p, N, n_src < 0 ? N : n_src);
 }
 
+template <int TAIL, int HEADK, int NORM = 0>
+static void launch16_t(const FfnArgs& a, hipStream_t s, const FfnTail& tail, const FfnHead& head) {
+    const size_t lds = (size_t)(P16_BM * PC_XLD + 2 * P16_BM * PC_HLD) * sizeof(float);
+    hipLaunchKernelGGL((ffn16_kernel<TAIL, HEADK, NORM>), dim3((a.M + P16_BM - 1) / P16_BM), dim3(512), lds, s, a.x, a.lnw, a.lnb, a.w1,
+                       a.b1, a.w2, a.b2, a.M, a.dff, a.eps, a.scale, tail, head);
+}
+
 // full-d_ff launch of the 16-row kernel (w1 / w2: launch_pack_ffn16 copies; tail->W, head->W: launch_pack_rows16 copies).
 // Returns 2 when the tail stage ran, 4 when the head stage ran, 0 otherwise, -1 for what this kernel does not cover (the caller
 // checks first: d_model 256, d_ff a multiple of 128, tail N a multiple of 256, head with 15 or 7 taps, never both).
-int launch_ffn16(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2, const float* b2, int M,
-                 int dff, float eps, float scale, hipStream_t s, const FfnTail* tail, const FfnHead* head) {
-    if (M <= 0) return 0;
-    if (dff % PC_CH || dff <= 0 || (tail && tail->out && head && head->glu)) return -1;
-    const size_t lds = (size_t)(P16_BM * PC_XLD + 2 * P16_BM * PC_HLD) * sizeof(float);
-    const dim3 grid((M + P16_BM - 1) / P16_BM);
-    if (head && head->glu) {
-        if (head->norm != 0 && head->norm != 1) return -1;
-        if (head->ktaps == 15 && head->norm == 1)
-            hipLaunchKernelGGL((ffn16_kernel<0, 15, 1>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, *head);
-        else if (head->ktaps == 7 && head->norm == 1)
-            hipLaunchKernelGGL((ffn16_kernel<0, 7, 1>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, *head);
-        else if (head->ktaps == 15)
-            hipLaunchKernelGGL((ffn16_kernel<0, 15>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, *head);
-        else if (head->ktaps == 7)
-            hipLaunchKernelGGL((ffn16_kernel<0, 7>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, *head);
-        else
-            return -1;
+int launch_ffn16(const FfnArgs& a, hipStream_t s) {
+    const bool tail = a.tail.W && a.tail.out, head = a.head.glu != nullptr;
+    if (a.M <= 0) return 0;
+    if (a.dff % PC_CH || a.dff <= 0 || (tail && head)) return -1;
+    if (head) {
+        if (a.head.norm != 0 && a.head.norm != 1) return -1;
+        if (a.head.ktaps == 15 && a.head.norm == 1) launch16_t<0, 15, 1>(a, s, FfnTail{}, a.head);
+        else if (a.head.ktaps == 7 && a.head.norm == 1) launch16_t<0, 7, 1>(a, s, FfnTail{}, a.head);
+        else if (a.head.ktaps == 15) launch16_t<0, 15>(a, s, FfnTail{}, a.head);
+        else if (a.head.ktaps == 7) launch16_t<0, 7>(a, s, FfnTail{}, a.head);
+        else return -1;
         return 4;
     }
-    if (tail && tail->out) {
-        if (tail->N % 256) return -1;
-        hipLaunchKernelGGL((ffn16_kernel<1, 0>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, *tail, FfnHead{});
+    if (tail) {
+        if (a.tail.N % 256) return -1;
+        launch16_t<1, 0>(a, s, a.tail, FfnHead{});
         return 2;
     }
-    hipLaunchKernelGGL((ffn16_kernel<0, 0>), grid, dim3(512), lds, s, x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, FfnTail{}, FfnHead{});
+    launch16_t<0, 0>(a, s, FfnTail{}, FfnHead{});
     return 0;
 }
 
@@ -1146,84 +1147,80 @@ void launch_pack_ffn_pc(const float* w1, const float* w2, float* p1, float* p2, 
 }
 
 template <int HEADK, int VAR, int NORM = 0>
-static void launch_head_t(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2,
-                          const float* b2, int M, int dff, float eps, float scale, hipStream_t s, const FfnHead& head, size_t lds) {
+static void launch_head_t(const FfnArgs& a, hipStream_t s, size_t lds) {
     static LdsAttr attr;
     ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<0, 0, VAR, 0, HEADK, NORM>), lds, attr);
-    hipLaunchKernelGGL((ffn_pc_kernel<0, 0, VAR, 0, HEADK, NORM>), dim3((M + PC_BM - 1) / PC_BM), dim3(512), lds, s, x, lnw, lnb, w1, b1, w2,
-                       b2, M, dff, eps, scale, (float*)nullptr, 0, FfnTail{}, head);
+    hipLaunchKernelGGL((ffn_pc_kernel<0, 0, VAR, 0, HEADK, NORM>), dim3((a.M + PC_BM - 1) / PC_BM), dim3(512), lds, s, a.x, a.lnw, a.lnb,
+                       a.w1, a.b1, a.w2, a.b2, a.M, a.dff, a.eps, a.scale, (float*)nullptr, 0, FfnTail{}, a.head);
 }
 
 // VAR: 0 production slab pipeline | 1 without weight loads (floor measurement) | 2 packed weights straight into registers
-// (w1 / w2 are then the packed copies; full kernels only -- the d_ff-split launches of small M keep the slab pipeline)
+// (w1 / w2 are then the packed copies).  The tail / head stages exist without the affine prologue and with weight loads only
 template <int AFFINE, int VAR>
-static int launch_pc_t(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2,
-                       const float* b2, int M, int dff, float eps, float scale, float* partial, int nsplit, hipStream_t s,
-                       const FfnPostLn* post, const FfnTail* tail, const FfnHead* head) {
+static int launch_pc_t(const FfnArgs& a, hipStream_t s) {
+    const bool tail = a.tail.W && a.tail.out, head = a.head.glu != nullptr;
     const size_t lds = (size_t)(PC_BM * PC_XLD + 2 * PC_BM * PC_HLD + 8 * 2 * PC_WSLAB) * sizeof(float);
     constexpr int TV = VAR == 1 ? 0 : VAR;               // variant of the tail / head kernels (never built for VAR == 1)
     static LdsAttr attr_full, attr_split, attr_tail;
     ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<AFFINE, 0, VAR, 0, 0>), lds, attr_full);
     ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<AFFINE, 1, 0, 0, 0>), lds, attr_split);
     ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<0, 0, TV, 1, 0>), lds, attr_tail);
-    const int nchunk = dff / PC_CH;
-    if (partial && nsplit > 1) {
+    const dim3 rows((a.M + PC_BM - 1) / PC_BM);
+    if (a.partial && a.nsplit > 1) {
         constexpr int SV = VAR == 2 ? 2 : 0;              // split launches: slab pipeline or packed weights (never the no-load variant)
         static LdsAttr attr_split_v;
         ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<AFFINE, 1, SV, 0, 0>), lds, attr_split_v);
-        const int cpb = (nchunk + nsplit - 1) / nsplit;
-        const int ny = (nchunk + cpb - 1) / cpb;          // every blockIdx.y owns at least one chunk
+        const FfnSlices sl = ffn_slices(a.dff, a.nsplit);  // every blockIdx.y owns at least one chunk
+        const dim3 grid(rows.x, sl.ny);
         // head stage on the split launch (few rows): every slice of a row block runs the conv module's [depthwise conv -> LN ->
         // SiLU -> pointwise_conv2 + residual] on the block's rows before its share of the FFN; slice 0 writes the updated rows to
-        // head->xout and the reduction continues from there
+        // head.xout and the reduction continues from there
 #if MASR_EXPERIMENTS
-        if (head && head->glu && head->xout && head->ktaps == 15 && !AFFINE && SV == 2) {
+        if (head && a.head.xout && a.head.ktaps == 15 && !AFFINE && SV == 2) {
             static LdsAttr attr_split_h, attr_split_hb;
-            if (head->norm == 1) {
+            if (a.head.norm == 1) {
                 ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<0, 1, 2, 0, 15, 1>), lds, attr_split_hb);
-                hipLaunchKernelGGL((ffn_pc_kernel<0, 1, 2, 0, 15, 1>), dim3((M + PC_BM - 1) / PC_BM, ny), dim3(512), lds, s, x, lnw, lnb,
-                                   w1, b1, w2, b2, M, dff, eps, scale, partial, cpb, FfnTail{}, *head);
+                hipLaunchKernelGGL((ffn_pc_kernel<0, 1, 2, 0, 15, 1>), grid, dim3(512), lds, s, a.x, a.lnw, a.lnb, a.w1, a.b1, a.w2, a.b2,
+                                   a.M, a.dff, a.eps, a.scale, a.partial, sl.cpb, FfnTail{}, a.head);
             } else {
                 ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_pc_kernel<0, 1, 2, 0, 15>), lds, attr_split_h);
-                hipLaunchKernelGGL((ffn_pc_kernel<0, 1, 2, 0, 15>), dim3((M + PC_BM - 1) / PC_BM, ny), dim3(512), lds, s, x, lnw, lnb,
-                                   w1, b1, w2, b2, M, dff, eps, scale, partial, cpb, FfnTail{}, *head);
+                hipLaunchKernelGGL((ffn_pc_kernel<0, 1, 2, 0, 15>), grid, dim3(512), lds, s, a.x, a.lnw, a.lnb, a.w1, a.b1, a.w2, a.b2,
+                                   a.M, a.dff, a.eps, a.scale, a.partial, sl.cpb, FfnTail{}, a.head);
             }
-            launch_ffn_reduce(x, partial, b2, M, ny, scale, s, post, head->xout);
-            return (post && post->y ? 1 : 0) | 4;
+            launch_ffn_reduce(a, s, a.head.xout);
+            return (a.post.y ? 1 : 0) | 4;
         }
 #endif
-        hipLaunchKernelGGL((ffn_pc_kernel<AFFINE, 1, SV, 0, 0>), dim3((M + PC_BM - 1) / PC_BM, ny), dim3(512), lds, s, x, lnw, lnb, w1,
-                           b1, w2, b2, M, dff, eps, scale, partial, cpb, FfnTail{}, FfnHead{});
-        launch_ffn_reduce(x, partial, b2, M, ny, scale, s, post);
-        return post && post->y ? 1 : 0;
-    } else if (head && head->glu && (head->ktaps == 15 || head->ktaps == 7) && !AFFINE && VAR != 1 && !(tail && tail->out)) {
-        if (head->ktaps == 15 && head->norm == 1) launch_head_t<15, TV, 1>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, s, *head, lds);
-        else if (head->norm == 1) launch_head_t<7, TV, 1>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, s, *head, lds);
-        else if (head->ktaps == 15) launch_head_t<15, TV>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, s, *head, lds);
-        else launch_head_t<7, TV>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, s, *head, lds);
+        hipLaunchKernelGGL((ffn_pc_kernel<AFFINE, 1, SV, 0, 0>), grid, dim3(512), lds, s, a.x, a.lnw, a.lnb, a.w1, a.b1, a.w2, a.b2, a.M,
+                           a.dff, a.eps, a.scale, a.partial, sl.cpb, FfnTail{}, FfnHead{});
+        launch_ffn_reduce(a, s);
+        return a.post.y ? 1 : 0;
+    } else if (head && (a.head.ktaps == 15 || a.head.ktaps == 7) && !AFFINE && VAR != 1 && !tail) {
+        if (a.head.ktaps == 15 && a.head.norm == 1) launch_head_t<15, TV, 1>(a, s, lds);
+        else if (a.head.norm == 1) launch_head_t<7, TV, 1>(a, s, lds);
+        else if (a.head.ktaps == 15) launch_head_t<15, TV>(a, s, lds);
+        else launch_head_t<7, TV>(a, s, lds);
         return 4;                                         // head stage done
-    } else if (tail && tail->out && tail->N % 256 == 0 && !AFFINE && VAR != 1) {
-        hipLaunchKernelGGL((ffn_pc_kernel<0, 0, TV, 1, 0>), dim3((M + PC_BM - 1) / PC_BM), dim3(512), lds, s, x, lnw, lnb, w1, b1, w2,
-                           b2, M, dff, eps, scale, (float*)nullptr, 0, *tail, FfnHead{});
+    } else if (tail && a.tail.N % 256 == 0 && !AFFINE && VAR != 1) {
+        hipLaunchKernelGGL((ffn_pc_kernel<0, 0, TV, 1, 0>), rows, dim3(512), lds, s, a.x, a.lnw, a.lnb, a.w1, a.b1, a.w2, a.b2, a.M, a.dff,
+                           a.eps, a.scale, (float*)nullptr, 0, a.tail, FfnHead{});
         return 2;                                         // tail stage done
     } else {
-        hipLaunchKernelGGL((ffn_pc_kernel<AFFINE, 0, VAR, 0, 0>), dim3((M + PC_BM - 1) / PC_BM), dim3(512), lds, s, x, lnw, lnb, w1,
-                           b1, w2, b2, M, dff, eps, scale, (float*)nullptr, 0, FfnTail{}, FfnHead{});
+        hipLaunchKernelGGL((ffn_pc_kernel<AFFINE, 0, VAR, 0, 0>), rows, dim3(512), lds, s, a.x, a.lnw, a.lnb, a.w1, a.b1, a.w2, a.b2, a.M,
+                           a.dff, a.eps, a.scale, (float*)nullptr, 0, FfnTail{}, FfnHead{});
     }
     return 0;
 }
 
-// returns 1 when the post LayerNorm was applied (split-d_ff path), 2 when the tail stage ran (full kernel with `tail`), 4 when
-// the head stage ran (full kernel with `head`), 0 when the caller still has to run whichever it asked for
-int launch_ffn_pc(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2,
-                  const float* b2, int M, int dff, float eps, float scale, int affine_prologue, float* partial, int nsplit,
-                  hipStream_t s, int variant, const FfnPostLn* post, const FfnTail* tail, const FfnHead* head) {
-    if (M <= 0) return 0;
-    if (affine_prologue && variant == 2) return launch_pc_t<1, 2>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, partial, nsplit, s, post, nullptr, nullptr);
-    if (affine_prologue) return launch_pc_t<1, 0>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, partial, nsplit, s, post, nullptr, nullptr);
-    if (variant == 1) return launch_pc_t<0, 1>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, partial, nsplit, s, post, nullptr, nullptr);
-    if (variant == 2) return launch_pc_t<0, 2>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, partial, nsplit, s, post, tail, head);
-    return launch_pc_t<0, 0>(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, partial, nsplit, s, post, tail, head);
+// returns 1 when the post LayerNorm was applied (split-d_ff path), 2 when the tail stage ran (full kernel with a tail), 4 when
+// the head stage ran (full kernel with a head), 0 when the caller still has to run whichever it asked for
+int launch_ffn_pc(const FfnArgs& a, int variant, hipStream_t s) {
+    if (a.M <= 0) return 0;
+    if (a.affine && variant == 2) return launch_pc_t<1, 2>(a, s);
+    if (a.affine) return launch_pc_t<1, 0>(a, s);
+    if (variant == 1) return launch_pc_t<0, 1>(a, s);
+    if (variant == 2) return launch_pc_t<0, 2>(a, s);
+    return launch_pc_t<0, 0>(a, s);
 }
 
 }  // namespace masr

@@ -3,6 +3,7 @@
 // conformer/encoder.py:113-121,150-161); for few rows (streaming chunk steps) d_ff is split across workgroups into
 // partial sums that the kernel below adds in a fixed order, optionally followed by the layer's next LayerNorm.
 #include "common.h"
+#include "ffn_plan.h"
 
 namespace masr {
 
@@ -67,27 +68,22 @@ __global__ __launch_bounds__(256) void ffn_reduce_kernel(float* x, const float* 
     }
 }
 
-void launch_ffn_reduce(float* x, const float* partial, const float* b2, int M, int nsplit, float scale, hipStream_t s,
-                       const FfnPostLn* post, const float* xin) {
-    const dim3 grid((unsigned)(((size_t)M * FF_D / 4 + 255) / 256));
-    if (post && post->y)
-        hipLaunchKernelGGL(ffn_reduce_kernel<1>, grid, dim3(256), 0, s, x, partial, b2, M, nsplit, scale, post->lnw, post->lnb,
-                           post->y, post->eps, xin);
+void launch_ffn_reduce(const FfnArgs& a, hipStream_t s, const float* xin) {
+    const dim3 grid((unsigned)(((size_t)a.M * FF_D / 4 + 255) / 256));
+    const int ny = ffn_slices(a.dff, a.nsplit).ny;       // the slices that were launched
+    if (a.post.y)
+        hipLaunchKernelGGL(ffn_reduce_kernel<1>, grid, dim3(256), 0, s, a.x, a.partial, a.b2, a.M, ny, a.scale, a.post.lnw, a.post.lnb,
+                           a.post.y, a.post.eps, xin);
     else
-        hipLaunchKernelGGL(ffn_reduce_kernel<0>, grid, dim3(256), 0, s, x, partial, b2, M, nsplit, scale, (const float*)nullptr,
+        hipLaunchKernelGGL(ffn_reduce_kernel<0>, grid, dim3(256), 0, s, a.x, a.partial, a.b2, a.M, ny, a.scale, (const float*)nullptr,
                            (const float*)nullptr, (float*)nullptr, 0.f, xin);
 }
-int launch_ffn_pc(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2,
-                  const float* b2, int M, int dff, float eps, float scale, int affine_prologue, float* partial, int nsplit,
-                  hipStream_t s, int variant, const FfnPostLn* post, const FfnTail* tail, const FfnHead* head);
+int launch_ffn_pc(const FfnArgs& a, int variant, hipStream_t s);
 
-int launch_ffn_fused(float* x, const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2,
-                     const float* b2, int M, int dff, float eps, float scale, int affine_prologue, float* partial,
-                     int nsplit, hipStream_t s, const FfnPostLn* post, const FfnTail* tail, const FfnHead* head, bool packed) {
-    if (M <= 0) return 0;
-    // packed: w1 / w2 are the fragment-ordered copies of launch_pack_ffn_pc (full, non-split launches only)
-    return launch_ffn_pc(x, lnw, lnb, w1, b1, w2, b2, M, dff, eps, scale, affine_prologue, partial, nsplit, s,
-                         packed ? 2 : knobs().ffn_variant == 81 ? 1 : 0, post, tail, head);
+int launch_ffn_fused(const FfnArgs& a, hipStream_t s) {
+    if (a.M <= 0) return 0;
+    // packed: w1 / w2 are the fragment-ordered copies of launch_pack_ffn_pc
+    return launch_ffn_pc(a, a.packed ? 2 : knobs().ffn_variant == 81 ? 1 : 0, s);
 }
 
 }  // namespace masr

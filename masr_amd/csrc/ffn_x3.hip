@@ -262,12 +262,12 @@ void launch_pack_ffn_x3(const float* w1, const float* w2, unsigned short* p1, un
     hipLaunchKernelGGL(pack_ffn_x3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w1, w2, p1, p2, dff);
 }
 
-// d_model 256, d_ff a multiple of 128 (the shipped YAMLs); false = not taken
-bool launch_ffn_x3(float* x, const float* lnw, const float* lnb, const unsigned short* p1, const float* b1,
-                   const unsigned short* p2, const float* b2, int M, int dff, float eps, float scale, hipStream_t s) {
-    if (M <= 0 || dff % FX_CH != 0 || dff / FX_CH < 1) return false;
-    hipLaunchKernelGGL(ffn_x3_kernel, dim3((M + 31) / 32), dim3(512), 0, s, x, lnw, lnb, p1, b1, p2, b2, M, dff, eps, scale,
-                       knobs().ffn_x3_rotation);
+// d_model 256, d_ff a multiple of 128 (the shipped YAMLs); false = not taken.  a.w1 / a.w2: launch_pack_ffn_x3's copies
+bool launch_ffn_x3(const FfnArgs& a, hipStream_t s) {
+    if (a.M <= 0 || a.dff % FX_CH != 0 || a.dff / FX_CH < 1) return false;
+    hipLaunchKernelGGL(ffn_x3_kernel, dim3((a.M + 31) / 32), dim3(512), 0, s, a.x, a.lnw, a.lnb,
+                       reinterpret_cast<const unsigned short*>(a.w1), a.b1, reinterpret_cast<const unsigned short*>(a.w2), a.b2, a.M,
+                       a.dff, a.eps, a.scale, knobs().ffn_x3_rotation);
     return true;
 }
 

@@ -59,9 +59,9 @@ const KnobInfo* knob_find(int key) {
 
 int knob_default(const KnobInfo& k) { return Knobs{}.*k.field; }
 
-bool knob_set(int key, int value) {
+bool knob_set(int key, int value, Knobs& into) {
     const KnobInfo* k = knob_find(key);
-    if (k) knobs().*k->field = value;
+    if (k) into.*k->field = value;
     return k != nullptr;
 }
 

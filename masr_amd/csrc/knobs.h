@@ -99,7 +99,7 @@ Knobs& knobs();
 const KnobInfo* knob_info(int index);      // row `index` of the table; nullptr past the last row
 const KnobInfo* knob_find(int key);        // nullptr: no process-wide switch has this key
 int knob_default(const KnobInfo& k);
-bool knob_set(int key, int value);         // false: unknown key
+bool knob_set(int key, int value, Knobs& into = knobs());      // false: unknown key (into: a copy of the table, for queries)
 void knobs_reset();                        // every switch back to its default
 
 }  // namespace masr

@@ -1,7 +1,8 @@
 """The launch plan of the fused FFN family, restated in Python (a plain helper module: tests import it).
 
-``ffn()`` in masr_amd/csrc/engine.hip splits d_ff across workgroups when a call has few 32-row blocks, and ``launch_pc_t`` in
-ffn_pc.hip turns that wish into slices of whole 128-unit chunks:
+``ffn_plan()`` in masr_amd/csrc/ffn_plan.h splits d_ff across workgroups when a call has few 32-row blocks, and ``ffn_slices()``
+there turns that wish into slices of whole 128-unit chunks (this module is the independent statement: tests/test_ffn_plan_cpu.py
+holds the library's ``masr_ffn_plan`` to it):
 
     rowblocks = ceil(M / 32)                                                       nchunk = d_ff / 128
     nsplit    = min(nchunk, max(1, (rowblocks < 64 ? 128 : 256) / rowblocks))      if rowblocks < ffn_split_blocks (key 13), else 1
