@@ -41,7 +41,10 @@ typedef struct masr_config {
                               * feed_forward_expansion_factor.  Model kinds 0-2: any positive multiple of 128;
                               * masr_create refuses 0, negative values and non-multiples              */
     int32_t num_blocks;      /* encoder_conf.num_blocks         (12)                            */
-    int32_t cnn_kernel;      /* encoder_conf.cnn_module_kernel  (15)                            */
+    int32_t cnn_kernel;      /* encoder_conf.cnn_module_kernel  (15; squeezeformer 31).  Model kinds 0 and 1: any value in
+                              * [3, 31] with causal = 1, the odd ones with causal = 0 (symmetric padding of (K - 1) / 2
+                              * frames); model kind 2: 15.  masr_create refuses everything else by name.  The stream
+                              * caches and masr_stream_export_cache's cnn rows hold cnn_kernel - 1 frames          */
     int32_t n_mels;          /* preprocess_conf.n_mels          (80)                            */
     int32_t vocab_size;      /* len(vocabulary.txt)                                             */
     int32_t causal;          /* `streaming: True` => causal conv + dynamic-chunk masks (model.py:37-42) */

@@ -146,13 +146,15 @@ void launch_layernorm(const float* x, const float* w, const float* b, float* y, 
 void launch_conv1(const float* feats, const float* mean, const float* istd, const float* w9c, const float* bias,
                   float* out, int B, int T, int F, int C, hipStream_t s);
 // depthwise causal conv (k taps) + LayerNorm(C=256) + SiLU on padded layout [nseq, pad+Tq, 256] -> [nseq*Tq, 256]
-void launch_dwconv_ln_silu(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb,
+// k = 15 / 7 / 31: the kernels instantiated on the tap count; every other k in [1, 32]: dwconv_ln_silu_taps_kernel (tap count at
+// run time).  false: no kernel for k taps, nothing was launched -- the caller reports it
+bool launch_dwconv_ln_silu(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb,
                            float* out, int nseq, int Tq, int ktaps, float eps, hipStream_t s, const float* gconst = nullptr);
 // same with an eval-mode BatchNorm folded into a per-channel scale/shift instead of the LayerNorm
 void launch_glu_const(const float* bias512, float* out256, hipStream_t s);
 void launch_queue_spin(long long ticks, hipStream_t s);      // holds the stream's hardware queue for `ticks` x 10 ns
 void launch_queue_nop(hipStream_t s);
-void launch_dwconv_bn_silu(const float* g, const float* wkc, const float* bias, const float* scale, const float* shift,
+bool launch_dwconv_bn_silu(const float* g, const float* wkc, const float* bias, const float* scale, const float* shift,
                            float* out, int nseq, int Tq, int ktaps, hipStream_t s, const float* gconst = nullptr);
 // Efficient-Conformer stride layer: depthwise causal conv with stride 2 (+ LayerNorm + SiLU) on the padded layout
 // [nseq][ktaps-1 + Tin][256] -> [nseq * ceil(Tin/2), 256]; and the AvgPool1d(2, ceil_mode) residual path
@@ -496,7 +498,7 @@ void launch_conv1_wide(const float* feats, const float* mean, const float* istd,
 // out [M, d] = value * sigmoid(gate) of in [M, 2 d] (value | gate: a pointwise_conv1 output with its bias added)
 bool launch_glu_wide(const float* in, float* out, int M, int d, hipStream_t s);
 void launch_glu_const_wide(const float* bias2d, float* out, int d, hipStream_t s);      // launch_glu_const at width d
-// depthwise conv (ktaps = 15) + LayerNorm(d) + SiLU: g [nseq][in_pad + Tq][d] (in_pad materialised history rows) -> out [nseq * Tq, d];
+// depthwise conv (1 <= ktaps <= 32) + LayerNorm(d) + SiLU: g [nseq][in_pad + Tq][d] (in_pad materialised history rows) -> out [nseq * Tq, d];
 // tap j of output frame t reads input frame t + j - pad_l; frames in front of the materialised rows read gconst [d] (nullptr:
 // zero), frames behind the sequence read zero
 bool launch_dwconv_ln_silu_wide(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb, float* out,

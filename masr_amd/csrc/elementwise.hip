@@ -202,14 +202,104 @@ __global__ __launch_bounds__(256) void dwconv_ln_silu_kernel(const float* __rest
     }
 }
 
-void launch_dwconv_ln_silu(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb,
+// Tap counts without an instantiation of their own (encoder_conf.cnn_module_kernel off the shipped values): one kernel per CLASS of
+// tap counts, KMAX = 8 / 16 / 32 registers for the window and as many for the weights, the count K <= KMAX at run time.  Tap j
+// lives in slot KMAX - K + j, so the newest row always enters the last slot and the window shift stays a chain of register moves.
+// Same steps in the same order as dwconv_ln_silu_kernel<K, NORM>: acc = bias, then fmaf over the taps j = 0 .. K - 1 (the slots
+// in front of tap 0 are skipped by a wave-uniform test, not multiplied by zero), the tile through LDS, two-pass LayerNorm with
+// eps inside the root or the folded BatchNorm, SiLU.  The padded layout [nseq][K - 1 + Tq][256] and the three history modes are
+// the sibling's: materialised rows in front (chunk step), gconst (offline causal), zero rows on both sides (symmetric).  Every
+// row it touches lies inside the K - 1 + Tq padded rows of its own sequence whatever Tq is (Tq < K - 1 included): the preload
+// reads padded rows t0 .. t0 + K - 2 <= Tq + K - 3, the loop padded rows t0 + K - 1 + r <= Tq + K - 2.
+template <int KMAX, int NORM>
+__global__ __launch_bounds__(256) void dwconv_ln_silu_taps_kernel(const float* __restrict__ g, const float* __restrict__ wkc,
+                                                                  const float* __restrict__ bias,
+                                                                  const float* __restrict__ lnw,
+                                                                  const float* __restrict__ lnb, float* __restrict__ out,
+                                                                  int K, int Tq, float eps, const float* __restrict__ gconst) {
+    __shared__ __align__(16) float tile[DW_TT][256 + 4];
+    const int tiles = (Tq + DW_TT - 1) / DW_TT;
+    const int seq = blockIdx.x / tiles;
+    const int t0 = (blockIdx.x % tiles) * DW_TT;
+    const int c = threadIdx.x;
+    const int pad = K - 1, off = KMAX - K;          // slot of tap 0
+    const float* gin = g + ((size_t)seq * (pad + Tq) + t0) * 256 + c;
+    float w[KMAX], win[KMAX];
+#pragma unroll
+    for (int jj = 0; jj < KMAX; ++jj) w[jj] = jj >= off ? wkc[(jj - off) * 256 + c] : 0.f;
+    const float bv = bias[c];
+    const int nrows = min(DW_TT, Tq - t0);
+    const float gc = gconst ? gconst[c] : 0.f;
+    win[0] = 0.f;
+#pragma unroll
+    for (int jj = 1; jj < KMAX; ++jj) {             // taps 0 .. K - 2 of output row t0, one slot ahead of the first shift
+        const int j = jj - 1 - off;
+        win[jj] = j < 0 ? 0.f : (gconst && t0 + j < pad) ? gc : gin[(size_t)j * 256];
+    }
+    for (int r = 0; r < nrows; ++r) {
+#pragma unroll
+        for (int jj = 0; jj < KMAX - 1; ++jj) win[jj] = win[jj + 1];
+        win[KMAX - 1] = gin[(size_t)(pad + r) * 256];
+        float acc = bv;                       // out[t] = b + sum_j w[j] * gpad[t + j]
+#pragma unroll
+        for (int jj = 0; jj < KMAX; ++jj)
+            if (jj >= off) acc = fmaf(w[jj], win[jj], acc);
+        tile[r][c] = acc;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const f32x4 ww = *reinterpret_cast<const f32x4*>(lnw + lane * 4);
+    const f32x4 bb = *reinterpret_cast<const f32x4*>(lnb + lane * 4);
+    for (int r = wave; r < nrows; r += 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(&tile[r][lane * 4]);
+        f32x4 o;
+        if (NORM == 1) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = v[i] * ww[i] + bb[i];
+        } else {
+            const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / 256.0f);
+            const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
+            const float var = wave_sum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.0f / 256.0f);
+            const float rstd = 1.0f / sqrtf(var + eps);
+            o[0] = d0 * rstd * ww[0] + bb[0];
+            o[1] = d1 * rstd * ww[1] + bb[1];
+            o[2] = d2 * rstd * ww[2] + bb[2];
+            o[3] = d3 * rstd * ww[3] + bb[3];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = o[i] / (1.0f + expf(-o[i]));
+        *reinterpret_cast<f32x4*>(out + ((size_t)seq * Tq + t0 + r) * 256 + lane * 4) = o;
+    }
+}
+
+// the tap-count classes of dwconv_ln_silu_taps_kernel: false = no kernel for this many taps, nothing launched
+template <int NORM>
+static bool launch_dwconv_taps(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb, float* out,
+                               int nseq, int Tq, int ktaps, float eps, hipStream_t s, const float* gconst) {
+    if (ktaps < 1 || ktaps > 32) return false;
+    if (nseq * Tq <= 0) return true;
+    const int tiles = (Tq + DW_TT - 1) / DW_TT;
+    const dim3 grid(nseq * tiles), blk(256);
+    if (ktaps <= 8)
+        hipLaunchKernelGGL((dwconv_ln_silu_taps_kernel<8, NORM>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, eps, gconst);
+    else if (ktaps <= 16)
+        hipLaunchKernelGGL((dwconv_ln_silu_taps_kernel<16, NORM>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, eps, gconst);
+    else
+        hipLaunchKernelGGL((dwconv_ln_silu_taps_kernel<32, NORM>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, eps, gconst);
+    return true;
+}
+
+bool launch_dwconv_ln_silu(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb,
                            float* out, int nseq, int Tq, int ktaps, float eps, hipStream_t s, const float* gconst) {
-    if (nseq * Tq <= 0) return;
+    if (ktaps < 1 || ktaps > 32) return false;          // (no rows to do is no excuse for a tap count without a kernel)
+    if (nseq * Tq <= 0) return true;
     const int tiles = (Tq + DW_TT - 1) / DW_TT;
     const dim3 grid(nseq * tiles), blk(256);
     if (ktaps == 15) hipLaunchKernelGGL((dwconv_ln_silu_kernel<15, 0>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, Tq, eps, gconst);
     else if (ktaps == 7) hipLaunchKernelGGL((dwconv_ln_silu_kernel<7, 0>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, Tq, eps, gconst);
     else if (ktaps == 31) hipLaunchKernelGGL((dwconv_ln_silu_kernel<31, 0>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, Tq, eps, gconst);
+    else return launch_dwconv_taps<0>(g, wkc, bias, lnw, lnb, out, nseq, Tq, ktaps, eps, s, gconst);
+    return true;
 }
 
 // glu(bias) of pointwise_conv1 with the arithmetic of the rowgemm GLU epilogue: the constant history rows of the offline
@@ -222,14 +312,17 @@ void launch_glu_const(const float* bias512, float* out256, hipStream_t s) {
     hipLaunchKernelGGL(glu_const_kernel, dim3(1), dim3(256), 0, s, bias512, out256);
 }
 
-void launch_dwconv_bn_silu(const float* g, const float* wkc, const float* bias, const float* scale, const float* shift,
+bool launch_dwconv_bn_silu(const float* g, const float* wkc, const float* bias, const float* scale, const float* shift,
                            float* out, int nseq, int Tq, int ktaps, hipStream_t s, const float* gconst) {
-    if (nseq * Tq <= 0) return;
+    if (ktaps < 1 || ktaps > 32) return false;
+    if (nseq * Tq <= 0) return true;
     const int tiles = (Tq + DW_TT - 1) / DW_TT;
     const dim3 grid(nseq * tiles), blk(256);
     if (ktaps == 31) hipLaunchKernelGGL((dwconv_ln_silu_kernel<31, 1>), grid, blk, 0, s, g, wkc, bias, scale, shift, out, Tq, 0.f, gconst);
     else if (ktaps == 15) hipLaunchKernelGGL((dwconv_ln_silu_kernel<15, 1>), grid, blk, 0, s, g, wkc, bias, scale, shift, out, Tq, 0.f, gconst);
     else if (ktaps == 7) hipLaunchKernelGGL((dwconv_ln_silu_kernel<7, 1>), grid, blk, 0, s, g, wkc, bias, scale, shift, out, Tq, 0.f, gconst);
+    else return launch_dwconv_taps<1>(g, wkc, bias, scale, shift, out, nseq, Tq, ktaps, 0.f, s, gconst);
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------

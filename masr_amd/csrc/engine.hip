@@ -663,11 +663,21 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
             return fail("output_size " + std::to_string(cfg->d_model) + ": input_layer must be conv2d (conv2d6 / conv2d8 are implemented at "
                         "output_size 256 only)");
     }
-    if (cfg->model_kind == 3) {
-    } else if (cfg->model_kind == 0 || cfg->model_kind == 2) {
-        if (cfg->cnn_kernel != 15) return fail("conformer: cnn_module_kernel must be 15");
-    } else {
-        if (cfg->cnn_kernel != 31) return fail("squeezeformer: cnn_module_kernel must be 31");
+    if (cfg->model_kind == 2) {
+        // (the stride layer halves the kernel: its kernels are built around 15 / 7)
+        if (cfg->cnn_kernel != 15)
+            return fail("efficient_conformer: cnn_module_kernel (masr_config.cnn_kernel) = " + std::to_string(cfg->cnn_kernel) +
+                        " is not supported: 15 only");
+    } else if (cfg->model_kind != 3) {
+        // the depthwise kernels hold at most 32 taps in registers; the symmetric padding of a streaming: False build needs
+        // (K - 1) / 2 rows on each side (the reference asserts it, convolution.py)
+        const char* fam = cfg->model_kind == 0 ? "conformer" : "squeezeformer";
+        if (cfg->cnn_kernel < 3 || cfg->cnn_kernel > 31)
+            return fail(std::string(fam) + ": cnn_module_kernel (masr_config.cnn_kernel) = " + std::to_string(cfg->cnn_kernel) +
+                        " is not supported: an integer in [3, 31]");
+        if (!cfg->causal && cfg->cnn_kernel % 2 == 0)
+            return fail(std::string(fam) + ": cnn_module_kernel (masr_config.cnn_kernel) = " + std::to_string(cfg->cnn_kernel) +
+                        " is not supported with streaming: False (causal = 0): the symmetric padding needs an odd value in [3, 31]");
     }
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
@@ -995,6 +1005,12 @@ FfnTail qkv_tail(const masr_engine* e, const LayerW& w, float* out, int ldo) {
     t.lnw = w.ln_mha_w; t.lnb = w.ln_mha_b; t.W = w.wqkv; t.bias = w.bqkv; t.out = out; t.N = 3 * e->cfg.d_model; t.ldo = ldo;
     return t;
 }
+// a depthwise launch of elementwise.hip; a tap count it has no kernel for is an error, never a launch that did not happen
+#define DWCHK(launched, ktaps)                                                                                        \
+    do {                                                                                                              \
+        if (!(launched)) return fail("no depthwise kernel for cnn_module_kernel " + std::to_string(ktaps) + ": " #launched); \
+    } while (0)
+
 // head stage of a layer's second FFN: the conv module behind pointwise_conv1 + GLU, on the offline GLU buffer (whose causal
 // history rows are the constant glu(bias), not materialised)
 FfnHead conv_head(const masr_engine* e, const LayerW& w, const int* lens, int Tq, int ktaps, int mstride) {
@@ -1030,11 +1046,11 @@ FfnDone ffn(masr_engine* e, hipStream_t s, FfnArgs a) {
         // the rest of the conv module as its own two launches: depthwise conv + LayerNorm + SiLU, pointwise_conv2 + mask + residual
         CHK(e->dwo.ensure((size_t)M * d * sizeof(float)));
         if (head.norm == 1)
-            launch_dwconv_bn_silu(head.glu, head.dw_w, head.dw_b, head.lnw, head.lnb, e->dwo.as<float>(), M / head.seq_t, head.seq_t,
-                                  head.ktaps, s, head.gconst);
+            DWCHK(launch_dwconv_bn_silu(head.glu, head.dw_w, head.dw_b, head.lnw, head.lnb, e->dwo.as<float>(), M / head.seq_t, head.seq_t,
+                                        head.ktaps, s, head.gconst), head.ktaps);
         else
-            launch_dwconv_ln_silu(head.glu, head.dw_w, head.dw_b, head.lnw, head.lnb, e->dwo.as<float>(), M / head.seq_t, head.seq_t,
-                                  head.ktaps, 1e-5f, s, head.gconst);
+            DWCHK(launch_dwconv_ln_silu(head.glu, head.dw_w, head.dw_b, head.lnw, head.lnb, e->dwo.as<float>(), M / head.seq_t, head.seq_t,
+                                        head.ktaps, 1e-5f, s, head.gconst), head.ktaps);
         RowGemmArgs g = rg_args(e->dwo.as<float>(), d, head.W, head.bias, x, d, M, d);
         g.R = x; g.ldr = d; g.lens = head.lens; g.mask_tp = head.lens ? head.seq_t : 0; g.mstride = head.mstride;
         rowgemm(e, s, RG_PRO_PLAIN, RG_EPI_RESID, g);
@@ -1289,10 +1305,10 @@ int conv_module(masr_engine* e, hipStream_t s, const LayerW& w, const EncodeCtx&
         if (!e->conv_bn && knobs().few_rows_path && launch_rowgemm(a, RG_PRO_DWCONV, RG_EPI_RESID, s)) return 0;
     }
     if (e->conv_bn)        // BatchNorm build: the depthwise kernel's BN variant (the Squeezeformer's), then pointwise_conv2
-        launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), c.nseq, c.Tq, K, s, gconst);
+        DWCHK(launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), c.nseq, c.Tq, K, s, gconst), K);
     else
-        launch_dwconv_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), c.nseq, c.Tq, K,
-                              1e-5f, s, gconst);
+        DWCHK(launch_dwconv_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), c.nseq, c.Tq, K,
+                                    1e-5f, s, gconst), K);
     {
         RowGemmArgs g = rg_args(e->dwo.as<float>(), d, w.pw2_w, w.pw2_b, x, d, M, d);
         g.R = x; g.ldr = d; g.lens = c.lens; g.mask_tp = c.lens ? c.Tq : 0; g.mstride = mstride;
@@ -1333,10 +1349,10 @@ int conv_module_stream(masr_engine* e, hipStream_t s, const LayerW& w, int n, in
         //  variant, then pointwise_conv2 on the small-M kernel)
         if (e->conv_bn || !launch_rowgemm(a, RG_PRO_DWCONV, RG_EPI_RESID, s)) {
             if (e->conv_bn)
-                launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K, s, nullptr);
+                DWCHK(launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K, s, nullptr), K);
             else
-                launch_dwconv_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K, 1e-5f, s,
-                                      nullptr);
+                DWCHK(launch_dwconv_ln_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), n, Tq, K, 1e-5f, s,
+                                            nullptr), K);
             a.A = e->dwo.as<float>();
             launch_rowgemm(a, RG_PRO_PLAIN, RG_EPI_RESID, s);
         }
@@ -1644,7 +1660,7 @@ static int finalize_squeezeformer(masr_engine* e, hipStream_t s) {
 // SqueezeformerEncoder.forward, streaming = False (squeezeformer/encoder.py:168-216)
 static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float* feats, const int* lens, int B, int T,
                                      float* enc_out, int chunk) {
-    const int d = e->cfg.d_model, H = e->cfg.heads, K = e->cfg.cnn_kernel, half = (K - 1) / 2;
+    const int d = e->cfg.d_model, H = e->cfg.heads, K = e->cfg.cnn_kernel, half = (K - 1) / 2, pad = K - 1;
     int T0 = 0;
     // Row blocks / tiles that hold padded frames only are not computed (the valid frames' results do not depend on them: pad masks,
     // klen; reference encoder.py:168-216 computes and masks them): conv2, the input projection, attention (queries and keys stop at the
@@ -1664,7 +1680,7 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
     const bool causal = e->cfg.causal != 0;   // streaming-trained build: K-1 history rows in front (constant glu(bias))
     const int pad_l = causal ? K - 1 : half;
     auto new_resolution = [&]() -> int {     // zero the symmetric pad rows of the GLU buffer, rebuild the descriptors
-        if (!causal) HIPCHK(hipMemsetAsync(e->glu.p, 0, (size_t)B * (Tq + 2 * half) * d * sizeof(float), s));
+        if (!causal) HIPCHK(hipMemsetAsync(e->glu.p, 0, (size_t)B * (Tq + pad) * d * sizeof(float), s));
         launch_attseq_full(e->attseq.as<AttSeq>(), e->qkv.as<float>(), e->att.as<float>(), lens, B, Tq, mstride, s, (skm & 4) ? 1 : 0);
         return 0;
     };
@@ -1716,7 +1732,7 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
             a.ffn_s = w.f1_s; a.ffn_b = w.f1_b; a.b1 = w.f1_b1; a.b2 = w.f1_b2;
             CHK(packed_ffn_of(e, w.f1_w1, w.f1_w2, s, &a.w1, &a.w2));
             a.tail_w = packed_rows_of(e, w.pw1_w, 2 * d, s); a.tail_b = w.pw1_b; a.tail_s = w.cv_s; a.tail_sb = w.cv_b; a.tail_n = 2 * d;
-            a.glu_out = e->glu.as<float>(); a.glu_pad_l = pad_l; a.glu_pad_tot = 2 * half;
+            a.glu_out = e->glu.as<float>(); a.glu_pad_l = pad_l; a.glu_pad_tot = pad;
             a.lens = lens; a.M = M; a.dff = e->cfg.d_ff; a.seq_t = Tq; a.mstride = mstride; a.ktaps = K; a.eps = 1e-5f; a.skip_pad = skm & 1;
             if (!a.head_w || !a.tail_w) return fail("squeezeformer: packing the layer's weights failed");
             {
@@ -1760,11 +1776,11 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
         {
             RowGemmArgs g = rg_args(x, d, w.pw1_w, w.pw1_b, e->glu.as<float>(), d, M, 2 * d);
             g.lnw = w.cv_s; g.lnb = w.cv_b; g.lens = lens; g.seq_t = Tq; g.mstride = mstride; g.out_seq_t = Tq;
-            g.out_pad_l = pad_l; g.out_pad_tot = 2 * half;
+            g.out_pad_l = pad_l; g.out_pad_tot = pad;
             rowgemm(e, s, RG_PRO_AFFINE, RG_EPI_GLU, g);
         }
-        launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.bn_scale, w.bn_shift, e->dwo.as<float>(), B, Tq, K, s,
-                              causal ? w.gconst : nullptr);
+        DWCHK(launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.bn_scale, w.bn_shift, e->dwo.as<float>(), B, Tq, K, s,
+                                    causal ? w.gconst : nullptr), K);
         {
             RowGemmArgs g = rg_args(e->dwo.as<float>(), d, w.pw2_w, w.pw2_b, x, d, M, d);
             g.R = x; g.ldr = d; g.lens = lens; g.mask_tp = Tq; g.mstride = mstride;
@@ -2930,7 +2946,7 @@ static int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector
                 launch_rowgemm(a, RG_PRO_PLAIN, RG_EPI_GLU, s);
             }
         }
-        launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.bn_scale, w.bn_shift, e->dwo.as<float>(), n, Tq, K, s);
+        DWCHK(launch_dwconv_bn_silu(e->glu.as<float>(), w.dw_w, w.dw_b, w.bn_scale, w.bn_shift, e->dwo.as<float>(), n, Tq, K, s), K);
         {
             RowGemmArgs g = rg_args(e->dwo.as<float>(), d, w.pw2_w, w.pw2_b, x, d, M, d);
             g.R = x; g.ldr = d;

@@ -29,9 +29,13 @@ __device__ __forceinline__ float rs_wsum(float v) {
     return wave_sum_dpp(v);
 }
 
+// RG_PRO_DWCONV for 16 .. 32 taps (cnn_module_kernel 31): its own prologue value, known to this file only, so that the kernel
+// of up to 15 taps keeps its code
+constexpr int RS_PRO_DWCONV_LONG = 6;
+
 template <int PRO, int EPI>
 __global__ __launch_bounds__(512) void rowgemm_small_kernel(RowGemmArgs p) {
-    constexpr bool STAGED = PRO == RG_PRO_HIST || PRO == RG_PRO_DWCONV;
+    constexpr bool STAGED = PRO == RG_PRO_HIST || PRO == RG_PRO_DWCONV || PRO == RS_PRO_DWCONV_LONG;
     constexpr int ALD = 256 + 4;
     __shared__ __align__(16) float xch[4 * 2 * 16 * 64];     // [kq][ct][acc register][lane]
     __shared__ float stat[32 * 2];                            // LayerNorm mean / rstd of the 32 rows
@@ -229,6 +233,53 @@ __global__ __launch_bounds__(512) void rowgemm_small_kernel(RowGemmArgs p) {
             if (lr >= 0) *reinterpret_cast<f32x4*>(&at[lr * ALD + lane * 4]) = o;
         }
         __syncthreads();
+    } else if (PRO == RS_PRO_DWCONV_LONG) {
+        // The same rows for 16 .. 32 taps: a window of KT + 3 rows and KT weight rows do not fit the registers of a 512-thread
+        // workgroup next to the GEMM fragments, so both stream through: window row j is loaded once and feeds tap j - rr of the
+        // wave's row rr (rr = 0 .. 3), the four weight rows in use slide along.  Every output row still sums b + w[0] g[t] +
+        // w[1] g[t + 1] ... in tap order (taps outside 0 .. KT - 1 are skipped by a wave-uniform test): dwconv_ln_silu_kernel's
+        // arithmetic.  Rows read: padded rows t .. t + KT + 2 <= pad + seq_t - 1 of stream i (t <= seq_t - 4).
+        const int KT = p.pad + 1;
+        const int row = min(row0 + wave * 4, p.M - 4);
+        const int i = row / p.seq_t, t = row - i * p.seq_t;
+        const float* gin = p.A + ((size_t)i * (p.pad + p.seq_t) + t) * 256 + lane * 4;
+        const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 gc = p.gconst ? *reinterpret_cast<const f32x4*>(p.gconst + lane * 4) : zero4;
+        const f32x4 cb = *reinterpret_cast<const f32x4*>(p.dw_b + lane * 4);
+        const f32x4 lw = *reinterpret_cast<const f32x4*>(p.lnw + lane * 4);
+        const f32x4 lb = *reinterpret_cast<const f32x4*>(p.lnb + lane * 4);
+        f32x4 v4[4] = {cb, cb, cb, cb}, wq[4] = {zero4, zero4, zero4, zero4};      // wq[rr] = w[j - rr]
+#pragma unroll 4
+        for (int j = 0; j < KT + 3; ++j) {
+            f32x4 g = *reinterpret_cast<const f32x4*>(gin + (size_t)j * 256);
+            if (p.gconst && t + j < p.pad) g = gc;       // unmaterialised history of the offline causal conv
+            wq[3] = wq[2]; wq[2] = wq[1]; wq[1] = wq[0];
+            wq[0] = *reinterpret_cast<const f32x4*>(p.dw_w + min(j, KT - 1) * 256 + lane * 4);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr)
+                if (j >= rr && j - rr < KT) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v4[rr][k] = fmaf(wq[rr][k], g[k], v4[rr][k]);
+                }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const f32x4 v = v4[rr];
+            const float mean = rs_wsum(v[0] + v[1] + v[2] + v[3]) * (1.0f / 256.0f);
+            const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
+            const float var = rs_wsum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.0f / 256.0f);
+            const float rstd = 1.0f / sqrtf(var + p.eps);
+            f32x4 o;
+            o[0] = d0 * rstd * lw[0] + lb[0];
+            o[1] = d1 * rstd * lw[1] + lb[1];
+            o[2] = d2 * rstd * lw[2] + lb[2];
+            o[3] = d3 * rstd * lw[3] + lb[3];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = o[k] / (1.0f + expf(-o[k]));
+            const int lr = row - row0 + rr;                                 // (the clamped last group re-writes valid rows)
+            if (lr >= 0) *reinterpret_cast<f32x4*>(&at[lr * ALD + lane * 4]) = o;
+        }
+        __syncthreads();
     }
     if (STAGED) {
 #pragma unroll
@@ -367,9 +418,11 @@ bool launch_rowgemm_small(const RowGemmArgs& a, int pro, int epi, hipStream_t s)
     else if (pro == RG_PRO_DWCONV && epi == RG_EPI_RESID) {
         // groups of 4 rows share one sequence's window: frames per sequence a multiple of 4 -- or ONE sequence (its last group is
         // clamped to the last 4 rows and re-writes valid rows)
-        if (a.pad + 1 > 15 || a.M < 4) return false;
+        // (up to 15 taps: window and weights in registers; 16 .. 32: streamed, RS_PRO_DWCONV_LONG)
+        if (a.pad + 1 < 1 || a.pad + 1 > 32 || a.M < 4) return false;
         if ((a.seq_t % 4 || a.M % 4) && a.M != a.seq_t) return false;
-        launch_rs<RG_PRO_DWCONV, RG_EPI_RESID>(a, s);
+        if (a.pad + 1 <= 15) launch_rs<RG_PRO_DWCONV, RG_EPI_RESID>(a, s);
+        else launch_rs<RS_PRO_DWCONV_LONG, RG_EPI_RESID>(a, s);
     }
     else return false;
     return true;

@@ -191,6 +191,59 @@ __global__ __launch_bounds__(256) void dwconv_ln_silu_wide_kernel(const float* _
     }
 }
 
+// The same for tap counts without an instantiation (dwconv_ln_silu_taps_kernel of elementwise.hip): KMAX = 8 / 16 / 32 registers,
+// the tap count K <= KMAX at run time, tap j in slot KMAX - K + j; same steps in the same order as dwconv_ln_silu_wide_kernel<D, K>.
+template <int D, int KMAX>
+__global__ __launch_bounds__(256) void dwconv_ln_silu_wide_taps_kernel(const float* __restrict__ g, const float* __restrict__ wkc,
+                                                                       const float* __restrict__ bias,
+                                                                       const float* __restrict__ lnw,
+                                                                       const float* __restrict__ lnb, float* __restrict__ out, int K,
+                                                                       int Tq, int in_pad, int pad_l, float eps,
+                                                                       const float* __restrict__ gconst) {
+    __shared__ __align__(16) float tile[WDW_TT][D + 4];
+    const int tiles = (Tq + WDW_TT - 1) / WDW_TT;
+    const int seq = blockIdx.x / tiles;
+    const int t0 = (blockIdx.x % tiles) * WDW_TT;
+    const int nrows = min(WDW_TT, Tq - t0);
+    const int off = KMAX - K;                                                // slot of tap 0
+    const float* gseq = g + ((size_t)seq * (in_pad + Tq) + in_pad) * D;      // frame 0 of this sequence
+    for (int c = threadIdx.x; c < D; c += 256) {
+        float w[KMAX], win[KMAX];
+#pragma unroll
+        for (int jj = 0; jj < KMAX; ++jj) w[jj] = jj >= off ? wkc[(jj - off) * D + c] : 0.f;
+        const float bv = bias[c];
+        const float gc = gconst ? gconst[c] : 0.f;
+        auto frame = [&](int ti) -> float {
+            if (ti >= Tq) return 0.f;
+            if (ti >= -in_pad) return gseq[(long)ti * D + c];
+            return gc;
+        };
+        win[0] = 0.f;
+#pragma unroll
+        for (int jj = 1; jj < KMAX; ++jj) win[jj] = jj - 1 < off ? 0.f : frame(t0 + jj - 1 - off - pad_l);
+        for (int r = 0; r < nrows; ++r) {
+#pragma unroll
+            for (int jj = 0; jj < KMAX - 1; ++jj) win[jj] = win[jj + 1];
+            win[KMAX - 1] = frame(t0 + r + K - 1 - pad_l);
+            float acc = bv;                       // out[t] = b + sum_j w[j] * in[t + j - pad_l]
+#pragma unroll
+            for (int jj = 0; jj < KMAX; ++jj)
+                if (jj >= off) acc = fmaf(w[jj], win[jj], acc);
+            tile[r][c] = acc;
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = wave; r < nrows; r += 4) {
+        RowVec<D> o = layernorm_row<D>(load_row<D>(&tile[r][0], lane), lnw, lnb, eps, lane);
+#pragma unroll
+        for (int i = 0; i < RowVec<D>::V; ++i)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o.v[i][k] = o.v[i][k] / (1.0f + expf(-o.v[i][k]));
+        store_row<D>(out + ((size_t)seq * Tq + t0 + r) * D, lane, o);
+    }
+}
+
 // streaming conv-module front (conv_hist_kernel, LayerNorm variant): lnpad[i][tp] = tp < pad ? cache_rd[i][tp] :
 // LayerNorm(x[i][tp - pad]); cache_wr[i][r] = lnpad[i][Tq + r].  One wave per padded row.
 template <int D>
@@ -274,11 +327,22 @@ void launch_glu_const_wide(const float* bias2d, float* out, int d, hipStream_t s
 bool launch_dwconv_ln_silu_wide(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb, float* out,
                                 int nseq, int Tq, int d, int ktaps, int in_pad, int pad_l, float eps, const float* gconst,
                                 hipStream_t s) {
-    if (d != 512 || ktaps != 15) return false;
+    if (d != 512 || ktaps < 1 || ktaps > 32) return false;
     if (nseq * Tq <= 0) return true;
     const int tiles = (Tq + WDW_TT - 1) / WDW_TT;
-    hipLaunchKernelGGL((dwconv_ln_silu_wide_kernel<512, 15>), dim3(nseq * tiles), dim3(256), 0, s, g, wkc, bias, lnw, lnb, out, Tq,
-                       in_pad, pad_l, eps, gconst);
+    const dim3 grid(nseq * tiles), blk(256);
+    if (ktaps == 15)
+        hipLaunchKernelGGL((dwconv_ln_silu_wide_kernel<512, 15>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, Tq, in_pad, pad_l, eps,
+                           gconst);
+    else if (ktaps <= 8)
+        hipLaunchKernelGGL((dwconv_ln_silu_wide_taps_kernel<512, 8>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, in_pad,
+                           pad_l, eps, gconst);
+    else if (ktaps <= 16)
+        hipLaunchKernelGGL((dwconv_ln_silu_wide_taps_kernel<512, 16>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, in_pad,
+                           pad_l, eps, gconst);
+    else
+        hipLaunchKernelGGL((dwconv_ln_silu_wide_taps_kernel<512, 32>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, in_pad,
+                           pad_l, eps, gconst);
     return true;
 }
 

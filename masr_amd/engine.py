@@ -89,9 +89,38 @@ def reference_gains(mean_square, target_db, max_gain_db=300.0):
     return out
 
 
-def _validate_encoder_conf(use_model, enc, state_dict):
+CNN_KERNEL_DEFAULT = {'conformer': 15, 'efficient_conformer': 15, 'squeezeformer': 31}
+CNN_KERNEL_MIN, CNN_KERNEL_MAX = 3, 31
+
+
+def _validate_cnn_kernel(use_model, enc, state_dict, streaming):
+    """``encoder_conf.cnn_module_kernel`` (masr_create repeats the range and parity checks): every integer from 3 to 31 on a
+    ``streaming: True`` build, the odd ones on a ``streaming: False`` build (the symmetric padding is ``(K - 1) / 2`` frames on each
+    side; the reference asserts it), 15 only for the Efficient Conformer (its stride layer halves the kernel).  ``streaming=None``:
+    not known, the parity check is skipped.  The value has to be the checkpoint's own."""
+    k = enc.get('cnn_module_kernel', CNN_KERNEL_DEFAULT.get(use_model, 15))
+    head = f'{use_model}: encoder_conf.cnn_module_kernel={k!r} is not supported: '
+    if use_model == 'efficient_conformer':
+        if isinstance(k, bool) or not isinstance(k, int) or k != 15:
+            raise _lib.MasrError(head + '15 only (the stride layer halves the kernel: the kernels are built around 15 / 7)')
+    else:
+        accepted = (f'an integer from {CNN_KERNEL_MIN} to {CNN_KERNEL_MAX} with streaming: True, an odd one with streaming: False')
+        if isinstance(k, bool) or not isinstance(k, int) or not CNN_KERNEL_MIN <= k <= CNN_KERNEL_MAX:
+            raise _lib.MasrError(head + accepted)
+        if streaming is not None and not streaming and k % 2 == 0:
+            raise _lib.MasrError(head + f'streaming: False pads (K - 1) / 2 frames on each side ({accepted})')
+    key = 'encoder.encoders.0.conv_module.depthwise_conv.weight'
+    if state_dict is not None and key in state_dict:
+        have = int(state_dict[key].shape[-1])
+        if have != k:
+            raise _lib.MasrError(f'{use_model}: encoder_conf.cnn_module_kernel={k} but the checkpoint was trained with '
+                                 f'cnn_module_kernel={have} ({key} is {list(state_dict[key].shape)})')
+
+
+def _validate_encoder_conf(use_model, enc, state_dict, streaming=None):
     """The kernels implement exactly the module variants the shipped YAMLs select; anything else must fail here instead of
-    loading cleanly into the wrong arithmetic (e.g. ``cnn_module_norm: batch_norm`` has LayerNorm-shaped ``norm.weight``)."""
+    loading cleanly into the wrong arithmetic (e.g. ``cnn_module_norm: batch_norm`` has LayerNorm-shaped ``norm.weight``).
+    ``streaming``: the build, where the caller knows it (``cnn_module_kernel`` has to be odd on a ``streaming: False`` one)."""
     def want(key, allowed, default):
         v = enc.get(key, default)
         if v not in allowed:
@@ -110,6 +139,7 @@ def _validate_encoder_conf(use_model, enc, state_dict):
             if enc.get('input_layer', 'conv2d') != 'conv2d':
                 raise _lib.MasrError(f'conformer: encoder_conf.input_layer={enc.get("input_layer")!r} is implemented at output_size '
                                      f'256 only (output_size 512 takes conv2d)')
+        _validate_cnn_kernel(use_model, enc, state_dict, streaming)
     if use_model in ('conformer', 'efficient_conformer'):
         # batch_norm (conformer/convolution.py:60-67, eval-mode statistics folded into scale / shift): Conformer in the full-context
         # forward only, Efficient Conformer full-context and chunked.  An absent key means layer_norm here for both families (the
@@ -183,7 +213,7 @@ class HipEngine:
             vocab_size = int(state_dict[ctc_key].shape[0]) if state_dict is not None else 1
         self.device = torch.device('cuda', device)
         torch.cuda.set_device(self.device)
-        _validate_encoder_conf(use_model, enc, state_dict)
+        _validate_encoder_conf(use_model, enc, state_dict, bool(streaming))
         if use_model == 'deepspeech2':
             _validate_rnn_size(enc, state_dict)
         # subsampling front-end (Conformer / Efficient Conformer; the other models have their own)
