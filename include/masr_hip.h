@@ -446,6 +446,22 @@ int masr_op_layernorm(masr_engine* e, const float* x_dev, const float* w_dev, co
                       int32_t M, float eps, void* stream);
 int masr_op_gemm(masr_engine* e, const float* a_dev, const float* w_dev, const float* bias_dev, const float* res_dev,
                  float* c_dev, int32_t M, int32_t N, int32_t K, int32_t act, float alpha, void* stream);
+/* One relative-position attention launch on the caller's buffers: builds the per-sequence descriptor table from the host arrays
+ * [nseq] and calls the launcher the encoder calls, so the process-wide switches (keys 7, 14, 26, 28) pick the kernel as they do
+ * in a forward pass.  group = 1: q rows of q_stride floats, k / v rows of kv_stride floats (>= heads * 64), out rows of heads * 64;
+ * key j of a sequence reads positional row pos0 + pos_stride * j of ptab_dev [n_pos, heads * 64].  group = 3 (4 heads): q / k / v /
+ * out are planar, zero-padded [3 * nq, 256] = [nq, 4, 192] buffers (both strides 768), ptab frames pos0 .. pos0 + t_true - 1 are
+ * read and frames from t_true on count as zero, pos_stride is not used.  *_off: element offsets of a sequence's first row from the
+ * buffer's pointer; keys j >= klen are masked; chunk_size > 0 adds the chunk mask of query q_abs0 + i (group 3: of frame 3 i).
+ * Returns when the launch has finished.  Non-zero: a null pointer, nseq <= 0, heads other than 4 / 8, group other than 1 / 3, a
+ * negative count or offset, klen > nk, a stride below heads * 64, strides / offsets / pointers that are not 16-byte aligned, a
+ * positional table shorter than the rows the keys name. */
+int masr_op_attention(masr_engine* e, const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev,
+                      const float* ptab_dev, int32_t n_pos, const float* bias_u_dev, const float* bias_v_dev, int32_t nseq,
+                      const int64_t* q_off, const int64_t* k_off, const int64_t* v_off, const int64_t* out_off, const int32_t* nq,
+                      const int32_t* nk, const int32_t* klen, const int32_t* pos0, const int32_t* q_abs0, int32_t heads,
+                      int32_t q_stride, int32_t kv_stride, int32_t chunk_size, int32_t pos_stride, int32_t group, int32_t t_true,
+                      void* stream);
 
 /* Side streams owned by the library: kind 0 / 1 = prefix searches of consecutive device passes, 2 = per-pass preparation (upload,
  * mean squares, gains), 3 = copies, 4 = the encoder passes of lane 1 (masr_select_lane).  One set per DEVICE, made with the first

@@ -3311,6 +3311,76 @@ int masr_op_gemm(masr_engine* e, const float* a_dev, const float* w_dev, const f
     return 0;
 }
 
+int masr_op_attention(masr_engine* e, const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev,
+                      const float* ptab_dev, int32_t n_pos, const float* bias_u_dev, const float* bias_v_dev, int32_t nseq,
+                      const int64_t* q_off, const int64_t* k_off, const int64_t* v_off, const int64_t* out_off, const int32_t* nq,
+                      const int32_t* nk, const int32_t* klen, const int32_t* pos0, const int32_t* q_abs0, int32_t heads,
+                      int32_t q_stride, int32_t kv_stride, int32_t chunk_size, int32_t pos_stride, int32_t group, int32_t t_true,
+                      void* stream) {
+    // every refusal comes before the engine is touched: none of them needs a device
+    if (!q_dev || !k_dev || !v_dev || !out_dev || !ptab_dev || !bias_u_dev || !bias_v_dev || !q_off || !k_off || !v_off ||
+        !out_off || !nq || !nk || !klen || !pos0 || !q_abs0)
+        return fail("masr_op_attention: null argument");
+    if (nseq <= 0) return fail("masr_op_attention: nseq must be positive");
+    if (heads != 4 && heads != 8) return fail("masr_op_attention: heads must be 4 or 8");
+    if (group != 1 && group != 3) return fail("masr_op_attention: group must be 1 or 3");
+    const int w = heads * 64;
+    if (q_stride < w || kv_stride < w) return fail("masr_op_attention: q_stride and kv_stride must be at least heads * 64");
+    if (group == 3 && (heads != 4 || q_stride != 3 * w || kv_stride != 3 * w))
+        return fail("masr_op_attention: the grouped kernels take 4 heads and planar rows of heads * 192 floats");
+    if (chunk_size < 0 || pos_stride < 1 || n_pos < 0 || t_true < 0)
+        return fail("masr_op_attention: chunk_size, n_pos and t_true must not be negative, pos_stride at least 1");
+    if ((q_stride | kv_stride) & 3) return fail("masr_op_attention: strides must be multiples of 4 floats");
+    for (const void* p : {(const void*)q_dev, (const void*)k_dev, (const void*)v_dev, (const void*)out_dev, (const void*)ptab_dev,
+                          (const void*)bias_u_dev, (const void*)bias_v_dev})
+        if ((uintptr_t)p & 15) return fail("masr_op_attention: device buffers must be 16-byte aligned");
+    int max_nq = 0;
+    std::vector<AttSeq> hs((size_t)nseq);
+    for (int b = 0; b < nseq; ++b) {
+        if (nq[b] < 0 || nk[b] < 0 || klen[b] < 0 || pos0[b] < 0 || q_abs0[b] < 0 || q_off[b] < 0 || k_off[b] < 0 || v_off[b] < 0 ||
+            out_off[b] < 0)
+            return fail("masr_op_attention: negative count or offset in sequence " + std::to_string(b));
+        if (klen[b] > nk[b]) return fail("masr_op_attention: klen > nk in sequence " + std::to_string(b));
+        if ((q_off[b] | k_off[b] | v_off[b] | out_off[b]) & 3)
+            return fail("masr_op_attention: offsets must be multiples of 4 floats");
+        if ((int64_t)nk[b] * kv_stride >= ((int64_t)1 << 30))
+            return fail("masr_op_attention: the key rows of one sequence must span less than 4 GiB");
+        // the last positional row a kernel may read: row pos0 + pos_stride * (nk - 1); grouped: frame pos0 + min(t_true, 3 nk) - 1
+        const int64_t last = group == 3 ? (int64_t)pos0[b] + std::min<int64_t>(t_true, 3 * (int64_t)nk[b]) - 1
+                                        : (int64_t)pos0[b] + (int64_t)pos_stride * (nk[b] - 1);
+        if (nk[b] > 0 && last >= n_pos) return fail("masr_op_attention: the positional table is too short for sequence " + std::to_string(b));
+        AttSeq& a = hs[(size_t)b];
+        a.q = q_dev + q_off[b];
+        a.k = k_dev + k_off[b];
+        a.v = v_dev + v_off[b];
+        a.out = out_dev + out_off[b];
+        a.nq = nq[b];
+        a.nk = nk[b];
+        a.klen = klen[b];
+        a.pos0 = pos0[b];
+        a.q_abs0 = q_abs0[b];
+        a.pad_ = 0;
+        max_nq = std::max(max_nq, nq[b]);
+    }
+    if (!e) return fail("null engine");
+    ENTER(e);
+    hipStream_t s = (hipStream_t)stream;
+    struct Table {
+        AttSeq* p = nullptr;
+        ~Table() { if (p) (void)hipFree(p); }
+    } tab;
+    HIPCHK(hipMalloc((void**)&tab.p, hs.size() * sizeof(AttSeq)));
+    HIPCHK(hipMemcpyAsync(tab.p, hs.data(), hs.size() * sizeof(AttSeq), hipMemcpyHostToDevice, s));
+    {
+        ProfScope ps(e, s, PROF_ATT, 6.0 * w * (double)max_nq * max_nq * nseq);
+        if (group > 1) launch_attention_grouped(tab.p, nseq, max_nq, heads, group, ptab_dev, t_true, bias_u_dev, bias_v_dev, s, chunk_size);
+        else launch_attention(tab.p, nseq, max_nq, heads, q_stride, kv_stride, ptab_dev, bias_u_dev, bias_v_dev, chunk_size, pos_stride, s, w);
+    }
+    LAUNCHCHK();
+    HIPCHK(hipStreamSynchronize(s));       // the table is freed, and the host copy leaves scope, behind the kernel
+    return 0;
+}
+
 int masr_select_lane(masr_engine* e, int32_t lane) {
     if (!e) return fail("null engine");
     if (lane < 0 || lane >= MASR_LANES) return fail("masr_select_lane: lane must be in [0, " + std::to_string(MASR_LANES) + ")");

@@ -681,6 +681,20 @@ class HipEngine:
                                     float(alpha), _stream()))
         return c
 
+    def op_attention(self, q, k, v, out, ptab, bias_u, bias_v, seqs, heads, q_stride, kv_stride, chunk_size=0, pos_stride=1,
+                     group=1, t_true=0):
+        """masr_op_attention: one attention launch on the caller's device buffers, written into ``out`` in place.  ``seqs``: one
+        dict per sequence with the element offsets ``q_off`` / ``k_off`` / ``v_off`` / ``out_off`` of its first rows from the
+        buffers' pointers and ``nq``, ``nk``, ``klen``, ``pos0``, ``q_abs0``."""
+        n = len(seqs)
+        col = lambda name, ct: (ct * max(n, 1))(*[int(s[name]) for s in seqs])
+        check(self.lib.masr_op_attention(
+            self.h, _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(ptab), ptab.shape[0], _ptr(bias_u), _ptr(bias_v), n,
+            col('q_off', C.c_int64), col('k_off', C.c_int64), col('v_off', C.c_int64), col('out_off', C.c_int64),
+            col('nq', C.c_int32), col('nk', C.c_int32), col('klen', C.c_int32), col('pos0', C.c_int32), col('q_abs0', C.c_int32),
+            int(heads), int(q_stride), int(kv_stride), int(chunk_size), int(pos_stride), int(group), int(t_true), _stream()))
+        return out
+
     def profile_select(self, kind):
         check(self.lib.masr_profile_select(self.h, int(kind)))
 
