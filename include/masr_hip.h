@@ -55,7 +55,15 @@ typedef struct masr_config {
                                 stride layer); conformer: [0] = 1 -> cnn_module_norm: batch_norm (convolution.py:60-67; full-context only);
                                 conformer and efficient_conformer: [3] input_layer, 0 = conv2d (x4), 1 = conv2d6 (x6), 2 = conv2d8 (x8)
                                 (conformer/subsampling.py:65-211); deepspeech2 (model_kind 3): [0] recurrent cell, 0 = LSTM,
-                                1 = GRU (encoder_conf.use_gru, deepspeech2/encoder.py:21-33), any other value is refused */
+                                1 = GRU (encoder_conf.use_gru, deepspeech2/encoder.py:21-33), any other value is refused;
+                                conformer: [2] pos_enc_layer_type (conformer/encoder.py:239-281), 0 = rel_pos (RelPositionalEncoding +
+                                RelPositionMultiHeadedAttention), 1 = abs_pos (PositionalEncoding: x * sqrt(d) + pe[offset : offset + T],
+                                plain MultiHeadedAttention), 2 = no_pos (NoPositionalEncoding: x unscaled, plain attention), at
+                                (256, 4) and (512, 8), every entry point; 1 and 2 load checkpoints WITHOUT self_attn.linear_pos /
+                                pos_bias_u / pos_bias_v (masr_finalize refuses one that holds them, and a rel_pos engine one that
+                                lacks them, naming pos_enc_layer_type and the key) and build no positional key tables.  masr_create
+                                refuses any other value by name, and a non-zero [2] for the squeezeformer (rel_pos only there; the
+                                efficient_conformer's [2] is its group size: that family has no such slot and runs rel_pos only) */
 } masr_config;
 
 const char* masr_last_error(void);
@@ -462,6 +470,13 @@ int masr_op_attention(masr_engine* e, const float* q_dev, const float* k_dev, co
                       const int32_t* nk, const int32_t* klen, const int32_t* pos0, const int32_t* q_abs0, int32_t heads,
                       int32_t q_stride, int32_t kv_stride, int32_t chunk_size, int32_t pos_stride, int32_t group, int32_t t_true,
                       void* stream);
+/* The same for the plain attention of pos_enc_layer_type abs_pos / no_pos (score = q . k^T / sqrt(64): no positional table, no
+ * biases; group 1 only): launch_attention's instantiations with the positional term compiled out, chosen by the same switches
+ * (keys 7, 28; key 14 has nothing to act on).  pos_stride scales the chunk mask only.  Same refusals, under the same name. */
+int masr_op_attention_plain(masr_engine* e, const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t nseq,
+                            const int64_t* q_off, const int64_t* k_off, const int64_t* v_off, const int64_t* out_off,
+                            const int32_t* nq, const int32_t* nk, const int32_t* klen, const int32_t* q_abs0, int32_t heads,
+                            int32_t q_stride, int32_t kv_stride, int32_t chunk_size, int32_t pos_stride, void* stream);
 
 /* Side streams owned by the library: kind 0 / 1 = prefix searches of consecutive device passes, 2 = per-pass preparation (upload,
  * mean squares, gains), 3 = copies, 4 = the encoder passes of lane 1 (masr_select_lane).  One set per DEVICE, made with the first

@@ -114,6 +114,7 @@ SIGNATURES = {
     'masr_op_layernorm': [_P, _P, _P, _P, _P, _I, _F, _P],
     'masr_op_gemm': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     'masr_op_attention': [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    'masr_op_attention_plain': [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     'masr_side_stream': [_P, _I, C.POINTER(_P)],
     'masr_select_lane': [_P, _I],
     'masr_stage_rows': [_P, C.c_int64, _P, _P, _I, _I, _I],

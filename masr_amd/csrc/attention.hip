@@ -17,6 +17,16 @@
 //  * 1/sqrt(64) = 0.125 is folded into the query fragment (exact power of two).
 //  * the softmax exponentials use __expf (v_exp_f32): 2.5 us of the kernel's 41.7 us at B = 32 x 10 s against the libm expf,
 //    encoder output moves by 4e-6 (tools/perf_ab.py of round 2); all three attention kernels use the same function.
+//
+// Plain attention (pos_enc_layer_type abs_pos / no_pos: MultiHeadedAttention, conformer/attention.py:133-167):
+//     score[i,j] = q_i . k_j / sqrt(d_k)        -- no u / v on the query, no positional keys, the rest as above
+// runs as the POS = 0 instantiations of the tiled and the key-split kernel (attention_kernel<0, 0>, attention_fewq_kernel<0>): the
+// positional term is compiled out -- no ptab loads, no P tile or folded per-key constants in LDS, one 64-wide contraction per key
+// tile -- not fed with zero tables.  launch_attention takes the variant as an explicit argument (common.h AttPos) and chooses
+// between the two kernels on the same launch geometry as for rel_pos.  Resources (gfx950, -O3), plain | rel_pos counterpart:
+//     tiled      124 VGPRs, 34.0 KB LDS | 149 (fold) / 158 (two-term) VGPRs, 51.3 KB LDS      both two workgroups per CU by LDS
+//     key-split  163 VGPRs, 68.0 KB LDS | 235 VGPRs, 68.0 KB LDS                              (the merge buffer: unchanged)
+// The POS = 1 instantiations compile to the instruction streams they had before the parameter existed.
 #include "common.h"
 
 namespace masr {
@@ -72,16 +82,23 @@ static constexpr int V_LD = 68;
 // contraction replaces the 128-wide one: 64 instead of 96 MFMAs per key tile, no P tile in LDS.  Same value up to fp32
 // rounding (the reference's own summation order is not reproduced by either form); FOLD = 0 (masr_debug_set key 14) keeps the
 // two-term contraction for A/B runs.
-template <int FOLD>
+//
+// POS = 0: the plain attention of pos_enc_layer_type abs_pos / no_pos (conformer/attention.py:133-167, MultiHeadedAttention):
+// score[i,j] = q_i . k_j / sqrt(d_k) -- no u / v added to the query, no positional keys.  The positional term is compiled out:
+// no ptab loads, no P tile, no per-key constants (34.0 KB of LDS instead of 51.3 KB), ONE 64-wide contraction per key tile on
+// the raw keys.  ptab / bias_u / bias_v are not read (null).  Masking, online softmax, the merge and the store are the same code.
+template <int FOLD, int POS = 1>
 __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict__ seqs, int q_stride, int kv_stride,
                                                         const float* __restrict__ ptab,
                                                         const float* __restrict__ bias_u,
                                                         const float* __restrict__ bias_v, int chunk_size,
                                                         int pos_stride, int nqb_1d, int heads_1d, int nseq_1d, int row_w) {
-    __shared__ __align__(16) float lds_att[2 * 32 * KP_LD * 2 + 2 * 32 * V_LD + 64];
+    static_assert(POS || !FOLD, "the fold is a rewrite of the positional term: nothing to fold without it");
+    constexpr int LDS_FLOATS = POS ? 2 * 32 * KP_LD * 2 + 2 * 32 * V_LD + 64 : 2 * 32 * KP_LD + 2 * 32 * V_LD;
+    __shared__ __align__(16) float lds_att[LDS_FLOATS];
     float* Ks = lds_att;                       // [2 tiles][32][68]
-    float* Ps = Ks + 2 * 32 * KP_LD;
-    float* Vs = Ps + 2 * 32 * KP_LD;
+    float* Ps = Ks + 2 * 32 * KP_LD;           // (POS only: without it the V tiles follow the K tiles)
+    float* Vs = POS ? Ps + 2 * 32 * KP_LD : Ps;
     float* Cs = Vs + 2 * 32 * V_LD;            // FOLD: [2 tiles][32] per-key constants
 
     // 1-D launch (ATT_XCD_MAP): workgroup ids go round-robin over the 8 XCDs, so id -> (XCD = id % 8, k = id / 8); the query
@@ -115,12 +132,17 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
             const f32x4 q = *reinterpret_cast<const f32x4*>(qrow + 8 * g + 4 * h);
-            const f32x4 u = *reinterpret_cast<const f32x4*>(bias_u + head * DK + 8 * g + 4 * h);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(bias_v + head * DK + 8 * g + 4 * h);
+            if constexpr (POS) {
+                const f32x4 u = *reinterpret_cast<const f32x4*>(bias_u + head * DK + 8 * g + 4 * h);
+                const f32x4 v = *reinterpret_cast<const f32x4*>(bias_v + head * DK + 8 * g + 4 * h);
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                qu[g][s] = FOLD ? q[s] * 0.125f : (q[s] + u[s]) * 0.125f;
-                qv[g][s] = (q[s] + v[s]) * 0.125f;         // unused (dead) when FOLD
+                for (int s = 0; s < 4; ++s) {
+                    qu[g][s] = FOLD ? q[s] * 0.125f : (q[s] + u[s]) * 0.125f;
+                    qv[g][s] = (q[s] + v[s]) * 0.125f;         // unused (dead) when FOLD
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) qu[g][s] = q[s] * 0.125f;
             }
         }
     }
@@ -158,8 +180,8 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
     const unsigned kv_row_bytes = (unsigned)kv_stride * 4u, p_row_bytes = (unsigned)(pos_stride * row_w) * 4u;
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sq.k), 0, (unsigned)sq.nk * kv_row_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sq.v), 0, (unsigned)sq.nk * kv_row_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptab + (size_t)sq.pos0 * row_w), 0,
-                                                                         (unsigned)sq.nk * p_row_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(POS ? ptab + (size_t)sq.pos0 * row_w : sq.k), 0,
+                                                                         (unsigned)sq.nk * p_row_bytes, 0x00020000);      // (POS = 0: never used)
     unsigned kvo[2], po[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -173,7 +195,7 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
         for (int i = 0; i < 2; ++i) {
             pk[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, kvo[i], skv, 0));
             pv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, kvo[i], skv, 0));
-            pp[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(prs, po[i], sp, 0));
+            if constexpr (POS) pp[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(prs, po[i], sp, 0));
         }
     };
 #else
@@ -184,7 +206,7 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
             const int jc = min(j, sq.nk - 1);                      // clamped address, masked below
             pk[i] = *reinterpret_cast<const f32x4*>(sq.k + (size_t)jc * kv_stride + head * DK + sc4);
             pv[i] = *reinterpret_cast<const f32x4*>(sq.v + (size_t)jc * kv_stride + head * DK + sc4);
-            pp[i] = *reinterpret_cast<const f32x4*>(ptab + (size_t)(sq.pos0 + jc * pos_stride) * row_w + head * DK + sc4);
+            if constexpr (POS) pp[i] = *reinterpret_cast<const f32x4*>(ptab + (size_t)(sq.pos0 + jc * pos_stride) * row_w + head * DK + sc4);
             if (j >= sq.nk) { pk[i] = f32x4{0.f, 0.f, 0.f, 0.f}; pv[i] = pk[i]; pp[i] = pk[i]; }
         }
     };
@@ -210,7 +232,7 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
                 if ((tid & 15) == 0) Cs[sti * 32 + r] = c;
             } else {
                 *reinterpret_cast<f32x4*>(&Ks[sti * 32 * KP_LD + r * KP_LD + sc4]) = pk[i];
-                *reinterpret_cast<f32x4*>(&Ps[sti * 32 * KP_LD + r * KP_LD + sc4]) = pp[i];
+                if constexpr (POS) *reinterpret_cast<f32x4*>(&Ps[sti * 32 * KP_LD + r * KP_LD + sc4]) = pp[i];
             }
             *reinterpret_cast<f32x4*>(&Vs[sti * 32 * V_LD + r * V_LD + sc4]) = pv[i];
         }
@@ -239,7 +261,7 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
 #pragma unroll
             for (int s = 0; s < 4; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qu[g][s], st, 0, 0, 0);
         }
-        if (!FOLD) {
+        if constexpr (!FOLD && POS) {
 #pragma unroll
             for (int g = 0; g < 8; ++g) {
                 const f32x4 pf = *reinterpret_cast<const f32x4*>(pb + 8 * g);
@@ -286,8 +308,9 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
 
     // ---- merge the odd-tile state into the even-tile wave of the same query group (through the tile LDS) -------------
     __syncthreads();
-    float* mg = lds_att;                                // [4 query groups][34][64 lanes] floats (34.8 KB <= Ks + Ps)
+    float* mg = lds_att;                                // [4 query groups][34][64 lanes] floats (34.8 KB <= Ks + Ps; POS = 0: == Ks + Vs)
     static_assert(4 * 34 * 64 <= 2 * 2 * 32 * KP_LD, "merge buffer must fit into the K and P tiles");
+    static_assert(4 * 34 * 64 <= LDS_FLOATS, "merge buffer must fit into the tiles");
     if (kh == 1) {
         float* d = mg + (size_t)qg * 34 * 64 + lane;
         d[0] = m_run;
@@ -334,6 +357,9 @@ __global__ __launch_bounds__(512) void attention_kernel(const AttSeq* __restrict
 // online-softmax state; the eight states are merged once through LDS (each wave finishes 4 of the 32 output registers).
 // The K / P / V fragments are read straight from global memory in MFMA operand layout -- all loads of a tile are issued
 // before the first use, no LDS staging, no workgroup barrier before the merge.  Same arithmetic as attention_kernel.
+// POS = 0: the plain attention (see attention_kernel): no u / v, no positional fragments -- 32 instead of 64 score MFMAs and 8
+// fewer 16-byte loads per lane and key tile; ptab / bias_u / bias_v are not read (null).
+template <int POS>
 __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __restrict__ seqs, int q_stride, int kv_stride,
                                                              const float* __restrict__ ptab,
                                                              const float* __restrict__ bias_u,
@@ -357,12 +383,17 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
             const f32x4 q = *reinterpret_cast<const f32x4*>(qrow + 8 * g + 4 * h);
-            const f32x4 u = *reinterpret_cast<const f32x4*>(bias_u + head * DK + 8 * g + 4 * h);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(bias_v + head * DK + 8 * g + 4 * h);
+            if constexpr (POS) {
+                const f32x4 u = *reinterpret_cast<const f32x4*>(bias_u + head * DK + 8 * g + 4 * h);
+                const f32x4 v = *reinterpret_cast<const f32x4*>(bias_v + head * DK + 8 * g + 4 * h);
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                qu[g][s] = (q[s] + u[s]) * 0.125f;
-                qv[g][s] = (q[s] + v[s]) * 0.125f;
+                for (int s = 0; s < 4; ++s) {
+                    qu[g][s] = (q[s] + u[s]) * 0.125f;
+                    qv[g][s] = (q[s] + v[s]) * 0.125f;
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) qu[g][s] = q[s] * 0.125f;
             }
         }
     }
@@ -382,8 +413,8 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
     const unsigned kv_row_bytes = (unsigned)kv_stride * 4u, p_row_bytes = (unsigned)(pos_stride * row_w) * 4u;
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sq.k), 0, (unsigned)sq.nk * kv_row_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sq.v), 0, (unsigned)sq.nk * kv_row_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptab + (size_t)sq.pos0 * row_w), 0,
-                                                                         (unsigned)sq.nk * p_row_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(POS ? ptab + (size_t)sq.pos0 * row_w : sq.k), 0,
+                                                                         (unsigned)sq.nk * p_row_bytes, 0x00020000);      // (POS = 0: never used)
     const unsigned ko = (unsigned)(lane & 31) * kv_row_bytes + (unsigned)(head * DK + 4 * h) * 4u;
     const unsigned po = (unsigned)(lane & 31) * p_row_bytes + (unsigned)(head * DK + 4 * h) * 4u;
     const unsigned vo = (unsigned)(4 * h) * kv_row_bytes + (unsigned)(head * DK + (lane & 31)) * 4u;
@@ -396,9 +427,11 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
 #pragma unroll
         for (int g = 0; g < 8; ++g)
             kf[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, ko + 32u * g, (unsigned)j0 * kv_row_bytes, 0));
+        if constexpr (POS) {
 #pragma unroll
-        for (int g = 0; g < 8; ++g)
-            pf[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(prs, po + 32u * g, (unsigned)j0 * p_row_bytes, 0));
+            for (int g = 0; g < 8; ++g)
+                pf[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(prs, po + 32u * g, (unsigned)j0 * p_row_bytes, 0));
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const unsigned so = (unsigned)(j0 + (r & 3) + 8 * (r >> 2)) * kv_row_bytes;
@@ -409,11 +442,13 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
         // ---- all operand loads of this tile (clamped rows: masked keys get probability 0, times a finite value) ----------
         const int jr = min(j0 + (lane & 31), sq.nk - 1);
         const float* kp = sq.k + (size_t)jr * kv_stride + head * DK + 4 * h;
-        const float* pp = ptab + (size_t)(sq.pos0 + jr * pos_stride) * row_w + head * DK + 4 * h;
 #pragma unroll
         for (int g = 0; g < 8; ++g) kf[g] = *reinterpret_cast<const f32x4*>(kp + 8 * g);
+        if constexpr (POS) {
+            const float* pp = ptab + (size_t)(sq.pos0 + jr * pos_stride) * row_w + head * DK + 4 * h;
 #pragma unroll
-        for (int g = 0; g < 8; ++g) pf[g] = *reinterpret_cast<const f32x4*>(pp + 8 * g);
+            for (int g = 0; g < 8; ++g) pf[g] = *reinterpret_cast<const f32x4*>(pp + 8 * g);
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int jv = min(j0 + (r & 3) + 8 * (r >> 2) + 4 * h, sq.nk - 1);
@@ -431,10 +466,12 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
         for (int g = 0; g < 8; ++g)
 #pragma unroll
             for (int s = 0; s < 4; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[g][s], qu[g][s], st, 0, 0, 0);
+        if constexpr (POS) {
 #pragma unroll
-        for (int g = 0; g < 8; ++g)
+            for (int g = 0; g < 8; ++g)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(pf[g][s], qv[g][s], st, 0, 0, 0);
+                for (int s = 0; s < 4; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(pf[g][s], qv[g][s], st, 0, 0, 0);
+        }
 
         float tmax = -INFINITY;
 #pragma unroll
@@ -498,17 +535,34 @@ __global__ __launch_bounds__(512) void attention_fewq_kernel(const AttSeq* __res
     }
 }
 
+// pos_mode (common.h AttPos): ATT_REL_POS runs the kernels above with the positional term, exactly as before there was a choice;
+// ATT_NO_POS (pos_enc_layer_type abs_pos / no_pos) their POS = 0 instantiations -- the same choice between the key-split and the
+// tiled kernel on the same launch geometry, ptab / bias_u / bias_v unread.  The fold switch (key 14) has nothing to act on there.
 void launch_attention(const AttSeq* seqs, int nseq, int max_nq, int heads, int q_stride, int kv_stride,
                       const float* ptab, const float* bias_u, const float* bias_v, int chunk_size, int pos_stride,
-                      hipStream_t s, int row_w) {
+                      hipStream_t s, int row_w, int pos_mode) {
     if (nseq <= 0 || max_nq <= 0) return;
     const int nqb = (max_nq + 127) / 128;
+    const bool pos = pos_mode == ATT_REL_POS;
     // the key-split kernel (eight waves share 32 queries and split the key tiles) also takes short offline batches, one
     // workgroup per (head, sequence, 32 queries): attention_kernel would give such a batch nqb * heads * nseq workgroups that each
     // walk ALL key tiles in pairs (one 8.4 s utterance: 8 workgroups, 22 us; here 28 workgroups of one tile per wave)
     if (knobs().attention_fewq && (max_nq <= 32 || nqb * heads * nseq < knobs().attention_fewq_wgs)) {
-        hipLaunchKernelGGL(attention_fewq_kernel, dim3(heads, nseq, (max_nq + 31) / 32), dim3(512), 0, s, seqs, q_stride, kv_stride,
-                           ptab, bias_u, bias_v, chunk_size, pos_stride, row_w);
+        if (pos)
+            hipLaunchKernelGGL(attention_fewq_kernel<1>, dim3(heads, nseq, (max_nq + 31) / 32), dim3(512), 0, s, seqs, q_stride, kv_stride,
+                               ptab, bias_u, bias_v, chunk_size, pos_stride, row_w);
+        else
+            hipLaunchKernelGGL(attention_fewq_kernel<0>, dim3(heads, nseq, (max_nq + 31) / 32), dim3(512), 0, s, seqs, q_stride, kv_stride,
+                               nullptr, nullptr, nullptr, chunk_size, pos_stride, row_w);
+        return;
+    }
+    if (!pos) {
+        if (ATT_XCD_MAP)
+            hipLaunchKernelGGL((attention_kernel<0, 0>), dim3(8 * nqb * ((heads * nseq + 7) / 8)), dim3(512), 0, s, seqs, q_stride,
+                               kv_stride, nullptr, nullptr, nullptr, chunk_size, pos_stride, nqb, heads, nseq, row_w);
+        else
+            hipLaunchKernelGGL((attention_kernel<0, 0>), dim3(nqb, heads, nseq), dim3(512), 0, s, seqs, q_stride,
+                               kv_stride, nullptr, nullptr, nullptr, chunk_size, pos_stride, 0, heads, nseq, row_w);
         return;
     }
     const int fold = knobs().attention_fold;

@@ -468,10 +468,18 @@ bool launch_attn_chain(const AttnChainArgs& a, int max_nq, hipStream_t s);
 #else
 inline bool launch_attn_chain(const AttnChainArgs&, int, hipStream_t) { return false; }
 #endif
+// encoder_conf.pos_enc_layer_type of the Conformer (masr_config.reserved[2]; conformer/encoder.py:239-281)
+enum PosEnc { POS_ENC_REL = 0, POS_ENC_ABS = 1, POS_ENC_NONE = 2 };
+// which instantiations launch_attention runs: with the relative-position term, or the plain q . k^T / sqrt(d_k) of
+// MultiHeadedAttention (abs_pos and no_pos alike: they differ in the embedding only)
+enum AttPos { ATT_REL_POS = 0, ATT_NO_POS = 1 };
 // row_w = heads * 64: the row stride of AttSeq::out and of ptab [max_pos, row_w] (256; the wide Conformer path: 512)
+// pos_mode ATT_NO_POS: ptab / bias_u / bias_v are not read (may be null), pos_stride still scales the chunk mask
 void launch_attention(const AttSeq* seqs, int nseq, int max_nq, int heads, int q_stride, int kv_stride,
                       const float* ptab /*[max_pos,row_w]*/, const float* bias_u, const float* bias_v,
-                      int chunk_size, int pos_stride, hipStream_t s, int row_w);
+                      int chunk_size, int pos_stride, hipStream_t s, int row_w, int pos_mode);
+// x [nseq * Tq, d] += pe[offs[b] + t] (abs_pos embedding; offs == nullptr: offset 0); rows at or past n_pos are not touched
+void launch_add_pos_rows(float* x, const float* pe, const int* offs, int nseq, int Tq, int d, int n_pos, hipStream_t s);
 void launch_attention_grouped(const AttSeq* seqs, int nseq, int max_nq, int heads, int group, const float* ptab,
                               int t_true, const float* bias_u, const float* bias_v, hipStream_t s, int chunk_size = 0);
 void launch_attseq_grouped(AttSeq* seqs, const float* q, const float* k, const float* v, float* out, const int* lens,

@@ -711,6 +711,27 @@ void launch_sub_lens(const int* lens, int B, int rate, int* out, hipStream_t s) 
     hipLaunchKernelGGL(sub_lens_kernel, dim3((B + 63) / 64), dim3(64), 0, s, lens, B, rate, out);
 }
 
+// abs_pos embedding (conformer/embedding.py:52-54): x[b, t, :] += pe[offs[b] + t, :] behind the input projection's (W.x + b) * sqrt(d).
+// One thread per float4; d is a multiple of 4 (256 / 512).  A row past the table (the callers refuse it before) is left alone.
+__global__ __launch_bounds__(256) void add_pos_rows_kernel(float* __restrict__ x, const float* __restrict__ pe,
+                                                           const int* __restrict__ offs, int nseq, int Tq, int d4, int n_pos) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nseq * Tq * d4) return;
+    const int row = i / d4, c = i - row * d4;
+    const int b = row / Tq, t = row - b * Tq;
+    const int p = (offs ? offs[b] : 0) + t;
+    if (p < 0 || p >= n_pos) return;
+    f32x4 v = reinterpret_cast<f32x4*>(x)[i];
+    const f32x4 q = reinterpret_cast<const f32x4*>(pe)[(size_t)p * d4 + c];
+    v[0] += q[0]; v[1] += q[1]; v[2] += q[2]; v[3] += q[3];
+    reinterpret_cast<f32x4*>(x)[i] = v;
+}
+void launch_add_pos_rows(float* x, const float* pe, const int* offs, int nseq, int Tq, int d, int n_pos, hipStream_t s) {
+    const long n4 = (long)nseq * Tq * (d / 4);
+    if (n4 <= 0) return;
+    hipLaunchKernelGGL(add_pos_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, x, pe, offs, nseq, Tq, d / 4, n_pos);
+}
+
 // stream caches -> reference layouts (encoder.py:404-419): att [L,H,t,2dk], cnn [L,1,d,pad]
 // rate = 2: the layer keeps its cache at half the frame rate; the reference layout repeats every entry (encoder.py:347)
 __global__ void export_att_kernel(const float* __restrict__ cache, float* __restrict__ out, int H, int cap, int t,

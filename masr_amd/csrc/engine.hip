@@ -233,10 +233,11 @@ struct EngineWs {
     DevBuf x1, x2, x, ln, hid, qkv, att, lnpad, glu, dwo, logits, feats, enc, idx, maxp, attseq, gain, nframes, lens, xsave,
         xred, xh;      // xh: rows updated by the head stage of a d_ff-split FFN launch (few rows)
     DevBuf x3, sublens;   // conv2d8: the third subsampling conv's output; conv2d6 / conv2d8: the lengths in conv2d units (sub_lens)
+    DevBuf posoff;        // abs_pos chunk steps: the streams' offsets (first positional row of each stream's new frames)
     void release_all() {
         for (DevBuf* b : {&gx, &rnn_out, &hstate, &cstate, &ds2_lens, &qplanes, &attp, &cnnptrs, &ffpart, &fb_scratch, &x1, &x2, &x,
                           &ln, &hid, &qkv, &att, &lnpad, &glu, &dwo, &logits, &feats, &enc, &idx, &maxp, &attseq, &gain, &nframes,
-                          &lens, &xsave, &xred, &xh, &x3, &sublens})
+                          &lens, &xsave, &xred, &xh, &x3, &sublens, &posoff})
             b->release();
         stage.release();
     }
@@ -289,6 +290,7 @@ struct masr_engine : EngineWs {
     int input_layer = IL_CONV2D;     // Conformer / Efficient-Conformer subsampling front-end (cfg.reserved[3], common.h InputLayer)
     bool conv_bn = false;            // cnn_module_norm: batch_norm (Conformer: cfg.reserved[0] = 1, Efficient Conformer: cfg.reserved[4] = 1): LayerW::cln_w / cln_b hold the folded scale / shift
     bool ds2_gru = false;            // DeepSpeech2 with use_gru: True (cfg.reserved[0] = 1): nn.GRU recurrent layers (gru.hip)
+    int pos_enc = POS_ENC_REL;       // Conformer pos_enc_layer_type (cfg.reserved[2], common.h PosEnc): rel_pos, abs_pos or no_pos
     // fbank tables
     float *window = nullptr, *melwt = nullptr, *tw512 = nullptr, *twr4 = nullptr;
     FbankTables fbank_tables() const { return FbankTables{window, melwt, tw512, twr4, mel_lo}; }
@@ -663,6 +665,14 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
             return fail("output_size " + std::to_string(cfg->d_model) + ": input_layer must be conv2d (conv2d6 / conv2d8 are implemented at "
                         "output_size 256 only)");
     }
+    // pos_enc_layer_type: the Conformer's slot is reserved[2]; the Squeezeformer leaves that slot unused and runs rel_pos only (the
+    // Efficient Conformer keeps its group size there and has no slot for a mode: rel_pos only as well)
+    if (cfg->model_kind == 0 && (cfg->reserved[2] < POS_ENC_REL || cfg->reserved[2] > POS_ENC_NONE))
+        return fail("conformer: pos_enc_layer_type (masr_config.reserved[2]) must be 0 = rel_pos, 1 = abs_pos or 2 = no_pos, got " +
+                    std::to_string(cfg->reserved[2]));
+    if (cfg->model_kind == 1 && cfg->reserved[2] != 0)
+        return fail("squeezeformer: pos_enc_layer_type (masr_config.reserved[2]) = " + std::to_string(cfg->reserved[2]) +
+                    " is not supported: rel_pos (0) only; abs_pos / no_pos are implemented for the conformer (model_kind 0)");
     if (cfg->model_kind == 2) {
         // (the stride layer halves the kernel: its kernels are built around 15 / 7)
         if (cfg->cnn_kernel != 15)
@@ -695,6 +705,7 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
     e->conv_bn = (cfg->model_kind == 0 && cfg->reserved[0] == 1) || (cfg->model_kind == 2 && cfg->reserved[4] == 1);
     e->ds2_gru = cfg->model_kind == 3 && cfg->reserved[0] == 1;
     e->recover_idx = cfg->model_kind == 1 ? cfg->reserved[1] : -1;
+    e->pos_enc = cfg->model_kind == 0 ? cfg->reserved[2] : POS_ENC_REL;
     if (cfg->model_kind == 0 || cfg->model_kind == 2) {
         if (cfg->reserved[3] < IL_CONV2D || cfg->reserved[3] > IL_CONV2D8) {
             delete e;
@@ -910,10 +921,23 @@ int masr_finalize(masr_engine* e, void* stream) {
         }
         CHK(up(e, p + "self_attn.linear_out.weight", {d, d}, &w.wo));
         CHK(up(e, p + "self_attn.linear_out.bias", {d}, &w.bo));
-        CHK(up(e, p + "self_attn.linear_pos.weight", {d, d}, &w.wpos));
         const int gk = layer_grouped(e, i) ? dk * e->group_size : dk;
-        CHK(up(e, p + "self_attn.pos_bias_u", {H, gk}, &w.pos_u));
-        CHK(up(e, p + "self_attn.pos_bias_v", {H, gk}, &w.pos_v));
+        if (e->pos_enc == POS_ENC_REL) {
+            for (const char* key : {"self_attn.linear_pos.weight", "self_attn.pos_bias_u", "self_attn.pos_bias_v"})
+                if (!e->host.count(p + key))
+                    return fail("pos_enc_layer_type rel_pos but the checkpoint has no " + p + key +
+                                " (a checkpoint trained with abs_pos / no_pos: plain MultiHeadedAttention)");
+            CHK(up(e, p + "self_attn.linear_pos.weight", {d, d}, &w.wpos));
+            CHK(up(e, p + "self_attn.pos_bias_u", {H, gk}, &w.pos_u));
+            CHK(up(e, p + "self_attn.pos_bias_v", {H, gk}, &w.pos_v));
+        } else {
+            // plain MultiHeadedAttention (conformer/attention.py:10-167) has none of the three; a checkpoint that holds one was
+            // trained with rel_pos
+            for (const char* key : {"self_attn.linear_pos.weight", "self_attn.pos_bias_u", "self_attn.pos_bias_v"})
+                if (e->host.count(p + key))
+                    return fail(std::string("pos_enc_layer_type ") + (e->pos_enc == POS_ENC_ABS ? "abs_pos" : "no_pos") +
+                                " but the checkpoint holds " + p + key + " (a checkpoint trained with rel_pos)");
+        }
         CHK(up(e, p + "conv_module.pointwise_conv1.weight", {2 * d, d, 1}, &w.pw1_w));   // rows: value c, gate d + c
         CHK(up(e, p + "conv_module.pointwise_conv1.bias", {2 * d}, &w.pw1_b));
         if (d == 256) {   // [Wo; W_pw1] and [bo; b_pw1]: one continuous weight stream for the fused kernel of the offline path
@@ -945,7 +969,7 @@ int masr_finalize(masr_engine* e, void* stream) {
         }
         CHK(up(e, p + "conv_module.pointwise_conv2.weight", {d, d, 1}, &w.pw2_w));
         CHK(up(e, p + "conv_module.pointwise_conv2.bias", {d}, &w.pw2_b));
-        {   // positional keys p_j = W_pos * PE(j) for every position, once (attention.py:229-231)
+        if (e->pos_enc == POS_ENC_REL) {   // positional keys p_j = W_pos * PE(j) for every position, once (attention.py:229-231)
             void* pt = nullptr;
             HIPCHK(hipMalloc(&pt, (size_t)e->cfg.max_pos * d * sizeof(float)));
             e->owned.push_back(pt);
@@ -1219,7 +1243,8 @@ int embed(masr_engine* e, hipStream_t s, const float* feats, int nseq, int T, in
     {   // Conformer: (W.x + b) * sqrt(d)  (embedding.py:97);  Squeezeformer: W.(x * sqrt(d)) + b  (subsampling.py:72-75)
         GemmArgs a{};
         a.A = xs; a.lda = F2 * d; a.W = e->embed_w; a.bias = e->embed_b; a.C = e->x.as<float>(); a.ldc = d;
-        a.M = M; a.N = d; a.K = F2 * d; a.act = ACT_NONE; a.alpha = sqrtf((float)d);
+        // (no_pos: NoPositionalEncoding returns x as it is -- no xscale, embedding.py:104-117)
+        a.M = M; a.N = d; a.K = F2 * d; a.act = ACT_NONE; a.alpha = e->pos_enc == POS_ENC_NONE ? 1.f : sqrtf((float)d);
         a.bias_after_alpha = e->cfg.model_kind == 1 ? 1 : 0;
         if (skip_lens) { a.lens = skip_lens; a.skip_rps = Tq; a.skip_div = 1; }
         ProfScope ps(e, s, PROF_GEMM, 2.0 * M * (double)d * F2 * d);
@@ -1250,6 +1275,17 @@ int embed(masr_engine* e, hipStream_t s, const float* feats, int nseq, int T, in
     *Tq_out = Tq;
     return 0;
 }
+
+// abs_pos (PositionalEncoding.forward, embedding.py:39-56): x * sqrt(d) + pe[offset : offset + Tq] -- embed() has multiplied, this
+// adds the sinusoid rows in a launch of its own (multiply, round, add, round: the reference's two operations).  offs: the device
+// offsets of the sequences (chunk steps: each stream's own), nullptr = 0 for all (full context).  The callers have checked
+// offset + Tq against max_pos.  rel_pos hands the same rows to the layers instead; no_pos adds nothing.
+void add_abs_pos(masr_engine* e, hipStream_t s, int nseq, int Tq, const int* offs) {
+    if (e->pos_enc != POS_ENC_ABS) return;
+    launch_add_pos_rows(e->x.as<float>(), e->pe, offs, nseq, Tq, e->cfg.d_model, e->cfg.max_pos, s);
+}
+// which attention instantiation a Conformer layer runs (common.h AttPos)
+int att_pos(const masr_engine* e) { return e->pos_enc == POS_ENC_REL ? ATT_REL_POS : ATT_NO_POS; }
 
 int ensure_layer_ws(masr_engine* e, int nseq, int Tq) {
     const int d = e->cfg.d_model, pad = e->cfg.cnn_kernel - 1;
@@ -1441,7 +1477,7 @@ int wide_layer(masr_engine* e, hipStream_t s, const LayerW& w, int nseq, int Tq,
     if (stream) WIDECHK(PROF_WIDE_CACHE, launch_kv_append_wide(seqs, e->qkv.as<float>(), nseq, Tq, d, s));
     {
         ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * nseq);
-        launch_attention(seqs, nseq, Tq, H, 3 * d, stream ? 2 * d : 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, 1, s, d);
+        launch_attention(seqs, nseq, Tq, H, 3 * d, stream ? 2 * d : 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, 1, s, d, att_pos(e));
     }
     gemm(e, s, e->att.as<float>(), d, w.wo, w.bo, x, d, M, d, d, ACT_NONE, 1.f, x, d);
     // conv module: x <- x + mask(pw2(SiLU(LayerNorm(dwconv(GLU(pw1(mask(LayerNorm(x)))))))))
@@ -1469,6 +1505,7 @@ int encode_full_wide(masr_engine* e, hipStream_t s, const float* feats, const in
     int Tq = 0;
     CHK(embed(e, s, feats, B, T, &Tq));
     if (Tq >= e->cfg.max_pos) return fail("sequence longer than max_pos");   // embedding.py:48-50 assert
+    add_abs_pos(e, s, B, Tq, nullptr);
     CHK(ensure_wide_ws(e, B, Tq));
     CHK(e->attseq.ensure(sizeof(AttSeq) * B));
     launch_attseq_full_wide(e->attseq.as<AttSeq>(), e->qkv.as<float>(), e->att.as<float>(), lens, B, Tq, d, s);
@@ -1720,7 +1757,7 @@ static int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float*
         {
             ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * B);
             // (chunk > 0: decoding_chunk_size of the streaming-trained build; the kernel thins the mask by the layer's rate)
-            launch_attention(e->attseq.as<AttSeq>(), B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, pstride, s, 256);
+            launch_attention(e->attseq.as<AttSeq>(), B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, pstride, s, 256, ATT_REL_POS);
         }
         if (fused) {
             // the next layer's QKV projection rides on this layer's last launch unless the frame rate changes in between
@@ -1870,7 +1907,7 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
             if (!r1.tail_done) mhsa(e, s, w, M);
             {
                 ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * B);
-                launch_attention(seq_r, B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, pstride, s, 256);
+                launch_attention(seq_r, B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, pstride, s, 256, ATT_REL_POS);
             }
             if (fused) mhsa_out_pw1(e, s, w, ctx0, mstride, Ki);
             else mhsa_out(e, s, w, M);
@@ -2114,6 +2151,7 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
     int Tq = 0;
     CHK(embed(e, s, feats_dev, B, T, &Tq));
     if (Tq >= e->cfg.max_pos) return fail("sequence longer than max_pos");   // embedding.py:48-50 assert
+    add_abs_pos(e, s, B, Tq, nullptr);
     const int M = B * Tq;
     CHK(ensure_layer_ws(e, B, Tq));
     CHK(e->attseq.ensure(sizeof(AttSeq) * B));
@@ -2133,7 +2171,9 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
         CHK(r1);
         if (!r1.tail_done) mhsa(e, s, w, M);
         // attention and the chain kernel behind it as ONE launch (32 queries x all four heads per workgroup; key 34 = 0: two launches)
-        const bool fuse_ac = knobs().attn_chain && !few_rows && !knobs().no_chain && H == 4 && d == 256 && knobs().rowgemm_packed;
+        // (the experimental one-launch kernel carries the positional term only)
+        const bool fuse_ac = knobs().attn_chain && !few_rows && !knobs().no_chain && H == 4 && d == 256 && knobs().rowgemm_packed &&
+                             e->pos_enc == POS_ENC_REL;
         if (fuse_ac) {
             AttnChainArgs a{};
             a.seqs = e->attseq.as<AttSeq>(); a.nseq = B; a.q_stride = 3 * d; a.kv_stride = 3 * d;
@@ -2148,7 +2188,7 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
         } else {
             ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * B);
             launch_attention(e->attseq.as<AttSeq>(), B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v,
-                             (decoding_chunk_size > 0 && e->cfg.causal) ? decoding_chunk_size : 0, 1, s, 256);   // use_dynamic_chunk only in the streaming build
+                             (decoding_chunk_size > 0 && e->cfg.causal) ? decoding_chunk_size : 0, 1, s, 256, att_pos(e));   // use_dynamic_chunk only in the streaming build
         }
         if (few_rows) {
             // few row blocks (one utterance, a handful of short ones): latency-cut kernels of the chunk steps -- the row-block
@@ -2923,7 +2963,7 @@ static int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector
             g.lnw = w.att_s; g.lnb = w.att_b; g.kv_seqs = seqs; g.kv_tq = Tq;
             rowgemm(e, s, RG_PRO_AFFINE, RG_EPI_STORE, g);
         }
-        launch_attention(seqs, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, reduced(l) ? 2 : 1, s, 256);
+        launch_attention(seqs, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, reduced(l) ? 2 : 1, s, 256, ATT_REL_POS);
         {
             RowGemmArgs g = rg_args(e->att.as<float>(), d, w.wo, w.bo, x, d, M, d);
             g.R = x; g.ldr = d;
@@ -3081,7 +3121,7 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
             }
         } else {
             mhsa(e, s, w, M, seqs, Tq);                 // k | v rows go straight to the streams' caches
-            launch_attention(seqs, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, rate(l), s, 256);
+            launch_attention(seqs, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, rate(l), s, 256, ATT_REL_POS);
             mhsa_out(e, s, w, M);
         }
         const int K = layer_kernel(e, l), pad = K - 1;
@@ -3194,10 +3234,17 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
             hp[(size_t)(L + l) * n + i] = st[i]->cnn2.as<float>() + (size_t)l * pad * d;
         }
     CHK(e->cnnptrs.ensure(sizeof(float*) * hp.size()));
-    CHK(e->stage.begin(sizeof(AttSeq) * hs.size() + sizeof(float*) * hp.size() + 64));
+    std::vector<int> ho;                          // abs_pos: pe[offset : offset + Tq] of every stream (embedding.py:52-54)
+    if (e->pos_enc == POS_ENC_ABS) {
+        for (int i = 0; i < n; ++i) ho.push_back(st[i]->offset);
+        CHK(e->posoff.ensure(sizeof(int) * ho.size()));
+    }
+    CHK(e->stage.begin(sizeof(AttSeq) * hs.size() + sizeof(float*) * hp.size() + sizeof(int) * ho.size() + 64));
     CHK(e->stage.push(e->attseq.p, hs.data(), sizeof(AttSeq) * hs.size(), s));
     CHK(e->stage.push(e->cnnptrs.p, hp.data(), sizeof(float*) * hp.size(), s));
+    if (!ho.empty()) CHK(e->stage.push(e->posoff.p, ho.data(), sizeof(int) * ho.size(), s));
     CHK(e->stage.end(s));
+    add_abs_pos(e, s, n, Tq, e->posoff.as<int>());
     float* x = e->x.as<float>();
     EncodeCtx ctx{n, Tq, nullptr};
     for (int l = 0; l < L; ++l) {
@@ -3209,7 +3256,7 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
         const LayerW& w = e->layers[knobs().hot_weights ? 0 : l];
         CHK(ffn(e, s, ffn_macaron(w, M)));
         mhsa(e, s, w, M, e->attseq.as<AttSeq>() + (size_t)l * n, Tq);     // q -> qkv buffer, k|v rows -> the streams' caches
-        launch_attention(e->attseq.as<AttSeq>() + (size_t)l * n, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, 1, s, 256);
+        launch_attention(e->attseq.as<AttSeq>() + (size_t)l * n, n, Tq, H, 3 * d, 2 * d, w.ptab, w.pos_u, w.pos_v, 0, 1, s, 256, att_pos(e));
         mhsa_out(e, s, w, M);
         float* const* cptr = e->cnnptrs.as<float*>() + (size_t)l * n;
         // [depthwise conv -> LN -> SiLU -> pointwise_conv2 + residual] rides on the second FFN launch as its head stage (on the
@@ -3311,14 +3358,18 @@ int masr_op_gemm(masr_engine* e, const float* a_dev, const float* w_dev, const f
     return 0;
 }
 
-int masr_op_attention(masr_engine* e, const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev,
+}  // extern "C"
+
+// masr_op_attention (pos_mode ATT_REL_POS) and masr_op_attention_plain (ATT_NO_POS: no table, no biases, group 1)
+static int op_attention(masr_engine* e, int pos_mode, const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev,
                       const float* ptab_dev, int32_t n_pos, const float* bias_u_dev, const float* bias_v_dev, int32_t nseq,
                       const int64_t* q_off, const int64_t* k_off, const int64_t* v_off, const int64_t* out_off, const int32_t* nq,
                       const int32_t* nk, const int32_t* klen, const int32_t* pos0, const int32_t* q_abs0, int32_t heads,
                       int32_t q_stride, int32_t kv_stride, int32_t chunk_size, int32_t pos_stride, int32_t group, int32_t t_true,
                       void* stream) {
     // every refusal comes before the engine is touched: none of them needs a device
-    if (!q_dev || !k_dev || !v_dev || !out_dev || !ptab_dev || !bias_u_dev || !bias_v_dev || !q_off || !k_off || !v_off ||
+    const bool pos = pos_mode == ATT_REL_POS;
+    if (!q_dev || !k_dev || !v_dev || !out_dev || (pos && (!ptab_dev || !bias_u_dev || !bias_v_dev)) || !q_off || !k_off || !v_off ||
         !out_off || !nq || !nk || !klen || !pos0 || !q_abs0)
         return fail("masr_op_attention: null argument");
     if (nseq <= 0) return fail("masr_op_attention: nseq must be positive");
@@ -3348,7 +3399,7 @@ int masr_op_attention(masr_engine* e, const float* q_dev, const float* k_dev, co
         // the last positional row a kernel may read: row pos0 + pos_stride * (nk - 1); grouped: frame pos0 + min(t_true, 3 nk) - 1
         const int64_t last = group == 3 ? (int64_t)pos0[b] + std::min<int64_t>(t_true, 3 * (int64_t)nk[b]) - 1
                                         : (int64_t)pos0[b] + (int64_t)pos_stride * (nk[b] - 1);
-        if (nk[b] > 0 && last >= n_pos) return fail("masr_op_attention: the positional table is too short for sequence " + std::to_string(b));
+        if (pos && nk[b] > 0 && last >= n_pos) return fail("masr_op_attention: the positional table is too short for sequence " + std::to_string(b));
         AttSeq& a = hs[(size_t)b];
         a.q = q_dev + q_off[b];
         a.k = k_dev + k_off[b];
@@ -3374,11 +3425,33 @@ int masr_op_attention(masr_engine* e, const float* q_dev, const float* k_dev, co
     {
         ProfScope ps(e, s, PROF_ATT, 6.0 * w * (double)max_nq * max_nq * nseq);
         if (group > 1) launch_attention_grouped(tab.p, nseq, max_nq, heads, group, ptab_dev, t_true, bias_u_dev, bias_v_dev, s, chunk_size);
-        else launch_attention(tab.p, nseq, max_nq, heads, q_stride, kv_stride, ptab_dev, bias_u_dev, bias_v_dev, chunk_size, pos_stride, s, w);
+        else launch_attention(tab.p, nseq, max_nq, heads, q_stride, kv_stride, ptab_dev, bias_u_dev, bias_v_dev, chunk_size, pos_stride, s, w, pos_mode);
     }
     LAUNCHCHK();
     HIPCHK(hipStreamSynchronize(s));       // the table is freed, and the host copy leaves scope, behind the kernel
     return 0;
+}
+
+extern "C" {
+
+int masr_op_attention(masr_engine* e, const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev,
+                      const float* ptab_dev, int32_t n_pos, const float* bias_u_dev, const float* bias_v_dev, int32_t nseq,
+                      const int64_t* q_off, const int64_t* k_off, const int64_t* v_off, const int64_t* out_off, const int32_t* nq,
+                      const int32_t* nk, const int32_t* klen, const int32_t* pos0, const int32_t* q_abs0, int32_t heads,
+                      int32_t q_stride, int32_t kv_stride, int32_t chunk_size, int32_t pos_stride, int32_t group, int32_t t_true,
+                      void* stream) {
+    return op_attention(e, ATT_REL_POS, q_dev, k_dev, v_dev, out_dev, ptab_dev, n_pos, bias_u_dev, bias_v_dev, nseq, q_off, k_off, v_off,
+                        out_off, nq, nk, klen, pos0, q_abs0, heads, q_stride, kv_stride, chunk_size, pos_stride, group, t_true, stream);
+}
+
+int masr_op_attention_plain(masr_engine* e, const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t nseq,
+                            const int64_t* q_off, const int64_t* k_off, const int64_t* v_off, const int64_t* out_off,
+                            const int32_t* nq, const int32_t* nk, const int32_t* klen, const int32_t* q_abs0, int32_t heads,
+                            int32_t q_stride, int32_t kv_stride, int32_t chunk_size, int32_t pos_stride, void* stream) {
+    if (nseq <= 0) return fail("masr_op_attention: nseq must be positive");
+    const std::vector<int32_t> pos0((size_t)nseq, 0);         // (no positional rows: nothing is read at them)
+    return op_attention(e, ATT_NO_POS, q_dev, k_dev, v_dev, out_dev, nullptr, 0, nullptr, nullptr, nseq, q_off, k_off, v_off, out_off, nq,
+                        nk, klen, pos0.data(), q_abs0, heads, q_stride, kv_stride, chunk_size, pos_stride, 1, 0, stream);
 }
 
 int masr_select_lane(masr_engine* e, int32_t lane) {

@@ -89,6 +89,36 @@ def reference_gains(mean_square, target_db, max_gain_db=300.0):
     return out
 
 
+# encoder_conf.pos_enc_layer_type -> masr_config.reserved[2] of the Conformer (include/masr_hip.h; conformer/encoder.py:239-281)
+POS_ENC_LAYER_TYPES = {'rel_pos': 0, 'abs_pos': 1, 'no_pos': 2}
+# what only RelPositionMultiHeadedAttention owns: a checkpoint has all three per layer (rel_pos) or none (abs_pos / no_pos)
+REL_POS_KEYS = ('self_attn.linear_pos.weight', 'self_attn.pos_bias_u', 'self_attn.pos_bias_v')
+
+
+def _validate_pos_enc(use_model, enc, state_dict):
+    """``encoder_conf.pos_enc_layer_type``: rel_pos for every family; the Conformer also abs_pos (sinusoid rows added to the scaled
+    embedding, plain attention) and no_pos (plain attention, nothing added).  Config and checkpoint have to agree in both
+    directions: only a rel_pos checkpoint holds ``linear_pos`` / ``pos_bias_u`` / ``pos_bias_v``."""
+    v = enc.get('pos_enc_layer_type', 'rel_pos')
+    if use_model != 'conformer':
+        if v != 'rel_pos':
+            raise _lib.MasrError(f'{use_model}: encoder_conf.pos_enc_layer_type={v!r} is not implemented for the {use_model} '
+                                 f"(supported: ('rel_pos',); abs_pos / no_pos run for the conformer only)")
+        return
+    if not isinstance(v, str) or v not in POS_ENC_LAYER_TYPES:
+        raise _lib.MasrError(f'{use_model}: encoder_conf.pos_enc_layer_type={v!r} is not implemented '
+                             f'(supported: {tuple(POS_ENC_LAYER_TYPES)})')
+    if state_dict is None:
+        return
+    for key in (f'encoder.encoders.0.{k}' for k in REL_POS_KEYS):
+        if v == 'rel_pos' and key not in state_dict:
+            raise _lib.MasrError(f'{use_model}: encoder_conf.pos_enc_layer_type={v!r} but the checkpoint has no {key} '
+                                 f'(it was trained with abs_pos or no_pos)')
+        if v != 'rel_pos' and key in state_dict:
+            raise _lib.MasrError(f'{use_model}: encoder_conf.pos_enc_layer_type={v!r} but the checkpoint holds {key} '
+                                 f'(it was trained with rel_pos)')
+
+
 CNN_KERNEL_DEFAULT = {'conformer': 15, 'efficient_conformer': 15, 'squeezeformer': 31}
 CNN_KERNEL_MIN, CNN_KERNEL_MAX = 3, 31
 
@@ -150,7 +180,7 @@ def _validate_encoder_conf(use_model, enc, state_dict, streaming=None):
         want('use_cnn_module', (True,), True)
         want('macaron_style', (True,), True)
         want('input_layer', tuple(INPUT_LAYERS), 'conv2d')
-        want('pos_enc_layer_type', ('rel_pos',), 'rel_pos')
+        _validate_pos_enc(use_model, enc, state_dict)
         has_bn = state_dict is not None and any(k.endswith('conv_module.norm.running_mean') for k in state_dict)
         is_bn = enc.get('cnn_module_norm', 'layer_norm') == 'batch_norm'
         if has_bn != is_bn and state_dict is not None:
@@ -160,7 +190,7 @@ def _validate_encoder_conf(use_model, enc, state_dict, streaming=None):
         want('cnn_norm_type', ('batch_norm',), 'batch_norm')
         want('activation_type', ('swish',), 'swish')
         want('normalize_before', (False,), False)
-        want('pos_enc_layer_type', ('rel_pos',), 'rel_pos')
+        _validate_pos_enc(use_model, enc, state_dict)
         want('adaptive_scale', (True,), True)
         want('dw_stride', (False,), False)
     elif use_model == 'deepspeech2':
@@ -227,6 +257,7 @@ class HipEngine:
                              device_id=device)
             cfg.reserved[0] = 1 if enc.get('cnn_module_norm', 'layer_norm') == 'batch_norm' else 0
             cfg.reserved[3] = INPUT_LAYERS[self.input_layer]
+            cfg.reserved[2] = POS_ENC_LAYER_TYPES[enc.get('pos_enc_layer_type', 'rel_pos')]
         elif use_model == 'squeezeformer':
             # configs/squeezeformer.yml: encoder_dim, feed_forward_expansion_factor, reduce_idx / recover_idx
             dim = int(enc.get('encoder_dim', 256))
@@ -273,6 +304,7 @@ class HipEngine:
             raise _lib.MasrError(f'use_model={use_model}: conformer, squeezeformer, efficient_conformer, deepspeech2 '
                                  f'are implemented')
         self.use_model = use_model
+        self.pos_enc_layer_type = enc.get('pos_enc_layer_type', 'rel_pos') if use_model == 'conformer' else 'rel_pos'
         self.cfg = cfg
         self.d_model, self.vocab_size, self.n_mels = cfg.d_model, cfg.vocab_size, n_mels
         # width of the encoder output rows (DeepSpeech2: rnn_size x directions)
@@ -682,12 +714,22 @@ class HipEngine:
         return c
 
     def op_attention(self, q, k, v, out, ptab, bias_u, bias_v, seqs, heads, q_stride, kv_stride, chunk_size=0, pos_stride=1,
-                     group=1, t_true=0):
+                     group=1, t_true=0, positional=True):
         """masr_op_attention: one attention launch on the caller's device buffers, written into ``out`` in place.  ``seqs``: one
         dict per sequence with the element offsets ``q_off`` / ``k_off`` / ``v_off`` / ``out_off`` of its first rows from the
-        buffers' pointers and ``nq``, ``nk``, ``klen``, ``pos0``, ``q_abs0``."""
+        buffers' pointers and ``nq``, ``nk``, ``klen``, ``pos0``, ``q_abs0``.  ``positional=False`` (masr_op_attention_plain): the
+        plain attention of pos_enc_layer_type abs_pos / no_pos -- ``ptab``, ``bias_u``, ``bias_v`` and ``pos0`` are not used."""
         n = len(seqs)
         col = lambda name, ct: (ct * max(n, 1))(*[int(s[name]) for s in seqs])
+        if not positional:
+            if group != 1:
+                raise _lib.MasrError('op_attention: the plain attention has no grouped form')
+            check(self.lib.masr_op_attention_plain(
+                self.h, _ptr(q), _ptr(k), _ptr(v), _ptr(out), n,
+                col('q_off', C.c_int64), col('k_off', C.c_int64), col('v_off', C.c_int64), col('out_off', C.c_int64),
+                col('nq', C.c_int32), col('nk', C.c_int32), col('klen', C.c_int32), col('q_abs0', C.c_int32),
+                int(heads), int(q_stride), int(kv_stride), int(chunk_size), int(pos_stride), _stream()))
+            return out
         check(self.lib.masr_op_attention(
             self.h, _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(ptab), ptab.shape[0], _ptr(bias_u), _ptr(bias_v), n,
             col('q_off', C.c_int64), col('k_off', C.c_int64), col('v_off', C.c_int64), col('out_off', C.c_int64),

@@ -22,12 +22,16 @@ def _uniform(seed, name, shape, bound):
 
 
 def conformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, d_ff=2048, num_blocks=12,
-                         kernel=15, n_mels=80, ctc_gain=6.0, cnn_module_norm='layer_norm', input_layer='conv2d'):
+                         kernel=15, n_mels=80, ctc_gain=6.0, cnn_module_norm='layer_norm', input_layer='conv2d',
+                         pos_enc_layer_type='rel_pos'):
     """Keys/shapes == reference ``encoder.*`` + ``ctc.*`` entries (attention-decoder
     ``decoder.*`` entries are never used by get_encoder_out*, model.py:152-190).  ``cnn_module_norm='batch_norm'``
     (conformer/convolution.py:60-67): the conv module's norm carries running statistics (same weight / bias shapes).
     ``input_layer`` 'conv2d6' / 'conv2d8' (conformer/subsampling.py:115-211): a 5x5 second conv, or a third 3x3 conv
-    (``embed.conv.4``), and the projection under ``embed.linear``."""
+    (``embed.conv.4``), and the projection under ``embed.linear``.  ``pos_enc_layer_type`` 'abs_pos' / 'no_pos'
+    (conformer/encoder.py:275-279): plain MultiHeadedAttention, so a layer has no ``linear_pos`` / ``pos_bias_u`` / ``pos_bias_v``;
+    every other tensor is the one of the rel_pos dict (each draw is seeded by its own name)."""
+    assert pos_enc_layer_type in ('rel_pos', 'abs_pos', 'no_pos'), pos_enc_layer_type
     sd = {}
     f1 = (n_mels - 1) // 2
     f2 = {'conv2d6': (f1 - 2) // 3, 'conv2d8': ((f1 - 1) // 2 - 1) // 2}.get(input_layer, (f1 - 1) // 2)
@@ -59,9 +63,10 @@ def conformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, d_ff=2048, num
         p = f'encoder.encoders.{i}.'
         for q in ('linear_q', 'linear_k', 'linear_v', 'linear_out'):
             lin(p + 'self_attn.' + q, d, d)
-        lin(p + 'self_attn.linear_pos', d, d, bias=False)
-        sd[p + 'self_attn.pos_bias_u'] = _uniform(seed, p + 'u', (heads, d // heads), 0.3)
-        sd[p + 'self_attn.pos_bias_v'] = _uniform(seed, p + 'v', (heads, d // heads), 0.3)
+        if pos_enc_layer_type == 'rel_pos':
+            lin(p + 'self_attn.linear_pos', d, d, bias=False)
+            sd[p + 'self_attn.pos_bias_u'] = _uniform(seed, p + 'u', (heads, d // heads), 0.3)
+            sd[p + 'self_attn.pos_bias_v'] = _uniform(seed, p + 'v', (heads, d // heads), 0.3)
         for ff in ('feed_forward', 'feed_forward_macaron'):
             lin(p + ff + '.w_1', d_ff, d)
             lin(p + ff + '.w_2', d, d_ff)
