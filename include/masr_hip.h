@@ -63,7 +63,18 @@ typedef struct masr_config {
                                 pos_bias_u / pos_bias_v (masr_finalize refuses one that holds them, and a rel_pos engine one that
                                 lacks them, naming pos_enc_layer_type and the key) and build no positional key tables.  masr_create
                                 refuses any other value by name, and a non-zero [2] for the squeezeformer (rel_pos only there; the
-                                efficient_conformer's [2] is its group size: that family has no such slot and runs rel_pos only) */
+                                efficient_conformer's [2] is its group size: that family has no such slot and runs rel_pos only);
+                                conformer: [4] activation_type (utils/common.py get_activation, torch's defaults), 0 = swish, 1 = relu,
+                                2 = gelu (erf-exact), 3 = tanh, 4 = hardtanh (clamp to [-1, 1]), 5 = selu: the hidden activation of
+                                both feed-forward modules and the one behind the conv module's norm (the GLU keeps its sigmoid), at
+                                (256, 4) and (512, 8), every entry point.  A non-zero [4] runs the width-generic path of separate
+                                launches at (256, 4) too: no packed weight copies for the layers, none of the fused row-block
+                                kernels, and the masr_debug_set keys that choose between them have no effect there (as at 512; the
+                                attention keys keep theirs); 0 keeps the launches and bits it had.  masr_create refuses any other
+                                value by name (activation_type), and a non-zero [4] together with [0] = 1 (batch_norm runs with
+                                swish only).  No other model kind reads [4] as an activation (the efficient_conformer's [4] is its
+                                norm selector): those families run swish only.  An activation has no weights: nothing in a checkpoint
+                                can confirm the value */
 } masr_config;
 
 const char* masr_last_error(void);

@@ -62,6 +62,33 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 #undef MASR_DPP_F
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+
+// The activations behind ACT_SILU (GemmAct), on the device math library's erff / tanhf / expf (1-2 ulp), never the fast
+// intrinsics.  ACT as a template argument: the row kernels of wide.hip; act_f(act, v): the GEMM epilogues, where act is uniform
+// over the launch and the switch is a scalar branch.  ACT_SILU is the expression of silu_f (gemm_f32.hip) and of the wide
+// depthwise kernels, so that a swish launch keeps its bits.
+template <int ACT>
+__device__ __forceinline__ float act_f(float v) {
+    static_assert(ACT >= 0 && ACT <= 6, "GemmAct");
+    if (ACT == 1) return fmaxf(v, 0.f);
+    if (ACT == 2) return v / (1.0f + expf(-v));
+    if (ACT == 3) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+    if (ACT == 4) return tanhf(v);
+    if (ACT == 5) return fminf(fmaxf(v, -1.0f), 1.0f);
+    if (ACT == 6) return v > 0.f ? 1.0507009873554805f * v : 1.7580993408473766f * (expf(v) - 1.0f);   // scale * alpha
+    return v;
+}
+__device__ __forceinline__ float act_f(int act, float v) {
+    switch (act) {
+    case 1: return act_f<1>(v);
+    case 2: return act_f<2>(v);
+    case 3: return act_f<3>(v);
+    case 4: return act_f<4>(v);
+    case 5: return act_f<5>(v);
+    case 6: return act_f<6>(v);
+    default: return v;
+    }
+}
 #endif
 
 
@@ -83,9 +110,20 @@ __host__ __device__ inline int sub_frames(int il, int T) { return T < sub_min_fr
 __host__ __device__ inline int sub_bins(int il, int F) { return sub_after_conv1(il, (F - 1) / 2); }
 
 // ---- GEMM: C[M,N] = epilogue(A[M,K] * W[N,K]^T) on v_mfma_f32_32x32x2_f32 ----------------
-enum GemmAct { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2 };
+enum GemmAct { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_GELU = 3, ACT_TANH = 4, ACT_HARDTANH = 5, ACT_SELU = 6 };
+inline bool gemm_act_valid(int act) { return act >= ACT_NONE && act <= ACT_SELU; }
+// encoder_conf.activation_type of the Conformer (masr_config.reserved[4]; model_utils/utils/common.py get_activation): the hidden
+// activation of both feed-forward modules and the one behind the conv module's norm.  Torch's defaults: erf-exact GELU, Hardtanh
+// on [-1, 1], SELU with scale 1.0507009873554805 and alpha 1.6732632423543772.
+enum EncAct { ENC_ACT_SWISH = 0, ENC_ACT_RELU = 1, ENC_ACT_GELU = 2, ENC_ACT_TANH = 3, ENC_ACT_HARDTANH = 4, ENC_ACT_SELU = 5 };
+// the GemmAct of an EncAct (ACT_NONE for a value outside the enum: masr_create refuses those)
+inline int gemm_act_of(int enc_act) {
+    constexpr int t[6] = {ACT_SILU, ACT_RELU, ACT_GELU, ACT_TANH, ACT_HARDTANH, ACT_SELU};
+    return enc_act >= 0 && enc_act < 6 ? t[enc_act] : ACT_NONE;
+}
 enum GemmAMode { A_PLAIN = 0, A_CONV2 = 1, A_CONV5 = 2 };     // A_CONV5: the 5x5 stride-3 gather of conv2d6 (A_CONV2 geometry)
-enum GemmEpi { EPI_STD = 0, EPI_GLU = 1, EPI_SPLITK = 2 };    // EPI_GLU is NOT implemented by launch_gemm (gemm_f32.hip has no GLU
+enum GemmEpi { EPI_STD = 0, EPI_GLU = 1, EPI_SPLITK = 2, EPI_ACT = 3 };   // EPI_ACT: EPI_STD + GemmAct 3 .. 6 (launch_gemm picks it by a.act);
+                                                                // EPI_GLU is NOT implemented by launch_gemm (gemm_f32.hip has no GLU
                                                                 // epilogue; the number is kept so that EPI_SPLITK keeps its value): the
                                                                 // row-block kernels carry RG_EPI_GLU, the wide path runs launch_glu_wide
 
@@ -98,7 +136,7 @@ struct GemmArgs {
     const int* lens;     // optional per-sequence feature lengths for row masking (see mask_tp)
     int M, N, K;
     int lda, ldc, ldr;
-    int act;             // GemmAct (EPI_STD only)
+    int act;             // GemmAct (EPI_STD only; launch_gemm_bf16x3 takes none / relu / silu and leaves the rest to launch_gemm)
     float alpha;         // out = R + alpha * act(acc + bias)
     int mask_tp;         // >0: row r -> (b = r / mask_tp, t = r % mask_tp); rows with 4*t >= lens[b] give act(..)=0
     int bias_after_alpha; // 1: out = R + alpha*act(acc) + bias  (Squeezeformer input_proj: scaling precedes the Linear)
@@ -493,7 +531,7 @@ void launch_attseq_full(AttSeq* seqs, const float* qkv, float* out, const int* l
                         hipStream_t s, int valid_only = 0);     // valid_only: nq = nk = klen (padded queries / keys are not touched)
 
 // ---- width-generic Conformer path (wide.hip): counterparts of the 256-only row kernels, rows of width d ------------------------
-// wide_supported(d): the widths the templated kernels are instantiated for (512).  The bool launchers are those templated on the
+// wide_supported(d): the widths the templated kernels are instantiated for (256, 512).  The bool launchers are those templated on the
 // width: false, with nothing launched, for any other d.  The void launchers (conv1, glu(bias), sequence descriptors) run plain
 // kernels that take d at run time and serve any width.
 bool wide_supported(int d);
@@ -506,11 +544,11 @@ void launch_conv1_wide(const float* feats, const float* mean, const float* istd,
 // out [M, d] = value * sigmoid(gate) of in [M, 2 d] (value | gate: a pointwise_conv1 output with its bias added)
 bool launch_glu_wide(const float* in, float* out, int M, int d, hipStream_t s);
 void launch_glu_const_wide(const float* bias2d, float* out, int d, hipStream_t s);      // launch_glu_const at width d
-// depthwise conv (1 <= ktaps <= 32) + LayerNorm(d) + SiLU: g [nseq][in_pad + Tq][d] (in_pad materialised history rows) -> out [nseq * Tq, d];
+// depthwise conv (1 <= ktaps <= 32) + LayerNorm(d) + act (a GemmAct from ACT_RELU to ACT_SELU): g [nseq][in_pad + Tq][d] (in_pad materialised history rows) -> out [nseq * Tq, d];
 // tap j of output frame t reads input frame t + j - pad_l; frames in front of the materialised rows read gconst [d] (nullptr:
 // zero), frames behind the sequence read zero
 bool launch_dwconv_ln_silu_wide(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb, float* out,
-                                int nseq, int Tq, int d, int ktaps, int in_pad, int pad_l, float eps, const float* gconst,
+                                int nseq, int Tq, int d, int ktaps, int in_pad, int pad_l, float eps, const float* gconst, int act,
                                 hipStream_t s);
 // launch_conv_hist (LayerNorm variant) at width d
 bool launch_conv_hist_wide(const float* x, const float* w, const float* b, float* const* cache_rd, float* const* cache_wr,

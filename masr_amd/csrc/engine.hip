@@ -291,6 +291,7 @@ struct masr_engine : EngineWs {
     bool conv_bn = false;            // cnn_module_norm: batch_norm (Conformer: cfg.reserved[0] = 1, Efficient Conformer: cfg.reserved[4] = 1): LayerW::cln_w / cln_b hold the folded scale / shift
     bool ds2_gru = false;            // DeepSpeech2 with use_gru: True (cfg.reserved[0] = 1): nn.GRU recurrent layers (gru.hip)
     int pos_enc = POS_ENC_REL;       // Conformer pos_enc_layer_type (cfg.reserved[2], common.h PosEnc): rel_pos, abs_pos or no_pos
+    int act = ENC_ACT_SWISH;         // Conformer activation_type (cfg.reserved[4], common.h EncAct); anything but swish runs the width-generic layer
     // fbank tables
     float *window = nullptr, *melwt = nullptr, *tw512 = nullptr, *twr4 = nullptr;
     FbankTables fbank_tables() const { return FbankTables{window, melwt, tw512, twr4, mel_lo}; }
@@ -670,6 +671,17 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
     if (cfg->model_kind == 0 && (cfg->reserved[2] < POS_ENC_REL || cfg->reserved[2] > POS_ENC_NONE))
         return fail("conformer: pos_enc_layer_type (masr_config.reserved[2]) must be 0 = rel_pos, 1 = abs_pos or 2 = no_pos, got " +
                     std::to_string(cfg->reserved[2]));
+    // activation_type: the Conformer's slot is reserved[4] (no other kind reads it there: the Efficient Conformer keeps its norm
+    // selector in it).  Anything but swish runs the width-generic layer, which carries LayerNorm in the conv module only.
+    if (cfg->model_kind == 0) {
+        if (cfg->reserved[4] < ENC_ACT_SWISH || cfg->reserved[4] > ENC_ACT_SELU)
+            return fail("conformer: activation_type (masr_config.reserved[4]) must be 0 = swish, 1 = relu, 2 = gelu, 3 = tanh, "
+                        "4 = hardtanh or 5 = selu, got " + std::to_string(cfg->reserved[4]));
+        if (cfg->reserved[4] != ENC_ACT_SWISH && cfg->reserved[0] == 1)
+            return fail("conformer: activation_type (masr_config.reserved[4]) = " + std::to_string(cfg->reserved[4]) +
+                        " with cnn_module_norm: batch_norm (masr_config.reserved[0] = 1) is not supported: batch_norm runs with swish "
+                        "(0) only");
+    }
     if (cfg->model_kind == 1 && cfg->reserved[2] != 0)
         return fail("squeezeformer: pos_enc_layer_type (masr_config.reserved[2]) = " + std::to_string(cfg->reserved[2]) +
                     " is not supported: rel_pos (0) only; abs_pos / no_pos are implemented for the conformer (model_kind 0)");
@@ -706,7 +718,8 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
     e->ds2_gru = cfg->model_kind == 3 && cfg->reserved[0] == 1;
     e->recover_idx = cfg->model_kind == 1 ? cfg->reserved[1] : -1;
     e->pos_enc = cfg->model_kind == 0 ? cfg->reserved[2] : POS_ENC_REL;
-    if (cfg->model_kind == 0 || cfg->model_kind == 2) {
+    e->act = cfg->model_kind == 0 ? cfg->reserved[4] : ENC_ACT_SWISH;
+    if (cfg->model_kind == 0 ||cfg->model_kind == 2) {
         if (cfg->reserved[3] < IL_CONV2D || cfg->reserved[3] > IL_CONV2D8) {
             delete e;
             return fail("input_layer (masr_config.reserved[3]) must be 0 = conv2d, 1 = conv2d6 or 2 = conv2d8");
@@ -940,7 +953,7 @@ int masr_finalize(masr_engine* e, void* stream) {
         }
         CHK(up(e, p + "conv_module.pointwise_conv1.weight", {2 * d, d, 1}, &w.pw1_w));   // rows: value c, gate d + c
         CHK(up(e, p + "conv_module.pointwise_conv1.bias", {2 * d}, &w.pw1_b));
-        if (d == 256) {   // [Wo; W_pw1] and [bo; b_pw1]: one continuous weight stream for the fused kernel of the offline path
+        if (d == 256 && e->act == ENC_ACT_SWISH) {   // [Wo; W_pw1] and [bo; b_pw1]: one continuous weight stream for the fused kernel of the offline path
             const HostTensor *a, *b, *c2, *d2;
             CHK(get(e, p + "self_attn.linear_out.weight", {d, d}, &a));
             CHK(get(e, p + "self_attn.linear_out.bias", {d}, &b));
@@ -1431,12 +1444,14 @@ void mhsa_out_pw1(masr_engine* e, hipStream_t s, const LayerW& w, const EncodeCt
 }
 
 // ------------------------------------------------------------------------------------------------
-// Width-generic Conformer path (output_size 512, attention_heads 8; masr_create admits it for model_kind 0 only): the layer of
-// conformer/encoder.py:88-167 with every step as its own launch -- the row kernels of wide.hip, the tiled GEMM of gemm_f32.hip
-// for every product and the attention kernels with 8 heads of 64.  No packed weight copies, none of the fused row-block kernels
-// (they are built for K = 256), so none of their masr_debug_set switches applies here.
+// Width-generic Conformer path (masr_create admits it for model_kind 0 only): output_size 512 / attention_heads 8, and output_size
+// 256 / 4 with an activation_type other than swish.  The layer of conformer/encoder.py:88-167 with every step as its own launch --
+// the row kernels of wide.hip, the tiled GEMM of gemm_f32.hip for every product and the attention kernels with heads of 64.  No
+// packed weight copies for the layers, none of the fused row-block kernels (they are built for K = 256 and for Swish), so none of
+// their masr_debug_set switches applies here; the subsampling front end has no activation_type and runs as on the fused path.
+// The activation (e->act) sits in two places: the epilogue of the first GEMM of wide_ffn and the tail of the depthwise kernel.
 // ------------------------------------------------------------------------------------------------
-bool is_wide(const masr_engine* e) { return e->cfg.model_kind == 0 && e->cfg.d_model != 256; }
+bool is_wide(const masr_engine* e) { return e->cfg.model_kind == 0 && (e->cfg.d_model != 256 || e->act != ENC_ACT_SWISH); }
 // a wide.hip launch under its profile class (masr_profile_select kinds 9-12); a width the kernels are not built for is an error
 #define WIDECHK(kind, launched)                                                                                      \
     do {                                                                                                             \
@@ -1451,13 +1466,13 @@ int ensure_wide_ws(masr_engine* e, int nseq, int Tq) {
     return e->hid.ensure(Mp * std::max(e->cfg.d_ff, 2 * e->cfg.d_model) * sizeof(float));
 }
 
-// x <- x + 0.5 * (W2 . silu(W1 . LayerNorm(x) + b1) + b2)
+// x <- x + 0.5 * (W2 . act(W1 . LayerNorm(x) + b1) + b2), act = the engine's activation_type
 int wide_ffn(masr_engine* e, hipStream_t s, int M, const float* lnw, const float* lnb, const float* w1, const float* b1,
              const float* w2, const float* b2) {
     const int d = e->cfg.d_model, dff = e->cfg.d_ff;
     float *x = e->x.as<float>(), *ln = e->ln.as<float>(), *hid = e->hid.as<float>();
     WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, lnw, lnb, ln, M, d, 1e-5f, 0, 0, nullptr, s));
-    gemm(e, s, ln, d, w1, b1, hid, dff, M, dff, d, ACT_SILU, 1.f, nullptr, 0, PROF_FFN1);
+    gemm(e, s, ln, d, w1, b1, hid, dff, M, dff, d, gemm_act_of(e->act), 1.f, nullptr, 0, PROF_FFN1);
     gemm(e, s, hid, dff, w2, b2, x, d, M, d, dff, ACT_NONE, 0.5f, x, d, PROF_FFN1);
     return 0;
 }
@@ -1480,7 +1495,7 @@ int wide_layer(masr_engine* e, hipStream_t s, const LayerW& w, int nseq, int Tq,
         launch_attention(seqs, nseq, Tq, H, 3 * d, stream ? 2 * d : 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, 1, s, d, att_pos(e));
     }
     gemm(e, s, e->att.as<float>(), d, w.wo, w.bo, x, d, M, d, d, ACT_NONE, 1.f, x, d);
-    // conv module: x <- x + mask(pw2(SiLU(LayerNorm(dwconv(GLU(pw1(mask(LayerNorm(x)))))))))
+    // conv module: x <- x + mask(pw2(act(LayerNorm(dwconv(GLU(pw1(mask(LayerNorm(x)))))))))
     const int in_pad = stream ? pad : 0, Mp = nseq * (Tq + in_pad);
     if (stream) {
         WIDECHK(PROF_WIDE_CACHE, launch_conv_hist_wide(x, w.ln_conv_w, w.ln_conv_b, cache_rd, cache_wr, e->lnpad.as<float>(), nseq, Tq, pad, d, 1e-5f, s));
@@ -1491,14 +1506,14 @@ int wide_layer(masr_engine* e, hipStream_t s, const LayerW& w, int nseq, int Tq,
     WIDECHK(PROF_WIDE_GLU, launch_glu_wide(hid, glu, Mp, d, s));
     WIDECHK(PROF_WIDE_DWCONV, launch_dwconv_ln_silu_wide(glu, w.dw_w, w.dw_b, w.cln_w, w.cln_b, e->dwo.as<float>(), nseq, Tq, d, K, in_pad,
                                        (stream || e->cfg.causal) ? pad : pad / 2, 1e-5f,
-                                       (!stream && e->cfg.causal) ? w.gconst : nullptr, s));
+                                       (!stream && e->cfg.causal) ? w.gconst : nullptr, gemm_act_of(e->act), s));
     gemm(e, s, e->dwo.as<float>(), d, w.pw2_w, w.pw2_b, x, d, M, d, d, ACT_NONE, 1.f, x, d, PROF_GEMM, lens, lens ? Tq : 0);
     CHK(wide_ffn(e, s, M, w.ln_ff_w, w.ln_ff_b, w.ff_w1, w.ff_b1, w.ff_w2, w.ff_b2));
     WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, w.ln_fin_w, w.ln_fin_b, x, M, d, 1e-5f, 0, 0, nullptr, s));
     return 0;
 }
 
-// ConformerEncoder.forward at output_size 512 (masr_encode_full): feats [B, T, n_mels] -> enc_out [B * T', d]
+// ConformerEncoder.forward on the width-generic layer (masr_encode_full): feats [B, T, n_mels] -> enc_out [B * T', d]
 int encode_full_wide(masr_engine* e, hipStream_t s, const float* feats, const int* lens, int B, int T, float* enc_out, int chunk) {
     const int d = e->cfg.d_model;
     if (!wide_supported(d)) return fail("no kernels for output_size " + std::to_string(d));
@@ -2251,7 +2266,7 @@ int masr_ctc_greedy_frames(masr_engine* e, const float* enc_dev, int32_t M, int3
     if (!e || !e->finalized) return fail("engine not finalized");
     ENTER(e);
     CallGuard call_guard(e, (hipStream_t)stream);
-    if (e->cfg.model_kind == 3 || is_wide(e))      // K = 512 / 1024 / 2048 rows: generic GEMM + softmax statistics (logits stay in a workspace)
+    if (e->cfg.model_kind == 3 || is_wide(e))      // K = 512 / 1024 / 2048 rows, or the width-generic path at 256 (no packed copies): generic GEMM + softmax statistics (logits stay in a workspace)
         return ctc_head(e, enc_dev, M, nullptr, 0, argmax_dev, maxprob_dev, (hipStream_t)stream);
     // few row blocks (one utterance: 7; the Efficient Conformer's half-rate output at 32 x 10 s: 124): the fused head gives a
     // workgroup 32 rows x the WHOLE vocabulary (165 us whether 7 or 248 row blocks run); below knobs().ctc_fused_blocks the logits go
@@ -3201,7 +3216,7 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
     for (int i = 0; i < n; ++i)
         if (st[i]->offset + Tq > st[i]->cap) return fail("stream exceeds its max_frames_out / max_pos");
     const int M = n * Tq;
-    const bool wide = is_wide(e);        // output_size 512: the same descriptors and caches, every layer as separate launches
+    const bool wide = is_wide(e);        // output_size 512 or a non-swish activation: the same descriptors and caches, every layer as separate launches
     if (wide && !wide_supported(d)) return fail("no kernels for output_size " + std::to_string(d));
     CHK(wide ? ensure_wide_ws(e, n, Tq) : ensure_layer_ws(e, n, Tq));
     CHK(e->attseq.ensure(sizeof(AttSeq) * (size_t)n * L));
@@ -3349,6 +3364,10 @@ int masr_op_layernorm(masr_engine* e, const float* x_dev, const float* w_dev, co
 
 int masr_op_gemm(masr_engine* e, const float* a_dev, const float* w_dev, const float* bias_dev, const float* res_dev,
                  float* c_dev, int32_t M, int32_t N, int32_t K, int32_t act, float alpha, void* stream) {
+    // (refused before the engine is touched: an unknown value used to run as "none")
+    if (!gemm_act_valid(act))
+        return fail("masr_op_gemm: act = " + std::to_string(act) + " is not an activation: 0 = none, 1 = relu, 2 = silu, 3 = gelu, "
+                    "4 = tanh, 5 = hardtanh, 6 = selu");
     if (!e) return fail("null engine");
     ENTER(e);
     CallGuard call_guard(e, (hipStream_t)stream);

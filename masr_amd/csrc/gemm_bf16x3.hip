@@ -233,7 +233,7 @@ void launch_x(const GemmArgs& a, hipStream_t s) {
 
 // true when the launch was taken (K a multiple of 32; plain row-major A or the conv2 gather; the standard epilogue)
 bool launch_gemm_bf16x3(const GemmArgs& a, int amode, hipStream_t s) {
-    if (a.M <= 0 || a.N <= 0 || a.K % XBK != 0) return false;
+    if (a.M <= 0 || a.N <= 0 || a.K % XBK != 0 || a.act > ACT_SILU) return false;    // (its epilogue carries none / relu / silu)
     if (amode == A_CONV2) {
         if ((long)((a.M + 127) / 128) * ((a.N + 127) / 128) < 200) launch_x<64, 64, 2, 2, A_CONV2>(a, s);
         else if (knobs().gemm_bf16x3_waves == 4) launch_x<128, 128, 2, 2, A_CONV2>(a, s);     // 64 x 64 per wave: 8 fragment reads per 12 MFMAs

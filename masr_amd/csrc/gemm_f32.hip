@@ -186,7 +186,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(GemmArgs p) {
                 }
         }
     }
-    if (EPI == EPI_STD) {
+    if (EPI == EPI_STD || EPI == EPI_ACT) {   // EPI_ACT: EPI_STD with the activations behind ACT_SILU (instantiations of their own:
+                                              // the product launches keep the code they had)
 #pragma unroll
         for (int n = 0; n < TN; ++n) {
             const int col = bn + wn * (BN / WN) + n * 32 + ccol;
@@ -206,6 +207,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(GemmArgs p) {
                     float v = acc[m][n][r] + (p.bias_after_alpha ? 0.f : bv);
                     if (p.act == ACT_RELU) v = fmaxf(v, 0.f);
                     else if (p.act == ACT_SILU) v = silu_f(v);
+                    else if (EPI == EPI_ACT) v = act_f(p.act, v);       // gelu / tanh / hardtanh / selu: act is uniform, a scalar branch
                     if (p.mask_tp > 0) {
                         const int rc = min(row, p.M - 1);
                         const int b = rc / p.mask_tp, t = rc - b * p.mask_tp;
@@ -525,6 +527,18 @@ bool gemm_conv2_rows(const GemmArgs& a) { return a.M > 0 && conv2_tiles(a) == 0;
 
 void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) return;
+    if (a.act > ACT_SILU) {       // gelu / tanh / hardtanh / selu: the plain tiled launch only (wide_ffn, masr_op_gemm)
+        if (amode != A_PLAIN || epi != EPI_STD || a.act > ACT_SELU) {
+            note_launch_error("launch_gemm: an activation behind silu runs on the plain tiled launch only", hipErrorInvalidValue);
+            return;
+        }
+        const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);     // the tile choice of the EPI_STD launch below
+        const long t64 = (long)((a.M + 63) / 64) * ((a.N + 127) / 128);
+        if (t128 >= 384) launch_t<128, 128, 2, 2, A_PLAIN, EPI_ACT>(a, s);
+        else if (t64 >= 200) launch_t<64, 128, 2, 2, A_PLAIN, EPI_ACT>(a, s);
+        else launch_t<64, 64, 2, 2, A_PLAIN, EPI_ACT>(a, s);
+        return;
+    }
     if (amode == A_CONV2 && epi == EPI_SPLITK) {      // caller set a.C = partial buffer, a.nsplit, a.ksplit
         launch_t<64, 64, 2, 2, A_CONV2, EPI_SPLITK>(a, s);
         return;

@@ -1,7 +1,8 @@
-// Row kernels of the width-generic Conformer path (output_size 512, attention_heads 8): the counterparts of the 256-only kernels
-// of elementwise.hip / attention.hip.  Every kernel performs the arithmetic steps of its 256 counterpart in the same order.
-// * Templated on the row width D (a multiple of 256; instantiated for 512): LayerNorm, GLU, depthwise conv + LayerNorm + SiLU, the
-//   streaming conv front and kv_append.  Bandwidth-bound: one wave per row, D / 256 float4 per lane (lane l holds columns
+// Row kernels of the width-generic Conformer path (output_size 512 / attention_heads 8, and output_size 256 with an
+// activation_type other than swish): the counterparts of the 256-only kernels of elementwise.hip / attention.hip.  Every kernel
+// performs the arithmetic steps of its 256 counterpart in the same order.
+// * Templated on the row width D (a multiple of 256; instantiated for 256 and 512): LayerNorm, GLU, depthwise conv + LayerNorm +
+//   activation (a second template argument: the GemmAct behind the norm), the streaming conv front and kv_append.  Bandwidth-bound: one wave per row, D / 256 float4 per lane (lane l holds columns
 //   256 i + 4 l .. + 3), DPP wave reductions.  Their launchers return bool: false, with nothing launched, for a width they are
 //   not instantiated for -- the engine turns that into an error, never into another code path.
 // * Plain kernels that take the width at run time and so serve any d (void launchers, nothing to refuse): conv1 for more
@@ -137,13 +138,13 @@ __global__ void glu_const_wide_kernel(const float* __restrict__ bias, float* __r
     for (int c = threadIdx.x; c < d; c += blockDim.x) out[c] = bias[c] * __builtin_amdgcn_rcpf(1.0f + __expf(-bias[d + c]));
 }
 
-// Depthwise Conv1d (KT taps) + LayerNorm(D) + SiLU (dwconv_ln_silu_kernel).  Input: GLU rows [nseq][in_pad + Tq][D], real rows
+// Depthwise Conv1d (KT taps) + LayerNorm(D) + activation ACT (a GemmAct; ACT_SILU: dwconv_ln_silu_kernel).  Input: GLU rows [nseq][in_pad + Tq][D], real rows
 // behind in_pad materialised history rows.  Output frame t sums taps j over input frame t + j - pad_l (pad_l = KT - 1: causal,
 // (KT - 1) / 2: symmetric).  An input frame in front of the materialised rows reads gconst (the constant glu(bias) history row of
 // the offline causal conv) or zero; a frame behind the sequence reads zero.  Workgroup = 16 output frames of one sequence;
 // thread = channel (D / 256 of them in turn) for the sliding window, then the tile goes through LDS and each wave normalises rows.
 static constexpr int WDW_TT = 16;
-template <int D, int KT>
+template <int D, int KT, int ACT>
 __global__ __launch_bounds__(256) void dwconv_ln_silu_wide_kernel(const float* __restrict__ g, const float* __restrict__ wkc,
                                                                   const float* __restrict__ bias, const float* __restrict__ lnw,
                                                                   const float* __restrict__ lnb, float* __restrict__ out, int Tq,
@@ -186,14 +187,14 @@ __global__ __launch_bounds__(256) void dwconv_ln_silu_wide_kernel(const float* _
 #pragma unroll
         for (int i = 0; i < RowVec<D>::V; ++i)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) o.v[i][k] = o.v[i][k] / (1.0f + expf(-o.v[i][k]));
+            for (int k = 0; k < 4; ++k) o.v[i][k] = act_f<ACT>(o.v[i][k]);
         store_row<D>(out + ((size_t)seq * Tq + t0 + r) * D, lane, o);
     }
 }
 
 // The same for tap counts without an instantiation (dwconv_ln_silu_taps_kernel of elementwise.hip): KMAX = 8 / 16 / 32 registers,
-// the tap count K <= KMAX at run time, tap j in slot KMAX - K + j; same steps in the same order as dwconv_ln_silu_wide_kernel<D, K>.
-template <int D, int KMAX>
+// the tap count K <= KMAX at run time, tap j in slot KMAX - K + j; same steps in the same order as dwconv_ln_silu_wide_kernel<D, K, ACT>.
+template <int D, int KMAX, int ACT>
 __global__ __launch_bounds__(256) void dwconv_ln_silu_wide_taps_kernel(const float* __restrict__ g, const float* __restrict__ wkc,
                                                                        const float* __restrict__ bias,
                                                                        const float* __restrict__ lnw,
@@ -239,7 +240,7 @@ __global__ __launch_bounds__(256) void dwconv_ln_silu_wide_taps_kernel(const flo
 #pragma unroll
         for (int i = 0; i < RowVec<D>::V; ++i)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) o.v[i][k] = o.v[i][k] / (1.0f + expf(-o.v[i][k]));
+            for (int k = 0; k < 4; ++k) o.v[i][k] = act_f<ACT>(o.v[i][k]);
         store_row<D>(out + ((size_t)seq * Tq + t0 + r) * D, lane, o);
     }
 }
@@ -294,13 +295,15 @@ __global__ void attseq_full_wide_kernel(AttSeq* seqs, const float* qkv, float* o
 
 }  // namespace
 
-bool wide_supported(int d) { return d == 512; }
+bool wide_supported(int d) { return d == 256 || d == 512; }
 
 bool launch_layernorm_wide(const float* x, const float* w, const float* b, float* y, int M, int d, float eps, int seq_t, int pad,
                            const int* lens, hipStream_t s) {
-    if (d != 512) return false;
+    if (!wide_supported(d)) return false;
     if (M <= 0) return true;
-    hipLaunchKernelGGL(layernorm_wide_kernel<512>, dim3((M + 3) / 4), dim3(256), 0, s, x, w, b, y, M, eps, seq_t, pad, lens);
+    const dim3 grid((M + 3) / 4), blk(256);
+    if (d == 256) hipLaunchKernelGGL(layernorm_wide_kernel<256>, grid, blk, 0, s, x, w, b, y, M, eps, seq_t, pad, lens);
+    else hipLaunchKernelGGL(layernorm_wide_kernel<512>, grid, blk, 0, s, x, w, b, y, M, eps, seq_t, pad, lens);
     return true;
 }
 
@@ -313,10 +316,12 @@ void launch_conv1_wide(const float* feats, const float* mean, const float* istd,
 }
 
 bool launch_glu_wide(const float* in, float* out, int M, int d, hipStream_t s) {
-    if (d != 512) return false;
+    if (!wide_supported(d)) return false;
     if (M <= 0) return true;
     const long n4 = (long)M * (d / 4);
-    hipLaunchKernelGGL(glu_wide_kernel<512>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, in, out, n4);
+    const dim3 grid((unsigned)((n4 + 255) / 256)), blk(256);
+    if (d == 256) hipLaunchKernelGGL(glu_wide_kernel<256>, grid, blk, 0, s, in, out, n4);
+    else hipLaunchKernelGGL(glu_wide_kernel<512>, grid, blk, 0, s, in, out, n4);
     return true;
 }
 
@@ -324,42 +329,70 @@ void launch_glu_const_wide(const float* bias2d, float* out, int d, hipStream_t s
     hipLaunchKernelGGL(glu_const_wide_kernel, dim3(1), dim3(256), 0, s, bias2d, out, d);
 }
 
-bool launch_dwconv_ln_silu_wide(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb, float* out,
-                                int nseq, int Tq, int d, int ktaps, int in_pad, int pad_l, float eps, const float* gconst,
-                                hipStream_t s) {
-    if (d != 512 || ktaps < 1 || ktaps > 32) return false;
-    if (nseq * Tq <= 0) return true;
+namespace {
+// the tap class of a kernel size: 15 has an instantiation of its own, every other count runs on 8 / 16 / 32 tap registers
+template <int D, int ACT>
+void launch_dwconv_wide_t(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb, float* out, int nseq,
+                          int Tq, int ktaps, int in_pad, int pad_l, float eps, const float* gconst, hipStream_t s) {
     const int tiles = (Tq + WDW_TT - 1) / WDW_TT;
     const dim3 grid(nseq * tiles), blk(256);
     if (ktaps == 15)
-        hipLaunchKernelGGL((dwconv_ln_silu_wide_kernel<512, 15>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, Tq, in_pad, pad_l, eps,
+        hipLaunchKernelGGL((dwconv_ln_silu_wide_kernel<D, 15, ACT>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, Tq, in_pad, pad_l, eps,
                            gconst);
     else if (ktaps <= 8)
-        hipLaunchKernelGGL((dwconv_ln_silu_wide_taps_kernel<512, 8>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, in_pad,
+        hipLaunchKernelGGL((dwconv_ln_silu_wide_taps_kernel<D, 8, ACT>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, in_pad,
                            pad_l, eps, gconst);
     else if (ktaps <= 16)
-        hipLaunchKernelGGL((dwconv_ln_silu_wide_taps_kernel<512, 16>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, in_pad,
+        hipLaunchKernelGGL((dwconv_ln_silu_wide_taps_kernel<D, 16, ACT>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, in_pad,
                            pad_l, eps, gconst);
     else
-        hipLaunchKernelGGL((dwconv_ln_silu_wide_taps_kernel<512, 32>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, in_pad,
+        hipLaunchKernelGGL((dwconv_ln_silu_wide_taps_kernel<D, 32, ACT>), grid, blk, 0, s, g, wkc, bias, lnw, lnb, out, ktaps, Tq, in_pad,
                            pad_l, eps, gconst);
-    return true;
+}
+template <int D>
+bool launch_dwconv_wide_d(int act, const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb, float* out,
+                          int nseq, int Tq, int ktaps, int in_pad, int pad_l, float eps, const float* gconst, hipStream_t s) {
+    switch (act) {
+#define MASR_WDW_ACT(A) \
+    case A: launch_dwconv_wide_t<D, A>(g, wkc, bias, lnw, lnb, out, nseq, Tq, ktaps, in_pad, pad_l, eps, gconst, s); return true;
+    MASR_WDW_ACT(ACT_RELU)
+    MASR_WDW_ACT(ACT_SILU)
+    MASR_WDW_ACT(ACT_GELU)
+    MASR_WDW_ACT(ACT_TANH)
+    MASR_WDW_ACT(ACT_HARDTANH)
+    MASR_WDW_ACT(ACT_SELU)
+#undef MASR_WDW_ACT
+    default: return false;       // (ACT_NONE is no activation_type: refused like an unknown width)
+    }
+}
+}  // namespace
+
+bool launch_dwconv_ln_silu_wide(const float* g, const float* wkc, const float* bias, const float* lnw, const float* lnb, float* out,
+                                int nseq, int Tq, int d, int ktaps, int in_pad, int pad_l, float eps, const float* gconst, int act,
+                                hipStream_t s) {
+    if (!wide_supported(d) || ktaps < 1 || ktaps > 32 || act < ACT_RELU || act > ACT_SELU) return false;
+    if (nseq * Tq <= 0) return true;
+    return d == 256 ? launch_dwconv_wide_d<256>(act, g, wkc, bias, lnw, lnb, out, nseq, Tq, ktaps, in_pad, pad_l, eps, gconst, s)
+                    : launch_dwconv_wide_d<512>(act, g, wkc, bias, lnw, lnb, out, nseq, Tq, ktaps, in_pad, pad_l, eps, gconst, s);
 }
 
 bool launch_conv_hist_wide(const float* x, const float* w, const float* b, float* const* cache_rd, float* const* cache_wr,
                            float* lnpad, int n, int Tq, int pad, int d, float eps, hipStream_t s) {
-    if (d != 512) return false;
+    if (!wide_supported(d)) return false;
     const int rows = n * (Tq + pad);
     if (rows <= 0) return true;
-    hipLaunchKernelGGL(conv_hist_wide_kernel<512>, dim3((rows + 3) / 4), dim3(256), 0, s, x, w, b, cache_rd, cache_wr, lnpad, n, Tq,
-                       pad, eps);
+    const dim3 grid((rows + 3) / 4), blk(256);
+    if (d == 256) hipLaunchKernelGGL(conv_hist_wide_kernel<256>, grid, blk, 0, s, x, w, b, cache_rd, cache_wr, lnpad, n, Tq, pad, eps);
+    else hipLaunchKernelGGL(conv_hist_wide_kernel<512>, grid, blk, 0, s, x, w, b, cache_rd, cache_wr, lnpad, n, Tq, pad, eps);
     return true;
 }
 
 bool launch_kv_append_wide(const AttSeq* seqs, const float* qkv, int n, int Tq, int d, hipStream_t s) {
-    if (d != 512) return false;
+    if (!wide_supported(d)) return false;
     if (n * Tq <= 0) return true;
-    hipLaunchKernelGGL(kv_append_wide_kernel<512>, dim3(Tq, n), dim3(256), 0, s, seqs, qkv, Tq);
+    // one thread per float4 of a k | v row (2 d floats): d / 2 threads, the kernel's launch bound
+    if (d == 256) hipLaunchKernelGGL(kv_append_wide_kernel<256>, dim3(Tq, n), dim3(128), 0, s, seqs, qkv, Tq);
+    else hipLaunchKernelGGL(kv_append_wide_kernel<512>, dim3(Tq, n), dim3(256), 0, s, seqs, qkv, Tq);
     return true;
 }
 

@@ -119,6 +119,30 @@ def _validate_pos_enc(use_model, enc, state_dict):
                                  f'(it was trained with rel_pos)')
 
 
+# encoder_conf.activation_type -> masr_config.reserved[4] of the Conformer (include/masr_hip.h; get_activation of the reference's
+# model_utils/utils/common.py): torch's defaults, i.e. erf-exact GELU, Hardtanh on [-1, 1], SELU with its own scale and alpha
+ACTIVATION_TYPES = {'swish': 0, 'relu': 1, 'gelu': 2, 'tanh': 3, 'hardtanh': 4, 'selu': 5}
+
+
+def _validate_activation(use_model, enc):
+    """``encoder_conf.activation_type``: the hidden activation of both feed-forward modules and the one behind the conv module's
+    norm (the GLU keeps its sigmoid).  ``swish`` for every family; the Conformer also the other five of the reference's
+    ``get_activation``, on the width-generic layer (csrc/wide.hip), which carries layer_norm only.  An activation has no weights:
+    nothing in a checkpoint can confirm the value, so a wrong one loads cleanly into the wrong arithmetic."""
+    v = enc.get('activation_type', 'swish')
+    if not isinstance(v, str) or v not in ACTIVATION_TYPES:
+        raise _lib.MasrError(f'{use_model}: encoder_conf.activation_type={v!r} is not implemented '
+                             f'(supported: {tuple(ACTIVATION_TYPES)} for the conformer, swish for the other families)')
+    if v == 'swish':
+        return
+    if use_model != 'conformer':
+        raise _lib.MasrError(f'{use_model}: encoder_conf.activation_type={v!r} is not implemented for the {use_model} '
+                             f"(supported: ('swish',); the other activations run for the conformer only)")
+    if enc.get('cnn_module_norm', 'layer_norm') == 'batch_norm':
+        raise _lib.MasrError(f"conformer: encoder_conf.activation_type={v!r} with encoder_conf.cnn_module_norm='batch_norm' is not "
+                             f'implemented (batch_norm runs with swish only: the width-generic layer carries layer_norm)')
+
+
 CNN_KERNEL_DEFAULT = {'conformer': 15, 'efficient_conformer': 15, 'squeezeformer': 31}
 CNN_KERNEL_MIN, CNN_KERNEL_MAX = 3, 31
 
@@ -175,7 +199,7 @@ def _validate_encoder_conf(use_model, enc, state_dict, streaming=None):
         # forward only, Efficient Conformer full-context and chunked.  An absent key means layer_norm here for both families (the
         # reference's EfficientConformerEncoder defaults to batch_norm; the shipped YAML sets layer_norm)
         want('cnn_module_norm', ('layer_norm', 'batch_norm'), 'layer_norm')
-        want('activation_type', ('swish',), 'swish')
+        _validate_activation(use_model, enc)
         want('normalize_before', (True,), True)
         want('use_cnn_module', (True,), True)
         want('macaron_style', (True,), True)
@@ -188,7 +212,7 @@ def _validate_encoder_conf(use_model, enc, state_dict, streaming=None):
                                  f'{"holds" if has_bn else "has no"} BatchNorm statistics (conv_module.norm.running_mean)')
     elif use_model == 'squeezeformer':
         want('cnn_norm_type', ('batch_norm',), 'batch_norm')
-        want('activation_type', ('swish',), 'swish')
+        _validate_activation(use_model, enc)
         want('normalize_before', (False,), False)
         _validate_pos_enc(use_model, enc, state_dict)
         want('adaptive_scale', (True,), True)
@@ -258,6 +282,7 @@ class HipEngine:
             cfg.reserved[0] = 1 if enc.get('cnn_module_norm', 'layer_norm') == 'batch_norm' else 0
             cfg.reserved[3] = INPUT_LAYERS[self.input_layer]
             cfg.reserved[2] = POS_ENC_LAYER_TYPES[enc.get('pos_enc_layer_type', 'rel_pos')]
+            cfg.reserved[4] = ACTIVATION_TYPES[enc.get('activation_type', 'swish')]
         elif use_model == 'squeezeformer':
             # configs/squeezeformer.yml: encoder_dim, feed_forward_expansion_factor, reduce_idx / recover_idx
             dim = int(enc.get('encoder_dim', 256))
@@ -305,6 +330,7 @@ class HipEngine:
                                  f'are implemented')
         self.use_model = use_model
         self.pos_enc_layer_type = enc.get('pos_enc_layer_type', 'rel_pos') if use_model == 'conformer' else 'rel_pos'
+        self.activation_type = enc.get('activation_type', 'swish') if use_model == 'conformer' else 'swish'
         self.cfg = cfg
         self.d_model, self.vocab_size, self.n_mels = cfg.d_model, cfg.vocab_size, n_mels
         # width of the encoder output rows (DeepSpeech2: rnn_size x directions)
