@@ -87,7 +87,8 @@ void masr_destroy(masr_engine* e);
 
 /* Weight upload keyed by the reference state_dict names (produced by
  * masr/trainer.py:308,684-689).  `host` is fp32, `shape` has `ndim` entries.  Names outside
- * `encoder.*` / `ctc.*` are ignored (attention decoder, unused by get_encoder_out*).
+ * `encoder.*` / `ctc.*` are ignored (attention decoder, unused by get_encoder_out*) -- unless masr_decoder_enable came
+ * first: then `decoder.left_decoder.*` / `decoder.right_decoder.*` are kept for masr_rescore.
  * The optional name "__pos_table__" [max_pos, d_model] overrides the built-in sin/cos table
  * (conformer/embedding.py:31-37) so that it is bit-identical to torch's. */
 int masr_load_tensor(masr_engine* e, const char* name, const float* host, const int64_t* shape, int32_t ndim);
@@ -488,6 +489,49 @@ int masr_op_attention_plain(masr_engine* e, const float* q_dev, const float* k_d
                             const int64_t* q_off, const int64_t* k_off, const int64_t* v_off, const int64_t* out_off,
                             const int32_t* nq, const int32_t* nk, const int32_t* klen, const int32_t* q_abs0, int32_t heads,
                             int32_t q_stride, int32_t kv_stride, int32_t chunk_size, int32_t pos_stride, void* stream);
+
+/* Attention decoder (second pass, `decoder: attention_rescoring`).  Replaces BiTransformerDecoder.forward
+ * (masr/model_utils/transformer/decoder.py:68-99: left_decoder, and right_decoder on the reversed hypotheses) + the
+ * log_softmax / gather / sum of WeNet's attention_rescoring, for the n-best prefixes of the CTC search.
+ *   masr_decoder_enable  before masr_load_tensor / masr_finalize: from then on the engine keeps the `decoder.left_decoder.*` and
+ *                        `decoder.right_decoder.*` tensors and masr_finalize uploads them (fused q | k | v and source k | v
+ *                        projections).  An engine that never calls it ignores those names, allocates and launches exactly what
+ *                        it did before.  attention_heads / linear_units / num_blocks / r_num_blocks = the YAML decoder_conf; the
+ *                        checkpoint has to hold exactly num_blocks left and r_num_blocks right blocks of these shapes
+ *                        (masr_finalize names the tensor or the key that disagrees).  Refused by name: model kind 3 (DeepSpeech2:
+ *                        its `decoder.` prefix is the CTC head), heads other than d_model / 64, linear_units no positive multiple
+ *                        of 32, num_blocks < 1, r_num_blocks < 0.  The numbers are checked before the engine is touched.
+ *                        A later masr_finalize that again carries decoder tensors replaces the whole set (the old weights are
+ *                        freed after the device has drained); one that fails midway leaves the engine without a decoder.
+ *   masr_rescore         enc_dev [B, Tp, d_model] (the encoder output of a pass), enc_lens_dev [B] valid encoder frames, hyp_dev
+ *                        [B, N, Lmax] int32 token ids, hyp_lens_dev [B, N] (0 <= L <= Lmax; ids past L are never read) ->
+ *                        att_dev, r_att_dev [B, N] f32: sum over the L + 1 positions of log_softmax(logits)[target] of the left
+ *                        and (with_right != 0; else zeros) the right decoder, sos = eos = vocab_size - 1.  Runs on `stream` and
+ *                        the active lane's workspaces, never synchronises.  A hypothesis' scores do not depend on N, B, the other
+ *                        hypotheses, the ids past its length or the lane.  Refused: N outside 1 .. 64, Lmax > max_pos - 1
+ *                        (hypotheses longer than max_pos - 1), B * N > 65535, with_right without a right decoder.
+ *   masr_op_decoder_scores  the same launches driven alone, from HOST tables (hyp_host, hyp_lens_host, enc_lens_host), every
+ *                        entry validated (lengths in [0, Lmax], ids in [0, vocab_size), frames in [1, Tp]); outputs to host
+ *                        arrays; returns when the work has finished.
+ *   masr_decoder_info    enabled | left blocks | right blocks | bytes of decoder weights on the device | bytes of decoder
+ *                        workspace of the ACTIVE lane (0 until its first masr_rescore).  Null outputs are skipped. */
+int masr_decoder_enable(masr_engine* e, int32_t attention_heads, int32_t linear_units, int32_t num_blocks, int32_t r_num_blocks);
+int masr_rescore(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const int32_t* hyp_dev,
+                 const int32_t* hyp_lens_dev, int32_t N, int32_t Lmax, int32_t with_right, float* att_dev, float* r_att_dev,
+                 void* stream);
+int masr_op_decoder_scores(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t Tp,
+                           const int32_t* hyp_host, const int32_t* hyp_lens_host, int32_t N, int32_t Lmax, int32_t with_right,
+                           float* att_host, float* r_att_host, void* stream);
+int masr_decoder_info(masr_engine* e, int32_t* enabled, int32_t* num_blocks, int32_t* r_num_blocks, int64_t* weight_bytes,
+                      int64_t* workspace_bytes);
+/* The N best prefixes of the LM-free host-thread search (masr_beam_search_batch's search, same pruned candidates): per utterance
+ * tokens_host [B, nbest, max_len], len_host [B, nbest], score_host [B, nbest] = log probability of each prefix, count_host [B] =
+ * prefixes returned (<= min(nbest, beam_size)), best first in the search's own order (score, then the smaller last character), so
+ * entry 0 is masr_beam_search_batch's result. */
+int masr_beam_search_batch_nbest(const int32_t* idx_host, const float* logp_host, const int32_t* count_host,
+                                 const int32_t* frames_host, int32_t B, int32_t T_stride, int32_t K, int32_t beam_size,
+                                 int32_t blank, int32_t num_threads, int32_t nbest, int32_t* tokens_host, int32_t max_len,
+                                 int32_t* len_host, float* score_host, int32_t* nbest_count_host);
 
 /* Side streams owned by the library: kind 0 / 1 = prefix searches of consecutive device passes, 2 = per-pass preparation (upload,
  * mean squares, gains), 3 = copies, 4 = the encoder passes of lane 1 (masr_select_lane).  One set per DEVICE, made with the first

@@ -115,6 +115,11 @@ SIGNATURES = {
     'masr_op_gemm': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     'masr_op_attention': [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     'masr_op_attention_plain': [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    'masr_decoder_enable': [_P, _I, _I, _I, _I],
+    'masr_rescore': [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
+    'masr_op_decoder_scores': [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
+    'masr_decoder_info': [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    'masr_beam_search_batch_nbest': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
     'masr_side_stream': [_P, _I, C.POINTER(_P)],
     'masr_select_lane': [_P, _I],
     'masr_stage_rows': [_P, C.c_int64, _P, _P, _I, _I, _I],

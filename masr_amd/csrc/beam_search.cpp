@@ -224,6 +224,27 @@ struct Beam {
         }
     }
 
+    // the `want` best live prefixes (scorer-free search), best first in prefix_compare's order; entry 0 is what best() returns
+    int nbest(int want, int32_t* tokens, int max_len, int32_t* len, float* score) {
+        const size_t live = std::min(prefixes.size(), (size_t)beam_size);
+        std::vector<int> order(prefixes.begin(), prefixes.begin() + live);
+        // best() keeps the FIRST of equal (score, character) pairs: a stable sort keeps that one in front
+        std::stable_sort(order.begin(), order.end(), [this](int a, int b) {
+            const Node &x = pool[a], &y = pool[b];
+            return x.score > y.score || (x.score == y.score && x.ch < y.ch);
+        });
+        const int n = std::min((int)order.size(), want);
+        for (int r = 0; r < n; ++r) {
+            std::vector<int> rev;
+            for (int k = order[r]; k > 0; k = pool[k].parent) rev.push_back(pool[k].ch);
+            const int L = std::min((int)rev.size(), max_len);
+            for (int i = 0; i < L; ++i) tokens[(size_t)r * max_len + i] = rev[rev.size() - 1 - i];
+            len[r] = L;
+            score[r] = pool[order[r]].score;
+        }
+        return n;
+    }
+
     // best hypothesis so far: token ids (root -> leaf) and its log probability
     int best(int32_t* tokens, int max_len, float* score) {
         const size_t live = std::min(prefixes.size(), (size_t)beam_size);
@@ -370,6 +391,37 @@ int masr_beam_search_batch_lm(const int32_t* idx_host, const float* logp_host, c
                 bm.step(idx_host + (base + t) * K, logp_host + (base + t) * K, std::min(count_host[base + t], K),
                         blank_logp_host ? blank_logp_host[base + t] : NAN);
             len_host[b] = bm.best(tokens_host + (size_t)b * max_len, max_len, score_host + b);
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < num_threads; ++t) th.emplace_back(work, t);
+    work(0);
+    for (auto& x : th) x.join();
+    return 0;
+}
+
+int masr_beam_search_batch_nbest(const int32_t* idx_host, const float* logp_host, const int32_t* count_host,
+                                 const int32_t* frames_host, int32_t B, int32_t T_stride, int32_t K, int32_t beam_size,
+                                 int32_t blank, int32_t num_threads, int32_t nbest, int32_t* tokens_host, int32_t max_len,
+                                 int32_t* len_host, float* score_host, int32_t* nbest_count_host) {
+    if (B <= 0) return 0;
+    if (!idx_host || !logp_host || !count_host || !frames_host || !tokens_host || !len_host || !score_host || !nbest_count_host ||
+        beam_size <= 0 || nbest <= 0 || max_len <= 0)
+        return 1;
+    if (num_threads <= 0) num_threads = 1;
+    num_threads = std::min(num_threads, B);
+    auto work = [&](int tid) {
+        Beam bm;
+        bm.beam_size = beam_size;
+        bm.blank = blank;
+        for (int b = tid; b < B; b += num_threads) {
+            bm.reset();
+            const size_t base = (size_t)b * T_stride;
+            const int T = std::min(frames_host[b], T_stride);
+            for (int t = 0; t < T; ++t)
+                bm.step(idx_host + (base + t) * K, logp_host + (base + t) * K, std::min(count_host[base + t], K), NAN);
+            nbest_count_host[b] = bm.nbest(nbest, tokens_host + (size_t)b * nbest * max_len, max_len, len_host + (size_t)b * nbest,
+                                           score_host + (size_t)b * nbest);
         }
     };
     std::vector<std::thread> th;

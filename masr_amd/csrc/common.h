@@ -557,6 +557,21 @@ bool launch_kv_append_wide(const AttSeq* seqs, const float* qkv, int n, int Tq, 
 // launch_attseq_full over a [B * Tp, 3 d] q | k | v buffer and [B * Tp, d] output rows (conv2d rate: 4 feature frames per frame)
 void launch_attseq_full_wide(AttSeq* seqs, const float* qkv, float* out, const int* lens, int B, int Tp, int d, hipStream_t s);
 
+// ---- attention decoder of the second pass (decoder.hip) ------------------------------------------------------------
+// Row space [S = B * N sequences][Lmax + 1 positions]; hyp [S, Lmax] int32 token ids, lens [S] their lengths (clamped to [0, Lmax]
+// in the kernels).  reverse = 1: the right-to-left decoder's view of the same table.
+// x [S * (Lmax + 1), d] <- emb[token] * sqrt(d) + pe[position]; rows past a hypothesis' length are zeroed
+void launch_dec_embed(const int* hyp, const int* lens, const float* emb, const float* pe, float* x, int S, int Lmax, int d, int V,
+                      int reverse, hipStream_t s);
+// few-query attention over heads of 64: causal = 1 over the sequence's own rows (k / v rows of the same row space), causal = 0 over
+// the Tp encoder frames of utterance s / N (k / v rows [B * Tp]), keys j < key_lens[s / N]
+void launch_dec_attention(const float* q, int q_stride, const float* k, const float* v, int kv_stride, float* out, int out_stride,
+                          const int* hyp_lens, const int* key_lens, int S, int N, int Lmax, int Tp, int heads, int causal,
+                          hipStream_t s);
+// out [S] = sum over positions 0 .. L of log_softmax(logits [row, V])[target]; rowlp [S * (Lmax + 1)] scratch
+void launch_dec_scores(const float* logits, const int* hyp, const int* lens, float* rowlp, float* out, int S, int Lmax, int V,
+                       int reverse, hipStream_t s);
+
 // ---- features ------------------------------------------------------------------------------
 size_t fbank_gain_scratch_floats(int B);   // size of gain_scratch ([B] gains + partial sums)
 // use_db: 0 = no dB normalisation, 1 = gains computed on the device, 2 = gains supplied in gain_scratch[0 .. B)

@@ -234,10 +234,18 @@ struct EngineWs {
         xred, xh;      // xh: rows updated by the head stage of a d_ff-split FFN launch (few rows)
     DevBuf x3, sublens;   // conv2d8: the third subsampling conv's output; conv2d6 / conv2d8: the lengths in conv2d units (sub_lens)
     DevBuf posoff;        // abs_pos chunk steps: the streams' offsets (first positional row of each stream's new frames)
+    // attention decoder (masr_rescore; allocated on the lane's first rescoring call, never by an engine without the decoder):
+    // residual rows, LayerNorm rows, q | k | v (self) / q (source), attention output, source k | v of the encoder frames, FFN hidden
+    // rows, logits, per-row log-probabilities
+    DevBuf dec_x, dec_ln, dec_qkv, dec_att, dec_kv, dec_hid, dec_logits, dec_rowlp;
+    size_t decoder_bytes() const {
+        return dec_x.bytes + dec_ln.bytes + dec_qkv.bytes + dec_att.bytes + dec_kv.bytes + dec_hid.bytes + dec_logits.bytes + dec_rowlp.bytes;
+    }
     void release_all() {
         for (DevBuf* b : {&gx, &rnn_out, &hstate, &cstate, &ds2_lens, &qplanes, &attp, &cnnptrs, &ffpart, &fb_scratch, &x1, &x2, &x,
                           &ln, &hid, &qkv, &att, &lnpad, &glu, &dwo, &logits, &feats, &enc, &idx, &maxp, &attseq, &gain, &nframes,
-                          &lens, &xsave, &xred, &xh, &x3, &sublens, &posoff})
+                          &lens, &xsave, &xred, &xh, &x3, &sublens, &posoff, &dec_x, &dec_ln, &dec_qkv, &dec_att, &dec_kv, &dec_hid,
+                          &dec_logits, &dec_rowlp})
             b->release();
         stage.release();
     }
@@ -251,8 +259,28 @@ static int clear_sync(void* p, int value, size_t n) {
     return 0;
 }
 
+// one block of the attention decoder (DecoderLayer, transformer/decoder.py:273-394): pre-norm self-attention (q | k | v fused),
+// source attention (q; k | v of the encoder frames fused), ReLU feed-forward
+struct DecLayerW {
+    float *n1w, *n1b, *wqkv, *bqkv, *wo, *bo;
+    float *n2w, *n2b, *wq2, *bq2, *wkv2, *bkv2, *wo2, *bo2;
+    float *n3w, *n3b, *w1, *b1, *w2, *b2;
+};
+struct DecoderW {       // one TransformerDecoder: embedding, blocks, after_norm, output_layer
+    float *emb = nullptr, *after_w = nullptr, *after_b = nullptr, *out_w = nullptr, *out_b = nullptr;
+    std::vector<DecLayerW> layers;
+};
+struct DecoderState {   // masr_decoder_enable: the YAML decoder_conf; weights uploaded by masr_finalize
+    bool enabled = false, ready = false;
+    int heads = 0, dff = 0, nl = 0, nr = 0;
+    DecoderW left, right;
+    size_t weight_bytes = 0;
+    std::vector<void*> owned;   // the decoder's device weights (a reload replaces the whole set; masr_destroy frees it)
+};
+
 struct masr_engine : EngineWs {
     masr_config cfg;
+    DecoderState dec;
     EngineWs parked[MASR_LANES];     // the workspace sets of the lanes that are not active (parked[lane] is unused)
     int lane = 0;
     hipEvent_t pack_ev = nullptr;    // recorded behind the last call that built a packed weight copy on first use ...
@@ -743,6 +771,7 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
 void masr_destroy(masr_engine* e) {
     if (!e) return;
     for (void* p : e->owned) (void)hipFree(p);
+    for (void* p : e->dec.owned) (void)hipFree(p);
     e->release_all();
     for (auto& w : e->parked) w.release_all();
     e->beam_pool.release();
@@ -785,7 +814,8 @@ static void drop_packed_weights(masr_engine* e) {
 int masr_load_tensor(masr_engine* e, const char* name, const float* host, const int64_t* shape, int32_t ndim) {
     if (!e || !name || !host) return fail("null argument");
     std::string n(name);
-    if (n.rfind("encoder.", 0) != 0 && n.rfind("ctc.", 0) != 0 && n.rfind("decoder.ctc_lo.", 0) != 0 && n != "__pos_table__")
+    const bool dec_name = e->dec.enabled && (n.rfind("decoder.left_decoder.", 0) == 0 || n.rfind("decoder.right_decoder.", 0) == 0);
+    if (n.rfind("encoder.", 0) != 0 && n.rfind("ctc.", 0) != 0 && n.rfind("decoder.ctc_lo.", 0) != 0 && n != "__pos_table__" && !dec_name)
         return 0;
     drop_packed_weights(e);
     HostTensor t;
@@ -810,8 +840,17 @@ static int layer_kernel(const masr_engine* e, int i) {          // efficient con
 }
 static bool layer_grouped(const masr_engine* e, int i) { return e->cfg.model_kind == 2 && i < e->n_group_layers; }
 
+static int finalize_decoder(masr_engine* e);
+static int finalize_model(masr_engine* e, void* stream);
+
 int masr_finalize(masr_engine* e, void* stream) {
     if (!e) return fail("null engine");
+    // the decoder first: the model's own finalize drops the host copies of every tensor when it is done
+    if (e->dec.enabled) CHK(finalize_decoder(e));
+    return finalize_model(e, stream);
+}
+
+static int finalize_model(masr_engine* e, void* stream) {
     if (e->cfg.model_kind == 1) return finalize_squeezeformer(e, (hipStream_t)stream);
     if (e->cfg.model_kind == 3) return finalize_ds2(e);
     hipStream_t s = (hipStream_t)stream;
@@ -3583,6 +3622,275 @@ int masr_profile_read(masr_engine* e, double* total_ms, int64_t* launches, doubl
         e->prof_used = 0;
         e->prof_flops = 0.0;
     }
+    return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Attention decoder of the second pass (decoder: attention_rescoring): weights + masr_rescore
+// reference: masr/model_utils/transformer/decoder.py (BiTransformerDecoder, TransformerDecoder, DecoderLayer)
+// ------------------------------------------------------------------------------------------------
+static int finalize_decoder_side(masr_engine* e, const std::string& pre, const char* conf_key, int nl, DecoderW& w) {
+    const int d = e->cfg.d_model, V = e->cfg.vocab_size, dff = e->dec.dff;
+    auto upn = [&](const std::string& name, std::vector<int64_t> shape, float** out) -> int {
+        const HostTensor* t;
+        CHK(get(e, name, shape, &t));
+        e->dec.weight_bytes += t->v.size() * sizeof(float);
+        return upload(e, t->v, out);
+    };
+    // rows of several [rows, cols] tensors one under the other (fused projections)
+    auto cat = [&](std::vector<std::string> names, int rows, int cols, float** out) -> int {
+        std::vector<float> v;
+        for (const std::string& n : names) {
+            const HostTensor* t;
+            CHK(get(e, n, cols ? std::vector<int64_t>{rows, cols} : std::vector<int64_t>{rows}, &t));
+            v.insert(v.end(), t->v.begin(), t->v.end());
+        }
+        e->dec.weight_bytes += v.size() * sizeof(float);
+        return upload(e, v, out);
+    };
+    const std::string beyond = pre + "decoders." + std::to_string(nl) + ".norm1.weight";
+    if (e->host.count(beyond))
+        return fail(std::string("decoder_conf.") + conf_key + "=" + std::to_string(nl) + " but the checkpoint holds " + beyond +
+                    " (it was trained with more blocks)");
+    w.layers.assign(nl, DecLayerW{});
+    if (nl == 0) return 0;
+    CHK(upn(pre + "embed.0.weight", {V, d}, &w.emb));
+    for (int i = 0; i < nl; ++i) {
+        const std::string p = pre + "decoders." + std::to_string(i) + ".";
+        if (!e->host.count(p + "norm1.weight"))
+            return fail(std::string("decoder_conf.") + conf_key + "=" + std::to_string(nl) + " but the checkpoint has no " + p +
+                        "norm1.weight (it was trained with fewer blocks)");
+        DecLayerW& l = w.layers[i];
+        CHK(upn(p + "norm1.weight", {d}, &l.n1w));
+        CHK(upn(p + "norm1.bias", {d}, &l.n1b));
+        CHK(cat({p + "self_attn.linear_q.weight", p + "self_attn.linear_k.weight", p + "self_attn.linear_v.weight"}, d, d, &l.wqkv));
+        CHK(cat({p + "self_attn.linear_q.bias", p + "self_attn.linear_k.bias", p + "self_attn.linear_v.bias"}, d, 0, &l.bqkv));
+        CHK(upn(p + "self_attn.linear_out.weight", {d, d}, &l.wo));
+        CHK(upn(p + "self_attn.linear_out.bias", {d}, &l.bo));
+        CHK(upn(p + "norm2.weight", {d}, &l.n2w));
+        CHK(upn(p + "norm2.bias", {d}, &l.n2b));
+        CHK(upn(p + "src_attn.linear_q.weight", {d, d}, &l.wq2));
+        CHK(upn(p + "src_attn.linear_q.bias", {d}, &l.bq2));
+        CHK(cat({p + "src_attn.linear_k.weight", p + "src_attn.linear_v.weight"}, d, d, &l.wkv2));
+        CHK(cat({p + "src_attn.linear_k.bias", p + "src_attn.linear_v.bias"}, d, 0, &l.bkv2));
+        CHK(upn(p + "src_attn.linear_out.weight", {d, d}, &l.wo2));
+        CHK(upn(p + "src_attn.linear_out.bias", {d}, &l.bo2));
+        CHK(upn(p + "norm3.weight", {d}, &l.n3w));
+        CHK(upn(p + "norm3.bias", {d}, &l.n3b));
+        auto b1 = e->host.find(p + "feed_forward.w_1.bias");
+        if (b1 != e->host.end() && (int64_t)b1->second.v.size() != dff)
+            return fail("decoder_conf.linear_units=" + std::to_string(dff) + " but the checkpoint was trained with linear_units=" +
+                        std::to_string(b1->second.v.size()) + " (" + p + "feed_forward.w_1.bias)");
+        CHK(upn(p + "feed_forward.w_1.weight", {dff, d}, &l.w1));
+        CHK(upn(p + "feed_forward.w_1.bias", {dff}, &l.b1));
+        CHK(upn(p + "feed_forward.w_2.weight", {d, dff}, &l.w2));
+        CHK(upn(p + "feed_forward.w_2.bias", {d}, &l.b2));
+    }
+    CHK(upn(pre + "after_norm.weight", {d}, &w.after_w));
+    CHK(upn(pre + "after_norm.bias", {d}, &w.after_b));
+    CHK(upn(pre + "output_layer.weight", {V, d}, &w.out_w));
+    CHK(upn(pre + "output_layer.bias", {V}, &w.out_b));
+    return 0;
+}
+
+static int finalize_decoder(masr_engine* e) {
+    HIPCHK(hipSetDevice(e->cfg.device_id));
+    bool any = false;
+    for (const auto& kv : e->host) any = any || kv.first.rfind("decoder.left_decoder.", 0) == 0;
+    if (!any) {
+        if (e->dec.ready) return 0;        // a reload of encoder tensors only: the decoder weights stay as they are
+        return fail("attention_rescoring: the checkpoint holds no decoder.left_decoder.* tensors (it has no attention decoder)");
+    }
+    // a reload replaces the whole set: the previous weights are freed once the device has drained (launches in flight may
+    // still read them), and a finalize that fails midway leaves no half-filled decoder behind
+    auto drop = [&]() {
+        for (void* p : e->dec.owned) (void)hipFree(p);
+        e->dec.owned.clear();
+        e->dec.left = DecoderW{};
+        e->dec.right = DecoderW{};
+        e->dec.weight_bytes = 0;
+        e->dec.ready = false;
+    };
+    if (!e->dec.owned.empty()) (void)hipDeviceSynchronize();
+    drop();
+    const size_t n0 = e->owned.size();
+    int rc = finalize_decoder_side(e, "decoder.left_decoder.", "num_blocks", e->dec.nl, e->dec.left);
+    if (!rc) rc = finalize_decoder_side(e, "decoder.right_decoder.", "r_num_blocks", e->dec.nr, e->dec.right);
+    e->dec.owned.assign(e->owned.begin() + n0, e->owned.end());       // (upload() files every allocation under e->owned)
+    e->owned.resize(n0);
+    if (rc) {
+        drop();
+        return rc;
+    }
+    e->dec.ready = true;
+    return 0;
+}
+
+namespace {
+
+// one TransformerDecoder over the hypothesis table -> out [B * N] (reverse: the right-to-left decoder's view of the table)
+int decoder_forward(masr_engine* e, hipStream_t s, const DecoderW& w, int reverse, const float* enc, const int* enc_lens, int B,
+                    int Tp, const int* hyp, const int* hyp_lens, int N, int Lmax, float* out) {
+    const int d = e->cfg.d_model, V = e->cfg.vocab_size, dff = e->dec.dff, H = e->dec.heads;
+    const int S = B * N, Lp = Lmax + 1, M = S * Lp, Mk = B * Tp;
+    float *x = e->dec_x.as<float>(), *ln = e->dec_ln.as<float>(), *qkv = e->dec_qkv.as<float>(), *att = e->dec_att.as<float>(),
+          *kv = e->dec_kv.as<float>(), *hid = e->dec_hid.as<float>(), *logits = e->dec_logits.as<float>();
+    const float eps = 1e-12f;          // nn.LayerNorm(size, eps=1e-12) throughout the decoder (decoder.py:173, 308-310)
+    launch_dec_embed(hyp, hyp_lens, w.emb, e->pe, x, S, Lmax, d, V, reverse, s);
+    for (const DecLayerW& l : w.layers) {
+        // x <- x + Wo . self_attn(norm1(x)), causal over the hypothesis' own rows
+        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n1w, l.n1b, ln, M, d, eps, 0, 0, nullptr, s));
+        gemm(e, s, ln, d, l.wqkv, l.bqkv, qkv, 3 * d, M, 3 * d, d, ACT_NONE, 1.f, nullptr, 0);
+        launch_dec_attention(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, hyp_lens, nullptr, S, N, Lmax, Tp, H, 1, s);
+        gemm(e, s, att, d, l.wo, l.bo, x, d, M, d, d, ACT_NONE, 1.f, x, d);
+        // x <- x + Wo . src_attn(norm2(x), memory): k | v of the utterance's encoder frames projected ONCE for its N hypotheses
+        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n2w, l.n2b, ln, M, d, eps, 0, 0, nullptr, s));
+        gemm(e, s, ln, d, l.wq2, l.bq2, qkv, d, M, d, d, ACT_NONE, 1.f, nullptr, 0);
+        gemm(e, s, enc, d, l.wkv2, l.bkv2, kv, 2 * d, Mk, 2 * d, d, ACT_NONE, 1.f, nullptr, 0);
+        launch_dec_attention(qkv, d, kv, kv + d, 2 * d, att, d, hyp_lens, enc_lens, S, N, Lmax, Tp, H, 0, s);
+        gemm(e, s, att, d, l.wo2, l.bo2, x, d, M, d, d, ACT_NONE, 1.f, x, d);
+        // x <- x + W2 . relu(W1 . norm3(x))
+        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n3w, l.n3b, ln, M, d, eps, 0, 0, nullptr, s));
+        gemm(e, s, ln, d, l.w1, l.b1, hid, dff, M, dff, d, ACT_RELU, 1.f, nullptr, 0);
+        gemm(e, s, hid, dff, l.w2, l.b2, x, d, M, d, dff, ACT_NONE, 1.f, x, d);
+    }
+    WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, w.after_w, w.after_b, ln, M, d, eps, 0, 0, nullptr, s));
+    gemm(e, s, ln, d, w.out_w, w.out_b, logits, V, M, V, d, ACT_NONE, 1.f, nullptr, 0);
+    launch_dec_scores(logits, hyp, hyp_lens, e->dec_rowlp.as<float>(), out, S, Lmax, V, reverse, s);
+    return 0;
+}
+
+// what needs no device: refused before the engine is touched
+int rescore_shape_check(const char* who, const void* enc, const void* enc_lens, int B, int Tp, const void* hyp, const void* hyp_lens,
+                        int N, int Lmax, const void* att, const void* r_att) {
+    const std::string w(who);
+    if (!enc || !enc_lens || !hyp || !hyp_lens || !att || !r_att) return fail(w + ": null argument");
+    if (B <= 0 || Tp <= 0) return fail(w + ": B and Tp must be positive");
+    if (N < 1 || N > 64) return fail(w + ": N = " + std::to_string(N) + " hypotheses per utterance is outside 1 .. 64 (beam_size)");
+    if (Lmax < 1) return fail(w + ": Lmax must be at least 1");
+    if ((int64_t)B * N > 65535) return fail(w + ": B * N must not exceed 65535 sequences per call");
+    return 0;
+}
+
+int rescore_impl(masr_engine* e, const float* enc, const int* enc_lens, int B, int Tp, const int* hyp, const int* hyp_lens, int N,
+                 int Lmax, int with_right, float* att, float* r_att, hipStream_t s) {
+    if (!e->dec.enabled || !e->dec.ready)
+        return fail("masr_rescore: this engine holds no attention decoder (masr_decoder_enable before masr_finalize)");
+    if (Lmax > e->cfg.max_pos - 1)
+        return fail("masr_rescore: hypotheses longer than max_pos - 1 = " + std::to_string(e->cfg.max_pos - 1) +
+                    " tokens have no positional rows (Lmax = " + std::to_string(Lmax) + ")");
+    if (with_right && e->dec.nr == 0)
+        return fail("masr_rescore: reverse_weight > 0 needs the right-to-left decoder, and this checkpoint has none (r_num_blocks: 0)");
+    const int d = e->cfg.d_model, V = e->cfg.vocab_size;
+    const size_t M = (size_t)B * N * (Lmax + 1), f = sizeof(float);
+    CHK(e->dec_x.ensure(M * d * f));
+    CHK(e->dec_ln.ensure(M * d * f));
+    CHK(e->dec_qkv.ensure(M * 3 * d * f));
+    CHK(e->dec_att.ensure(M * d * f));
+    CHK(e->dec_kv.ensure((size_t)B * Tp * 2 * d * f));
+    CHK(e->dec_hid.ensure(M * e->dec.dff * f));
+    CHK(e->dec_logits.ensure(M * V * f));
+    CHK(e->dec_rowlp.ensure(M * f));
+    CHK(decoder_forward(e, s, e->dec.left, 0, enc, enc_lens, B, Tp, hyp, hyp_lens, N, Lmax, att));
+    if (with_right) CHK(decoder_forward(e, s, e->dec.right, 1, enc, enc_lens, B, Tp, hyp, hyp_lens, N, Lmax, r_att));
+    else HIPCHK(hipMemsetAsync(r_att, 0, (size_t)B * N * f, s));
+    LAUNCHCHK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int masr_decoder_enable(masr_engine* e, int32_t attention_heads, int32_t linear_units, int32_t num_blocks, int32_t r_num_blocks) {
+    if (attention_heads != 4 && attention_heads != 8)
+        return fail("decoder_conf.attention_heads=" + std::to_string(attention_heads) + " is not supported: output_size / 64 (4 at "
+                    "256, 8 at 512; the decoder's attention kernel runs heads of 64)");
+    if (linear_units <= 0 || linear_units % 32)
+        return fail("decoder_conf.linear_units=" + std::to_string(linear_units) + " is not supported: a positive multiple of 32");
+    if (num_blocks < 1) return fail("decoder_conf.num_blocks=" + std::to_string(num_blocks) + " is not supported: at least 1");
+    if (r_num_blocks < 0) return fail("decoder_conf.r_num_blocks=" + std::to_string(r_num_blocks) + " is not supported: 0 or more");
+    if (!e) return fail("null engine");
+    if (e->cfg.model_kind == 3)
+        return fail("attention_rescoring: use_model deepspeech2 has no attention decoder (its decoder.* tensors are the CTC head)");
+    if (!wide_supported(e->cfg.d_model) || e->cfg.d_model != attention_heads * 64)
+        return fail("decoder_conf.attention_heads=" + std::to_string(attention_heads) + " is not supported at output_size " +
+                    std::to_string(e->cfg.d_model) + ": output_size / 64 heads, output_size 256 or 512");
+    if (e->finalized) return fail("masr_decoder_enable: call it before masr_load_tensor / masr_finalize");
+    e->dec.enabled = true;
+    e->dec.heads = attention_heads;
+    e->dec.dff = linear_units;
+    e->dec.nl = num_blocks;
+    e->dec.nr = r_num_blocks;
+    return 0;
+}
+
+int masr_rescore(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const int32_t* hyp_dev,
+                 const int32_t* hyp_lens_dev, int32_t N, int32_t Lmax, int32_t with_right, float* att_dev, float* r_att_dev,
+                 void* stream) {
+    CHK(rescore_shape_check("masr_rescore", enc_dev, enc_lens_dev, B, Tp, hyp_dev, hyp_lens_dev, N, Lmax, att_dev, r_att_dev));
+    if (!e || !e->finalized) return fail("engine not finalized");
+    ENTER(e);
+    CallGuard call_guard(e, (hipStream_t)stream);
+    return rescore_impl(e, enc_dev, enc_lens_dev, B, Tp, hyp_dev, hyp_lens_dev, N, Lmax, with_right, att_dev, r_att_dev,
+                        (hipStream_t)stream);
+}
+
+int masr_op_decoder_scores(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t Tp,
+                           const int32_t* hyp_host, const int32_t* hyp_lens_host, int32_t N, int32_t Lmax, int32_t with_right,
+                           float* att_host, float* r_att_host, void* stream) {
+    CHK(rescore_shape_check("masr_op_decoder_scores", enc_dev, enc_lens_host, B, Tp, hyp_host, hyp_lens_host, N, Lmax, att_host,
+                            r_att_host));
+    for (int b = 0; b < B; ++b)
+        if (enc_lens_host[b] < 1 || enc_lens_host[b] > Tp)
+            return fail("masr_op_decoder_scores: utterance " + std::to_string(b) + " has " + std::to_string(enc_lens_host[b]) +
+                        " encoder frames, outside 1 .. Tp");
+    for (int s = 0; s < B * N; ++s)
+        if (hyp_lens_host[s] < 0 || hyp_lens_host[s] > Lmax)
+            return fail("masr_op_decoder_scores: hypothesis " + std::to_string(s) + " has length " + std::to_string(hyp_lens_host[s]) +
+                        ", outside 0 .. Lmax");
+    if (!e || !e->finalized) return fail("engine not finalized");
+    const int V = e->cfg.vocab_size;
+    for (int s = 0; s < B * N; ++s)
+        for (int i = 0; i < hyp_lens_host[s]; ++i) {
+            const int t = hyp_host[(size_t)s * Lmax + i];
+            if (t < 0 || t >= V)
+                return fail("masr_op_decoder_scores: token id " + std::to_string(t) + " of hypothesis " + std::to_string(s) +
+                            " is outside the vocabulary");
+        }
+    ENTER(e);
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard call_guard(e, st);
+    const size_t S = (size_t)B * N;
+    struct Table {
+        int* p = nullptr;
+        ~Table() { if (p) (void)hipFree(p); }
+    } tab;
+    // hyp [S, Lmax] | hyp_lens [S] | enc_lens [B] | att [S] | r_att [S] (the last two as float)
+    const size_t n_int = S * Lmax + S + B, n_all = n_int + 2 * S;
+    HIPCHK(hipMalloc((void**)&tab.p, n_all * sizeof(int)));
+    int *hyp_d = tab.p, *len_d = hyp_d + S * Lmax, *enc_d = len_d + S;
+    float *att_d = reinterpret_cast<float*>(enc_d + B), *ratt_d = att_d + S;
+    HIPCHK(hipMemcpyAsync(hyp_d, hyp_host, S * Lmax * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(len_d, hyp_lens_host, S * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(enc_d, enc_lens_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+    CHK(rescore_impl(e, enc_dev, enc_d, B, Tp, hyp_d, len_d, N, Lmax, with_right, att_d, ratt_d, st));
+    HIPCHK(hipMemcpyAsync(att_host, att_d, S * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(r_att_host, ratt_d, S * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int masr_decoder_info(masr_engine* e, int32_t* enabled, int32_t* num_blocks, int32_t* r_num_blocks, int64_t* weight_bytes,
+                      int64_t* workspace_bytes) {
+    if (!e) return fail("null engine");
+    if (enabled) *enabled = e->dec.enabled ? 1 : 0;
+    if (num_blocks) *num_blocks = e->dec.nl;
+    if (r_num_blocks) *r_num_blocks = e->dec.nr;
+    if (weight_bytes) *weight_bytes = (int64_t)e->dec.weight_bytes;
+    if (workspace_bytes) *workspace_bytes = (int64_t)e->decoder_bytes();
     return 0;
 }
 

@@ -228,6 +228,64 @@ def _validate_encoder_conf(use_model, enc, state_dict, streaming=None):
                                  f'.weight_ih_l0)')
 
 
+DECODER_PREFIXES = ('decoder.left_decoder.', 'decoder.right_decoder.')
+
+
+def _decoder_blocks(state_dict, side):
+    """number of DecoderLayers a checkpoint holds under ``decoder.<side>_decoder.decoders``"""
+    head = f'decoder.{side}_decoder.decoders.'
+    return len({k[len(head):].split('.', 1)[0] for k in state_dict if k.startswith(head)})
+
+
+def _validate_decoder_conf(use_model, dec, state_dict, d_model=256):
+    """``decoder_conf`` of an engine that is to rescore with the checkpoint's attention decoder (``decoder: attention_rescoring``):
+    the BiTransformerDecoder the reference trains beside the CTC head (transformer/decoder.py; configs: 3 + 3 blocks, 4 heads,
+    linear_units 1024).  The kernels run the shipped variant -- pre-norm blocks, no concat, an output layer, heads of 64 -- and
+    ``attention_heads`` / ``linear_units`` / ``num_blocks`` / ``r_num_blocks`` have to be the checkpoint's own, in both directions.
+    -> (attention_heads, linear_units, num_blocks, r_num_blocks); masr_decoder_enable / masr_finalize repeat the checks."""
+    dec = dict(dec or {})
+    if use_model == 'deepspeech2':
+        raise _lib.MasrError("deepspeech2: decoder='attention_rescoring' is not available: use_model deepspeech2 has no attention "
+                             "decoder (its decoder.* tensors are the CTC head)")
+    if state_dict is None or not any(k.startswith('decoder.left_decoder.') for k in state_dict):
+        raise _lib.MasrError(f"{use_model}: decoder='attention_rescoring' but the checkpoint holds no decoder.left_decoder.* tensors "
+                             f"(it has no attention decoder)")
+    for key, allowed, default in (('normalize_before', (True,), True), ('concat_after', (False,), False),
+                                  ('use_output_layer', (True,), True), ('input_layer', ('embed',), 'embed')):
+        v = dec.get(key, default)
+        if v not in allowed or isinstance(v, bool) != isinstance(allowed[0], bool):
+            raise _lib.MasrError(f'{use_model}: decoder_conf.{key}={v!r} is not implemented (supported: {allowed})')
+
+    def integer(key, default):
+        v = dec.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise _lib.MasrError(f'{use_model}: decoder_conf.{key}={v!r} is not an integer')
+        return v
+    heads, units = integer('attention_heads', 4), integer('linear_units', 2048)
+    nl, nr = integer('num_blocks', 6), integer('r_num_blocks', 0)
+    if heads * 64 != d_model:
+        raise _lib.MasrError(f'{use_model}: decoder_conf.attention_heads={heads} is not supported at an encoder output of {d_model}: '
+                             f'{d_model // 64} (the decoder\'s attention kernel runs heads of 64)')
+    if units <= 0 or units % 32:
+        raise _lib.MasrError(f'{use_model}: decoder_conf.linear_units={units} is not supported: a positive multiple of 32')
+    key = 'decoder.left_decoder.decoders.0.feed_forward.w_1.weight'
+    if key in state_dict and int(state_dict[key].shape[0]) != units:
+        raise _lib.MasrError(f'{use_model}: decoder_conf.linear_units={units} but the checkpoint was trained with '
+                             f'linear_units={int(state_dict[key].shape[0])} ({key} is {list(state_dict[key].shape)})')
+    key = 'decoder.left_decoder.embed.0.weight'
+    if key in state_dict and int(state_dict[key].shape[1]) != d_model:
+        raise _lib.MasrError(f'{use_model}: the attention decoder is {int(state_dict[key].shape[1])} wide ({key}) but the encoder '
+                             f'output is {d_model}')
+    for conf_key, side, want in (('num_blocks', 'left', nl), ('r_num_blocks', 'right', nr)):
+        have = _decoder_blocks(state_dict, side)
+        if have != want:
+            raise _lib.MasrError(f'{use_model}: decoder_conf.{conf_key}={want} but the checkpoint holds {have} blocks under '
+                                 f'decoder.{side}_decoder.decoders')
+    if nl < 1:
+        raise _lib.MasrError(f'{use_model}: decoder_conf.num_blocks={nl} is not supported: at least 1')
+    return heads, units, nl, nr
+
+
 RNN_SIZES = tuple(range(256, 2049, 256))
 
 
@@ -254,7 +312,10 @@ class HipEngine:
     engine that can run the model-independent kernels (fbank, argmax, CTC collapse)."""
 
     def __init__(self, state_dict, encoder_conf=None, vocab_size=None, streaming=True, n_mels=80, device=None,
-                 max_pos=5000, use_model='conformer'):
+                 max_pos=5000, use_model='conformer', decoder_conf=None, attention_decoder=False):
+        """``attention_decoder=True`` (``decoder: attention_rescoring``): the engine also loads the checkpoint's
+        ``decoder.left_decoder.*`` / ``decoder.right_decoder.*`` tensors, described by ``decoder_conf`` (the YAML block), and
+        ``rescore`` works; otherwise those tensors are never touched and the engine is what it always was."""
         if not torch.cuda.is_available():
             raise _lib.MasrError('no HIP device visible to torch: the MI355X engine has no CPU fallback')
         if device is None:          # the calling rank's GPU (one process per GPU: torch.cuda.set_device(LOCAL_RANK) comes first)
@@ -336,15 +397,23 @@ class HipEngine:
         # width of the encoder output rows (DeepSpeech2: rnn_size x directions)
         self.enc_dim = cfg.d_model * (1 if streaming else 2) if use_model == 'deepspeech2' else cfg.d_model
         self.num_blocks, self.heads, self.cnn_kernel = cfg.num_blocks, cfg.heads, cfg.cnn_kernel
+        # (refused before an engine exists: nothing to release on the way out)
+        dconf = _validate_decoder_conf(use_model, decoder_conf, state_dict, self.enc_dim) if attention_decoder else None
         h = C.c_void_p()
         check(self.lib.masr_create(C.byref(cfg), C.byref(h)))
         self.h = h
         self.has_weights = state_dict is not None
+        self.has_decoder = False
+        self.max_pos = int(max_pos)
+        if attention_decoder:
+            check(self.lib.masr_decoder_enable(self.h, *dconf))
+            self.has_decoder, self.decoder_blocks = True, dconf[2:]
         if state_dict is None:      # weight-less engine: fbank / argmax / collapse kernels only
             return
         for name, t in state_dict.items():
             if not (name.startswith('encoder.') or name.startswith('ctc.') or name.startswith('decoder.ctc_lo.')):
-                continue
+                if not (self.has_decoder and name.startswith(DECODER_PREFIXES) and torch.is_tensor(t) and t.is_floating_point()):
+                    continue
             self._load(name, t)
         if use_model != 'deepspeech2':
             self._load('__pos_table__', positional_table(max_pos, cfg.d_model))
@@ -723,6 +792,41 @@ class HipEngine:
         cnn = torch.zeros(self.num_blocks, 1, self.d_model, self.cnn_kernel - 1, dtype=torch.float32, device=self.device)
         check(self.lib.masr_stream_export_cache(self.h, sid, _ptr(att), _ptr(cnn), _stream()))
         return att, cnn
+
+    # ---- attention decoder (second pass) -----------------------------------------------------------------
+    def rescore(self, enc, enc_lens, hyps, hyp_lens, with_right=True):
+        """masr_rescore on the current stream and the active lane: ``enc`` [B, T', d] (the encoder output of a pass), ``enc_lens``
+        [B] int32 valid encoder frames, ``hyps`` [B, N, Lmax] int32 token ids, ``hyp_lens`` [B, N] int32 (all device tensors) ->
+        (att, r_att) [B, N] float32 device tensors: the left and the right decoder's summed log-probabilities of every hypothesis
+        (``with_right=False``: r_att is zero).  Nothing is waited for."""
+        B, Tp, _ = enc.shape
+        _, N, Lmax = hyps.shape
+        att = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        r_att = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        check(self.lib.masr_rescore(self.h, _ptr(enc), _ptr(enc_lens), B, Tp, _ptr(hyps), _ptr(hyp_lens), N, Lmax,
+                                    1 if with_right else 0, _ptr(att), _ptr(r_att), _stream()))
+        return att, r_att
+
+    def op_decoder_scores(self, enc, enc_lens, hyps, hyp_lens, with_right=True):
+        """masr_op_decoder_scores: the decoder's launches driven alone from HOST tables (``enc_lens`` [B], ``hyps`` [B, N, Lmax],
+        ``hyp_lens`` [B, N]; ``enc`` [B, T', d] on the device), every entry validated -> (att, r_att) [B, N] numpy; returns when
+        the work has finished."""
+        hyps = np.ascontiguousarray(hyps, np.int32)
+        hyp_lens = np.ascontiguousarray(hyp_lens, np.int32)
+        enc_lens = np.ascontiguousarray(enc_lens, np.int32)
+        B, N, Lmax = hyps.shape
+        att, r_att = np.zeros((B, N), np.float32), np.zeros((B, N), np.float32)
+        as_p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self.lib.masr_op_decoder_scores(self.h, _ptr(enc), as_p(enc_lens), B, enc.shape[1], as_p(hyps), as_p(hyp_lens), N, Lmax,
+                                              1 if with_right else 0, as_p(att), as_p(r_att), _stream()))
+        return att, r_att
+
+    def decoder_info(self):
+        """masr_decoder_info -> {'enabled', 'num_blocks', 'r_num_blocks', 'weight_bytes', 'workspace_bytes' (active lane)}"""
+        en, nl, nr, wb, ws = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        check(self.lib.masr_decoder_info(self.h, C.byref(en), C.byref(nl), C.byref(nr), C.byref(wb), C.byref(ws)))
+        return {'enabled': bool(en.value), 'num_blocks': nl.value, 'r_num_blocks': nr.value, 'weight_bytes': wb.value,
+                'workspace_bytes': ws.value}
 
     # ---- single ops / profiling -----------------------------------------------------------------------
     def op_layernorm(self, x, w, b, eps=1e-5):

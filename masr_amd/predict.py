@@ -76,6 +76,18 @@ class MASRPredictor:
             from masr_amd.decoders.beam_search_decoder import BeamSearchDecoder
             self.beam_search_decoder = BeamSearchDecoder(vocab_list=self._text_featurizer.vocab_list,
                                                          **self.configs.ctc_beam_search_decoder_conf)
+        self.rescoring_decoder = None
+        if self.configs.decoder == 'attention_rescoring':
+            # second pass with the checkpoint's attention decoder over the CTC n-best (decoders/attention_rescoring.py); the
+            # configuration is checked before anything is loaded
+            from masr_amd.decoders.attention_rescoring import AttentionRescoringDecoder, validate_rescoring_conf
+            if self.configs.use_model == 'deepspeech2':
+                raise Exception("decoder='attention_rescoring' is not available for use_model deepspeech2: it has no attention "
+                                "decoder (its decoder.* tensors are the CTC head)")
+            dconf = dict(self.configs.get('decoder_conf', {}) or {})
+            rconf = validate_rescoring_conf(self.configs.get('attention_rescoring_decoder_conf', None),
+                                            self.configs.get('model_conf', None), dconf.get('r_num_blocks', 0))
+            self.rescoring_decoder = AttentionRescoringDecoder(vocab_list=self._text_featurizer.vocab_list, **rconf)
         if state_dict is None and not os.path.exists(model_path):
             raise Exception("模型文件不存在，请检查{}是否存在！".format(model_path))
         self.predictor = InferencePredictor(configs=self.configs, use_model=self.configs.use_model,
@@ -90,6 +102,9 @@ class MASRPredictor:
     # ---- helpers ----------------------------------------------------------------------------------------------------------
     def decode(self, output_data, use_pun, is_itn):
         """predict.py:118-144: probabilities [T', V] of one utterance -> (score, text)."""
+        if self.configs.decoder == 'attention_rescoring':
+            raise Exception("decoder='attention_rescoring' needs the encoder output of the utterance, not only its probabilities: "
+                            "use predict / predict_batch")
         if self.configs.decoder == 'ctc_beam_search':
             score, text = self.beam_search_decoder.decode_beam_search_offline(probs_split=output_data)
         else:
@@ -385,7 +400,8 @@ class MASRPredictor:
             return (lambda: out) if defer else out
         live = ok                # (only its length is used below)
         xs, ns, gain = self._prepare_finish(began['prep'], pc.target_dB)
-        greedy = self.configs.decoder != 'ctc_beam_search'
+        rescoring = self.configs.decoder == 'attention_rescoring'
+        greedy = self.configs.decoder != 'ctc_beam_search' and not rescoring
         if greedy and method == 'fbank':
             # the whole pass is ONE C-ABI call and ONE copy back: rows [B, T' + 2] = tokens | count | score bits
             rows = eng.transcribe_rows(xs, ns, pc.use_dB_normalization, pc.target_dB, gain_in=gain,
@@ -412,6 +428,22 @@ class MASRPredictor:
         with debug_keys(eng, skip_padding=0) if decode_all_frames else contextlib.nullcontext():
             enc = eng.encode_full(feats, frames, -1)
         nenc = None if decode_all_frames else eng.enc_frames(frames).to(torch.int32)
+        if rescoring:
+            # first pass: CTC head, vocabulary pruning on the GPU, the n-best prefixes of the LM-free prefix search; second pass:
+            # both attention decoders over this pass's encoder output, queued behind it on the SAME stream and lane (the caller
+            # selected them), so two passes on two lanes never share a decoder workspace; the host waits for the first pass
+            # (pruned candidates, host-thread search), never for the second: its results are fetched behind an event
+            probs = eng.ctc_probs(enc)
+            n_host = [probs.shape[1]] * len(live) if nenc is None else \
+                eng.enc_frames((n.astype(np.int64) - min_samples) // 160 + 1).tolist()
+            enc_lens = nenc if nenc is not None else torch.full((len(live),), enc.shape[1], dtype=torch.int32, device=eng.device)
+            fetch_pass = self.rescoring_decoder.decode_pass(eng, enc, enc_lens.contiguous(), probs, n_host, want_tokens=as_tokens)
+
+            def fetch_rescored():
+                for i, r in zip(ok, fetch_pass()):
+                    out[i] = r if as_tokens else {'text': r[1], 'score': r[0]}
+                return out
+            return fetch_rescored if defer else fetch_rescored()
         if not greedy:
             # probabilities stay on the GPU: vocabulary pruning, prefix search and LM scoring run there
             probs = eng.ctc_probs(enc)
@@ -750,6 +782,9 @@ class MASRPredictor:
         if not self.configs.streaming:
             raise Exception(f"不支持改该模型流式识别，当前模型：{self.configs.use_model}，参数streaming为：{self.configs.streaming}")
         self._no_itn(is_itn)
+        if self.configs.decoder == 'attention_rescoring':
+            from masr_amd.decoders.attention_rescoring import STREAM_REFUSAL
+            raise Exception(STREAM_REFUSAL)
         if self._pool is None:
             from masr_amd.serving import StreamPool
             self._pool = StreamPool(self)

@@ -151,6 +151,9 @@ class StreamPool:
         cfg = predictor.configs
         if not cfg.streaming or not ('former' in cfg.use_model or cfg.use_model == 'deepspeech2'):
             raise Exception(f"不支持改该模型流式识别，当前模型：{cfg.use_model}，参数streaming为：{cfg.streaming}")
+        if cfg.decoder == 'attention_rescoring':
+            from masr_amd.decoders.attention_rescoring import STREAM_REFUSAL
+            raise Exception(STREAM_REFUSAL)
         if cfg.decoder not in ('ctc_greedy', 'ctc_beam_search'):
             raise Exception(f'unknown decoder {cfg.decoder}')
         self.predictor = predictor

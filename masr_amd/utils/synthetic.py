@@ -21,16 +21,52 @@ def _uniform(seed, name, shape, bound):
     return torch.from_numpy(_rng(seed, name).uniform(-bound, bound, shape).astype(np.float32))
 
 
+def attention_decoder_state_dict(seed=0, vocab_size=4233, d=256, linear_units=1024, num_blocks=3, r_num_blocks=3,
+                                 out_gain=4.0):
+    """Keys/shapes == the reference's ``decoder.*`` entries (BiTransformerDecoder, masr/model_utils/transformer/decoder.py):
+    ``left_decoder`` with ``num_blocks`` and ``right_decoder`` with ``r_num_blocks`` DecoderLayers, each side with its own
+    embedding, ``after_norm`` and ``output_layer`` (a right decoder of 0 blocks keeps those three, as the reference's does).  Every
+    draw is seeded by its own name: adding these keys to a checkpoint changes none of its other tensors."""
+    sd = {}
+
+    def lin(name, out_f, in_f, gain=1.0):
+        b = gain / math.sqrt(in_f)
+        sd[name + '.weight'] = _uniform(seed, name + '.weight', (out_f, in_f), b * math.sqrt(3.0))
+        sd[name + '.bias'] = _uniform(seed, name + '.bias', (out_f,), 0.1)
+
+    def ln(name):
+        sd[name + '.weight'] = 1.0 + _uniform(seed, name + '.weight', (d,), 0.2)
+        sd[name + '.bias'] = _uniform(seed, name + '.bias', (d,), 0.1)
+
+    for side, n in (('left_decoder', num_blocks), ('right_decoder', r_num_blocks)):
+        p = f'decoder.{side}.'
+        sd[p + 'embed.0.weight'] = _uniform(seed, p + 'embed.0.weight', (vocab_size, d), 1.0 / math.sqrt(d))
+        for i in range(n):
+            q = f'{p}decoders.{i}.'
+            for att in ('self_attn', 'src_attn'):
+                for m in ('linear_q', 'linear_k', 'linear_v', 'linear_out'):
+                    lin(q + att + '.' + m, d, d)
+            lin(q + 'feed_forward.w_1', linear_units, d)
+            lin(q + 'feed_forward.w_2', d, linear_units)
+            for m in ('norm1', 'norm2', 'norm3'):
+                ln(q + m)
+        ln(p + 'after_norm')
+        # sharpened like the CTC head: a flat output layer would rank every hypothesis by its length alone
+        lin(p + 'output_layer', vocab_size, d, gain=out_gain)
+    return sd
+
+
 def conformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, d_ff=2048, num_blocks=12,
                          kernel=15, n_mels=80, ctc_gain=6.0, cnn_module_norm='layer_norm', input_layer='conv2d',
-                         pos_enc_layer_type='rel_pos'):
+                         pos_enc_layer_type='rel_pos', decoder=None):
     """Keys/shapes == reference ``encoder.*`` + ``ctc.*`` entries (attention-decoder
     ``decoder.*`` entries are never used by get_encoder_out*, model.py:152-190).  ``cnn_module_norm='batch_norm'``
     (conformer/convolution.py:60-67): the conv module's norm carries running statistics (same weight / bias shapes).
     ``input_layer`` 'conv2d6' / 'conv2d8' (conformer/subsampling.py:115-211): a 5x5 second conv, or a third 3x3 conv
     (``embed.conv.4``), and the projection under ``embed.linear``.  ``pos_enc_layer_type`` 'abs_pos' / 'no_pos'
     (conformer/encoder.py:275-279): plain MultiHeadedAttention, so a layer has no ``linear_pos`` / ``pos_bias_u`` / ``pos_bias_v``;
-    every other tensor is the one of the rel_pos dict (each draw is seeded by its own name)."""
+    every other tensor is the one of the rel_pos dict (each draw is seeded by its own name).  ``decoder`` (default: none, the
+    dict it always was): keyword arguments of ``attention_decoder_state_dict`` -- its ``decoder.*`` tensors are added."""
     assert pos_enc_layer_type in ('rel_pos', 'abs_pos', 'no_pos'), pos_enc_layer_type
     sd = {}
     f1 = (n_mels - 1) // 2
@@ -86,6 +122,8 @@ def conformer_state_dict(seed=0, vocab_size=4233, d=256, heads=4, d_ff=2048, num
     # sharpened CTC head: with gain 1 the softmax over V is nearly flat and the
     # greedy argmax is decided by 1e-6 gaps
     lin('ctc.ctc_lo', vocab_size, d, gain=ctc_gain)
+    if decoder is not None:
+        sd.update(attention_decoder_state_dict(seed, vocab_size, d, **decoder))
     return sd
 
 
