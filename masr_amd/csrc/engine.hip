@@ -2182,25 +2182,10 @@ static int ds2_forward(masr_engine* e, hipStream_t s, const float* feats, const 
     return 0;
 }
 
-extern "C" {
-
-int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat_lens_dev, int32_t B, int32_t T,
-                     int32_t decoding_chunk_size, float* enc_out_dev, void* stream) {
-    if (!e || !e->finalized) return fail("engine not finalized");
-    ENTER(e);
-    CallGuard call_guard(e, (hipStream_t)stream);
-    if (B <= 0) return fail("empty batch");
-    hipStream_t s = (hipStream_t)stream;
-    if (e->cfg.model_kind == 3) return ds2_forward(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, nullptr, nullptr);
-    // decoding_chunk_size > 0 limits the attention to chunks in the streaming-trained builds only (use_dynamic_chunk follows
-    // `streaming`, model.py of every family; utils/mask.py:117-143 ignores it otherwise)
-    const int chunk = (decoding_chunk_size > 0 && e->cfg.causal) ? decoding_chunk_size : 0;
-    // conv2d6 / conv2d8: every mask below tests 4 * t against the lengths in conv2d units
-    if (feat_lens_dev && e->input_layer != IL_CONV2D && !(feat_lens_dev = sub_lens(e, s, feat_lens_dev, B)))
-        return fail("out of device memory (subsampled lengths)");
-    if (e->cfg.model_kind == 1) return encode_full_squeezeformer(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
-    if (e->cfg.model_kind == 2) return encode_full_efficient(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
-    if (is_wide(e)) return encode_full_wide(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
+// ConformerEncoder.forward on the fused kernels (masr_encode_full: output_size 256, swish).  chunk: decoding_chunk_size in the
+// streaming-trained build, 0 otherwise
+static int encode_full_conformer(masr_engine* e, hipStream_t s, const float* feats_dev, const int* feat_lens_dev, int B, int T,
+                                 float* enc_out_dev, int chunk) {
     const int d = e->cfg.d_model, H = e->cfg.heads, pad = e->cfg.cnn_kernel - 1;
     int Tq = 0;
     CHK(embed(e, s, feats_dev, B, T, &Tq));
@@ -2231,7 +2216,7 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
         if (fuse_ac) {
             AttnChainArgs a{};
             a.seqs = e->attseq.as<AttSeq>(); a.nseq = B; a.q_stride = 3 * d; a.kv_stride = 3 * d;
-            a.chunk_size = (decoding_chunk_size > 0 && e->cfg.causal) ? decoding_chunk_size : 0; a.pos_stride = 1;
+            a.chunk_size = chunk; a.pos_stride = 1;
             a.ptab = w.ptab; a.bias_u = w.pos_u; a.bias_v = w.pos_v;
             a.Wp = packed_rows_of(e, w.chain_w, 3 * d, s); a.bias = w.chain_b; a.lnw = w.ln_conv_w; a.lnb = w.ln_conv_b;
             a.R = x; a.R2 = x; a.C = e->glu.as<float>(); a.lens = feat_lens_dev; a.seq_t = Tq; a.mstride = 4;
@@ -2241,8 +2226,7 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
             launch_attn_chain(a, Tq, s);
         } else {
             ProfScope ps(e, s, PROF_ATT, 6.0 * d * (double)Tq * Tq * B);
-            launch_attention(e->attseq.as<AttSeq>(), B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v,
-                             (decoding_chunk_size > 0 && e->cfg.causal) ? decoding_chunk_size : 0, 1, s, 256, att_pos(e));   // use_dynamic_chunk only in the streaming build
+            launch_attention(e->attseq.as<AttSeq>(), B, Tq, H, 3 * d, 3 * d, w.ptab, w.pos_u, w.pos_v, chunk, 1, s, 256, att_pos(e));   // use_dynamic_chunk only in the streaming build
         }
         if (few_rows) {
             // few row blocks (one utterance, a handful of short ones): latency-cut kernels of the chunk steps -- the row-block
@@ -2276,6 +2260,31 @@ int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat
     return 0;
 }
 
+// the one refusal of a vocabulary the softmax / pruning kernels cannot hold (masr_ctc_probs and the chunk steps)
+static const char kVocabRefusal[] = "vocab_size > 16384 is not supported by the softmax / pruning kernels (one 256-thread workgroup holds a row in registers)";
+
+extern "C" {
+
+int masr_encode_full(masr_engine* e, const float* feats_dev, const int32_t* feat_lens_dev, int32_t B, int32_t T,
+                     int32_t decoding_chunk_size, float* enc_out_dev, void* stream) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    ENTER(e);
+    CallGuard call_guard(e, (hipStream_t)stream);
+    if (B <= 0) return fail("empty batch");
+    hipStream_t s = (hipStream_t)stream;
+    if (e->cfg.model_kind == 3) return ds2_forward(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, nullptr, nullptr);
+    // decoding_chunk_size > 0 limits the attention to chunks in the streaming-trained builds only (use_dynamic_chunk follows
+    // `streaming`, model.py of every family; utils/mask.py:117-143 ignores it otherwise)
+    const int chunk = (decoding_chunk_size > 0 && e->cfg.causal) ? decoding_chunk_size : 0;
+    // conv2d6 / conv2d8: every mask below tests 4 * t against the lengths in conv2d units
+    if (feat_lens_dev && e->input_layer != IL_CONV2D && !(feat_lens_dev = sub_lens(e, s, feat_lens_dev, B)))
+        return fail("out of device memory (subsampled lengths)");
+    if (e->cfg.model_kind == 1) return encode_full_squeezeformer(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
+    if (e->cfg.model_kind == 2) return encode_full_efficient(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
+    if (is_wide(e)) return encode_full_wide(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
+    return encode_full_conformer(e, s, feats_dev, feat_lens_dev, B, T, enc_out_dev, chunk);
+}
+
 static int ctc_head(masr_engine* e, const float* enc_dev, int M, float* probs_dev, int write_probs, int32_t* argmax_dev,
                     float* maxprob_dev, hipStream_t s) {
     const int d = enc_dim(e), V = e->cfg.vocab_size;
@@ -2296,7 +2305,7 @@ int masr_ctc_probs(masr_engine* e, const float* enc_dev, int32_t M, float* probs
     ENTER(e);
     CallGuard call_guard(e, (hipStream_t)stream);
     if (!probs_dev) return fail("probs_dev is null");
-    if (e->cfg.vocab_size > 16384) return fail("vocab_size > 16384 is not supported by the softmax / pruning kernels (one 256-thread workgroup holds a row in registers)");
+    if (e->cfg.vocab_size > 16384) return fail(kVocabRefusal);
     return ctc_head(e, enc_dev, M, probs_dev, 1, argmax_dev, maxprob_dev, (hipStream_t)stream);
 }
 
@@ -2938,6 +2947,73 @@ static int half_rate_window(const Stream& st, int want, int* first, int* count) 
     return 0;
 }
 
+// ---- the tables and the tail the chunk steps of the families share --------------------------------------------------------
+// The attention descriptor of one stream in one layer whose cache holds interleaved k | v rows of 2 d floats: Tl new queries at q
+// attend over the ncached rows from cache row `first` on and over themselves.
+static AttSeq interleaved_seq(const float* q, float* cache, int d, int first, int ncached, int Tl, float* out, int pos0, int q_abs0) {
+    AttSeq a;
+    a.q = q;
+    a.k = cache + (size_t)first * 2 * d;
+    a.v = a.k + d;
+    a.out = out;
+    a.nq = Tl;
+    a.nk = ncached + Tl;           // (the new rows are appended at k + (nk - nq) rows: the cache row of the first new frame)
+    a.klen = a.nk;
+    a.pos0 = pos0;
+    a.q_abs0 = q_abs0;
+    a.pad_ = 0;
+    return a;
+}
+
+// [read | written]: per (layer, stream) the base of the layer's rows in the stream's cnn cache, then the same in its second half
+static std::vector<float*> cnn_cache_table(const std::vector<Stream*>& st, int L, size_t layer_floats) {
+    const size_t n = st.size();
+    std::vector<float*> hp(n * L * 2);
+    for (int l = 0; l < L; ++l)
+        for (size_t i = 0; i < n; ++i) {
+            hp[(size_t)l * n + i] = st[i]->cnn.as<float>() + (size_t)l * layer_floats;
+            hp[(size_t)(L + l) * n + i] = st[i]->cnn2.as<float>() + (size_t)l * layer_floats;     // written half of the double buffer
+        }
+    return hp;
+}
+
+// The step's tables to the device through the pinned staging area, in one go: the descriptors to e->attseq, the cnn cache pointers to
+// e->cnnptrs and, where a step has one, a third table (the PlaneCopy rows, the abs_pos offsets) to third_dev.
+static int upload_chunk_tables(masr_engine* e, hipStream_t s, const std::vector<AttSeq>& hs, const std::vector<float*>& hp,
+                               void* third_dev = nullptr, const void* third = nullptr, size_t third_bytes = 0) {
+    CHK(e->stage.begin(sizeof(AttSeq) * hs.size() + sizeof(float*) * hp.size() + third_bytes + 64));
+    CHK(e->stage.push(e->attseq.p, hs.data(), sizeof(AttSeq) * hs.size(), s));
+    CHK(e->stage.push(e->cnnptrs.p, hp.data(), sizeof(float*) * hp.size(), s));
+    if (third_bytes) CHK(e->stage.push(third_dev, third, third_bytes, s));
+    CHK(e->stage.end(s));
+    return 0;
+}
+
+// the CTC head on the step's encoder rows: probabilities where the caller asks for them, argmax and its probability always
+static int chunk_ctc(masr_engine* e, hipStream_t s, const float* enc, int rows, float* probs, int32_t* argmax, float* maxprob) {
+    if (e->cfg.vocab_size > 16384) return fail(kVocabRefusal);
+    return ctc_head(e, enc, rows, probs, probs ? 1 : 0, argmax, maxprob, s);
+}
+
+// behind a step of T0 input-rate frames (Tr at the half rate) of the Squeezeformer or the Efficient Conformer
+static void advance_half_rate(std::vector<Stream*>& st, const std::vector<ChunkWindow>& win, int T0, int Tr) {
+    for (size_t i = 0; i < st.size(); ++i) {
+        st[i]->offset += T0;
+        st[i]->offset_r += Tr;
+        st[i]->cache_t1 = win[i].next_cache_t1;
+        st[i]->first_half += win[i].ncs / 2;
+        std::swap(st[i]->cnn, st[i]->cnn2);
+    }
+}
+
+// a stream given twice in one call would be advanced twice from one state
+static int distinct_streams(const std::vector<Stream*>& st) {
+    for (size_t i = 0; i < st.size(); ++i)
+        for (size_t j = 0; j < i; ++j)
+            if (st[i] == st[j]) return fail("duplicate stream id in one call");
+    return 0;
+}
+
 // Squeezeformer chunk step (streaming-trained build), n streams in lock-step: SqueezeformerEncoder.forward_chunk
 // (squeezeformer/encoder.py:240-362) with required_cache_size < 0.  Every layer keeps its key/value cache at its OWN frame
 // rate (the reference stores the half-rate layers repeat-interleaved and reads every second entry back, :338-347), the cnn
@@ -2958,7 +3034,6 @@ static int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector
     CHK(e->attseq.ensure(sizeof(AttSeq) * (size_t)n * L));
     auto reduced = [&](int l) { return e->reduce_idx >= 0 && l >= e->reduce_idx && l < e->recover_idx; };
     std::vector<AttSeq> hs((size_t)n * L);
-    std::vector<float*> hp((size_t)n * L * 2);    // cnn cache bases: current (read) | next (written)
     std::vector<ChunkWindow> win(n);
     std::vector<int> hfirst(n), hcount(n);
     for (int i = 0; i < n; ++i) {
@@ -2969,30 +3044,18 @@ static int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector
     for (int l = 0; l < L; ++l) {
         const int Tl = reduced(l) ? Tr : T0;
         for (int i = 0; i < n; ++i) {
-            AttSeq& a = hs[(size_t)l * n + i];
             const int off = reduced(l) ? st[i]->offset_r : st[i]->offset;
             const int first = reduced(l) ? hfirst[i] : win[i].first_full;       // first cache row attended over
             const int ncached = reduced(l) ? hcount[i] : win[i].cache_t1;
             float* cache = st[i]->att.as<float>() + (size_t)l * st[i]->cap * 2 * d;
-            a.q = e->qkv.as<float>() + (size_t)i * Tl * 3 * d;
-            a.k = cache + (size_t)first * 2 * d;
-            a.v = a.k + d;
-            a.out = e->att.as<float>() + (size_t)i * Tl * d;
-            a.nq = Tl;
-            a.nk = ncached + Tl;           // (the new rows are appended at k + (nk - nq) rows = cache row `off`)
-            a.klen = a.nk;
-            a.pos0 = win[i].first_full;    // key j of a half-rate layer sits at position first_full + 2 j (pos_emb[:, ::2])
-            a.q_abs0 = off;
-            a.pad_ = 0;
-            hp[(size_t)l * n + i] = st[i]->cnn.as<float>() + (size_t)l * pad * d;
-            hp[(size_t)(L + l) * n + i] = st[i]->cnn2.as<float>() + (size_t)l * pad * d;
+            // pos0: key j of a half-rate layer sits at position first_full + 2 j (pos_emb[:, ::2])
+            hs[(size_t)l * n + i] = interleaved_seq(e->qkv.as<float>() + (size_t)i * Tl * 3 * d, cache, d, first, ncached, Tl,
+                                                    e->att.as<float>() + (size_t)i * Tl * d, win[i].first_full, off);
         }
     }
+    const std::vector<float*> hp = cnn_cache_table(st, L, (size_t)pad * d);    // cnn cache bases: current (read) | next (written)
     CHK(e->cnnptrs.ensure(sizeof(float*) * hp.size()));
-    CHK(e->stage.begin(sizeof(AttSeq) * hs.size() + sizeof(float*) * hp.size() + 64));
-    CHK(e->stage.push(e->attseq.p, hs.data(), sizeof(AttSeq) * hs.size(), s));
-    CHK(e->stage.push(e->cnnptrs.p, hp.data(), sizeof(float*) * hp.size(), s));
-    CHK(e->stage.end(s));
+    CHK(upload_chunk_tables(e, s, hs, hp));
     float* x = e->x.as<float>();
     launch_layernorm(x, e->preln_w, e->preln_b, x, n * T0, 1e-5f, 0, 0, nullptr, s);
     CHK(e->enc.ensure((size_t)n * T0 * d * sizeof(float)));
@@ -3049,15 +3112,8 @@ static int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector
         launch_layernorm(x, w.ln3_w, w.ln3_b, x, M, 1e-5f, 0, 0, nullptr, s);
         CHK(ffn(e, s, ffn_sqz2(w, M, l == L - 1 ? e->enc.as<float>() : x)));
     }
-    if (e->cfg.vocab_size > 16384) return fail("vocab_size > 16384 is not supported by the softmax / pruning kernels (one 256-thread workgroup holds a row in registers)");
-    CHK(ctc_head(e, e->enc.as<float>(), n * T0, probs_dev, probs_dev ? 1 : 0, argmax_dev, maxprob_dev, s));
-    for (int i = 0; i < n; ++i) {
-        st[i]->offset += T0;
-        st[i]->offset_r += Tr;
-        st[i]->cache_t1 = win[i].next_cache_t1;
-        st[i]->first_half += win[i].ncs / 2;
-        std::swap(st[i]->cnn, st[i]->cnn2);
-    }
+    CHK(chunk_ctc(e, s, e->enc.as<float>(), n * T0, probs_dev, argmax_dev, maxprob_dev));
+    advance_half_rate(st, win, T0, Tr);
     return 0;
 }
 
@@ -3093,7 +3149,6 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
     const int padmax = e->cfg.cnn_kernel - 1;
     std::vector<AttSeq> hs((size_t)n * L);
     std::vector<PlaneCopy> pcs((size_t)n * e->n_group_layers);
-    std::vector<float*> hp((size_t)n * L * 2);   // cnn cache bases: current (read) | next (written)
     std::vector<ChunkWindow> win(n);
     std::vector<int> hfirst(n), hcount(n);
     for (int i = 0; i < n; ++i) {
@@ -3130,28 +3185,15 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
                 const int off = rate(l) == 2 ? st[i]->offset_r : st[i]->offset;
                 const int first = rate(l) == 2 ? hfirst[i] : win[i].first_full;
                 const int ncached = rate(l) == 2 ? hcount[i] : win[i].cache_t1;
-                a.q = e->qkv.as<float>() + (size_t)i * Tl * 3 * d;
-                a.k = cache + (size_t)first * 2 * d;
-                a.v = a.k + d;
-                a.out = e->att.as<float>() + (size_t)i * Tl * d;
-                a.nq = Tl;
-                a.nk = ncached + Tl;
-                a.klen = a.nk;
-                a.pos0 = win[i].first_full;
-                a.q_abs0 = off;
-                a.pad_ = 0;
+                a = interleaved_seq(e->qkv.as<float>() + (size_t)i * Tl * 3 * d, cache, d, first, ncached, Tl,
+                                    e->att.as<float>() + (size_t)i * Tl * d, win[i].first_full, off);
             }
-            hp[(size_t)l * n + i] = st[i]->cnn.as<float>() + (size_t)l * padmax * d;
-            hp[(size_t)(L + l) * n + i] = st[i]->cnn2.as<float>() + (size_t)l * padmax * d;     // written half of the double buffer
         }
     }
+    const std::vector<float*> hp = cnn_cache_table(st, L, (size_t)padmax * d);   // cnn cache bases: current (read) | next (written)
     CHK(e->cnnptrs.ensure(sizeof(float*) * hp.size() + sizeof(PlaneCopy) * pcs.size()));
     PlaneCopy* pc_dev = reinterpret_cast<PlaneCopy*>(e->cnnptrs.as<float*>() + hp.size());
-    CHK(e->stage.begin(sizeof(AttSeq) * hs.size() + sizeof(float*) * hp.size() + sizeof(PlaneCopy) * pcs.size() + 64));
-    CHK(e->stage.push(e->attseq.p, hs.data(), sizeof(AttSeq) * hs.size(), s));
-    CHK(e->stage.push(e->cnnptrs.p, hp.data(), sizeof(float*) * hp.size(), s));
-    CHK(e->stage.push(pc_dev, pcs.data(), sizeof(PlaneCopy) * pcs.size(), s));
-    CHK(e->stage.end(s));
+    CHK(upload_chunk_tables(e, s, hs, hp, pc_dev, pcs.data(), sizeof(PlaneCopy) * pcs.size()));
     float* x = e->x.as<float>();
     for (int l = 0; l < L; ++l) {
         const LayerW& w = e->layers[l];
@@ -3206,51 +3248,33 @@ static int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Str
     }
     CHK(e->enc.ensure((size_t)n * T2 * d * sizeof(float)));
     launch_layernorm(x, e->after_w, e->after_b, e->enc.as<float>(), n * T2, 1e-5f, 0, 0, nullptr, s);
-    if (e->cfg.vocab_size > 16384) return fail("vocab_size > 16384 is not supported by the softmax / pruning kernels (one 256-thread workgroup holds a row in registers)");
-    CHK(ctc_head(e, e->enc.as<float>(), n * T2, probs_dev, probs_dev ? 1 : 0, argmax_dev, maxprob_dev, s));
-    for (int i = 0; i < n; ++i) {
-        st[i]->offset += T0;
-        st[i]->offset_r += T2;
-        st[i]->cache_t1 = win[i].next_cache_t1;
-        st[i]->first_half += win[i].ncs / 2;
-        std::swap(st[i]->cnn, st[i]->cnn2);
-    }
+    CHK(chunk_ctc(e, s, e->enc.as<float>(), n * T2, probs_dev, argmax_dev, maxprob_dev));
+    advance_half_rate(st, win, T0, T2);
     return 0;
 }
 
-extern "C" {
-
-int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc,
-                      float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, void* stream) {
-    if (!e || !e->finalized) return fail("engine not finalized");
-    ENTER(e);
-    CallGuard call_guard(e, (hipStream_t)stream);
-    if (n <= 0) return fail("no streams");
-    hipStream_t s = (hipStream_t)stream;
-    const int d = e->cfg.d_model, H = e->cfg.heads, L = e->cfg.num_blocks, pad = e->cfg.cnn_kernel - 1;
-    std::vector<Stream*> st(n);
-    for (int i = 0; i < n; ++i) CHK(stream_of(e, stream_ids[i], &st[i]));
+// DeepSpeech2 chunk step, n streams in lock-step (deepspeech2/model.py:79-108): chunk conv + LSTM stack with carried (h, c)
+static int encode_chunk_ds2(masr_engine* e, hipStream_t s, std::vector<Stream*>& st, const float* feats_dev, int Tc,
+                            float* probs_dev, int32_t* argmax_dev, float* maxprob_dev) {
+    const int n = (int)st.size();
     int Tq = 0;
-    if (e->cfg.model_kind == 1 || e->cfg.model_kind == 2) {
-        for (int i = 0; i < n; ++i)
-            for (int j = 0; j < i; ++j)
-                if (st[i] == st[j]) return fail("duplicate stream id in one call");
-        return e->cfg.model_kind == 1 ? encode_chunk_squeezeformer(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev)
-                                      : encode_chunk_efficient(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev);
-    }
-    if (e->cfg.model_kind == 3) {       // deepspeech2/model.py:79-108: chunk conv + LSTM stack with carried (h, c)
-        for (int i = 0; i < n; ++i)
-            for (int j = 0; j < i; ++j)
-                if (st[i] == st[j]) return fail("duplicate stream id in one call");
-        const int Tq3 = ((Tc - 1) / 2 - 1) / 2;
-        if (Tq3 <= 0) return fail("chunk too short");
-        CHK(e->enc.ensure((size_t)n * Tq3 * enc_dim(e) * sizeof(float)));
-        CHK(ds2_forward(e, s, feats_dev, nullptr, n, Tc, e->enc.as<float>(), st.data(), &Tq));
-        if (e->cfg.vocab_size > 16384) return fail("vocab_size > 16384 is not supported by the softmax / pruning kernels (one 256-thread workgroup holds a row in registers)");
-        CHK(ctc_head(e, e->enc.as<float>(), n * Tq, probs_dev, probs_dev ? 1 : 0, argmax_dev, maxprob_dev, s));
-        for (int i = 0; i < n; ++i) st[i]->offset += Tq;
-        return 0;
-    }
+    const int Tq3 = ((Tc - 1) / 2 - 1) / 2;
+    if (Tq3 <= 0) return fail("chunk too short");
+    CHK(e->enc.ensure((size_t)n * Tq3 * enc_dim(e) * sizeof(float)));
+    CHK(ds2_forward(e, s, feats_dev, nullptr, n, Tc, e->enc.as<float>(), st.data(), &Tq));
+    CHK(chunk_ctc(e, s, e->enc.as<float>(), n * Tq, probs_dev, argmax_dev, maxprob_dev));
+    for (int i = 0; i < n; ++i) st[i]->offset += Tq;
+    return 0;
+}
+
+// Conformer chunk step, n streams in lock-step: ConformerEncoder.forward_chunk (conformer/encoder.py:355-420), on the fused
+// kernels or (is_wide) on the width-generic layer.  Unlike the other families' steps this one has never refused a stream id given
+// twice in one call (distinct_streams): whether it should is a behaviour decision of its own.
+static int encode_chunk_conformer(masr_engine* e, hipStream_t s, std::vector<Stream*>& st, const float* feats_dev, int Tc,
+                                  float* probs_dev, int32_t* argmax_dev, float* maxprob_dev) {
+    const int n = (int)st.size();
+    const int d = e->cfg.d_model, H = e->cfg.heads, L = e->cfg.num_blocks, pad = e->cfg.cnn_kernel - 1;
+    int Tq = 0;
     CHK(embed(e, s, feats_dev, n, Tc, &Tq));
     for (int i = 0; i < n; ++i)
         if (st[i]->offset + Tq > st[i]->cap) return fail("stream exceeds its max_frames_out / max_pos");
@@ -3263,41 +3287,23 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
     std::vector<AttSeq> hs((size_t)n * L);
     for (int l = 0; l < L; ++l)
         for (int i = 0; i < n; ++i) {
-            AttSeq& a = hs[(size_t)l * n + i];
             float* cache = st[i]->att.as<float>() + (size_t)l * st[i]->cap * 2 * d;
             // keys the chunk attends over: the last cache_t1 cached rows + its own (encoder.py:390-395,397-410: the reference
             // trims its cache tensor to required_cache_size after every step; here the rows stay where they were appended and
             // the window moves).  The positional index of the first key is offset - cache_t1.
             const int cache_t1 = st[i]->cache_t1;
             const int first = st[i]->offset - cache_t1;
-            a.q = e->qkv.as<float>() + (size_t)i * Tq * 3 * d;
-            a.k = cache + (size_t)first * 2 * d;
-            a.v = a.k + d;
-            a.out = e->att.as<float>() + (size_t)i * Tq * d;
-            a.nq = Tq;
-            a.nk = cache_t1 + Tq;          // (the new rows are appended at k + (nk - nq) rows = cache row `offset`)
-            a.klen = a.nk;
-            a.pos0 = first;
-            a.q_abs0 = st[i]->offset;
-            a.pad_ = 0;
+            hs[(size_t)l * n + i] = interleaved_seq(e->qkv.as<float>() + (size_t)i * Tq * 3 * d, cache, d, first, cache_t1, Tq,
+                                                    e->att.as<float>() + (size_t)i * Tq * d, first, st[i]->offset);
         }
-    std::vector<float*> hp((size_t)n * L * 2);    // cnn cache base of (layer, stream): current (read) | next (written)
-    for (int l = 0; l < L; ++l)
-        for (int i = 0; i < n; ++i) {
-            hp[(size_t)l * n + i] = st[i]->cnn.as<float>() + (size_t)l * pad * d;
-            hp[(size_t)(L + l) * n + i] = st[i]->cnn2.as<float>() + (size_t)l * pad * d;
-        }
+    const std::vector<float*> hp = cnn_cache_table(st, L, (size_t)pad * d);    // cnn cache base of (layer, stream): current (read) | next (written)
     CHK(e->cnnptrs.ensure(sizeof(float*) * hp.size()));
     std::vector<int> ho;                          // abs_pos: pe[offset : offset + Tq] of every stream (embedding.py:52-54)
     if (e->pos_enc == POS_ENC_ABS) {
         for (int i = 0; i < n; ++i) ho.push_back(st[i]->offset);
         CHK(e->posoff.ensure(sizeof(int) * ho.size()));
     }
-    CHK(e->stage.begin(sizeof(AttSeq) * hs.size() + sizeof(float*) * hp.size() + sizeof(int) * ho.size() + 64));
-    CHK(e->stage.push(e->attseq.p, hs.data(), sizeof(AttSeq) * hs.size(), s));
-    CHK(e->stage.push(e->cnnptrs.p, hp.data(), sizeof(float*) * hp.size(), s));
-    if (!ho.empty()) CHK(e->stage.push(e->posoff.p, ho.data(), sizeof(int) * ho.size(), s));
-    CHK(e->stage.end(s));
+    CHK(upload_chunk_tables(e, s, hs, hp, e->posoff.p, ho.data(), sizeof(int) * ho.size()));
     add_abs_pos(e, s, n, Tq, e->posoff.as<int>());
     float* x = e->x.as<float>();
     EncodeCtx ctx{n, Tq, nullptr};
@@ -3327,14 +3333,34 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
     CHK(e->enc.ensure((size_t)M * d * sizeof(float)));
     if (wide) WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, e->after_w, e->after_b, e->enc.as<float>(), M, d, 1e-5f, 0, 0, nullptr, s));
     else launch_layernorm(x, e->after_w, e->after_b, e->enc.as<float>(), M, 1e-5f, 0, 0, nullptr, s);
-    if (e->cfg.vocab_size > 16384) return fail("vocab_size > 16384 is not supported by the softmax / pruning kernels (one 256-thread workgroup holds a row in registers)");
-    CHK(ctc_head(e, e->enc.as<float>(), M, probs_dev, probs_dev ? 1 : 0, argmax_dev, maxprob_dev, s));
+    CHK(chunk_ctc(e, s, e->enc.as<float>(), M, probs_dev, argmax_dev, maxprob_dev));
     for (int i = 0; i < n; ++i) {
         st[i]->cache_t1 = chunk_window(*st[i], Tq).next_cache_t1;
         st[i]->offset += Tq;
         std::swap(st[i]->cnn, st[i]->cnn2);
     }
     return 0;
+}
+
+extern "C" {
+
+int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc,
+                      float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, void* stream) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    ENTER(e);
+    CallGuard call_guard(e, (hipStream_t)stream);
+    if (n <= 0) return fail("no streams");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<Stream*> st(n);
+    for (int i = 0; i < n; ++i) CHK(stream_of(e, stream_ids[i], &st[i]));
+    // (the Conformer step, model_kind 0, has never had this check and gets none here: whether it should is a behaviour decision)
+    if (e->cfg.model_kind != 0) CHK(distinct_streams(st));
+    switch (e->cfg.model_kind) {
+    case 1: return encode_chunk_squeezeformer(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev);
+    case 2: return encode_chunk_efficient(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev);
+    case 3: return encode_chunk_ds2(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev);
+    default: return encode_chunk_conformer(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev);
+    }
 }
 
 int masr_stream_export_cache(masr_engine* e, int32_t stream_id, float* att_dev, float* cnn_dev, void* stream) {
