@@ -514,7 +514,8 @@ int masr_op_attention_plain(masr_engine* e, const float* q_dev, const float* k_d
  *                        entry validated (lengths in [0, Lmax], ids in [0, vocab_size), frames in [1, Tp]); outputs to host
  *                        arrays; returns when the work has finished.
  *   masr_decoder_info    enabled | left blocks | right blocks | bytes of decoder weights on the device | bytes of decoder
- *                        workspace of the ACTIVE lane (0 until its first masr_rescore).  Null outputs are skipped. */
+ *                        workspace of the ACTIVE lane (0 until its first masr_rescore / masr_attention_decode /
+ *                        masr_op_decoder_step; the step workspaces of the search are counted).  Null outputs are skipped. */
 int masr_decoder_enable(masr_engine* e, int32_t attention_heads, int32_t linear_units, int32_t num_blocks, int32_t r_num_blocks);
 int masr_rescore(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const int32_t* hyp_dev,
                  const int32_t* hyp_lens_dev, int32_t N, int32_t Lmax, int32_t with_right, float* att_dev, float* r_att_dev,
@@ -524,6 +525,49 @@ int masr_op_decoder_scores(masr_engine* e, const float* enc_dev, const int32_t* 
                            float* att_host, float* r_att_host, void* stream);
 int masr_decoder_info(masr_engine* e, int32_t* enabled, int32_t* num_blocks, int32_t* r_num_blocks, int64_t* weight_bytes,
                       int64_t* workspace_bytes);
+
+/* Attention decoding (`decoder: attention`): left-to-right beam search driven by the LEFT decoder alone, one decoder row per
+ * hypothesis and step (TransformerDecoder.forward_one_step, masr/model_utils/transformer/decoder.py:233-270), everything on the
+ * device.  sos = eos = vocab_size - 1; N = beam_size.  Per utterance b over its valid frames enc[b, :enc_lens[b]]:
+ *   start    N hypotheses [sos] with scores [0, -inf, ..., -inf], none finished.
+ *   step i   logp = log_softmax(output_layer(after_norm(x_last))) of every hypothesis; its top N, the LARGER value first and of
+ *            bit-equal values the SMALLER token id first.  A hypothesis whose last token is eos offers (0, eos), (-inf, eos), ...
+ *            instead.  Candidate score = hypothesis score + logp; the top N of the utterance's N x N candidates, of bit-equal
+ *            scores (-inf included) the SMALLER flat index parent_rank * N + candidate_rank first; the new hypotheses are parent +
+ *            token in that order.  (torch.topk leaves the order of ties open; these rules are this library's.)
+ *   stop     after limit_b = min(enc_lens[b], max_len when max_len > 0, max_pos - 1, Lcap) steps -- per utterance, so that an
+ *            utterance's result is that of the same search run on it alone -- or earlier when all N are finished.  Steps past
+ *            that add +0 and eos and change no result.
+ *   result   per rank n (best first): tokens_dev [B, N, Lcap] = the tokens behind sos up to and excluding the first eos (eos from
+ *            there on), lens_dev [B, N] their count, scores_dev [B, N] the summed log-probability.  The best hypothesis is rank
+ *            0 (the highest score, an exact tie to the earlier rank).  No CTC score, no length penalty, no right decoder.
+ * Self-attention k | v of a position are projected once and kept per layer ([blocks][steps][B * N][2 d]); reordering the beam
+ * rewrites a small ancestor table, never the cache.  The encoder k | v projection is one GEMM per layer before the loop.
+ *   masr_attention_decode  enc_dev [B, Tp, d_model], enc_lens_dev [B] -> the result above; *steps_host_or_null = steps launched.
+ *                        Runs on `stream` and the active lane's workspaces.  The only host round trip is the end poll: every
+ *                        MASR_ATTENTION_POLL steps (environment, read per call; default 8, 0 = never) the host waits for the
+ *                        count of utterances still running and stops launching at 0; results do not depend on it.  A hypothesis'
+ *                        tokens and score are bit-identical whatever B, the other utterances, Tp or the lane: every launch is row-
+ *                        local or per utterance, and the tiled f32 GEMM accumulates an element over K in the same order in each of
+ *                        its tile shapes (the shape is chosen by the row count).  This does not extend to the experimental split-
+ *                        bf16 GEMM (masr_debug_set, experiment builds only).  Memory: the self-attention cache holds blocks x
+ *                        steps x B x N x 2 d_model floats for steps = min(Tp, Lcap, max_len, max_pos - 1) (488 MB at 32 utterances
+ *                        of 248 frames, beam 10, 3 blocks, d_model 256): the caller bounds it through max_len or Lcap, and a
+ *                        failed allocation is reported by name.  Refused by name:
+ *                        no decoder (masr_decoder_enable), beam_size outside 1 .. 64 or above vocab_size, B * beam_size > 65535,
+ *                        Lcap < 1, max_len < 0.
+ *   masr_op_decoder_step  the step's launches driven alone from HOST tables (teacher forced): prefix_host [B * N, L] tokens behind
+ *                        sos, prefix_lens_host [B * N] in 0 .. L, enc_lens_host [B] in 1 .. Tp, ids in [0, vocab_size), every
+ *                        entry validated.  The prefixes are fed one position at a time through the same launches and the same
+ *                        k | v cache as the search (row s is its own ancestor); each row reports at its last position:
+ *                        top_ids_host / top_logp_host [B * N, top_n] (top_n in 1 .. min(64, vocab_size)) and, when given,
+ *                        logp_host_or_null [B * N, vocab_size].  Returns when the work has finished. */
+int masr_attention_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, int32_t beam_size,
+                          int32_t max_len, int32_t* tokens_dev, int32_t Lcap, int32_t* lens_dev, float* scores_dev,
+                          int32_t* steps_host_or_null, void* stream);
+int masr_op_decoder_step(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t Tp,
+                         const int32_t* prefix_host, const int32_t* prefix_lens_host, int32_t N, int32_t L, int32_t top_n,
+                         int32_t* top_ids_host, float* top_logp_host, float* logp_host_or_null, void* stream);
 /* The N best prefixes of the LM-free host-thread search (masr_beam_search_batch's search, same pruned candidates): per utterance
  * tokens_host [B, nbest, max_len], len_host [B, nbest], score_host [B, nbest] = log probability of each prefix, count_host [B] =
  * prefixes returned (<= min(nbest, beam_size)), best first in the search's own order (score, then the smaller last character), so

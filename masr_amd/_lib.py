@@ -119,6 +119,8 @@ SIGNATURES = {
     'masr_rescore': [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
     'masr_op_decoder_scores': [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
     'masr_decoder_info': [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    'masr_attention_decode': [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, C.POINTER(_I), _P],
+    'masr_op_decoder_step': [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     'masr_beam_search_batch_nbest': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
     'masr_side_stream': [_P, _I, C.POINTER(_P)],
     'masr_select_lane': [_P, _I],

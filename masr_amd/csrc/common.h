@@ -572,6 +572,43 @@ void launch_dec_attention(const float* q, int q_stride, const float* k, const fl
 void launch_dec_scores(const float* logits, const int* hyp, const int* lens, float* rowlp, float* out, int S, int Lmax, int V,
                        int reverse, hipStream_t s);
 
+// ---- attention decoder, one autoregressive step (decoder_step.hip; decoder: attention) ----
+// Row s = b * N + n; step i handles position p = i - 1.  tok / anc [S, Lcap] int32: the tokens after sos and, per position j < p,
+// the rank whose cache slot holds the hypothesis' position j.
+// x [S, d] = emb[last token] * sqrt(d) + pe[p]  (last token: sos = V - 1 at p = 0, else tok[s][p - 1])
+void launch_step_embed(const int* tok, const float* emb, const float* pe, float* x, int S, int p, int Lcap, int d, int V,
+                       hipStream_t s);
+// one query per (hypothesis, head of 64), the keys split over the lanes of a wave.  anc given: self-attention over positions
+// 0 .. p of the cache kv [Lrun][S][2 d] (key p is the row's own slot); anc null: source attention over the key_lens[s / N] frames of
+// kv [B * Tp][2 d]
+void launch_step_attention(const float* q, int q_stride, const float* kv, float* out, const int* anc, const int* key_lens, int S,
+                           int N, int Tp, int Lcap, int p, int d, int heads, hipStream_t s);
+// log_softmax + top n of each logits row (larger first, bit-equal values: the smaller id first) -> top_v / top_i [S, n]; full
+// [S, V] log-probabilities when given; only_pos [S] given: a row writes at p == only_pos[row] alone
+void launch_step_topn(const float* logits, int S, int V, int n, float* top_v, int* top_i, float* full, const int* only_pos, int p,
+                      hipStream_t s);
+struct StepMerge {           // the merge kernel's argument
+    const float* top_v;      // [S, N]
+    const int* top_i;        // [S, N]
+    const float* score_cur;  // [S]
+    float* score_next;
+    const int* tok_cur;      // [S, Lcap]
+    int* tok_next;
+    const int* anc_cur;      // [S, Lcap]
+    int* anc_next;
+    const int* enc_lens;     // [B]
+    int* done;               // [B] 0 / 1
+    int* active;             // [1] utterances not done
+    int N, Lcap, Tp, V, p, max_len, max_pos;
+};
+// beam merge of step p + 1, per utterance (finished-row masking, N x N top N with ties to the smaller flat index, tables through
+// the parent index, the count of utterances still running in *active)
+void launch_step_merge(const StepMerge& m, int B, hipStream_t s);
+void launch_step_init(float* score, int* done, int* active, const int* enc_lens, int B, int N, int Tp, int Lcap, int max_len,
+                      int max_pos, hipStream_t s);
+void launch_step_result(const int* tok, const float* score, const int* enc_lens, int* tokens_out, int* lens_out, float* scores_out,
+                        int S, int N, int Lcap, int Tp, int V, int steps, int max_len, int max_pos, hipStream_t s);
+
 // ---- features ------------------------------------------------------------------------------
 size_t fbank_gain_scratch_floats(int B);   // size of gain_scratch ([B] gains + partial sums)
 // use_db: 0 = no dB normalisation, 1 = gains computed on the device, 2 = gains supplied in gain_scratch[0 .. B)

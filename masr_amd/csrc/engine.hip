@@ -238,14 +238,22 @@ struct EngineWs {
     // residual rows, LayerNorm rows, q | k | v (self) / q (source), attention output, source k | v of the encoder frames, FFN hidden
     // rows, logits, per-row log-probabilities
     DevBuf dec_x, dec_ln, dec_qkv, dec_att, dec_kv, dec_hid, dec_logits, dec_rowlp;
+    // autoregressive search (masr_attention_decode / masr_op_decoder_step; allocated on the lane's first such call): the step's rows
+    // (residual, LayerNorm, q, attention output, FFN hidden, logits), the self-attention k | v cache [blocks][Lrun][S][2 d], the
+    // source k | v [blocks][B * Tp][2 d], top-N values | ids, the double-buffered token / ancestor / score tables and flags, and
+    // the test op's [S, V] log-probabilities
+    DevBuf st_x, st_ln, st_q, st_att, st_hid, st_logits, st_cache, st_src, st_top, st_tab, st_full;
     size_t decoder_bytes() const {
-        return dec_x.bytes + dec_ln.bytes + dec_qkv.bytes + dec_att.bytes + dec_kv.bytes + dec_hid.bytes + dec_logits.bytes + dec_rowlp.bytes;
+        return dec_x.bytes + dec_ln.bytes + dec_qkv.bytes + dec_att.bytes + dec_kv.bytes + dec_hid.bytes + dec_logits.bytes +
+               dec_rowlp.bytes + st_x.bytes + st_ln.bytes + st_q.bytes + st_att.bytes + st_hid.bytes + st_logits.bytes + st_cache.bytes +
+               st_src.bytes + st_top.bytes + st_tab.bytes + st_full.bytes;
     }
     void release_all() {
         for (DevBuf* b : {&gx, &rnn_out, &hstate, &cstate, &ds2_lens, &qplanes, &attp, &cnnptrs, &ffpart, &fb_scratch, &x1, &x2, &x,
                           &ln, &hid, &qkv, &att, &lnpad, &glu, &dwo, &logits, &feats, &enc, &idx, &maxp, &attseq, &gain, &nframes,
                           &lens, &xsave, &xred, &xh, &x3, &sublens, &posoff, &dec_x, &dec_ln, &dec_qkv, &dec_att, &dec_kv, &dec_hid,
-                          &dec_logits, &dec_rowlp})
+                          &dec_logits, &dec_rowlp, &st_x, &st_ln, &st_q, &st_att, &st_hid, &st_logits, &st_cache, &st_src, &st_top,
+                          &st_tab, &st_full})
             b->release();
         stage.release();
     }
@@ -3905,6 +3913,238 @@ int masr_op_decoder_scores(masr_engine* e, const float* enc_dev, const int32_t* 
     CHK(rescore_impl(e, enc_dev, enc_d, B, Tp, hyp_d, len_d, N, Lmax, with_right, att_d, ratt_d, st));
     HIPCHK(hipMemcpyAsync(att_host, att_d, S * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(r_att_host, ratt_d, S * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// decoder: attention -- left-to-right beam search with the LEFT decoder alone, one new row per hypothesis and step
+// (forward_one_step, transformer/decoder.py:233-270; the kernels and the cache layout: decoder_step.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct StepPlan {
+    int B, N, S, Tp, Lcap, Lrun, max_len;
+    int *tok[2], *anc[2], *done, *active;
+    float* score[2];
+};
+
+// steps the host may have to launch: no utterance runs longer (enc_lens <= Tp)
+int step_run_bound(const masr_engine* e, int Tp, int Lcap, int max_len) {
+    int r = std::min(std::min(Tp, Lcap), e->cfg.max_pos - 1);
+    if (max_len > 0) r = std::min(r, max_len);
+    return std::max(r, 1);
+}
+
+int step_workspaces(masr_engine* e, StepPlan& pl, int topn) {
+    const int d = e->cfg.d_model, V = e->cfg.vocab_size, nl = e->dec.nl;
+    const size_t S = (size_t)pl.S, f = sizeof(float);
+    CHK(e->st_x.ensure(S * d * f));
+    CHK(e->st_ln.ensure(S * d * f));
+    CHK(e->st_q.ensure(S * d * f));
+    CHK(e->st_att.ensure(S * d * f));
+    CHK(e->st_hid.ensure(S * e->dec.dff * f));
+    CHK(e->st_logits.ensure(S * V * f));
+    CHK(e->st_cache.ensure((size_t)nl * pl.Lrun * S * 2 * d * f));
+    CHK(e->st_src.ensure((size_t)nl * pl.B * pl.Tp * 2 * d * f));
+    CHK(e->st_top.ensure(S * topn * (f + sizeof(int))));
+    // tok[2] | anc[2] [S, Lcap], score[2] [S], done [B], active [1]
+    const size_t tab = S * pl.Lcap;
+    CHK(e->st_tab.ensure((4 * tab + 2 * S + pl.B + 1) * sizeof(int)));
+    int* t = e->st_tab.as<int>();
+    pl.tok[0] = t;
+    pl.tok[1] = t + tab;
+    pl.anc[0] = t + 2 * tab;
+    pl.anc[1] = t + 3 * tab;
+    pl.score[0] = reinterpret_cast<float*>(t + 4 * tab);
+    pl.score[1] = pl.score[0] + S;
+    pl.done = t + 4 * tab + 2 * S;
+    pl.active = pl.done + pl.B;
+    return 0;
+}
+
+// source k | v of every block: ONE GEMM per utterance batch and layer, before the loop
+void step_source_kv(masr_engine* e, hipStream_t s, const float* enc, const StepPlan& pl) {
+    const int d = e->cfg.d_model, Mk = pl.B * pl.Tp;
+    float* src = e->st_src.as<float>();
+    for (size_t i = 0; i < e->dec.left.layers.size(); ++i) {
+        const DecLayerW& l = e->dec.left.layers[i];
+        gemm(e, s, enc, d, l.wkv2, l.bkv2, src + i * (size_t)Mk * 2 * d, 2 * d, Mk, 2 * d, d, ACT_NONE, 1.f, nullptr, 0);
+    }
+}
+
+// position p of every row: embedding, the blocks (the new k | v written straight into cache slab p), after_norm, output layer,
+// log_softmax + top n.  full / only_pos: the teacher-forced op's outputs (launch_step_topn)
+int step_forward(masr_engine* e, hipStream_t s, const StepPlan& pl, int p, const int* tok, const int* anc, const int* enc_lens,
+                 int topn, float* full, const int* only_pos) {
+    const DecoderW& w = e->dec.left;
+    const int d = e->cfg.d_model, V = e->cfg.vocab_size, dff = e->dec.dff, H = e->dec.heads, S = pl.S;
+    float *x = e->st_x.as<float>(), *ln = e->st_ln.as<float>(), *q = e->st_q.as<float>(), *att = e->st_att.as<float>(),
+          *hid = e->st_hid.as<float>(), *logits = e->st_logits.as<float>();
+    const float eps = 1e-12f;
+    launch_step_embed(tok, w.emb, e->pe, x, S, p, pl.Lcap, d, V, s);
+    for (size_t i = 0; i < w.layers.size(); ++i) {
+        const DecLayerW& l = w.layers[i];
+        float* cache = e->st_cache.as<float>() + i * (size_t)pl.Lrun * S * 2 * d;
+        const float* src = e->st_src.as<float>() + i * (size_t)pl.B * pl.Tp * 2 * d;
+        // x <- x + Wo . self_attn(norm1(x)): q of the new row; its k | v (rows d .. 3 d of the fused projection) appended as slab p
+        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n1w, l.n1b, ln, S, d, eps, 0, 0, nullptr, s));
+        gemm(e, s, ln, d, l.wqkv, l.bqkv, q, d, S, d, d, ACT_NONE, 1.f, nullptr, 0);
+        gemm(e, s, ln, d, l.wqkv + (size_t)d * d, l.bqkv + d, cache + (size_t)p * S * 2 * d, 2 * d, S, 2 * d, d, ACT_NONE, 1.f, nullptr, 0);
+        launch_step_attention(q, d, cache, att, anc, nullptr, S, pl.N, pl.Tp, pl.Lcap, p, d, H, s);
+        gemm(e, s, att, d, l.wo, l.bo, x, d, S, d, d, ACT_NONE, 1.f, x, d);
+        // x <- x + Wo . src_attn(norm2(x), memory)
+        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n2w, l.n2b, ln, S, d, eps, 0, 0, nullptr, s));
+        gemm(e, s, ln, d, l.wq2, l.bq2, q, d, S, d, d, ACT_NONE, 1.f, nullptr, 0);
+        launch_step_attention(q, d, src, att, nullptr, enc_lens, S, pl.N, pl.Tp, pl.Lcap, p, d, H, s);
+        gemm(e, s, att, d, l.wo2, l.bo2, x, d, S, d, d, ACT_NONE, 1.f, x, d);
+        // x <- x + W2 . relu(W1 . norm3(x))
+        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n3w, l.n3b, ln, S, d, eps, 0, 0, nullptr, s));
+        gemm(e, s, ln, d, l.w1, l.b1, hid, dff, S, dff, d, ACT_RELU, 1.f, nullptr, 0);
+        gemm(e, s, hid, dff, l.w2, l.b2, x, d, S, d, dff, ACT_NONE, 1.f, x, d);
+    }
+    WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, w.after_w, w.after_b, ln, S, d, eps, 0, 0, nullptr, s));
+    gemm(e, s, ln, d, w.out_w, w.out_b, logits, V, S, V, d, ACT_NONE, 1.f, nullptr, 0);
+    float* top_v = e->st_top.as<float>();
+    int* top_i = reinterpret_cast<int*>(top_v + (size_t)S * topn);
+    launch_step_topn(logits, S, V, topn, top_v, top_i, full, only_pos, p, s);
+    return 0;
+}
+
+int step_shape_check(const masr_engine* e, const char* who, int B, int Tp, int N, int Lcap) {
+    const std::string w(who);
+    if (B <= 0 || Tp <= 0) return fail(w + ": B and Tp must be positive");
+    if (N < 1 || N > 64) return fail(w + ": beam_size = " + std::to_string(N) + " is outside 1 .. 64");
+    if (Lcap < 1) return fail(w + ": Lcap must be at least 1");
+    if ((int64_t)B * N > 65535) return fail(w + ": B * beam_size must not exceed 65535 hypotheses per call");
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!e->dec.enabled || !e->dec.ready)
+        return fail(w + ": this engine holds no attention decoder (masr_decoder_enable before masr_finalize)");
+    if (N > e->cfg.vocab_size)
+        return fail(w + ": beam_size = " + std::to_string(N) + " exceeds the vocabulary of " + std::to_string(e->cfg.vocab_size));
+    return 0;
+}
+
+// end poll of masr_attention_decode: every MASR_ATTENTION_POLL steps (default 8; 0 = never) the host reads the count of
+// utterances still running and stops launching at 0.  The results do not depend on it.
+int step_poll_every() {
+    const char* v = getenv("MASR_ATTENTION_POLL");
+    if (!v || !*v) return 8;
+    const int n = atoi(v);
+    return n < 0 ? 0 : n;
+}
+
+}  // namespace
+
+extern "C" {
+
+int masr_attention_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, int32_t beam_size,
+                          int32_t max_len, int32_t* tokens_dev, int32_t Lcap, int32_t* lens_dev, float* scores_dev,
+                          int32_t* steps_host_or_null, void* stream) {
+    if (!enc_dev || !enc_lens_dev || !tokens_dev || !lens_dev || !scores_dev) return fail("masr_attention_decode: null argument");
+    if (max_len < 0) return fail("masr_attention_decode: max_len must be 0 (no limit of its own) or positive");
+    CHK(step_shape_check(e, "masr_attention_decode", B, Tp, beam_size, Lcap));
+    ENTER(e);
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard call_guard(e, st);
+    StepPlan pl{};
+    pl.B = B; pl.N = beam_size; pl.S = B * beam_size; pl.Tp = Tp; pl.Lcap = Lcap; pl.max_len = max_len;
+    pl.Lrun = step_run_bound(e, Tp, Lcap, max_len);
+    CHK(step_workspaces(e, pl, pl.N));
+    const int V = e->cfg.vocab_size, poll = step_poll_every();
+    launch_step_init(pl.score[0], pl.done, pl.active, enc_lens_dev, B, pl.N, Tp, Lcap, max_len, e->cfg.max_pos, st);
+    step_source_kv(e, st, enc_dev, pl);
+    float* top_v = e->st_top.as<float>();
+    int cur = 0, steps = 0;
+    for (int p = 0; p < pl.Lrun; ++p) {
+        CHK(step_forward(e, st, pl, p, pl.tok[cur], pl.anc[cur], enc_lens_dev, pl.N, nullptr, nullptr));
+        StepMerge m{};
+        m.top_v = top_v; m.top_i = reinterpret_cast<const int*>(top_v + (size_t)pl.S * pl.N);
+        m.score_cur = pl.score[cur]; m.score_next = pl.score[cur ^ 1];
+        m.tok_cur = pl.tok[cur]; m.tok_next = pl.tok[cur ^ 1]; m.anc_cur = pl.anc[cur]; m.anc_next = pl.anc[cur ^ 1];
+        m.enc_lens = enc_lens_dev; m.done = pl.done; m.active = pl.active;
+        m.N = pl.N; m.Lcap = Lcap; m.Tp = Tp; m.V = V; m.p = p; m.max_len = max_len; m.max_pos = e->cfg.max_pos;
+        launch_step_merge(m, B, st);
+        cur ^= 1;
+        steps = p + 1;
+        if (poll > 0 && steps % poll == 0 && steps < pl.Lrun) {
+            int active = 1;
+            HIPCHK(hipMemcpyAsync(&active, pl.active, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (active <= 0) break;
+        }
+    }
+    launch_step_result(pl.tok[cur], pl.score[cur], enc_lens_dev, tokens_dev, lens_dev, scores_dev, pl.S, pl.N, Lcap, Tp, V, steps,
+                       max_len, e->cfg.max_pos, st);
+    LAUNCHCHK();
+    if (steps_host_or_null) *steps_host_or_null = steps;
+    return 0;
+}
+
+int masr_op_decoder_step(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t Tp,
+                         const int32_t* prefix_host, const int32_t* prefix_lens_host, int32_t N, int32_t L, int32_t top_n,
+                         int32_t* top_ids_host, float* top_logp_host, float* logp_host_or_null, void* stream) {
+    if (!enc_dev || !enc_lens_host || !prefix_host || !prefix_lens_host || !top_ids_host || !top_logp_host)
+        return fail("masr_op_decoder_step: null argument");
+    CHK(step_shape_check(e, "masr_op_decoder_step", B, Tp, N, L));
+    const int V = e->cfg.vocab_size, S = B * N;
+    if (top_n < 1 || top_n > 64 || top_n > V)
+        return fail("masr_op_decoder_step: top_n = " + std::to_string(top_n) + " is outside 1 .. min(64, vocabulary)");
+    if (L + 1 > e->cfg.max_pos - 1)
+        return fail("masr_op_decoder_step: prefixes of L = " + std::to_string(L) + " tokens behind sos exceed max_pos - 1 = " +
+                    std::to_string(e->cfg.max_pos - 1) + " positions");
+    for (int b = 0; b < B; ++b)
+        if (enc_lens_host[b] < 1 || enc_lens_host[b] > Tp)
+            return fail("masr_op_decoder_step: utterance " + std::to_string(b) + " has " + std::to_string(enc_lens_host[b]) +
+                        " encoder frames, outside 1 .. Tp");
+    int maxlen = 0;
+    for (int s = 0; s < S; ++s) {
+        if (prefix_lens_host[s] < 0 || prefix_lens_host[s] > L)
+            return fail("masr_op_decoder_step: prefix " + std::to_string(s) + " has length " + std::to_string(prefix_lens_host[s]) +
+                        ", outside 0 .. L");
+        maxlen = std::max(maxlen, prefix_lens_host[s]);
+        for (int i = 0; i < prefix_lens_host[s]; ++i) {
+            const int t = prefix_host[(size_t)s * L + i];
+            if (t < 0 || t >= V)
+                return fail("masr_op_decoder_step: token id " + std::to_string(t) + " of prefix " + std::to_string(s) +
+                            " is outside the vocabulary");
+        }
+    }
+    ENTER(e);
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard call_guard(e, st);
+    StepPlan pl{};
+    pl.B = B; pl.N = N; pl.S = S; pl.Tp = Tp; pl.Lcap = L; pl.max_len = 0;
+    pl.Lrun = maxlen + 1;                      // positions 0 .. maxlen: [sos, tokens...]
+    CHK(step_workspaces(e, pl, top_n));
+    if (logp_host_or_null) CHK(e->st_full.ensure((size_t)S * V * sizeof(float)));
+    // every row is its own ancestor at every position; it writes its outputs at its last position, p = its length
+    std::vector<int> anc((size_t)S * L), pos(S), tok((size_t)S * L, 0);
+    for (int s = 0; s < S; ++s) {
+        pos[s] = prefix_lens_host[s];
+        for (int j = 0; j < L; ++j) anc[(size_t)s * L + j] = s % N;
+        for (int j = 0; j < prefix_lens_host[s]; ++j) tok[(size_t)s * L + j] = prefix_host[(size_t)s * L + j];
+    }
+    struct Table {
+        int* p = nullptr;
+        ~Table() { if (p) (void)hipFree(p); }
+    } tab;
+    HIPCHK(hipMalloc((void**)&tab.p, (size_t)(S + B) * sizeof(int)));
+    int *pos_d = tab.p, *enc_d = pos_d + S;
+    HIPCHK(hipMemcpyAsync(pl.tok[0], tok.data(), tok.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pl.anc[0], anc.data(), anc.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pos_d, pos.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(enc_d, enc_lens_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+    step_source_kv(e, st, enc_dev, pl);
+    float* full = logp_host_or_null ? e->st_full.as<float>() : nullptr;
+    for (int p = 0; p < pl.Lrun; ++p) CHK(step_forward(e, st, pl, p, pl.tok[0], pl.anc[0], enc_d, top_n, full, pos_d));
+    LAUNCHCHK();
+    float* top_v = e->st_top.as<float>();
+    HIPCHK(hipMemcpyAsync(top_logp_host, top_v, (size_t)S * top_n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(top_ids_host, top_v + (size_t)S * top_n, (size_t)S * top_n * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (full) HIPCHK(hipMemcpyAsync(logp_host_or_null, full, (size_t)S * V * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return 0;
 }

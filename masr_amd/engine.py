@@ -821,6 +821,41 @@ class HipEngine:
                                               1 if with_right else 0, as_p(att), as_p(r_att), _stream()))
         return att, r_att
 
+    def attention_decode(self, enc, enc_lens, beam_size=10, max_len=0, lcap=None):
+        """masr_attention_decode on the current stream and the active lane: left-to-right beam search with the left decoder over
+        ``enc`` [B, T', d] / ``enc_lens`` [B] int32 (device tensors) -> (tokens [B, N, Lcap] int32, lens [B, N] int32, scores
+        [B, N] float32) device tensors, best hypothesis first, and the number of steps launched.  ``lcap`` (default: the most
+        steps any utterance of the batch may run) bounds the hypotheses' length.  The host waits only at the end polls."""
+        B, Tp, _ = enc.shape
+        N, max_len = int(beam_size), int(max_len)
+        if lcap is None:
+            lcap = max(1, min(Tp, self.max_pos - 1, max_len if max_len > 0 else Tp))
+        tokens = torch.empty(B, max(N, 1), max(int(lcap), 1), dtype=torch.int32, device=self.device)
+        lens = torch.empty(B, max(N, 1), dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, max(N, 1), dtype=torch.float32, device=self.device)
+        steps = C.c_int32(0)
+        check(self.lib.masr_attention_decode(self.h, _ptr(enc), _ptr(enc_lens), B, Tp, N, max_len, _ptr(tokens), int(lcap), _ptr(lens),
+                                             _ptr(scores), C.byref(steps), _stream()))
+        return tokens, lens, scores, steps.value
+
+    def op_decoder_step(self, enc, enc_lens, prefixes, prefix_lens, top_n=1, want_logp=True):
+        """masr_op_decoder_step: the decode step driven alone from HOST tables, teacher forced.  ``enc`` [B, T', d] on the device,
+        ``enc_lens`` [B], ``prefixes`` [B, N, L] tokens behind sos, ``prefix_lens`` [B, N] in 0 .. L -> (top ids [B, N, top_n]
+        int32, top log-probabilities [B, N, top_n], log-probabilities [B, N, V] or None) numpy, of the position behind each
+        prefix; returns when the work has finished."""
+        prefixes = np.ascontiguousarray(prefixes, np.int32)
+        prefix_lens = np.ascontiguousarray(prefix_lens, np.int32)
+        enc_lens = np.ascontiguousarray(enc_lens, np.int32)
+        B, N, L = prefixes.shape
+        top_n = int(top_n)
+        ids = np.zeros((B, N, max(top_n, 1)), np.int32)
+        top = np.zeros((B, N, max(top_n, 1)), np.float32)
+        logp = np.zeros((B, N, self.vocab_size), np.float32) if want_logp else None
+        as_p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self.lib.masr_op_decoder_step(self.h, _ptr(enc), as_p(enc_lens), B, enc.shape[1], as_p(prefixes), as_p(prefix_lens), N, L,
+                                            top_n, as_p(ids), as_p(top), as_p(logp) if want_logp else None, _stream()))
+        return ids, top, logp
+
     def decoder_info(self):
         """masr_decoder_info -> {'enabled', 'num_blocks', 'r_num_blocks', 'weight_bytes', 'workspace_bytes' (active lane)}"""
         en, nl, nr, wb, ws = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()

@@ -88,6 +88,15 @@ class MASRPredictor:
             rconf = validate_rescoring_conf(self.configs.get('attention_rescoring_decoder_conf', None),
                                             self.configs.get('model_conf', None), dconf.get('r_num_blocks', 0))
             self.rescoring_decoder = AttentionRescoringDecoder(vocab_list=self._text_featurizer.vocab_list, **rconf)
+        self.attention_decoder = None
+        if self.configs.decoder == 'attention':
+            # autoregressive beam search with the checkpoint's attention decoder, on the GPU (decoders/attention_decoder.py); the
+            # configuration is checked before anything is loaded
+            from masr_amd.decoders.attention_decoder import AttentionDecoder, DS2_REFUSAL, validate_attention_conf
+            if self.configs.use_model == 'deepspeech2':
+                raise Exception(DS2_REFUSAL)
+            aconf = validate_attention_conf(self.configs.get('attention_decoder_conf', None), len(self._text_featurizer.vocab_list))
+            self.attention_decoder = AttentionDecoder(vocab_list=self._text_featurizer.vocab_list, **aconf)
         if state_dict is None and not os.path.exists(model_path):
             raise Exception("模型文件不存在，请检查{}是否存在！".format(model_path))
         self.predictor = InferencePredictor(configs=self.configs, use_model=self.configs.use_model,
@@ -105,6 +114,9 @@ class MASRPredictor:
         if self.configs.decoder == 'attention_rescoring':
             raise Exception("decoder='attention_rescoring' needs the encoder output of the utterance, not only its probabilities: "
                             "use predict / predict_batch")
+        if self.configs.decoder == 'attention':
+            from masr_amd.decoders.attention_decoder import DECODE_REFUSAL
+            raise Exception(DECODE_REFUSAL)
         if self.configs.decoder == 'ctc_beam_search':
             score, text = self.beam_search_decoder.decode_beam_search_offline(probs_split=output_data)
         else:
@@ -401,7 +413,8 @@ class MASRPredictor:
         live = ok                # (only its length is used below)
         xs, ns, gain = self._prepare_finish(began['prep'], pc.target_dB)
         rescoring = self.configs.decoder == 'attention_rescoring'
-        greedy = self.configs.decoder != 'ctc_beam_search' and not rescoring
+        attention = self.configs.decoder == 'attention'
+        greedy = self.configs.decoder != 'ctc_beam_search' and not rescoring and not attention
         if greedy and method == 'fbank':
             # the whole pass is ONE C-ABI call and ONE copy back: rows [B, T' + 2] = tokens | count | score bits
             rows = eng.transcribe_rows(xs, ns, pc.use_dB_normalization, pc.target_dB, gain_in=gain,
@@ -428,6 +441,17 @@ class MASRPredictor:
         with debug_keys(eng, skip_padding=0) if decode_all_frames else contextlib.nullcontext():
             enc = eng.encode_full(feats, frames, -1)
         nenc = None if decode_all_frames else eng.enc_frames(frames).to(torch.int32)
+        if attention:
+            # the search is queued behind this pass's encoder on the SAME stream and lane (the caller selected them): no CTC head,
+            # no prefix search; the host waits at the search's end polls and fetches the hypotheses behind an event
+            enc_lens = nenc if nenc is not None else torch.full((len(live),), enc.shape[1], dtype=torch.int32, device=eng.device)
+            fetch_pass = self.attention_decoder.decode_pass(eng, enc, enc_lens.contiguous(), want_tokens=as_tokens)
+
+            def fetch_searched():
+                for i, r in zip(ok, fetch_pass()):
+                    out[i] = r if as_tokens else {'text': r[1], 'score': r[0]}
+                return out
+            return fetch_searched if defer else fetch_searched()
         if rescoring:
             # first pass: CTC head, vocabulary pruning on the GPU, the n-best prefixes of the LM-free prefix search; second pass:
             # both attention decoders over this pass's encoder output, queued behind it on the SAME stream and lane (the caller
@@ -784,6 +808,9 @@ class MASRPredictor:
         self._no_itn(is_itn)
         if self.configs.decoder == 'attention_rescoring':
             from masr_amd.decoders.attention_rescoring import STREAM_REFUSAL
+            raise Exception(STREAM_REFUSAL)
+        if self.configs.decoder == 'attention':
+            from masr_amd.decoders.attention_decoder import STREAM_REFUSAL
             raise Exception(STREAM_REFUSAL)
         if self._pool is None:
             from masr_amd.serving import StreamPool

@@ -154,6 +154,9 @@ class StreamPool:
         if cfg.decoder == 'attention_rescoring':
             from masr_amd.decoders.attention_rescoring import STREAM_REFUSAL
             raise Exception(STREAM_REFUSAL)
+        if cfg.decoder == 'attention':
+            from masr_amd.decoders.attention_decoder import STREAM_REFUSAL
+            raise Exception(STREAM_REFUSAL)
         if cfg.decoder not in ('ctc_greedy', 'ctc_beam_search'):
             raise Exception(f'unknown decoder {cfg.decoder}')
         self.predictor = predictor
