@@ -71,9 +71,9 @@ def line(name, f):
             f'(ref {f["rms_ref"]:.3e}, x{f["ratio_rms"]:.2f})  floor {f["ulp_floor"]:.2e}  C {f["c"]:g}')
 
 
-def check(name, y64, y32, y, mask=None, c=C):
-    """print the figures of one case, then assert the rule"""
-    f = evaluate(y64, y32, y, mask, c)
+def check(name, y64, y32, y, mask=None, c=C, c_max=None):
+    """print the figures of one case, then assert the rule (``c_max``: the case's own allowance on the max criterion)"""
+    f = evaluate(y64, y32, y, mask, c, c_max)
     print(line(name, f), flush=True)
     assert f['ok'], 'over budget -- ' + line(name, f)
     return f

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from masr_amd._lib import debug_keys
+from tests import budget
 
 pytestmark = pytest.mark.gpu
 
@@ -131,6 +132,7 @@ def test_fbank_testwav_against_reference_fixture(eng512, oracle_mods):
     # FFT / mel numerics in isolation: float64 oracle fbank of the SAME int16 samples
     f64 = ofb.kaldi_fbank(mine_i16, 80, np.float64)
     assert np.abs(out - f64).max() < 1e-3, np.abs(out - f64).max()
+    budget.check('fbank test.wav, own samples', f64, ofb.kaldi_fbank(mine_i16, 80, np.float32), out)
     # against the reference fixture: frames whose 400 samples are identical must agree to 1e-3,
     # frames containing a +-1 LSB sample (near-silent frames amplify it) to 0.1
     bad = np.flatnonzero(diff)
@@ -164,6 +166,7 @@ def test_fbank_ragged_batch(eng512, oracle_mods):
     feats2, _ = e.fbank_batch(dev(pcm[:1]), dev(np.array(lens[:1], np.int32)), False, -20.0)
     ref = ofb.kaldi_fbank(pcm[0, :lens[0]], 80, np.float64)
     assert np.abs(feats2[0].cpu().numpy()[:ref.shape[0]] - ref).max() < 1e-3
+    budget.check('fbank synthetic_pcm 16000, no dB', ref, ofb.kaldi_fbank(pcm[0, :lens[0]], 80, np.float32), feats2[0].cpu().numpy()[:ref.shape[0]])
 
 
 # ---------------------------------------------------------------------------------------------------
