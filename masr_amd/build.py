@@ -12,7 +12,8 @@ LIB_DIR = os.path.join(ROOT, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libmasr_hip.so')
 SOURCES = ['gemm_f32.hip', 'ffn_reduce.hip', 'ffn_pc.hip', 'sqz_layer.hip', 'rowgemm.hip', 'rowgemm_small.hip', 'elementwise.hip', 'wide.hip',
            'attention.hip', 'lstm.hip', 'gru.hip', 'beam_gpu.hip', 'lm_scorer.cpp', 'fbank.hip', 'silero.hip', 'engine.hip', 'pool.hip',
-           'beam_search.cpp', 'stage.cpp', 'resample.cpp', 'resample.hip', 'knobs.cpp', 'decoder.hip', 'decoder_step.hip']
+           'beam_search.cpp', 'stage.cpp', 'resample.cpp', 'resample.hip', 'knobs.cpp', 'decoder.hip', 'decoder_step.hip',
+           'engine_attdecoder.hip']
 # MASR_BUILD_EXPERIMENTS=1: the measured-and-rejected kernels of earlier rounds (A/B material behind masr_debug_set keys 20 / 24 /
 # 30 / 34 / 35) are compiled in as well; the default library holds the product kernels only
 EXPERIMENTS = os.environ.get('MASR_BUILD_EXPERIMENTS') == '1'
@@ -20,7 +21,7 @@ EXPERIMENT_SOURCES = ['gemm_bf16x3.hip', 'ffn_x3.hip', 'ffn_coop.hip', 'ffn_dual
 if EXPERIMENTS:
     SOURCES = SOURCES + EXPERIMENT_SOURCES
 HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'knobs.h'), os.path.join(CSRC, 'ffn_plan.h'),
-           os.path.join(CSRC, 'lm_scorer.h'),
+           os.path.join(CSRC, 'lm_scorer.h'), os.path.join(CSRC, 'engine_state.h'),
            os.path.join(os.path.dirname(ROOT), 'include', 'masr_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value'] + (['-DMASR_EXPERIMENTS=1'] if EXPERIMENTS else [])
 # resample.hip reproduces the host loop of resample.cpp bit for bit: a multiply and the add behind it must round separately (no
@@ -36,8 +37,14 @@ def _hipcc():
     return 'hipcc'
 
 
-def _sources():
-    return [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
+def _sources(sources=None):
+    """the files to compile: a listed source that is not in csrc/ is an error (its object would be missing from the link and the
+    library would die in the first call that reaches it); an experiment source may be absent"""
+    sources = SOURCES if sources is None else sources
+    missing = [s for s in sources if s not in EXPERIMENT_SOURCES and not os.path.exists(os.path.join(CSRC, s))]
+    if missing:
+        raise FileNotFoundError('masr_amd.build: listed in SOURCES but not in %s: %s' % (CSRC, ', '.join(missing)))
+    return [s for s in sources if os.path.exists(os.path.join(CSRC, s))]
 
 
 def _obj(src):
@@ -90,7 +97,7 @@ def build(force=False, verbose=False):
 
     with ThreadPoolExecutor(max_workers=min(8, max(1, os.cpu_count() or 1))) as ex:
         list(ex.map(compile_one, todo))
-    cmd = [_hipcc(), '--offload-arch=gfx950', '-shared', '-fPIC', '-pthread', '-o', LIB_PATH] + [_obj(s) for s in _sources()]
+    cmd = [_hipcc(), '--offload-arch=gfx950', '-shared', '-fPIC', '-pthread', '-Wl,-z,defs', '-o', LIB_PATH] + [_obj(s) for s in _sources()]
     if verbose:
         print(' '.join(cmd), flush=True)
     subprocess.run(cmd, check=True)

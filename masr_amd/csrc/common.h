@@ -24,7 +24,7 @@ namespace masr {
 
 // Opt-in to more than 64 KB of dynamic LDS for a kernel, checked and per device: `st` is the call site's table of the sizes
 // already granted on each device ordinal (one process may drive several GPUs).  A failing hipFuncSetAttribute is not silent: it is
-// recorded with note_launch_error() and the C ABI entry point that issued the launch returns it (engine.hip, LAUNCHCHK).
+// recorded with note_launch_error() and the C ABI entry point that issued the launch returns it (engine_state.h, LAUNCHCHK).
 struct LdsAttr {
     size_t granted[32] = {};
 };

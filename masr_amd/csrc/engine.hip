@@ -11,43 +11,29 @@
 #include <string>
 #include <vector>
 
-#include "../../include/masr_hip.h"
-#include "common.h"
-#include "ffn_plan.h"
+#include "engine_state.h"
 
 using namespace masr;
-namespace masr {
-int lm_device_view(masr_lm* lm, LmView* out);      // lm_scorer.cpp: the LM table in the memory of the current device
-bool lm_word_based(const masr_lm* lm);
-}
-extern "C" const char* masr_lm_last_error(void);
 
 static thread_local std::string g_err;
-static int fail(const std::string& m) {
+namespace masr {
+int engine_fail(const std::string& m) {      // fail() of engine_state.h; pool.hip reports through the same masr_last_error()
     g_err = m;
     return 1;
 }
-namespace masr {
-int engine_fail(const std::string& m) { return fail(m); }      // pool.hip reports through the same masr_last_error()
 }
-#define HIPCHK(expr)                                                                                    \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                           \
-            return fail(std::string(#expr) + ": " + hipGetErrorString(_e) + " (" + __FILE__ + ":" +     \
-                        std::to_string(__LINE__) + ")");                                                \
-    } while (0)
-#define CHK(expr)              \
-    do {                       \
-        int _r = (expr);       \
-        if (_r) return _r;     \
-    } while (0)
 
 // errors noted by the kernel launchers (a refused dynamic-LDS opt-in, ...) since the last check on this thread
 static thread_local std::string g_launch_err;
 namespace masr {
 void note_launch_error(const char* what, hipError_t e) {
     if (g_launch_err.empty()) g_launch_err = std::string(what) + ": " + hipGetErrorString(e);
+}
+bool launch_error_pending() { return !g_launch_err.empty(); }
+std::string take_launch_error() {
+    std::string m;
+    m.swap(g_launch_err);
+    return m;
 }
 void ensure_dynamic_lds(const void* fn, size_t bytes, LdsAttr& st) {
     int dev = 0;
@@ -61,203 +47,6 @@ void ensure_dynamic_lds(const void* fn, size_t bytes, LdsAttr& st) {
     st.granted[dev] = bytes;
 }
 }  // namespace masr
-// after a group of launches: a launcher-side error first, then the runtime's sticky launch error
-#define LAUNCHCHK()                                     \
-    do {                                                \
-        if (!g_launch_err.empty()) {                    \
-            std::string _m = g_launch_err;              \
-            g_launch_err.clear();                       \
-            (void)hipGetLastError();                    \
-            return fail(_m);                            \
-        }                                               \
-        HIPCHK(hipGetLastError());                      \
-    } while (0)
-// every entry point that touches the device first makes the engine's GPU current on the calling thread (an engine on
-// device != 0 may be driven from a worker thread whose current device is still 0)
-#define ENTER(e) HIPCHK(hipSetDevice((e)->cfg.device_id))
-
-namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t n) {
-        if (n <= bytes) return 0;
-        if (p) HIPCHK(hipFree(p));
-        p = nullptr;
-        bytes = 0;
-        size_t want = n + n / 8 + 256;
-        HIPCHK(hipMalloc(&p, want));
-        // zero once: kernels that skip the padded row blocks of a batch (masr_debug_set key 38) leave those rows as they are, and
-        // what is there must at least be finite -- a later 0 * stale product must not see the NaN patterns of fresh memory
-        HIPCHK(hipMemset(p, 0, want));
-        // (the fill runs on the NULL stream, which a non-blocking stream does not wait for: without this a lane's first launches
-        // could write the buffer BEFORE it is cleared -- the first two-lane call lost its second pass that way)
-        HIPCHK(hipStreamSynchronize(nullptr));
-        bytes = want;
-        return 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
-
-// one packed weight copy (masr_engine::packed): `a` alone, or the W1 | W2 pair of an FFN
-struct PackedW {
-    DevBuf a, b;
-    void release() {
-        a.release();
-        b.release();
-    }
-};
-
-// Pinned host staging for the per-call descriptor tables (AttSeq rows, cache pointers) of the streaming chunk step: the
-// copies to the device are truly asynchronous, so the chunk step does not stall the host on the work queued before it.
-// One call owns the area at a time: `begin` waits for the previous call's copies (normally long done).
-struct PinnedStage {
-    char* p = nullptr;
-    size_t bytes = 0, used = 0;
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-    int begin(size_t need) {
-        if (pending) {
-            HIPCHK(hipEventSynchronize(ev));
-            pending = false;
-        }
-        if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        if (need > bytes) {
-            if (p) HIPCHK(hipHostFree(p));
-            p = nullptr;
-            bytes = 0;
-            const size_t want = need + need / 4 + 4096;
-            HIPCHK(hipHostMalloc((void**)&p, want, hipHostMallocDefault));
-            bytes = want;
-        }
-        used = 0;
-        return 0;
-    }
-    // copy `n` bytes of `src` through the staging area to `dst` (device) on stream `s`
-    int push(void* dst, const void* src, size_t n, hipStream_t s) {
-        if (n == 0) return 0;
-        const size_t at = (used + 15) & ~(size_t)15;
-        if (at + n > bytes) return fail("descriptor staging area overflow");
-        memcpy(p + at, src, n);
-        used = at + n;
-        HIPCHK(hipMemcpyAsync(dst, p + at, n, hipMemcpyHostToDevice, s));
-        return 0;
-    }
-    int end(hipStream_t s) {
-        HIPCHK(hipEventRecord(ev, s));
-        pending = true;
-        return 0;
-    }
-    void release() {
-        if (pending) (void)hipEventSynchronize(ev);
-        if (p) (void)hipHostFree(p);
-        if (ev) (void)hipEventDestroy(ev);
-        p = nullptr;
-        ev = nullptr;
-        bytes = 0;
-        pending = false;
-    }
-};
-
-struct LayerW {
-    float *ln_ffm_w, *ln_ffm_b, *ffm_w1, *ffm_b1, *ffm_w2, *ffm_b2;
-    float *ln_mha_w, *ln_mha_b, *wqkv, *bqkv, *wo, *bo, *pos_u, *pos_v, *wpos, *ptab;
-    float *ln_conv_w, *ln_conv_b, *pw1_w, *pw1_b, *dw_w, *dw_b, *cln_w, *cln_b, *pw2_w, *pw2_b, *gconst;
-    float *chain_w, *chain_b;     // [Wo; W_pw1] [768,256] and [bo; b_pw1] for the fused out-proj -> LN -> pw1 -> GLU kernel
-    float *ln_ff_w, *ln_ff_b, *ff_w1, *ff_b1, *ff_w2, *ff_b2;
-    float *ln_fin_w, *ln_fin_b;
-};
-
-struct SqLayerW {   // Squeezeformer block (post-LN, adaptive scale/bias, BatchNorm conv module)
-    float *att_s, *att_b, *wqkv, *bqkv, *wo, *bo, *pos_u, *pos_v, *wpos, *ptab, *ln1_w, *ln1_b;
-    float *f1_s, *f1_b, *f1_w1, *f1_b1, *f1_w2, *f1_b2, *ln2_w, *ln2_b;
-    float *cv_s, *cv_b, *pw1_w, *pw1_b, *dw_w, *dw_b, *bn_scale, *bn_shift, *pw2_w, *pw2_b, *ln3_w, *ln3_b, *gconst;
-    float *f2_s, *f2_b, *f2_w1, *f2_b1, *f2_w2, *f2_b2, *ln4_w, *ln4_b;
-};
-
-struct Ds2LayerW {  // DeepSpeech2 RNN layer: input projection of both directions stacked, recurrent weights, LayerNorm
-    float *wih, *bih, *whh, *ln_w, *ln_b;
-    float* bhn = nullptr;   // use_gru: b_hn [ndir][H] (inside the reset-gate product, not folded into bih)
-    int kin;
-};
-
-struct HostTensor {
-    std::vector<float> v;
-    std::vector<int64_t> shape;
-};
-
-struct Stream {
-    bool open = false;
-    int offset = 0;
-    int offset_r = 0;   // frames emitted at the reduced rate (Squeezeformer blocks between time reduction and recovery)
-    int cap = 0;
-    int history = -1;   // required_cache_size of forward_chunk: < 0 keep every key, >= 0 attend over at most that many cached keys
-    int cache_t1 = 0;   // cached keys the next chunk attends over, in input-rate frames (= att_cache.size(2) of the reference)
-    int first_half = 0; // half-rate layers (Squeezeformer between reduction and recovery, Efficient-Conformer behind the stride
-                        // layer): index of their first kept cache entry (advances by next_cache_start // 2 per step)
-    DevBuf att;  // [L][cap][2*d]  (k | v per row)
-    DevBuf cnn;  // [L][kernel-1][d]   (DeepSpeech2: LSTM state [L][2 (h, c)][rnn_size]; GRU: h in both)
-    DevBuf cnn2; // Conformer / Squeezeformer: second half of the double-buffered cnn cache (a chunk step reads `cnn`, writes
-                 // `cnn2`, then the two are swapped -- lets one kernel read the history and write the new cache without ordering)
-};
-
-struct GBeam {        // device-resident streaming CTC prefix beam search (masr_gbeam_*)
-    bool open = false, started = false;
-    int beam = 0, blank = 0, cap = 0;
-    DevBuf pool, state;
-    masr_lm* lm = nullptr;       // external scorer bound with masr_gbeam_set_lm (not owned)
-    float alpha = 0.f, beta = 0.f;
-};
-
-enum ProfKind { PROF_NONE = 0, PROF_GEMM = 1, PROF_FFN1 = 2, PROF_CONV2 = 3, PROF_ATT = 4, PROF_FBANK = 5,
-                PROF_FFN_TAIL = 6, PROF_FFN_HEAD = 7, PROF_RNN = 8,
-                PROF_WIDE_LN = 9, PROF_WIDE_GLU = 10, PROF_WIDE_DWCONV = 11, PROF_WIDE_CACHE = 12 };   // 9-12: the row kernels of wide.hip (12 = conv_hist + kv_append)     // 2 = the plain fused FFN kernel; 6 = its variant with the QKV tail stage, 7 = with the conv-module head stage (own kernel names)
-
-}  // namespace
-
-// Everything a forward call WRITES on the device (and the pinned descriptor staging of the chunk step): one set per LANE.
-// masr_select_lane parks the active set and brings another one in, so two offline passes can be in flight on two streams of one
-// engine (one set of weights) -- launches that share a lane must be ordered by their stream, as before.
-struct EngineWs {
-    DevBuf gx, rnn_out, hstate, cstate, ds2_lens;                               // DeepSpeech2 workspaces
-    PinnedStage stage;
-    DevBuf qplanes, attp, cnnptrs, ffpart;                                      // planar q|k|v and attention output, [B][Tpad][256]
-    DevBuf fb_scratch;
-    DevBuf x1, x2, x, ln, hid, qkv, att, lnpad, glu, dwo, logits, feats, enc, idx, maxp, attseq, gain, nframes, lens, xsave,
-        xred, xh;      // xh: rows updated by the head stage of a d_ff-split FFN launch (few rows)
-    DevBuf x3, sublens;   // conv2d8: the third subsampling conv's output; conv2d6 / conv2d8: the lengths in conv2d units (sub_lens)
-    DevBuf posoff;        // abs_pos chunk steps: the streams' offsets (first positional row of each stream's new frames)
-    // attention decoder (masr_rescore; allocated on the lane's first rescoring call, never by an engine without the decoder):
-    // residual rows, LayerNorm rows, q | k | v (self) / q (source), attention output, source k | v of the encoder frames, FFN hidden
-    // rows, logits, per-row log-probabilities
-    DevBuf dec_x, dec_ln, dec_qkv, dec_att, dec_kv, dec_hid, dec_logits, dec_rowlp;
-    // autoregressive search (masr_attention_decode / masr_op_decoder_step; allocated on the lane's first such call): the step's rows
-    // (residual, LayerNorm, q, attention output, FFN hidden, logits), the self-attention k | v cache [blocks][Lrun][S][2 d], the
-    // source k | v [blocks][B * Tp][2 d], top-N values | ids, the double-buffered token / ancestor / score tables and flags, and
-    // the test op's [S, V] log-probabilities
-    DevBuf st_x, st_ln, st_q, st_att, st_hid, st_logits, st_cache, st_src, st_top, st_tab, st_full;
-    size_t decoder_bytes() const {
-        return dec_x.bytes + dec_ln.bytes + dec_qkv.bytes + dec_att.bytes + dec_kv.bytes + dec_hid.bytes + dec_logits.bytes +
-               dec_rowlp.bytes + st_x.bytes + st_ln.bytes + st_q.bytes + st_att.bytes + st_hid.bytes + st_logits.bytes + st_cache.bytes +
-               st_src.bytes + st_top.bytes + st_tab.bytes + st_full.bytes;
-    }
-    void release_all() {
-        for (DevBuf* b : {&gx, &rnn_out, &hstate, &cstate, &ds2_lens, &qplanes, &attp, &cnnptrs, &ffpart, &fb_scratch, &x1, &x2, &x,
-                          &ln, &hid, &qkv, &att, &lnpad, &glu, &dwo, &logits, &feats, &enc, &idx, &maxp, &attseq, &gain, &nframes,
-                          &lens, &xsave, &xred, &xh, &x3, &sublens, &posoff, &dec_x, &dec_ln, &dec_qkv, &dec_att, &dec_kv, &dec_hid,
-                          &dec_logits, &dec_rowlp, &st_x, &st_ln, &st_q, &st_att, &st_hid, &st_logits, &st_cache, &st_src, &st_top,
-                          &st_tab, &st_full})
-            b->release();
-        stage.release();
-    }
-};
 
 // hipMemset runs on the NULL stream, which a non-blocking stream (every torch side stream, the library's own) does not wait for:
 // the host waits for the fill, so that whatever is launched next on any stream sees the cleared memory
@@ -267,98 +56,7 @@ static int clear_sync(void* p, int value, size_t n) {
     return 0;
 }
 
-// one block of the attention decoder (DecoderLayer, transformer/decoder.py:273-394): pre-norm self-attention (q | k | v fused),
-// source attention (q; k | v of the encoder frames fused), ReLU feed-forward
-struct DecLayerW {
-    float *n1w, *n1b, *wqkv, *bqkv, *wo, *bo;
-    float *n2w, *n2b, *wq2, *bq2, *wkv2, *bkv2, *wo2, *bo2;
-    float *n3w, *n3b, *w1, *b1, *w2, *b2;
-};
-struct DecoderW {       // one TransformerDecoder: embedding, blocks, after_norm, output_layer
-    float *emb = nullptr, *after_w = nullptr, *after_b = nullptr, *out_w = nullptr, *out_b = nullptr;
-    std::vector<DecLayerW> layers;
-};
-struct DecoderState {   // masr_decoder_enable: the YAML decoder_conf; weights uploaded by masr_finalize
-    bool enabled = false, ready = false;
-    int heads = 0, dff = 0, nl = 0, nr = 0;
-    DecoderW left, right;
-    size_t weight_bytes = 0;
-    std::vector<void*> owned;   // the decoder's device weights (a reload replaces the whole set; masr_destroy frees it)
-};
-
-struct masr_engine : EngineWs {
-    masr_config cfg;
-    DecoderState dec;
-    EngineWs parked[MASR_LANES];     // the workspace sets of the lanes that are not active (parked[lane] is unused)
-    int lane = 0;
-    hipEvent_t pack_ev = nullptr;    // recorded behind the last call that built a packed weight copy on first use ...
-    void* pack_stream = nullptr;     // ... on this stream: calls on OTHER streams wait for it before they read the copies
-    bool pack_pending = false;
-    bool finalized = false;
-    std::map<std::string, HostTensor> host;
-    std::vector<void*> owned;   // device weight allocations
-    // weights
-    float *cmvn_mean = nullptr, *cmvn_istd = nullptr, *conv1_w = nullptr, *conv1_b = nullptr, *conv2_w = nullptr,
-          *conv2_b = nullptr, *conv3_w = nullptr, *conv3_b = nullptr, *embed_w = nullptr, *embed_b = nullptr, *after_w = nullptr, *after_b = nullptr,
-          *ctc_w = nullptr, *ctc_b = nullptr, *pe = nullptr;
-    std::vector<LayerW> layers;
-    std::vector<SqLayerW> sq_layers;
-    std::vector<Ds2LayerW> ds2_layers;
-    std::vector<GBeam> gbeams;
-    DevBuf beam_pool, beam_state;
-    // whole-utterance prefix searches launched on OTHER streams than the first one get workspaces of their own: two searches may
-    // run next to each other (predict_batch: the passes' searches on two side streams), launches on one stream are ordered anyway
-    std::map<void*, std::pair<DevBuf, DevBuf>> beam_ws;
-    // masr_mean_square runs on whatever stream prepares the NEXT pass (the facade's side stream, the contract step's copy stream)
-    // while the feature launch of the current pass reads e->gain on the compute stream: its chunk sums and its unused gain slots
-    // live in a scratch of their own, one per calling stream (launches on one stream are ordered anyway)
-    std::map<void*, DevBuf> ms_ws;
-    int skip_padding = 7;            // masr_debug_set key 38: the offline Squeezeformer launches skip the all-padding row blocks of a batch
-    void* beam_first_stream = nullptr;
-    bool beam_first_set = false;
-    // every fragment-ordered weight copy, built on first use by packed_of(): (common.h PackLayout, source device pointer) -> copy
-    std::map<std::pair<int, const float*>, PackedW> packed;
-    long long* beam_prof = nullptr;                                             // debug: phase cycle counters (masr_debug_set key 2)                                               // GPU beam search scratch                               // DeepSpeech2 workspaces
-    float *preln_w = nullptr, *preln_b = nullptr, *tr_dw_w = nullptr, *tr_dw_b = nullptr, *tr_pw_w = nullptr,
-          *tr_pw_b = nullptr, *rec_w = nullptr, *rec_b = nullptr;
-    int reduce_idx = -1, recover_idx = -1;
-    int stride_idx = -1, n_group_layers = 0, group_size = 3;   // Efficient-Conformer (model_kind 2)
-    int input_layer = IL_CONV2D;     // Conformer / Efficient-Conformer subsampling front-end (cfg.reserved[3], common.h InputLayer)
-    bool conv_bn = false;            // cnn_module_norm: batch_norm (Conformer: cfg.reserved[0] = 1, Efficient Conformer: cfg.reserved[4] = 1): LayerW::cln_w / cln_b hold the folded scale / shift
-    bool ds2_gru = false;            // DeepSpeech2 with use_gru: True (cfg.reserved[0] = 1): nn.GRU recurrent layers (gru.hip)
-    int pos_enc = POS_ENC_REL;       // Conformer pos_enc_layer_type (cfg.reserved[2], common.h PosEnc): rel_pos, abs_pos or no_pos
-    int act = ENC_ACT_SWISH;         // Conformer activation_type (cfg.reserved[4], common.h EncAct); anything but swish runs the width-generic layer
-    // fbank tables
-    float *window = nullptr, *melwt = nullptr, *tw512 = nullptr, *twr4 = nullptr;
-    FbankTables fbank_tables() const { return FbankTables{window, melwt, tw512, twr4, mel_lo}; }
-    int* mel_lo = nullptr;
-    // mfcc / linear tables (built on first use)
-    float *dct = nullptr, *lifter = nullptr;
-    int dct_ceps = 0;
-    double *lin_win = nullptr, *lin_tw = nullptr;
-    double lin_scale = 0.0;
-    // streams
-    std::vector<Stream> streams;
-    // profiling
-    int prof_kind = 0;
-    int prof_stride = 1, prof_seen = 0;                     // every prof_stride-th matching launch is timed (masr_debug_set key 16)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
-    size_t prof_used = 0;
-    double prof_flops = 0.0;
-};
-
-namespace {
-
-template <class T>
-int upload(masr_engine* e, const std::vector<T>& v, T** out) {
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, std::max<size_t>(v.size(), 1) * sizeof(T)));
-    HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    e->owned.push_back(p);
-    *out = reinterpret_cast<T*>(p);
-    return 0;
-}
-
+namespace masr {
 int get(masr_engine* e, const std::string& name, std::vector<int64_t> shape, const HostTensor** out) {
     auto it = e->host.find(name);
     if (it == e->host.end()) return fail("missing tensor: " + name);
@@ -371,67 +69,9 @@ int get(masr_engine* e, const std::string& name, std::vector<int64_t> shape, con
     return 0;
 }
 
-int up(masr_engine* e, const std::string& name, std::vector<int64_t> shape, float** out) {
-    const HostTensor* t;
-    CHK(get(e, name, shape, &t));
-    return upload(e, t->v, out);
-}
-
-// ---- profiling helpers ------------------------------------------------------------------------------
-struct ProfScope {
-    masr_engine* e;
-    hipStream_t s;
-    bool on;
-    ProfScope(masr_engine* e_, hipStream_t s_, int kind, double flops) : e(e_), s(s_) {
-        on = e->prof_kind != 0 && (e->prof_kind == kind || (e->prof_kind == PROF_GEMM && (kind == PROF_FFN1 || kind == PROF_CONV2 || kind == PROF_FFN_TAIL || kind == PROF_FFN_HEAD)));
-        if (on && e->prof_stride > 1) on = (e->prof_seen++ % e->prof_stride) == 0;     // a sample of the launches: two event
-        if (!on) return;                                                                // records cost ~6 us of stream time
-        if (e->prof_used == e->prof_events.size()) {
-            hipEvent_t a, b;
-            hipEventCreate(&a);
-            hipEventCreate(&b);
-            e->prof_events.push_back({a, b});
-        }
-        hipEventRecord(e->prof_events[e->prof_used].first, s);
-        e->prof_flops += flops;
-    }
-    ~ProfScope() {
-        if (!on) return;
-        hipEventRecord(e->prof_events[e->prof_used].second, s);
-        e->prof_used++;
-    }
-};
-
-// Packed weight copies are built on first use by whatever call needs them first, on that call's stream.  With two lanes a call
-// on ANOTHER stream may find the copy in the cache while the packing launch is still queued: the call that packed (the cache has
-// grown under it) records an event behind itself, and calls on other streams wait for that event until it has completed.
-struct CallGuard {
-    masr_engine* e;
-    hipStream_t s;
-    size_t n0;
-    CallGuard(masr_engine* e_, hipStream_t s_) : e(e_), s(s_), n0(e_->packed.size()) {
-        if (!e->pack_pending) return;
-        if (hipEventQuery(e->pack_ev) == hipSuccess) {
-            e->pack_pending = false;
-        } else {
-            (void)hipGetLastError();          // (hipErrorNotReady is not an error of ours)
-            if ((void*)s != e->pack_stream) (void)hipStreamWaitEvent(s, e->pack_ev, 0);
-        }
-    }
-    ~CallGuard() {
-        if (e->packed.size() == n0) return;
-        if (!e->pack_ev && hipEventCreateWithFlags(&e->pack_ev, hipEventDisableTiming) != hipSuccess) return;
-        // (a pending event of another stream: this call waited for it at its start, so the new record covers it)
-        if (hipEventRecord(e->pack_ev, s) == hipSuccess) {
-            e->pack_stream = (void*)s;
-            e->pack_pending = true;
-        }
-    }
-};
-
 void gemm(masr_engine* e, hipStream_t s, const float* A, int lda, const float* W, const float* bias, float* C, int ldc,
-          int M, int N, int K, int act, float alpha, const float* R, int ldr, int kind = PROF_GEMM,
-          const int* lens = nullptr, int mask_tp = 0) {
+          int M, int N, int K, int act, float alpha, const float* R, int ldr, int kind,
+          const int* lens, int mask_tp) {
     GemmArgs a{};
     a.A = A; a.W = W; a.bias = bias; a.C = C; a.R = R; a.lens = lens;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr;
@@ -439,6 +79,15 @@ void gemm(masr_engine* e, hipStream_t s, const float* A, int lda, const float* W
     ProfScope ps(e, s, kind, 2.0 * M * (double)N * K);
     if (knobs().bf16x3 && launch_gemm_bf16x3(a, A_PLAIN, s)) return;
     launch_gemm(a, A_PLAIN, EPI_STD, s);
+}
+}  // namespace masr
+
+namespace {
+
+int up(masr_engine* e, const std::string& name, std::vector<int64_t> shape, float** out) {
+    const HostTensor* t;
+    CHK(get(e, name, shape, &t));
+    return upload(e, t->v, out);
 }
 
 // The packed copy of `src` in `layout`, built on first use and kept: buffers of bytes_a (and bytes_b, 0 = none), filled by
@@ -848,7 +497,6 @@ static int layer_kernel(const masr_engine* e, int i) {          // efficient con
 }
 static bool layer_grouped(const masr_engine* e, int i) { return e->cfg.model_kind == 2 && i < e->n_group_layers; }
 
-static int finalize_decoder(masr_engine* e);
 static int finalize_model(masr_engine* e, void* stream);
 
 int masr_finalize(masr_engine* e, void* stream) {
@@ -1499,12 +1147,6 @@ void mhsa_out_pw1(masr_engine* e, hipStream_t s, const LayerW& w, const EncodeCt
 // The activation (e->act) sits in two places: the epilogue of the first GEMM of wide_ffn and the tail of the depthwise kernel.
 // ------------------------------------------------------------------------------------------------
 bool is_wide(const masr_engine* e) { return e->cfg.model_kind == 0 && (e->cfg.d_model != 256 || e->act != ENC_ACT_SWISH); }
-// a wide.hip launch under its profile class (masr_profile_select kinds 9-12); a width the kernels are not built for is an error
-#define WIDECHK(kind, launched)                                                                                      \
-    do {                                                                                                             \
-        ProfScope _ps(e, s, kind, 0.0);                                                                              \
-        if (!(launched)) return fail("no kernel for output_size " + std::to_string(e->cfg.d_model) + ": " #launched); \
-    } while (0)
 
 int ensure_wide_ws(masr_engine* e, int nseq, int Tq) {
     CHK(ensure_layer_ws(e, nseq, Tq));
@@ -2025,7 +1667,6 @@ static int encode_full_efficient(masr_engine* e, hipStream_t s, const float* fea
     LAUNCHCHK();
     return 0;
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // DeepSpeech2 (model_kind 3): weights + forward (full utterances and stateful chunks)
@@ -3656,507 +3297,6 @@ int masr_profile_read(masr_engine* e, double* total_ms, int64_t* launches, doubl
         e->prof_used = 0;
         e->prof_flops = 0.0;
     }
-    return 0;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Attention decoder of the second pass (decoder: attention_rescoring): weights + masr_rescore
-// reference: masr/model_utils/transformer/decoder.py (BiTransformerDecoder, TransformerDecoder, DecoderLayer)
-// ------------------------------------------------------------------------------------------------
-static int finalize_decoder_side(masr_engine* e, const std::string& pre, const char* conf_key, int nl, DecoderW& w) {
-    const int d = e->cfg.d_model, V = e->cfg.vocab_size, dff = e->dec.dff;
-    auto upn = [&](const std::string& name, std::vector<int64_t> shape, float** out) -> int {
-        const HostTensor* t;
-        CHK(get(e, name, shape, &t));
-        e->dec.weight_bytes += t->v.size() * sizeof(float);
-        return upload(e, t->v, out);
-    };
-    // rows of several [rows, cols] tensors one under the other (fused projections)
-    auto cat = [&](std::vector<std::string> names, int rows, int cols, float** out) -> int {
-        std::vector<float> v;
-        for (const std::string& n : names) {
-            const HostTensor* t;
-            CHK(get(e, n, cols ? std::vector<int64_t>{rows, cols} : std::vector<int64_t>{rows}, &t));
-            v.insert(v.end(), t->v.begin(), t->v.end());
-        }
-        e->dec.weight_bytes += v.size() * sizeof(float);
-        return upload(e, v, out);
-    };
-    const std::string beyond = pre + "decoders." + std::to_string(nl) + ".norm1.weight";
-    if (e->host.count(beyond))
-        return fail(std::string("decoder_conf.") + conf_key + "=" + std::to_string(nl) + " but the checkpoint holds " + beyond +
-                    " (it was trained with more blocks)");
-    w.layers.assign(nl, DecLayerW{});
-    if (nl == 0) return 0;
-    CHK(upn(pre + "embed.0.weight", {V, d}, &w.emb));
-    for (int i = 0; i < nl; ++i) {
-        const std::string p = pre + "decoders." + std::to_string(i) + ".";
-        if (!e->host.count(p + "norm1.weight"))
-            return fail(std::string("decoder_conf.") + conf_key + "=" + std::to_string(nl) + " but the checkpoint has no " + p +
-                        "norm1.weight (it was trained with fewer blocks)");
-        DecLayerW& l = w.layers[i];
-        CHK(upn(p + "norm1.weight", {d}, &l.n1w));
-        CHK(upn(p + "norm1.bias", {d}, &l.n1b));
-        CHK(cat({p + "self_attn.linear_q.weight", p + "self_attn.linear_k.weight", p + "self_attn.linear_v.weight"}, d, d, &l.wqkv));
-        CHK(cat({p + "self_attn.linear_q.bias", p + "self_attn.linear_k.bias", p + "self_attn.linear_v.bias"}, d, 0, &l.bqkv));
-        CHK(upn(p + "self_attn.linear_out.weight", {d, d}, &l.wo));
-        CHK(upn(p + "self_attn.linear_out.bias", {d}, &l.bo));
-        CHK(upn(p + "norm2.weight", {d}, &l.n2w));
-        CHK(upn(p + "norm2.bias", {d}, &l.n2b));
-        CHK(upn(p + "src_attn.linear_q.weight", {d, d}, &l.wq2));
-        CHK(upn(p + "src_attn.linear_q.bias", {d}, &l.bq2));
-        CHK(cat({p + "src_attn.linear_k.weight", p + "src_attn.linear_v.weight"}, d, d, &l.wkv2));
-        CHK(cat({p + "src_attn.linear_k.bias", p + "src_attn.linear_v.bias"}, d, 0, &l.bkv2));
-        CHK(upn(p + "src_attn.linear_out.weight", {d, d}, &l.wo2));
-        CHK(upn(p + "src_attn.linear_out.bias", {d}, &l.bo2));
-        CHK(upn(p + "norm3.weight", {d}, &l.n3w));
-        CHK(upn(p + "norm3.bias", {d}, &l.n3b));
-        auto b1 = e->host.find(p + "feed_forward.w_1.bias");
-        if (b1 != e->host.end() && (int64_t)b1->second.v.size() != dff)
-            return fail("decoder_conf.linear_units=" + std::to_string(dff) + " but the checkpoint was trained with linear_units=" +
-                        std::to_string(b1->second.v.size()) + " (" + p + "feed_forward.w_1.bias)");
-        CHK(upn(p + "feed_forward.w_1.weight", {dff, d}, &l.w1));
-        CHK(upn(p + "feed_forward.w_1.bias", {dff}, &l.b1));
-        CHK(upn(p + "feed_forward.w_2.weight", {d, dff}, &l.w2));
-        CHK(upn(p + "feed_forward.w_2.bias", {d}, &l.b2));
-    }
-    CHK(upn(pre + "after_norm.weight", {d}, &w.after_w));
-    CHK(upn(pre + "after_norm.bias", {d}, &w.after_b));
-    CHK(upn(pre + "output_layer.weight", {V, d}, &w.out_w));
-    CHK(upn(pre + "output_layer.bias", {V}, &w.out_b));
-    return 0;
-}
-
-static int finalize_decoder(masr_engine* e) {
-    HIPCHK(hipSetDevice(e->cfg.device_id));
-    bool any = false;
-    for (const auto& kv : e->host) any = any || kv.first.rfind("decoder.left_decoder.", 0) == 0;
-    if (!any) {
-        if (e->dec.ready) return 0;        // a reload of encoder tensors only: the decoder weights stay as they are
-        return fail("attention_rescoring: the checkpoint holds no decoder.left_decoder.* tensors (it has no attention decoder)");
-    }
-    // a reload replaces the whole set: the previous weights are freed once the device has drained (launches in flight may
-    // still read them), and a finalize that fails midway leaves no half-filled decoder behind
-    auto drop = [&]() {
-        for (void* p : e->dec.owned) (void)hipFree(p);
-        e->dec.owned.clear();
-        e->dec.left = DecoderW{};
-        e->dec.right = DecoderW{};
-        e->dec.weight_bytes = 0;
-        e->dec.ready = false;
-    };
-    if (!e->dec.owned.empty()) (void)hipDeviceSynchronize();
-    drop();
-    const size_t n0 = e->owned.size();
-    int rc = finalize_decoder_side(e, "decoder.left_decoder.", "num_blocks", e->dec.nl, e->dec.left);
-    if (!rc) rc = finalize_decoder_side(e, "decoder.right_decoder.", "r_num_blocks", e->dec.nr, e->dec.right);
-    e->dec.owned.assign(e->owned.begin() + n0, e->owned.end());       // (upload() files every allocation under e->owned)
-    e->owned.resize(n0);
-    if (rc) {
-        drop();
-        return rc;
-    }
-    e->dec.ready = true;
-    return 0;
-}
-
-namespace {
-
-// one TransformerDecoder over the hypothesis table -> out [B * N] (reverse: the right-to-left decoder's view of the table)
-int decoder_forward(masr_engine* e, hipStream_t s, const DecoderW& w, int reverse, const float* enc, const int* enc_lens, int B,
-                    int Tp, const int* hyp, const int* hyp_lens, int N, int Lmax, float* out) {
-    const int d = e->cfg.d_model, V = e->cfg.vocab_size, dff = e->dec.dff, H = e->dec.heads;
-    const int S = B * N, Lp = Lmax + 1, M = S * Lp, Mk = B * Tp;
-    float *x = e->dec_x.as<float>(), *ln = e->dec_ln.as<float>(), *qkv = e->dec_qkv.as<float>(), *att = e->dec_att.as<float>(),
-          *kv = e->dec_kv.as<float>(), *hid = e->dec_hid.as<float>(), *logits = e->dec_logits.as<float>();
-    const float eps = 1e-12f;          // nn.LayerNorm(size, eps=1e-12) throughout the decoder (decoder.py:173, 308-310)
-    launch_dec_embed(hyp, hyp_lens, w.emb, e->pe, x, S, Lmax, d, V, reverse, s);
-    for (const DecLayerW& l : w.layers) {
-        // x <- x + Wo . self_attn(norm1(x)), causal over the hypothesis' own rows
-        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n1w, l.n1b, ln, M, d, eps, 0, 0, nullptr, s));
-        gemm(e, s, ln, d, l.wqkv, l.bqkv, qkv, 3 * d, M, 3 * d, d, ACT_NONE, 1.f, nullptr, 0);
-        launch_dec_attention(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, hyp_lens, nullptr, S, N, Lmax, Tp, H, 1, s);
-        gemm(e, s, att, d, l.wo, l.bo, x, d, M, d, d, ACT_NONE, 1.f, x, d);
-        // x <- x + Wo . src_attn(norm2(x), memory): k | v of the utterance's encoder frames projected ONCE for its N hypotheses
-        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n2w, l.n2b, ln, M, d, eps, 0, 0, nullptr, s));
-        gemm(e, s, ln, d, l.wq2, l.bq2, qkv, d, M, d, d, ACT_NONE, 1.f, nullptr, 0);
-        gemm(e, s, enc, d, l.wkv2, l.bkv2, kv, 2 * d, Mk, 2 * d, d, ACT_NONE, 1.f, nullptr, 0);
-        launch_dec_attention(qkv, d, kv, kv + d, 2 * d, att, d, hyp_lens, enc_lens, S, N, Lmax, Tp, H, 0, s);
-        gemm(e, s, att, d, l.wo2, l.bo2, x, d, M, d, d, ACT_NONE, 1.f, x, d);
-        // x <- x + W2 . relu(W1 . norm3(x))
-        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n3w, l.n3b, ln, M, d, eps, 0, 0, nullptr, s));
-        gemm(e, s, ln, d, l.w1, l.b1, hid, dff, M, dff, d, ACT_RELU, 1.f, nullptr, 0);
-        gemm(e, s, hid, dff, l.w2, l.b2, x, d, M, d, dff, ACT_NONE, 1.f, x, d);
-    }
-    WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, w.after_w, w.after_b, ln, M, d, eps, 0, 0, nullptr, s));
-    gemm(e, s, ln, d, w.out_w, w.out_b, logits, V, M, V, d, ACT_NONE, 1.f, nullptr, 0);
-    launch_dec_scores(logits, hyp, hyp_lens, e->dec_rowlp.as<float>(), out, S, Lmax, V, reverse, s);
-    return 0;
-}
-
-// what needs no device: refused before the engine is touched
-int rescore_shape_check(const char* who, const void* enc, const void* enc_lens, int B, int Tp, const void* hyp, const void* hyp_lens,
-                        int N, int Lmax, const void* att, const void* r_att) {
-    const std::string w(who);
-    if (!enc || !enc_lens || !hyp || !hyp_lens || !att || !r_att) return fail(w + ": null argument");
-    if (B <= 0 || Tp <= 0) return fail(w + ": B and Tp must be positive");
-    if (N < 1 || N > 64) return fail(w + ": N = " + std::to_string(N) + " hypotheses per utterance is outside 1 .. 64 (beam_size)");
-    if (Lmax < 1) return fail(w + ": Lmax must be at least 1");
-    if ((int64_t)B * N > 65535) return fail(w + ": B * N must not exceed 65535 sequences per call");
-    return 0;
-}
-
-int rescore_impl(masr_engine* e, const float* enc, const int* enc_lens, int B, int Tp, const int* hyp, const int* hyp_lens, int N,
-                 int Lmax, int with_right, float* att, float* r_att, hipStream_t s) {
-    if (!e->dec.enabled || !e->dec.ready)
-        return fail("masr_rescore: this engine holds no attention decoder (masr_decoder_enable before masr_finalize)");
-    if (Lmax > e->cfg.max_pos - 1)
-        return fail("masr_rescore: hypotheses longer than max_pos - 1 = " + std::to_string(e->cfg.max_pos - 1) +
-                    " tokens have no positional rows (Lmax = " + std::to_string(Lmax) + ")");
-    if (with_right && e->dec.nr == 0)
-        return fail("masr_rescore: reverse_weight > 0 needs the right-to-left decoder, and this checkpoint has none (r_num_blocks: 0)");
-    const int d = e->cfg.d_model, V = e->cfg.vocab_size;
-    const size_t M = (size_t)B * N * (Lmax + 1), f = sizeof(float);
-    CHK(e->dec_x.ensure(M * d * f));
-    CHK(e->dec_ln.ensure(M * d * f));
-    CHK(e->dec_qkv.ensure(M * 3 * d * f));
-    CHK(e->dec_att.ensure(M * d * f));
-    CHK(e->dec_kv.ensure((size_t)B * Tp * 2 * d * f));
-    CHK(e->dec_hid.ensure(M * e->dec.dff * f));
-    CHK(e->dec_logits.ensure(M * V * f));
-    CHK(e->dec_rowlp.ensure(M * f));
-    CHK(decoder_forward(e, s, e->dec.left, 0, enc, enc_lens, B, Tp, hyp, hyp_lens, N, Lmax, att));
-    if (with_right) CHK(decoder_forward(e, s, e->dec.right, 1, enc, enc_lens, B, Tp, hyp, hyp_lens, N, Lmax, r_att));
-    else HIPCHK(hipMemsetAsync(r_att, 0, (size_t)B * N * f, s));
-    LAUNCHCHK();
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int masr_decoder_enable(masr_engine* e, int32_t attention_heads, int32_t linear_units, int32_t num_blocks, int32_t r_num_blocks) {
-    if (attention_heads != 4 && attention_heads != 8)
-        return fail("decoder_conf.attention_heads=" + std::to_string(attention_heads) + " is not supported: output_size / 64 (4 at "
-                    "256, 8 at 512; the decoder's attention kernel runs heads of 64)");
-    if (linear_units <= 0 || linear_units % 32)
-        return fail("decoder_conf.linear_units=" + std::to_string(linear_units) + " is not supported: a positive multiple of 32");
-    if (num_blocks < 1) return fail("decoder_conf.num_blocks=" + std::to_string(num_blocks) + " is not supported: at least 1");
-    if (r_num_blocks < 0) return fail("decoder_conf.r_num_blocks=" + std::to_string(r_num_blocks) + " is not supported: 0 or more");
-    if (!e) return fail("null engine");
-    if (e->cfg.model_kind == 3)
-        return fail("attention_rescoring: use_model deepspeech2 has no attention decoder (its decoder.* tensors are the CTC head)");
-    if (!wide_supported(e->cfg.d_model) || e->cfg.d_model != attention_heads * 64)
-        return fail("decoder_conf.attention_heads=" + std::to_string(attention_heads) + " is not supported at output_size " +
-                    std::to_string(e->cfg.d_model) + ": output_size / 64 heads, output_size 256 or 512");
-    if (e->finalized) return fail("masr_decoder_enable: call it before masr_load_tensor / masr_finalize");
-    e->dec.enabled = true;
-    e->dec.heads = attention_heads;
-    e->dec.dff = linear_units;
-    e->dec.nl = num_blocks;
-    e->dec.nr = r_num_blocks;
-    return 0;
-}
-
-int masr_rescore(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const int32_t* hyp_dev,
-                 const int32_t* hyp_lens_dev, int32_t N, int32_t Lmax, int32_t with_right, float* att_dev, float* r_att_dev,
-                 void* stream) {
-    CHK(rescore_shape_check("masr_rescore", enc_dev, enc_lens_dev, B, Tp, hyp_dev, hyp_lens_dev, N, Lmax, att_dev, r_att_dev));
-    if (!e || !e->finalized) return fail("engine not finalized");
-    ENTER(e);
-    CallGuard call_guard(e, (hipStream_t)stream);
-    return rescore_impl(e, enc_dev, enc_lens_dev, B, Tp, hyp_dev, hyp_lens_dev, N, Lmax, with_right, att_dev, r_att_dev,
-                        (hipStream_t)stream);
-}
-
-int masr_op_decoder_scores(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t Tp,
-                           const int32_t* hyp_host, const int32_t* hyp_lens_host, int32_t N, int32_t Lmax, int32_t with_right,
-                           float* att_host, float* r_att_host, void* stream) {
-    CHK(rescore_shape_check("masr_op_decoder_scores", enc_dev, enc_lens_host, B, Tp, hyp_host, hyp_lens_host, N, Lmax, att_host,
-                            r_att_host));
-    for (int b = 0; b < B; ++b)
-        if (enc_lens_host[b] < 1 || enc_lens_host[b] > Tp)
-            return fail("masr_op_decoder_scores: utterance " + std::to_string(b) + " has " + std::to_string(enc_lens_host[b]) +
-                        " encoder frames, outside 1 .. Tp");
-    for (int s = 0; s < B * N; ++s)
-        if (hyp_lens_host[s] < 0 || hyp_lens_host[s] > Lmax)
-            return fail("masr_op_decoder_scores: hypothesis " + std::to_string(s) + " has length " + std::to_string(hyp_lens_host[s]) +
-                        ", outside 0 .. Lmax");
-    if (!e || !e->finalized) return fail("engine not finalized");
-    const int V = e->cfg.vocab_size;
-    for (int s = 0; s < B * N; ++s)
-        for (int i = 0; i < hyp_lens_host[s]; ++i) {
-            const int t = hyp_host[(size_t)s * Lmax + i];
-            if (t < 0 || t >= V)
-                return fail("masr_op_decoder_scores: token id " + std::to_string(t) + " of hypothesis " + std::to_string(s) +
-                            " is outside the vocabulary");
-        }
-    ENTER(e);
-    hipStream_t st = (hipStream_t)stream;
-    CallGuard call_guard(e, st);
-    const size_t S = (size_t)B * N;
-    struct Table {
-        int* p = nullptr;
-        ~Table() { if (p) (void)hipFree(p); }
-    } tab;
-    // hyp [S, Lmax] | hyp_lens [S] | enc_lens [B] | att [S] | r_att [S] (the last two as float)
-    const size_t n_int = S * Lmax + S + B, n_all = n_int + 2 * S;
-    HIPCHK(hipMalloc((void**)&tab.p, n_all * sizeof(int)));
-    int *hyp_d = tab.p, *len_d = hyp_d + S * Lmax, *enc_d = len_d + S;
-    float *att_d = reinterpret_cast<float*>(enc_d + B), *ratt_d = att_d + S;
-    HIPCHK(hipMemcpyAsync(hyp_d, hyp_host, S * Lmax * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(len_d, hyp_lens_host, S * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(enc_d, enc_lens_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-    CHK(rescore_impl(e, enc_dev, enc_d, B, Tp, hyp_d, len_d, N, Lmax, with_right, att_d, ratt_d, st));
-    HIPCHK(hipMemcpyAsync(att_host, att_d, S * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(r_att_host, ratt_d, S * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// decoder: attention -- left-to-right beam search with the LEFT decoder alone, one new row per hypothesis and step
-// (forward_one_step, transformer/decoder.py:233-270; the kernels and the cache layout: decoder_step.hip)
-// ------------------------------------------------------------------------------------------------
-namespace {
-
-struct StepPlan {
-    int B, N, S, Tp, Lcap, Lrun, max_len;
-    int *tok[2], *anc[2], *done, *active;
-    float* score[2];
-};
-
-// steps the host may have to launch: no utterance runs longer (enc_lens <= Tp)
-int step_run_bound(const masr_engine* e, int Tp, int Lcap, int max_len) {
-    int r = std::min(std::min(Tp, Lcap), e->cfg.max_pos - 1);
-    if (max_len > 0) r = std::min(r, max_len);
-    return std::max(r, 1);
-}
-
-int step_workspaces(masr_engine* e, StepPlan& pl, int topn) {
-    const int d = e->cfg.d_model, V = e->cfg.vocab_size, nl = e->dec.nl;
-    const size_t S = (size_t)pl.S, f = sizeof(float);
-    CHK(e->st_x.ensure(S * d * f));
-    CHK(e->st_ln.ensure(S * d * f));
-    CHK(e->st_q.ensure(S * d * f));
-    CHK(e->st_att.ensure(S * d * f));
-    CHK(e->st_hid.ensure(S * e->dec.dff * f));
-    CHK(e->st_logits.ensure(S * V * f));
-    CHK(e->st_cache.ensure((size_t)nl * pl.Lrun * S * 2 * d * f));
-    CHK(e->st_src.ensure((size_t)nl * pl.B * pl.Tp * 2 * d * f));
-    CHK(e->st_top.ensure(S * topn * (f + sizeof(int))));
-    // tok[2] | anc[2] [S, Lcap], score[2] [S], done [B], active [1]
-    const size_t tab = S * pl.Lcap;
-    CHK(e->st_tab.ensure((4 * tab + 2 * S + pl.B + 1) * sizeof(int)));
-    int* t = e->st_tab.as<int>();
-    pl.tok[0] = t;
-    pl.tok[1] = t + tab;
-    pl.anc[0] = t + 2 * tab;
-    pl.anc[1] = t + 3 * tab;
-    pl.score[0] = reinterpret_cast<float*>(t + 4 * tab);
-    pl.score[1] = pl.score[0] + S;
-    pl.done = t + 4 * tab + 2 * S;
-    pl.active = pl.done + pl.B;
-    return 0;
-}
-
-// source k | v of every block: ONE GEMM per utterance batch and layer, before the loop
-void step_source_kv(masr_engine* e, hipStream_t s, const float* enc, const StepPlan& pl) {
-    const int d = e->cfg.d_model, Mk = pl.B * pl.Tp;
-    float* src = e->st_src.as<float>();
-    for (size_t i = 0; i < e->dec.left.layers.size(); ++i) {
-        const DecLayerW& l = e->dec.left.layers[i];
-        gemm(e, s, enc, d, l.wkv2, l.bkv2, src + i * (size_t)Mk * 2 * d, 2 * d, Mk, 2 * d, d, ACT_NONE, 1.f, nullptr, 0);
-    }
-}
-
-// position p of every row: embedding, the blocks (the new k | v written straight into cache slab p), after_norm, output layer,
-// log_softmax + top n.  full / only_pos: the teacher-forced op's outputs (launch_step_topn)
-int step_forward(masr_engine* e, hipStream_t s, const StepPlan& pl, int p, const int* tok, const int* anc, const int* enc_lens,
-                 int topn, float* full, const int* only_pos) {
-    const DecoderW& w = e->dec.left;
-    const int d = e->cfg.d_model, V = e->cfg.vocab_size, dff = e->dec.dff, H = e->dec.heads, S = pl.S;
-    float *x = e->st_x.as<float>(), *ln = e->st_ln.as<float>(), *q = e->st_q.as<float>(), *att = e->st_att.as<float>(),
-          *hid = e->st_hid.as<float>(), *logits = e->st_logits.as<float>();
-    const float eps = 1e-12f;
-    launch_step_embed(tok, w.emb, e->pe, x, S, p, pl.Lcap, d, V, s);
-    for (size_t i = 0; i < w.layers.size(); ++i) {
-        const DecLayerW& l = w.layers[i];
-        float* cache = e->st_cache.as<float>() + i * (size_t)pl.Lrun * S * 2 * d;
-        const float* src = e->st_src.as<float>() + i * (size_t)pl.B * pl.Tp * 2 * d;
-        // x <- x + Wo . self_attn(norm1(x)): q of the new row; its k | v (rows d .. 3 d of the fused projection) appended as slab p
-        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n1w, l.n1b, ln, S, d, eps, 0, 0, nullptr, s));
-        gemm(e, s, ln, d, l.wqkv, l.bqkv, q, d, S, d, d, ACT_NONE, 1.f, nullptr, 0);
-        gemm(e, s, ln, d, l.wqkv + (size_t)d * d, l.bqkv + d, cache + (size_t)p * S * 2 * d, 2 * d, S, 2 * d, d, ACT_NONE, 1.f, nullptr, 0);
-        launch_step_attention(q, d, cache, att, anc, nullptr, S, pl.N, pl.Tp, pl.Lcap, p, d, H, s);
-        gemm(e, s, att, d, l.wo, l.bo, x, d, S, d, d, ACT_NONE, 1.f, x, d);
-        // x <- x + Wo . src_attn(norm2(x), memory)
-        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n2w, l.n2b, ln, S, d, eps, 0, 0, nullptr, s));
-        gemm(e, s, ln, d, l.wq2, l.bq2, q, d, S, d, d, ACT_NONE, 1.f, nullptr, 0);
-        launch_step_attention(q, d, src, att, nullptr, enc_lens, S, pl.N, pl.Tp, pl.Lcap, p, d, H, s);
-        gemm(e, s, att, d, l.wo2, l.bo2, x, d, S, d, d, ACT_NONE, 1.f, x, d);
-        // x <- x + W2 . relu(W1 . norm3(x))
-        WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n3w, l.n3b, ln, S, d, eps, 0, 0, nullptr, s));
-        gemm(e, s, ln, d, l.w1, l.b1, hid, dff, S, dff, d, ACT_RELU, 1.f, nullptr, 0);
-        gemm(e, s, hid, dff, l.w2, l.b2, x, d, S, d, dff, ACT_NONE, 1.f, x, d);
-    }
-    WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, w.after_w, w.after_b, ln, S, d, eps, 0, 0, nullptr, s));
-    gemm(e, s, ln, d, w.out_w, w.out_b, logits, V, S, V, d, ACT_NONE, 1.f, nullptr, 0);
-    float* top_v = e->st_top.as<float>();
-    int* top_i = reinterpret_cast<int*>(top_v + (size_t)S * topn);
-    launch_step_topn(logits, S, V, topn, top_v, top_i, full, only_pos, p, s);
-    return 0;
-}
-
-int step_shape_check(const masr_engine* e, const char* who, int B, int Tp, int N, int Lcap) {
-    const std::string w(who);
-    if (B <= 0 || Tp <= 0) return fail(w + ": B and Tp must be positive");
-    if (N < 1 || N > 64) return fail(w + ": beam_size = " + std::to_string(N) + " is outside 1 .. 64");
-    if (Lcap < 1) return fail(w + ": Lcap must be at least 1");
-    if ((int64_t)B * N > 65535) return fail(w + ": B * beam_size must not exceed 65535 hypotheses per call");
-    if (!e || !e->finalized) return fail("engine not finalized");
-    if (!e->dec.enabled || !e->dec.ready)
-        return fail(w + ": this engine holds no attention decoder (masr_decoder_enable before masr_finalize)");
-    if (N > e->cfg.vocab_size)
-        return fail(w + ": beam_size = " + std::to_string(N) + " exceeds the vocabulary of " + std::to_string(e->cfg.vocab_size));
-    return 0;
-}
-
-// end poll of masr_attention_decode: every MASR_ATTENTION_POLL steps (default 8; 0 = never) the host reads the count of
-// utterances still running and stops launching at 0.  The results do not depend on it.
-int step_poll_every() {
-    const char* v = getenv("MASR_ATTENTION_POLL");
-    if (!v || !*v) return 8;
-    const int n = atoi(v);
-    return n < 0 ? 0 : n;
-}
-
-}  // namespace
-
-extern "C" {
-
-int masr_attention_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, int32_t beam_size,
-                          int32_t max_len, int32_t* tokens_dev, int32_t Lcap, int32_t* lens_dev, float* scores_dev,
-                          int32_t* steps_host_or_null, void* stream) {
-    if (!enc_dev || !enc_lens_dev || !tokens_dev || !lens_dev || !scores_dev) return fail("masr_attention_decode: null argument");
-    if (max_len < 0) return fail("masr_attention_decode: max_len must be 0 (no limit of its own) or positive");
-    CHK(step_shape_check(e, "masr_attention_decode", B, Tp, beam_size, Lcap));
-    ENTER(e);
-    hipStream_t st = (hipStream_t)stream;
-    CallGuard call_guard(e, st);
-    StepPlan pl{};
-    pl.B = B; pl.N = beam_size; pl.S = B * beam_size; pl.Tp = Tp; pl.Lcap = Lcap; pl.max_len = max_len;
-    pl.Lrun = step_run_bound(e, Tp, Lcap, max_len);
-    CHK(step_workspaces(e, pl, pl.N));
-    const int V = e->cfg.vocab_size, poll = step_poll_every();
-    launch_step_init(pl.score[0], pl.done, pl.active, enc_lens_dev, B, pl.N, Tp, Lcap, max_len, e->cfg.max_pos, st);
-    step_source_kv(e, st, enc_dev, pl);
-    float* top_v = e->st_top.as<float>();
-    int cur = 0, steps = 0;
-    for (int p = 0; p < pl.Lrun; ++p) {
-        CHK(step_forward(e, st, pl, p, pl.tok[cur], pl.anc[cur], enc_lens_dev, pl.N, nullptr, nullptr));
-        StepMerge m{};
-        m.top_v = top_v; m.top_i = reinterpret_cast<const int*>(top_v + (size_t)pl.S * pl.N);
-        m.score_cur = pl.score[cur]; m.score_next = pl.score[cur ^ 1];
-        m.tok_cur = pl.tok[cur]; m.tok_next = pl.tok[cur ^ 1]; m.anc_cur = pl.anc[cur]; m.anc_next = pl.anc[cur ^ 1];
-        m.enc_lens = enc_lens_dev; m.done = pl.done; m.active = pl.active;
-        m.N = pl.N; m.Lcap = Lcap; m.Tp = Tp; m.V = V; m.p = p; m.max_len = max_len; m.max_pos = e->cfg.max_pos;
-        launch_step_merge(m, B, st);
-        cur ^= 1;
-        steps = p + 1;
-        if (poll > 0 && steps % poll == 0 && steps < pl.Lrun) {
-            int active = 1;
-            HIPCHK(hipMemcpyAsync(&active, pl.active, sizeof(int), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (active <= 0) break;
-        }
-    }
-    launch_step_result(pl.tok[cur], pl.score[cur], enc_lens_dev, tokens_dev, lens_dev, scores_dev, pl.S, pl.N, Lcap, Tp, V, steps,
-                       max_len, e->cfg.max_pos, st);
-    LAUNCHCHK();
-    if (steps_host_or_null) *steps_host_or_null = steps;
-    return 0;
-}
-
-int masr_op_decoder_step(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t Tp,
-                         const int32_t* prefix_host, const int32_t* prefix_lens_host, int32_t N, int32_t L, int32_t top_n,
-                         int32_t* top_ids_host, float* top_logp_host, float* logp_host_or_null, void* stream) {
-    if (!enc_dev || !enc_lens_host || !prefix_host || !prefix_lens_host || !top_ids_host || !top_logp_host)
-        return fail("masr_op_decoder_step: null argument");
-    CHK(step_shape_check(e, "masr_op_decoder_step", B, Tp, N, L));
-    const int V = e->cfg.vocab_size, S = B * N;
-    if (top_n < 1 || top_n > 64 || top_n > V)
-        return fail("masr_op_decoder_step: top_n = " + std::to_string(top_n) + " is outside 1 .. min(64, vocabulary)");
-    if (L + 1 > e->cfg.max_pos - 1)
-        return fail("masr_op_decoder_step: prefixes of L = " + std::to_string(L) + " tokens behind sos exceed max_pos - 1 = " +
-                    std::to_string(e->cfg.max_pos - 1) + " positions");
-    for (int b = 0; b < B; ++b)
-        if (enc_lens_host[b] < 1 || enc_lens_host[b] > Tp)
-            return fail("masr_op_decoder_step: utterance " + std::to_string(b) + " has " + std::to_string(enc_lens_host[b]) +
-                        " encoder frames, outside 1 .. Tp");
-    int maxlen = 0;
-    for (int s = 0; s < S; ++s) {
-        if (prefix_lens_host[s] < 0 || prefix_lens_host[s] > L)
-            return fail("masr_op_decoder_step: prefix " + std::to_string(s) + " has length " + std::to_string(prefix_lens_host[s]) +
-                        ", outside 0 .. L");
-        maxlen = std::max(maxlen, prefix_lens_host[s]);
-        for (int i = 0; i < prefix_lens_host[s]; ++i) {
-            const int t = prefix_host[(size_t)s * L + i];
-            if (t < 0 || t >= V)
-                return fail("masr_op_decoder_step: token id " + std::to_string(t) + " of prefix " + std::to_string(s) +
-                            " is outside the vocabulary");
-        }
-    }
-    ENTER(e);
-    hipStream_t st = (hipStream_t)stream;
-    CallGuard call_guard(e, st);
-    StepPlan pl{};
-    pl.B = B; pl.N = N; pl.S = S; pl.Tp = Tp; pl.Lcap = L; pl.max_len = 0;
-    pl.Lrun = maxlen + 1;                      // positions 0 .. maxlen: [sos, tokens...]
-    CHK(step_workspaces(e, pl, top_n));
-    if (logp_host_or_null) CHK(e->st_full.ensure((size_t)S * V * sizeof(float)));
-    // every row is its own ancestor at every position; it writes its outputs at its last position, p = its length
-    std::vector<int> anc((size_t)S * L), pos(S), tok((size_t)S * L, 0);
-    for (int s = 0; s < S; ++s) {
-        pos[s] = prefix_lens_host[s];
-        for (int j = 0; j < L; ++j) anc[(size_t)s * L + j] = s % N;
-        for (int j = 0; j < prefix_lens_host[s]; ++j) tok[(size_t)s * L + j] = prefix_host[(size_t)s * L + j];
-    }
-    struct Table {
-        int* p = nullptr;
-        ~Table() { if (p) (void)hipFree(p); }
-    } tab;
-    HIPCHK(hipMalloc((void**)&tab.p, (size_t)(S + B) * sizeof(int)));
-    int *pos_d = tab.p, *enc_d = pos_d + S;
-    HIPCHK(hipMemcpyAsync(pl.tok[0], tok.data(), tok.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(pl.anc[0], anc.data(), anc.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(pos_d, pos.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(enc_d, enc_lens_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-    step_source_kv(e, st, enc_dev, pl);
-    float* full = logp_host_or_null ? e->st_full.as<float>() : nullptr;
-    for (int p = 0; p < pl.Lrun; ++p) CHK(step_forward(e, st, pl, p, pl.tok[0], pl.anc[0], enc_d, top_n, full, pos_d));
-    LAUNCHCHK();
-    float* top_v = e->st_top.as<float>();
-    HIPCHK(hipMemcpyAsync(top_logp_host, top_v, (size_t)S * top_n * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(top_ids_host, top_v + (size_t)S * top_n, (size_t)S * top_n * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (full) HIPCHK(hipMemcpyAsync(logp_host_or_null, full, (size_t)S * V * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
-}
-
-int masr_decoder_info(masr_engine* e, int32_t* enabled, int32_t* num_blocks, int32_t* r_num_blocks, int64_t* weight_bytes,
-                      int64_t* workspace_bytes) {
-    if (!e) return fail("null engine");
-    if (enabled) *enabled = e->dec.enabled ? 1 : 0;
-    if (num_blocks) *num_blocks = e->dec.nl;
-    if (r_num_blocks) *r_num_blocks = e->dec.nr;
-    if (weight_bytes) *weight_bytes = (int64_t)e->dec.weight_bytes;
-    if (workspace_bytes) *workspace_bytes = (int64_t)e->decoder_bytes();
     return 0;
 }
 

@@ -1,6 +1,6 @@
 // The process-wide masr_debug_set switches: one struct of ints, one table of (key, name, field).  Host only (no HIP include).
 // A launcher reads knobs().field at launch time; production = the in-class defaults, which are written nowhere else.  Keys 2, 16
-// and 38 are not here: they are fields of masr_engine (engine.hip).
+// and 38 are not here: they are fields of masr_engine (engine_state.h).
 #pragma once
 
 namespace masr {

@@ -18,6 +18,8 @@
 #define LM_HD inline
 #endif
 
+struct masr_lm;      // the loaded model (lm_scorer.cpp); include/masr_hip.h names it as an opaque handle
+
 namespace masr {
 
 struct LmEntry {
@@ -34,6 +36,11 @@ struct LmView {
     int n_words;                      // vocabulary size + 2
     int bos, eos;                     // ids of <s> and </s> (= vocabulary size, vocabulary size + 1)
 };
+
+// host side, lm_scorer.cpp: the LM table in the memory of the current device (uploaded on first use there), and whether the model
+// scores words spelt out of several tokens (searched on host threads only)
+int lm_device_view(masr_lm* lm, LmView* out);
+bool lm_word_based(const masr_lm* lm);
 
 static constexpr float LM_OOV_SCORE = -1000.0f;   // scorer.h OOV_SCORE: returned as it is (not converted from log10)
 

@@ -26,12 +26,9 @@
 
 #include "../../include/masr_hip.h"
 #include "common.h"
+#include "engine_state.h"      // masr::subsampled_frames and masr::engine_fail, nothing else: the engine is used through the C ABI
 
 using namespace masr;
-namespace masr {
-int subsampled_frames(const masr_engine* e, int feature_frames);     // engine.hip: frames behind the subsampling front-end
-int engine_fail(const std::string& m);
-}
 
 #define PFAIL(msg) return masr::engine_fail(msg)
 #define PHIP(expr)                                                                                                        \
