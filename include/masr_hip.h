@@ -164,6 +164,34 @@ int masr_ctc_collapse(masr_engine* e, const int32_t* argmax_dev, const float* ma
 int masr_argmax_rows(masr_engine* e, const float* probs_dev, int32_t M, int32_t V, int32_t* argmax_dev,
                      float* maxprob_dev, void* stream);
 
+/* CTC forced alignment: when each token of a hypothesis was spoken (an addition: the reference has no such function).  Per
+ * utterance the best path through the CTC trellis of its hypothesis -- extended labels blank, y1, blank, ..., yL, blank
+ * (S = 2 L + 1 states, blank = id 0); transitions stay, advance by one, skip the blank between two DIFFERENT tokens; the path starts
+ * in state 0 or 1 and ends in state S - 1 or S - 2 -- whichever decoder produced the hypothesis.
+ *   post_dev [B, T', V] f32: input_is_log = 1: log-probabilities (the kernel only adds and compares float32 values, so a float32
+ *     restatement on a CPU matches to the bit); 0: probabilities as masr_ctc_probs writes them, the kernel takes the logarithm
+ *     itself and a probability <= 0 (or NaN) counts as MASR_ALIGN_NEG
+ *   n_frames_dev [B] valid frames, tokens_dev [B, Lmax] with n_tokens_dev [B] ids in [1, V); frames behind n_frames[b] and slots
+ *     behind n_tokens[b] are never read
+ *   start_dev / end_dev [B, Lmax] int32: first and last frame (inclusive) the path spends in the token's state; peak_dev [B, Lmax]
+ *     f32: the token's largest log-probability over those frames; score_dev [B]: the path's log-probability
+ *   status_dev [B]: 0 = aligned; 1 = the trellis has no path: n_frames < L + (number of adjacent equal tokens); 2 = n_frames /
+ *     n_tokens outside [0, T'] / [0, Lmax] or a token id outside [1, V).  With status != 0, and behind n_tokens[b] always, start / end
+ *     are -1 and peak / score 0.  L = 0 aligns to the all-blank path (n_frames = 0: score 0).
+ * Tie rule (part of the contract): the predecessor of a state is taken in the order stay, s - 1, s - 2, and a later candidate
+ * replaces an earlier one only if STRICTLY greater; at the end state S - 1 wins a tie against S - 2.  "Unreachable" is the finite
+ * MASR_ALIGN_NEG, never an infinity; a hypothesis whose best path crosses a zero probability scores <= MASR_ALIGN_NEG / 2 and its
+ * frames mean nothing.
+ * One workgroup per utterance; per frame only the L + 1 needed columns of the V-wide row are read.  The predecessor choices
+ * ([B, T', 2 Lmax + 1] bytes) live in a workspace of the engine's CURRENT lane (masr_select_lane): two passes on two lanes never
+ * share it.  Refused (non-zero, masr_last_error): Lmax > MASR_ALIGN_MAX_TOKENS (the trellis rows in LDS hold S <= 2 * that + 1),
+ * Lmax > T', V > 16384. */
+#define MASR_ALIGN_NEG (-1.0e30f)
+#define MASR_ALIGN_MAX_TOKENS 1024
+int masr_ctc_align(masr_engine* e, const float* post_dev, int32_t input_is_log, int32_t B, int32_t Tp, int32_t V,
+                   const int32_t* n_frames_dev, const int32_t* tokens_dev, const int32_t* n_tokens_dev, int32_t Lmax,
+                   int32_t* start_dev, int32_t* end_dev, float* peak_dev, float* score_dev, int32_t* status_dev, void* stream);
+
 /* External n-gram language model scorer of the beam search.  Replaces the `Scorer` of paddlespeech_ctcdecoders (scorer.cpp on
  * KenLM; constructed in masr/decoders/beam_search_decoder.py:29-35, swig_wrapper.py:4-18; parameters alpha / beta of
  * configs/conformer.yml:74-88).  Character-based ARPA models up to order 5; `vocab_utf8` = the model's vocabulary tokens (the
@@ -357,6 +385,11 @@ int masr_pool_profile(masr_pool* p, double* phase_ms, int64_t* steps, int32_t re
 /* encoder frames that T feature frames give (Conv2dSubsampling4 / 6 / 8 by masr_config.reserved[3], subsampling.py:65-211; halved once more behind the Efficient
  * Conformer's stride layer) and the engine's geometry -- what a host needs to size the buffers above */
 int masr_encoder_frames(masr_engine* e, int32_t feature_frames, int32_t* encoder_frames);
+/* nominal time reduction of the loaded model, in feature frames per encoder frame: 4 / 6 / 8 by the input layer (DeepSpeech2's two
+ * stride-2 convs: 4), doubled by the Efficient Conformer's stride layer; the Squeezeformer's reduce / recover pair cancels.  For large
+ * F, masr_encoder_frames(F + r) - masr_encoder_frames(F) == 1.  Encoder frame t starts at feature frame r * t: what turns the frames
+ * of masr_ctc_align into times. */
+int masr_frame_reduction(masr_engine* e, int32_t* feature_frames_per_encoder_frame);
 int masr_engine_info(masr_engine* e, int32_t* device_id, int32_t* n_mels, int32_t* vocab_size);
 
 /* Streaming.  Replaces InferencePredictor.predict_chunk_conformer / reset_stream

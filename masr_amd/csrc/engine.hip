@@ -2532,6 +2532,15 @@ int masr_encoder_frames(masr_engine* e, int32_t feature_frames, int32_t* encoder
     return 0;
 }
 
+int masr_frame_reduction(masr_engine* e, int32_t* feature_frames_per_encoder_frame) {
+    if (!e || !feature_frames_per_encoder_frame) return fail("null argument");
+    // the subsampling front end (4 / 6 / 8; DeepSpeech2's two stride-2 convs: 4), once more halved by the Efficient Conformer's
+    // stride layer; the Squeezeformer's time reduction is undone by its recovery layer
+    const int r = sub_rate(e->input_layer);
+    *feature_frames_per_encoder_frame = e->cfg.model_kind == 2 && e->stride_idx >= 0 ? 2 * r : r;
+    return 0;
+}
+
 int masr_engine_info(masr_engine* e, int32_t* device_id, int32_t* n_mels, int32_t* vocab_size) {
     if (!e) return fail("null engine");
     if (device_id) *device_id = e->cfg.device_id;

@@ -3,6 +3,7 @@
 //   engine.hip               error state, weight store, the encoders of the four model families, CTC head, feature front ends,
 //                            streams, single ops, debug and profile calls
 //   engine_attdecoder.hip    attention decoder: finalize, rescoring, autoregressive search (kernels: decoder.hip, decoder_step.hip)
+//   ctc_align.hip            forced alignment: kernel and masr_ctc_align
 // A helper that only one file uses stays static (or in an anonymous namespace) there and is not declared here.
 #pragma once
 #include <algorithm>
@@ -230,6 +231,9 @@ struct EngineWs {
     // source k | v [blocks][B * Tp][2 d], top-N values | ids, the double-buffered token / ancestor / score tables and flags, and
     // the test op's [S, V] log-probabilities
     DevBuf st_x, st_ln, st_q, st_att, st_hid, st_logits, st_cache, st_src, st_top, st_tab, st_full;
+    // forced alignment (masr_ctc_align; allocated on the lane's first such call): the predecessor choice of every state and frame,
+    // [B][T'][2 Lmax + 1] bytes
+    DevBuf align_bp;
     size_t decoder_bytes() const {
         return dec_x.bytes + dec_ln.bytes + dec_qkv.bytes + dec_att.bytes + dec_kv.bytes + dec_hid.bytes + dec_logits.bytes +
                dec_rowlp.bytes + st_x.bytes + st_ln.bytes + st_q.bytes + st_att.bytes + st_hid.bytes + st_logits.bytes + st_cache.bytes +
@@ -240,7 +244,7 @@ struct EngineWs {
                           &ln, &hid, &qkv, &att, &lnpad, &glu, &dwo, &logits, &feats, &enc, &idx, &maxp, &attseq, &gain, &nframes,
                           &lens, &xsave, &xred, &xh, &x3, &sublens, &posoff, &dec_x, &dec_ln, &dec_qkv, &dec_att, &dec_kv, &dec_hid,
                           &dec_logits, &dec_rowlp, &st_x, &st_ln, &st_q, &st_att, &st_hid, &st_logits, &st_cache, &st_src, &st_top,
-                          &st_tab, &st_full})
+                          &st_tab, &st_full, &align_bp})
             b->release();
         stage.release();
     }

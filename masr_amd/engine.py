@@ -709,6 +709,37 @@ class HipEngine:
                                          _ptr(ntok), _ptr(score), _stream()))
         return tokens, ntok, score
 
+    def ctc_align(self, post, n_frames, tokens, n_tokens, input_is_log=False, out=None):
+        """masr_ctc_align on the current stream and the active lane: ``post`` [B, T', V] float32 (probabilities as ``ctc_probs``
+        writes them, or log-probabilities with ``input_is_log=True``), ``n_frames`` [B] int32, ``tokens`` [B, Lmax] int32,
+        ``n_tokens`` [B] int32 (all device tensors) -> (start, end [B, Lmax] int32, peak [B, Lmax] float32, score [B] float32,
+        status [B] int32) device tensors (include/masr_hip.h: the tie rule and the meaning of ``status``).  ``out``: a flat int32
+        device buffer of B * (3 Lmax + 2) elements = start | end | peak bits | score bits | status to write them into (so that
+        ONE copy brings them back, ``unpack_alignment``); the five results are views of it.  Nothing is waited for."""
+        B, Tp, V = post.shape
+        Lmax = tokens.shape[1]
+        if out is None:
+            out = torch.empty(B * (3 * Lmax + 2), dtype=torch.int32, device=self.device)
+        flat = out.view(-1)
+        n = B * Lmax
+        start, end = flat[:n].view(B, Lmax), flat[n:2 * n].view(B, Lmax)
+        peak = flat[2 * n:3 * n].view(torch.float32).view(B, Lmax)
+        score, status = flat[3 * n:3 * n + B].view(torch.float32), flat[3 * n + B:3 * n + 2 * B]
+        if not (post.is_contiguous() and tokens.is_contiguous() and post.dtype == torch.float32 and tokens.dtype == torch.int32
+                and n_frames.dtype == torch.int32 and n_tokens.dtype == torch.int32):
+            raise ValueError('ctc_align: contiguous float32 posteriors and int32 tokens / n_frames / n_tokens expected')
+        check(self.lib.masr_ctc_align(self.h, _ptr(post), 1 if input_is_log else 0, B, Tp, V, _ptr(n_frames), _ptr(tokens),
+                                      _ptr(n_tokens), Lmax, _ptr(start), _ptr(end), _ptr(peak), _ptr(score), _ptr(status),
+                                      _stream()))
+        return start, end, peak, score, status
+
+    def frame_reduction(self):
+        """masr_frame_reduction: feature frames per encoder frame of the loaded model (4 / 6 / 8 by the input layer, doubled by
+        the Efficient Conformer's stride layer)"""
+        r = C.c_int32()
+        check(self.lib.masr_frame_reduction(self.h, C.byref(r)))
+        return r.value
+
     def argmax_rows(self, probs):
         M, V = probs.shape
         idx = torch.empty(M, dtype=torch.int32, device=self.device)

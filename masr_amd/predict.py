@@ -144,10 +144,13 @@ class MASRPredictor:
         return ''.join(vocab[j] for j in ids).replace('<space>', ' ')
 
     # ---- offline ------------------------------------------------------------------------------------------------------------
-    def predict(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000):
-        """predict.py:167-192: one utterance -> {'text', 'score'} (a batch of one on the device path)."""
+    def predict(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000, timestamps=False):
+        """predict.py:167-192: one utterance -> {'text', 'score'} (a batch of one on the device path).  ``timestamps=True``: the
+        result gains ``'tokens'``: [{'token', 'start', 'end', 'score'}] per token of the text, in seconds of the utterance (CTC
+        forced alignment of the hypothesis on the GPU, decoders/ctc_alignment.py); [] for an empty transcript, None when the CTC
+        trellis holds no path for the hypothesis."""
         self._no_itn(is_itn)
-        return self._predict_local([self._load_audio(audio_data, sample_rate)])[0]
+        return self._predict_local([self._load_audio(audio_data, sample_rate)], timestamps=timestamps)[0]
 
     def init_vad(self, vad_predictor=None):
         """predict.py:110-115: ``VADPredictor()`` -- the Silero network (on the GPU, weights from the reference's
@@ -160,12 +163,15 @@ class MASRPredictor:
             from masr_amd.infer_utils.vad_predictor import VADPredictor
             self.vad_predictor = VADPredictor()
 
-    def predict_long(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000, vad_predictor=None, batch_size=32):
+    def predict_long(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000, vad_predictor=None, batch_size=32,
+                     timestamps=False):
         """predict.py:195-234: long audio -> VAD segments -> text.  The reference recognises the segments one after the
         other (``self.predict`` per segment, :220); here they go through ``predict_batch`` in length-sorted batches of
         ``batch_size`` (one device pass per batch); texts are joined in time order exactly like the reference (:222-227,233).
         A padded batch follows the reference's own batch > 1 semantics (its pad mask keeps one padding-contaminated key per
-        shorter utterance, trainer.py:632); ``batch_size=1`` is the reference's per-segment ``predict`` to the bit."""
+        shorter utterance, trainer.py:632); ``batch_size=1`` is the reference's per-segment ``predict`` to the bit.
+        ``timestamps=True``: the result gains ``'tokens'`` (see ``predict``) over the WHOLE recording in time order: every
+        token's times are shifted by the start of its VAD segment."""
         if use_pun:
             raise Exception('punctuation (PaddleNLP) is outside the hot path and not provided')
         self._no_itn(is_itn)
@@ -187,7 +193,7 @@ class MASRPredictor:
         for lo in range(0, len(order), batch_size):
             idx = order[lo:lo + batch_size]
             for i, res in zip(idx, self._predict_local([AudioSegment.from_ndarray(pieces[i], audio_segment.sample_rate)
-                                                        for i in idx])):
+                                                        for i in idx], timestamps=timestamps)):
                 results[i] = res
         texts, scores = '', []
         for res in results:
@@ -197,7 +203,12 @@ class MASRPredictor:
             logger.info(f'长语音识别片段结果：{res["text"]}')
         if texts[:1] == '，':
             texts = texts[1:]
-        return {'text': texts, 'score': round(sum(scores) / len(scores), 2) if scores else 0}
+        out = {'text': texts, 'score': round(sum(scores) / len(scores), 2) if scores else 0}
+        if timestamps:
+            from masr_amd.decoders.ctc_alignment import join_segments
+            out['tokens'] = join_segments([res['tokens'] for res in results],
+                                          [t['start'] / float(audio_segment.sample_rate) for t in stamps])
+        return out
 
     def _prep_stream(self):
         """side stream of the per-pass preparation (upload, mean squares and their read-back, gains): the host waits for THIS
@@ -391,13 +402,85 @@ class MASRPredictor:
         return {'count': len(segs), 'ok': ok, 'n': n, 'min_samples': min_samples,
                 'prep': self._prepare_begin(live, n, pc.use_dB_normalization, groups) if ok else None}
 
-    def _predict_local(self, segs, decode_all_frames=False, as_tokens=False, defer=False, hold_search=False, began=None):
+    def _pinned_slot(self, name, numel, dtype=torch.int32, slots=8):
+        """a pinned host buffer of ``numel`` elements out of a named ring (more slots than passes are ever in flight)"""
+        ring = self.__dict__.setdefault('_pinned_rings', {}).setdefault((name, dtype), {'bufs': [None] * slots, 'turn': 0})
+        k = ring['turn']
+        ring['turn'] = (k + 1) % slots
+        if ring['bufs'][k] is None or ring['bufs'][k].numel() < numel:
+            ring['bufs'][k] = torch.empty(max(numel, 1 << 12), dtype=dtype, pin_memory=True)
+        return ring['bufs'][k][:numel]
+
+    def _align_queue(self, eng, probs, nenc, tok_dev, ntok_dev):
+        """ONE masr_ctc_align call for a pass on the current stream and the active lane, and ONE copy of its packed results to
+        pinned memory behind an event -> (pinned int32 buffer, event, what must stay alive until the event)"""
+        B, lmax = tok_dev.shape
+        packed = torch.empty(B * (3 * lmax + 2), dtype=torch.int32, device=eng.device)
+        eng.ctc_align(probs, nenc, tok_dev, ntok_dev, out=packed)
+        host = self._pinned_slot('align', packed.numel())
+        host.copy_(packed, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return host, ev, (probs, nenc, tok_dev, ntok_dev, packed)
+
+    def _align_rows(self, eng, host, ids_list, lmax, n, alignable=None):
+        """the packed alignment of a pass on the host -> the ``'tokens'`` value of every utterance of the pass"""
+        from masr_amd.decoders.ctc_alignment import unpack_alignment, utterance_tokens
+        rate = int(self.configs.preprocess_conf.get('sample_rate', 16000))
+        if self.__dict__.get('_frame_reduction') is None:
+            self._frame_reduction = eng.frame_reduction()
+        start, end, peak, score, status = unpack_alignment(host.numpy(), len(ids_list), lmax)
+        vocab = self._text_featurizer.vocab_list
+        return [utterance_tokens(ids, start[j], end[j], peak[j], score[j], status[j] if alignable is None or alignable[j] else 1,
+                                 self._frame_reduction, rate, float(n[j]) / rate, vocab) for j, ids in enumerate(ids_list)]
+
+    def _timestamp_finisher(self, eng, probs, nenc, n, ok, out):
+        """for the decoders whose hypotheses reach the host first (beam search, rescoring, attention): the pass keeps its CTC
+        posteriors ``probs`` on the device; the function returned takes the pass's [(token ids, score)] once they are known, sends
+        the ids up in one small copy, aligns them with ONE masr_ctc_align call on the pass's own stream and lane, waits for the one
+        copy back and fills ``out`` with {'text', 'score', 'tokens'}"""
+        from masr_amd.decoders.ctc_alignment import pack_hypotheses
+        stream = torch.cuda.current_stream(eng.device)
+        lane = getattr(eng, 'lane', 0)
+        if nenc is None:
+            nenc = torch.full((probs.shape[0],), probs.shape[1], dtype=torch.int32, device=eng.device)
+
+        def finish(res):
+            ids_list = [[int(t) for t in r[0]] for r in res]
+            flat, lmax, alignable = pack_hypotheses(ids_list, probs.shape[1])
+            B = len(ids_list)
+            active = getattr(eng, 'lane', 0)
+            if lane != active:
+                eng.select_lane(lane)
+            try:
+                with torch.cuda.stream(stream):
+                    dev = eng.to_device(flat)
+                    host, ev, keep = self._align_queue(eng, probs, nenc, dev[:B * lmax].view(B, lmax), dev[B * lmax:])
+            finally:
+                if lane != active:
+                    eng.select_lane(active)
+            ev.synchronize()
+            del keep
+            toks = self._align_rows(eng, host, ids_list, lmax, n, alignable)
+            for j, i in enumerate(ok):
+                out[i] = {'text': self._text(ids_list[j]), 'score': res[j][1], 'tokens': toks[j]}
+            return out
+        return finish
+
+    def _predict_local(self, segs, decode_all_frames=False, as_tokens=False, defer=False, hold_search=False, began=None,
+                       timestamps=False):
         """AudioSegments -> [{'text','score'}] on THIS rank's engine.  Utterances too short for one feature frame decode to
         the empty transcript (the reference's encoder cannot take them either); a digitally silent utterance (mean square 0) is
         normalised with gain = target_dB like the reference (audio.py:519-529), only a gain above max_gain_db raises (:300-303).
         ``defer=True``: nothing is waited for -- a zero-argument function that returns the results is handed back, so the caller
         prepares and launches the next device pass underneath this one (greedy: the packed hypothesis rows come back in one
-        copy behind an event; beam search on the GPU: the prefix search runs on a side stream)."""
+        copy behind an event; beam search on the GPU: the prefix search runs on a side stream).
+        ``timestamps=True``: every result gains ``'tokens'`` (decoders/ctc_alignment.py).  The pass keeps its CTC posteriors on the
+        device until its hypotheses are known and aligns them with one masr_ctc_align call (``attention`` runs the CTC head for
+        that alone); ``ctc_greedy`` takes the route of separate calls whatever the features.  Without it nothing changes."""
+        if timestamps and (as_tokens or hold_search):
+            from masr_amd.decoders.ctc_alignment import DISTRIBUTED_REFUSAL, HELD_SEARCH_REFUSAL
+            raise Exception(DISTRIBUTED_REFUSAL if as_tokens else HELD_SEARCH_REFUSAL)
         eng = self.predictor.engine
         pc = self.configs.preprocess_conf
         method = pc.get('feature_method', 'fbank')
@@ -407,7 +490,7 @@ class MASRPredictor:
         out = [None] * began['count']
         if len(ok) != began['count']:
             for i in set(range(began['count'])) - set(ok):
-                out[i] = ([], 0) if as_tokens else {'text': '', 'score': 0}
+                out[i] = ([], 0) if as_tokens else {'text': '', 'score': 0, 'tokens': []} if timestamps else {'text': '', 'score': 0}
         if not ok:
             return (lambda: out) if defer else out
         live = ok                # (only its length is used below)
@@ -415,7 +498,7 @@ class MASRPredictor:
         rescoring = self.configs.decoder == 'attention_rescoring'
         attention = self.configs.decoder == 'attention'
         greedy = self.configs.decoder != 'ctc_beam_search' and not rescoring and not attention
-        if greedy and method == 'fbank':
+        if greedy and method == 'fbank' and not timestamps:
             # the whole pass is ONE C-ABI call and ONE copy back: rows [B, T' + 2] = tokens | count | score bits
             rows = eng.transcribe_rows(xs, ns, pc.use_dB_normalization, pc.target_dB, gain_in=gain,
                                        decode_all_frames=decode_all_frames)
@@ -441,13 +524,18 @@ class MASRPredictor:
         with debug_keys(eng, skip_padding=0) if decode_all_frames else contextlib.nullcontext():
             enc = eng.encode_full(feats, frames, -1)
         nenc = None if decode_all_frames else eng.enc_frames(frames).to(torch.int32)
+        want_ids = as_tokens or timestamps
         if attention:
             # the search is queued behind this pass's encoder on the SAME stream and lane (the caller selected them): no CTC head,
             # no prefix search; the host waits at the search's end polls and fetches the hypotheses behind an event
             enc_lens = nenc if nenc is not None else torch.full((len(live),), enc.shape[1], dtype=torch.int32, device=eng.device)
-            fetch_pass = self.attention_decoder.decode_pass(eng, enc, enc_lens.contiguous(), want_tokens=as_tokens)
+            # (timestamps: the CTC head runs for the alignment alone, in front of the search)
+            finish = self._timestamp_finisher(eng, eng.ctc_probs(enc), nenc, n, ok, out) if timestamps else None
+            fetch_pass = self.attention_decoder.decode_pass(eng, enc, enc_lens.contiguous(), want_tokens=want_ids)
 
             def fetch_searched():
+                if finish is not None:
+                    return finish(fetch_pass())
                 for i, r in zip(ok, fetch_pass()):
                     out[i] = r if as_tokens else {'text': r[1], 'score': r[0]}
                 return out
@@ -461,9 +549,12 @@ class MASRPredictor:
             n_host = [probs.shape[1]] * len(live) if nenc is None else \
                 eng.enc_frames((n.astype(np.int64) - min_samples) // 160 + 1).tolist()
             enc_lens = nenc if nenc is not None else torch.full((len(live),), enc.shape[1], dtype=torch.int32, device=eng.device)
-            fetch_pass = self.rescoring_decoder.decode_pass(eng, enc, enc_lens.contiguous(), probs, n_host, want_tokens=as_tokens)
+            finish = self._timestamp_finisher(eng, probs, nenc, n, ok, out) if timestamps else None
+            fetch_pass = self.rescoring_decoder.decode_pass(eng, enc, enc_lens.contiguous(), probs, n_host, want_tokens=want_ids)
 
             def fetch_rescored():
+                if finish is not None:
+                    return finish(fetch_pass())
                 for i, r in zip(ok, fetch_pass()):
                     out[i] = r if as_tokens else {'text': r[1], 'score': r[0]}
                 return out
@@ -474,8 +565,11 @@ class MASRPredictor:
             n_host = [probs.shape[1]] * len(live) if nenc is None else eng.enc_frames((n.astype(np.int64) - min_samples) // 160 + 1).tolist()
             seqs = probs                       # searched in place: padded [B, T', V] + the valid frames per utterance
             dec = self.beam_search_decoder
+            finish = self._timestamp_finisher(eng, probs, nenc, n, ok, out) if timestamps else None
 
             def fill(res):
+                if finish is not None:
+                    return finish(res)
                 for i, r in zip(ok, res):
                     out[i] = r if as_tokens else {'text': r[1], 'score': r[0]}
                 return out
@@ -499,7 +593,7 @@ class MASRPredictor:
                     side.wait_stream(main)
                     with torch.cuda.stream(side):
                         pending = dec._batch(seqs, defer=True, frames=n_host)
-                    return lambda: fill(dec._batch_collect(pending, want_tokens=as_tokens))
+                    return lambda: fill(dec._batch_collect(pending, want_tokens=want_ids))
                 if hold_search:
                     # the pass's candidates are pruned here, on the main stream right behind its CTC head (the 134 MB of
                     # probabilities are then dead); the search itself is launched ONCE for the passes of a group (_run_sorted)
@@ -508,12 +602,40 @@ class MASRPredictor:
             if defer and torch.is_tensor(seqs) and seqs.is_cuda and os.environ.get('MASR_HOST_SEARCH_DEFER', '1') == '1':
                 # host-thread search (word-based scorer, sizes beyond the GPU kernel): pruning queued now, candidates fetched and
                 # searched when the results are collected -- under the encoders of the passes launched in between
-                handle = dec.search_host_deferred(seqs, n_host, want_tokens=as_tokens)
+                handle = dec.search_host_deferred(seqs, n_host, want_tokens=want_ids)
                 return lambda: fill(handle())
-            res = fill(dec._batch(seqs, want_tokens=as_tokens, frames=n_host))
+            res = fill(dec._batch(seqs, want_tokens=want_ids, frames=n_host))
             return (lambda: res) if defer else res
         idx, mp = eng.ctc_greedy_frames(enc)
         tok, ntok, score = eng.ctc_collapse(idx, mp, nenc)
+        if timestamps:
+            # the greedy tokens never leave the device before they are aligned: the CTC head's posteriors, ONE masr_ctc_align call
+            # behind the collapse, and the hypotheses and the packed alignment come back behind one event
+            from masr_amd.decoders.ctc_alignment import MAX_TOKENS
+            B, Tp = tok.shape
+            lmax = min(Tp, MAX_TOKENS)          # (a longer hypothesis comes back with status 2: 'tokens' is None)
+            frames_dev = nenc if nenc is not None else torch.full((B,), Tp, dtype=torch.int32, device=eng.device)
+            tok_in = tok if lmax == Tp else tok[:, :lmax].contiguous()
+            a_host, ev, keep = self._align_queue(eng, eng.ctc_probs(enc), frames_dev.contiguous(), tok_in, ntok)
+            g_host = self._pinned_slot('greedy', B * Tp + 2 * B)
+            g_host[:B * Tp].view(B, Tp).copy_(tok, non_blocking=True)
+            g_host[B * Tp:B * Tp + B].copy_(ntok, non_blocking=True)
+            g_host[B * Tp + B:].view(torch.float32).copy_(score, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            keep = keep + (tok, ntok, score)
+
+            def fetch_aligned(_keep=keep):
+                ev.synchronize()
+                g = g_host.numpy()
+                tok_h, ntok_h, score_h = g[:B * Tp].reshape(B, Tp), g[B * Tp:B * Tp + B], g[B * Tp + B:].view(np.float32)
+                ids_list = [tok_h[j, :ntok_h[j]].tolist() for j in range(B)]
+                toks = self._align_rows(eng, a_host, ids_list, lmax, n)
+                for j, i in enumerate(ok):
+                    sc = float(score_h[j]) * 100.0 if ntok_h[j] > 0 or score_h[j] > 0 else 0
+                    out[i] = {'text': self._text(ids_list[j]), 'score': sc, 'tokens': toks[j]}
+                return out
+            return fetch_aligned if defer else fetch_aligned()
         tok, ntok, score = eng.to_host(tok), eng.to_host(ntok), eng.to_host(score)
         for j, i in enumerate(ok):
             sc = float(score[j]) * 100.0 if ntok[j] > 0 or score[j] > 0 else 0
@@ -543,7 +665,7 @@ class MASRPredictor:
         return 64 if self.configs.use_model == 'efficient_conformer' else 32
 
     def predict_batch(self, audio_list, sample_rate=16000, decode_all_frames=False, batch_size=0, distributed=None,
-                      lengths=None, pass_padded=None):
+                      lengths=None, pass_padded=None, timestamps=False):
         """Batched offline path (an addition; the reference's only batched consumer is MASRTrainer.evaluate,
         trainer.py:592-651): a list of utterances -> [{'text','score'}] in input order.
 
@@ -561,7 +683,8 @@ class MASRPredictor:
         used for sorting and sharding instead of reading every file's header.
         With an initialised ``torch.distributed`` group (``distributed=None``: automatically when world > 1) the utterances
         are dealt out length-balanced over the ranks -- every rank must call with the same list -- each rank decodes ONLY
-        its shard on its own GPU and ONE all-gather of the token ids returns all hypotheses to every rank."""
+        its shard on its own GPU and ONE all-gather of the token ids returns all hypotheses to every rank.
+        ``timestamps=True``: every result gains ``'tokens'`` (see ``predict``); refused on the sharded path."""
         hints = list(lengths) if lengths is not None else [self._length_hint(a, sample_rate) for a in audio_list]
         if batch_size == 'auto':
             batch_size = self.pass_size()
@@ -576,9 +699,12 @@ class MASRPredictor:
         rank, world = parallel.world_info()
         if distributed is None:
             distributed = world > 1
+        if timestamps and distributed:
+            from masr_amd.decoders.ctc_alignment import DISTRIBUTED_REFUSAL
+            raise Exception(DISTRIBUTED_REFUSAL)
         if not distributed or not parallel.collectives_on():
             return self._run_sorted(audio_list, sample_rate, hints, list(range(len(audio_list))), decode_all_frames, batch_size,
-                                    as_tokens=False)
+                                    as_tokens=False, timestamps=timestamps)
         shards = parallel.length_balanced_shards(hints, world)
         mine = shards[rank]
         local = self._run_sorted(audio_list, sample_rate, hints, mine, decode_all_frames, batch_size, as_tokens=True)
@@ -592,12 +718,14 @@ class MASRPredictor:
         tok, nt, sc = parallel.gather_sharded_results(tok, nt, sc, shards, len(audio_list))
         return [{'text': self._text(tok[i, :nt[i]]), 'score': float(sc[i])} for i in range(len(audio_list))]
 
-    def predict_batch_deferred(self, audio_list, sample_rate=16000):
+    def predict_batch_deferred(self, audio_list, sample_rate=16000, timestamps=False):
         """ONE device pass over ``audio_list`` launched, nothing waited for: returns a function that -- when called -- waits for the
         pass and returns [{'text', 'score'}] in input order.  What a serving loop calls for the batch it has formed BEFORE it
         collects the previous one: staging, upload and launches of batch k + 1 then run under the device work of batch k, and
         consecutive calls alternate over the engine's two lanes (not with the prefix search on the GPU, whose launches already
-        run beside the next pass).  The reference serves one request at a time (infer_server.py:48-71)."""
+        run beside the next pass).  The reference serves one request at a time (infer_server.py:48-71).
+        ``timestamps=True``: every result gains ``'tokens'`` (see ``predict``); the pass stays deferred -- ``ctc_greedy`` aligns
+        behind its collapse, the other decoders align when the function is called and their hypotheses are known."""
         eng = self.predictor.engine
         dec = self.beam_search_decoder if self.configs.decoder == 'ctc_beam_search' else None
         gpu_search = dec is not None and getattr(dec, 'use_gpu_search', False) and \
@@ -618,12 +746,12 @@ class MASRPredictor:
             eng.select_lane(lane)
         try:
             with torch.cuda.stream(stream):
-                return self._predict_local(None, defer=True, began=began)
+                return self._predict_local(None, defer=True, began=began, timestamps=timestamps)
         finally:
             if lane:
                 eng.select_lane(0)
 
-    def _run_sorted(self, audio_list, sample_rate, hints, which, decode_all_frames, batch_size, as_tokens):
+    def _run_sorted(self, audio_list, sample_rate, hints, which, decode_all_frames, batch_size, as_tokens, timestamps=False):
         """decode ``audio_list[i] for i in which`` in length-sorted device passes (cut shortest first, ties in input order -- the
         batches ``evaluate`` forms from a duration-sorted manifest); results in the order of ``which``.  Pipeline depth 2:
         pass k is launched (its prefix search on a side stream), then pass k - 1 is collected and its audio dropped."""
@@ -739,7 +867,7 @@ class MASRPredictor:
             try:
                 with torch.cuda.stream(lane_streams[lane]):
                     res = self._predict_local(None, decode_all_frames, as_tokens, defer=True, hold_search=group_utts > 0,
-                                              began=began.pop(k))
+                                              began=began.pop(k), timestamps=timestamps)
             finally:
                 if lane:
                     eng.select_lane(0)
