@@ -326,7 +326,7 @@ struct FfnHead {
                                // until the split reduction, which then reads xout and writes x
     int norm;                  // 0 = LayerNorm, 1 = folded BatchNorm: y = silu(conv * lnw[c] + lnb[c]), no row statistics
 };
-// One FFN call, from ffn()'s call sites (engine.hip) to the launchers.  ffn_plan.h chooses the launcher; ffn() hands it the weights
+// One FFN call, from ffn()'s call sites (the engine's family files; ffn() itself: engine_layers.hip) to the launchers.  ffn_plan.h chooses the launcher; ffn() hands it the weights
 // in that kernel's order (w1 / w2, tail.W, head.W) and only the stages the kernel is to run
 struct FfnArgs {
     float* x = nullptr;           // rows [M, 256], updated in place (ffn(): the engine's residual stream)
@@ -409,7 +409,7 @@ inline void launch_ffn_coop(const FfnArgs&, hipStream_t) {}
 void launch_ffn_reduce(const FfnArgs& a, hipStream_t s, const float* xin = nullptr);
 
 // Fragment-ordered weight copies, one layout per packing routine: the engine keeps every copy it has built under
-// (layout, device pointer of the source weights) -- engine.hip packed_of()
+// (layout, device pointer of the source weights) -- engine_encoder.h packed_of()
 enum PackLayout {
     PACK_FFN_PC,        // launch_pack_ffn_pc: W1 | W2 of an FFN, keyed by W1
     PACK_ROWS_PC,       // launch_pack_rows_pc: [N, 256] rows, N rounded up to a multiple of 256
@@ -612,7 +612,7 @@ void launch_step_result(const int* tok, const float* score, const int* enc_lens,
 // ---- features ------------------------------------------------------------------------------
 size_t fbank_gain_scratch_floats(int B);   // size of gain_scratch ([B] gains + partial sums)
 // use_db: 0 = no dB normalisation, 1 = gains computed on the device, 2 = gains supplied in gain_scratch[0 .. B)
-// tables of the fbank front-end (engine.hip build_fbank_tables): povey window [400]; mel weights transposed [16 taps][80] (tap i of
+// tables of the fbank front-end (engine_frontend.hip build_fbank_tables): povey window [400]; mel weights transposed [16 taps][80] (tap i of
 // filter m = bin mel_lo[m] + i, zero past the filter's last bin); W512^k (k <= 256) for the real-split pass; twr4 [3 passes][3][64]:
 // the twiddles of the radix-4 passes Ns = 4, 16, 64 per lane
 struct FbankTables {

@@ -701,7 +701,7 @@ void launch_frame_counts(const int* nsamp, int B, int* nfr, int* nenc, int halve
     hipLaunchKernelGGL(frame_counts_kernel, dim3((B + 63) / 64), dim3(64), 0, s, nsamp, B, nfr, nenc, halve, input_layer);
 }
 
-// feature lengths -> lengths in conv2d units for a front-end of subsampling rate r: 4 * ceil(len / r) (engine.hip sub_lens)
+// feature lengths -> lengths in conv2d units for a front-end of subsampling rate r: 4 * ceil(len / r) (engine_layers.hip sub_lens)
 __global__ void sub_lens_kernel(const int* __restrict__ lens, int B, int rate, int* __restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) out[b] = 4 * ((max(lens[b], 0) + rate - 1) / rate);

@@ -1,11 +1,24 @@
 // libmasr_hip.so -- what the engine's translation units share: the error plumbing, the engine's state structs and the
 // declarations of the host helpers that cross a file boundary.  Private to csrc/ (the public C ABI is include/masr_hip.h).
-//   engine.hip               error state, weight store, the encoders of the four model families, CTC head, feature front ends,
-//                            streams, single ops, debug and profile calls
+//   engine.hip               error state, weight store, create / load / finalize and the encode calls as dispatchers, streams, lanes
+//   engine_layers.hip        what the attention families share: GEMM and row-block calls, FFN block, front-end, conv module,
+//                            attention projections, finalize pieces, chunk-step tables
+//   engine_conformer.hip     Conformer: finalize (also the Efficient Conformer's), fused and width-generic forward, chunk step
+//   engine_efficient.hip     Efficient Conformer: forward, chunk step
+//   engine_squeezeformer.hip Squeezeformer: finalize, forward, chunk step
+//   engine_ds2.hip           DeepSpeech2: finalize, forward, chunk step
+//   engine_ctc.hip           CTC head, collapse, top-k, prefix beam search on the device
+//   engine_frontend.hip      fbank / MFCC / linear features, resampling, masr_transcribe_*
+//   engine_ops.hip           single ops of the tests, debug switches, profile calls
 //   engine_attdecoder.hip    attention decoder: finalize, rescoring, autoregressive search (kernels: decoder.hip, decoder_step.hip)
 //   ctc_align.hip            forced alignment: kernel and masr_ctc_align
-// A helper that only one file uses stays static (or in an anonymous namespace) there and is not declared here.
+// A helper that only one file uses stays static (or in an anonymous namespace) there and is not declared here; what only the
+// encoder files share (engine_layers.hip's helpers, the families' entry points) is declared in engine_encoder.h.
 #pragma once
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
 #include <algorithm>
 #include <map>
 #include <string>
@@ -401,6 +414,9 @@ struct CallGuard {
 
 // ---- engine.hip ---------------------------------------------------------------------------------------------------------------
 int get(masr_engine* e, const std::string& name, std::vector<int64_t> shape, const HostTensor** out);
+// ---- engine_frontend.hip (masr_create builds the tables: a weight-less engine can already run the feature front-end) -----------
+int build_fbank_tables(masr_engine* e);
+// ---- engine_layers.hip --------------------------------------------------------------------------------------------------------
 void gemm(masr_engine* e, hipStream_t s, const float* A, int lda, const float* W, const float* bias, float* C, int ldc,
           int M, int N, int K, int act, float alpha, const float* R, int ldr, int kind = PROF_GEMM,
           const int* lens = nullptr, int mask_tp = 0);

@@ -1,4 +1,4 @@
-// Which kernel of the fused FFN family one ffn() call launches (engine.hip), as a pure function of the sizes, of what the call
+// Which kernel of the fused FFN family one ffn() call launches (engine_layers.hip), as a pure function of the sizes, of what the call
 // asks for and of the masr_debug_set switches.  Host only (no HIP include): ffn() evaluates it on knobs(), masr_ffn_plan
 // (include/masr_hip.h) on a copy of the defaults with overrides, and tests/test_ffn_plan_cpu.py holds it to tests/ffn_plan.py.
 #pragma once

@@ -96,7 +96,7 @@ def test_fixture_equals_the_live_reference():
 
 
 def _fold(w, b, mean, var):
-    """masr_finalize's fold (engine.hip, `if (e->conv_bn)`), float32 throughout: invstd = 1 / sqrtf(var + 1e-5f), scale = w * invstd,
+    """masr_finalize's fold (engine_conformer.hip finalize_conformer, `if (e->conv_bn)`), float32 throughout: invstd = 1 / sqrtf(var + 1e-5f), scale = w * invstd,
     shift = fmaf(-mean, scale, b) (one rounding: the product of two float32 is exact in float64)"""
     invstd = (np.float32(1) / np.sqrt(var + np.float32(1e-5))).astype(np.float32)
     scale = (w * invstd).astype(np.float32)

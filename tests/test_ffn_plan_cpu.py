@@ -1,4 +1,4 @@
-"""CPU: masr_ffn_plan -- the function ffn() in masr_amd/csrc/engine.hip chooses its kernel with (csrc/ffn_plan.h), evaluated by
+"""CPU: masr_ffn_plan -- the function ffn() in masr_amd/csrc/engine_layers.hip chooses its kernel with (csrc/ffn_plan.h), evaluated by
 the library on the switch defaults plus overrides -- against three independent statements:
 
   1. the split rule of tests/ffn_plan.py, over every accepted d_ff up to 4096, 1 ... 300 row blocks and four cut-overs;

@@ -5,7 +5,7 @@ Offline Conformer, d_model 256, two blocks; 3 utterances of 403 / 371 / 290 feat
 of 32: the sequence boundaries (rows 100, 200) fall inside row blocks and the last block holds 12 rows.  By default such a batch runs
 the d_ff-split FFN launches (10 < ffn_split_blocks = 192), which carry neither stage; with ffn_split_blocks = 0 every layer runs
 one full-d_ff launch with the QKV tail stage (profile kind 6) and one with the conv-module head stage (kind 7): by ffn() and
-masr_encode_full in engine.hip, one launch of each kind per block with ffn_split_blocks = 0 and none without.  few_rows_path needs
+encode_full_conformer in engine_conformer.hip, one launch of each kind per block with ffn_split_blocks = 0 and none without.  few_rows_path needs
 no change: the few-rows layer path is taken below min(rowgemm_small_blocks, ffn_split_blocks) row blocks, which is 0 here."""
 import pytest
 import torch

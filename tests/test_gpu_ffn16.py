@@ -2,7 +2,7 @@
 key 39 = 0 selects the 32-row kernel.  Every dot product is the same fmaf chain in both (tests/test_gpu_mfma_order.py), so the
 encoder output and the CTC probabilities must be BIT-identical with the switch on and off -- for the QKV tail and the conv-module
 head (offline Conformer, streaming True and False), the Efficient Conformer (planar QKV tail), ragged batches whose last 16-row
-block is partial and whose sequences start inside blocks, and M on both sides of the cut-overs of ffn() in engine.hip.
+block is partial and whose sequences start inside blocks, and M on both sides of the cut-overs of ffn() in engine_layers.hip.
 
 Full launches (nsplit = 1) need >= 129 32-row blocks: below that ffn() splits d_ff (nsplit = min(d_ff / 128, 256 / blocks) > 1).
 The conv-module head rides on the FFN launch from ffn_split_blocks = 192 blocks (masr_debug_set key 13) on."""

@@ -1,4 +1,4 @@
-"""The Conformer at output_size 512 / attention_heads 8 on the GPU (the width-generic path of engine.hip + wide.hip): full-context
+"""The Conformer at output_size 512 / attention_heads 8 on the GPU (the width-generic path of engine_conformer.hip + wide.hip): full-context
 forwards and chunk steps under the float64 budget rule of tests/budget.py (C = 8, valid frames, truth = the oracle in float64
 with heads = 8), parity with the reference fixture tests/golden/conformer_wide_v50.npz (tools/make_wide_golden.py; max abs < 1e-3,
 the bound of every fixture test of test_gpu_parity.py), two sessions out of phase, both lanes, and the facade."""
