@@ -175,6 +175,64 @@ class BeamSearchDecoder:
                 return pool.pop(i)
         return torch.empty(max(n, 1 << 15), dtype=torch.int32, pin_memory=True)
 
+    def _results(self, toks, lens, scores, want_tokens):
+        """host arrays of a search -> [(token ids, score)] (what a multi-GPU caller gathers instead of text, and what is aligned)
+        or [(score, text)]"""
+        ids = [toks[i, :lens[i]].tolist() for i in range(len(lens))]
+        if want_tokens:
+            return [(ids[i], float(scores[i])) for i in range(len(ids))]
+        return [(float(scores[i]), self._text(ids[i])) for i in range(len(ids))]
+
+    def _unpacked(self, rows, max_len, want_tokens):
+        """packed host rows [B, max_len + 2] int32 = tokens | length | score bits -> results"""
+        return self._results(rows[:, :max_len], rows[:, max_len].copy(), rows[:, max_len + 1].copy().view(np.float32), want_tokens)
+
+    def _search_gpu(self, eng, cand, frames, B, Ts):
+        """masr_beam_search_gpu_lm over the candidates ``cand`` = (idx, logp, cnt, blp, K) of ``_candidates`` on the current stream
+        -> (packed rows [B, max_len + 2] on the device, max_len, what must stay alive until they are read)"""
+        idx, logp, cnt, blp, K = cand
+        max_len = max(Ts, 1)
+        fr = eng.to_device(frames)
+        toks = torch.zeros(B, max_len, dtype=torch.int32, device=eng.device)
+        lens = torch.zeros(B, dtype=torch.int32, device=eng.device)
+        scores = torch.zeros(B, dtype=torch.float32, device=eng.device)
+        check(self._lib.masr_beam_search_gpu_lm(eng.h, C.c_void_p(idx.data_ptr()), C.c_void_p(logp.data_ptr()),
+                                                C.c_void_p(cnt.data_ptr()), C.c_void_p(fr.data_ptr()), B, Ts, K,
+                                                self.beam_size, self.blank_id, *self._lm_args(), self._ptr(blp),
+                                                C.c_void_p(toks.data_ptr()), max_len,
+                                                C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        packed = torch.cat([toks, lens[:, None], scores.view(torch.int32)[:, None]], 1)       # one contiguous copy back
+        return packed, max_len, (idx, logp, cnt, blp, fr, toks, lens, scores)
+
+    def _search_host(self, idx, logp, cnt, blp, frames, B, Ts, K, want_tokens):
+        """masr_beam_search_batch_lm on ``num_processes`` host threads over host candidates -> results"""
+        max_len = max(Ts, 1)
+        toks = np.zeros((B, max_len), np.int32)
+        lens = np.zeros(B, np.int32)
+        scores = np.zeros(B, np.float32)
+        fr = np.ascontiguousarray(frames, np.int32)
+        rc = self._lib.masr_beam_search_batch_lm(idx.ctypes.data_as(C.c_void_p), logp.ctypes.data_as(C.c_void_p),
+                                                 cnt.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p), B, Ts, K,
+                                                 self.beam_size, self.blank_id, self.num_processes, *self._lm_args(),
+                                                 self._ptr(blp), toks.ctypes.data_as(C.c_void_p), max_len,
+                                                 lens.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise _lib.MasrError('masr_beam_search_batch failed')
+        return self._results(toks, lens, scores, want_tokens)
+
+    def _say_host_search(self, beyond_gpu=False):
+        """once per decoder: why the prefix search runs on host threads"""
+        if getattr(self, '_said_host', False):
+            return
+        if self._ext_scorer is not None and not self._ext_scorer.is_character_based:
+            self._said_host = True
+            logger.info('masr_amd BeamSearchDecoder: word-based language model -> prefix search on host threads')
+        elif beyond_gpu:
+            self._said_host = True
+            logger.warning(f'masr_amd BeamSearchDecoder: beam_size={self.beam_size} x cutoff_top_n={self.cutoff_top_n} is beyond the '
+                           f'GPU search (LDS), using {self.num_processes} host threads')
+
     def _batch_collect(self, pending, want_tokens=False):
         """results of a ``_batch(..., defer=True)`` launch.  The host waits for the EVENT behind this pass's search, then copies
         the packed rows (tokens | length | score bits, int32) back on the library's copy stream and waits for that copy only.
@@ -191,13 +249,9 @@ class BeamSearchDecoder:
             ev = torch.cuda.Event()
             ev.record()
         ev.synchronize()
-        r = host[:B * (max_len + 2)].view(B, max_len + 2).numpy()
-        toks, lens, scores = r[:, :max_len], r[:, max_len].copy(), r[:, max_len + 1].copy().view(np.float32)
-        res_tok = [toks[i, :lens[i]].tolist() for i in range(B)]
+        res = self._unpacked(host[:B * (max_len + 2)].view(B, max_len + 2).numpy(), max_len, want_tokens)
         self._pin_free.append(host)
-        if want_tokens:
-            return [(res_tok[i], float(scores[i])) for i in range(B)]
-        return [(float(scores[i]), self._text(res_tok[i])) for i in range(B)]
+        return res
 
     def _batch(self, probs_list, defer=False, want_tokens=False, frames=None):
         """``defer=True`` (device-resident probabilities, GPU search): launch pruning + search on the current torch stream and
@@ -211,7 +265,6 @@ class BeamSearchDecoder:
             B, Ts, V = stacked.shape
             frames = np.asarray(frames, np.int32)
             assert frames.shape == (B,) and (B == 0 or int(frames.max()) <= Ts)
-            probs_list = stacked
         else:
             B = len(probs_list)
             frames = np.array([p.shape[0] for p in probs_list], np.int32)
@@ -223,107 +276,30 @@ class BeamSearchDecoder:
                 stacked = np.zeros((B, Ts, V), np.float32)
             for i, p in enumerate(probs_list):
                 stacked[i, :p.shape[0]] = p
-        max_len = max(Ts, 1)
         if B and Ts and self.use_gpu_search and self.gpu_search_supported(Ts, V):
             # whole search on the device: candidates never leave HBM, one workgroup per utterance
             eng = runtime.aux_engine(stacked.device if torch.is_tensor(stacked) else None)
-            idx, logp, cnt, blp, K = self._candidates(stacked.reshape(B * Ts, V), to_host=False)
-            fr = eng.to_device(frames)
-            toks = torch.zeros(B, max_len, dtype=torch.int32, device=eng.device)
-            lens = torch.zeros(B, dtype=torch.int32, device=eng.device)
-            scores = torch.zeros(B, dtype=torch.float32, device=eng.device)
-            check(self._lib.masr_beam_search_gpu_lm(eng.h, C.c_void_p(idx.data_ptr()), C.c_void_p(logp.data_ptr()),
-                                                    C.c_void_p(cnt.data_ptr()), C.c_void_p(fr.data_ptr()), B, Ts, K,
-                                                    self.beam_size, self.blank_id, *self._lm_args(), self._ptr(blp),
-                                                    C.c_void_p(toks.data_ptr()), max_len,
-                                                    C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
-                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            packed, max_len, keep = self._search_gpu(eng, self._candidates(stacked.reshape(B * Ts, V), to_host=False), frames, B, Ts)
             if defer:                      # nothing has been synchronised: _batch_collect() fetches the result later
-                packed = torch.cat([toks, lens[:, None], scores.view(torch.int32)[:, None]], 1)       # one contiguous copy back
                 done = torch.cuda.Event()
                 done.record()
-                return ('gpu', B, max_len, packed, (stacked, idx, logp, cnt, blp, fr, probs_list, toks, lens, scores), done)
-            toks, lens, scores = toks.cpu().numpy(), lens.cpu().numpy(), scores.cpu().numpy()
-            if want_tokens:          # (token ids, score): what a multi-GPU caller gathers instead of text
-                return [(toks[i, :lens[i]].tolist(), float(scores[i])) for i in range(B)]
-            return [(float(scores[i]), self._text(toks[i, :lens[i]])) for i in range(B)]
+                return ('gpu', B, max_len, packed, (stacked, probs_list) + keep, done)
+            return self._unpacked(packed.cpu().numpy(), max_len, want_tokens)
         if defer:
             raise Exception('deferred batch search needs the GPU search (device-resident probabilities within its limits)')
-        if self._ext_scorer is not None and not self._ext_scorer.is_character_based and not getattr(self, '_said_host', False):
-            self._said_host = True
-            logger.info('masr_amd BeamSearchDecoder: word-based language model -> prefix search on host threads')
-        elif self.use_gpu_search and B and Ts and not getattr(self, '_said_host', False):
-            self._said_host = True
-            logger.warning(f'masr_amd BeamSearchDecoder: beam_size={self.beam_size} x cutoff_top_n={self.cutoff_top_n} is beyond the '
-                           f'GPU search (LDS), using {self.num_processes} host threads')
+        self._say_host_search(beyond_gpu=bool(self.use_gpu_search and B and Ts))
         idx, logp, cnt, blp, K = self._candidates(stacked.reshape(B * Ts, V))
-        toks = np.zeros((B, max_len), np.int32)
-        lens = np.zeros(B, np.int32)
-        scores = np.zeros(B, np.float32)
-        rc = self._lib.masr_beam_search_batch_lm(idx.ctypes.data_as(C.c_void_p), logp.ctypes.data_as(C.c_void_p),
-                                                 cnt.ctypes.data_as(C.c_void_p), frames.ctypes.data_as(C.c_void_p), B, Ts, K,
-                                                 self.beam_size, self.blank_id, self.num_processes, *self._lm_args(),
-                                                 self._ptr(blp), toks.ctypes.data_as(C.c_void_p), max_len,
-                                                 lens.ctypes.data_as(C.c_void_p),
-                                                 scores.ctypes.data_as(C.c_void_p))
-        if rc != 0:
-            raise _lib.MasrError('masr_beam_search_batch failed')
-        if want_tokens:
-            return [(toks[i, :lens[i]].tolist(), float(scores[i])) for i in range(B)]
-        return [(float(scores[i]), self._text(toks[i, :lens[i]])) for i in range(B)]
+        return self._search_host(idx, logp, cnt, blp, frames, B, Ts, K, want_tokens)
 
-    # ---- one search for the utterances of several device passes ---------------------------------------------------------------
+    # ---- host-thread search of a device pass, deferred ---------------------------------------------------------------------------
     def prune_padded(self, probs, frames):
         """vocabulary pruning of ONE device pass (padded probabilities [B, Ts, V] on the device, ``frames[i]`` valid rows) on the
-        current stream; the probabilities are not needed afterwards.  -> a part for ``search_pruned``."""
+        current stream; the probabilities are not needed afterwards.  -> a part for ``search_host_deferred``."""
         B, Ts, V = probs.shape
         idx, logp, cnt, blp, K = self._candidates(probs.reshape(B * Ts, V), to_host=False)
         return {'idx': idx.view(B, Ts, K), 'logp': logp.view(B, Ts, K), 'cnt': cnt.view(B, Ts), 'blp': None if blp is None else blp.view(B, Ts),
                 'frames': np.asarray(frames, np.int32), 'B': B, 'Ts': Ts, 'K': K}
 
-    def search_pruned(self, parts):
-        """ONE prefix-search launch over the utterances of every part (one workgroup per utterance): the candidates of the passes
-        are gathered into common [B_total, T_max, K] arrays (a few MB) and searched together, on the current stream.  Returns a
-        handle for ``_batch_collect``; results come back in the order of the parts.  (Round 6: a search that runs BESIDE an
-        encoder pass holds 32 compute units for milliseconds, and every row-block launch of that encoder pass -- sized for one
-        round of 256 -- then takes two rounds; searched together behind the encoders of the group, all utterances advance at the
-        kernel's stand-alone rate and the call is encoders + the longest utterance's search.)"""
-        eng = runtime.aux_engine(parts[0]['idx'].device)
-        Bt, Tm, K = sum(p['B'] for p in parts), max(p['Ts'] for p in parts), parts[0]['K']
-        if len(parts) == 1:
-            p = parts[0]
-            idx, logp, cnt, blp = p['idx'], p['logp'], p['cnt'], p['blp']
-        else:
-            idx = torch.zeros(Bt, Tm, K, dtype=torch.int32, device=eng.device)
-            logp = torch.zeros(Bt, Tm, K, dtype=torch.float32, device=eng.device)
-            cnt = torch.zeros(Bt, Tm, dtype=torch.int32, device=eng.device)
-            blp = None if parts[0]['blp'] is None else torch.zeros(Bt, Tm, dtype=torch.float32, device=eng.device)
-            lo = 0
-            for p in parts:
-                idx[lo:lo + p['B'], :p['Ts']] = p['idx']
-                logp[lo:lo + p['B'], :p['Ts']] = p['logp']
-                cnt[lo:lo + p['B'], :p['Ts']] = p['cnt']
-                if blp is not None:
-                    blp[lo:lo + p['B'], :p['Ts']] = p['blp']
-                lo += p['B']
-        frames = np.concatenate([p['frames'] for p in parts]).astype(np.int32)
-        fr = eng.to_device(frames)
-        max_len = max(Tm, 1)
-        toks = torch.zeros(Bt, max_len, dtype=torch.int32, device=eng.device)
-        lens = torch.zeros(Bt, dtype=torch.int32, device=eng.device)
-        scores = torch.zeros(Bt, dtype=torch.float32, device=eng.device)
-        check(self._lib.masr_beam_search_gpu_lm(eng.h, C.c_void_p(idx.data_ptr()), C.c_void_p(logp.data_ptr()),
-                                                C.c_void_p(cnt.data_ptr()), C.c_void_p(fr.data_ptr()), Bt, Tm, K,
-                                                self.beam_size, self.blank_id, *self._lm_args(), self._ptr(blp),
-                                                C.c_void_p(toks.data_ptr()), max_len,
-                                                C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
-                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        packed = torch.cat([toks, lens[:, None], scores.view(torch.int32)[:, None]], 1)
-        done = torch.cuda.Event()
-        done.record()
-        return ('gpu', Bt, max_len, packed, (idx, logp, cnt, blp, fr, toks, lens, scores, parts), done)
-
-    # ---- host-thread search of a device pass, deferred ---------------------------------------------------------------------------
     def search_host_deferred(self, probs, frames, want_tokens=False):
         """The host-thread prefix search (word-based scorers, sizes beyond the GPU kernel) of ONE device pass without stalling the
         device: the vocabulary pruning is queued on the current stream right behind the pass's CTC head, and a function is
@@ -334,17 +310,13 @@ class BeamSearchDecoder:
         part = self.prune_padded(probs, frames)
         done = torch.cuda.Event()
         done.record()
-        if self._ext_scorer is not None and not self._ext_scorer.is_character_based and not getattr(self, '_said_host', False):
-            self._said_host = True
-            logger.info('masr_amd BeamSearchDecoder: word-based language model -> prefix search on host threads')
+        self._say_host_search()
 
         def collect():
-            B, Ts, K = part['B'], part['Ts'], part['K']
             dev = [part['idx'].view(-1), part['logp'].view(-1).view(torch.int32), part['cnt'].view(-1)]
             if part['blp'] is not None:
                 dev.append(part['blp'].view(-1).view(torch.int32))
-            total = sum(t.numel() for t in dev)
-            host = self._pinned_out(total)
+            host = self._pinned_out(sum(t.numel() for t in dev))
             done.synchronize()
             with torch.cuda.stream(runtime.aux_engine(part['idx'].device).side_stream(3)):
                 at, views = 0, []
@@ -355,24 +327,12 @@ class BeamSearchDecoder:
                 ev = torch.cuda.Event()
                 ev.record()
             ev.synchronize()
-            idx, logp, cnt = views[0], views[1].view(np.float32), views[2]
             blp = views[3].view(np.float32) if part['blp'] is not None else None
-            max_len = max(Ts, 1)
-            toks = np.zeros((B, max_len), np.int32)
-            lens = np.zeros(B, np.int32)
-            scores = np.zeros(B, np.float32)
-            fr = np.ascontiguousarray(part['frames'], np.int32)
-            rc = self._lib.masr_beam_search_batch_lm(idx.ctypes.data_as(C.c_void_p), logp.ctypes.data_as(C.c_void_p),
-                                                     cnt.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p), B, Ts, K,
-                                                     self.beam_size, self.blank_id, self.num_processes, *self._lm_args(),
-                                                     self._ptr(blp), toks.ctypes.data_as(C.c_void_p), max_len,
-                                                     lens.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p))
-            self._pin_free.append(host)
-            if rc != 0:
-                raise _lib.MasrError('masr_beam_search_batch failed')
-            if want_tokens:
-                return [(toks[i, :lens[i]].tolist(), float(scores[i])) for i in range(B)]
-            return [(float(scores[i]), self._text(toks[i, :lens[i]])) for i in range(B)]
+            try:
+                return self._search_host(views[0], views[1].view(np.float32), views[2], blp, part['frames'], part['B'], part['Ts'],
+                                         part['K'], want_tokens)
+            finally:
+                self._pin_free.append(host)
         return collect
 
     def decode_chunk(self, probs, logits_lens):

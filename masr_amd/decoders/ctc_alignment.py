@@ -21,7 +21,6 @@ MAX_TOKENS = 1024           # MASR_ALIGN_MAX_TOKENS: the longest hypothesis the 
 
 DISTRIBUTED_REFUSAL = ("timestamps=True does not run on the sharded path (distributed=True): the all-gather carries token ids and "
                        "scores only; call predict_batch with distributed=False on every rank's own utterances")
-HELD_SEARCH_REFUSAL = "timestamps=True does not run with MASR_BEAM_GROUP (held prefix searches): unset it"
 
 
 def frames_to_times(start, end, peak, reduction, hop_samples, sample_rate, duration_s, vocab):

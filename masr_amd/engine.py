@@ -1,5 +1,6 @@
 """Python handle on the HIP engine (libmasr_hip.so).  torch is used only for device memory,
 streams and host<->device copies; all arithmetic of the hot path runs in the HIP kernels."""
+import contextlib
 import ctypes as C
 import math
 
@@ -8,6 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import MasrConfig, check
+from .pinned import PinnedRing
 
 
 def _ptr(t):
@@ -402,6 +404,8 @@ class HipEngine:
         h = C.c_void_p()
         check(self.lib.masr_create(C.byref(cfg), C.byref(h)))
         self.h = h
+        self.lane = 0
+        self._up_ring = PinnedRing(8, min_numel=64, events=True)          # ``to_device``
         self.has_weights = state_dict is not None
         self.has_decoder = False
         self.max_pos = int(max_pos)
@@ -545,6 +549,20 @@ class HipEngine:
         check(self.lib.masr_select_lane(self.h, int(lane)))
         self.lane = int(lane)
 
+    @contextlib.contextmanager
+    def on_lane(self, lane, stream):
+        """the calls inside run on workspace set ``lane`` and on ``stream``; afterwards the lane that was active is selected again
+        (every caller outside such a block works on lane 0)"""
+        active = self.lane
+        if lane != active:
+            self.select_lane(lane)
+        try:
+            with torch.cuda.stream(stream):
+                yield
+        finally:
+            if lane != active:
+                self.select_lane(active)
+
     def to_host(self, t):
         """small device tensor -> numpy through a pinned buffer, waiting for THIS stream only.  (``tensor.cpu()`` copies to
         pageable memory, which the HIP runtime serialises against every stream of the device: a prefix search running on a side
@@ -566,20 +584,10 @@ class HipEngine:
         waited for before the slot is rewritten -- a copy queued on a side stream behind a long prefix search keeps its source
         however many uploads follow."""
         t = torch.from_numpy(np.ascontiguousarray(a).reshape(-1))
-        slot = self.__dict__.setdefault('_up_ring', {}).setdefault(t.dtype, {'bufs': [None] * 8, 'events': [None] * 8, 'turn': 0})
-        k = slot['turn']
-        slot['turn'] = (k + 1) & 7
-        if slot['events'][k] is not None:
-            slot['events'][k].synchronize()
-        buf = slot['bufs'][k]
-        if buf is None or buf.numel() < t.numel():
-            buf = slot['bufs'][k] = torch.empty(max(t.numel(), 64), dtype=t.dtype, pin_memory=True)
-        view = buf[:t.numel()]
-        view.copy_(t)
-        out = view.view(np.shape(a)).to(self.device, non_blocking=True)
-        ev = slot['events'][k] or torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        slot['events'][k] = ev
+        slot = self._up_ring.take(t.numel(), t.dtype)
+        slot.buf.copy_(t)
+        out = slot.buf.view(np.shape(a)).to(self.device, non_blocking=True)
+        slot.record(torch.cuda.current_stream(self.device))
         return out
 
     def host_gains(self, samples, n_samples, target_db, max_gain_db=300.0):

@@ -24,15 +24,15 @@ SHARP = os.environ.get('MASR_PROFILE_SHARP') == '1'
 PASS = os.environ.get('MASR_BENCH_BEAM_PASS', 'balanced')
 PASS = PASS if PASS == 'balanced' else ([int(v) for v in PASS.split(',')] if ',' in PASS else int(PASS))
 pred = bench.facade('squeezeformer', 'ctc_beam_search', 0, streaming=False, beam_conf=conf, head_gain=bench.SHARP_HEAD_GAIN if SHARP else None)
-print(f'passes: {PASS}, sharp head: {SHARP}, side streams: {os.environ.get("MASR_BEAM_SIDES", "3")}, group: {os.environ.get("MASR_BEAM_GROUP", "4")}')
+print(f'passes: {PASS}, sharp head: {SHARP}, side streams: {os.environ.get("MASR_BEAM_SIDES", "2")}')
 marks = []
-orig_local = pred._predict_local
+orig_launch = pred._passes.launch             # masr_amd/offline_pass.py: one device pass -> the function that collects it
 
 
-def local(segs, *a, **k):
+def launch(began, *a, **k):
     t0 = time.perf_counter()
-    fetch = orig_local(segs, *a, **k)
-    tag = 'pass of %d (longest %.1f s)' % (len(segs), max(s.num_samples for s in segs) / 16000)
+    fetch = orig_launch(began, *a, **k)
+    tag = 'pass of %d (longest %.1f s)' % (began['count'], max(began['n'], default=0) / 16000)
     marks.append(('encoder enqueued: ' + tag, t0, time.perf_counter()))
 
     def timed(f):
@@ -42,12 +42,10 @@ def local(segs, *a, **k):
             marks.append(('collected ' + tag, t1, time.perf_counter()))
             return r
         return timed_fetch
-    if isinstance(fetch, tuple) and fetch[0] == 'held':          # round 6: pruned here, searched per group of passes (MASR_BEAM_GROUP)
-        return fetch
     return timed(fetch)
 
 
-pred._predict_local = local
+pred._passes.launch = launch
 for rep in range(3):
     pred.predict_batch(audio, batch_size=PASS)
 for rep in range(2):

@@ -32,9 +32,13 @@ for name, batch in (('b32', audio), ('b1', [wav])):
     n = np.array([s.num_samples for s in segs], np.int32)
     print(name, 'predict_batch            %.3f ms' % timed(lambda: pred.predict_batch(batch)))
     print(name, '  _length_hint + _load   %.3f ms' % timed(lambda: [pred._length_hint(a, 16000) for a in batch] and [pred._load_audio(a, 16000) for a in batch]))
-    print(name, '  _stage_batch           %.3f ms' % timed(lambda: pred._stage_batch(segs, n)))
-    print(name, '  _prepare (stage+gains) %.3f ms' % timed(lambda: pred._prepare(segs, n, True, -20.0)))
-    xs, ns, gain = pred._prepare(segs, n, True, -20.0)
+    passes = pred._passes                    # masr_amd/offline_pass.py
+
+    def prepare():
+        return passes.prepare_finish(passes.prepare_begin(segs, n, True), -20.0)
+    print(name, '  stage_batch            %.3f ms' % timed(lambda: passes.stage_batch(segs, n)))
+    print(name, '  prepare (stage+gains)  %.3f ms' % timed(prepare))
+    xs, ns, gain = prepare()
     print(name, '  transcribe_rows (GPU)  %.3f ms' % timed(lambda: eng.transcribe_rows(xs, ns, True, -20.0, gain_in=gain)))
     print(name, '  _predict_local         %.3f ms' % timed(lambda: pred._predict_local(segs)))
     rows = eng.transcribe_rows(xs, ns, True, -20.0, gain_in=gain).cpu().numpy()

@@ -42,11 +42,12 @@ def wrap(obj, name, label=None):
 
 
 wrap(pred, '_load_audio')
-wrap(pred, '_stage_batch')
-wrap(pred, '_prepare')
+wrap(pred._passes, 'stage_batch')                   # masr_amd/offline_pass.py: the steps of one device pass
+wrap(pred._passes, 'prepare_begin')
+wrap(pred._passes, 'prepare_finish')
 wrap(eng, 'host_gains')
 wrap(eng, 'transcribe_rows')
-wrap(pred, '_predict_local')
+wrap(pred._passes, 'launch')
 for _ in range(3):
     pred.predict_batch(audio, batch_size=32)
 torch.cuda.synchronize()
