@@ -191,6 +191,24 @@ int masr_argmax_rows(masr_engine* e, const float* probs_dev, int32_t M, int32_t 
 int masr_ctc_align(masr_engine* e, const float* post_dev, int32_t input_is_log, int32_t B, int32_t Tp, int32_t V,
                    const int32_t* n_frames_dev, const int32_t* tokens_dev, const int32_t* n_tokens_dev, int32_t Lmax,
                    int32_t* start_dev, int32_t* end_dev, float* peak_dev, float* score_dev, int32_t* status_dev, void* stream);
+/* The same alignment over frames that are NOT contiguous: frame t of utterance b is row frame_row_dev[b, t] of the matrix
+ * rows_dev [n_rows, V] -- the posterior history of streaming sessions, whose chunks land wherever the row pool had room, so that
+ * nothing has to be packed into a dense [B, T', V] batch before it is aligned (the kernel reads L + 1 values per frame; a packed
+ * copy would move whole V-wide rows of every session on every step).
+ *   frame_row_dev [B, Tmax] int64: row numbers in frame order; they need be neither contiguous nor increasing, and a row may
+ *     appear more than once.  Entries behind n_frames[b] are never read.
+ *   A row number outside [0, n_rows) among the n_frames[b] valid frames gives status 2 for THAT utterance (start / end -1,
+ *     peak / score 0) before any of its rows is read; the other utterances are not disturbed.
+ *   Every address made from a row number is 64-bit: n_rows * V * 4 bytes may exceed 2^31.
+ * Everything else -- the trellis, the tie rule, MASR_ALIGN_NEG, input_is_log, the status codes, one workgroup per utterance, the
+ * predecessor workspace ([B, Tmax, 2 Lmax + 1] bytes of the CURRENT lane) -- is masr_ctc_align's: it is the same kernel with
+ * another way to find a frame, and the outputs equal, bit for bit, those of masr_ctc_align on the gathered dense copy.  Refused
+ * alike: Lmax > MASR_ALIGN_MAX_TOKENS, Lmax > Tmax, V > 16384; and n_rows <= 0.  The row number of a frame is fetched once per
+ * frame and workgroup, two frames ahead of its use. */
+int masr_ctc_align_rows(masr_engine* e, const float* rows_dev, int64_t n_rows, int32_t V, int32_t input_is_log,
+                        const int64_t* frame_row_dev, int32_t B, int32_t Tmax, const int32_t* n_frames_dev,
+                        const int32_t* tokens_dev, const int32_t* n_tokens_dev, int32_t Lmax, int32_t* start_dev, int32_t* end_dev,
+                        float* peak_dev, float* score_dev, int32_t* status_dev, void* stream);
 
 /* External n-gram language model scorer of the beam search.  Replaces the `Scorer` of paddlespeech_ctcdecoders (scorer.cpp on
  * KenLM; constructed in masr/decoders/beam_search_decoder.py:29-35, swig_wrapper.py:4-18; parameters alpha / beta of

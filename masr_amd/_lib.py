@@ -93,6 +93,7 @@ SIGNATURES = {
     'masr_encoder_frames': [_P, _I, C.POINTER(_I)],
     'masr_frame_reduction': [_P, C.POINTER(_I)],
     'masr_ctc_align': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
+    'masr_ctc_align_rows': [_P, _P, C.c_int64, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     'masr_engine_info': [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)],
     'masr_stream_open': [_P, _I, C.POINTER(_I)],
     'masr_stream_reset': [_P, _I],

@@ -1,16 +1,22 @@
 """Token timestamps: host side of the CTC forced alignment (``timestamps=True`` of ``MASRPredictor.predict`` / ``predict_batch`` /
-``predict_batch_deferred`` / ``predict_long``).
+``predict_batch_deferred`` / ``predict_long`` / ``predict_stream`` and of ``serving.StreamPool``).
 
 Every model family has a CTC head, so every hypothesis -- whichever decoder produced it, the attention decoders included -- can be
 aligned against the CTC posteriors of its own utterance: masr_ctc_align (csrc/ctc_align.hip, include/masr_hip.h) finds the Viterbi
 path through the trellis of the hypothesis on the GPU and returns, per token, the first and last encoder frame of its state and its
 largest log-probability over those frames.  This module turns those frames into seconds; it needs neither the library nor a GPU.
 
+Streaming sessions (``StreamPool(predictor, timestamps=True)``) keep the CTC head's rows of every session in one device-resident row
+pool and align the hypothesis so far against all frames so far on every step: masr_ctc_align_rows, the same kernel reading its
+frames through a row table.  The functions below serve both: a partial stream is an utterance whose ``duration_s`` is the audio fed
+so far, and its times count from the session's ``open()`` / ``reset()``.
+
 Tie rule of the path (part of the contract, restated by tests/ctc_align_ref.py): predecessors in the order stay, s - 1, s - 2, a
 later one only if strictly greater; at the end the last blank wins a tie against the last token.  ``status`` 0 = aligned, 1 = the
 trellis has no path (fewer frames than tokens + adjacent repeats), 2 = an argument out of range.
 
-Left out: streaming sessions, the sharded (``distributed``) path, ``evaluate``, word grouping and punctuation."""
+Left out: ``ShardedStreamPool`` and the websocket server (streaming timestamps exist on ``StreamPool`` / ``predict_stream`` only),
+second passes on streams, the sharded (``distributed``) path, ``evaluate``, word grouping and punctuation."""
 import math
 
 import numpy as np

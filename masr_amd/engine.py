@@ -741,6 +741,32 @@ class HipEngine:
                                       _stream()))
         return start, end, peak, score, status
 
+    def ctc_align_rows(self, rows, frame_row, n_frames, tokens, n_tokens, input_is_log=False, out=None):
+        """masr_ctc_align_rows on the current stream and the active lane: ``ctc_align`` over frames that are not contiguous.
+        ``rows`` [n_rows, V] float32 (a row pool), ``frame_row`` [B, Tmax] int64: frame t of utterance b is row ``frame_row[b, t]``
+        (any order, entries behind ``n_frames[b]`` are never read; a number outside [0, n_rows) gives status 2 for that utterance);
+        ``n_frames``, ``tokens``, ``n_tokens``, ``input_is_log`` and the packed ``out`` of B * (3 Lmax + 2) int32 as in
+        ``ctc_align``, and the same five views come back, bit for bit what ``ctc_align`` gives on ``rows[frame_row]``.  Nothing is
+        waited for."""
+        n_rows, V = rows.shape
+        B, Tmax = frame_row.shape
+        Lmax = tokens.shape[1]
+        if out is None:
+            out = torch.empty(B * (3 * Lmax + 2), dtype=torch.int32, device=self.device)
+        flat = out.view(-1)
+        n = B * Lmax
+        start, end = flat[:n].view(B, Lmax), flat[n:2 * n].view(B, Lmax)
+        peak = flat[2 * n:3 * n].view(torch.float32).view(B, Lmax)
+        score, status = flat[3 * n:3 * n + B].view(torch.float32), flat[3 * n + B:3 * n + 2 * B]
+        if not (rows.is_contiguous() and frame_row.is_contiguous() and tokens.is_contiguous() and rows.dtype == torch.float32
+                and frame_row.dtype == torch.int64 and tokens.dtype == torch.int32 and n_frames.dtype == torch.int32
+                and n_tokens.dtype == torch.int32):
+            raise ValueError('ctc_align_rows: contiguous float32 rows, int64 frame_row and int32 tokens / n_frames / n_tokens expected')
+        check(self.lib.masr_ctc_align_rows(self.h, _ptr(rows), n_rows, V, 1 if input_is_log else 0, _ptr(frame_row), B, Tmax,
+                                           _ptr(n_frames), _ptr(tokens), _ptr(n_tokens), Lmax, _ptr(start), _ptr(end), _ptr(peak),
+                                           _ptr(score), _ptr(status), _stream()))
+        return start, end, peak, score, status
+
     def frame_reduction(self):
         """masr_frame_reduction: feature frames per encoder frame of the loaded model (4 / 6 / 8 by the input layer, doubled by
         the Efficient Conformer's stride layer)"""

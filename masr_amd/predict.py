@@ -57,6 +57,8 @@ class MASRPredictor:
         self.beam_search_decoder = None
         self.vad_predictor = None
         self._pool = None             # predict_stream: a StreamPool with one session, opened on first use
+        self._pool_timestamps = False    # ... created with timestamps=True?
+        self._stream_running = False     # an utterance of predict_stream has begun (its first call fixed the flag)
         self._session = None
         if self.configs.decoder == 'ctc_beam_search':
             # predict.py:96-109; the search is masr_amd's own (vocabulary pruning, prefix search and LM scoring on the GPU)
@@ -400,9 +402,12 @@ class MASRPredictor:
 
     # ---- streaming ------------------------------------------------------------------------------------------------------------
     def predict_stream(self, audio_data, is_end=False, use_pun=False, is_itn=False, channels=1, samp_width=2,
-                       sample_rate=16000):
+                       sample_rate=16000, timestamps=False):
         """predict.py:237-343: feed raw PCM bytes / ndarray chunks, get the transcript so far ({'text','score'}), or None
-        while fewer frames than one decoding window have arrived.  One session of a ``StreamPool``."""
+        while fewer frames than one decoding window have arrived.  One session of a ``StreamPool``.
+        ``timestamps=True``: the result gains ``'tokens'`` as in ``predict`` -- the transcript so far aligned against all frames of
+        the utterance so far, in seconds since the utterance began (``StreamPool(timestamps=True)``: its cost is stated there).
+        The flag of an utterance's first call decides for the utterance; change it after ``reset_stream()``."""
         if not self.configs.streaming:
             raise Exception(f"不支持改该模型流式识别，当前模型：{self.configs.use_model}，参数streaming为：{self.configs.streaming}")
         self._no_itn(is_itn)
@@ -412,15 +417,34 @@ class MASRPredictor:
         if self.configs.decoder == 'attention':
             from masr_amd.decoders.attention_decoder import STREAM_REFUSAL
             raise Exception(STREAM_REFUSAL)
-        if self._pool is None:
-            from masr_amd.serving import StreamPool
-            self._pool = StreamPool(self)
-            self._session = self._pool.open()
+        self._stream_pool_for(bool(timestamps))
         self._pool.feed(self._session, audio_data, is_end, channels=channels, samp_width=samp_width, sample_rate=sample_rate)
         return self._pool.step()[self._session]
+
+    def _new_stream_pool(self, timestamps):
+        from masr_amd.serving import StreamPool
+        return StreamPool(self, timestamps=True) if timestamps else StreamPool(self)
+
+    def _stream_pool_for(self, timestamps):
+        """the single-session pool of ``predict_stream``: made on first use, and made anew at an utterance boundary when the new
+        utterance's first call asks for the other kind; inside an utterance the flag cannot change"""
+        if self._pool is not None and self._pool_timestamps != timestamps:
+            if self._stream_running:
+                from masr_amd._lib import MasrError
+                raise MasrError(f'predict_stream: timestamps={timestamps} inside an utterance that began with timestamps='
+                                f'{self._pool_timestamps}: the first call of an utterance decides; call reset_stream() first')
+            self._pool.close(self._session)
+            self._pool.shutdown()
+            self._pool = None
+        if self._pool is None:
+            self._pool = self._new_stream_pool(timestamps)
+            self._pool_timestamps = timestamps
+            self._session = self._pool.open()
+        self._stream_running = True
 
     def reset_stream(self):
         """predict.py:346-353: forget the stream (caches, pending audio and frames, decoder history)."""
         self.predictor.reset_stream()
+        self._stream_running = False
         if self._pool is not None:
             self._pool.reset(self._session)

@@ -18,6 +18,16 @@ pending is done together:
     beam search (``BeamSearchDecoder.decode_chunk``, beam_search_decoder.py:75-91).
 
 Every session receives exactly the partial results its own reference ``predict_stream`` loop would produce.
+
+``StreamPool(predictor, timestamps=True)`` -- token timestamps on streams: the pool keeps what the CTC head emitted for every
+session on the device, one V-wide row per encoder frame in ONE row pool [n_rows, V] that all sessions share (posterior_rows.py
+says which rows are whose: freed rows are reused, so a session's rows are neither contiguous nor increasing), and every step
+aligns the current hypothesis of each session that advanced against ALL of its frames so far with one masr_ctc_align_rows launch
+behind the decoding (csrc/ctc_align.hip reads the frames through the row table: a step packs and copies no history; only the
+step in which the pool outgrows its allocation re-houses it, into twice the rows, every row keeping its number).  The result
+gains ``'tokens'`` as offline (decoders/ctc_alignment.py), in seconds on the session's own clock.  Such a pool runs the python
+framing below for ``ctc_greedy`` too; it costs V * 4 bytes of device memory per encoder frame and session (V = 4233: 17 KB per
+frame, about 4 MB per 10 s of speech), bounded by the stream's own frame limit and given back on ``reset`` / ``close``.
 """
 import ctypes as C
 import os
@@ -29,6 +39,7 @@ import torch
 from masr_amd import _lib
 from masr_amd._lib import MasrError
 from masr_amd.data_utils.audio import AudioSegment
+from masr_amd.decoders import ctc_alignment
 from masr_amd.engine import reference_gains
 
 _PCM_SCALE = np.float32(1.0 / 32768.0)
@@ -114,6 +125,14 @@ class _HostStage:
                                              'int64': torch.int64}[dtype.name]).view(*shape)
         return view, lambda: src.to(self.device, non_blocking=True)
 
+    def fetch(self, dev):
+        """device tensor (int32 / int64 / float32) -> numpy view of its copy in the pinned area; the copy is asynchronous on the
+        current stream: the caller waits for that stream (or an event on it) before it reads the view"""
+        view, _ = self.take(tuple(dev.shape), str(dev.dtype).replace('torch.', ''))
+        at = self.used - view.nbytes
+        self.buf[at:at + view.nbytes].view(dev.dtype).view(dev.shape).copy_(dev, non_blocking=True)
+        return view
+
     def put(self, array, dtype=np.int64):
         view, upload = self.take(np.shape(array), dtype)
         view[...] = array
@@ -125,7 +144,7 @@ class _HostStage:
 
 
 class _Session:
-    __slots__ = ('sid', 'remained', 'fresh', 'f0', 'nf', 'row', 'frames', 'result', 'decoder', 'tokens', 'beam_last')
+    __slots__ = ('sid', 'remained', 'fresh', 'f0', 'nf', 'row', 'frames', 'result', 'decoder', 'tokens', 'beam_last', 'samples')
 
     def __init__(self, sid, row, decoder=None):
         self.sid = sid
@@ -139,15 +158,27 @@ class _Session:
         self.decoder = decoder        # ctc_beam_search: this session's own search state
         self.tokens = []              # token ids of the last partial result
         self.beam_last = None         # beam search: the last decode_chunk result (what a step without a window returns)
+        self.samples = 0              # samples fed so far at the model's rate (timestamps: the end of the session's clock)
 
 
 class StreamPool:
     """``pool = StreamPool(predictor)`` on a streaming MASRPredictor (conformer / squeezeformer / efficient_conformer /
     uni-directional deepspeech2; ``ctc_greedy`` or ``ctc_beam_search``).  ``open()`` -> handle; ``feed(handle, pcm_bytes,
     is_end)`` queues audio; ``step()`` processes everything queued since the last step and returns ``{handle: {'text',
-    'score'} or None}`` for the sessions that were fed; ``close(handle)`` releases the stream."""
+    'score'} or None}`` for the sessions that were fed; ``close(handle)`` releases the stream.
 
-    def __init__(self, predictor, max_frames_out=0):
+    ``timestamps=True``: every result gains ``'tokens'`` -- [{'token', 'start', 'end', 'score'}] as ``predict(timestamps=True)``
+    gives offline, [] for an empty transcript, None when the CTC trellis holds no path for the hypothesis (or it is longer than
+    MASR_ALIGN_MAX_TOKENS) -- in seconds since ``open()`` / ``reset()``; ``end`` never exceeds the audio fed so far.  The pool
+    then keeps the CTC posteriors of every open session on the device, V * 4 bytes per encoder frame (V = 4233: 17 KB per frame,
+    about 4 MB per 10 s of speech and session) until ``reset`` / ``close`` gives the rows back, bounded by the stream's frame
+    limit (``max_frames_out`` / the positional table); each step re-aligns the whole history of the sessions that advanced in one
+    launch, and ``ctc_greedy`` sessions run the python framing instead of the C step.  ``posterior_rows`` / ``posteriors`` show
+    what is kept.  Without the flag nothing of this exists and the pool is what it was."""
+
+    ROW_SLAB = 4096                   # rows the posterior pool grows by (V = 4233: 69 MB)
+
+    def __init__(self, predictor, max_frames_out=0, timestamps=False):
         cfg = predictor.configs
         if not cfg.streaming or not ('former' in cfg.use_model or cfg.use_model == 'deepspeech2'):
             raise Exception(f"不支持改该模型流式识别，当前模型：{cfg.use_model}，参数streaming为：{cfg.streaming}")
@@ -188,7 +219,13 @@ class StreamPool:
         self._packed = None
         self._rate_slots = {}         # source rate -> slot of masr_pool_set_rate
         self.device_resampled = 0     # off-rate feeds handed to the device resampler (masr_pool_step_rates) so far
-        if not self.beam and not os.environ.get('MASR_POOL_PY'):
+        self.timestamps = bool(timestamps)
+        if self.timestamps:
+            from masr_amd.posterior_rows import RowAllocator
+            self._alloc = RowAllocator(self.ROW_SLAB)
+            self._post = torch.empty(0, self.engine.vocab_size, dtype=torch.float32, device=self.engine.device)    # the row pool
+            self._reduction = self.engine.frame_reduction()
+        if not self.beam and not self.timestamps and not os.environ.get('MASR_POOL_PY'):
             self._lib = _lib.lib()
             h = C.c_void_p()
             method = {'fbank': 0, 'mfcc': 1, 'linear': 2}[self.method]
@@ -287,6 +324,8 @@ class StreamPool:
             s.decoder.close()
         self._free_rows.append(s.row)
         self._fed.pop(handle, None)
+        if self.timestamps:
+            self._alloc.release(handle)
 
     def reset(self, handle):
         """start a new utterance on an open session (MASRPredictor.reset_stream, predict.py:346-353)"""
@@ -303,6 +342,8 @@ class StreamPool:
             old.decoder.reset_decoder()
         self.sessions[handle] = _Session(handle, old.row, old.decoder)
         self._fed.pop(handle, None)
+        if self.timestamps:
+            self._alloc.release(handle)
 
     def _rate_slot(self, sample_rate):
         """the pool's slot for a source rate: registered once (masr_pool_set_rate uploads the filter table)"""
@@ -356,6 +397,77 @@ class StreamPool:
         """token ids behind the session's last partial result (what a multi-GPU front-end gathers instead of text)"""
         return self.sessions[handle].tokens
 
+    # ---- timestamps: the posterior history and its alignment -----------------------------------------------------------------------
+    def posterior_rows(self, handle):
+        """timestamps pool: the rows of the pool's posterior matrix that hold the session's encoder frames, in frame order (int64)"""
+        self._needs_timestamps()
+        return np.asarray(self._alloc.rows_of(self.sessions[handle].sid), np.int64)
+
+    def posteriors(self, handle):
+        """timestamps pool: the CTC-head probabilities of all frames of the session so far, gathered -> [frames, V] device tensor"""
+        rows = torch.from_numpy(self.posterior_rows(handle)).to(self.engine.device)
+        return self._post[rows]
+
+    def _needs_timestamps(self):
+        if not self.timestamps:
+            raise MasrError('this StreamPool keeps no posteriors: create it with timestamps=True')
+
+    def _keep_posteriors(self, items, probs):
+        """append the rows ``probs`` [n, Tq, V] of one lock-step call to the sessions' histories: n * Tq rows of the pool, taken
+        wherever it has room, filled with one copy of the size of this call (never of a history)"""
+        tq = probs.shape[1]
+        rows = np.concatenate([self._alloc.take(s.sid, tq) for s, _ in items])
+        if self._alloc.capacity > self._post.shape[0]:
+            # more slabs: the rows keep their numbers.  (The matrix has to stay ONE allocation -- the kernel takes one base pointer --
+            # so the step that outgrows it re-houses the pool, into at least twice the rows: the cost per row stays constant, and
+            # no other step copies anything of the size of a history.)
+            grown = torch.empty(max(self._alloc.capacity, 2 * self._post.shape[0]), self._post.shape[1], dtype=torch.float32,
+                                device=self.engine.device)
+            grown[:self._post.shape[0]] = self._post
+            self._post = grown
+        self._post[self._dev_index(rows)] = probs.reshape(-1, probs.shape[2])
+
+    def _align(self, sess):
+        """ONE masr_ctc_align_rows launch for the sessions ``sess`` (each with a result and at least one frame): their hypotheses,
+        row tables and lengths go up in one staged copy, the packed alignment comes back in one, and that one is waited for ->
+        the ``'tokens'`` value of each"""
+        eng, st = self.engine, self._stage
+        B = len(sess)
+        tables = [self._alloc.rows_of(s.sid) for s in sess]
+        tmax = max(len(t) for t in tables)
+        flat, lmax, alignable = ctc_alignment.pack_hypotheses([s.tokens for s in sess], tmax)
+        n32 = B + flat.size                                    # n_frames | tokens | n_tokens behind the int64 row table
+        up, upload = st.take((B * tmax + (n32 + 1) // 2,), np.int64)
+        table = up[:B * tmax].reshape(B, tmax)
+        for b, t in enumerate(tables):
+            table[b, :len(t)] = t
+            table[b, len(t):] = -1
+        small = up[B * tmax:].view(np.int32)
+        small[:B] = [len(t) for t in tables]
+        small[B:n32] = flat
+        dev = upload()
+        dsmall = dev[B * tmax:].view(torch.int32)
+        packed = torch.empty(B * (3 * lmax + 2), dtype=torch.int32, device=eng.device)
+        eng.ctc_align_rows(self._post, dev[:B * tmax].view(B, tmax), dsmall[:B], dsmall[B:B + B * lmax].view(B, lmax),
+                           dsmall[B + B * lmax:n32], out=packed)
+        host = st.fetch(packed)
+        done = torch.cuda.Event()
+        done.record()
+        done.synchronize()
+        start, end, peak, score, status = ctc_alignment.unpack_alignment(host, B, lmax)
+        return [ctc_alignment.utterance_tokens(s.tokens, start[b], end[b], peak[b], score[b], status[b] if alignable[b] else 1,
+                                               self._reduction, self.sample_rate, s.samples / float(self.sample_rate), self.vocab)
+                for b, s in enumerate(sess)]
+
+    def _stamp(self, sess):
+        """``'tokens'`` into the results of the sessions that decoded a window in this step"""
+        todo = [s for s in sess if s.result is not None and s.frames > 0]
+        for s, toks in zip(todo, self._align(todo) if todo else []):
+            s.result['tokens'] = toks
+        for s in sess:
+            if s.result is not None and s.frames == 0:     # only windows too short for a frame so far: the empty transcript
+                s.result['tokens'] = [] if not s.tokens else None
+
     # ---- one batched step -------------------------------------------------------------------------------------------------
     def _featurize(self, sess):
         """features of all pending samples in one ragged launch (predict.py:274-281 per session), appended on the device to
@@ -368,6 +480,7 @@ class StreamPool:
         lens = np.array([c + sum(len(a) for a in s.fresh) for c, s in zip(carried, sess)], np.int32)
         buf, upload_buf = st.take((n, max(int(lens.max()), self.min_samples)), np.float32)
         for i, s in enumerate(sess):
+            s.samples += int(lens[i]) - carried[i]
             row, at = buf[i], carried[i]
             if at:
                 row[:at] = s.remained
@@ -531,13 +644,17 @@ class StreamPool:
                 sids = [s.sid for s, _ in items]
                 if self.beam:
                     probs, _, _ = eng.encode_chunk(sids, x, want_probs=True)
+                    if self.timestamps:
+                        self._keep_posteriors(items, probs)
                     for i, (s, _) in enumerate(items):
                         score, text = s.decoder.decode_chunk(probs=probs[i:i + 1], logits_lens=[probs.shape[1]])
                         s.frames += probs.shape[1]
                         s.result = s.beam_last = {'text': text, 'score': score}
                         s.tokens = list(s.decoder.last_tokens)
                     continue
-                _, idx, mp = eng.encode_chunk(sids, x, want_probs=False, want_argmax=True)
+                probs, idx, mp = eng.encode_chunk(sids, x, want_probs=self.timestamps, want_argmax=True)
+                if self.timestamps:
+                    self._keep_posteriors(items, probs)
                 tq = idx.shape[1]
                 self._grow(0, max(s.frames for s, _ in items) + tq)
                 at = self._dev_index(np.array([s.row * self._hist_idx.shape[1] + s.frames for s, _ in items],
@@ -564,6 +681,8 @@ class StreamPool:
                 text = ''.join(self.vocab[t] for t in s.tokens).replace('<space>', ' ')
                 # the score counts every non-blank frame (repeats included); with none the reference returns 0
                 s.result = {'text': text, 'score': float(np.float32(score[j])) * 100.0 if ntok[j] > 0 else 0}
+        if self.timestamps:
+            self._stamp([s for s, p in zip(sess, plans) if p])
         self._stage.end()
         out = {}
         for s, p in zip(sess, plans):
