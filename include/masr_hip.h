@@ -155,7 +155,9 @@ int masr_ctc_greedy_frames(masr_engine* e, const float* enc_dev, int32_t M, int3
 /* Best-path collapse + score.  Replaces the list logic of greedy_decoder
  * (ctc_greedy_decoder.py:20-30): tokens_dev [B, Tp] (-1 padded), n_tokens_dev [B],
  * score_dev [B] = fp32 sequential mean of the non-blank max-probs (caller multiplies by 100).
- * n_frames_dev [B] (may be NULL = all Tp frames, the reference's batch behaviour trainer.py:340). */
+ * n_frames_dev [B] (may be NULL = all Tp frames, the reference's batch behaviour trainer.py:340).
+ * Tp > 16384 is refused by name, nothing launched (the kernel stages Tp max-probs in dynamic LDS); masr_transcribe_batch /
+ * masr_transcribe_rows and masr_pool_step refuse the same way. */
 int masr_ctc_collapse(masr_engine* e, const int32_t* argmax_dev, const float* maxprob_dev, const int32_t* n_frames_dev,
                       int32_t B, int32_t Tp, int32_t blank, int32_t* tokens_dev, int32_t* n_tokens_dev,
                       float* score_dev, void* stream);
@@ -517,6 +519,14 @@ int masr_op_layernorm(masr_engine* e, const float* x_dev, const float* w_dev, co
                       int32_t M, float eps, void* stream);
 int masr_op_gemm(masr_engine* e, const float* a_dev, const float* w_dev, const float* bias_dev, const float* res_dev,
                  float* c_dev, int32_t M, int32_t N, int32_t K, int32_t act, float alpha, void* stream);
+/* The two packed-row forms of the CTC collapse, which otherwise run only inside masr_transcribe_rows (in_rows NULL) and
+ * masr_pool_step (in_rows given): rows_dev [B, Tp + 2] = tokens (-1 padded) | token count | score bits, the values masr_ctc_collapse
+ * gives.  in_rows_dev_or_null [B]: utterance b reads row in_rows[b] of argmax_dev / maxprob_dev, whose rows are ld_in frames apart
+ * (ld_in is not read without it: the rows are then Tp apart).  n_frames_dev [B] is required.  Non-zero: a null pointer, B < 0,
+ * Tp < 0, ld_in < Tp, Tp > 16384. */
+int masr_op_ctc_collapse_rows(masr_engine* e, const int32_t* argmax_dev, const float* maxprob_dev, const int32_t* n_frames_dev,
+                              const int32_t* in_rows_dev_or_null, int32_t ld_in, int32_t B, int32_t Tp, int32_t blank,
+                              int32_t* rows_dev, void* stream);
 /* One relative-position attention launch on the caller's buffers: builds the per-sequence descriptor table from the host arrays
  * [nseq] and calls the launcher the encoder calls, so the process-wide switches (keys 7, 14, 26, 28) pick the kernel as they do
  * in a forward pass.  group = 1: q rows of q_stride floats, k / v rows of kv_stride floats (>= heads * 64), out rows of heads * 64;

@@ -116,6 +116,7 @@ SIGNATURES = {
     'masr_stream_export_cache': [_P, _I, _P, _P, _P],
     'masr_op_layernorm': [_P, _P, _P, _P, _P, _I, _F, _P],
     'masr_op_gemm': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    'masr_op_ctc_collapse_rows': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     'masr_op_attention': [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     'masr_op_attention_plain': [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     'masr_decoder_enable': [_P, _I, _I, _I, _I],

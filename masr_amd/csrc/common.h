@@ -209,7 +209,11 @@ void launch_time_reduce_dw(const float* x, const float* w5c, const float* bias, 
 void launch_recover_add(const float* saved, const float* y, float* x, int B, int T, int L, hipStream_t s);
 // softmax over V per row (in place) + argmax / max prob
 void launch_softmax_argmax(float* logits, int M, int V, int ldv, int write_probs, int* idx, float* maxp, hipStream_t s);
-// CTC collapse per utterance
+// CTC collapse per utterance.  The kernel stages the non-blank max-probs of an utterance in Tp * 4 bytes of dynamic LDS and
+// nothing raises its limit above the default 64 KB (ensure_dynamic_lds): every caller refuses Tp > CTC_COLLAPSE_MAX_FRAMES by
+// name (ctc_collapse_refusal) before it launches
+constexpr int CTC_COLLAPSE_MAX_FRAMES = 16384;
+constexpr char ctc_collapse_refusal[] = "more than 16384 frames per utterance are not supported by the CTC collapse kernel (it stages Tp max-probs in 64 KB of dynamic LDS)";
 void launch_ctc_collapse(const int* idx, const float* maxp, const int* nframes, int B, int Tp, int blank,
                          int* tokens, int* ntok, float* score, hipStream_t s);
 struct PoolSeg {            // masr_pool_step: one contiguous run of rows to copy (rows of `width` floats)

@@ -800,7 +800,8 @@ __global__ __launch_bounds__(256) void topk_prune_kernel(const float* __restrict
     __shared__ int red_i[4];
     const float* x = probs + (size_t)blockIdx.x * V;
     // ln p(blank) of the frame as the decoder's min_cutoff rule takes it (std::log(prob[blank_id]), no FLT_MIN added)
-    if (out_blank_lp && threadIdx.x == 0) out_blank_lp[blockIdx.x] = logf(x[blank]);
+    // (the logarithms of this kernel are taken in double and rounded once: logf here was up to 2.1 float32 ulp from the exact value)
+    if (out_blank_lp && threadIdx.x == 0) out_blank_lp[blockIdx.x] = (float)log((double)x[blank]);
     float v[SM_MAXPT];
 #pragma unroll
     for (int i = 0; i < SM_MAXPT; ++i) {
@@ -834,7 +835,7 @@ __global__ __launch_bounds__(256) void topk_prune_kernel(const float* __restrict
         if (m < 0.f) break;                              // vocabulary exhausted (V < top_n)
         if (threadIdx.x == 0) {
             out_idx[(size_t)blockIdx.x * top_n + k] = mi;
-            out_logp[(size_t)blockIdx.x * top_n + k] = logf(m + 1.17549435e-38f);
+            out_logp[(size_t)blockIdx.x * top_n + k] = m;      // the probability: its logarithm is taken behind the rounds
         }
         // remove the winner from its owner's registers
 #pragma unroll
@@ -845,6 +846,13 @@ __global__ __launch_bounds__(256) void topk_prune_kernel(const float* __restrict
         if (cutoff_prob < 1.0f && cum >= (double)cutoff_prob) break;
     }
     if (threadIdx.x == 0) out_cnt[blockIdx.x] = cnt;
+    // log(p + FLT_MIN) of the cnt winners, one per thread and off the rounds' critical path (cnt is the same in every thread: m
+    // and cum come from the shared reduction)
+    __syncthreads();
+    for (int k = threadIdx.x; k < cnt; k += 256) {
+        float* lp = out_logp + (size_t)blockIdx.x * top_n + k;
+        *lp = (float)log((double)(*lp + 1.17549435e-38f));
+    }
 }
 
 void launch_topk_prune(const float* probs, int M, int V, int top_n, float cutoff_prob, int* out_idx, float* out_logp,

@@ -58,8 +58,27 @@ int masr_ctc_collapse(masr_engine* e, const int32_t* argmax_dev, const float* ma
                       float* score_dev, void* stream) {
     if (!e) return fail("null engine");
     ENTER(e);
+    if (Tp > CTC_COLLAPSE_MAX_FRAMES) return fail(std::string("masr_ctc_collapse: ") + ctc_collapse_refusal);
     launch_ctc_collapse(argmax_dev, maxprob_dev, n_frames_dev, B, Tp, blank, tokens_dev, n_tokens_dev, score_dev,
                         (hipStream_t)stream);
+    LAUNCHCHK();
+    return 0;
+}
+
+int masr_op_ctc_collapse_rows(masr_engine* e, const int32_t* argmax_dev, const float* maxprob_dev, const int32_t* n_frames_dev,
+                              const int32_t* in_rows_dev_or_null, int32_t ld_in, int32_t B, int32_t Tp, int32_t blank,
+                              int32_t* rows_dev, void* stream) {
+    if (!e) return fail("null engine");
+    if (!argmax_dev || !maxprob_dev || !n_frames_dev || !rows_dev) return fail("masr_op_ctc_collapse_rows: null argument");
+    if (B < 0 || Tp < 0) return fail("masr_op_ctc_collapse_rows: B and Tp must not be negative");
+    if (in_rows_dev_or_null && ld_in < Tp) return fail("masr_op_ctc_collapse_rows: ld_in must be at least Tp");
+    if (Tp > CTC_COLLAPSE_MAX_FRAMES) return fail(std::string("masr_op_ctc_collapse_rows: ") + ctc_collapse_refusal);
+    ENTER(e);
+    if (in_rows_dev_or_null)
+        launch_ctc_collapse_hist(argmax_dev, maxprob_dev, n_frames_dev, in_rows_dev_or_null, ld_in, B, Tp, blank, rows_dev,
+                                 (hipStream_t)stream);
+    else
+        launch_ctc_collapse_rows(argmax_dev, maxprob_dev, n_frames_dev, B, Tp, blank, rows_dev, (hipStream_t)stream);
     LAUNCHCHK();
     return 0;
 }

@@ -266,6 +266,9 @@ static int transcribe_impl(masr_engine* e, const void* samples_dev, int32_t fmt,
     const bool halved = e->cfg.model_kind == 2 && e->stride_idx >= 0;      // efficient conformer: one more stride-2 stage
     const int Tq = halved ? (Tsub + 1) / 2 : Tsub;
     if (Tsub <= 0) return fail("utterances too short");
+    // both forms of the collapse behind this pass (masr_ctc_collapse, launch_ctc_collapse_rows) take Tq frames per utterance: refused
+    // here, before anything is computed (the Conformer families are bounded by max_pos as well, DeepSpeech2 by nothing else)
+    if (Tq > CTC_COLLAPSE_MAX_FRAMES) return fail(std::string("masr_transcribe: ") + ctc_collapse_refusal);
     CHK(e->feats.ensure((size_t)B * T * F * sizeof(float)));
     CHK(e->nframes.ensure(sizeof(int) * 2 * B));
     CHK(e->enc.ensure((size_t)B * Tq * d * sizeof(float)));

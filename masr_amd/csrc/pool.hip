@@ -769,6 +769,10 @@ int masr_pool_step_rates(masr_pool* p, int32_t n_feeds, const int32_t* feed_hand
         }
     const int na = (int)adv.size(), width = hmax + 2;
     int32_t* rows_h = nullptr;
+    // the collapse takes the longest history as its Tp: a Conformer-family session stops at its stream's max_frames_out <= max_pos
+    // (5000 unless the engine was created with more), a DeepSpeech2 session has no frame limit -- the same refusal as
+    // masr_ctc_collapse, by name, instead of a launch that asks for more dynamic LDS than the kernel may have
+    if (hmax > CTC_COLLAPSE_MAX_FRAMES) PFAIL(std::string("masr_pool_step: ") + ctc_collapse_refusal);
     if (na) {
         int32_t* meta_h = nullptr;                 // [rows | frame counts]
         PCHK(p->pin.take((size_t)2 * na * 4, (void**)&meta_h));

@@ -935,6 +935,18 @@ class HipEngine:
                                          float(eps), _stream()))
         return y
 
+    def op_ctc_collapse_rows(self, idx, maxp, n_frames, in_rows=None, Tp=None, blank=0):
+        """masr_op_ctc_collapse_rows: the packed-row collapse of ``transcribe_rows`` (``in_rows`` None: ``idx`` / ``maxp`` [B, Tp]) or
+        of the pool step (``in_rows`` [B] int32: utterance b reads row ``in_rows[b]`` of the history matrices ``idx`` / ``maxp``
+        [*, ld_in], ``Tp`` frames at the most) -> rows [B, Tp + 2] int32 = tokens | count | score bits"""
+        B = n_frames.shape[0]
+        ld_in = idx.shape[1]
+        Tp = ld_in if Tp is None else int(Tp)
+        rows = torch.empty(B, Tp + 2, dtype=torch.int32, device=self.device)
+        check(self.lib.masr_op_ctc_collapse_rows(self.h, _ptr(idx), _ptr(maxp), _ptr(n_frames), _ptr(in_rows), ld_in, B, Tp, blank,
+                                                 _ptr(rows), _stream()))
+        return rows
+
     def op_gemm(self, a, w, bias=None, res=None, act=0, alpha=1.0):
         M, K = a.shape
         N = w.shape[0]
