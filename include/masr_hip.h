@@ -309,6 +309,23 @@ int masr_gbeam_close(masr_engine* e, int32_t handle);
 /* external scorer of a streaming search (between utterances only: after open or reset) */
 int masr_gbeam_set_lm(masr_engine* e, int32_t handle, masr_lm* lm, float alpha, float beta);
 
+/* The N best prefixes of the GPU search (csrc/beam_nbest.hip): a second, small kernel (one 512-thread workgroup per utterance) over
+ * what the search left on the device -- the live set it persists when it ends and the trie nodes of its survivors.  The search
+ * itself is untouched, so its own result stays what it is.  Order: the search's own best pick -- higher score first (the search
+ * score, scorer share included); of bit-equal scores the smaller last character; of equal (score, character) the smaller live
+ * index -- so entry 0 is the search's result bit for bit.  Outputs (device arrays): tokens_dev [B, nbest, max_len] (positions
+ * below max_len only), len_dev / score_dev [B, nbest] with the conventions of masr_beam_search_gpu (with a scorer: approx_ctc where
+ * the prefix fits max_len), count_dev [B] = min(nbest, live prefixes); rows past count have len 0, score -inf, tokens untouched.
+ * masr_beam_nbest_gpu reads the workspace of the last masr_beam_search_gpu(_lm) on the SAME stream of this engine (the stream
+ * orders the two).  Non-zero (masr_last_error, nothing launched): no search on that stream yet, B or beam_size other than that
+ * search's, lm_or_null other than the scorer it had bound (or, with it, alpha / beta other than that search's), nbest outside 1 .. beam_size, max_len < 1, a null output.
+ * masr_gbeam_nbest: the same for a streaming search after at least one masr_gbeam_advance since open or reset, with the stream's
+ * own scorer, alpha and beta. */
+int masr_beam_nbest_gpu(masr_engine* e, int32_t B, int32_t beam_size, int32_t nbest, masr_lm* lm_or_null, float alpha, float beta,
+                        int32_t* tokens_dev, int32_t max_len, int32_t* len_dev, float* score_dev, int32_t* count_dev, void* stream);
+int masr_gbeam_nbest(masr_engine* e, int32_t handle, int32_t nbest, int32_t* tokens_dev, int32_t max_len, int32_t* len_dev,
+                     float* score_dev, int32_t* count_dev, void* stream);
+
 /* Silero VAD network (the segmentation model of MASRPredictor.predict_long).  Replaces the onnxruntime session of the reference's
  * VADPredictor (masr/infer_utils/vad_predictor.py:36 InferenceSession(silero_vad.onnx), :83-104 session.run per window): the
  * weights are read out of the user's copy of that ONNX file by the host side (masr_amd/infer_utils/silero_vad.py) and handed
@@ -527,6 +544,16 @@ int masr_op_gemm(masr_engine* e, const float* a_dev, const float* w_dev, const f
 int masr_op_ctc_collapse_rows(masr_engine* e, const int32_t* argmax_dev, const float* maxprob_dev, const int32_t* n_frames_dev,
                               const int32_t* in_rows_dev_or_null, int32_t ld_in, int32_t B, int32_t Tp, int32_t blank,
                               int32_t* rows_dev, void* stream);
+/* The n-best kernel of masr_beam_nbest_gpu on a host-supplied live set and node pool, LM-free: per utterance n_live_host [B] live
+ * prefixes with node_host / ch_host / score_host [B, beam_size] (entries below n_live are read) over pool_parent_host /
+ * pool_ch_host [B, pool_cap]; outputs as above but HOST arrays (tokens_host is read first: positions no row writes come back as
+ * given).  Returns when done.  Non-zero: a null pointer, B < 1, beam_size outside 1 .. 512, pool_cap outside 1 .. 2^24, nbest
+ * outside 1 .. beam_size, max_len < 1, an n_live outside 0 .. beam_size, a live node outside [0, pool_cap), a pool node (>= 1)
+ * whose parent is not below it. */
+int masr_op_beam_nbest(masr_engine* e, const int32_t* n_live_host, const int32_t* node_host, const int32_t* ch_host,
+                       const float* score_host, const int32_t* pool_parent_host, const int32_t* pool_ch_host, int32_t B,
+                       int32_t beam_size, int32_t pool_cap, int32_t nbest, int32_t* tokens_host, int32_t max_len, int32_t* len_host,
+                       float* score_host_out, int32_t* count_host);
 /* One relative-position attention launch on the caller's buffers: builds the per-sequence descriptor table from the host arrays
  * [nseq] and calls the launcher the encoder calls, so the process-wide switches (keys 7, 14, 26, 28) pick the kernel as they do
  * in a forward pass.  group = 1: q rows of q_stride floats, k / v rows of kv_stride floats (>= heads * 64), out rows of heads * 64;

@@ -126,6 +126,9 @@ SIGNATURES = {
     'masr_attention_decode': [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, C.POINTER(_I), _P],
     'masr_op_decoder_step': [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     'masr_beam_search_batch_nbest': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
+    'masr_beam_nbest_gpu': [_P, _I, _I, _I, _P, _F, _F, _P, _I, _P, _P, _P, _P],
+    'masr_gbeam_nbest': [_P, _I, _I, _P, _I, _P, _P, _P, _P],
+    'masr_op_beam_nbest': [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P],
     'masr_side_stream': [_P, _I, C.POINTER(_P)],
     'masr_select_lane': [_P, _I],
     'masr_stage_rows': [_P, C.c_int64, _P, _P, _I, _I, _I],

@@ -11,7 +11,7 @@ CSRC = os.path.join(ROOT, 'csrc')
 LIB_DIR = os.path.join(ROOT, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libmasr_hip.so')
 SOURCES = ['gemm_f32.hip', 'ffn_reduce.hip', 'ffn_pc.hip', 'sqz_layer.hip', 'rowgemm.hip', 'rowgemm_small.hip', 'elementwise.hip', 'wide.hip',
-           'attention.hip', 'lstm.hip', 'gru.hip', 'beam_gpu.hip', 'lm_scorer.cpp', 'fbank.hip', 'silero.hip', 'engine.hip', 'pool.hip',
+           'attention.hip', 'lstm.hip', 'gru.hip', 'beam_gpu.hip', 'beam_nbest.hip', 'lm_scorer.cpp', 'fbank.hip', 'silero.hip', 'engine.hip', 'pool.hip',
            'beam_search.cpp', 'stage.cpp', 'resample.cpp', 'resample.hip', 'knobs.cpp', 'decoder.hip', 'decoder_step.hip',
            'engine_attdecoder.hip', 'ctc_align.hip', 'engine_layers.hip', 'engine_conformer.hip', 'engine_efficient.hip',
            'engine_squeezeformer.hip', 'engine_ds2.hip', 'engine_ctc.hip', 'engine_frontend.hip', 'engine_ops.hip']

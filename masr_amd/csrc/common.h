@@ -462,6 +462,23 @@ inline void beam_state_carve(void* base, int B, int beam, unsigned long long** h
 size_t beam_gpu_lds_bytes(int beam, int K, bool use_lm);
 int launch_beam_search(const BeamGpuArgs& a, int B, hipStream_t s);   // 1: sizes not supported
 
+// ---- the N best prefixes of a finished search (beam_nbest.hip): reads the live set launch_beam_search persisted ----
+struct BeamNbestArgs {
+    const int* state_i;        // [B][2 + 3 * beam] of the search (n_live, -, node[], ch[], -)
+    const float* state_f;      // [B][7 * beam]     of the search (score[] at 2 * beam)
+    const int* pool_parent;    // [B][pool_cap]
+    const int* pool_ch;        // [B][pool_cap]
+    int pool_cap, beam, nbest, max_len;
+    int* tokens;               // [B][nbest][max_len]
+    int* len;                  // [B][nbest]
+    float* score;              // [B][nbest]
+    int* count;                // [B] = min(nbest, n_live)
+    int use_lm;                // 1: the reported scores are the decoder's approx_ctc (the ranking stays on the search score)
+    LmView lm;
+    float alpha, beta;
+};
+int launch_beam_nbest(const BeamNbestArgs& a, int B, hipStream_t s);  // 1: sizes not supported
+
 // ---- DeepSpeech2 (lstm.hip, gru.hip) ------------------------------------------------------
 // step launchers: H = every multiple of 256 in [256, 2048]; 1 (and nothing launched) for any other H
 int launch_lstm_step(const float* gx, const float* whh, const float* h_prev, float* h_next, float* c, float* out,

@@ -165,6 +165,8 @@ int masr_beam_search_gpu_lm(masr_engine* e, const int32_t* idx_dev, const float*
         pool = &ws.first;
         state = &ws.second;
     }
+    BeamLast& last = e->beam_last[stream];      // (masr_beam_nbest_gpu: nothing to read until this search is launched)
+    last.valid = false;
     CHK(pool->ensure((size_t)B * a.pool_cap * 2 * sizeof(int)));
     CHK(state->ensure((size_t)B * beam_state_bytes(beam_size)));
     a.pool_parent = pool->as<int>();
@@ -176,6 +178,137 @@ int masr_beam_search_gpu_lm(masr_engine* e, const int32_t* idx_dev, const float*
     a.tokens = tokens_dev; a.len = len_dev; a.score = score_dev;
     if (launch_beam_search(a, B, (hipStream_t)stream)) return fail("beam search launch rejected the sizes");
     LAUNCHCHK();
+    last.valid = true;
+    last.lm = lm;
+    last.alpha = lm ? alpha : 0.f;
+    last.beta = lm ? beta : 0.f;
+    last.B = B;
+    last.beam = beam_size;
+    last.pool_cap = a.pool_cap;
+    return 0;
+}
+
+// ---- the N best prefixes of the search that ran last (beam_nbest.hip) ----------------------------------------------------------
+static int nbest_sizes(const char* who, int beam, int nbest, int max_len, const void* tokens, const void* len, const void* score,
+                       const void* count) {
+    if (!tokens || !len || !score || !count) return fail(std::string(who) + ": null output");
+    if (nbest < 1 || nbest > beam)
+        return fail(std::string(who) + ": nbest = " + std::to_string(nbest) + " is outside 1 .. beam_size = " + std::to_string(beam));
+    if (max_len < 1) return fail(std::string(who) + ": max_len must be at least 1");
+    return 0;
+}
+
+int masr_beam_nbest_gpu(masr_engine* e, int32_t B, int32_t beam_size, int32_t nbest, masr_lm* lm, float alpha, float beta,
+                        int32_t* tokens_dev, int32_t max_len, int32_t* len_dev, float* score_dev, int32_t* count_dev, void* stream) {
+    if (!e) return fail("null engine");
+    const auto it = e->beam_last.find(stream);
+    if (it == e->beam_last.end() || !it->second.valid)
+        return fail("masr_beam_nbest_gpu: no masr_beam_search_gpu has run on this stream of the engine: there is no live set to read");
+    const BeamLast& last = it->second;
+    if (B != last.B || beam_size != last.beam)
+        return fail("masr_beam_nbest_gpu: B = " + std::to_string(B) + ", beam_size = " + std::to_string(beam_size) +
+                    " are not the last search's on this stream (B = " + std::to_string(last.B) + ", beam_size = " +
+                    std::to_string(last.beam) + ")");
+    if ((const void*)lm != last.lm)
+        return fail(!lm ? "masr_beam_nbest_gpu: the last search on this stream had a language model bound and this call has none"
+                        : last.lm ? "masr_beam_nbest_gpu: the language model is not the one the last search on this stream had bound"
+                                  : "masr_beam_nbest_gpu: the last search on this stream had no language model bound and this call has one");
+    if (lm && (alpha != last.alpha || beta != last.beta))
+        return fail("masr_beam_nbest_gpu: alpha = " + std::to_string(alpha) + ", beta = " + std::to_string(beta) +
+                    " are not the weights of the last search on this stream (alpha = " + std::to_string(last.alpha) + ", beta = " +
+                    std::to_string(last.beta) + "): entry 0 would not be that search's score");
+    CHK(nbest_sizes("masr_beam_nbest_gpu", beam_size, nbest, max_len, tokens_dev, len_dev, score_dev, count_dev));
+    ENTER(e);
+    const bool first = e->beam_first_set && stream == e->beam_first_stream;
+    DevBuf& pool = first ? e->beam_pool : e->beam_ws[stream].first;
+    DevBuf& state = first ? e->beam_state : e->beam_ws[stream].second;
+    BeamGpuArgs g{};
+    g.pool_cap = last.pool_cap;
+    g.pool_parent = pool.as<int>();
+    g.pool_ch = g.pool_parent + (size_t)B * g.pool_cap;
+    beam_state_carve(state.p, B, beam_size, &g.state_h, &g.state_i, &g.state_f);
+    CHK(bind_lm(g, lm, alpha, beta));
+    BeamNbestArgs a{};
+    a.state_i = g.state_i; a.state_f = g.state_f; a.pool_parent = g.pool_parent; a.pool_ch = g.pool_ch;
+    a.pool_cap = g.pool_cap; a.beam = beam_size; a.nbest = nbest; a.max_len = max_len;
+    a.tokens = tokens_dev; a.len = len_dev; a.score = score_dev; a.count = count_dev;
+    a.use_lm = g.use_lm; a.lm = g.lm; a.alpha = alpha; a.beta = beta;
+    if (launch_beam_nbest(a, B, (hipStream_t)stream)) return fail("masr_beam_nbest_gpu: launch rejected the sizes");
+    LAUNCHCHK();
+    return 0;
+}
+
+int masr_op_beam_nbest(masr_engine* e, const int32_t* n_live_host, const int32_t* node_host, const int32_t* ch_host,
+                       const float* score_host, const int32_t* pool_parent_host, const int32_t* pool_ch_host, int32_t B,
+                       int32_t beam_size, int32_t pool_cap, int32_t nbest, int32_t* tokens_host, int32_t max_len, int32_t* len_host,
+                       float* score_host_out, int32_t* count_host) {
+    // every refusal comes before the engine is touched: none of them needs a device
+    static const char who[] = "masr_op_beam_nbest";
+    if (!n_live_host || !node_host || !ch_host || !score_host || !pool_parent_host || !pool_ch_host)
+        return fail(std::string(who) + ": null input");
+    if (B < 1) return fail(std::string(who) + ": B must be at least 1");
+    if (beam_size < 1 || beam_size > 512) return fail(std::string(who) + ": beam_size must be in 1 .. 512");
+    if (pool_cap < 1 || pool_cap > (1 << 24)) return fail(std::string(who) + ": pool_cap must be in 1 .. 2^24");
+    CHK(nbest_sizes(who, beam_size, nbest, max_len, tokens_host, len_host, score_host_out, count_host));
+    for (int b = 0; b < B; ++b) {
+        if (n_live_host[b] < 0 || n_live_host[b] > beam_size)
+            return fail(std::string(who) + ": n_live of utterance " + std::to_string(b) + " is outside 0 .. beam_size");
+        for (int i = 0; i < n_live_host[b]; ++i)
+            if (node_host[(size_t)b * beam_size + i] < 0 || node_host[(size_t)b * beam_size + i] >= pool_cap)
+                return fail(std::string(who) + ": node " + std::to_string(i) + " of utterance " + std::to_string(b) +
+                            " is outside the pool");
+        for (int x = 1; x < pool_cap; ++x)
+            if (pool_parent_host[(size_t)b * pool_cap + x] >= x)
+                return fail(std::string(who) + ": the parent of pool node " + std::to_string(x) + " of utterance " + std::to_string(b) +
+                            " is not below it");
+    }
+    if (!e) return fail("null engine");
+    ENTER(e);
+    // the search's own layouts: state_i [B][2 + 3 * beam], state_f [B][7 * beam], pool parent | ch [B][pool_cap] each
+    const size_t ni = (size_t)B * (2 + 3 * beam_size), nf = (size_t)B * 7 * beam_size, np = (size_t)B * pool_cap;
+    const size_t rows = (size_t)B * nbest;
+    std::vector<int32_t> hi(ni, 0);
+    std::vector<float> hf(nf, 0.f);
+    for (int b = 0; b < B; ++b) {
+        int32_t* si = hi.data() + (size_t)b * (2 + 3 * beam_size);
+        float* sf = hf.data() + (size_t)b * 7 * beam_size;
+        si[0] = n_live_host[b];
+        for (int i = 0; i < n_live_host[b]; ++i) {
+            si[2 + i] = node_host[(size_t)b * beam_size + i];
+            si[2 + beam_size + i] = ch_host[(size_t)b * beam_size + i];
+            sf[2 * beam_size + i] = score_host[(size_t)b * beam_size + i];
+        }
+    }
+    struct Scratch {
+        void* p = nullptr;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } dev;
+    const size_t words = ni + nf + 2 * np + rows * max_len + 2 * rows + B;
+    HIPCHK(hipMalloc(&dev.p, words * 4));
+    int32_t* d_i = (int32_t*)dev.p;
+    float* d_f = (float*)(d_i + ni);
+    int32_t* d_pp = (int32_t*)(d_f + nf);
+    int32_t* d_pc = d_pp + np;
+    int32_t* d_tok = d_pc + np;
+    int32_t* d_len = d_tok + rows * max_len;
+    float* d_sc = (float*)(d_len + rows);
+    int32_t* d_cnt = (int32_t*)(d_sc + rows);
+    HIPCHK(hipMemcpy(d_i, hi.data(), ni * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_f, hf.data(), nf * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_pp, pool_parent_host, np * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_pc, pool_ch_host, np * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tok, tokens_host, rows * max_len * 4, hipMemcpyHostToDevice));     // (tokens a row does not write stay as given)
+    BeamNbestArgs a{};
+    a.state_i = d_i; a.state_f = d_f; a.pool_parent = d_pp; a.pool_ch = d_pc;
+    a.pool_cap = pool_cap; a.beam = beam_size; a.nbest = nbest; a.max_len = max_len;
+    a.tokens = d_tok; a.len = d_len; a.score = d_sc; a.count = d_cnt;
+    if (launch_beam_nbest(a, B, nullptr)) return fail(std::string(who) + ": launch rejected the sizes");
+    LAUNCHCHK();
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(tokens_host, d_tok, rows * max_len * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(len_host, d_len, rows * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(score_host_out, d_sc, rows * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(count_host, d_cnt, B * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -277,6 +410,27 @@ int masr_gbeam_advance_lm(masr_engine* e, int32_t handle, const int32_t* idx_dev
     if (launch_beam_search(a, 1, (hipStream_t)stream)) return fail("beam search launch rejected the sizes");
     LAUNCHCHK();
     g->started = true;
+    return 0;
+}
+
+int masr_gbeam_nbest(masr_engine* e, int32_t handle, int32_t nbest, int32_t* tokens_dev, int32_t max_len, int32_t* len_dev,
+                     float* score_dev, int32_t* count_dev, void* stream) {
+    GBeam* g;
+    CHK(gbeam_of(e, handle, &g));
+    if (!g->started)
+        return fail("masr_gbeam_nbest: no masr_gbeam_advance since the stream was opened or reset: there is no live set to read");
+    CHK(nbest_sizes("masr_gbeam_nbest", g->beam, nbest, max_len, tokens_dev, len_dev, score_dev, count_dev));
+    ENTER(e);
+    BeamGpuArgs s{};
+    gbeam_args(*g, s);
+    CHK(bind_lm(s, g->lm, g->alpha, g->beta));
+    BeamNbestArgs a{};
+    a.state_i = s.state_i; a.state_f = s.state_f; a.pool_parent = s.pool_parent; a.pool_ch = s.pool_ch;
+    a.pool_cap = s.pool_cap; a.beam = g->beam; a.nbest = nbest; a.max_len = max_len;
+    a.tokens = tokens_dev; a.len = len_dev; a.score = score_dev; a.count = count_dev;
+    a.use_lm = s.use_lm; a.lm = s.lm; a.alpha = g->alpha; a.beta = g->beta;
+    if (launch_beam_nbest(a, 1, (hipStream_t)stream)) return fail("masr_gbeam_nbest: launch rejected the sizes");
+    LAUNCHCHK();
     return 0;
 }
 

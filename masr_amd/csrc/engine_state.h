@@ -218,6 +218,12 @@ struct GBeam {        // device-resident streaming CTC prefix beam search (masr_
     masr_lm* lm = nullptr;       // external scorer bound with masr_gbeam_set_lm (not owned)
     float alpha = 0.f, beta = 0.f;
 };
+struct BeamLast {     // what the last whole-utterance search left in one workspace (masr_beam_nbest_gpu reads it back)
+    bool valid = false;
+    const void* lm = nullptr;    // the scorer that search had bound (not owned)
+    float alpha = 0.f, beta = 0.f;   // ... with these weights: the reported scores take the scorer's share out with them
+    int B = 0, beam = 0, pool_cap = 0;
+};
 
 enum ProfKind { PROF_NONE = 0, PROF_GEMM = 1, PROF_FFN1 = 2, PROF_CONV2 = 3, PROF_ATT = 4, PROF_FBANK = 5,
                 PROF_FFN_TAIL = 6, PROF_FFN_HEAD = 7, PROF_RNN = 8,
@@ -309,6 +315,7 @@ struct masr_engine : masr::EngineWs {
     // whole-utterance prefix searches launched on OTHER streams than the first one get workspaces of their own: two searches may
     // run next to each other (predict_batch: the passes' searches on two side streams), launches on one stream are ordered anyway
     std::map<void*, std::pair<masr::DevBuf, masr::DevBuf>> beam_ws;
+    std::map<void*, masr::BeamLast> beam_last;       // by stream, the first stream's workspace included
     // masr_mean_square runs on whatever stream prepares the NEXT pass (the facade's side stream, the contract step's copy stream)
     // while the feature launch of the current pass reads e->gain on the compute stream: its chunk sums and its unused gain slots
     // live in a scratch of their own, one per calling stream (launches on one stream are ordered anyway)

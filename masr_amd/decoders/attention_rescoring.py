@@ -10,8 +10,10 @@ model family follows:
     r_att  = the same from right_decoder on the reversed hypothesis
     score  = att * (1 - reverse_weight) + r_att * reverse_weight + ctc_weight * ctc_score
 
-The n-best prefixes and their log-probabilities ``ctc_score`` come from the CTC prefix beam search without a language model (the
-host-thread search of libmasr_hip.so, masr_beam_search_batch_nbest, on the candidates the GPU pruned); both decoders run on the GPU
+The n-best prefixes and their log-probabilities ``ctc_score`` come from the CTC prefix beam search without a language model:
+``first_pass: 'host'`` (default) the host-thread search of libmasr_hip.so (masr_beam_search_batch_nbest) on the candidates the GPU
+pruned; ``first_pass: 'gpu'`` masr_beam_search_gpu + masr_beam_nbest_gpu on the pass's stream over the device-resident
+probabilities, only the n-best rows coming back (one pinned copy, one wait).  Both decoders run on the GPU
 (masr_rescore), on the stream and the lane of the pass whose encoder output they read.  The winner is the highest score; an exact
 tie goes to the hypothesis that ranked earlier in the search.
 
@@ -30,6 +32,7 @@ STREAM_REFUSAL = ("decoder='attention_rescoring' does not run on streaming sessi
                   "predict_batch, or ctc_greedy / ctc_beam_search for streams")
 
 BEAM_MIN, BEAM_MAX = 1, 64
+FIRST_PASSES = ('host', 'gpu')      # where the first pass's prefix search runs
 
 
 def validate_rescoring_conf(conf, model_conf=None, r_num_blocks=None):
@@ -38,7 +41,7 @@ def validate_rescoring_conf(conf, model_conf=None, r_num_blocks=None):
     0 without one), ``cutoff_prob`` / ``cutoff_top_n`` as in the CTC search block (0.99 / 40).  ``r_num_blocks`` given: a positive
     ``reverse_weight`` needs a right-to-left decoder."""
     conf = dict(conf or {})
-    known = ('beam_size', 'ctc_weight', 'reverse_weight', 'cutoff_prob', 'cutoff_top_n', 'num_processes')
+    known = ('beam_size', 'ctc_weight', 'reverse_weight', 'cutoff_prob', 'cutoff_top_n', 'num_processes', 'first_pass')
     for k in conf:
         if k not in known:
             raise _lib.MasrError(f'attention_rescoring_decoder_conf.{k} is not a known key (known: {known})')
@@ -61,6 +64,11 @@ def validate_rescoring_conf(conf, model_conf=None, r_num_blocks=None):
     if isinstance(top_n, bool) or not isinstance(top_n, int) or top_n < 1:
         raise _lib.MasrError(f'attention_rescoring_decoder_conf.cutoff_top_n={top_n!r} is not supported: a positive integer')
     out['cutoff_top_n'] = top_n
+    if 'first_pass' in conf:            # (not named: the decoder's own default, 'host' -- the path and the bits it was)
+        if conf['first_pass'] not in FIRST_PASSES:
+            raise _lib.MasrError(f'attention_rescoring_decoder_conf.first_pass={conf["first_pass"]!r} is not supported: one of '
+                                 f'{FIRST_PASSES}')
+        out['first_pass'] = conf['first_pass']
     if r_num_blocks is not None and out['reverse_weight'] > 0 and r_num_blocks == 0:
         raise _lib.MasrError(f'attention_rescoring_decoder_conf.reverse_weight={out["reverse_weight"]} needs the right-to-left '
                              f'decoder, and this checkpoint has none (decoder_conf.r_num_blocks: 0)')
@@ -98,7 +106,7 @@ def build_table(nbest, max_pos=None):
 
 class AttentionRescoringDecoder:
     def __init__(self, vocab_list, beam_size=10, ctc_weight=0.5, reverse_weight=0.0, cutoff_prob=0.99, cutoff_top_n=40,
-                 num_processes=10, blank_id=0):
+                 num_processes=10, blank_id=0, first_pass='host'):
         from masr_amd.decoders.beam_search_decoder import BeamSearchDecoder
         self.vocab_list = vocab_list
         self.beam_size, self.ctc_weight, self.reverse_weight = int(beam_size), float(ctc_weight), float(reverse_weight)
@@ -108,6 +116,13 @@ class AttentionRescoringDecoder:
                                          vocab_list=vocab_list, num_processes=num_processes, blank_id=blank_id,
                                          language_model_path=None)
         self._lib = _lib.lib()
+        if first_pass not in FIRST_PASSES:
+            raise _lib.MasrError(f'attention_rescoring_decoder_conf.first_pass={first_pass!r} is not supported: one of {FIRST_PASSES}')
+        if first_pass == 'gpu' and not self._pruner.gpu_search_supported(1, len(vocab_list)):
+            raise _lib.MasrError(f"attention_rescoring_decoder_conf.first_pass='gpu' with beam_size={self.beam_size}, cutoff_top_n="
+                                 f"{cutoff_top_n} is beyond the GPU prefix search (beam_size 2 .. 512, cutoff_top_n <= 64, its "
+                                 f"tables within 160 KB of LDS); use first_pass='host'")
+        self.first_pass = first_pass
 
     def _text(self, toks):
         return ''.join(self.vocab_list[t] for t in toks).replace('<space>', ' ')
@@ -117,6 +132,8 @@ class AttentionRescoringDecoder:
         ``beam_size`` best prefixes [(token ids, log-probability)], best first"""
         B, Ts, V = probs.shape
         frames = np.ascontiguousarray(frames, np.int32)
+        if self.first_pass == 'gpu':
+            return self._nbest_gpu(probs, frames)
         idx, logp, cnt, _, K = self._pruner._candidates(probs.reshape(B * Ts, V))
         N, max_len = self.beam_size, max(Ts, 1)
         toks = np.zeros((B, N, max_len), np.int32)
@@ -128,6 +145,28 @@ class AttentionRescoringDecoder:
         if rc != 0:
             raise _lib.MasrError('masr_beam_search_batch_nbest failed')
         return [[(toks[b, n, :lens[b, n]].tolist(), float(scores[b, n])) for n in range(count[b])] for b in range(B)]
+
+    def _nbest_gpu(self, probs, frames):
+        """``first_pass: 'gpu'``: pruning, the LM-free masr_beam_search_gpu and masr_beam_nbest_gpu on the current stream; only the
+        packed n-best rows [B, N, max_len + 2] + counts come back: one pinned copy behind them, one wait"""
+        from masr_amd import runtime
+        dec = self._pruner
+        B, Ts, V = probs.shape
+        if not torch.is_tensor(probs):
+            probs = torch.as_tensor(np.asarray(probs), dtype=torch.float32)
+        eng = runtime.aux_engine(probs.device if probs.is_cuda else None)
+        cand = dec._candidates(probs.reshape(B * Ts, V), to_host=False)
+        _, max_len, keep = dec._search_gpu(eng, cand, frames, B, Ts, pack=False)
+        flat, keep_n = dec._nbest_gpu(eng, B, max_len, self.beam_size)
+        host = dec._pinned_out(flat.numel())
+        host[:flat.numel()].copy_(flat, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        done.synchronize()
+        try:
+            return dec._unpacked_nbest(host[:flat.numel()].numpy(), B, self.beam_size, max_len, True)
+        finally:
+            dec.__dict__.setdefault('_pin_free', []).append(host)
 
     def rescore_launch(self, eng, enc, enc_lens, nbest):
         """second pass QUEUED on ``eng``'s current stream and active lane, nothing waited for: the hypothesis table goes up through

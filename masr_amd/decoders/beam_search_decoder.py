@@ -45,6 +45,7 @@ class BeamSearchDecoder:
         self._geng = None                # ... and the (per-device) auxiliary engine that owns it
         self._gout = None
         self.last_tokens = []            # token ids of the last decode_chunk result
+        self.last_nbest, self.last_nbest_tokens = [], []     # decode_chunk(nbest=N): [(score, text)] and [token ids], best first
         self._lib = _lib.lib()
         self._ext_scorer = None
         self.prune_min_cutoff = True     # the decoder's min_cutoff / full_beam rule (only ever applies with a scorer bound)
@@ -83,6 +84,7 @@ class BeamSearchDecoder:
         other = object.__new__(BeamSearchDecoder)
         other.__dict__.update(self.__dict__)
         other._gstream, other._geng, other._gout, other.last_tokens = None, None, None, []
+        other.last_nbest, other.last_nbest_tokens = [], []
         h = C.c_void_p()
         if self._lib.masr_beam_create(self.beam_size, self.blank_id, C.byref(h)) != 0:
             raise _lib.MasrError('masr_beam_create failed')
@@ -187,7 +189,36 @@ class BeamSearchDecoder:
         """packed host rows [B, max_len + 2] int32 = tokens | length | score bits -> results"""
         return self._results(rows[:, :max_len], rows[:, max_len].copy(), rows[:, max_len + 1].copy().view(np.float32), want_tokens)
 
-    def _search_gpu(self, eng, cand, frames, B, Ts):
+    def check_nbest(self, nbest):
+        """``nbest`` as an int in 1 .. beam_size (None stays None: one result, today's path), refused by name otherwise"""
+        if nbest is None:
+            return None
+        if isinstance(nbest, bool) or not isinstance(nbest, (int, np.integer)) or not 1 <= int(nbest) <= self.beam_size:
+            raise ValueError(f'nbest={nbest!r}: nbest must be an integer in 1 .. beam_size = {self.beam_size}')
+        return int(nbest)
+
+    def _unpacked_nbest(self, flat, B, N, max_len, want_tokens):
+        """packed host int32 [B * N * (max_len + 2) + B] = per utterance N rows of tokens | length | score bits, best first, then
+        the B row counts -> per utterance the list of its count results, each as ``_results`` gives them"""
+        flat = np.asarray(flat)
+        rows = flat[:B * N * (max_len + 2)].reshape(B, N, max_len + 2)
+        count = flat[B * N * (max_len + 2):B * N * (max_len + 2) + B]
+        return [self._unpacked(rows[b, :int(count[b])], max_len, want_tokens) for b in range(B)]
+
+    def _nbest_gpu(self, eng, B, max_len, N):
+        """masr_beam_nbest_gpu behind the ``_search_gpu`` launch on the current stream -> (packed int32 [B * N * (max_len + 2) + B]
+        on the device, what must stay alive until it is read)"""
+        toks = torch.zeros(B, N, max_len, dtype=torch.int32, device=eng.device)
+        lens = torch.zeros(B, N, dtype=torch.int32, device=eng.device)
+        scores = torch.zeros(B, N, dtype=torch.float32, device=eng.device)
+        count = torch.zeros(B, dtype=torch.int32, device=eng.device)
+        check(self._lib.masr_beam_nbest_gpu(eng.h, B, self.beam_size, N, *self._lm_args(), C.c_void_p(toks.data_ptr()), max_len,
+                                            C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
+                                            C.c_void_p(count.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        rows = torch.cat([toks, lens[:, :, None], scores.view(torch.int32)[:, :, None]], 2)
+        return torch.cat([rows.view(-1), count]), (toks, lens, scores, count)
+
+    def _search_gpu(self, eng, cand, frames, B, Ts, pack=True):
         """masr_beam_search_gpu_lm over the candidates ``cand`` = (idx, logp, cnt, blp, K) of ``_candidates`` on the current stream
         -> (packed rows [B, max_len + 2] on the device, max_len, what must stay alive until they are read)"""
         idx, logp, cnt, blp, K = cand
@@ -202,7 +233,8 @@ class BeamSearchDecoder:
                                                 C.c_void_p(toks.data_ptr()), max_len,
                                                 C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        packed = torch.cat([toks, lens[:, None], scores.view(torch.int32)[:, None]], 1)       # one contiguous copy back
+        # one contiguous copy back (not packed for a caller that reads the n-best rows instead: entry 0 of them is this result)
+        packed = torch.cat([toks, lens[:, None], scores.view(torch.int32)[:, None]], 1) if pack else None
         return packed, max_len, (idx, logp, cnt, blp, fr, toks, lens, scores)
 
     def _search_host(self, idx, logp, cnt, blp, frames, B, Ts, K, want_tokens):
@@ -220,6 +252,28 @@ class BeamSearchDecoder:
         if rc != 0:
             raise _lib.MasrError('masr_beam_search_batch failed')
         return self._results(toks, lens, scores, want_tokens)
+
+    def _search_host_nbest(self, idx, logp, cnt, frames, B, Ts, K, N, want_tokens):
+        """masr_beam_search_batch_nbest (LM-free) on ``num_processes`` host threads -> per utterance its n-best results"""
+        if self._ext_scorer is not None:
+            kind = 'character-based' if self._ext_scorer.is_character_based else 'word-based'
+            raise ValueError(f'nbest is not available from the host-thread search with a language model bound (here a {kind} '
+                             'scorer; word-based scorers and sizes beyond the GPU search run there): its n-best search '
+                             '(masr_beam_search_batch_nbest) is LM-free')
+        max_len = max(Ts, 1)
+        toks = np.zeros((B, N, max_len), np.int32)
+        lens = np.zeros((B, N), np.int32)
+        scores = np.zeros((B, N), np.float32)
+        count = np.zeros(B, np.int32)
+        fr = np.ascontiguousarray(frames, np.int32)
+        rc = self._lib.masr_beam_search_batch_nbest(idx.ctypes.data_as(C.c_void_p), logp.ctypes.data_as(C.c_void_p),
+                                                    cnt.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p), B, Ts, K,
+                                                    self.beam_size, self.blank_id, self.num_processes, N,
+                                                    toks.ctypes.data_as(C.c_void_p), max_len, lens.ctypes.data_as(C.c_void_p),
+                                                    scores.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise _lib.MasrError('masr_beam_search_batch_nbest failed')
+        return [self._results(toks[b, :count[b]], lens[b, :count[b]], scores[b, :count[b]], want_tokens) for b in range(B)]
 
     def _say_host_search(self, beyond_gpu=False):
         """once per decoder: why the prefix search runs on host threads"""
@@ -241,25 +295,34 @@ class BeamSearchDecoder:
         behind the search kernel is a DMA-engine command that waits 6 ms and holds up the next pass's upload on the same engine
         (the host sat 17 ms in the next pass's preparation); a copy enqueued on the search's stream at collection time queues
         behind the search of pass k + 2, which shares that stream."""
-        _, B, max_len, packed, _keep, done = pending
-        host = self._pinned_out(B * (max_len + 2))
+        _, B, max_len, packed, _keep, done = pending[:6]
+        N = pending[6] if len(pending) > 6 else None      # an n-best launch: [B, N, max_len + 2] rows + [B] counts, the same one copy
+        n = B * (max_len + 2) if N is None else packed.numel()
+        host = self._pinned_out(n)
         done.synchronize()                           # the search (and the packing behind it) of THIS pass
         with torch.cuda.stream(runtime.aux_engine(packed.device).side_stream(3)):          # the library's copy stream: idle
-            host[:B * (max_len + 2)].copy_(packed.view(-1), non_blocking=True)
+            host[:n].copy_(packed.view(-1), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
         ev.synchronize()
-        res = self._unpacked(host[:B * (max_len + 2)].view(B, max_len + 2).numpy(), max_len, want_tokens)
+        if N is None:
+            res = self._unpacked(host[:n].view(B, max_len + 2).numpy(), max_len, want_tokens)
+        else:
+            res = self._unpacked_nbest(host[:n].numpy(), B, N, max_len, want_tokens)
         self._pin_free.append(host)
         return res
 
-    def _batch(self, probs_list, defer=False, want_tokens=False, frames=None):
+    def _batch(self, probs_list, defer=False, want_tokens=False, frames=None, nbest=None):
         """``defer=True`` (device-resident probabilities, GPU search): launch pruning + search on the current torch stream and
         return a handle for ``_batch_collect`` without synchronising -- lets the caller run the search of one sub-batch on a
         side stream while the encoder works on the next one (the search occupies one workgroup per utterance).
         ``frames`` given: ``probs_list`` is ONE padded [B, Ts, V] array / device tensor (what the CTC head of a device pass
         leaves behind) with ``frames[i]`` valid rows per utterance -- searched in place, no restacking (round 6: the 32 slice
-        copies + the fill of a 134 MB buffer were 3 ms on the critical path of every BASELINE configs[2] pass)."""
+        copies + the fill of a 134 MB buffer were 3 ms on the critical path of every BASELINE configs[2] pass).
+        ``nbest=N``: every utterance's result is the LIST of its (at most N) best prefixes, best first, entry 0 being what the
+        call returns without it -- on the GPU a second small kernel over what the search left (masr_beam_nbest_gpu), whose rows
+        come back in the same single packed copy; None: one result, nothing else launched."""
+        nbest = self.check_nbest(nbest)
         if frames is not None:
             stacked = probs_list
             B, Ts, V = stacked.shape
@@ -279,16 +342,27 @@ class BeamSearchDecoder:
         if B and Ts and self.use_gpu_search and self.gpu_search_supported(Ts, V):
             # whole search on the device: candidates never leave HBM, one workgroup per utterance
             eng = runtime.aux_engine(stacked.device if torch.is_tensor(stacked) else None)
-            packed, max_len, keep = self._search_gpu(eng, self._candidates(stacked.reshape(B * Ts, V), to_host=False), frames, B, Ts)
+            packed, max_len, keep = self._search_gpu(eng, self._candidates(stacked.reshape(B * Ts, V), to_host=False), frames, B, Ts,
+                                                     pack=nbest is None)
+            if nbest is not None:          # the n-best rows take the single result's place in the packed copy (entry 0 is that result)
+                packed, keep_n = self._nbest_gpu(eng, B, max_len, nbest)
+                keep = keep + keep_n
             if defer:                      # nothing has been synchronised: _batch_collect() fetches the result later
                 done = torch.cuda.Event()
                 done.record()
-                return ('gpu', B, max_len, packed, (stacked, probs_list) + keep, done)
+                pending = ('gpu', B, max_len, packed, (stacked, probs_list) + keep, done)
+                return pending if nbest is None else pending + (nbest,)
+            if nbest is not None:
+                return self._unpacked_nbest(packed.cpu().numpy(), B, nbest, max_len, want_tokens)
             return self._unpacked(packed.cpu().numpy(), max_len, want_tokens)
         if defer:
             raise Exception('deferred batch search needs the GPU search (device-resident probabilities within its limits)')
+        if nbest is not None and not (B and Ts):
+            return [[r] for r in self._batch(probs_list, want_tokens=want_tokens, frames=frames)]
         self._say_host_search(beyond_gpu=bool(self.use_gpu_search and B and Ts))
         idx, logp, cnt, blp, K = self._candidates(stacked.reshape(B * Ts, V))
+        if nbest is not None:
+            return self._search_host_nbest(idx, logp, cnt, frames, B, Ts, K, nbest, want_tokens)
         return self._search_host(idx, logp, cnt, blp, frames, B, Ts, K, want_tokens)
 
     # ---- host-thread search of a device pass, deferred ---------------------------------------------------------------------------
@@ -335,13 +409,19 @@ class BeamSearchDecoder:
                 self._pin_free.append(host)
         return collect
 
-    def decode_chunk(self, probs, logits_lens):
+    def decode_chunk(self, probs, logits_lens, nbest=None):
         """streaming: feed a chunk probs [1, T, V]; returns (score, text) of the best prefix so far
-        (beam_search_decoder.py:75-91)."""
+        (beam_search_decoder.py:75-91).  ``nbest=N`` (the device-resident search only): ``last_nbest`` / ``last_nbest_tokens``
+        then hold the (at most N) best prefixes so far as [(score, text)] / [token ids], best first, entry 0 being the returned
+        result (masr_gbeam_nbest behind the chunk's advance); None launches nothing else."""
+        nbest = self.check_nbest(nbest)
         n_valid = int(np.asarray(logits_lens).reshape(-1)[0])
         p = probs[0][:n_valid] if torch.is_tensor(probs) else np.asarray(probs)[0][:n_valid]     # device tensors stay there
         if self.use_gpu_search and self.gpu_search_supported(1, p.shape[1]):
-            return self._decode_chunk_gpu(p)
+            return self._decode_chunk_gpu(p, nbest)
+        if nbest is not None:
+            raise ValueError('nbest of a streaming search comes from the device-resident search (masr_gbeam_nbest); this decoder '
+                             'streams on the host (word-based scorer, use_gpu_search off or sizes beyond the GPU search)')
         idx, logp, cnt, blp, K = self._candidates(p)
         if p.shape[0]:
             self._lib.masr_beam_advance_lm(self._stream, idx.ctypes.data_as(C.c_void_p), logp.ctypes.data_as(C.c_void_p),
@@ -352,8 +432,8 @@ class BeamSearchDecoder:
         self.last_tokens = toks[:n.value].tolist()
         return float(sc.value), self._text(toks[:n.value])
 
-    def _decode_chunk_gpu(self, p):
-        """device-resident search state (masr_gbeam_*): only the best prefix travels back per chunk"""
+    def _decode_chunk_gpu(self, p, nbest=None):
+        """device-resident search state (masr_gbeam_*): only the best prefix (with ``nbest``: the N best) travels back per chunk"""
         eng = self._geng if self._gstream is not None else runtime.aux_engine()
         if self._gstream is None:
             self._geng = eng             # the stream's state lives in THIS device's engine until close()
@@ -374,6 +454,26 @@ class BeamSearchDecoder:
                                               C.c_void_p(cnt.data_ptr()), self._ptr(blp), T, K, C.c_void_p(toks.data_ptr()),
                                               max_len, C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        if nbest is not None:
+            # the chunk's one result is entry 0 of the rows: ONE packed copy brings everything back.  Prefixes of a stream are far
+            # shorter than the 5000 frames its pool allows: the rows hold 512 tokens and a longer prefix is an error by name
+            nl = 512
+            ntoks = torch.zeros(1, nbest, nl, dtype=torch.int32, device=eng.device)
+            nlens = torch.zeros(1, nbest, dtype=torch.int32, device=eng.device)
+            nscores = torch.zeros(1, nbest, dtype=torch.float32, device=eng.device)
+            count = torch.zeros(1, dtype=torch.int32, device=eng.device)
+            check(self._lib.masr_gbeam_nbest(eng.h, self._gstream, nbest, C.c_void_p(ntoks.data_ptr()), nl,
+                                             C.c_void_p(nlens.data_ptr()), C.c_void_p(nscores.data_ptr()),
+                                             C.c_void_p(count.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            rows = torch.cat([ntoks, nlens[:, :, None], nscores.view(torch.int32)[:, :, None]], 2)
+            flat = torch.cat([rows.view(-1), count]).cpu().numpy()
+            if int(flat[:nbest * (nl + 2)].reshape(nbest, nl + 2)[:, nl].max()) > nl:
+                raise _lib.MasrError(f'decode_chunk(nbest={nbest}): a prefix of more than {nl} tokens does not fit the n-best rows')
+            ids = self._unpacked_nbest(flat, 1, nbest, nl, True)[0]
+            self.last_nbest_tokens = [t for t, _ in ids]
+            self.last_nbest = [(sc, self._text(t)) for t, sc in ids]
+            self.last_tokens = list(ids[0][0])
+            return self.last_nbest[0]
         n = int(lens.item())
         self.last_tokens = toks[0, :n].cpu().numpy().tolist()
         return float(scores.item()), self._text(self.last_tokens)

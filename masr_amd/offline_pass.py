@@ -24,7 +24,7 @@ from masr_amd.pinned import PinnedRing
 
 # what the decoder routes of one pass work on: the engine, the rows that take part (``ok``: their indices in the pass, ``n``:
 # their samples), the encoder output and its valid frames per row (None: every padded frame is decoded), and the call's flags
-_Pass = namedtuple('_Pass', 'eng ok n min_samples enc nenc decode_all_frames want_ids defer timestamps')
+_Pass = namedtuple('_Pass', 'eng ok n min_samples enc nenc decode_all_frames want_ids defer timestamps nbest', defaults=(None,))
 
 
 def device_resample():
@@ -37,11 +37,25 @@ def greedy_score(score, ntok):
     return float(score) * 100.0 if ntok > 0 or score > 0 else 0
 
 
-def empty_result(as_tokens, timestamps):
+def empty_result(as_tokens, timestamps, nbest=None):
     """an utterance too short for one feature frame"""
     if as_tokens:
         return [], 0
-    return {'text': '', 'score': 0, 'tokens': []} if timestamps else {'text': '', 'score': 0}
+    out = {'text': '', 'score': 0, 'tokens': []} if timestamps else {'text': '', 'score': 0}
+    if nbest is not None:
+        out['nbest'] = [{'text': '', 'score': 0}]
+    return out
+
+
+def first_of_nbest(fetch):
+    """a fetch of per-utterance n-best lists -> (a fetch of every utterance's entry 0, what the other routes return; a box that
+    holds the lists under 'many' once that fetch has run)"""
+    box = {}
+
+    def first():
+        box['many'] = fetch()
+        return [m[0] for m in box['many']]
+    return first, box
 
 
 class OfflinePasses:
@@ -329,6 +343,8 @@ class OfflinePasses:
         probs = eng.ctc_probs(ps.enc)
         n_host = self._n_host(ps)
         align = self._aligner(ps, probs) if ps.timestamps else None
+        if ps.nbest is not None:
+            return self._beam_search_nbest(ps, probs, n_host, align)
         if ps.defer and dec.use_gpu_search and dec.gpu_search_supported(probs.shape[1], probs.shape[2]):
             # The prefix search of a pass (one workgroup per utterance, frames in sequence) runs on a side stream
             # (``search_stream``), launched at once: the call is bound by the longest utterance's ~30 us per frame x 494 frames, and
@@ -350,13 +366,33 @@ class OfflinePasses:
             return (lambda: res), lambda _res: toks
         return (lambda: res), None
 
+    def _beam_search_nbest(self, ps, probs, n_host, align):
+        """``_beam_search`` with ``nbest=N``: the same launches plus the n-best kernel behind the search, the rows in the search's
+        one packed copy; entry 0 of every utterance takes the place of the single result (alignment included).  Beyond the GPU
+        search the host-thread search gives them at once (LM-free; refused by name with a scorer bound)."""
+        eng, dec, want = ps.eng, self.beam, ps.want_ids
+        if ps.defer and dec.use_gpu_search and dec.gpu_search_supported(probs.shape[1], probs.shape[2]):
+            main = torch.cuda.current_stream(eng.device)
+            side = self.search_stream()
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                pending = dec._batch(probs, defer=True, frames=n_host, nbest=ps.nbest)
+            fetch, self._nbest_box = first_of_nbest(lambda: dec._batch_collect(pending, want_tokens=want))
+            return fetch, align
+        many = dec._batch(probs, want_tokens=want, frames=n_host, nbest=ps.nbest)
+        fetch, self._nbest_box = first_of_nbest(lambda: many)
+        if align is not None:
+            toks = align(fetch())
+            return fetch, lambda _res: toks
+        return fetch, None
+
     # ---- one pass ---------------------------------------------------------------------------------------------------------------
-    def _decode(self, began, decode_all_frames, want_ids, defer, timestamps):
+    def _decode(self, began, decode_all_frames, want_ids, defer, timestamps, nbest=None):
         """features, encoder and the configured decoder's route of the rows of ``began`` that take part, on the current stream"""
         eng, pc, decoder = self.eng, self.configs.preprocess_conf, self.configs.decoder
         method = pc.get('feature_method', 'fbank')
         xs, ns, gain = self.prepare_finish(began['prep'], pc.target_dB)
-        ps = _Pass(eng, began['ok'], began['n'], began['min_samples'], None, None, decode_all_frames, want_ids, defer, timestamps)
+        ps = _Pass(eng, began['ok'], began['n'], began['min_samples'], None, None, decode_all_frames, want_ids, defer, timestamps, nbest)
         greedy = decoder not in ('ctc_beam_search', 'attention_rescoring', 'attention')
         if greedy and method == 'fbank' and not timestamps:
             return self._greedy_rows(ps, xs, ns, gain)
@@ -370,7 +406,7 @@ class OfflinePasses:
             return self._greedy_calls(ps)
         return {'attention': self._attention, 'attention_rescoring': self._rescoring, 'ctc_beam_search': self._beam_search}[decoder](ps)
 
-    def launch(self, began, decode_all_frames=False, as_tokens=False, defer=False, timestamps=False):
+    def launch(self, began, decode_all_frames=False, as_tokens=False, defer=False, timestamps=False, nbest=None):
         """the pass ``began`` (``begin``) on the current stream and the active lane -> a zero-argument function that waits for it
         and returns [{'text', 'score'}] (``as_tokens``: [(token ids, score)]) in the order of the pass.  Utterances too short for
         one feature frame decode to the empty transcript (the reference's encoder cannot take them either); a digitally silent
@@ -379,16 +415,26 @@ class OfflinePasses:
         so nothing may be waited for here (beam search on the GPU: the prefix search runs on a side stream); otherwise the caller
         calls the function at once.  ``timestamps=True``: every result gains ``'tokens'`` (decoders/ctc_alignment.py).  The pass
         keeps its CTC posteriors on the device until its hypotheses are known and aligns them with one masr_ctc_align call
-        (``attention`` runs the CTC head for that alone); ``ctc_greedy`` takes the route of separate calls whatever the features."""
+        (``attention`` runs the CTC head for that alone); ``ctc_greedy`` takes the route of separate calls whatever the features.
+        ``nbest=N`` (ctc_beam_search only; the caller has validated it): every result gains ``'nbest'``: [{'text', 'score'}]."""
         if timestamps and as_tokens:
             raise Exception(ctc_alignment.DISTRIBUTED_REFUSAL)
+        if nbest is not None and (as_tokens or self.configs.decoder != 'ctc_beam_search'):
+            raise ValueError("nbest needs decoder='ctc_beam_search' and is not available on the sharded path")
         ok = began['ok']
         out = [None] * began['count']
         for i in set(range(began['count'])) - set(ok):
-            out[i] = empty_result(as_tokens, timestamps)
+            out[i] = empty_result(as_tokens, timestamps, nbest)
         if not ok:
             return lambda: out
-        fetch, align = self._decode(began, decode_all_frames, as_tokens or timestamps, defer, timestamps)
+        fetch, align = self._decode(began, decode_all_frames, as_tokens or timestamps, defer, timestamps, nbest)
+        box = self._nbest_box if nbest is not None else None          # (this pass's: the next launch replaces the attribute)
+
+        def entry(e):
+            a, b = e
+            if isinstance(b, str):                     # (score, text)
+                a, b = b, a
+            return {'text': a if isinstance(a, str) else self.text(a), 'score': b}
 
         def collect():
             res = fetch()
@@ -403,5 +449,7 @@ class OfflinePasses:
                 out[i] = {'text': first if isinstance(first, str) else self.text(first), 'score': score}
                 if toks is not None:
                     out[i]['tokens'] = toks[j]
+                if box is not None:
+                    out[i]['nbest'] = [entry(e) for e in box['many'][j]]
             return out
         return collect

@@ -135,14 +135,37 @@ class MASRPredictor:
         vocab = self._text_featurizer.vocab_list
         return ''.join(vocab[j] for j in ids).replace('<space>', ' ')
 
+    def _nbest(self, nbest):
+        """``nbest=N`` of the predict calls -> N, or None when it is not asked for; refused by name where there is no such n-best:
+        a decoder other than ctc_beam_search, N outside 1 .. beam_size, a word-based scorer (its search runs on host threads,
+        whose n-best is LM-free)"""
+        if nbest is None:
+            return None
+        decoder = self.configs.decoder
+        if decoder in ('attention_rescoring', 'attention'):
+            raise ValueError(f"nbest={nbest!r} with decoder={decoder!r}: nbest returns the prefixes of the CTC prefix beam search "
+                             f"(decoder='ctc_beam_search'); the n-best of {decoder} -- its rescored or autoregressive hypotheses -- "
+                             f"is not this one and is not returned")
+        if decoder != 'ctc_beam_search':
+            raise ValueError(f"nbest={nbest!r} with decoder={decoder!r}: only decoder='ctc_beam_search' keeps more than one hypothesis")
+        dec = self.beam_search_decoder
+        nbest = dec.check_nbest(nbest)
+        if dec._ext_scorer is not None and not dec._ext_scorer.is_character_based:
+            raise ValueError('nbest with a word-based language model: that search runs on host threads, whose n-best '
+                             '(masr_beam_search_batch_nbest) is LM-free; use a character-based model or language_model_path=None')
+        return nbest
+
     # ---- offline ------------------------------------------------------------------------------------------------------------
-    def predict(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000, timestamps=False):
+    def predict(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000, timestamps=False, nbest=None):
         """predict.py:167-192: one utterance -> {'text', 'score'} (a batch of one on the device path).  ``timestamps=True``: the
         result gains ``'tokens'``: [{'token', 'start', 'end', 'score'}] per token of the text, in seconds of the utterance (CTC
         forced alignment of the hypothesis on the GPU, decoders/ctc_alignment.py); [] for an empty transcript, None when the CTC
-        trellis holds no path for the hypothesis."""
+        trellis holds no path for the hypothesis.  ``nbest=N`` (decoder ctc_beam_search, 1 <= N <= beam_size): the result gains
+        ``'nbest'``: [{'text', 'score'}] of the (at most) N best prefixes of the search, best first, entry 0 being the result's
+        own text and score; without it the result is what it was, key for key."""
+        nbest = self._nbest(nbest)
         self._no_itn(is_itn)
-        return self._predict_local([self._load_audio(audio_data, sample_rate)], timestamps=timestamps)[0]
+        return self._predict_local([self._load_audio(audio_data, sample_rate)], timestamps=timestamps, nbest=nbest)[0]
 
     def init_vad(self, vad_predictor=None):
         """predict.py:110-115: ``VADPredictor()`` -- the Silero network (on the GPU, weights from the reference's
@@ -156,14 +179,16 @@ class MASRPredictor:
             self.vad_predictor = VADPredictor()
 
     def predict_long(self, audio_data, use_pun=False, is_itn=False, sample_rate=16000, vad_predictor=None, batch_size=32,
-                     timestamps=False):
+                     timestamps=False, nbest=None):
         """predict.py:195-234: long audio -> VAD segments -> text.  The reference recognises the segments one after the
         other (``self.predict`` per segment, :220); here they go through ``predict_batch`` in length-sorted batches of
         ``batch_size`` (one device pass per batch); texts are joined in time order exactly like the reference (:222-227,233).
         A padded batch follows the reference's own batch > 1 semantics (its pad mask keeps one padding-contaminated key per
         shorter utterance, trainer.py:632); ``batch_size=1`` is the reference's per-segment ``predict`` to the bit.
         ``timestamps=True``: the result gains ``'tokens'`` (see ``predict``) over the WHOLE recording in time order: every
-        token's times are shifted by the start of its VAD segment."""
+        token's times are shifted by the start of its VAD segment.  ``nbest=N``: the result gains ``'nbest'``: per VAD segment, in
+        time order, that segment's [{'text', 'score'}] (see ``predict``) -- the segments' alternatives are not multiplied out."""
+        nbest = self._nbest(nbest)
         if use_pun:
             raise Exception('punctuation (PaddleNLP) is outside the hot path and not provided')
         self._no_itn(is_itn)
@@ -185,7 +210,7 @@ class MASRPredictor:
         for lo in range(0, len(order), batch_size):
             idx = order[lo:lo + batch_size]
             for i, res in zip(idx, self._predict_local([AudioSegment.from_ndarray(pieces[i], audio_segment.sample_rate)
-                                                        for i in idx], timestamps=timestamps)):
+                                                        for i in idx], timestamps=timestamps, **({} if nbest is None else {'nbest': nbest}))):
                 results[i] = res
         texts, scores = '', []
         for res in results:
@@ -196,6 +221,8 @@ class MASRPredictor:
         if texts[:1] == '，':
             texts = texts[1:]
         out = {'text': texts, 'score': round(sum(scores) / len(scores), 2) if scores else 0}
+        if nbest is not None:
+            out['nbest'] = [res['nbest'] for res in results]
         if timestamps:
             from masr_amd.decoders.ctc_alignment import join_segments
             out['tokens'] = join_segments([res['tokens'] for res in results],
@@ -212,9 +239,9 @@ class MASRPredictor:
     def _resample_long(self, seg, rate):
         return self._passes.resample_long(seg, rate)
 
-    def _predict_local(self, segs, decode_all_frames=False, as_tokens=False, timestamps=False):
+    def _predict_local(self, segs, decode_all_frames=False, as_tokens=False, timestamps=False, nbest=None):
         """AudioSegments -> [{'text','score'}] on THIS rank's engine: one pass on the current stream, waited for"""
-        return self._passes.launch(self._begin_pass(segs), decode_all_frames, as_tokens, timestamps=timestamps)()
+        return self._passes.launch(self._begin_pass(segs), decode_all_frames, as_tokens, timestamps=timestamps, nbest=nbest)()
 
     def _gpu_search(self):
         """does the configured decoder's prefix search run on the GPU?"""
@@ -243,7 +270,7 @@ class MASRPredictor:
         return 64 if self.configs.use_model == 'efficient_conformer' else 32
 
     def predict_batch(self, audio_list, sample_rate=16000, decode_all_frames=False, batch_size=0, distributed=None,
-                      lengths=None, pass_padded=None, timestamps=False):
+                      lengths=None, pass_padded=None, timestamps=False, nbest=None):
         """Batched offline path (an addition; the reference's only batched consumer is MASRTrainer.evaluate,
         trainer.py:592-651): a list of utterances -> [{'text','score'}] in input order.
 
@@ -262,7 +289,9 @@ class MASRPredictor:
         With an initialised ``torch.distributed`` group (``distributed=None``: automatically when world > 1) the utterances
         are dealt out length-balanced over the ranks -- every rank must call with the same list -- each rank decodes ONLY
         its shard on its own GPU and ONE all-gather of the token ids returns all hypotheses to every rank.
-        ``timestamps=True``: every result gains ``'tokens'`` (see ``predict``); refused on the sharded path."""
+        ``timestamps=True``: every result gains ``'tokens'`` (see ``predict``); refused on the sharded path.
+        ``nbest=N``: every result gains ``'nbest'`` (see ``predict``); refused on the sharded path."""
+        nbest = self._nbest(nbest)
         hints = list(lengths) if lengths is not None else [self._length_hint(a, sample_rate) for a in audio_list]
         if batch_size == 'auto':
             batch_size = self.pass_size()
@@ -280,9 +309,12 @@ class MASRPredictor:
         if timestamps and distributed:
             from masr_amd.decoders.ctc_alignment import DISTRIBUTED_REFUSAL
             raise Exception(DISTRIBUTED_REFUSAL)
+        if nbest is not None and distributed:
+            raise ValueError('nbest is not available on the sharded path (predict_batch under a process group): the all-gather '
+                             'carries one hypothesis per utterance; call with distributed=False')
         if not distributed or not parallel.collectives_on():
             return self._run_sorted(audio_list, sample_rate, hints, list(range(len(audio_list))), decode_all_frames, batch_size,
-                                    as_tokens=False, timestamps=timestamps)
+                                    as_tokens=False, timestamps=timestamps, nbest=nbest)
         shards = parallel.length_balanced_shards(hints, world)
         mine = shards[rank]
         local = self._run_sorted(audio_list, sample_rate, hints, mine, decode_all_frames, batch_size, as_tokens=True)
@@ -296,14 +328,16 @@ class MASRPredictor:
         tok, nt, sc = parallel.gather_sharded_results(tok, nt, sc, shards, len(audio_list))
         return [{'text': self._text(tok[i, :nt[i]]), 'score': float(sc[i])} for i in range(len(audio_list))]
 
-    def predict_batch_deferred(self, audio_list, sample_rate=16000, timestamps=False):
+    def predict_batch_deferred(self, audio_list, sample_rate=16000, timestamps=False, nbest=None):
         """ONE device pass over ``audio_list`` launched, nothing waited for: returns a function that -- when called -- waits for the
         pass and returns [{'text', 'score'}] in input order.  What a serving loop calls for the batch it has formed BEFORE it
         collects the previous one: staging, upload and launches of batch k + 1 then run under the device work of batch k, and
         consecutive calls alternate over the engine's two lanes (not with the prefix search on the GPU, whose launches already
         run beside the next pass).  The reference serves one request at a time (infer_server.py:48-71).
         ``timestamps=True``: every result gains ``'tokens'`` (see ``predict``); the pass stays deferred -- ``ctc_greedy`` aligns
-        behind its collapse, the other decoders align when the function is called and their hypotheses are known."""
+        behind its collapse, the other decoders align when the function is called and their hypotheses are known.
+        ``nbest=N``: every result gains ``'nbest'`` (see ``predict``); the n-best rows come back in the search's one packed copy."""
+        nbest = self._nbest(nbest)
         eng = self.predictor.engine
         # (consecutive calls are the passes: the lane count of a call of several passes)
         lanes = pass_policy(self.configs.decoder, self._gpu_search(), 2, os.environ).lanes
@@ -318,9 +352,9 @@ class MASRPredictor:
                 self._lane1_ordered = True
         began = self._begin_pass([self._load_audio(a, sample_rate) for a in audio_list])
         with eng.on_lane(lane, stream):
-            return self._passes.launch(began, defer=True, timestamps=timestamps)
+            return self._passes.launch(began, defer=True, timestamps=timestamps, nbest=nbest)
 
-    def _run_sorted(self, audio_list, sample_rate, hints, which, decode_all_frames, batch_size, as_tokens, timestamps=False):
+    def _run_sorted(self, audio_list, sample_rate, hints, which, decode_all_frames, batch_size, as_tokens, timestamps=False, nbest=None):
         """decode ``audio_list[i] for i in which`` in length-sorted device passes (cut shortest first, ties in input order -- the
         batches ``evaluate`` forms from a duration-sorted manifest); results in the order of ``which``.  ``pass_plan`` cuts the
         passes and says how they are pipelined: pass k is launched (its prefix search on a side stream), then pass k - depth + 1
@@ -353,7 +387,8 @@ class MASRPredictor:
                 begin(k + 1)
             lane = k % plan.lanes
             with eng.on_lane(lane, lane_streams[lane]):
-                fetch = self._passes.launch(began.pop(k), decode_all_frames, as_tokens, defer=True, timestamps=timestamps)
+                fetch = self._passes.launch(began.pop(k), decode_all_frames, as_tokens, defer=True, timestamps=timestamps,
+                                           nbest=nbest)
             pending.append((order[lo:hi], fetch))
             if len(pending) >= plan.depth:
                 collect(*pending.pop(0))
@@ -402,12 +437,15 @@ class MASRPredictor:
 
     # ---- streaming ------------------------------------------------------------------------------------------------------------
     def predict_stream(self, audio_data, is_end=False, use_pun=False, is_itn=False, channels=1, samp_width=2,
-                       sample_rate=16000, timestamps=False):
+                       sample_rate=16000, timestamps=False, nbest=None):
         """predict.py:237-343: feed raw PCM bytes / ndarray chunks, get the transcript so far ({'text','score'}), or None
         while fewer frames than one decoding window have arrived.  One session of a ``StreamPool``.
         ``timestamps=True``: the result gains ``'tokens'`` as in ``predict`` -- the transcript so far aligned against all frames of
         the utterance so far, in seconds since the utterance began (``StreamPool(timestamps=True)``: its cost is stated there).
-        The flag of an utterance's first call decides for the utterance; change it after ``reset_stream()``."""
+        The flag of an utterance's first call decides for the utterance; change it after ``reset_stream()``.
+        ``nbest=N`` (decoder ctc_beam_search): the result gains ``'nbest'`` as in ``predict``, read from the stream's
+        device-resident search after every decoded chunk; the utterance's first call decides the value, as with ``timestamps``."""
+        nbest = self._nbest(nbest)
         if not self.configs.streaming:
             raise Exception(f"不支持改该模型流式识别，当前模型：{self.configs.use_model}，参数streaming为：{self.configs.streaming}")
         self._no_itn(is_itn)
@@ -417,18 +455,25 @@ class MASRPredictor:
         if self.configs.decoder == 'attention':
             from masr_amd.decoders.attention_decoder import STREAM_REFUSAL
             raise Exception(STREAM_REFUSAL)
-        self._stream_pool_for(bool(timestamps))
+        self._stream_pool_for(bool(timestamps), nbest)
         self._pool.feed(self._session, audio_data, is_end, channels=channels, samp_width=samp_width, sample_rate=sample_rate)
         return self._pool.step()[self._session]
 
-    def _new_stream_pool(self, timestamps):
+    def _new_stream_pool(self, timestamps, nbest=None):
         from masr_amd.serving import StreamPool
-        return StreamPool(self, timestamps=True) if timestamps else StreamPool(self)
+        kw = dict(timestamps=True) if timestamps else {}
+        if nbest is not None:
+            kw['nbest'] = nbest
+        return StreamPool(self, **kw)
 
-    def _stream_pool_for(self, timestamps):
+    def _stream_pool_for(self, timestamps, nbest=None):
         """the single-session pool of ``predict_stream``: made on first use, and made anew at an utterance boundary when the new
         utterance's first call asks for the other kind; inside an utterance the flag cannot change"""
-        if self._pool is not None and self._pool_timestamps != timestamps:
+        if self._pool is not None and getattr(self, '_pool_nbest', None) != nbest and self._stream_running:
+            from masr_amd._lib import MasrError
+            raise MasrError(f'predict_stream: nbest={nbest} inside an utterance that began with nbest={self._pool_nbest}: the first '
+                            f'call of an utterance decides; call reset_stream() first')
+        if self._pool is not None and (self._pool_timestamps != timestamps or getattr(self, '_pool_nbest', None) != nbest):
             if self._stream_running:
                 from masr_amd._lib import MasrError
                 raise MasrError(f'predict_stream: timestamps={timestamps} inside an utterance that began with timestamps='
@@ -437,8 +482,9 @@ class MASRPredictor:
             self._pool.shutdown()
             self._pool = None
         if self._pool is None:
-            self._pool = self._new_stream_pool(timestamps)
+            self._pool = self._new_stream_pool(timestamps) if nbest is None else self._new_stream_pool(timestamps, nbest)
             self._pool_timestamps = timestamps
+            self._pool_nbest = nbest
             self._session = self._pool.open()
         self._stream_running = True
 

@@ -178,7 +178,7 @@ class StreamPool:
 
     ROW_SLAB = 4096                   # rows the posterior pool grows by (V = 4233: 69 MB)
 
-    def __init__(self, predictor, max_frames_out=0, timestamps=False):
+    def __init__(self, predictor, max_frames_out=0, timestamps=False, nbest=None):
         cfg = predictor.configs
         if not cfg.streaming or not ('former' in cfg.use_model or cfg.use_model == 'deepspeech2'):
             raise Exception(f"不支持改该模型流式识别，当前模型：{cfg.use_model}，参数streaming为：{cfg.streaming}")
@@ -190,6 +190,9 @@ class StreamPool:
             raise Exception(STREAM_REFUSAL)
         if cfg.decoder not in ('ctc_greedy', 'ctc_beam_search'):
             raise Exception(f'unknown decoder {cfg.decoder}')
+        # nbest=N (ctc_beam_search sessions): every result gains 'nbest': [{'text', 'score'}], read from the session's
+        # device-resident search behind each decoded chunk (masr_gbeam_nbest); the predictor refuses what has no such n-best
+        self.nbest = predictor._nbest(nbest)
         self.predictor = predictor
         self.engine = predictor.predictor.engine
         self.vocab = predictor._text_featurizer.vocab_list
@@ -647,9 +650,14 @@ class StreamPool:
                     if self.timestamps:
                         self._keep_posteriors(items, probs)
                     for i, (s, _) in enumerate(items):
-                        score, text = s.decoder.decode_chunk(probs=probs[i:i + 1], logits_lens=[probs.shape[1]])
+                        if self.nbest is None:
+                            score, text = s.decoder.decode_chunk(probs=probs[i:i + 1], logits_lens=[probs.shape[1]])
+                            res = {'text': text, 'score': score}
+                        else:
+                            score, text = s.decoder.decode_chunk(probs=probs[i:i + 1], logits_lens=[probs.shape[1]], nbest=self.nbest)
+                            res = {'text': text, 'score': score, 'nbest': [{'text': t, 'score': sc} for sc, t in s.decoder.last_nbest]}
                         s.frames += probs.shape[1]
-                        s.result = s.beam_last = {'text': text, 'score': score}
+                        s.result = s.beam_last = res
                         s.tokens = list(s.decoder.last_tokens)
                     continue
                 probs, idx, mp = eng.encode_chunk(sids, x, want_probs=self.timestamps, want_argmax=True)

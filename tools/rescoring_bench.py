@@ -65,9 +65,10 @@ def main():
     eng.close()
 
 
-def predict_batch_lanes(runs=10, batch=32, passes=2, seconds=10.0, vocab=4233, nbest=10):
+def predict_batch_lanes(runs=10, batch=32, passes=2, seconds=10.0, vocab=4233, nbest=10, first_pass='host'):
     """``predict_batch`` of ``passes`` x ``batch`` utterances with ``decoder: attention_rescoring`` (passes of ``batch``), on one
-    lane and on two (MASR_LANES, read per call), alternating; host wall time per call -> one JSON line"""
+    lane and on two (MASR_LANES, read per call), alternating; host wall time per call -> one JSON line.  ``first_pass``: 'host' or
+    'gpu' (``--first-pass gpu``: attention_rescoring_decoder_conf.first_pass)"""
     import tempfile
     import time
     from masr_amd.predict import MASRPredictor
@@ -81,7 +82,7 @@ def predict_batch_lanes(runs=10, batch=32, passes=2, seconds=10.0, vocab=4233, n
     cfg = {'encoder_conf': {}, 'decoder_conf': dict(attention_heads=4, **dec), 'model_conf': {'ctc_weight': 0.3, 'reverse_weight': 0.3},
            'preprocess_conf': {'feature_method': 'fbank', 'n_mels': 80, 'n_mfcc': 40, 'sample_rate': 16000,
                                'use_dB_normalization': True, 'target_dB': -20},
-           'attention_rescoring_decoder_conf': {'beam_size': nbest}, 'dataset_conf': {'dataset_vocab': vpath},
+           'attention_rescoring_decoder_conf': {'beam_size': nbest, 'first_pass': first_pass}, 'dataset_conf': {'dataset_vocab': vpath},
            'use_model': 'conformer', 'streaming': True, 'decoder': 'attention_rescoring', 'metrics_type': 'cer'}
     pred = MASRPredictor(configs=cfg, use_gpu=True, state_dict=sd)
     n = int(seconds * 16000)
@@ -100,13 +101,13 @@ def predict_batch_lanes(runs=10, batch=32, passes=2, seconds=10.0, vocab=4233, n
                 times[lanes].append(dt)
             lengths = [len(r['text']) for r in res]
     stat = lambda v: {'median_ms': float(np.median(v)), 'min_ms': float(min(v)), 'max_ms': float(max(v))}
-    print(json.dumps({'predict_batch': f'{passes} passes x {batch} utterances x {seconds} s, beam_size {nbest}', 'runs': runs,
+    print(json.dumps({'predict_batch': f'{passes} passes x {batch} utterances x {seconds} s, beam_size {nbest}', 'first_pass': first_pass, 'runs': runs,
                       'one_lane': stat(times['1']), 'two_lanes': stat(times['2']),
                       'winner_tokens_mean': float(np.mean(lengths))}))
 
 
 if __name__ == '__main__':
     if '--predict-batch' in sys.argv:
-        predict_batch_lanes()
+        predict_batch_lanes(first_pass=sys.argv[sys.argv.index('--first-pass') + 1] if '--first-pass' in sys.argv else 'host')
     else:
         main()
