@@ -16,6 +16,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from masr_amd.serving import token_text
+
 
 # ---- process group ---------------------------------------------------------------------------------------------------
 def world_info(group=None):
@@ -305,6 +307,6 @@ class ShardedStreamPool:
                 if row[0] < 0:
                     out[g] = None
                 else:
-                    text = ''.join(self.pool.vocab[k] for k in row[3:3 + row[0]]).replace('<space>', ' ')
+                    text = token_text(self.pool.vocab, row[3:3 + row[0]])
                     out[g] = {'text': text, 'score': float(np.ascontiguousarray(row[1:3]).view(np.float64)[0])}
         return out

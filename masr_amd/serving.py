@@ -4,7 +4,17 @@ BASELINE configs[4]); ``MASRPredictor.predict_stream`` itself is a pool with one
 The reference server holds one MASRPredictor -- i.e. one stream -- per websocket and decodes them one after the other
 (infer_server.py:42-46,103-156).  Here every session keeps the state the reference keeps per stream (samples not yet framed,
 feature frames not yet consumed, decoder history; predict.py:237-343) but the device work of all sessions that have audio
-pending is done together:
+pending is done together.  Three classes:
+
+``StreamPool`` -- the public name and the base: the configuration read, the refusals, ``errors`` / ``device_resampled`` /
+``last_tokens``, and the front of ``feed`` (``route_feed`` + the host decode).  ``StreamPool(predictor, ...)`` returns one of the
+two classes below, chosen once, there; ``pool.framing`` says which.
+
+``CStepPool`` (``framing == 'c'``; ``ctc_greedy`` without timestamps) -- the whole step is ONE C-ABI call (``masr_pool_step``,
+csrc/pool.hip); the class keeps the handles, hands over the fed buffers and builds the text.
+
+``LockStepPool`` (``framing == 'python'``; ``ctc_beam_search``, ``timestamps=True`` and MASR_POOL_PY=1 (A/B), and what the C step
+is tested against):
 
   * ONE ragged feature launch for the new samples of all sessions (dB normalisation gains evaluated like the reference); the
     feature frames never leave the device: they are appended to a device-resident pool [session, frame, F] and the 67-frame
@@ -25,8 +35,8 @@ says which rows are whose: freed rows are reused, so a session's rows are neithe
 aligns the current hypothesis of each session that advanced against ALL of its frames so far with one masr_ctc_align_rows launch
 behind the decoding (csrc/ctc_align.hip reads the frames through the row table: a step packs and copies no history; only the
 step in which the pool outgrows its allocation re-houses it, into twice the rows, every row keeping its number).  The result
-gains ``'tokens'`` as offline (decoders/ctc_alignment.py), in seconds on the session's own clock.  Such a pool runs the python
-framing below for ``ctc_greedy`` too; it costs V * 4 bytes of device memory per encoder frame and session (V = 4233: 17 KB per
+gains ``'tokens'`` as offline (decoders/ctc_alignment.py), in seconds on the session's own clock.  Such a pool is a
+``LockStepPool`` for ``ctc_greedy`` too; it costs V * 4 bytes of device memory per encoder frame and session (V = 4233: 17 KB per
 frame, about 4 MB per 10 s of speech), bounded by the stream's own frame limit and given back on ``reset`` / ``close``.
 """
 import ctypes as C
@@ -49,6 +59,15 @@ DECODING_CHUNK, SUBSAMPLING, CONTEXT = 16, 4, 7
 WINDOW = (DECODING_CHUNK - 1) * SUBSAMPLING + CONTEXT      # 67 feature frames per window
 STRIDE = SUBSAMPLING * DECODING_CHUNK                      # 64
 OVERLAP = CONTEXT - SUBSAMPLING                            # 3 frames carried over
+
+
+def window_plan(n_frames, is_end):
+    """the decoding windows of ``n_frames`` pending feature frames (predict.py:283-306) -> [(first, last)]: full windows only
+    until the stream ends; at its end a short last window too, while it has the context's frames"""
+    if (n_frames < WINDOW and not is_end) or n_frames < CONTEXT:
+        return []
+    left = CONTEXT if is_end else WINDOW
+    return [(cur, min(cur + WINDOW, n_frames)) for cur in range(0, n_frames - left + 1, STRIDE)]
 
 
 def device_resample_enabled():
@@ -83,6 +102,290 @@ def route_feed(audio_data, channels, samp_width, sample_rate, target_rate, c_fra
     else:
         return ('host',)
     return ('raw', x, fmt, resampled_length(x.shape[0], sample_rate, target_rate))
+
+
+def token_text(vocab, tokens):
+    """token ids -> the transcript"""
+    return ''.join([vocab[t] for t in tokens]).replace('<space>', ' ')
+
+
+def greedy_result(vocab, tokens, score):
+    """the partial result of a greedy session from its collapsed best path (token ids, float32 score); the score counts every
+    non-blank frame (repeats included); with none the reference returns 0"""
+    return {'text': token_text(vocab, tokens), 'score': float(score) * 100.0 if tokens else 0}
+
+
+class StreamPool:
+    """``pool = StreamPool(predictor)`` on a streaming MASRPredictor (conformer / squeezeformer / efficient_conformer /
+    uni-directional deepspeech2; ``ctc_greedy`` or ``ctc_beam_search``).  ``open()`` -> handle; ``feed(handle, pcm_bytes,
+    is_end)`` queues audio; ``step()`` processes everything queued since the last step and returns ``{handle: {'text',
+    'score'} or None}`` for the sessions that were fed; ``close(handle)`` releases the stream.  The call returns a ``CStepPool``
+    for greedy sessions and a ``LockStepPool`` for beam search, ``timestamps=True`` and MASR_POOL_PY=1 (``framing``: 'c' /
+    'python'); this class is what the two share.
+
+    ``timestamps=True``: every result gains ``'tokens'`` -- [{'token', 'start', 'end', 'score'}] as ``predict(timestamps=True)``
+    gives offline, [] for an empty transcript, None when the CTC trellis holds no path for the hypothesis (or it is longer than
+    MASR_ALIGN_MAX_TOKENS) -- in seconds since ``open()`` / ``reset()``; ``end`` never exceeds the audio fed so far.  The pool
+    then keeps the CTC posteriors of every open session on the device, V * 4 bytes per encoder frame (V = 4233: 17 KB per frame,
+    about 4 MB per 10 s of speech and session) until ``reset`` / ``close`` gives the rows back, bounded by the stream's frame
+    limit (``max_frames_out`` / the positional table); each step re-aligns the whole history of the sessions that advanced in one
+    launch, and ``ctc_greedy`` sessions run the python framing instead of the C step.  ``posterior_rows`` / ``posteriors`` show
+    what is kept.  Without the flag nothing of this exists and the pool is what it was."""
+
+    def __new__(cls, predictor, max_frames_out=0, timestamps=False, nbest=None):
+        if cls is StreamPool:                                  # the one place the framing is chosen
+            lock_step = predictor.configs.decoder == 'ctc_beam_search' or timestamps or os.environ.get('MASR_POOL_PY')
+            cls = LockStepPool if lock_step else CStepPool
+        return super().__new__(cls)
+
+    def __init__(self, predictor, max_frames_out=0, timestamps=False, nbest=None):
+        cfg = predictor.configs
+        if not cfg.streaming or not ('former' in cfg.use_model or cfg.use_model == 'deepspeech2'):
+            raise Exception(f"不支持改该模型流式识别，当前模型：{cfg.use_model}，参数streaming为：{cfg.streaming}")
+        if cfg.decoder == 'attention_rescoring':
+            from masr_amd.decoders.attention_rescoring import STREAM_REFUSAL
+            raise Exception(STREAM_REFUSAL)
+        if cfg.decoder == 'attention':
+            from masr_amd.decoders.attention_decoder import STREAM_REFUSAL
+            raise Exception(STREAM_REFUSAL)
+        if cfg.decoder not in ('ctc_greedy', 'ctc_beam_search'):
+            raise Exception(f'unknown decoder {cfg.decoder}')
+        # nbest=N (ctc_beam_search sessions): every result gains 'nbest': [{'text', 'score'}], read from the session's
+        # device-resident search behind each decoded chunk (masr_gbeam_nbest); the predictor refuses what has no such n-best
+        self.nbest = predictor._nbest(nbest)
+        self.predictor = predictor
+        self.engine = predictor.predictor.engine
+        self.vocab = predictor._text_featurizer.vocab_list
+        pc = cfg.preprocess_conf
+        self.method = pc.get('feature_method', 'fbank')
+        self.n_mfcc = int(pc.get('n_mfcc', 40))
+        self.sample_rate = int(pc.get('sample_rate', 16000))
+        self.use_db, self.target_db = bool(pc.use_dB_normalization), pc.target_dB
+        self.max_frames_out = max_frames_out
+        self.timestamps = bool(timestamps)
+        self.sessions = {}
+        self.errors = {}              # handle -> message of a session the last step left out (full stream)
+        self.device_resampled = 0     # off-rate feeds handed to the device resampler (masr_pool_step_rates) so far
+
+    def shutdown(self):
+        """release what the pool holds on its engine.  Idempotent; called by ``HipEngine.close()`` for every C-step pool still
+        alive on it, so a pool never touches a destroyed engine."""
+        self._closed = True
+        self.sessions = {}
+
+    def __del__(self):                                         # fallback only: owners call shutdown()
+        try:
+            self.shutdown()
+        except Exception:                                      # noqa: BLE001  (interpreter shutdown)
+            pass
+
+    def _alive(self):
+        if getattr(self, '_closed', False):
+            raise MasrError('this StreamPool is shut down (its engine was closed): open a new pool on a live engine')
+
+    def feed(self, handle, audio_data, is_end=False, channels=1, samp_width=2, sample_rate=16000):
+        """queue raw PCM bytes (or a float / int numpy array) for a session (predict.py:260-272); processed by the next
+        ``step()``.  Audio off the model's rate is queued as fed, with its rate: the step resamples it on the device
+        (``route_feed``; MASR_DEVICE_RESAMPLE=0: on the host, here)."""
+        self._alive()
+        s = self.sessions[handle]
+        route = route_feed(audio_data, channels, samp_width, sample_rate, self.sample_rate, self._C_FRAMING, device_resample_enabled())
+        if route[0] == 'host':
+            if isinstance(audio_data, np.ndarray):
+                seg = AudioSegment.from_ndarray(audio_data, sample_rate)
+            elif isinstance(audio_data, (bytes, bytearray, memoryview)):
+                seg = AudioSegment.from_pcm_bytes(bytes(audio_data), channels=channels, samp_width=samp_width,
+                                                  sample_rate=sample_rate)
+            else:
+                raise Exception(f'不支持该数据类型，当前数据类型为：{type(audio_data)}')
+            if seg.sample_rate != self.sample_rate:
+                seg.resample(self.sample_rate)
+            route = ('host', seg.samples)
+        self._queue(s, route, bool(is_end), sample_rate)
+
+    def last_tokens(self, handle):
+        """token ids behind the session's last partial result (what a multi-GPU front-end gathers instead of text)"""
+        return self.sessions[handle].tokens
+
+    def posterior_rows(self, handle):
+        raise MasrError('this StreamPool keeps no posteriors: create it with timestamps=True')
+
+    posteriors = posterior_rows
+
+
+class _CSession:
+    __slots__ = ('sid', 'result', 'tokens')
+
+    def __init__(self, sid):
+        self.sid = sid
+        self.result = None
+        self.tokens = []              # token ids of the last partial result
+
+
+class CStepPool(StreamPool):
+    """greedy sessions: the whole step is ONE C-ABI call (masr_pool_step, csrc/pool.hip); this class keeps the handles, hands
+    over the fed buffers and builds the text"""
+
+    framing = property(lambda self: 'c')
+    _C_FRAMING = True
+
+    def __init__(self, predictor, max_frames_out=0, timestamps=False, nbest=None):
+        super().__init__(predictor, max_frames_out, timestamps, nbest)
+        self._feeds = []              # (handle, buffer, format, is_end, rate slot) since the last step
+        self._packed = None           # the last step's rows as the C call left them: (device pointer, n, width, handles, host rows)
+        self._rows = None             # ... and as ``last_packed`` hands them out, once asked for
+        self._rate_slots = {}         # source rate -> slot of masr_pool_set_rate
+        self._gain_error = None
+        self._lib = _lib.lib()
+        h = C.c_void_p()
+        method = {'fbank': 0, 'mfcc': 1, 'linear': 2}[self.method]
+        _lib.check(self._lib.masr_pool_create(self.engine.h, method, self.n_mfcc, 1 if self.use_db else 0, float(self.target_db),
+                                              int(max_frames_out), C.byref(h)))
+        self._c = h
+        me = weakref.ref(self)                             # (no reference cycle through the callback: the pool dies with
+
+        def gain_cb(ms_ptr, n, target_db, out_ptr, user):  #  its last reference, not at some later garbage collection)
+            pool = me()
+            return pool._gains(ms_ptr, n, target_db, out_ptr, user) if pool is not None else 1
+        self._gain_cb = _lib.GAIN_FN(gain_cb)              # (kept alive with the pool)
+        self.engine.__dict__.setdefault('_pools', weakref.WeakSet()).add(self)     # HipEngine.close() shuts its pools down first
+
+    def shutdown(self):
+        """destroy the C pool (closes its streams on the engine, synchronises the engine's device)"""
+        c, self._c = getattr(self, '_c', None), None
+        super().shutdown()
+        if c and getattr(self.engine, 'h', None):
+            with torch.cuda.device(self.engine.device):
+                self._lib.masr_pool_destroy(c)
+        self._feeds = []
+
+    def _gains(self, ms_ptr, n, target_db, out_ptr, _user):
+        """masr_gain_fn: the reference's scalar numpy expressions (audio.py:287-304,519-529) on the device's mean squares"""
+        try:
+            ms = np.ctypeslib.as_array(ms_ptr, (n,))
+            np.ctypeslib.as_array(out_ptr, (n,))[:] = reference_gains(ms, self.target_db)
+            return 0
+        except Exception as exc:                               # noqa: BLE001  (re-raised by step() once the C call has returned)
+            self._gain_error = exc
+            return 1
+
+    def open(self):
+        self._alive()
+        h = C.c_int32()
+        _lib.check(self._lib.masr_pool_open(self._c, C.byref(h)))
+        self.sessions[h.value] = _CSession(h.value)
+        return h.value
+
+    def close(self, handle):
+        self._alive()
+        _lib.check(self._lib.masr_pool_close(self._c, int(handle)))
+        self.sessions.pop(handle)
+        self._forget(handle)
+
+    def reset(self, handle):
+        """start a new utterance on an open session (MASRPredictor.reset_stream, predict.py:346-353)"""
+        self._alive()
+        _lib.check(self._lib.masr_pool_reset(self._c, int(handle)))
+        self.sessions[handle] = _CSession(handle)
+        self._forget(handle)
+
+    def _forget(self, handle):
+        self.errors.pop(handle, None)
+        self._feeds = [f for f in self._feeds if f[0] != handle]
+
+    def _rate_slot(self, sample_rate):
+        """the pool's slot for a source rate: registered once (masr_pool_set_rate uploads the filter table)"""
+        slot = self._rate_slots.get(sample_rate)
+        if slot is None:
+            from masr_amd.data_utils.resample import device_table
+            pairs, num_table = device_table(sample_rate, self.sample_rate)
+            out = C.c_int32()
+            _lib.check(self._lib.masr_pool_set_rate(self._c, int(sample_rate), float(self.sample_rate) / sample_rate,
+                                                    pairs.ctypes.data_as(C.c_void_p), pairs.shape[0], num_table, C.byref(out)))
+            slot = self._rate_slots[sample_rate] = out.value
+        return slot
+
+    def _queue(self, s, route, is_end, sample_rate):
+        if route[0] == 'wire':
+            # (the buffer is handed to masr_pool_step as it is: the array keeps the caller's bytes alive until the step has run)
+            self._feeds.append((s.sid, route[1], 0, is_end, -1))
+        elif route[0] == 'raw':
+            self._feeds.append((s.sid, route[1], route[2], is_end, self._rate_slot(sample_rate)))
+        else:
+            self._feeds.append((s.sid, np.ascontiguousarray(route[1], np.float32), 1, is_end, -1))
+
+    @property
+    def last_packed(self):
+        """(device rows [n, tmax + 2] = tokens | count | score bits, tmax, handles) of the sessions that advanced in the last
+        step -- what a multi-GPU front-end all-gathers (parallel.ShardedStreamPool) -- or None"""
+        if self._rows is None and self._packed is not None:
+            ptr, na, width, sids, host = self._packed
+            try:            # zero-copy view of the pool's device rows (valid until the next step)
+                view = type('_DevRows', (), {'__cuda_array_interface__': {'shape': (na, width), 'typestr': '<i4', 'data': (ptr, False),
+                                                                         'version': 2, 'strides': None}})()
+                rows = torch.as_tensor(view, device=self.engine.device)
+            except Exception:                                  # noqa: BLE001
+                rows = torch.from_numpy(host.copy()).to(self.engine.device)
+            self._rows = (rows, width - 2, sids)
+        return self._rows
+
+    def step(self):
+        """one masr_pool_step call over everything fed since the last step"""
+        self._alive()
+        feeds, self._feeds = self._feeds, []
+        self._packed = self._rows = None
+        if not feeds:
+            return {}
+        n = len(feeds)
+        handles = np.fromiter((f[0] for f in feeds), np.int32, n)
+        ptrs = np.fromiter((f[1].__array_interface__['data'][0] for f in feeds), np.uint64, n)
+        counts = np.fromiter((f[1].shape[0] for f in feeds), np.int64, n)
+        fmts = np.fromiter((f[2] for f in feeds), np.int32, n)
+        ends = np.fromiter((f[3] for f in feeds), np.int32, n)
+        ns, width = C.c_int32(), C.c_int32()
+        h_out, st_out, rows_h, rows_d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._gain_error = None
+        slots = np.fromiter((f[4] for f in feeds), np.int32, n)
+        n_off = int((slots >= 0).sum())
+        tail = (C.cast(self._gain_cb, C.c_void_p), None, C.byref(ns), C.byref(h_out), C.byref(st_out), C.byref(rows_h), C.byref(width),
+                C.byref(rows_d), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        head = (self._c, n, handles.ctypes.data, ptrs.ctypes.data, counts.ctypes.data, fmts.ctypes.data, ends.ctypes.data)
+        if n_off:                                              # off-rate feeds: resampled on the device inside the step
+            rc = self._lib.masr_pool_step_rates(*head, slots.ctypes.data, *tail)
+        else:
+            rc = self._lib.masr_pool_step(*head, *tail)
+        if self._gain_error is not None:
+            raise self._gain_error
+        _lib.check(rc)
+        self.device_resampled += n_off
+        m, w = ns.value, width.value
+        hs = np.ctypeslib.as_array(C.cast(h_out, C.POINTER(C.c_int32)), (m,))
+        st = np.ctypeslib.as_array(C.cast(st_out, C.POINTER(C.c_int32)), (m,))
+        na = int((st == 1).sum())
+        rows = np.ctypeslib.as_array(C.cast(rows_h, C.POINTER(C.c_int32)), (na, w)) if na else None
+        out, j, adv = {}, 0, []
+        vocab = self.vocab
+        for h, ok in zip(hs.tolist(), st.tolist()):
+            s = self.sessions[h]
+            if ok < 0:
+                # left out of the step: its stream is full (max_frames_out / the positional table).  The reference asserts there
+                # (embedding.py:48-50); here the OTHER sessions keep their results and this one carries the error until it is reset
+                s.result = None
+                out[h] = None
+                self.errors[h] = 'stream exceeds max_frames_out / max_pos: reset_stream() or close it'
+                continue
+            if not ok:
+                s.result = None
+                out[h] = None
+                continue
+            r = rows[j]
+            j += 1
+            s.tokens = r[:int(r[w - 2])].tolist()
+            s.result = out[h] = greedy_result(vocab, s.tokens, r[w - 1:w].view(np.float32)[0])
+            adv.append(h)
+        if na:
+            self._packed = (rows_d.value, na, w, adv, rows)
+        return out
 
 
 class _HostStage:
@@ -161,52 +464,21 @@ class _Session:
         self.samples = 0              # samples fed so far at the model's rate (timestamps: the end of the session's clock)
 
 
-class StreamPool:
-    """``pool = StreamPool(predictor)`` on a streaming MASRPredictor (conformer / squeezeformer / efficient_conformer /
-    uni-directional deepspeech2; ``ctc_greedy`` or ``ctc_beam_search``).  ``open()`` -> handle; ``feed(handle, pcm_bytes,
-    is_end)`` queues audio; ``step()`` processes everything queued since the last step and returns ``{handle: {'text',
-    'score'} or None}`` for the sessions that were fed; ``close(handle)`` releases the stream.
+class LockStepPool(StreamPool):
+    """the python framing: ragged features into a device-resident frame pool, the windows of all sessions advanced in lock-step
+    through ``masr_encode_chunk``, greedy histories collapsed in one launch or a prefix beam search per session; with
+    ``timestamps=True`` the posterior rows and their alignment (the module docstring has the whole of it)"""
 
-    ``timestamps=True``: every result gains ``'tokens'`` -- [{'token', 'start', 'end', 'score'}] as ``predict(timestamps=True)``
-    gives offline, [] for an empty transcript, None when the CTC trellis holds no path for the hypothesis (or it is longer than
-    MASR_ALIGN_MAX_TOKENS) -- in seconds since ``open()`` / ``reset()``; ``end`` never exceeds the audio fed so far.  The pool
-    then keeps the CTC posteriors of every open session on the device, V * 4 bytes per encoder frame (V = 4233: 17 KB per frame,
-    about 4 MB per 10 s of speech and session) until ``reset`` / ``close`` gives the rows back, bounded by the stream's frame
-    limit (``max_frames_out`` / the positional table); each step re-aligns the whole history of the sessions that advanced in one
-    launch, and ``ctc_greedy`` sessions run the python framing instead of the C step.  ``posterior_rows`` / ``posteriors`` show
-    what is kept.  Without the flag nothing of this exists and the pool is what it was."""
-
+    framing = property(lambda self: 'python')
+    _C_FRAMING = False
     ROW_SLAB = 4096                   # rows the posterior pool grows by (V = 4233: 69 MB)
 
     def __init__(self, predictor, max_frames_out=0, timestamps=False, nbest=None):
-        cfg = predictor.configs
-        if not cfg.streaming or not ('former' in cfg.use_model or cfg.use_model == 'deepspeech2'):
-            raise Exception(f"不支持改该模型流式识别，当前模型：{cfg.use_model}，参数streaming为：{cfg.streaming}")
-        if cfg.decoder == 'attention_rescoring':
-            from masr_amd.decoders.attention_rescoring import STREAM_REFUSAL
-            raise Exception(STREAM_REFUSAL)
-        if cfg.decoder == 'attention':
-            from masr_amd.decoders.attention_decoder import STREAM_REFUSAL
-            raise Exception(STREAM_REFUSAL)
-        if cfg.decoder not in ('ctc_greedy', 'ctc_beam_search'):
-            raise Exception(f'unknown decoder {cfg.decoder}')
-        # nbest=N (ctc_beam_search sessions): every result gains 'nbest': [{'text', 'score'}], read from the session's
-        # device-resident search behind each decoded chunk (masr_gbeam_nbest); the predictor refuses what has no such n-best
-        self.nbest = predictor._nbest(nbest)
-        self.predictor = predictor
-        self.engine = predictor.predictor.engine
-        self.vocab = predictor._text_featurizer.vocab_list
-        pc = cfg.preprocess_conf
-        self.method = pc.get('feature_method', 'fbank')
-        self.n_mfcc = int(pc.get('n_mfcc', 40))
-        self.sample_rate = int(pc.get('sample_rate', 16000))
-        self.use_db, self.target_db = bool(pc.use_dB_normalization), pc.target_dB
+        super().__init__(predictor, max_frames_out, timestamps, nbest)
         self.min_samples = 320 if self.method == 'linear' else 400
-        self.beam = cfg.decoder == 'ctc_beam_search'
-        self.max_frames_out = max_frames_out
-        self.sessions = {}
-        self.errors = {}              # handle -> message of a session the last step left out (full stream)
-        self._fed = {}
+        self.beam = predictor.configs.decoder == 'ctc_beam_search'
+        self._last_packed = None
+        self._fed = {}                # handle -> is_end of the sessions fed since the last step
         self._free_rows = []
         self._hist_idx = torch.zeros(0, 0, dtype=torch.int32, device=self.engine.device)      # [rows, frames]
         self._hist_mp = torch.zeros(0, 0, dtype=torch.float32, device=self.engine.device)
@@ -214,35 +486,11 @@ class StreamPool:
         self._feat_cap = 512                                                                   # frames per session row
         self._feat = torch.zeros(0, self._feat_cap, self.feat_dim, dtype=torch.float32, device=self.engine.device)
         self._stage = _HostStage(self.engine.device)
-        # greedy sessions: the whole step is ONE C-ABI call (masr_pool_step, csrc/pool.hip); this class keeps the handles, hands
-        # over the fed buffers and builds the text.  Beam-search sessions (a device-resident prefix search per session) and
-        # MASR_POOL_PY=1 (A/B) keep the python framing below.
-        self._c = None
-        self._feeds = []
-        self._packed = None
-        self._rate_slots = {}         # source rate -> slot of masr_pool_set_rate
-        self.device_resampled = 0     # off-rate feeds handed to the device resampler (masr_pool_step_rates) so far
-        self.timestamps = bool(timestamps)
         if self.timestamps:
             from masr_amd.posterior_rows import RowAllocator
             self._alloc = RowAllocator(self.ROW_SLAB)
             self._post = torch.empty(0, self.engine.vocab_size, dtype=torch.float32, device=self.engine.device)    # the row pool
             self._reduction = self.engine.frame_reduction()
-        if not self.beam and not self.timestamps and not os.environ.get('MASR_POOL_PY'):
-            self._lib = _lib.lib()
-            h = C.c_void_p()
-            method = {'fbank': 0, 'mfcc': 1, 'linear': 2}[self.method]
-            _lib.check(self._lib.masr_pool_create(self.engine.h, method, self.n_mfcc, 1 if self.use_db else 0, float(self.target_db),
-                                                  int(max_frames_out), C.byref(h)))
-            self._c = h
-            self._gain_error = None
-            me = weakref.ref(self)                             # (no reference cycle through the callback: the pool dies with
-
-            def gain_cb(ms_ptr, n, target_db, out_ptr, user):  #  its last reference, not at some later garbage collection)
-                pool = me()
-                return pool._gains(ms_ptr, n, target_db, out_ptr, user) if pool is not None else 1
-            self._gain_cb = _lib.GAIN_FN(gain_cb)              # (kept alive with the pool)
-            self.engine.__dict__.setdefault('_pools', weakref.WeakSet()).add(self)     # HipEngine.close() shuts its pools down first
 
     # ---- session life cycle ---------------------------------------------------------------------------------------------
     def _grow(self, rows, frames):
@@ -268,44 +516,8 @@ class StreamPool:
     def _new_decoder(self):
         return self.predictor.beam_search_decoder.fork() if self.beam else None
 
-    def shutdown(self):
-        """destroy the C pool (closes its streams on the engine, synchronises the engine's device).  Idempotent; called by
-        ``HipEngine.close()`` for every pool still alive on it, so a pool never touches a destroyed engine."""
-        c, self._c = getattr(self, '_c', None), None
-        self._closed = True
-        if c is not None and getattr(self.engine, 'h', None):
-            with torch.cuda.device(self.engine.device):
-                self._lib.masr_pool_destroy(c)
-        self.sessions = {}
-        self._feeds = []
-
-    def __del__(self):                                         # fallback only: owners call shutdown()
-        try:
-            self.shutdown()
-        except Exception:                                      # noqa: BLE001  (interpreter shutdown)
-            pass
-
-    def _gains(self, ms_ptr, n, target_db, out_ptr, _user):
-        """masr_gain_fn: the reference's scalar numpy expressions (audio.py:287-304,519-529) on the device's mean squares"""
-        try:
-            ms = np.ctypeslib.as_array(ms_ptr, (n,))
-            np.ctypeslib.as_array(out_ptr, (n,))[:] = reference_gains(ms, self.target_db)
-            return 0
-        except Exception as exc:                               # noqa: BLE001  (re-raised by step() once the C call has returned)
-            self._gain_error = exc
-            return 1
-
-    def _alive(self):
-        if getattr(self, '_closed', False):
-            raise MasrError('this StreamPool is shut down (its engine was closed): open a new pool on a live engine')
-
     def open(self):
         self._alive()
-        if self._c is not None:
-            h = C.c_int32()
-            _lib.check(self._lib.masr_pool_open(self._c, C.byref(h)))
-            self.sessions[h.value] = _Session(h.value, 0, None)
-            return h.value
         sid = self.engine.stream_open(self.max_frames_out)
         used = {s.row for s in self.sessions.values()}
         row = self._free_rows.pop() if self._free_rows else len(used)
@@ -315,12 +527,6 @@ class StreamPool:
 
     def close(self, handle):
         self._alive()
-        if self._c is not None:
-            _lib.check(self._lib.masr_pool_close(self._c, int(handle)))
-            self.sessions.pop(handle)
-            self.errors.pop(handle, None)
-            self._feeds = [f for f in self._feeds if f[0] != handle]
-            return
         self.engine.stream_close(handle)
         s = self.sessions.pop(handle)
         if s.decoder is not None:
@@ -333,12 +539,6 @@ class StreamPool:
     def reset(self, handle):
         """start a new utterance on an open session (MASRPredictor.reset_stream, predict.py:346-353)"""
         self._alive()
-        if self._c is not None:
-            _lib.check(self._lib.masr_pool_reset(self._c, int(handle)))
-            self.sessions[handle] = _Session(handle, 0, None)
-            self.errors.pop(handle, None)
-            self._feeds = [f for f in self._feeds if f[0] != handle]
-            return
         self.engine.stream_reset(handle)
         old = self.sessions[handle]
         if old.decoder is not None:
@@ -348,72 +548,23 @@ class StreamPool:
         if self.timestamps:
             self._alloc.release(handle)
 
-    def _rate_slot(self, sample_rate):
-        """the pool's slot for a source rate: registered once (masr_pool_set_rate uploads the filter table)"""
-        slot = self._rate_slots.get(sample_rate)
-        if slot is None:
-            from masr_amd.data_utils.resample import device_table
-            pairs, num_table = device_table(sample_rate, self.sample_rate)
-            out = C.c_int32()
-            _lib.check(self._lib.masr_pool_set_rate(self._c, int(sample_rate), float(self.sample_rate) / sample_rate,
-                                                    pairs.ctypes.data_as(C.c_void_p), pairs.shape[0], num_table, C.byref(out)))
-            slot = self._rate_slots[sample_rate] = out.value
-        return slot
-
-    def feed(self, handle, audio_data, is_end=False, channels=1, samp_width=2, sample_rate=16000):
-        """queue raw PCM bytes (or a float / int numpy array) for a session (predict.py:260-272); processed by the next
-        ``step()``.  Audio off the model's rate is queued as fed, with its rate: the step resamples it on the device
-        (``route_feed``; MASR_DEVICE_RESAMPLE=0: on the host, here)."""
-        self._alive()
-        s = self.sessions[handle]
-        route = route_feed(audio_data, channels, samp_width, sample_rate, self.sample_rate, self._c is not None,
-                           device_resample_enabled())
-        wire = route[0] == 'wire'
-        if wire and self._c is not None:
-            # (the buffer is handed to masr_pool_step as it is: the array keeps the caller's bytes alive until the step has run)
-            self._feeds.append((handle, route[1], 0, bool(is_end), -1))
-            return
-        if route[0] == 'raw':
-            self._feeds.append((handle, route[1], route[2], bool(is_end), self._rate_slot(sample_rate)))
-            return
-        if wire:
-            # the common wire format: kept as int16 (a view of the caller's bytes); x / 2^15 -- the float32 value
-            # from_pcm_bytes produces -- happens when the step stages the samples for the device
-            s.fresh.append(route[1])
-        else:
-            if isinstance(audio_data, np.ndarray):
-                seg = AudioSegment.from_ndarray(audio_data, sample_rate)
-            elif isinstance(audio_data, (bytes, bytearray, memoryview)):
-                seg = AudioSegment.from_pcm_bytes(bytes(audio_data), channels=channels, samp_width=samp_width,
-                                                  sample_rate=sample_rate)
-            else:
-                raise Exception(f'不支持该数据类型，当前数据类型为：{type(audio_data)}')
-            if seg.sample_rate != self.sample_rate:
-                seg.resample(self.sample_rate)
-            if self._c is not None:
-                self._feeds.append((handle, np.ascontiguousarray(seg.samples, np.float32), 1, bool(is_end), -1))
-                return
-            s.fresh.append(seg.samples)
-        self._fed[handle] = bool(is_end) or self._fed.get(handle, False)
-
-    def last_tokens(self, handle):
-        """token ids behind the session's last partial result (what a multi-GPU front-end gathers instead of text)"""
-        return self.sessions[handle].tokens
+    def _queue(self, s, route, is_end, sample_rate):
+        # wire PCM, the common format, is kept as int16 (a view of the caller's bytes); x / 2^15 -- the float32 value
+        # from_pcm_bytes produces -- happens when the step stages the samples for the device
+        s.fresh.append(route[1])
+        self._fed[s.sid] = is_end or self._fed.get(s.sid, False)
 
     # ---- timestamps: the posterior history and its alignment -----------------------------------------------------------------------
     def posterior_rows(self, handle):
         """timestamps pool: the rows of the pool's posterior matrix that hold the session's encoder frames, in frame order (int64)"""
-        self._needs_timestamps()
+        if not self.timestamps:
+            return super().posterior_rows(handle)
         return np.asarray(self._alloc.rows_of(self.sessions[handle].sid), np.int64)
 
     def posteriors(self, handle):
         """timestamps pool: the CTC-head probabilities of all frames of the session so far, gathered -> [frames, V] device tensor"""
         rows = torch.from_numpy(self.posterior_rows(handle)).to(self.engine.device)
         return self._post[rows]
-
-    def _needs_timestamps(self):
-        if not self.timestamps:
-            raise MasrError('this StreamPool keeps no posteriors: create it with timestamps=True')
 
     def _keep_posteriors(self, items, probs):
         """append the rows ``probs`` [n, Tq, V] of one lock-step call to the sessions' histories: n * Tq rows of the pool, taken
@@ -529,89 +680,13 @@ class StreamPool:
 
     @property
     def last_packed(self):
-        """(device rows [n, tmax + 2] = tokens | count | score bits, tmax, handles) of the sessions that advanced in the last
-        step -- what a multi-GPU front-end all-gathers (parallel.ShardedStreamPool) -- or None"""
-        pk = self._packed
-        if pk is not None and not torch.is_tensor(pk[0]):
-            ptr, na, width, sids, host = pk
-            try:            # zero-copy view of the pool's device rows (valid until the next step)
-                view = type('_DevRows', (), {'__cuda_array_interface__': {'shape': (na, width), 'typestr': '<i4', 'data': (ptr, False),
-                                                                         'version': 2, 'strides': None}})()
-                rows = torch.as_tensor(view, device=self.engine.device)
-            except Exception:                                  # noqa: BLE001
-                rows = torch.from_numpy(host.copy()).to(self.engine.device)
-            pk = self._packed = (rows, width - 2, sids)
-        return pk
-
-    @last_packed.setter
-    def last_packed(self, value):
-        self._packed = value
-
-    def _step_c(self):
-        """one masr_pool_step call over everything fed since the last step"""
-        feeds, self._feeds = self._feeds, []
-        self._packed = None
-        if not feeds:
-            return {}
-        n = len(feeds)
-        handles = np.fromiter((f[0] for f in feeds), np.int32, n)
-        ptrs = np.fromiter((f[1].__array_interface__['data'][0] for f in feeds), np.uint64, n)
-        counts = np.fromiter((f[1].shape[0] for f in feeds), np.int64, n)
-        fmts = np.fromiter((f[2] for f in feeds), np.int32, n)
-        ends = np.fromiter((f[3] for f in feeds), np.int32, n)
-        ns, width = C.c_int32(), C.c_int32()
-        h_out, st_out, rows_h, rows_d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self._gain_error = None
-        slots = np.fromiter((f[4] for f in feeds), np.int32, n)
-        n_off = int((slots >= 0).sum())
-        tail = (C.cast(self._gain_cb, C.c_void_p), None, C.byref(ns), C.byref(h_out), C.byref(st_out), C.byref(rows_h), C.byref(width),
-                C.byref(rows_d), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        head = (self._c, n, handles.ctypes.data, ptrs.ctypes.data, counts.ctypes.data, fmts.ctypes.data, ends.ctypes.data)
-        if n_off:                                              # off-rate feeds: resampled on the device inside the step
-            rc = self._lib.masr_pool_step_rates(*head, slots.ctypes.data, *tail)
-        else:
-            rc = self._lib.masr_pool_step(*head, *tail)
-        if self._gain_error is not None:
-            raise self._gain_error
-        _lib.check(rc)
-        self.device_resampled += n_off
-        m, w = ns.value, width.value
-        hs = np.ctypeslib.as_array(C.cast(h_out, C.POINTER(C.c_int32)), (m,))
-        st = np.ctypeslib.as_array(C.cast(st_out, C.POINTER(C.c_int32)), (m,))
-        na = int((st == 1).sum())
-        rows = np.ctypeslib.as_array(C.cast(rows_h, C.POINTER(C.c_int32)), (na, w)) if na else None
-        out, j, adv = {}, 0, []
-        vocab = self.vocab
-        for h, ok in zip(hs.tolist(), st.tolist()):
-            s = self.sessions[h]
-            if ok < 0:
-                # left out of the step: its stream is full (max_frames_out / the positional table).  The reference asserts there
-                # (embedding.py:48-50); here the OTHER sessions keep their results and this one carries the error until it is reset
-                s.result = None
-                out[h] = None
-                self.errors[h] = 'stream exceeds max_frames_out / max_pos: reset_stream() or close it'
-                continue
-            if not ok:
-                s.result = None
-                out[h] = None
-                continue
-            r = rows[j]
-            j += 1
-            nt = int(r[w - 2])
-            s.tokens = r[:nt].tolist()
-            text = ''.join([vocab[t] for t in s.tokens]).replace('<space>', ' ')
-            # the score counts every non-blank frame (repeats included); with none the reference returns 0
-            s.result = out[h] = {'text': text, 'score': float(r[w - 1:w].view(np.float32)[0]) * 100.0 if nt > 0 else 0}
-            adv.append(h)
-        if na:
-            self._packed = (rows_d.value, na, w, adv, rows)
-        return out
+        """(device rows [n, tmax + 2] = tokens | count | score bits, tmax, handles) of the greedy sessions that advanced in the
+        last step -- what a multi-GPU front-end all-gathers (parallel.ShardedStreamPool) -- or None"""
+        return self._last_packed
 
     def step(self):
         self._alive()
-        if self._c is not None:
-            return self._step_c()
-        self.last_packed = None
+        self._last_packed = None
         fed, self._fed = self._fed, {}
         if not fed:
             return {}
@@ -620,16 +695,9 @@ class StreamPool:
         self._stage.begin()
         self._featurize(sess)
         # windows of every session (predict.py:283-306), advanced in lock-step
-        plans = []
+        plans = [window_plan(s.nf, fed[s.sid]) for s in sess]
         for s in sess:
-            nfr = s.nf
-            is_end = fed[s.sid]
             s.result = None
-            if (nfr < WINDOW and not is_end) or nfr < CONTEXT:
-                plans.append([])
-                continue
-            left = CONTEXT if is_end else WINDOW
-            plans.append([(cur, min(cur + WINDOW, nfr)) for cur in range(0, nfr - left + 1, STRIDE)])
         for k in range(max((len(p) for p in plans), default=0)):
             groups = {}
             for s, p in zip(sess, plans):
@@ -681,14 +749,12 @@ class StreamPool:
             tok, ntok, score = eng.ctc_collapse(self._hist_idx[rows, :tmax].contiguous(), self._hist_mp[rows, :tmax].contiguous(), nfr)
             # one copy back: [tokens | count | score bits]
             packed_dev = torch.cat([tok, ntok[:, None], score.view(torch.int32)[:, None]], 1)
-            self.last_packed = (packed_dev, tmax, [s.sid for s in adv])       # device copy: what a multi-GPU gather ships
+            self._last_packed = (packed_dev, tmax, [s.sid for s in adv])      # device copy: what a multi-GPU gather ships
             packed = packed_dev.cpu().numpy()
             tok, ntok, score = packed[:, :tmax], packed[:, tmax], packed[:, tmax + 1].copy().view(np.float32)
             for j, s in enumerate(adv):
                 s.tokens = tok[j, :ntok[j]].tolist()
-                text = ''.join(self.vocab[t] for t in s.tokens).replace('<space>', ' ')
-                # the score counts every non-blank frame (repeats included); with none the reference returns 0
-                s.result = {'text': text, 'score': float(np.float32(score[j])) * 100.0 if ntok[j] > 0 else 0}
+                s.result = greedy_result(self.vocab, s.tokens, score[j])
         if self.timestamps:
             self._stamp([s for s, p in zip(sess, plans) if p])
         self._stage.end()

@@ -517,7 +517,7 @@ def test_c_pool_step_equals_the_python_framing(predictor, monkeypatch):
     py_pool = StreamPool(predictor)
     monkeypatch.delenv('MASR_POOL_PY')
     c_pool = StreamPool(predictor)
-    assert py_pool._c is None and c_pool._c is not None
+    assert py_pool.framing == 'python' and c_pool.framing == 'c'
     rng = np.random.default_rng(11)
     script = []                                        # per step: list of (session, samples, is_end)
     cuts = {1: sorted(rng.integers(1, len(pcm) - 1, 40).tolist()), 2: list(range(800, 60000, 800)), 3: [30000, 90000, 90000]}

@@ -273,7 +273,7 @@ def test_pool_python_framing_keeps_the_host_path(monkeypatch, predictor, audio):
         h = pool.open()
         pool.feed(h, audio[8000][:12000].tobytes(), is_end=True, sample_rate=8000)
         py = pool.step()[h]
-        assert pool._c is None and pool.device_resampled == 0
+        assert pool.framing == 'python' and pool.device_resampled == 0
     finally:
         pool.shutdown()
     monkeypatch.delenv('MASR_POOL_PY')

@@ -292,7 +292,7 @@ def test_tokens_of_every_step_equal_the_cpu_alignment_of_the_kept_posteriors(tmp
     from masr_amd.serving import StreamPool
     pred = _predictor(str(tmp_path), family, decoder)
     pool = StreamPool(pred, timestamps=True)
-    assert pool._c is None and pool.engine.frame_reduction() == (4 if family == 'conformer' else 8)
+    assert pool.framing == 'python' and pool.engine.frame_reduction() == (4 if family == 'conformer' else 8)
     seen = {'results': 0, 'tokens': 0}
 
     def check(i, h, res, samples):
@@ -393,7 +393,7 @@ def test_without_the_flag_nothing_changes(tmp_path, decoder):
     from masr_amd.serving import StreamPool
     pred = _predictor(str(tmp_path), 'conformer', decoder)
     plain, timed = StreamPool(pred), StreamPool(pred, timestamps=True)
-    assert not plain.timestamps and (plain._c is not None) == (decoder == 'ctc_greedy') and timed._c is None
+    assert not plain.timestamps and (plain.framing == 'c') == (decoder == 'ctc_greedy') and timed.framing == 'python'
     _, want = _drive(timed, _schedule())
     _, got = _drive(plain, _schedule())
     n = 0

@@ -148,7 +148,7 @@ def main():
         finally:
             os.environ.pop('MASR_POOL_PY', None)
         try:
-            assert (pool._c is not None) == (decoder == 'ctc_greedy' and not stamps and not py)
+            assert (pool.framing == 'c') == (decoder == 'ctc_greedy' and not stamps and not py)
             hs = [pool.open() for _ in range(n)]
             for _ in range(args.warmup):
                 utterance_ms(pool, hs, chunks)
