@@ -419,6 +419,11 @@ int masr_pool_step_rates(masr_pool* p, int32_t n_feeds, const int32_t* feed_hand
 /* diagnostics: host time of masr_pool_step per phase, accumulated over `steps` calls (ms): assemble the samples | upload + mean
  * squares + wait | gains | features + frame bookkeeping | windows (lock-step chunk steps enqueued) | collapse + copy back + wait */
 int masr_pool_profile(masr_pool* p, double* phase_ms, int64_t* steps, int32_t reset);
+/* The decoding windows a session with n_frames pending feature frames advances by in one step (csrc/pool_plan.h: the function the
+ * step's room check and its lock-step loop use; predict.py:283-306): 67-frame windows a stride of 64 apart, and at the end of a
+ * stream (is_end != 0) a short last window while 7 frames remain.  No pool, no engine, no GPU; no process state is read or written.
+ *   first_last [cap][2]: (first, last) of the first min(cap, *n_windows) windows; *n_windows: always the full count */
+int masr_pool_window_plan(int32_t n_frames, int32_t is_end, int32_t* first_last, int32_t cap, int32_t* n_windows);
 /* encoder frames that T feature frames give (Conv2dSubsampling4 / 6 / 8 by masr_config.reserved[3], subsampling.py:65-211; halved once more behind the Efficient
  * Conformer's stride layer) and the engine's geometry -- what a host needs to size the buffers above */
 int masr_encoder_frames(masr_engine* e, int32_t feature_frames, int32_t* encoder_frames);

@@ -90,6 +90,7 @@ SIGNATURES = {
     'masr_pool_step': [_P, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_I), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
                        C.POINTER(_I), C.POINTER(_P), _P],
     'masr_pool_profile': [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), _I],
+    'masr_pool_window_plan': [_I, _I, C.POINTER(_I), _I, C.POINTER(_I)],
     'masr_encoder_frames': [_P, _I, C.POINTER(_I)],
     'masr_frame_reduction': [_P, C.POINTER(_I)],
     'masr_ctc_align': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],

@@ -21,7 +21,7 @@ EXPERIMENTS = os.environ.get('MASR_BUILD_EXPERIMENTS') == '1'
 EXPERIMENT_SOURCES = ['gemm_bf16x3.hip', 'ffn_x3.hip', 'ffn_coop.hip', 'ffn_dual.hip']
 if EXPERIMENTS:
     SOURCES = SOURCES + EXPERIMENT_SOURCES
-HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'knobs.h'), os.path.join(CSRC, 'ffn_plan.h'),
+HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'knobs.h'), os.path.join(CSRC, 'ffn_plan.h'), os.path.join(CSRC, 'pool_plan.h'),
            os.path.join(CSRC, 'lm_scorer.h'), os.path.join(CSRC, 'engine_state.h'), os.path.join(CSRC, 'engine_encoder.h'),
            os.path.join(os.path.dirname(ROOT), 'include', 'masr_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value'] + (['-DMASR_EXPERIMENTS=1'] if EXPERIMENTS else [])

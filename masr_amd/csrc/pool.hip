@@ -27,6 +27,7 @@
 #include "../../include/masr_hip.h"
 #include "common.h"
 #include "engine_state.h"      // masr::subsampled_frames and masr::engine_fail, nothing else: the engine is used through the C ABI
+#include "pool_plan.h"         // the decoding windows (kWindow, kStride, kOverlap; pool_windows) and pool_feature_frames
 
 using namespace masr;
 
@@ -44,11 +45,6 @@ using namespace masr;
 
 namespace {
 
-// chunked decoding geometry of the reference facade (predict.py:283-290): 16 encoder frames per chunk, subsampling 4, context 7
-constexpr int kDecodingChunk = 16, kSubsampling = 4, kContext = 7;
-constexpr int kWindow = (kDecodingChunk - 1) * kSubsampling + kContext;      // 67 feature frames per window
-constexpr int kStride = kSubsampling * kDecodingChunk;                       // 64
-constexpr int kOverlap = kContext - kSubsampling;                            // 3 frames carried over
 constexpr int64_t kMaxFeedSamples = (int64_t)1 << 28;                        // per feed (4.6 h at 16 kHz): anything above is a caller bug
 
 struct Dev {                     // grow-only device buffer; `keep` bytes of the old contents survive a growth
@@ -146,14 +142,17 @@ struct masr_pool {
     int rows_cap = 0, feat_cap = 512;
     Dev hist_idx, hist_mp;        // [hist_rows][hist_cap]
     int hist_rows = 0, hist_cap = 0;
-    // per-step work buffers
-    Dev samples, lens, ms, gains, feats, win, idx, mp, segs, meta, rows_out;
-    // off-rate feeds: rate slots (host copy + device table, filter tables), the step's raw bytes + descriptors, the tails
+    // per-step work buffers; of off-rate feeds: the step's raw bytes + descriptors, the tails
+    Dev samples, lens, ms, gains, feats, win, idx, mp, segs, meta, rows_out, raw, tails_dev;
+    // every Dev above, for masr_pool_destroy
+    std::vector<Dev*> buffers() {
+        return {&feat, &hist_idx, &hist_mp, &samples, &lens, &ms, &gains, &feats, &win, &idx, &mp, &segs, &meta, &rows_out, &raw, &tails_dev};
+    }
+    // off-rate feeds: rate slots (host copy + device table, filter tables), the tails on their way back
     std::vector<masr_resample_rate> rates;
     std::map<int, int> rate_of;   // sr_orig -> slot
     std::vector<void*> rate_tables;
     masr_resample_rate* rates_dev = nullptr;
-    Dev raw, tails_dev;
     std::vector<Tail> tails;      // not yet copied into their sessions
     Pinned pin;
     hipEvent_t ev = nullptr;      // the previous step's copies out of `pin`
@@ -168,8 +167,16 @@ struct masr_pool {
 
 namespace {
 
-int feature_frames(const masr_pool* p, long n) {
-    return n >= p->min_samples ? (int)((n - p->min_samples) / 160 + 1) : 0;
+// d, [old_rows][old_row_bytes], becomes [rows][new_row_bytes] with the old rows at the front of the first old_rows new ones
+int regrow_rows(Dev& d, size_t rows, size_t old_rows, size_t old_row_bytes, size_t new_row_bytes, hipStream_t s) {
+    Dev nd;
+    PCHK(nd.ensure(rows * new_row_bytes, 0, s));
+    if (d.p && old_rows && old_row_bytes)
+        PHIP(hipMemcpy2DAsync(nd.p, new_row_bytes, d.p, old_row_bytes, old_row_bytes, old_rows, hipMemcpyDeviceToDevice, s));
+    PHIP(hipStreamSynchronize(s));
+    d.release();
+    d = nd;
+    return 0;
 }
 
 // make the histories at least [rows][frames] and the frame pool at least [rows][feat_cap] (contents kept)
@@ -177,16 +184,8 @@ int grow_state(masr_pool* p, int rows, int frames, hipStream_t s) {
     if (rows > p->hist_rows || frames > p->hist_cap) {
         const int r1 = rows <= p->hist_rows ? p->hist_rows : std::max({rows, 2 * p->hist_rows, 16});
         const int f1 = frames <= p->hist_cap ? p->hist_cap : std::max({frames, 2 * p->hist_cap, 256});
-        for (Dev* d : {&p->hist_idx, &p->hist_mp}) {
-            Dev nd;
-            PCHK(nd.ensure((size_t)r1 * f1 * 4, 0, s));
-            if (d->p && p->hist_rows && p->hist_cap)
-                PHIP(hipMemcpy2DAsync(nd.p, (size_t)f1 * 4, d->p, (size_t)p->hist_cap * 4, (size_t)p->hist_cap * 4, p->hist_rows,
-                                      hipMemcpyDeviceToDevice, s));
-            PHIP(hipStreamSynchronize(s));
-            d->release();
-            *d = nd;
-        }
+        for (Dev* d : {&p->hist_idx, &p->hist_mp})
+            PCHK(regrow_rows(*d, (size_t)r1, (size_t)p->hist_rows, (size_t)p->hist_cap * 4, (size_t)f1 * 4, s));
         p->hist_rows = r1;
         p->hist_cap = f1;
     }
@@ -200,14 +199,7 @@ int grow_state(masr_pool* p, int rows, int frames, hipStream_t s) {
 
 // wider rows of the frame pool (a whole utterance fed in one call)
 int widen_feat(masr_pool* p, int cap, hipStream_t s) {
-    Dev nd;
-    const size_t row_old = (size_t)p->feat_cap * p->F * 4, row_new = (size_t)cap * p->F * 4;
-    PCHK(nd.ensure((size_t)p->rows_cap * row_new, 0, s));
-    if (p->feat.p && p->rows_cap)
-        PHIP(hipMemcpy2DAsync(nd.p, row_new, p->feat.p, row_old, row_old, p->rows_cap, hipMemcpyDeviceToDevice, s));
-    PHIP(hipStreamSynchronize(s));
-    p->feat.release();
-    p->feat = nd;
+    PCHK(regrow_rows(p->feat, (size_t)p->rows_cap, (size_t)p->rows_cap, (size_t)p->feat_cap * p->F * 4, (size_t)cap * p->F * 4, s));
     p->feat_cap = cap;
     return 0;
 }
@@ -248,6 +240,485 @@ int upload(masr_pool* p, Dev& dst, const void* host_in_pin, size_t n, hipStream_
     return 0;
 }
 
+// One masr_pool_step_rates call: its arguments, and what its phases (below, in the order they run) hand to each other.  The
+// per-session vectors are indexed alike: session i of the step is sess[i], with end_flag[i], feeds_of[i], len[i], fresh[i], ...
+struct Step {
+    // the call
+    int32_t n_feeds;
+    const int32_t* feed_handle;
+    const void* const* feed_samples;
+    const int64_t* feed_n;
+    const int32_t *feed_format, *feed_is_end, *feed_rate_slot;
+    masr_gain_fn gain_fn;
+    void* gain_user;
+    int32_t* n_sessions;
+    const int32_t **handles_out, **state_out, **rows_host;
+    int32_t* row_width;
+    int32_t** rows_dev;
+    // check_feeds
+    std::vector<int64_t> out_n;              // samples every feed gives at the model's rate
+    int n_off = 0;                           // feeds off that rate
+    // group_by_session, admit
+    std::vector<Session*> sess;              // in the order they were first fed
+    std::vector<int> end_flag;
+    std::vector<std::vector<int>> feeds_of;
+    std::vector<long> len;                   // samples of the session's row: carried-over + fed
+    std::vector<int32_t> refused;            // handles of the sessions left out
+    int n = 0;                               // sessions that take part
+    // assemble_rows: rows of n_max floats in pinned memory; the raw bytes of off-rate feeds and their descriptors
+    long n_max = 0;
+    float* buf = nullptr;
+    int32_t* lens_h = nullptr;
+    std::vector<char> off_sess;              // the session has an off-rate feed in this step
+    std::vector<masr_resample_feed> rs_feeds;
+    size_t raw_bytes = 0;
+    char* raw_h = nullptr;
+    // upload_and_resample, gains, features
+    std::vector<int> fresh;                  // feature frames the row gives
+    std::vector<const float*> tail_h;        // where the carried-over samples of an off-rate session come back (pinned)
+    float* gains_h = nullptr;
+    int tmax = 0;                            // frames per row of the feature launch
+    // append_frames, run_windows: the windows, and the step's segment tables (ONE device array; every launch gets its own slice)
+    std::vector<std::vector<std::pair<int, int>>> plans;
+    size_t lockstep = 0;                     // windows of the session that has most
+    PoolSeg* seg_pin = nullptr;
+    size_t seg_at = 0;
+    // collapse_and_fetch: packed rows of the na sessions that advanced
+    int na = 0, width = 0;
+    int32_t* rows_h = nullptr;
+    // host time since the last lap goes to slot k of masr_pool_profile
+    std::chrono::steady_clock::time_point t_last;
+    void lap(masr_pool* p, int k) {
+        const auto t = std::chrono::steady_clock::now();
+        p->prof[k] += std::chrono::duration<double, std::milli>(t - t_last).count();
+        t_last = t;
+    }
+};
+
+// validate EVERYTHING before any session state is touched: a bad feed fails the call with nothing committed
+int check_feeds(const masr_pool* p, Step& st) {
+    if (!st.feed_handle || !st.feed_samples || !st.feed_n || !st.feed_format || !st.feed_is_end) PFAIL("masr_pool_step: null feed arrays");
+    for (int k = 0; k < st.n_feeds; ++k) {
+        if (p->sessions.find(st.feed_handle[k]) == p->sessions.end()) PFAIL("masr_pool_step: unknown handle");
+        if (st.feed_format[k] != 0 && st.feed_format[k] != 1) PFAIL("masr_pool_step: sample format 0 = int16 PCM, 1 = float32");
+        if (st.feed_n[k] < 0 || st.feed_n[k] > kMaxFeedSamples) PFAIL("masr_pool_step: feed_n out of range (0 .. 2^28 samples)");
+        if (st.feed_n[k] > 0 && !st.feed_samples[k]) PFAIL("masr_pool_step: null sample pointer with feed_n > 0");
+    }
+    // samples every feed gives at the model's rate: its own count, or (int)(n * ratio) of an off-rate feed (resample.cpp)
+    st.out_n.assign(st.feed_n, st.feed_n + st.n_feeds);
+    for (int k = 0; st.feed_rate_slot && k < st.n_feeds; ++k) {
+        const int slot = st.feed_rate_slot[k];
+        if (slot == -1) continue;
+        if (slot < 0 || slot >= (int)p->rates.size()) PFAIL("masr_pool_step: unknown rate slot (masr_pool_set_rate)");
+        const masr_resample_rate& r = p->rates[slot];
+        const int64_t m = (int64_t)((double)st.feed_n[k] * r.ratio);
+        if (m < 1 || m > kMaxFeedSamples) PFAIL("masr_pool_step: feed " + std::to_string(k) + " is too small to resample (or gives more than 2^28 samples)");
+        if ((int64_t)((double)(m - 1) * r.time_increment) >= st.feed_n[k])
+            PFAIL("masr_pool_step: feed " + std::to_string(k) + " asks for outputs beyond its input (n >= n_orig)");
+        st.out_n[k] = m;
+        ++st.n_off;
+    }
+    return 0;
+}
+
+// sessions of this step, in the order they were first fed
+void group_by_session(masr_pool* p, Step& st) {
+    std::map<int, int> pos;
+    for (int k = 0; k < st.n_feeds; ++k) {
+        auto it = p->sessions.find(st.feed_handle[k]);
+        auto q = pos.find(st.feed_handle[k]);
+        if (q == pos.end()) {
+            q = pos.emplace(st.feed_handle[k], (int)st.sess.size()).first;
+            st.sess.push_back(&it->second);
+            st.end_flag.push_back(0);
+            st.feeds_of.emplace_back();
+        }
+        st.end_flag[q->second] |= st.feed_is_end[k] ? 1 : 0;
+        st.feeds_of[q->second].push_back(k);
+    }
+}
+
+// a session whose stream cannot take the frames this step would emit (masr_encode_chunk would refuse the whole lock-step
+// call: "stream exceeds its max_frames_out / max_pos") is LEFT OUT, untouched, and reported with state -1: one full
+// session does not fail the step of the others
+int admit(masr_pool* p, Step& st) {
+    std::vector<Session*> keep_s;
+    std::vector<int> keep_e;
+    std::vector<std::vector<int>> keep_f;
+    for (size_t i = 0; i < st.sess.size(); ++i) {
+        long tot = (long)st.sess[i]->remained.size();
+        for (int k : st.feeds_of[i]) tot += st.out_n[k];
+        long emit = 0;                                   // (the unit of masr_stream_room: before any stride layer)
+        pool_windows(st.sess[i]->nf + pool_feature_frames(tot, p->min_samples), st.end_flag[i] != 0,
+                     [&](int first, int last) { emit += subsampled_frames(p->e, last - first); });
+        int32_t room = 0;
+        PCHK(masr_stream_room(p->e, st.sess[i]->sid, &room));
+        if (emit > 0 && emit > room) {                   // (masr_stream_room already holds back the Efficient-Conformer's group padding)
+            st.refused.push_back(st.sess[i]->sid);
+            continue;
+        }
+        keep_s.push_back(st.sess[i]);
+        keep_e.push_back(st.end_flag[i]);
+        keep_f.push_back(std::move(st.feeds_of[i]));
+        st.len.push_back(tot);
+    }
+    st.sess.swap(keep_s);
+    st.end_flag.swap(keep_e);
+    st.feeds_of.swap(keep_f);
+    st.n = (int)st.sess.size();
+    return 0;
+}
+
+// the first phase that touches the pool: the previous step's copies are waited for, its tails settled, the pinned area reset
+int begin_step(masr_pool* p, Step& st, hipStream_t s) {
+    if (p->pending) {                                // the previous step's copies out of the pinned area (long done)
+        PHIP(hipEventSynchronize(p->ev));
+        p->pending = false;
+    }
+    if (!p->ev) PHIP(hipEventCreateWithFlags(&p->ev, hipEventDisableTiming));
+    settle_tails(p);                                 // (a step that ended without a wait left its tails in the pinned area)
+    PCHK(p->pin.reset());
+    int max_row = 0;
+    for (Session* q : st.sess) max_row = std::max(max_row, q->row);
+    PCHK(grow_state(p, max_row + 1, std::max(p->hist_cap, 256), s));
+    return 0;
+}
+
+// [carried-over | fed] samples of every session, float32, in pinned memory (predict.py:260-281)
+int assemble_rows(masr_pool* p, Step& st) {
+    const int n = st.n;
+    st.n_max = p->min_samples;
+    for (long len : st.len) st.n_max = std::max(st.n_max, len);
+    const long n_max = st.n_max;
+    // off-rate feeds of the sessions that take part: their raw bytes are staged in pinned memory as fed, 4-byte aligned
+    st.off_sess.assign(n, 0);
+    if (st.n_off)
+        for (int i = 0; i < n; ++i)
+            for (int k : st.feeds_of[i])
+                if (st.feed_rate_slot[k] >= 0) {
+                    st.raw_bytes = ((st.raw_bytes + 3) & ~(size_t)3) + (size_t)st.feed_n[k] * (st.feed_format[k] ? 4 : 2);
+                    st.off_sess[i] = 1;
+                }
+    if (st.raw_bytes) PCHK(p->pin.take(st.raw_bytes, (void**)&st.raw_h));
+    size_t raw_at = 0;
+    PCHK(p->pin.take((size_t)n * n_max * 4, (void**)&st.buf));
+    PCHK(p->pin.take((size_t)n * 4, (void**)&st.lens_h));
+    for (int i = 0; i < n; ++i) {
+        float* row = st.buf + (size_t)i * n_max;
+        size_t at = st.sess[i]->remained.size();
+        if (at) memcpy(row, st.sess[i]->remained.data(), at * 4);
+        for (int k : st.feeds_of[i]) {
+            const long m = st.feed_n[k];
+            if (st.feed_rate_slot && st.feed_rate_slot[k] >= 0) {      // staged raw; its samples are a hole the device fills
+                raw_at = (raw_at + 3) & ~(size_t)3;
+                const size_t bytes = (size_t)m * (st.feed_format[k] ? 4 : 2);
+                memcpy(st.raw_h + raw_at, st.feed_samples[k], bytes);
+                st.rs_feeds.push_back(masr_resample_feed{(int64_t)raw_at, st.feed_format[k], (int32_t)m, (int32_t)st.out_n[k], i,
+                                                         (int32_t)at, st.feed_rate_slot[k]});
+                raw_at += bytes;
+                at += (size_t)st.out_n[k];
+                continue;
+            }
+            if (st.feed_format[k] == 1) {
+                memcpy(row + at, st.feed_samples[k], (size_t)m * 4);
+            } else {                                  // int16 PCM: x / 2^15 in float32 (buf_to_float, data_utils/utils.py:382-411)
+                const int16_t* src = (const int16_t*)st.feed_samples[k];
+                for (long j = 0; j < m; ++j) row[at + j] = (float)src[j] * (1.0f / 32768.0f);
+            }
+            at += (size_t)m;
+        }
+        if ((long)at < n_max) memset(row + at, 0, (size_t)(n_max - (long)at) * 4);
+        st.lens_h[i] = (int32_t)st.len[i];
+    }
+    return 0;
+}
+
+// ONE upload of the rows; off-rate feeds: ONE launch fills their holes, and the tails of their sessions come back behind it
+int upload_and_resample(masr_pool* p, Step& st, hipStream_t s) {
+    const int n = st.n;
+    const long n_max = st.n_max;
+    PCHK(upload(p, p->samples, st.buf, (size_t)n * n_max * 4, s));
+    PCHK(upload(p, p->lens, st.lens_h, (size_t)n * 4, s));
+    st.fresh.resize(n);
+    for (int i = 0; i < n; ++i) st.fresh[i] = pool_feature_frames(st.len[i], p->min_samples);
+    st.tail_h.assign(n, nullptr);
+    if (st.rs_feeds.empty()) return 0;
+    const int nf = (int)st.rs_feeds.size();
+    int64_t n_tiles = 0;                           // (what the plan will count: one tile per 256 outputs of a feed)
+    for (const masr_resample_feed& f : st.rs_feeds) n_tiles += (f.n_out + MASR_RESAMPLE_TILE - 1) / MASR_RESAMPLE_TILE;
+    int32_t bad = -1;
+    const char* why = nullptr;
+    std::vector<PoolSeg> tsegs;
+    long tail_total = 0;
+    int tail_max = 0;
+    for (int i = 0; i < n; ++i)
+        if (st.off_sess[i]) {
+            const long from = 160L * st.fresh[i], len = st.len[i] - from;
+            if (len > 0) {
+                tsegs.push_back(PoolSeg{(long)i * n_max + from, tail_total, (int)len, i});
+                tail_max = std::max(tail_max, (int)len);
+            }
+            tail_total += len;
+        }
+    // block: feeds | tiles | tail segments (descriptors; the raw bytes are their own copy: they may be large)
+    const size_t o_tiles = (size_t)nf * sizeof(masr_resample_feed), o_segs = o_tiles + (size_t)n_tiles * 8;
+    const size_t block = o_segs + tsegs.size() * sizeof(PoolSeg);
+    char* blk = nullptr;
+    PCHK(p->pin.take(block, (void**)&blk));
+    memcpy(blk, st.rs_feeds.data(), o_tiles);
+    int64_t planned = 0;
+    if (masr_resample_plan(st.rs_feeds.data(), nf, p->rates.data(), (int)p->rates.size(), (int64_t)st.raw_bytes, n, n_max,
+                           (int32_t*)(blk + o_tiles), n_tiles, &planned, &bad, &why) || planned != n_tiles)
+        PFAIL(std::string("masr_pool_step: off-rate feed: ") + (why ? why : "tile count"));
+    float* tails_h = nullptr;
+    if (tail_total) PCHK(p->pin.take((size_t)tail_total * 4, (void**)&tails_h));
+    for (PoolSeg& g : tsegs) {
+        st.tail_h[g.pad_] = tails_h + g.dst;
+        g.pad_ = 0;
+    }
+    if (!tsegs.empty()) memcpy(blk + o_segs, tsegs.data(), tsegs.size() * sizeof(PoolSeg));
+    const size_t dev_raw = (st.raw_bytes + 63) & ~(size_t)63;
+    PCHK(p->raw.ensure(dev_raw + block, 0, s));
+    char* raw_d = p->raw.as<char>();
+    PHIP(hipMemcpyAsync(raw_d, st.raw_h, st.raw_bytes, hipMemcpyHostToDevice, s));
+    PHIP(hipMemcpyAsync(raw_d + dev_raw, blk, block, hipMemcpyHostToDevice, s));
+    PCHK(masr_resample_feeds(p->e, raw_d, (int64_t)st.raw_bytes, st.rs_feeds.data(), (const masr_resample_feed*)(raw_d + dev_raw), nf,
+                             p->rates.data(), p->rates_dev, (int)p->rates.size(), (const int32_t*)(blk + o_tiles),
+                             (const int32_t*)(raw_d + dev_raw + o_tiles), n_tiles, p->samples.as<float>(), n, n_max, s));
+    if (tail_total) {
+        PCHK(p->tails_dev.ensure((size_t)tail_total * 4, 0, s));
+        launch_copy_segments(p->samples.as<float>(), p->tails_dev.as<float>(), nullptr, nullptr,
+                             (const PoolSeg*)(raw_d + dev_raw + o_segs), (int)tsegs.size(), tail_max, 1, s);
+        PHIP(hipMemcpyAsync(tails_h, p->tails_dev.p, (size_t)tail_total * 4, hipMemcpyDeviceToHost, s));
+    }
+    return 0;
+}
+
+// gains: mean squares from the device, the scalar expressions of AudioSegment.normalize on the host
+int gains(masr_pool* p, Step& st, hipStream_t s) {
+    if (!p->use_db) return 0;
+    const int n = st.n;
+    float* ms_h = nullptr;
+    PCHK(p->pin.take((size_t)n * 4, (void**)&ms_h));
+    PCHK(p->pin.take((size_t)n * 4, (void**)&st.gains_h));
+    PCHK(p->ms.ensure((size_t)n * 4, 0, s));
+    PCHK(masr_mean_square(p->e, p->samples.p, 1, p->lens.as<int32_t>(), n, (int32_t)st.n_max, p->ms.as<float>(), s));
+    PHIP(hipMemcpyAsync(ms_h, p->ms.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    PHIP(hipStreamSynchronize(s));
+    st.lap(p, 1);
+    if (st.gain_fn) {
+        if (st.gain_fn(ms_h, n, p->target_db, st.gains_h, st.gain_user)) PFAIL("masr_pool_step: the gain evaluator failed");
+    } else {                                       // libm evaluation of audio.py:287-304,519-529 (float32 steps)
+        for (int i = 0; i < n; ++i) {
+            const float m = ms_h[i] == 0.f ? 1.f : ms_h[i];
+            const float gain_db = p->target_db - 10.f * log10f(m);
+            if (gain_db > 300.f) PFAIL("masr_pool_step: gain beyond max_gain_db (300 dB)");
+            st.gains_h[i] = powf(10.f, gain_db / 20.f);
+        }
+    }
+    PCHK(upload(p, p->gains, st.gains_h, (size_t)n * 4, s));
+    st.lap(p, 2);
+    return 0;
+}
+
+// ONE ragged feature launch over the pending samples, by the pool's feature method
+int features(masr_pool* p, Step& st, hipStream_t s) {
+    const int n = st.n, mode = p->use_db ? 2 : 0;
+    const int32_t n_max = (int32_t)st.n_max;
+    st.tmax = p->method == 2 ? (int)((st.n_max - 320) / 160 + 1) : (int)(1 + (st.n_max - 400) / 160);
+    PCHK(p->feats.ensure((size_t)n * st.tmax * p->F * 4, 0, s));
+    if (p->method == 0)
+        return masr_fbank_batch(p->e, p->samples.p, 1, p->lens.as<int32_t>(), n, n_max, mode, p->target_db, p->feats.as<float>(), nullptr,
+                                nullptr, p->gains.as<float>(), s);
+    if (p->method == 1)
+        return masr_mfcc_batch(p->e, p->samples.p, 1, p->lens.as<int32_t>(), n, n_max, mode, p->target_db, p->n_mfcc, p->feats.as<float>(),
+                               nullptr, p->gains.as<float>(), s);
+    return masr_linear_batch(p->e, p->samples.p, 1, p->lens.as<int32_t>(), n, n_max, mode, p->target_db, p->feats.as<float>(), nullptr,
+                             p->gains.as<float>(), s);
+}
+
+// one table of the step's segments: copied into its slice of the pinned and of the device array, *dev = the device slice
+int push_segments(masr_pool* p, Step& st, const std::vector<PoolSeg>& v, const PoolSeg** dev, hipStream_t s) {
+    memcpy(st.seg_pin + st.seg_at, v.data(), v.size() * sizeof(PoolSeg));
+    PHIP(hipMemcpyAsync(p->segs.as<PoolSeg>() + st.seg_at, st.seg_pin + st.seg_at, v.size() * sizeof(PoolSeg), hipMemcpyHostToDevice, s));
+    *dev = p->segs.as<PoolSeg>() + st.seg_at;
+    st.seg_at += v.size();
+    return 0;
+}
+
+// bookkeeping: carried-over samples, new frames appended to the sessions' rows of the frame pool; the windows of every session
+// (predict.py:283-306) are planned here, where the segment tables of the whole step are sized
+int append_frames(masr_pool* p, Step& st, hipStream_t s) {
+    const int n = st.n;
+    int need = 0;
+    for (int i = 0; i < n; ++i) need = std::max(need, st.sess[i]->nf + st.fresh[i]);
+    if (need > p->feat_cap) PCHK(widen_feat(p, std::max(need, 2 * p->feat_cap), s));
+    std::vector<PoolSeg> seg_h;
+    int seg_rows = 0;
+    for (int i = 0; i < n; ++i) {
+        Session& q = *st.sess[i];
+        const float* row = st.buf + (size_t)i * st.n_max;
+        const long from = 160L * st.fresh[i], len = st.len[i];
+        if (st.off_sess[i]) {                                         // the device has the row: its tail is on its way back
+            q.remained.assign((size_t)(len - from), 0.f);
+            p->tails.push_back(Tail{q.sid, st.tail_h[i], (size_t)(len - from), p->use_db ? st.gains_h[i] : 1.f, p->use_db && len > 0});
+        } else {
+            q.remained.assign(row + from, row + len);                // normalised in place, like AudioSegment.normalize
+            if (p->use_db && len > 0)
+                for (float& v : q.remained) v *= st.gains_h[i];
+        }
+        if (q.f0 + q.nf + st.fresh[i] > p->feat_cap) {                // make room: the live frames move to the front of the row
+            float* base = p->feat.as<float>() + (size_t)q.row * p->feat_cap * p->F;
+            PCHK(p->win.ensure((size_t)q.nf * p->F * 4, 0, s));
+            PHIP(hipMemcpyAsync(p->win.p, base + (size_t)q.f0 * p->F, (size_t)q.nf * p->F * 4, hipMemcpyDeviceToDevice, s));
+            PHIP(hipMemcpyAsync(base, p->win.p, (size_t)q.nf * p->F * 4, hipMemcpyDeviceToDevice, s));
+            q.f0 = 0;
+        }
+        if (st.fresh[i]) {
+            seg_h.push_back(PoolSeg{(long)i * st.tmax, (long)q.row * p->feat_cap + q.f0 + q.nf, st.fresh[i], 0});
+            seg_rows = std::max(seg_rows, st.fresh[i]);
+        }
+        q.nf += st.fresh[i];
+    }
+    size_t seg_total = seg_h.size();
+    st.plans.resize(n);
+    for (int i = 0; i < n; ++i) {
+        pool_windows(st.sess[i]->nf, st.end_flag[i] != 0, [&](int first, int last) { st.plans[i].push_back({first, last}); });
+        st.lockstep = std::max(st.lockstep, st.plans[i].size());
+        seg_total += 2 * st.plans[i].size();
+    }
+    PCHK(p->segs.ensure((seg_total + 8) * sizeof(PoolSeg), 0, s));
+    PCHK(p->pin.take((seg_total + 8) * sizeof(PoolSeg), (void**)&st.seg_pin));
+    if (!seg_h.empty()) {
+        const PoolSeg* d = nullptr;
+        PCHK(push_segments(p, st, seg_h, &d, s));
+        launch_copy_segments(p->feats.as<float>(), p->feat.as<float>(), nullptr, nullptr, d, (int)seg_h.size(), seg_rows, p->F, s);
+    }
+    return 0;
+}
+
+// window k of the sessions whose window k is `len` frames long: gathered from the frame pool, advanced through masr_encode_chunk,
+// (argmax, max prob) appended to the histories
+int run_window_group(masr_pool* p, Step& st, size_t k, int len, std::vector<int32_t>& ids, hipStream_t s) {
+    const int n = st.n;
+    auto in_group = [&](int i) { return k < st.plans[i].size() && st.plans[i][k].second - st.plans[i][k].first == len; };
+    std::vector<PoolSeg> gat, sca;
+    ids.clear();
+    int32_t tq = 0;
+    PCHK(masr_encoder_frames(p->e, len, &tq));
+    int hist_need = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!in_group(i)) continue;
+        Session& q = *st.sess[i];
+        const long item = (long)ids.size();
+        gat.push_back(PoolSeg{(long)q.row * p->feat_cap + q.f0 + st.plans[i][k].first, item * len, len, 0});
+        sca.push_back(PoolSeg{item * tq, 0, tq, i});            // dst filled in once the history width is final
+        hist_need = std::max(hist_need, q.frames + tq);
+        ids.push_back(q.sid);
+    }
+    const int m = (int)ids.size();
+    PCHK(grow_state(p, 0, hist_need, s));
+    for (PoolSeg& g : sca) {
+        Session& q = *st.sess[g.pad_];
+        g.dst = (long)q.row * p->hist_cap + q.frames;
+        g.pad_ = 0;
+    }
+    PCHK(p->win.ensure((size_t)m * len * p->F * 4, 0, s));
+    PCHK(p->idx.ensure((size_t)m * std::max(tq, 1) * 4, 0, s));
+    PCHK(p->mp.ensure((size_t)m * std::max(tq, 1) * 4, 0, s));
+    const PoolSeg *dg = nullptr, *ds = nullptr;
+    PCHK(push_segments(p, st, gat, &dg, s));
+    launch_copy_segments(p->feat.as<float>(), p->win.as<float>(), nullptr, nullptr, dg, m, len, p->F, s);
+    // (a last window shorter than the front-end's minimum -- 8-14 frames under conv2d8, 7-10 under conv2d6 -- gives no
+    // encoder frame: nothing to run, where the reference's conv would refuse the input)
+    if (tq > 0) {
+        PCHK(masr_encode_chunk(p->e, ids.data(), m, p->win.as<float>(), len, nullptr, p->idx.as<int32_t>(), p->mp.as<float>(), s));
+        PCHK(push_segments(p, st, sca, &ds, s));
+        launch_copy_segments(reinterpret_cast<const float*>(p->idx.p), p->hist_idx.as<float>(), p->mp.as<float>(),
+                             p->hist_mp.as<float>(), ds, m, tq, 1, s);
+    }
+    for (int i = 0; i < n; ++i)
+        if (in_group(i)) st.sess[i]->frames += tq;
+    return 0;
+}
+
+// the windows of all sessions, advanced in lock-step
+int run_windows(masr_pool* p, Step& st, hipStream_t s) {
+    std::vector<int32_t> ids;
+    for (size_t k = 0; k < st.lockstep; ++k) {
+        // full windows together; a short last window on its own (lengths in ascending order of first appearance)
+        std::vector<int> lengths;
+        for (int i = 0; i < st.n; ++i)
+            if (k < st.plans[i].size()) {
+                const int len = st.plans[i][k].second - st.plans[i][k].first;
+                if (std::find(lengths.begin(), lengths.end(), len) == lengths.end()) lengths.push_back(len);
+            }
+        for (int len : lengths) PCHK(run_window_group(p, st, k, len, ids, s));
+    }
+    return 0;
+}
+
+// greedy: ONE collapse launch for every session that advanced (full-history best path + score, greedy_decoder_chunk semantics,
+// ctc_greedy_decoder.py:52-89); ONE copy back
+int collapse_and_fetch(masr_pool* p, Step& st, hipStream_t s) {
+    std::vector<int> adv;
+    int hmax = 0;
+    for (int i = 0; i < st.n; ++i)
+        if (!st.plans[i].empty()) {
+            adv.push_back(i);
+            hmax = std::max(hmax, st.sess[i]->frames);
+        }
+    const int na = st.na = (int)adv.size(), width = st.width = hmax + 2;
+    // the collapse takes the longest history as its Tp: a Conformer-family session stops at its stream's max_frames_out <= max_pos
+    // (5000 unless the engine was created with more), a DeepSpeech2 session has no frame limit -- the same refusal as
+    // masr_ctc_collapse, by name, instead of a launch that asks for more dynamic LDS than the kernel may have
+    if (hmax > CTC_COLLAPSE_MAX_FRAMES) PFAIL(std::string("masr_pool_step: ") + ctc_collapse_refusal);
+    if (na) {
+        int32_t* meta_h = nullptr;                 // [rows | frame counts]
+        PCHK(p->pin.take((size_t)2 * na * 4, (void**)&meta_h));
+        for (int j = 0; j < na; ++j) {
+            meta_h[j] = st.sess[adv[j]]->row;
+            meta_h[na + j] = st.sess[adv[j]]->frames;
+        }
+        PCHK(upload(p, p->meta, meta_h, (size_t)2 * na * 4, s));
+        PCHK(p->rows_out.ensure((size_t)na * width * 4, 0, s));
+        launch_ctc_collapse_hist(p->hist_idx.as<int>(), p->hist_mp.as<float>(), p->meta.as<int>() + na, p->meta.as<int>(), p->hist_cap,
+                                 na, hmax, 0, p->rows_out.as<int>(), s);
+        PCHK(p->pin.take((size_t)na * width * 4, (void**)&st.rows_h));
+        PHIP(hipMemcpyAsync(st.rows_h, p->rows_out.p, (size_t)na * width * 4, hipMemcpyDeviceToHost, s));
+    }
+    PHIP(hipGetLastError());
+    PHIP(hipEventRecord(p->ev, s));
+    p->pending = true;
+    if (na) PHIP(hipStreamSynchronize(s));
+    if (na || p->use_db) settle_tails(p);            // (waited for above, or with the mean squares; else: at the next step)
+    return 0;
+}
+
+// results + the windows' bookkeeping (predict.py:329: keep the overlap frames); the sessions left out follow with state -1
+void publish(masr_pool* p, Step& st) {
+    for (int i = 0; i < st.n; ++i) {
+        Session& q = *st.sess[i];
+        if (!st.plans[i].empty()) {
+            const int used = st.plans[i].back().second - kOverlap;
+            q.f0 += used;
+            q.nf -= used;
+        }
+        p->handles.push_back(q.sid);
+        p->state.push_back(st.plans[i].empty() ? 0 : 1);
+    }
+    for (int32_t h : st.refused) {
+        p->handles.push_back(h);
+        p->state.push_back(-1);
+    }
+    *st.n_sessions = st.n + (int32_t)st.refused.size();
+    if (st.handles_out) *st.handles_out = p->handles.data();
+    if (st.state_out) *st.state_out = p->state.data();
+    if (st.rows_host) *st.rows_host = st.rows_h;
+    if (st.row_width) *st.row_width = st.na ? st.width : 0;
+    if (st.rows_dev) *st.rows_dev = st.na ? p->rows_out.as<int32_t>() : nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -280,9 +751,7 @@ void masr_pool_destroy(masr_pool* p) {
     (void)hipSetDevice(p->device);
     (void)hipDeviceSynchronize();
     for (auto& kv : p->sessions) (void)masr_stream_close(p->e, kv.second.sid);
-    for (Dev* d : {&p->feat, &p->hist_idx, &p->hist_mp, &p->samples, &p->lens, &p->ms, &p->gains, &p->feats, &p->win, &p->idx,
-                   &p->mp, &p->segs, &p->meta, &p->rows_out, &p->raw, &p->tails_dev})
-        d->release();
+    for (Dev* d : p->buffers()) d->release();
     for (void* t : p->rate_tables) (void)hipFree(t);
     if (p->rates_dev) (void)hipFree(p->rates_dev);
     p->pin.release();
@@ -392,430 +861,47 @@ int masr_pool_step_rates(masr_pool* p, int32_t n_feeds, const int32_t* feed_hand
     p->handles.clear();
     p->state.clear();
     if (n_feeds <= 0) return 0;
-    // ---- validate EVERYTHING before any session state is touched: a bad feed fails the call with nothing committed ----------
-    if (!feed_handle || !feed_samples || !feed_n || !feed_format || !feed_is_end) PFAIL("masr_pool_step: null feed arrays");
-    for (int k = 0; k < n_feeds; ++k) {
-        if (p->sessions.find(feed_handle[k]) == p->sessions.end()) PFAIL("masr_pool_step: unknown handle");
-        if (feed_format[k] != 0 && feed_format[k] != 1) PFAIL("masr_pool_step: sample format 0 = int16 PCM, 1 = float32");
-        if (feed_n[k] < 0 || feed_n[k] > kMaxFeedSamples) PFAIL("masr_pool_step: feed_n out of range (0 .. 2^28 samples)");
-        if (feed_n[k] > 0 && !feed_samples[k]) PFAIL("masr_pool_step: null sample pointer with feed_n > 0");
-    }
-    // samples every feed gives at the model's rate: its own count, or (int)(n * ratio) of an off-rate feed (resample.cpp)
-    std::vector<int64_t> out_n(feed_n, feed_n + n_feeds);
-    int n_off = 0;
-    for (int k = 0; feed_rate_slot && k < n_feeds; ++k) {
-        const int slot = feed_rate_slot[k];
-        if (slot == -1) continue;
-        if (slot < 0 || slot >= (int)p->rates.size()) PFAIL("masr_pool_step: unknown rate slot (masr_pool_set_rate)");
-        const masr_resample_rate& r = p->rates[slot];
-        const int64_t m = (int64_t)((double)feed_n[k] * r.ratio);
-        if (m < 1 || m > kMaxFeedSamples) PFAIL("masr_pool_step: feed " + std::to_string(k) + " is too small to resample (or gives more than 2^28 samples)");
-        if ((int64_t)((double)(m - 1) * r.time_increment) >= feed_n[k])
-            PFAIL("masr_pool_step: feed " + std::to_string(k) + " asks for outputs beyond its input (n >= n_orig)");
-        out_n[k] = m;
-        ++n_off;
-    }
-    // ---- sessions of this step, in the order they were first fed ------------------------------------------------------
-    std::vector<Session*> sess;
-    std::vector<int> end_flag;
-    std::map<int, int> pos;
-    std::vector<std::vector<int>> feeds_of;
-    for (int k = 0; k < n_feeds; ++k) {
-        auto it = p->sessions.find(feed_handle[k]);
-        auto q = pos.find(feed_handle[k]);
-        if (q == pos.end()) {
-            q = pos.emplace(feed_handle[k], (int)sess.size()).first;
-            sess.push_back(&it->second);
-            end_flag.push_back(0);
-            feeds_of.emplace_back();
-        }
-        end_flag[q->second] |= feed_is_end[k] ? 1 : 0;
-        feeds_of[q->second].push_back(k);
-    }
-    // a session whose stream cannot take the frames this step would emit (masr_encode_chunk would refuse the whole lock-step
-    // call: "stream exceeds its max_frames_out / max_pos") is LEFT OUT, untouched, and reported with state -1: one full
-    // session does not fail the step of the others
-    std::vector<int32_t> refused;
-    {
-        std::vector<Session*> keep_s;
-        std::vector<int> keep_e;
-        std::vector<std::vector<int>> keep_f;
-        for (size_t i = 0; i < sess.size(); ++i) {
-            long tot = (long)sess[i]->remained.size();
-            for (int k : feeds_of[i]) tot += out_n[k];
-            const int nfr = sess[i]->nf + feature_frames(p, tot);
-            long emit = 0;
-            if (!((nfr < kWindow && !end_flag[i]) || nfr < kContext)) {
-                const int left = end_flag[i] ? kContext : kWindow;
-                for (int cur = 0; cur <= nfr - left; cur += kStride) {
-                    const int len = std::min(cur + kWindow, nfr) - cur;
-                    emit += subsampled_frames(p->e, len);       // (the unit of masr_stream_room: before any stride layer)
-                }
-            }
-            int32_t room = 0;
-            PCHK(masr_stream_room(p->e, sess[i]->sid, &room));
-            if (emit > 0 && emit > room) {               // (masr_stream_room already holds back the Efficient-Conformer's group padding)
-                refused.push_back(sess[i]->sid);
-                continue;
-            }
-            keep_s.push_back(sess[i]);
-            keep_e.push_back(end_flag[i]);
-            keep_f.push_back(std::move(feeds_of[i]));
-        }
-        sess.swap(keep_s);
-        end_flag.swap(keep_e);
-        feeds_of.swap(keep_f);
-    }
-    if (sess.empty()) {
-        for (int32_t h : refused) {
-            p->handles.push_back(h);
-            p->state.push_back(-1);
-        }
-        *n_sessions = (int32_t)refused.size();
-        if (handles_out) *handles_out = p->handles.data();
-        if (state_out) *state_out = p->state.data();
+    Step st{n_feeds, feed_handle, feed_samples, feed_n, feed_format, feed_is_end, feed_rate_slot, gain_fn, gain_user,
+            n_sessions, handles_out, state_out, rows_host, row_width, rows_dev};
+    PCHK(check_feeds(p, st));                        // (these three commit nothing: a refused call leaves the pool as it was)
+    group_by_session(p, st);
+    PCHK(admit(p, st));
+    if (st.sess.empty()) {                           // every session was left out
+        publish(p, st);
         return 0;
     }
-    const int n = (int)sess.size();
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](int k) {
-        const auto t = std::chrono::steady_clock::now();
-        p->prof[k] += std::chrono::duration<double, std::milli>(t - t_last).count();
-        t_last = t;
-    };
-    if (p->pending) {                                // the previous step's copies out of the pinned area (long done)
-        PHIP(hipEventSynchronize(p->ev));
-        p->pending = false;
-    }
-    if (!p->ev) PHIP(hipEventCreateWithFlags(&p->ev, hipEventDisableTiming));
-    settle_tails(p);                                 // (a step that ended without a wait left its tails in the pinned area)
-    PCHK(p->pin.reset());
-    int max_row = 0;
-    for (Session* q : sess) max_row = std::max(max_row, q->row);
-    PCHK(grow_state(p, max_row + 1, std::max(p->hist_cap, 256), s));
-
-    // ---- [carried-over | fed] samples of every session, float32, in pinned memory (predict.py:260-281) -----------------------
-    std::vector<long> L(n);
-    long n_max = p->min_samples;
-    for (int i = 0; i < n; ++i) {
-        long tot = (long)sess[i]->remained.size();
-        for (int k : feeds_of[i]) tot += out_n[k];
-        L[i] = tot;
-        n_max = std::max(n_max, tot);
-    }
-    // off-rate feeds of the sessions that take part: their raw bytes are staged in pinned memory as fed, 4-byte aligned
-    std::vector<masr_resample_feed> rs_feeds;
-    std::vector<char> off_sess(n, 0);
-    size_t raw_bytes = 0;
-    if (n_off)
-        for (int i = 0; i < n; ++i)
-            for (int k : feeds_of[i])
-                if (feed_rate_slot[k] >= 0) {
-                    raw_bytes = ((raw_bytes + 3) & ~(size_t)3) + (size_t)feed_n[k] * (feed_format[k] ? 4 : 2);
-                    off_sess[i] = 1;
-                }
-    char* raw_h = nullptr;
-    if (raw_bytes) PCHK(p->pin.take(raw_bytes, (void**)&raw_h));
-    size_t raw_at = 0;
-    float* buf = nullptr;
-    int32_t* lens_h = nullptr;
-    PCHK(p->pin.take((size_t)n * n_max * 4, (void**)&buf));
-    PCHK(p->pin.take((size_t)n * 4, (void**)&lens_h));
-    for (int i = 0; i < n; ++i) {
-        float* row = buf + (size_t)i * n_max;
-        size_t at = sess[i]->remained.size();
-        if (at) memcpy(row, sess[i]->remained.data(), at * 4);
-        for (int k : feeds_of[i]) {
-            const long m = feed_n[k];
-            if (feed_rate_slot && feed_rate_slot[k] >= 0) {      // staged raw; its samples are a hole the device fills
-                raw_at = (raw_at + 3) & ~(size_t)3;
-                const size_t bytes = (size_t)m * (feed_format[k] ? 4 : 2);
-                memcpy(raw_h + raw_at, feed_samples[k], bytes);
-                rs_feeds.push_back(masr_resample_feed{(int64_t)raw_at, feed_format[k], (int32_t)m, (int32_t)out_n[k], i, (int32_t)at,
-                                                      feed_rate_slot[k]});
-                raw_at += bytes;
-                at += (size_t)out_n[k];
-                continue;
-            }
-            if (feed_format[k] == 1) {
-                memcpy(row + at, feed_samples[k], (size_t)m * 4);
-            } else {                                  // int16 PCM: x / 2^15 in float32 (buf_to_float, data_utils/utils.py:382-411)
-                const int16_t* src = (const int16_t*)feed_samples[k];
-                for (long j = 0; j < m; ++j) row[at + j] = (float)src[j] * (1.0f / 32768.0f);
-            }
-            at += (size_t)m;
-        }
-        if ((long)at < n_max) memset(row + at, 0, (size_t)(n_max - (long)at) * 4);
-        lens_h[i] = (int32_t)L[i];
-    }
-    lap(0);
-    PCHK(upload(p, p->samples, buf, (size_t)n * n_max * 4, s));
-    PCHK(upload(p, p->lens, lens_h, (size_t)n * 4, s));
-    // ---- off-rate feeds: ONE launch fills their holes; the tails of their sessions come back behind it ----------------------
-    std::vector<int> fresh(n);
-    for (int i = 0; i < n; ++i) fresh[i] = feature_frames(p, L[i]);
-    std::vector<const float*> tail_h(n, nullptr);
-    if (!rs_feeds.empty()) {
-        const int nf = (int)rs_feeds.size();
-        int64_t n_tiles = 0;                           // (what the plan will count: one tile per 256 outputs of a feed)
-        for (const masr_resample_feed& f : rs_feeds) n_tiles += (f.n_out + MASR_RESAMPLE_TILE - 1) / MASR_RESAMPLE_TILE;
-        int32_t bad = -1;
-        const char* why = nullptr;
-        std::vector<PoolSeg> tsegs;
-        long tail_total = 0;
-        int tail_max = 0;
-        for (int i = 0; i < n; ++i)
-            if (off_sess[i]) {
-                const long from = 160L * fresh[i], len = L[i] - from;
-                if (len > 0) {
-                    tsegs.push_back(PoolSeg{(long)i * n_max + from, tail_total, (int)len, i});
-                    tail_max = std::max(tail_max, (int)len);
-                }
-                tail_total += len;
-            }
-        // block: feeds | tiles | tail segments (descriptors; the raw bytes are their own copy: they may be large)
-        const size_t o_tiles = (size_t)nf * sizeof(masr_resample_feed), o_segs = o_tiles + (size_t)n_tiles * 8;
-        const size_t block = o_segs + tsegs.size() * sizeof(PoolSeg);
-        char* blk = nullptr;
-        PCHK(p->pin.take(block, (void**)&blk));
-        memcpy(blk, rs_feeds.data(), o_tiles);
-        int64_t planned = 0;
-        if (masr_resample_plan(rs_feeds.data(), nf, p->rates.data(), (int)p->rates.size(), (int64_t)raw_bytes, n, n_max,
-                               (int32_t*)(blk + o_tiles), n_tiles, &planned, &bad, &why) || planned != n_tiles)
-            PFAIL(std::string("masr_pool_step: off-rate feed: ") + (why ? why : "tile count"));
-        float* tails_h = nullptr;
-        if (tail_total) PCHK(p->pin.take((size_t)tail_total * 4, (void**)&tails_h));
-        for (PoolSeg& g : tsegs) {
-            tail_h[g.pad_] = tails_h + g.dst;
-            g.pad_ = 0;
-        }
-        if (!tsegs.empty()) memcpy(blk + o_segs, tsegs.data(), tsegs.size() * sizeof(PoolSeg));
-        const size_t dev_raw = (raw_bytes + 63) & ~(size_t)63;
-        PCHK(p->raw.ensure(dev_raw + block, 0, s));
-        char* raw_d = p->raw.as<char>();
-        PHIP(hipMemcpyAsync(raw_d, raw_h, raw_bytes, hipMemcpyHostToDevice, s));
-        PHIP(hipMemcpyAsync(raw_d + dev_raw, blk, block, hipMemcpyHostToDevice, s));
-        PCHK(masr_resample_feeds(p->e, raw_d, (int64_t)raw_bytes, rs_feeds.data(), (const masr_resample_feed*)(raw_d + dev_raw), nf,
-                                 p->rates.data(), p->rates_dev, (int)p->rates.size(), (const int32_t*)(blk + o_tiles),
-                                 (const int32_t*)(raw_d + dev_raw + o_tiles), n_tiles, p->samples.as<float>(), n, n_max, stream));
-        if (tail_total) {
-            PCHK(p->tails_dev.ensure((size_t)tail_total * 4, 0, s));
-            launch_copy_segments(p->samples.as<float>(), p->tails_dev.as<float>(), nullptr, nullptr,
-                                 (const PoolSeg*)(raw_d + dev_raw + o_segs), (int)tsegs.size(), tail_max, 1, s);
-            PHIP(hipMemcpyAsync(tails_h, p->tails_dev.p, (size_t)tail_total * 4, hipMemcpyDeviceToHost, s));
-        }
-    }
-
-    // ---- gains: mean squares from the device, the scalar expressions of AudioSegment.normalize on the host ------------------
-    float* gains_h = nullptr;
-    if (p->use_db) {
-        float* ms_h = nullptr;
-        PCHK(p->pin.take((size_t)n * 4, (void**)&ms_h));
-        PCHK(p->pin.take((size_t)n * 4, (void**)&gains_h));
-        PCHK(p->ms.ensure((size_t)n * 4, 0, s));
-        PCHK(masr_mean_square(p->e, p->samples.p, 1, p->lens.as<int32_t>(), n, (int32_t)n_max, p->ms.as<float>(), stream));
-        PHIP(hipMemcpyAsync(ms_h, p->ms.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        PHIP(hipStreamSynchronize(s));
-        lap(1);
-        if (gain_fn) {
-            if (gain_fn(ms_h, n, p->target_db, gains_h, gain_user)) PFAIL("masr_pool_step: the gain evaluator failed");
-        } else {                                       // libm evaluation of audio.py:287-304,519-529 (float32 steps)
-            for (int i = 0; i < n; ++i) {
-                const float m = ms_h[i] == 0.f ? 1.f : ms_h[i];
-                const float gain_db = p->target_db - 10.f * log10f(m);
-                if (gain_db > 300.f) PFAIL("masr_pool_step: gain beyond max_gain_db (300 dB)");
-                gains_h[i] = powf(10.f, gain_db / 20.f);
-            }
-        }
-        PCHK(upload(p, p->gains, gains_h, (size_t)n * 4, s));
-        lap(2);
-    }
-    // ---- ONE ragged feature launch over the pending samples ------------------------------------------------------------------
-    const int tmax = p->method == 2 ? (int)((n_max - 320) / 160 + 1) : (int)(1 + (n_max - 400) / 160);
-    PCHK(p->feats.ensure((size_t)n * tmax * p->F * 4, 0, s));
-    const int mode = p->use_db ? 2 : 0;
-    if (p->method == 0)
-        PCHK(masr_fbank_batch(p->e, p->samples.p, 1, p->lens.as<int32_t>(), n, (int32_t)n_max, mode, p->target_db, p->feats.as<float>(),
-                              nullptr, nullptr, p->gains.as<float>(), stream));
-    else if (p->method == 1)
-        PCHK(masr_mfcc_batch(p->e, p->samples.p, 1, p->lens.as<int32_t>(), n, (int32_t)n_max, mode, p->target_db, p->n_mfcc,
-                             p->feats.as<float>(), nullptr, p->gains.as<float>(), stream));
-    else
-        PCHK(masr_linear_batch(p->e, p->samples.p, 1, p->lens.as<int32_t>(), n, (int32_t)n_max, mode, p->target_db, p->feats.as<float>(),
-                               nullptr, p->gains.as<float>(), stream));
-
-    // ---- bookkeeping: carried-over samples, new frames appended to the sessions' rows of the frame pool --------------------
-    int need = 0;
-    for (int i = 0; i < n; ++i) need = std::max(need, sess[i]->nf + fresh[i]);
-    if (need > p->feat_cap) PCHK(widen_feat(p, std::max(need, 2 * p->feat_cap), s));
-    std::vector<PoolSeg> seg_h;
-    int seg_rows = 0;
-    TailGuard tail_guard{p, s};
-    for (int i = 0; i < n; ++i) {
-        Session& q = *sess[i];
-        const float* row = buf + (size_t)i * n_max;
-        const long from = 160L * fresh[i];
-        if (off_sess[i]) {                                            // the device has the row: its tail is on its way back
-            q.remained.assign((size_t)(L[i] - from), 0.f);
-            p->tails.push_back(Tail{q.sid, tail_h[i], (size_t)(L[i] - from), p->use_db ? gains_h[i] : 1.f, p->use_db && L[i] > 0});
-        } else {
-            q.remained.assign(row + from, row + L[i]);               // normalised in place, like AudioSegment.normalize
-            if (p->use_db && L[i] > 0)
-                for (float& v : q.remained) v *= gains_h[i];
-        }
-        if (q.f0 + q.nf + fresh[i] > p->feat_cap) {                   // make room: the live frames move to the front of the row
-            float* base = p->feat.as<float>() + (size_t)q.row * p->feat_cap * p->F;
-            PCHK(p->win.ensure((size_t)q.nf * p->F * 4, 0, s));
-            PHIP(hipMemcpyAsync(p->win.p, base + (size_t)q.f0 * p->F, (size_t)q.nf * p->F * 4, hipMemcpyDeviceToDevice, s));
-            PHIP(hipMemcpyAsync(base, p->win.p, (size_t)q.nf * p->F * 4, hipMemcpyDeviceToDevice, s));
-            q.f0 = 0;
-        }
-        if (fresh[i]) {
-            seg_h.push_back(PoolSeg{(long)i * tmax, (long)q.row * p->feat_cap + q.f0 + q.nf, fresh[i], 0});
-            seg_rows = std::max(seg_rows, fresh[i]);
-        }
-        q.nf += fresh[i];
-    }
-    // the step's segment tables live in ONE device array; every launch gets its own slice
-    size_t seg_total = seg_h.size();
-    // windows of every session (predict.py:283-306), advanced in lock-step
-    std::vector<std::vector<std::pair<int, int>>> plans(n);
-    size_t lockstep = 0;
-    for (int i = 0; i < n; ++i) {
-        const int nfr = sess[i]->nf;
-        if ((nfr < kWindow && !end_flag[i]) || nfr < kContext) continue;
-        const int left = end_flag[i] ? kContext : kWindow;
-        for (int cur = 0; cur <= nfr - left; cur += kStride) plans[i].push_back({cur, std::min(cur + kWindow, nfr)});
-        lockstep = std::max(lockstep, plans[i].size());
-        seg_total += 2 * plans[i].size();
-    }
-    PCHK(p->segs.ensure((seg_total + 8) * sizeof(PoolSeg), 0, s));
-    PoolSeg* seg_pin = nullptr;
-    PCHK(p->pin.take((seg_total + 8) * sizeof(PoolSeg), (void**)&seg_pin));
-    size_t seg_at = 0;
-    auto push_segments = [&](const std::vector<PoolSeg>& v, const PoolSeg** dev) -> int {
-        memcpy(seg_pin + seg_at, v.data(), v.size() * sizeof(PoolSeg));
-        PHIP(hipMemcpyAsync(p->segs.as<PoolSeg>() + seg_at, seg_pin + seg_at, v.size() * sizeof(PoolSeg), hipMemcpyHostToDevice, s));
-        *dev = p->segs.as<PoolSeg>() + seg_at;
-        seg_at += v.size();
-        return 0;
-    };
-    if (!seg_h.empty()) {
-        const PoolSeg* d = nullptr;
-        PCHK(push_segments(seg_h, &d));
-        launch_copy_segments(p->feats.as<float>(), p->feat.as<float>(), nullptr, nullptr, d, (int)seg_h.size(), seg_rows, p->F, s);
-    }
-    std::vector<int32_t> ids;
-    lap(3);
-    for (size_t k = 0; k < lockstep; ++k) {
-        // full windows together; a short last window on its own (lengths in ascending order of first appearance)
-        std::vector<int> lengths;
-        for (int i = 0; i < n; ++i)
-            if (k < plans[i].size()) {
-                const int len = plans[i][k].second - plans[i][k].first;
-                if (std::find(lengths.begin(), lengths.end(), len) == lengths.end()) lengths.push_back(len);
-            }
-        for (int len : lengths) {
-            std::vector<PoolSeg> gat, sca;
-            ids.clear();
-            int32_t tq = 0;
-            PCHK(masr_encoder_frames(p->e, len, &tq));
-            int hist_need = 0;
-            for (int i = 0; i < n; ++i) {
-                if (k >= plans[i].size() || plans[i][k].second - plans[i][k].first != len) continue;
-                Session& q = *sess[i];
-                const long item = (long)ids.size();
-                gat.push_back(PoolSeg{(long)q.row * p->feat_cap + q.f0 + plans[i][k].first, item * len, len, 0});
-                sca.push_back(PoolSeg{item * tq, 0, tq, i});            // dst filled in once the history width is final
-                hist_need = std::max(hist_need, q.frames + tq);
-                ids.push_back(q.sid);
-            }
-            const int m = (int)ids.size();
-            PCHK(grow_state(p, 0, hist_need, s));
-            for (PoolSeg& g : sca) {
-                Session& q = *sess[g.pad_];
-                g.dst = (long)q.row * p->hist_cap + q.frames;
-                g.pad_ = 0;
-            }
-            PCHK(p->win.ensure((size_t)m * len * p->F * 4, 0, s));
-            PCHK(p->idx.ensure((size_t)m * std::max(tq, 1) * 4, 0, s));
-            PCHK(p->mp.ensure((size_t)m * std::max(tq, 1) * 4, 0, s));
-            const PoolSeg *dg = nullptr, *ds = nullptr;
-            PCHK(push_segments(gat, &dg));
-            launch_copy_segments(p->feat.as<float>(), p->win.as<float>(), nullptr, nullptr, dg, m, len, p->F, s);
-            // (a last window shorter than the front-end's minimum -- 8-14 frames under conv2d8, 7-10 under conv2d6 -- gives no
-            // encoder frame: nothing to run, where the reference's conv would refuse the input)
-            if (tq > 0)
-                PCHK(masr_encode_chunk(p->e, ids.data(), m, p->win.as<float>(), len, nullptr, p->idx.as<int32_t>(), p->mp.as<float>(),
-                                       stream));
-            if (tq > 0) {
-                PCHK(push_segments(sca, &ds));
-                launch_copy_segments(reinterpret_cast<const float*>(p->idx.p), p->hist_idx.as<float>(), p->mp.as<float>(),
-                                     p->hist_mp.as<float>(), ds, m, tq, 1, s);
-            }
-            for (int i = 0; i < n; ++i)
-                if (k < plans[i].size() && plans[i][k].second - plans[i][k].first == len) sess[i]->frames += tq;
-        }
-    }
-    // ---- greedy: ONE collapse launch for every session that advanced (full-history best path + score, greedy_decoder_chunk
-    // semantics, ctc_greedy_decoder.py:52-89); ONE copy back ------------------------------------------------------------------
-    lap(4);
-    std::vector<int> adv;
-    int hmax = 0;
-    for (int i = 0; i < n; ++i)
-        if (!plans[i].empty()) {
-            adv.push_back(i);
-            hmax = std::max(hmax, sess[i]->frames);
-        }
-    const int na = (int)adv.size(), width = hmax + 2;
-    int32_t* rows_h = nullptr;
-    // the collapse takes the longest history as its Tp: a Conformer-family session stops at its stream's max_frames_out <= max_pos
-    // (5000 unless the engine was created with more), a DeepSpeech2 session has no frame limit -- the same refusal as
-    // masr_ctc_collapse, by name, instead of a launch that asks for more dynamic LDS than the kernel may have
-    if (hmax > CTC_COLLAPSE_MAX_FRAMES) PFAIL(std::string("masr_pool_step: ") + ctc_collapse_refusal);
-    if (na) {
-        int32_t* meta_h = nullptr;                 // [rows | frame counts]
-        PCHK(p->pin.take((size_t)2 * na * 4, (void**)&meta_h));
-        for (int j = 0; j < na; ++j) {
-            meta_h[j] = sess[adv[j]]->row;
-            meta_h[na + j] = sess[adv[j]]->frames;
-        }
-        PCHK(upload(p, p->meta, meta_h, (size_t)2 * na * 4, s));
-        PCHK(p->rows_out.ensure((size_t)na * width * 4, 0, s));
-        launch_ctc_collapse_hist(p->hist_idx.as<int>(), p->hist_mp.as<float>(), p->meta.as<int>() + na, p->meta.as<int>(), p->hist_cap,
-                                 na, hmax, 0, p->rows_out.as<int>(), s);
-        PCHK(p->pin.take((size_t)na * width * 4, (void**)&rows_h));
-        PHIP(hipMemcpyAsync(rows_h, p->rows_out.p, (size_t)na * width * 4, hipMemcpyDeviceToHost, s));
-    }
-    PHIP(hipGetLastError());
-    PHIP(hipEventRecord(p->ev, s));
-    p->pending = true;
-    if (na) PHIP(hipStreamSynchronize(s));
-    if (na || p->use_db) settle_tails(p);            // (waited for above, or with the mean squares; else: at the next step)
+    st.t_last = std::chrono::steady_clock::now();
+    PCHK(begin_step(p, st, s));
+    PCHK(assemble_rows(p, st));
+    st.lap(p, 0);
+    PCHK(upload_and_resample(p, st, s));
+    PCHK(gains(p, st, s));                           // (laps 1 and 2: behind its wait, behind its upload)
+    PCHK(features(p, st, s));
+    TailGuard tail_guard{p, s};                      // append_frames queues the tails; any error return from here on settles them
+    PCHK(append_frames(p, st, s));
+    st.lap(p, 3);
+    PCHK(run_windows(p, st, s));
+    st.lap(p, 4);
+    PCHK(collapse_and_fetch(p, st, s));
     tail_guard.done = true;
-    lap(5);
+    st.lap(p, 5);
     ++p->prof_steps;
-    // ---- results + the windows' bookkeeping (predict.py:329: keep the overlap frames) -----------------------------------------
-    for (int i = 0; i < n; ++i) {
-        Session& q = *sess[i];
-        if (!plans[i].empty()) {
-            const int used = plans[i].back().second - kOverlap;
-            q.f0 += used;
-            q.nf -= used;
+    publish(p, st);
+    return 0;
+}
+
+int masr_pool_window_plan(int32_t n_frames, int32_t is_end, int32_t* first_last, int32_t cap, int32_t* n_windows) {
+    if (!n_windows || (cap > 0 && !first_last)) PFAIL("masr_pool_window_plan: null argument");
+    if (n_frames > (1 << 30)) PFAIL("masr_pool_window_plan: n_frames out of range (at most 2^30)");
+    int32_t n = 0;
+    pool_windows(n_frames, is_end != 0, [&](int first, int last) {
+        if (n < cap) {
+            first_last[2 * n] = first;
+            first_last[2 * n + 1] = last;
         }
-        p->handles.push_back(q.sid);
-        p->state.push_back(plans[i].empty() ? 0 : 1);
-    }
-    for (int32_t h : refused) {
-        p->handles.push_back(h);
-        p->state.push_back(-1);
-    }
-    *n_sessions = n + (int32_t)refused.size();
-    if (handles_out) *handles_out = p->handles.data();
-    if (state_out) *state_out = p->state.data();
-    if (rows_host) *rows_host = rows_h;
-    if (row_width) *row_width = na ? width : 0;
-    if (rows_dev) *rows_dev = na ? p->rows_out.as<int32_t>() : nullptr;
+        ++n;
+    });
+    *n_windows = n;
     return 0;
 }
 
