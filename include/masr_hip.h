@@ -531,6 +531,15 @@ int masr_resample_feeds(masr_engine* e, const void* src_dev, int64_t src_bytes, 
                         int64_t n_tiles, float* dst_dev, int32_t dst_rows, int64_t dst_stride, void* stream);
 int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc,
                       float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, void* stream);
+/* The same chunk step, which also hands out its encoder rows: enc_out_dev [n, Tq, d_model] (Tq = the step's encoder frames per
+ * stream, the row count of probs_dev) receives exactly the rows the step's CTC head read -- what an attention second pass at the
+ * end of the utterance attends over (masr_rescore_rows).  The final LayerNorm writes where it always did and ONE device-to-device
+ * copy of n * Tq * d_model floats follows the CTC head on `stream`; every launch in front of it is masr_encode_chunk's, so probs /
+ * argmax / maxprob and the streams' caches equal masr_encode_chunk's bit for bit.  masr_encode_chunk itself runs what it ran.
+ * Conformer (the width-generic 512 / 8 path included), Squeezeformer and Efficient Conformer (there Tq is the half-rate count).
+ * Refused by name: DeepSpeech2 (no attention decoder), a null enc_out_dev. */
+int masr_encode_chunk_enc(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc,
+                          float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, float* enc_out_dev, void* stream);
 /* Read back a stream's caches in the reference layout (for parity tests):
  * att [L, H, t, 2*dk], cnn [L, 1, d, kernel-1] -- device pointers, t = current offset.  DeepSpeech2: att <- h [L, rnn_size],
  * cnn <- c [L, rnn_size]; a GRU stream returns h in both (deepspeech2/gru.py: final_state_c = final_state_h). */
@@ -603,6 +612,25 @@ int masr_op_attention_plain(masr_engine* e, const float* q_dev, const float* k_d
  *                        the active lane's workspaces, never synchronises.  A hypothesis' scores do not depend on N, B, the other
  *                        hypotheses, the ids past its length or the lane.  Refused: N outside 1 .. 64, Lmax > max_pos - 1
  *                        (hypotheses longer than max_pos - 1), B * N > 65535, with_right without a right decoder.
+ *   masr_rescore_rows    masr_rescore over frames that are NOT contiguous: frame t of utterance b is row frame_row_dev[b, t] of
+ *                        the matrix rows_dev [n_rows, d_model] -- the kept encoder output of streaming sessions
+ *                        (masr_encode_chunk_enc), whose chunks land wherever the row pool had room, so that nothing is packed into
+ *                        a dense [B, Tmax, d_model] block before the second pass at the end of an utterance.
+ *                          frame_row_dev [B, Tmax] int64: row numbers in frame order; they need be neither contiguous nor
+ *                            increasing, and a row may appear more than once, in one utterance or in several.  n_frames_dev [B]
+ *                            takes enc_lens_dev's place.  Entries behind n_frames[b] are never used: they may be any number.
+ *                          A row number outside [0, n_rows) among the valid frames (the -1 padding, too) stands for a frame of
+ *                            zeros and is never dereferenced.
+ *                          Every address made from a row number is 64-bit: n_rows * d_model * 4 bytes may exceed 2^31.
+ *                        Only the per-layer source k | v projection differs: the tiled f32 GEMM reads its A rows through the
+ *                        table (one fetch of the row number per row and thread, ahead of the K loop) on the tile shape the dense
+ *                        projection takes at the same size, so every output element sees the same MFMA chain and att_dev /
+ *                        r_att_dev equal, bit for bit, masr_rescore's on the gathered block rows[frame_row] with enc_lens =
+ *                        n_frames.  Everything else -- the hypothesis table, sos / eos, with_right, the active lane's workspaces,
+ *                        never synchronising -- is masr_rescore's.  Refused alike (under its own name), and: n_rows <= 0,
+ *                        Tmax < 1, B * Tmax > 2^31 - 1.  (The bit equality holds in the product configuration: the row-table
+ *                        operand has no split-bf16 variant, so with the experimental masr_debug_set key 20 on, which moves
+ *                        masr_rescore's dense projection to that variant, the two differ by its rounding.)
  *   masr_op_decoder_scores  the same launches driven alone, from HOST tables (hyp_host, hyp_lens_host, enc_lens_host), every
  *                        entry validated (lengths in [0, Lmax], ids in [0, vocab_size), frames in [1, Tp]); outputs to host
  *                        arrays; returns when the work has finished.
@@ -613,6 +641,9 @@ int masr_decoder_enable(masr_engine* e, int32_t attention_heads, int32_t linear_
 int masr_rescore(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const int32_t* hyp_dev,
                  const int32_t* hyp_lens_dev, int32_t N, int32_t Lmax, int32_t with_right, float* att_dev, float* r_att_dev,
                  void* stream);
+int masr_rescore_rows(masr_engine* e, const float* rows_dev, int64_t n_rows, const int64_t* frame_row_dev,
+                      const int32_t* n_frames_dev, int32_t B, int32_t Tmax, const int32_t* hyp_dev, const int32_t* hyp_lens_dev,
+                      int32_t N, int32_t Lmax, int32_t with_right, float* att_dev, float* r_att_dev, void* stream);
 int masr_op_decoder_scores(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t Tp,
                            const int32_t* hyp_host, const int32_t* hyp_lens_host, int32_t N, int32_t Lmax, int32_t with_right,
                            float* att_host, float* r_att_host, void* stream);

@@ -114,6 +114,7 @@ SIGNATURES = {
                              C.POINTER(_I), C.POINTER(_P), _P],
     'masr_stream_set_history': [_P, _I, _I],
     'masr_encode_chunk': [_P, C.POINTER(_I), _I, _P, _I, _P, _P, _P, _P],
+    'masr_encode_chunk_enc': [_P, C.POINTER(_I), _I, _P, _I, _P, _P, _P, _P, _P],
     'masr_stream_export_cache': [_P, _I, _P, _P, _P],
     'masr_op_layernorm': [_P, _P, _P, _P, _P, _I, _F, _P],
     'masr_op_gemm': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
@@ -122,6 +123,7 @@ SIGNATURES = {
     'masr_op_attention_plain': [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     'masr_decoder_enable': [_P, _I, _I, _I, _I],
     'masr_rescore': [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
+    'masr_rescore_rows': [_P, _P, C.c_int64, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
     'masr_op_decoder_scores': [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
     'masr_decoder_info': [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     'masr_attention_decode': [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, C.POINTER(_I), _P],

@@ -121,14 +121,15 @@ inline int gemm_act_of(int enc_act) {
     constexpr int t[6] = {ACT_SILU, ACT_RELU, ACT_GELU, ACT_TANH, ACT_HARDTANH, ACT_SELU};
     return enc_act >= 0 && enc_act < 6 ? t[enc_act] : ACT_NONE;
 }
-enum GemmAMode { A_PLAIN = 0, A_CONV2 = 1, A_CONV5 = 2 };     // A_CONV5: the 5x5 stride-3 gather of conv2d6 (A_CONV2 geometry)
+enum GemmAMode { A_PLAIN = 0, A_CONV2 = 1, A_CONV5 = 2, A_ROWS = 3 };     // A_CONV5: the 5x5 stride-3 gather of conv2d6 (A_CONV2 geometry);
+                                                                          // A_ROWS: row m of A is row GemmArgs::rows[m] of a row pool
 enum GemmEpi { EPI_STD = 0, EPI_GLU = 1, EPI_SPLITK = 2, EPI_ACT = 3 };   // EPI_ACT: EPI_STD + GemmAct 3 .. 6 (launch_gemm picks it by a.act);
                                                                 // EPI_GLU is NOT implemented by launch_gemm (gemm_f32.hip has no GLU
                                                                 // epilogue; the number is kept so that EPI_SPLITK keeps its value): the
                                                                 // row-block kernels carry RG_EPI_GLU, the wide path runs launch_glu_wide
 
 struct GemmArgs {
-    const float* A;      // [M, lda] row-major (A_PLAIN) or conv activations [B,T1,F1,C] (A_CONV2 / A_CONV5)
+    const float* A;      // [M, lda] row-major (A_PLAIN), conv activations [B,T1,F1,C] (A_CONV2 / A_CONV5) or a row pool [n_rows, lda] (A_ROWS)
     const float* W;      // [N, K] row-major (K contiguous) -- torch Linear.weight layout
     const float* bias;   // [N] or nullptr
     float* C;            // [M, ldc]
@@ -153,6 +154,11 @@ struct GemmArgs {
     // feats [B, Tin, Fin] through CMVN (mean, istd) and the conv1 weights c1w [9][256], c1b [256]; A is not read (nullptr: from A)
     const float *feats, *mean, *istd, *c1w, *c1b;
     int Tin, Fin;
+    // A_ROWS: row m of the A operand is A + rows[m] * lda (64-bit: the pool may exceed 2^31 bytes), rows [M] int64 on the device.  An
+    // entry outside [0, n_rows) -- the -1 padding of a row table -- is a row of zeros and is never dereferenced.  EPI_STD only; the
+    // tile shapes are A_PLAIN's at the same (M, N), and every output element sees A_PLAIN's MFMA chain on the gathered dense copy
+    const int64_t* rows;
+    int64_t n_rows;
 };
 
 void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s);

@@ -558,9 +558,9 @@ static int distinct_streams(const std::vector<Stream*>& st) {
     return 0;
 }
 
-int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc,
-                      float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, void* stream) {
-    if (!e || !e->finalized) return fail("engine not finalized");
+// the chunk step of both entries: masr_encode_chunk (enc_out_dev == nullptr) and masr_encode_chunk_enc
+static int encode_chunk_any(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc, float* probs_dev,
+                            int32_t* argmax_dev, float* maxprob_dev, float* enc_out_dev, void* stream) {
     ENTER(e);
     CallGuard call_guard(e, (hipStream_t)stream);
     if (n <= 0) return fail("no streams");
@@ -570,11 +570,27 @@ int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, cons
     // (the Conformer step, model_kind 0, has never had this check and gets none here: whether it should is a behaviour decision)
     if (e->cfg.model_kind != 0) CHK(distinct_streams(st));
     switch (e->cfg.model_kind) {
-    case 1: return encode_chunk_squeezeformer(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev);
-    case 2: return encode_chunk_efficient(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev);
-    case 3: return encode_chunk_ds2(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev);
-    default: return encode_chunk_conformer(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev);
+    case 1: return encode_chunk_squeezeformer(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev, enc_out_dev);
+    case 2: return encode_chunk_efficient(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev, enc_out_dev);
+    case 3: return encode_chunk_ds2(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev, enc_out_dev);
+    default: return encode_chunk_conformer(e, s, st, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev, enc_out_dev);
     }
+}
+
+int masr_encode_chunk(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc,
+                      float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, void* stream) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    return encode_chunk_any(e, stream_ids, n, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev, nullptr, stream);
+}
+
+int masr_encode_chunk_enc(masr_engine* e, const int32_t* stream_ids, int32_t n, const float* feats_dev, int32_t Tc,
+                          float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, float* enc_out_dev, void* stream) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (e->cfg.model_kind == 3)
+        return fail("masr_encode_chunk_enc: use_model deepspeech2 has no attention decoder to hand its encoder rows to; use "
+                    "masr_encode_chunk");
+    if (!enc_out_dev) return fail("masr_encode_chunk_enc: enc_out_dev is null (masr_encode_chunk is the step without it)");
+    return encode_chunk_any(e, stream_ids, n, feats_dev, Tc, probs_dev, argmax_dev, maxprob_dev, enc_out_dev, stream);
 }
 
 int masr_stream_export_cache(masr_engine* e, int32_t stream_id, float* att_dev, float* cnn_dev, void* stream) {

@@ -117,8 +117,16 @@ int finalize_decoder(masr_engine* e) {
 
 namespace {
 
+// where the source k | v projection finds the encoder frames: frame t of utterance b is row b * Tp + t of the dense block enc, or
+// (table given: masr_rescore_rows) row table[b * Tp + t] of the row pool enc [n_rows, d]
+struct EncSource {
+    const float* enc;
+    const int64_t* table = nullptr;
+    int64_t n_rows = 0;
+};
+
 // one TransformerDecoder over the hypothesis table -> out [B * N] (reverse: the right-to-left decoder's view of the table)
-int decoder_forward(masr_engine* e, hipStream_t s, const DecoderW& w, int reverse, const float* enc, const int* enc_lens, int B,
+int decoder_forward(masr_engine* e, hipStream_t s, const DecoderW& w, int reverse, const EncSource& src, const int* enc_lens, int B,
                     int Tp, const int* hyp, const int* hyp_lens, int N, int Lmax, float* out) {
     const int d = e->cfg.d_model, V = e->cfg.vocab_size, dff = e->dec.dff, H = e->dec.heads;
     const int S = B * N, Lp = Lmax + 1, M = S * Lp, Mk = B * Tp;
@@ -135,7 +143,8 @@ int decoder_forward(masr_engine* e, hipStream_t s, const DecoderW& w, int revers
         // x <- x + Wo . src_attn(norm2(x), memory): k | v of the utterance's encoder frames projected ONCE for its N hypotheses
         WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, l.n2w, l.n2b, ln, M, d, eps, 0, 0, nullptr, s));
         gemm(e, s, ln, d, l.wq2, l.bq2, qkv, d, M, d, d, ACT_NONE, 1.f, nullptr, 0);
-        gemm(e, s, enc, d, l.wkv2, l.bkv2, kv, 2 * d, Mk, 2 * d, d, ACT_NONE, 1.f, nullptr, 0);
+        if (src.table) gemm_rows(e, s, src.enc, d, src.table, src.n_rows, l.wkv2, l.bkv2, kv, 2 * d, Mk, 2 * d, d);
+        else gemm(e, s, src.enc, d, l.wkv2, l.bkv2, kv, 2 * d, Mk, 2 * d, d, ACT_NONE, 1.f, nullptr, 0);
         launch_dec_attention(qkv, d, kv, kv + d, 2 * d, att, d, hyp_lens, enc_lens, S, N, Lmax, Tp, H, 0, s);
         gemm(e, s, att, d, l.wo2, l.bo2, x, d, M, d, d, ACT_NONE, 1.f, x, d);
         // x <- x + W2 . relu(W1 . norm3(x))
@@ -161,15 +170,16 @@ int rescore_shape_check(const char* who, const void* enc, const void* enc_lens, 
     return 0;
 }
 
-int rescore_impl(masr_engine* e, const float* enc, const int* enc_lens, int B, int Tp, const int* hyp, const int* hyp_lens, int N,
-                 int Lmax, int with_right, float* att, float* r_att, hipStream_t s) {
+int rescore_impl(masr_engine* e, const char* who, const EncSource& src, const int* enc_lens, int B, int Tp, const int* hyp,
+                 const int* hyp_lens, int N, int Lmax, int with_right, float* att, float* r_att, hipStream_t s) {
+    const std::string w(who);
     if (!e->dec.enabled || !e->dec.ready)
-        return fail("masr_rescore: this engine holds no attention decoder (masr_decoder_enable before masr_finalize)");
+        return fail(w + ": this engine holds no attention decoder (masr_decoder_enable before masr_finalize)");
     if (Lmax > e->cfg.max_pos - 1)
-        return fail("masr_rescore: hypotheses longer than max_pos - 1 = " + std::to_string(e->cfg.max_pos - 1) +
+        return fail(w + ": hypotheses longer than max_pos - 1 = " + std::to_string(e->cfg.max_pos - 1) +
                     " tokens have no positional rows (Lmax = " + std::to_string(Lmax) + ")");
     if (with_right && e->dec.nr == 0)
-        return fail("masr_rescore: reverse_weight > 0 needs the right-to-left decoder, and this checkpoint has none (r_num_blocks: 0)");
+        return fail(w + ": reverse_weight > 0 needs the right-to-left decoder, and this checkpoint has none (r_num_blocks: 0)");
     const int d = e->cfg.d_model, V = e->cfg.vocab_size;
     const size_t M = (size_t)B * N * (Lmax + 1), f = sizeof(float);
     CHK(e->dec_x.ensure(M * d * f));
@@ -180,8 +190,8 @@ int rescore_impl(masr_engine* e, const float* enc, const int* enc_lens, int B, i
     CHK(e->dec_hid.ensure(M * e->dec.dff * f));
     CHK(e->dec_logits.ensure(M * V * f));
     CHK(e->dec_rowlp.ensure(M * f));
-    CHK(decoder_forward(e, s, e->dec.left, 0, enc, enc_lens, B, Tp, hyp, hyp_lens, N, Lmax, att));
-    if (with_right) CHK(decoder_forward(e, s, e->dec.right, 1, enc, enc_lens, B, Tp, hyp, hyp_lens, N, Lmax, r_att));
+    CHK(decoder_forward(e, s, e->dec.left, 0, src, enc_lens, B, Tp, hyp, hyp_lens, N, Lmax, att));
+    if (with_right) CHK(decoder_forward(e, s, e->dec.right, 1, src, enc_lens, B, Tp, hyp, hyp_lens, N, Lmax, r_att));
     else HIPCHK(hipMemsetAsync(r_att, 0, (size_t)B * N * f, s));
     LAUNCHCHK();
     return 0;
@@ -221,7 +231,26 @@ int masr_rescore(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_d
     if (!e || !e->finalized) return fail("engine not finalized");
     ENTER(e);
     CallGuard call_guard(e, (hipStream_t)stream);
-    return rescore_impl(e, enc_dev, enc_lens_dev, B, Tp, hyp_dev, hyp_lens_dev, N, Lmax, with_right, att_dev, r_att_dev,
+    return rescore_impl(e, "masr_rescore", EncSource{enc_dev}, enc_lens_dev, B, Tp, hyp_dev, hyp_lens_dev, N, Lmax, with_right, att_dev,
+                        r_att_dev, (hipStream_t)stream);
+}
+
+int masr_rescore_rows(masr_engine* e, const float* rows_dev, int64_t n_rows, const int64_t* frame_row_dev, const int32_t* n_frames_dev,
+                      int32_t B, int32_t Tmax, const int32_t* hyp_dev, const int32_t* hyp_lens_dev, int32_t N, int32_t Lmax,
+                      int32_t with_right, float* att_dev, float* r_att_dev, void* stream) {
+    // (the sizes first: an empty pool or table has no address to give)
+    if (n_rows <= 0) return fail("masr_rescore_rows: n_rows = " + std::to_string(n_rows) + " must be positive");
+    if (Tmax < 1) return fail("masr_rescore_rows: Tmax = " + std::to_string(Tmax) + " must be at least 1");
+    if (!frame_row_dev) return fail("masr_rescore_rows: null argument");
+    CHK(rescore_shape_check("masr_rescore_rows", rows_dev, n_frames_dev, B, Tmax, hyp_dev, hyp_lens_dev, N, Lmax, att_dev, r_att_dev));
+    if ((int64_t)B * Tmax > INT32_MAX) return fail("masr_rescore_rows: B * Tmax must not exceed 2^31 - 1 table entries");
+    if (!e || !e->finalized) return fail("engine not finalized");
+    ENTER(e);
+    CallGuard call_guard(e, (hipStream_t)stream);
+    EncSource src{rows_dev};
+    src.table = frame_row_dev;
+    src.n_rows = n_rows;
+    return rescore_impl(e, "masr_rescore_rows", src, n_frames_dev, B, Tmax, hyp_dev, hyp_lens_dev, N, Lmax, with_right, att_dev, r_att_dev,
                         (hipStream_t)stream);
 }
 
@@ -263,7 +292,7 @@ int masr_op_decoder_scores(masr_engine* e, const float* enc_dev, const int32_t* 
     HIPCHK(hipMemcpyAsync(hyp_d, hyp_host, S * Lmax * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(len_d, hyp_lens_host, S * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(enc_d, enc_lens_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-    CHK(rescore_impl(e, enc_dev, enc_d, B, Tp, hyp_d, len_d, N, Lmax, with_right, att_d, ratt_d, st));
+    CHK(rescore_impl(e, "masr_rescore", EncSource{enc_dev}, enc_d, B, Tp, hyp_d, len_d, N, Lmax, with_right, att_d, ratt_d, st));
     HIPCHK(hipMemcpyAsync(att_host, att_d, S * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(r_att_host, ratt_d, S * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

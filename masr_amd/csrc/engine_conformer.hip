@@ -263,7 +263,7 @@ int encode_full_conformer(masr_engine* e, hipStream_t s, const float* feats_dev,
 // kernels or (is_wide) on the width-generic layer.  Unlike the other families' steps this one has never refused a stream id given
 // twice in one call (distinct_streams): whether it should is a behaviour decision of its own.
 int encode_chunk_conformer(masr_engine* e, hipStream_t s, std::vector<Stream*>& st, const float* feats_dev, int Tc,
-                                  float* probs_dev, int32_t* argmax_dev, float* maxprob_dev) {
+                                  float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, float* enc_out_dev) {
     const int n = (int)st.size();
     const int d = e->cfg.d_model, H = e->cfg.heads, L = e->cfg.num_blocks, pad = e->cfg.cnn_kernel - 1;
     int Tq = 0;
@@ -325,7 +325,7 @@ int encode_chunk_conformer(masr_engine* e, hipStream_t s, std::vector<Stream*>& 
     CHK(e->enc.ensure((size_t)M * d * sizeof(float)));
     if (wide) WIDECHK(PROF_WIDE_LN, launch_layernorm_wide(x, e->after_w, e->after_b, e->enc.as<float>(), M, d, 1e-5f, 0, 0, nullptr, s));
     else launch_layernorm(x, e->after_w, e->after_b, e->enc.as<float>(), M, 1e-5f, 0, 0, nullptr, s);
-    CHK(chunk_ctc(e, s, e->enc.as<float>(), M, probs_dev, argmax_dev, maxprob_dev));
+    CHK(chunk_ctc(e, s, e->enc.as<float>(), M, probs_dev, argmax_dev, maxprob_dev, enc_out_dev));
     for (int i = 0; i < n; ++i) {
         st[i]->cache_t1 = chunk_window(*st[i], Tq).next_cache_t1;
         st[i]->offset += Tq;

@@ -437,9 +437,13 @@ int masr_gbeam_nbest(masr_engine* e, int32_t handle, int32_t nbest, int32_t* tok
 }  // extern "C"
 
 namespace masr {
-// the CTC head on the step's encoder rows: probabilities where the caller asks for them, argmax and its probability always
-int chunk_ctc(masr_engine* e, hipStream_t s, const float* enc, int rows, float* probs, int32_t* argmax, float* maxprob) {
+// the CTC head on the step's encoder rows: probabilities where the caller asks for them, argmax and its probability always.
+// enc_out (masr_encode_chunk_enc): the rows the head read, copied out behind it (one device-to-device copy of rows x width floats)
+int chunk_ctc(masr_engine* e, hipStream_t s, const float* enc, int rows, float* probs, int32_t* argmax, float* maxprob,
+              float* enc_out) {
     if (e->cfg.vocab_size > 16384) return fail(kVocabRefusal);
-    return ctc_head(e, enc, rows, probs, probs ? 1 : 0, argmax, maxprob, s);
+    CHK(ctc_head(e, enc, rows, probs, probs ? 1 : 0, argmax, maxprob, s));
+    if (enc_out) HIPCHK(hipMemcpyAsync(enc_out, enc, (size_t)rows * enc_dim(e) * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
 }
 }  // namespace masr

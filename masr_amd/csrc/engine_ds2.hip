@@ -142,14 +142,14 @@ int ds2_forward(masr_engine* e, hipStream_t s, const float* feats, const int* le
 
 // DeepSpeech2 chunk step, n streams in lock-step (deepspeech2/model.py:79-108): chunk conv + LSTM stack with carried (h, c)
 int encode_chunk_ds2(masr_engine* e, hipStream_t s, std::vector<Stream*>& st, const float* feats_dev, int Tc,
-                            float* probs_dev, int32_t* argmax_dev, float* maxprob_dev) {
+                            float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, float* enc_out_dev) {
     const int n = (int)st.size();
     int Tq = 0;
     const int Tq3 = ((Tc - 1) / 2 - 1) / 2;
     if (Tq3 <= 0) return fail("chunk too short");
     CHK(e->enc.ensure((size_t)n * Tq3 * enc_dim(e) * sizeof(float)));
     CHK(ds2_forward(e, s, feats_dev, nullptr, n, Tc, e->enc.as<float>(), st.data(), &Tq));
-    CHK(chunk_ctc(e, s, e->enc.as<float>(), n * Tq, probs_dev, argmax_dev, maxprob_dev));
+    CHK(chunk_ctc(e, s, e->enc.as<float>(), n * Tq, probs_dev, argmax_dev, maxprob_dev, enc_out_dev));
     for (int i = 0; i < n; ++i) st[i]->offset += Tq;
     return 0;
 }

@@ -129,7 +129,7 @@ int encode_full_efficient(masr_engine* e, hipStream_t s, const float* feats, con
 // input frame rate (the flat regrouping runs over cache + chunk), layers behind the stride layer keep interleaved k|v rows
 // at half the rate (the reference stores them repeat-interleaved, :370); cnn caches hold each layer's own K-1 rows.
 int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Stream*>& st, const float* feats, int Tc,
-                                  float* probs_dev, int32_t* argmax_dev, float* maxprob_dev) {
+                                  float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, float* enc_out_dev) {
     const int n = (int)st.size();
     const int d = e->cfg.d_model, H = e->cfg.heads, L = e->cfg.num_blocks, G = e->group_size;
     // conv2d8 gives 7 frames per 67-frame window: the half-rate layers' caches of an odd chunk do not line up with the next
@@ -247,7 +247,7 @@ int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Stream*>& 
     }
     CHK(e->enc.ensure((size_t)n * T2 * d * sizeof(float)));
     launch_layernorm(x, e->after_w, e->after_b, e->enc.as<float>(), n * T2, 1e-5f, 0, 0, nullptr, s);
-    CHK(chunk_ctc(e, s, e->enc.as<float>(), n * T2, probs_dev, argmax_dev, maxprob_dev));
+    CHK(chunk_ctc(e, s, e->enc.as<float>(), n * T2, probs_dev, argmax_dev, maxprob_dev, enc_out_dev));
     advance_half_rate(st, win, T0, T2);
     return 0;
 }

@@ -107,7 +107,8 @@ int upload_chunk_tables(masr_engine* e, hipStream_t s, const std::vector<AttSeq>
 void advance_half_rate(std::vector<Stream*>& st, const std::vector<ChunkWindow>& win, int T0, int Tr);
 
 // ---- engine_ctc.hip -----------------------------------------------------------------------------------------------------------
-int chunk_ctc(masr_engine* e, hipStream_t s, const float* enc, int rows, float* probs, int32_t* argmax, float* maxprob);
+int chunk_ctc(masr_engine* e, hipStream_t s, const float* enc, int rows, float* probs, int32_t* argmax, float* maxprob,
+              float* enc_out = nullptr);
 
 // ---- the families: engine_conformer.hip, engine_efficient.hip, engine_squeezeformer.hip, engine_ds2.hip --------------------------
 bool is_wide(const masr_engine* e);
@@ -118,8 +119,9 @@ int ds2_forward(masr_engine* e, hipStream_t s, const float* feats, const int* le
                 int* Tq_out);
 typedef int EncodeFullFn(masr_engine* e, hipStream_t s, const float* feats, const int* lens, int B, int T, float* enc_out, int chunk);
 EncodeFullFn encode_full_conformer, encode_full_wide, encode_full_efficient, encode_full_squeezeformer;
+// enc_out_dev (masr_encode_chunk_enc; nullptr: masr_encode_chunk): the step's encoder rows, handed on to chunk_ctc
 typedef int EncodeChunkFn(masr_engine* e, hipStream_t s, std::vector<Stream*>& st, const float* feats, int Tc, float* probs_dev,
-                          int32_t* argmax_dev, float* maxprob_dev);
+                          int32_t* argmax_dev, float* maxprob_dev, float* enc_out_dev);
 EncodeChunkFn encode_chunk_conformer, encode_chunk_efficient, encode_chunk_squeezeformer, encode_chunk_ds2;
 
 }  // namespace masr

@@ -16,6 +16,16 @@ void gemm(masr_engine* e, hipStream_t s, const float* A, int lda, const float* W
     launch_gemm(a, A_PLAIN, EPI_STD, s);
 }
 
+void gemm_rows(masr_engine* e, hipStream_t s, const float* pool, int lda, const int64_t* rows, int64_t n_rows, const float* W,
+               const float* bias, float* C, int ldc, int M, int N, int K) {
+    GemmArgs a{};
+    a.A = pool; a.W = W; a.bias = bias; a.C = C; a.rows = rows; a.n_rows = n_rows;
+    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc;
+    a.act = ACT_NONE; a.alpha = 1.f;
+    ProfScope ps(e, s, PROF_GEMM, 2.0 * M * (double)N * K);
+    launch_gemm(a, A_ROWS, EPI_STD, s);
+}
+
 int enc_dim(const masr_engine* e) {      // width of the encoder output rows
     return e->cfg.model_kind == 3 ? e->cfg.d_model * (e->cfg.causal ? 1 : 2) : e->cfg.d_model;
 }

@@ -232,7 +232,7 @@ int encode_full_squeezeformer(masr_engine* e, hipStream_t s, const float* feats,
 // cache holds the last K-1 adaptive-scaled input rows of the conv module.  TimeReductionLayerStream (k = 1, stride 2) and the
 // recovery are chunk-local.
 int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector<Stream*>& st, const float* feats, int Tc,
-                                      float* probs_dev, int32_t* argmax_dev, float* maxprob_dev) {
+                                      float* probs_dev, int32_t* argmax_dev, float* maxprob_dev, float* enc_out_dev) {
     const int n = (int)st.size();
     const int d = e->cfg.d_model, H = e->cfg.heads, L = e->cfg.num_blocks, K = e->cfg.cnn_kernel, pad = K - 1;
     int T0 = 0;
@@ -312,7 +312,7 @@ int encode_chunk_squeezeformer(masr_engine* e, hipStream_t s, std::vector<Stream
         launch_layernorm(x, w.ln3_w, w.ln3_b, x, M, 1e-5f, 0, 0, nullptr, s);
         CHK(ffn(e, s, ffn_sqz2(w, M, l == L - 1 ? e->enc.as<float>() : x)));
     }
-    CHK(chunk_ctc(e, s, e->enc.as<float>(), n * T0, probs_dev, argmax_dev, maxprob_dev));
+    CHK(chunk_ctc(e, s, e->enc.as<float>(), n * T0, probs_dev, argmax_dev, maxprob_dev, enc_out_dev));
     advance_half_rate(st, win, T0, Tr);
     return 0;
 }

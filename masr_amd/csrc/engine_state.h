@@ -427,6 +427,10 @@ int build_fbank_tables(masr_engine* e);
 void gemm(masr_engine* e, hipStream_t s, const float* A, int lda, const float* W, const float* bias, float* C, int ldc,
           int M, int N, int K, int act, float alpha, const float* R, int ldr, int kind = PROF_GEMM,
           const int* lens = nullptr, int mask_tp = 0);
+// C[M, N] = A . W^T + bias with row m of A = row rows[m] of pool [n_rows, lda] (A_ROWS of gemm_f32.hip; never the split-bf16 variant,
+// so bit-equal to gemm() on the gathered copy only while masr_debug_set key 20 is off)
+void gemm_rows(masr_engine* e, hipStream_t s, const float* pool, int lda, const int64_t* rows, int64_t n_rows, const float* W,
+               const float* bias, float* C, int ldc, int M, int N, int K);
 
 // ---- engine_attdecoder.hip ----------------------------------------------------------------------------------------------------
 int finalize_decoder(masr_engine* e);       // masr_finalize: the decoder's weights, before the model's finalize drops the host copies

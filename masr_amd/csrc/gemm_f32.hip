@@ -11,6 +11,10 @@
 // * A operand modes: plain row-major, or implicit-GEMM gather for the subsampling convs over channels-last
 //   activations (reference conformer/subsampling.py:86-211): 3x3 stride 2 (A_CONV2) or 5x5 stride 3 (A_CONV5, conv2d6),
 //   K ordered [32-channel block][kh][kw][channel] so that overlapping window columns are re-read while still cached.
+//   A_ROWS: row m is row rows[m] of a row pool (the kept encoder frames of streaming sessions, masr_rescore_rows): the staging is
+//   A_PLAIN's, 8 threads x float4 per slab row, only the source pointer differs; the row number is read once per row and thread
+//   ahead of the K loop, the address is 64-bit, and a number outside [0, n_rows) stages zeros.  Bit-identical to A_PLAIN on the
+//   gathered dense copy: the same tile shape at the same (M, N), so every output element sees the same MFMA chain from zero.
 // * Epilogue: bias, ReLU/SiLU, alpha, residual, row masking.  (The K = 256 projections of the layers use
 //   rowgemm.hip, the FFN ffn_pc.hip; this kernel serves conv2, the embed projection, the positional-key
 //   precompute and the full-probability CTC head; the large offline conv2 runs on conv2_rows_kernel below.)
@@ -78,7 +82,13 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(GemmArgs p) {
         const int m = bm + lrow + RPP * i;
         aok[i] = m < p.M;
         const int mm = aok[i] ? m : 0;
-        if (AMODE == A_PLAIN) {
+        if constexpr (AMODE == A_ROWS) {
+            // the row number is fetched once per row and thread, here, ahead of the K loop; a number outside [0, n_rows) (the -1
+            // padding of a table) makes a row of zeros and no address
+            const int64_t r = p.rows[mm];
+            aok[i] = aok[i] && r >= 0 && r < p.n_rows;
+            aptr[i] = p.A + (aok[i] ? (size_t)r * (size_t)p.lda : (size_t)0) + lc4;
+        } else if (AMODE == A_PLAIN) {
             aptr[i] = p.A + (size_t)mm * p.lda + lc4;
         } else {
             const int f2 = mm % p.F2;
@@ -100,7 +110,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(GemmArgs p) {
     f32x4 areg[AL], wreg[WL];
     auto load_slab = [&](int kt) {
         size_t aoff;
-        if (AMODE == A_PLAIN) {
+        if constexpr (AMODE == A_ROWS) {
+            aoff = (size_t)kt * BK;       // (the row is in aptr: only the source pointer differs from A_PLAIN)
+        } else if (AMODE == A_PLAIN) {
             aoff = (size_t)kt * BK;
         } else {
             // K is ordered [channel block of 32][kh][kw][32 channels] (weights re-laid out at load): slab kt = window position
@@ -525,6 +537,14 @@ static int conv2_tiles(const GemmArgs& a) {
 }
 bool gemm_conv2_rows(const GemmArgs& a) { return a.M > 0 && conv2_tiles(a) == 0; }
 
+// Tile choice of the row-major EPI_STD launches (A_PLAIN, its EPI_ACT twin and A_ROWS): fill >= 256 CUs.  128x128 when that already
+// yields enough workgroups, otherwise 64x128 / 64x64 (N = 256 projections at M = B*T' ~ 8k rows).  -> the tile's BM + BN
+static int std_tiles(const GemmArgs& a) {
+    const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
+    const long t64 = (long)((a.M + 63) / 64) * ((a.N + 127) / 128);
+    return t128 >= 384 ? 256 : t64 >= 200 ? 192 : 128;
+}
+
 void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) return;
     if (a.act > ACT_SILU) {       // gelu / tanh / hardtanh / selu: the plain tiled launch only (wide_ffn, masr_op_gemm)
@@ -532,11 +552,22 @@ void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s) {
             note_launch_error("launch_gemm: an activation behind silu runs on the plain tiled launch only", hipErrorInvalidValue);
             return;
         }
-        const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);     // the tile choice of the EPI_STD launch below
-        const long t64 = (long)((a.M + 63) / 64) * ((a.N + 127) / 128);
-        if (t128 >= 384) launch_t<128, 128, 2, 2, A_PLAIN, EPI_ACT>(a, s);
-        else if (t64 >= 200) launch_t<64, 128, 2, 2, A_PLAIN, EPI_ACT>(a, s);
+        const int tiles = std_tiles(a);
+        if (tiles == 256) launch_t<128, 128, 2, 2, A_PLAIN, EPI_ACT>(a, s);
+        else if (tiles == 192) launch_t<64, 128, 2, 2, A_PLAIN, EPI_ACT>(a, s);
         else launch_t<64, 64, 2, 2, A_PLAIN, EPI_ACT>(a, s);
+        return;
+    }
+    if (amode == A_ROWS) {        // row-table A (GemmArgs::rows): instantiations of their own, A_PLAIN's tile at the same (M, N)
+        if (epi != EPI_STD || !a.rows || a.n_rows <= 0 || a.K % BK) {
+            note_launch_error("launch_gemm: the row-table A operand takes EPI_STD, a table, n_rows > 0 and K a multiple of 32",
+                              hipErrorInvalidValue);
+            return;
+        }
+        const int tiles = std_tiles(a);
+        if (tiles == 256) launch_t<128, 128, 2, 2, A_ROWS, EPI_STD>(a, s);
+        else if (tiles == 192) launch_t<64, 128, 2, 2, A_ROWS, EPI_STD>(a, s);
+        else launch_t<64, 64, 2, 2, A_ROWS, EPI_STD>(a, s);
         return;
     }
     if (amode == A_CONV2 && epi == EPI_SPLITK) {      // caller set a.C = partial buffer, a.nsplit, a.ksplit
@@ -586,12 +617,9 @@ void launch_gemm(const GemmArgs& a, int amode, int epi, hipStream_t s) {
         else launch_t<64, 64, 2, 2, A_PLAIN, EPI_SPLITK>(a, s);
         return;
     }
-    // Tile choice: fill >= 256 CUs.  128x128 when that already yields enough workgroups,
-    // otherwise 64x128 / 64x64 (N = 256 projections at M = B*T' ~ 8k rows).
-    const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    const long t64 = (long)((a.M + 63) / 64) * ((a.N + 127) / 128);
-    if (t128 >= 384) launch_t<128, 128, 2, 2, A_PLAIN, EPI_STD>(a, s);
-    else if (t64 >= 200) launch_t<64, 128, 2, 2, A_PLAIN, EPI_STD>(a, s);
+    const int tiles = std_tiles(a);
+    if (tiles == 256) launch_t<128, 128, 2, 2, A_PLAIN, EPI_STD>(a, s);
+    else if (tiles == 192) launch_t<64, 128, 2, 2, A_PLAIN, EPI_STD>(a, s);
     else launch_t<64, 64, 2, 2, A_PLAIN, EPI_STD>(a, s);
 }
 

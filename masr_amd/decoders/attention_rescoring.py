@@ -17,8 +17,16 @@ probabilities, only the n-best rows coming back (one pinned copy, one wait).  Bo
 (masr_rescore), on the stream and the lane of the pass whose encoder output they read.  The winner is the highest score; an exact
 tie goes to the hypothesis that ranked earlier in the search.
 
-Left out: streaming sessions (rescoring at the end of a stream would need the whole session's encoder output kept) and
-language-model fusion in the first pass."""
+Streaming sessions (``predict_stream`` / ``serving.StreamPool``) are opt-in: ``attention_rescoring_decoder_conf.on_streams``.
+``'refuse'`` (default, and what a configuration without the key gets): the decoder is refused on streams with ``STREAM_REFUSAL``.
+``'rescore_at_end'``: the U2 serving mode.  Each session's first pass is the device-resident CTC prefix search of this block
+(``_pruner.fork()``: no language model, the block's beam_size / cutoff_prob / cutoff_top_n) and its partial results are that
+search's best prefix; every chunk step also hands out its encoder rows (masr_encode_chunk_enc), which the pool keeps in one
+device row pool; in the step that ends an utterance the n-best of the live search is rescored against ALL kept frames of the
+session through the row table (masr_rescore_rows: nothing is gathered into a dense block), and the result is the winner with the
+combined score.  ``first_pass`` has no meaning there: a stream's first pass is always the device-resident search.
+
+Left out: language-model fusion in the first pass."""
 import ctypes as C
 
 import numpy as np
@@ -29,19 +37,36 @@ from masr_amd._lib import check
 
 STREAM_REFUSAL = ("decoder='attention_rescoring' does not run on streaming sessions (predict_stream / StreamPool): rescoring at the "
                   "end of a stream would need the whole session's encoder output kept, which is left out; use predict / "
-                  "predict_batch, or ctc_greedy / ctc_beam_search for streams")
+                  "predict_batch, or ctc_greedy / ctc_beam_search for streams.  "
+                  "attention_rescoring_decoder_conf.on_streams: 'rescore_at_end' keeps it and rescores when the utterance ends")
 
 BEAM_MIN, BEAM_MAX = 1, 64
 FIRST_PASSES = ('host', 'gpu')      # where the first pass's prefix search runs
+ON_STREAMS = ('refuse', 'rescore_at_end')      # attention_rescoring_decoder_conf.on_streams
+
+
+def check_on_streams(value):
+    """a value of ``attention_rescoring_decoder_conf.on_streams`` -> itself; one outside ``ON_STREAMS`` is refused by name"""
+    if value not in ON_STREAMS:
+        raise _lib.MasrError(f'attention_rescoring_decoder_conf.on_streams={value!r} is not supported: one of {ON_STREAMS}')
+    return value
+
+
+def on_streams(configs):
+    """``attention_rescoring_decoder_conf.on_streams`` of a predictor's configuration: 'refuse' where the block or the key is
+    absent"""
+    conf = configs.get('attention_rescoring_decoder_conf', None) or {}
+    return check_on_streams(dict(conf).get('on_streams', 'refuse'))
 
 
 def validate_rescoring_conf(conf, model_conf=None, r_num_blocks=None):
     """``attention_rescoring_decoder_conf`` -> dict(beam_size, ctc_weight, reverse_weight, cutoff_prob, cutoff_top_n, num_processes).
     ``beam_size`` 1 .. 64 (default 10), ``ctc_weight`` (default 0.5), ``reverse_weight`` (default ``model_conf.reverse_weight``,
     0 without one), ``cutoff_prob`` / ``cutoff_top_n`` as in the CTC search block (0.99 / 40).  ``r_num_blocks`` given: a positive
-    ``reverse_weight`` needs a right-to-left decoder."""
+    ``reverse_weight`` needs a right-to-left decoder.  ``on_streams`` ('refuse' / 'rescore_at_end') and ``first_pass`` are passed
+    on only when named."""
     conf = dict(conf or {})
-    known = ('beam_size', 'ctc_weight', 'reverse_weight', 'cutoff_prob', 'cutoff_top_n', 'num_processes', 'first_pass')
+    known = ('beam_size', 'ctc_weight', 'reverse_weight', 'cutoff_prob', 'cutoff_top_n', 'num_processes', 'first_pass', 'on_streams')
     for k in conf:
         if k not in known:
             raise _lib.MasrError(f'attention_rescoring_decoder_conf.{k} is not a known key (known: {known})')
@@ -69,6 +94,8 @@ def validate_rescoring_conf(conf, model_conf=None, r_num_blocks=None):
             raise _lib.MasrError(f'attention_rescoring_decoder_conf.first_pass={conf["first_pass"]!r} is not supported: one of '
                                  f'{FIRST_PASSES}')
         out['first_pass'] = conf['first_pass']
+    if 'on_streams' in conf:            # (not named: 'refuse', what streams always got)
+        out['on_streams'] = check_on_streams(conf['on_streams'])
     if r_num_blocks is not None and out['reverse_weight'] > 0 and r_num_blocks == 0:
         raise _lib.MasrError(f'attention_rescoring_decoder_conf.reverse_weight={out["reverse_weight"]} needs the right-to-left '
                              f'decoder, and this checkpoint has none (decoder_conf.r_num_blocks: 0)')
@@ -106,7 +133,7 @@ def build_table(nbest, max_pos=None):
 
 class AttentionRescoringDecoder:
     def __init__(self, vocab_list, beam_size=10, ctc_weight=0.5, reverse_weight=0.0, cutoff_prob=0.99, cutoff_top_n=40,
-                 num_processes=10, blank_id=0, first_pass='host'):
+                 num_processes=10, blank_id=0, first_pass='host', on_streams='refuse'):
         from masr_amd.decoders.beam_search_decoder import BeamSearchDecoder
         self.vocab_list = vocab_list
         self.beam_size, self.ctc_weight, self.reverse_weight = int(beam_size), float(ctc_weight), float(reverse_weight)
@@ -123,6 +150,7 @@ class AttentionRescoringDecoder:
                                  f"{cutoff_top_n} is beyond the GPU prefix search (beam_size 2 .. 512, cutoff_top_n <= 64, its "
                                  f"tables within 160 KB of LDS); use first_pass='host'")
         self.first_pass = first_pass
+        self.on_streams = check_on_streams(on_streams)
 
     def _text(self, toks):
         return ''.join(self.vocab_list[t] for t in toks).replace('<space>', ' ')

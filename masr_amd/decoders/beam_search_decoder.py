@@ -455,28 +455,41 @@ class BeamSearchDecoder:
                                               max_len, C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         if nbest is not None:
-            # the chunk's one result is entry 0 of the rows: ONE packed copy brings everything back.  Prefixes of a stream are far
-            # shorter than the 5000 frames its pool allows: the rows hold 512 tokens and a longer prefix is an error by name
-            nl = 512
-            ntoks = torch.zeros(1, nbest, nl, dtype=torch.int32, device=eng.device)
-            nlens = torch.zeros(1, nbest, dtype=torch.int32, device=eng.device)
-            nscores = torch.zeros(1, nbest, dtype=torch.float32, device=eng.device)
-            count = torch.zeros(1, dtype=torch.int32, device=eng.device)
-            check(self._lib.masr_gbeam_nbest(eng.h, self._gstream, nbest, C.c_void_p(ntoks.data_ptr()), nl,
-                                             C.c_void_p(nlens.data_ptr()), C.c_void_p(nscores.data_ptr()),
-                                             C.c_void_p(count.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-            rows = torch.cat([ntoks, nlens[:, :, None], nscores.view(torch.int32)[:, :, None]], 2)
-            flat = torch.cat([rows.view(-1), count]).cpu().numpy()
-            if int(flat[:nbest * (nl + 2)].reshape(nbest, nl + 2)[:, nl].max()) > nl:
-                raise _lib.MasrError(f'decode_chunk(nbest={nbest}): a prefix of more than {nl} tokens does not fit the n-best rows')
-            ids = self._unpacked_nbest(flat, 1, nbest, nl, True)[0]
-            self.last_nbest_tokens = [t for t, _ in ids]
-            self.last_nbest = [(sc, self._text(t)) for t, sc in ids]
-            self.last_tokens = list(ids[0][0])
-            return self.last_nbest[0]
+            return self._read_nbest(eng, nbest)
         n = int(lens.item())
         self.last_tokens = toks[0, :n].cpu().numpy().tolist()
         return float(scores.item()), self._text(self.last_tokens)
+
+    def live_nbest(self, nbest):
+        """the (at most ``nbest``) best prefixes of the device-resident streaming search as it stands, nothing advanced
+        (masr_gbeam_nbest alone) -> (score, text) of the best; ``last_nbest`` / ``last_nbest_tokens`` / ``last_tokens`` as after
+        ``decode_chunk(nbest=)``.  For a session whose last feed decoded no window; the search must have seen a chunk."""
+        nbest = self.check_nbest(nbest)
+        if self._gstream is None:
+            raise _lib.MasrError('live_nbest: this decoder has no device-resident search yet (no chunk was decoded)')
+        return self._read_nbest(self._geng, nbest)
+
+    def _read_nbest(self, eng, nbest):
+        """masr_gbeam_nbest on the current stream and its one packed copy back"""
+        # the chunk's one result is entry 0 of the rows: ONE packed copy brings everything back.  Prefixes of a stream are far
+        # shorter than the 5000 frames its pool allows: the rows hold 512 tokens and a longer prefix is an error by name
+        nl = 512
+        ntoks = torch.zeros(1, nbest, nl, dtype=torch.int32, device=eng.device)
+        nlens = torch.zeros(1, nbest, dtype=torch.int32, device=eng.device)
+        nscores = torch.zeros(1, nbest, dtype=torch.float32, device=eng.device)
+        count = torch.zeros(1, dtype=torch.int32, device=eng.device)
+        check(self._lib.masr_gbeam_nbest(eng.h, self._gstream, nbest, C.c_void_p(ntoks.data_ptr()), nl,
+                                         C.c_void_p(nlens.data_ptr()), C.c_void_p(nscores.data_ptr()),
+                                         C.c_void_p(count.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        rows = torch.cat([ntoks, nlens[:, :, None], nscores.view(torch.int32)[:, :, None]], 2)
+        flat = torch.cat([rows.view(-1), count]).cpu().numpy()
+        if int(flat[:nbest * (nl + 2)].reshape(nbest, nl + 2)[:, nl].max()) > nl:
+            raise _lib.MasrError(f'decode_chunk(nbest={nbest}): a prefix of more than {nl} tokens does not fit the n-best rows')
+        ids = self._unpacked_nbest(flat, 1, nbest, nl, True)[0]
+        self.last_nbest_tokens = [t for t, _ in ids]
+        self.last_nbest = [(sc, self._text(t)) for t, sc in ids]
+        self.last_tokens = list(ids[0][0])
+        return self.last_nbest[0]
 
     def reset_decoder(self):
         """beam_search_decoder.py:93-96."""

@@ -832,14 +832,21 @@ class HipEngine:
         check(self.lib.masr_stream_offset(self.h, sid, C.byref(off)))
         return off.value
 
-    def encode_chunk(self, stream_ids, feats, want_probs=True, want_argmax=False):
-        """feats f32 [n, Tc, 80] (device) -> probs [n, Tc', V] (+ argmax/maxprob [n, Tc'])."""
+    def encode_chunk(self, stream_ids, feats, want_probs=True, want_argmax=False, want_enc=False):
+        """feats f32 [n, Tc, 80] (device) -> probs [n, Tc', V] (+ argmax/maxprob [n, Tc']).  ``want_enc=True`` (attention
+        families): masr_encode_chunk_enc, and a fourth value comes back, the step's encoder rows [n, Tc', d_model] -- what the CTC
+        head read; without the flag the call and the three values are what they were."""
         n, Tc, _ = feats.shape
         Tq = self.out_frames(Tc)
         ids = (C.c_int32 * n)(*stream_ids)
         probs = torch.empty(n, Tq, self.vocab_size, dtype=torch.float32, device=self.device) if want_probs else None
         idx = torch.empty(n, Tq, dtype=torch.int32, device=self.device) if want_argmax else None
         mp = torch.empty(n, Tq, dtype=torch.float32, device=self.device) if want_argmax else None
+        if want_enc:
+            enc = torch.empty(n, Tq, self.d_model, dtype=torch.float32, device=self.device)
+            check(self.lib.masr_encode_chunk_enc(self.h, ids, n, _ptr(feats), Tc, _ptr(probs), _ptr(idx), _ptr(mp), _ptr(enc),
+                                                 _stream()))
+            return probs, idx, mp, enc
         check(self.lib.masr_encode_chunk(self.h, ids, n, _ptr(feats), Tc, _ptr(probs), _ptr(idx), _ptr(mp), _stream()))
         return probs, idx, mp
 
@@ -870,6 +877,26 @@ class HipEngine:
         r_att = torch.empty(B, N, dtype=torch.float32, device=self.device)
         check(self.lib.masr_rescore(self.h, _ptr(enc), _ptr(enc_lens), B, Tp, _ptr(hyps), _ptr(hyp_lens), N, Lmax,
                                     1 if with_right else 0, _ptr(att), _ptr(r_att), _stream()))
+        return att, r_att
+
+    def rescore_rows(self, rows, frame_row, n_frames, hyps, hyp_lens, with_right=True):
+        """masr_rescore_rows on the current stream and the active lane: ``rescore`` over encoder frames that are not contiguous.
+        ``rows`` [n_rows, d] float32 (a row pool), ``frame_row`` [B, Tmax] int64: frame t of utterance b is row ``frame_row[b, t]``
+        (any order; entries behind ``n_frames[b]`` are never used; a number outside [0, n_rows) among the valid ones stands for a
+        frame of zeros), ``n_frames`` [B] int32; ``hyps`` / ``hyp_lens`` / ``with_right`` and the (att, r_att) that come back as
+        in ``rescore``, bit for bit what it gives on ``rows[frame_row]``.  Nothing is waited for."""
+        n_rows, d = rows.shape
+        B, Tmax = frame_row.shape
+        _, N, Lmax = hyps.shape
+        if not (rows.is_contiguous() and frame_row.is_contiguous() and hyps.is_contiguous() and rows.dtype == torch.float32
+                and frame_row.dtype == torch.int64 and n_frames.dtype == torch.int32 and hyps.dtype == torch.int32
+                and hyp_lens.dtype == torch.int32 and d == self.d_model):
+            raise ValueError('rescore_rows: contiguous float32 rows [n_rows, d_model], int64 frame_row and int32 n_frames / hyps / '
+                             'hyp_lens expected')
+        att = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        r_att = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        check(self.lib.masr_rescore_rows(self.h, _ptr(rows), n_rows, _ptr(frame_row), _ptr(n_frames), B, Tmax, _ptr(hyps),
+                                         _ptr(hyp_lens), N, Lmax, 1 if with_right else 0, _ptr(att), _ptr(r_att), _stream()))
         return att, r_att
 
     def op_decoder_scores(self, enc, enc_lens, hyps, hyp_lens, with_right=True):

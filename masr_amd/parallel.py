@@ -226,6 +226,11 @@ class ShardedStreamPool:
     ``close(handle)``, ``reset(handle)`` and ``vocab`` / ``last_tokens(handle)`` for the gather."""
 
     def __init__(self, pool, group=None):
+        if getattr(pool, 'rescoring', False):
+            from masr_amd._lib import MasrError
+            raise MasrError("ShardedStreamPool does not take a pool of decoder 'attention_rescoring' sessions "
+                            "(attention_rescoring_decoder_conf.on_streams 'rescore_at_end'): the gather ships the tokens of partial "
+                            "results, and the rescored result of an utterance's end has no place in it yet; run one StreamPool per GPU")
         self.pool = pool
         self.group = group
         self.rank, self.world = world_info(group)

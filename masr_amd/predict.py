@@ -444,14 +444,19 @@ class MASRPredictor:
         the utterance so far, in seconds since the utterance began (``StreamPool(timestamps=True)``: its cost is stated there).
         The flag of an utterance's first call decides for the utterance; change it after ``reset_stream()``.
         ``nbest=N`` (decoder ctc_beam_search): the result gains ``'nbest'`` as in ``predict``, read from the stream's
-        device-resident search after every decoded chunk; the utterance's first call decides the value, as with ``timestamps``."""
+        device-resident search after every decoded chunk; the utterance's first call decides the value, as with ``timestamps``.
+        ``decoder: attention_rescoring`` runs here only with ``attention_rescoring_decoder_conf.on_streams: 'rescore_at_end'``:
+        the partial results are the CTC first pass's, and the call with ``is_end=True`` returns the rescored winner with the
+        combined score (serving.py has the whole of it)."""
         nbest = self._nbest(nbest)
         if not self.configs.streaming:
             raise Exception(f"不支持改该模型流式识别，当前模型：{self.configs.use_model}，参数streaming为：{self.configs.streaming}")
         self._no_itn(is_itn)
         if self.configs.decoder == 'attention_rescoring':
-            from masr_amd.decoders.attention_rescoring import STREAM_REFUSAL
-            raise Exception(STREAM_REFUSAL)
+            # (attention_rescoring_decoder_conf.on_streams: 'rescore_at_end' lifts it: the pool of one session rescores at is_end)
+            from masr_amd.decoders.attention_rescoring import STREAM_REFUSAL, on_streams
+            if on_streams(self.configs) != 'rescore_at_end':
+                raise Exception(STREAM_REFUSAL)
         if self.configs.decoder == 'attention':
             from masr_amd.decoders.attention_decoder import STREAM_REFUSAL
             raise Exception(STREAM_REFUSAL)

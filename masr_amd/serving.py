@@ -38,6 +38,18 @@ step in which the pool outgrows its allocation re-houses it, into twice the rows
 gains ``'tokens'`` as offline (decoders/ctc_alignment.py), in seconds on the session's own clock.  Such a pool is a
 ``LockStepPool`` for ``ctc_greedy`` too; it costs V * 4 bytes of device memory per encoder frame and session (V = 4233: 17 KB per
 frame, about 4 MB per 10 s of speech), bounded by the stream's own frame limit and given back on ``reset`` / ``close``.
+
+``decoder: attention_rescoring`` with ``attention_rescoring_decoder_conf.on_streams: 'rescore_at_end'`` (without the key the
+decoder is refused on streams, as it always was) -- a ``LockStepPool`` whose sessions search like ``ctc_beam_search`` sessions
+without a language model (each its own fork of the rescoring block's search; the partial results are that first pass's best
+prefix and score) while every lock-step call goes through ``masr_encode_chunk_enc`` and its encoder rows are appended to a second
+row pool [n_rows, d_model] (a second ``RowAllocator``, the same slab growth, one indexed copy of the size of the call:
+d_model * 4 bytes per encoder frame and session, 1 KB at 256).  In the step whose feed carried ``is_end=True`` the n-best of the
+session's live search is read behind its last window and ONE masr_rescore_rows launch scores the hypotheses of all sessions
+that end in that step against all of their kept frames through the row tables (one staged copy up, one back; more than
+65535 // beam_size sessions ending together are split into that many per launch, the call's own limit); the result is the
+winner with the combined score.  ``last_rescoring`` / ``encoder_rows`` show what happened; ``timestamps=True`` composes (the
+winner is what is aligned); ``reset`` / ``close`` give the rows back.
 """
 import ctypes as C
 import os
@@ -134,7 +146,8 @@ class StreamPool:
 
     def __new__(cls, predictor, max_frames_out=0, timestamps=False, nbest=None):
         if cls is StreamPool:                                  # the one place the framing is chosen
-            lock_step = predictor.configs.decoder == 'ctc_beam_search' or timestamps or os.environ.get('MASR_POOL_PY')
+            lock_step = (predictor.configs.decoder in ('ctc_beam_search', 'attention_rescoring') or timestamps
+                         or os.environ.get('MASR_POOL_PY'))
             cls = LockStepPool if lock_step else CStepPool
         return super().__new__(cls)
 
@@ -143,12 +156,21 @@ class StreamPool:
         if not cfg.streaming or not ('former' in cfg.use_model or cfg.use_model == 'deepspeech2'):
             raise Exception(f"不支持改该模型流式识别，当前模型：{cfg.use_model}，参数streaming为：{cfg.streaming}")
         if cfg.decoder == 'attention_rescoring':
-            from masr_amd.decoders.attention_rescoring import STREAM_REFUSAL
-            raise Exception(STREAM_REFUSAL)
+            # opt-in (attention_rescoring_decoder_conf.on_streams: 'rescore_at_end'); without the key, or without the block, the
+            # refusal streams always got -- before anything of a pool exists
+            from masr_amd.decoders.attention_rescoring import STREAM_REFUSAL, on_streams
+            if on_streams(cfg) != 'rescore_at_end':
+                raise Exception(STREAM_REFUSAL)
+            dec = predictor.rescoring_decoder
+            if not dec._pruner.gpu_search_supported(1, len(predictor._text_featurizer.vocab_list)):
+                raise MasrError(f"attention_rescoring_decoder_conf.on_streams='rescore_at_end' with beam_size={dec.beam_size}, "
+                                f"cutoff_top_n={dec._pruner.cutoff_top_n}: a stream's first pass is the device-resident prefix search "
+                                f"(beam_size 2 .. 512, cutoff_top_n <= 64, its tables within 160 KB of LDS), whose n-best is what "
+                                f"is rescored")
         if cfg.decoder == 'attention':
             from masr_amd.decoders.attention_decoder import STREAM_REFUSAL
             raise Exception(STREAM_REFUSAL)
-        if cfg.decoder not in ('ctc_greedy', 'ctc_beam_search'):
+        if cfg.decoder not in ('ctc_greedy', 'ctc_beam_search', 'attention_rescoring'):
             raise Exception(f'unknown decoder {cfg.decoder}')
         # nbest=N (ctc_beam_search sessions): every result gains 'nbest': [{'text', 'score'}], read from the session's
         # device-resident search behind each decoded chunk (masr_gbeam_nbest); the predictor refuses what has no such n-best
@@ -211,6 +233,12 @@ class StreamPool:
         raise MasrError('this StreamPool keeps no posteriors: create it with timestamps=True')
 
     posteriors = posterior_rows
+
+    def encoder_rows(self, handle):
+        raise MasrError("this StreamPool keeps no encoder rows: decoder 'attention_rescoring' with "
+                        "attention_rescoring_decoder_conf.on_streams 'rescore_at_end' does")
+
+    last_rescoring = encoder_output = encoder_rows
 
 
 class _CSession:
@@ -447,7 +475,8 @@ class _HostStage:
 
 
 class _Session:
-    __slots__ = ('sid', 'remained', 'fresh', 'f0', 'nf', 'row', 'frames', 'result', 'decoder', 'tokens', 'beam_last', 'samples')
+    __slots__ = ('sid', 'remained', 'fresh', 'f0', 'nf', 'row', 'frames', 'result', 'decoder', 'tokens', 'beam_last', 'samples',
+                 'rescored')
 
     def __init__(self, sid, row, decoder=None):
         self.sid = sid
@@ -462,6 +491,7 @@ class _Session:
         self.tokens = []              # token ids of the last partial result
         self.beam_last = None         # beam search: the last decode_chunk result (what a step without a window returns)
         self.samples = 0              # samples fed so far at the model's rate (timestamps: the end of the session's clock)
+        self.rescored = None          # rescore_at_end: the record of the session's last rescoring (``last_rescoring``)
 
 
 class LockStepPool(StreamPool):
@@ -476,7 +506,9 @@ class LockStepPool(StreamPool):
     def __init__(self, predictor, max_frames_out=0, timestamps=False, nbest=None):
         super().__init__(predictor, max_frames_out, timestamps, nbest)
         self.min_samples = 320 if self.method == 'linear' else 400
-        self.beam = predictor.configs.decoder == 'ctc_beam_search'
+        # rescore_at_end sessions search like beam sessions (their own LM-free search) and keep their encoder rows
+        self.rescoring = predictor.configs.decoder == 'attention_rescoring'
+        self.beam = predictor.configs.decoder == 'ctc_beam_search' or self.rescoring
         self._last_packed = None
         self._fed = {}                # handle -> is_end of the sessions fed since the last step
         self._free_rows = []
@@ -491,6 +523,10 @@ class LockStepPool(StreamPool):
             self._alloc = RowAllocator(self.ROW_SLAB)
             self._post = torch.empty(0, self.engine.vocab_size, dtype=torch.float32, device=self.engine.device)    # the row pool
             self._reduction = self.engine.frame_reduction()
+        if self.rescoring:
+            from masr_amd.posterior_rows import RowAllocator
+            self._enc_alloc = RowAllocator(self.ROW_SLAB)      # (d_model = 256: 4 MB per slab)
+            self._enc = torch.empty(0, self.engine.d_model, dtype=torch.float32, device=self.engine.device)       # the encoder row pool
 
     # ---- session life cycle ---------------------------------------------------------------------------------------------
     def _grow(self, rows, frames):
@@ -514,6 +550,8 @@ class LockStepPool(StreamPool):
         return self._stage.put(idx, np.int64)
 
     def _new_decoder(self):
+        if self.rescoring:            # the first pass of the rescoring block: no language model, its beam_size and cutoffs
+            return self.predictor.rescoring_decoder._pruner.fork()
         return self.predictor.beam_search_decoder.fork() if self.beam else None
 
     def open(self):
@@ -535,6 +573,8 @@ class LockStepPool(StreamPool):
         self._fed.pop(handle, None)
         if self.timestamps:
             self._alloc.release(handle)
+        if self.rescoring:
+            self._enc_alloc.release(handle)
 
     def reset(self, handle):
         """start a new utterance on an open session (MASRPredictor.reset_stream, predict.py:346-353)"""
@@ -547,6 +587,8 @@ class LockStepPool(StreamPool):
         self._fed.pop(handle, None)
         if self.timestamps:
             self._alloc.release(handle)
+        if self.rescoring:
+            self._enc_alloc.release(handle)
 
     def _queue(self, s, route, is_end, sample_rate):
         # wire PCM, the common format, is kept as int16 (a view of the caller's bytes); x / 2^15 -- the float32 value
@@ -569,17 +611,22 @@ class LockStepPool(StreamPool):
     def _keep_posteriors(self, items, probs):
         """append the rows ``probs`` [n, Tq, V] of one lock-step call to the sessions' histories: n * Tq rows of the pool, taken
         wherever it has room, filled with one copy of the size of this call (never of a history)"""
-        tq = probs.shape[1]
-        rows = np.concatenate([self._alloc.take(s.sid, tq) for s, _ in items])
-        if self._alloc.capacity > self._post.shape[0]:
+        self._post = self._append_rows(self._alloc, self._post, items, probs)
+
+    def _append_rows(self, alloc, pool, items, block):
+        """rows ``block`` [n, Tq, width] of one lock-step call into the row pool ``pool`` [n_rows, width] whose rows ``alloc`` hands
+        out -> the pool (another tensor when it has grown)"""
+        tq = block.shape[1]
+        rows = np.concatenate([alloc.take(s.sid, tq) for s, _ in items])
+        if alloc.capacity > pool.shape[0]:
             # more slabs: the rows keep their numbers.  (The matrix has to stay ONE allocation -- the kernel takes one base pointer --
             # so the step that outgrows it re-houses the pool, into at least twice the rows: the cost per row stays constant, and
             # no other step copies anything of the size of a history.)
-            grown = torch.empty(max(self._alloc.capacity, 2 * self._post.shape[0]), self._post.shape[1], dtype=torch.float32,
-                                device=self.engine.device)
-            grown[:self._post.shape[0]] = self._post
-            self._post = grown
-        self._post[self._dev_index(rows)] = probs.reshape(-1, probs.shape[2])
+            grown = torch.empty(max(alloc.capacity, 2 * pool.shape[0]), pool.shape[1], dtype=torch.float32, device=self.engine.device)
+            grown[:pool.shape[0]] = pool
+            pool = grown
+        pool[self._dev_index(rows)] = block.reshape(-1, block.shape[2])
+        return pool
 
     def _align(self, sess):
         """ONE masr_ctc_align_rows launch for the sessions ``sess`` (each with a result and at least one frame): their hypotheses,
@@ -621,6 +668,66 @@ class LockStepPool(StreamPool):
         for s in sess:
             if s.result is not None and s.frames == 0:     # only windows too short for a frame so far: the empty transcript
                 s.result['tokens'] = [] if not s.tokens else None
+
+    # ---- rescore_at_end: the encoder rows and the second pass -----------------------------------------------------------------------
+    def encoder_rows(self, handle):
+        """rescore_at_end pool: the rows of the pool's encoder matrix that hold the session's encoder frames, in frame order (int64)"""
+        if not self.rescoring:
+            return super().encoder_rows(handle)
+        return np.asarray(self._enc_alloc.rows_of(self.sessions[handle].sid), np.int64)
+
+    def encoder_output(self, handle):
+        """rescore_at_end pool: the encoder rows of all frames of the session so far, gathered -> [frames, d_model] device tensor"""
+        rows = torch.from_numpy(self.encoder_rows(handle)).to(self.engine.device)
+        return self._enc[rows]
+
+    def last_rescoring(self, handle):
+        """rescore_at_end pool: {'nbest': [token lists], 'ctc': [...], 'att': [...], 'r_att': [...], 'total': [...], 'winner': i} of
+        the session's last rescoring (the first pass's prefixes best first, their CTC log-probabilities, both decoders' scores, the
+        combined scores and the index of the result), or None before the first"""
+        if not self.rescoring:
+            return super().last_rescoring(handle)
+        return self.sessions[handle].rescored
+
+    def _rescore(self, sess):
+        """ONE masr_rescore_rows launch for the sessions ``sess`` that end in this step (each with at least one encoder frame and
+        the n-best of its search in its decoder): their row tables, frame counts and hypotheses go up in one staged copy, att /
+        r_att come back in one, and that one is waited for -> their results become the winner and the combined score"""
+        from masr_amd.decoders.attention_rescoring import build_table, combine, pick
+        eng, st, dec = self.engine, self._stage, self.predictor.rescoring_decoder
+        B = len(sess)
+        nbest = [list(s.decoder.last_nbest_tokens) for s in sess]
+        ctc = [np.array([sc for sc, _ in s.decoder.last_nbest], np.float32) for s in sess]
+        hyps, lens, count = build_table(nbest, eng.max_pos)
+        tables = [self._enc_alloc.rows_of(s.sid) for s in sess]
+        tmax = max(len(t) for t in tables)
+        n32 = B + hyps.size + lens.size                        # n_frames | hyps | hyp_lens behind the int64 row table
+        up, upload = st.take((B * tmax + (n32 + 1) // 2,), np.int64)
+        table = up[:B * tmax].reshape(B, tmax)
+        for b, t in enumerate(tables):
+            table[b, :len(t)] = t
+            table[b, len(t):] = -1
+        small = up[B * tmax:].view(np.int32)
+        small[:B] = [len(t) for t in tables]
+        small[B:B + hyps.size] = hyps.reshape(-1)
+        small[B + hyps.size:n32] = lens.reshape(-1)
+        dev = upload()
+        dsmall = dev[B * tmax:].view(torch.int32)
+        att, r_att = eng.rescore_rows(self._enc, dev[:B * tmax].view(B, tmax), dsmall[:B], dsmall[B:B + hyps.size].view(hyps.shape),
+                                      dsmall[B + hyps.size:n32].view(lens.shape), with_right=dec.reverse_weight > 0)
+        host = st.fetch(torch.stack([att, r_att]))
+        done = torch.cuda.Event()
+        done.record()
+        done.synchronize()
+        for b, s in enumerate(sess):
+            n = int(count[b])
+            a, r = host[0, b, :n].copy(), host[1, b, :n].copy()
+            total = combine(a, r, ctc[b], dec.ctc_weight, dec.reverse_weight)
+            w = pick(total, n)
+            s.rescored = {'nbest': nbest[b], 'ctc': ctc[b].tolist(), 'att': a.tolist(), 'r_att': r.tolist(), 'total': total.tolist(),
+                          'winner': w}
+            s.tokens = list(nbest[b][w])
+            s.result = s.beam_last = {'text': token_text(self.vocab, s.tokens), 'score': float(total[w])}
 
     # ---- one batched step -------------------------------------------------------------------------------------------------
     def _featurize(self, sess):
@@ -698,6 +805,10 @@ class LockStepPool(StreamPool):
         plans = [window_plan(s.nf, fed[s.sid]) for s in sess]
         for s in sess:
             s.result = None
+        if self.rescoring:
+            dec_beam = self.predictor.rescoring_decoder.beam_size
+            n_windows = {s.sid: len(p) for s, p in zip(sess, plans)}
+            read_nbest = set()            # sessions whose last decode_chunk of this step brought the n-best back
         for k in range(max((len(p) for p in plans), default=0)):
             groups = {}
             for s, p in zip(sess, plans):
@@ -714,11 +825,23 @@ class LockStepPool(StreamPool):
                 x = self._feat.view(-1, self.feat_dim)[self._dev_index(base[:, None] + np.arange(length)[None, :])]
                 sids = [s.sid for s, _ in items]
                 if self.beam:
-                    probs, _, _ = eng.encode_chunk(sids, x, want_probs=True)
+                    if self.rescoring:
+                        probs, _, _, enc = eng.encode_chunk(sids, x, want_probs=True, want_enc=True)
+                        self._enc = self._append_rows(self._enc_alloc, self._enc, items, enc)
+                    else:
+                        probs, _, _ = eng.encode_chunk(sids, x, want_probs=True)
                     if self.timestamps:
                         self._keep_posteriors(items, probs)
                     for i, (s, _) in enumerate(items):
-                        if self.nbest is None:
+                        if self.rescoring:
+                            # the last window of an utterance that ends here brings the search's n-best back with its result
+                            last = fed[s.sid] and k == n_windows[s.sid] - 1
+                            score, text = s.decoder.decode_chunk(probs=probs[i:i + 1], logits_lens=[probs.shape[1]],
+                                                                 nbest=dec_beam if last else None)
+                            if last:
+                                read_nbest.add(s.sid)
+                            res = {'text': text, 'score': score}
+                        elif self.nbest is None:
                             score, text = s.decoder.decode_chunk(probs=probs[i:i + 1], logits_lens=[probs.shape[1]])
                             res = {'text': text, 'score': score}
                         else:
@@ -755,8 +878,19 @@ class LockStepPool(StreamPool):
             for j, s in enumerate(adv):
                 s.tokens = tok[j, :ntok[j]].tolist()
                 s.result = greedy_result(self.vocab, s.tokens, score[j])
+        if self.rescoring:
+            # end of utterance: the second pass over all kept frames of every session that ends here and has any (a session that
+            # never produced an encoder frame keeps what the CTC path gave it)
+            ending = [s for s in sess if fed[s.sid] and s.frames > 0]
+            for s in ending:
+                if s.sid not in read_nbest:        # its last feed decoded no window: the live set as it stands
+                    s.decoder.live_nbest(dec_beam)
+            # one launch, or -- masr_rescore_rows takes B * N <= 65535 sequences per call -- one per 65535 // beam_size sessions
+            per = max(1, 65535 // dec_beam)
+            for at in range(0, len(ending), per):
+                self._rescore(ending[at:at + per])
         if self.timestamps:
-            self._stamp([s for s, p in zip(sess, plans) if p])
+            self._stamp([s for s, p in zip(sess, plans) if p or (self.rescoring and fed[s.sid])])
         self._stage.end()
         out = {}
         for s, p in zip(sess, plans):
