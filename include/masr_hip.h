@@ -74,7 +74,19 @@ typedef struct masr_config {
                                 value by name (activation_type), and a non-zero [4] together with [0] = 1 (batch_norm runs with
                                 swish only).  No other model kind reads [4] as an activation (the efficient_conformer's [4] is its
                                 norm selector): those families run swish only.  An activation has no weights: nothing in a checkpoint
-                                can confirm the value */
+                                can confirm the value.
+                                Layer layouts, L = num_blocks (masr_create refuses everything else before any allocation, naming
+                                the YAML key):
+                                  squeezeformer: [0] reduce_idx = -1 (null: no time reduction; [1] is then ignored, as the reference
+                                  ignores it) or a layer in [0, L); with [0] >= 0, [1] recover_idx is a layer in [reduce_idx, L)
+                                  ([1] = [0]: reduction and recovery in front of the same layer).  recover_idx < reduce_idx is
+                                  refused (the reference fails there on an empty stack).  reduce_idx set with recover_idx null
+                                  (-1) or >= L is a legal reference configuration whose output stays at HALF the frame rate: this
+                                  engine REFUSES it, naming recover_idx -- every entry point, masr_encoder_frames and
+                                  masr_frame_reduction included, keeps the Squeezeformer's output at the input frame rate;
+                                  efficient_conformer: [0] stride_layer_idx in [0, L) (one stride-2 layer: the output is always at
+                                  half the rate of the input layer); [1] = number of leading grouped layers (len(group_layer_idx))
+                                  in [0, [0] + 1]: grouped attention behind the stride layer is not implemented */
 } masr_config;
 
 const char* masr_last_error(void);

@@ -264,6 +264,29 @@ int masr_create(const masr_config* cfg, masr_engine** out) {
             return fail(std::string(fam) + ": cnn_module_kernel (masr_config.cnn_kernel) = " + std::to_string(cfg->cnn_kernel) +
                         " is not supported with streaming: False (causal = 0): the symmetric padding needs an odd value in [3, 31]");
     }
+    // layer layouts (the header states the accepted ranges under reserved[5]): the forward passes branch on these indices without
+    // looking at them again, so everything outside is refused here, before anything is allocated
+    if (cfg->model_kind == 1) {
+        const int L = cfg->num_blocks, r = cfg->reserved[0], c = cfg->reserved[1];
+        if (r < -1 || r >= L)
+            return fail("squeezeformer: reduce_idx (masr_config.reserved[0]) = " + std::to_string(r) + " is not supported: -1 (null) or a "
+                        "layer in [0, num_blocks = " + std::to_string(L) + ")");
+        if (r >= 0 && (c < r || c >= L))
+            return fail("squeezeformer: recover_idx (masr_config.reserved[1]) = " + std::to_string(c) + " with reduce_idx = " +
+                        std::to_string(r) + " is not supported: a layer in [reduce_idx, num_blocks = " + std::to_string(L) + "); the "
+                        "reference fails on a recovery in front of the reduction, and with recover_idx null (-1) or >= num_blocks its "
+                        "output stays at half the frame rate, which this engine does not implement");
+    }
+    if (cfg->model_kind == 2) {
+        const int L = cfg->num_blocks, s = cfg->reserved[0], g = cfg->reserved[1];
+        if (s < 0 || s >= L)
+            return fail("efficient_conformer: stride_layer_idx (masr_config.reserved[0]) = " + std::to_string(s) + " is not supported: "
+                        "one stride layer in [0, num_blocks = " + std::to_string(L) + ")");
+        if (g < 0 || g > s + 1)
+            return fail("efficient_conformer: group_layer_idx (masr_config.reserved[1] = its length) = " + std::to_string(g) +
+                        " leading grouped layers with stride_layer_idx = " + std::to_string(s) + " is not supported: 0 to "
+                        "stride_layer_idx + 1 (grouped attention after the stride layer is not implemented)");
+    }
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     if (ndev <= 0) return fail("no HIP device");
@@ -625,7 +648,8 @@ int masr_stream_export_cache(masr_engine* e, int32_t stream_id, float* att_dev, 
         } else if (e->cfg.model_kind == 1) {     // half-rate layers: every kept entry twice, the FIRST t of them (encoder.py:345-351)
             for (int l = 0; l < L; ++l) {
                 const float* base = st->att.as<float>() + (size_t)l * st->cap * 2 * d;
-                if (l >= e->reduce_idx && l < e->recover_idx)
+                // (reduce_idx: null with a recover_idx set: the reference ignores recover_idx, no layer runs at half rate)
+                if (e->reduce_idx >= 0 && l >= e->reduce_idx && l < e->recover_idx)
                     launch_export_att(base, att_dev + (size_t)l * t * 2 * d, 1, H, st->cap, t, d / H, s, 2, 2 * st->first_half);
                 else
                     launch_export_att(base + (size_t)first * 2 * d, att_dev + (size_t)l * t * 2 * d, 1, H, st->cap, t, d / H, s);

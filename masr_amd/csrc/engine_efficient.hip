@@ -109,7 +109,7 @@ int encode_full_efficient(masr_engine* e, hipStream_t s, const float* feats, con
                                               1e-5f, s);
             launch_avgpool2(x, e->xsave.as<float>(), B, Tq, s);
             Tq = T2; mstride *= 2; pstride *= 2; M = B * Tq;
-            if (!causal)     // half rate, kernel 7 from here on: a new padded layout
+            if (!causal && i + 1 < L)     // half rate, kernel 7 from here on: a new padded layout (no layer behind a stride layer that is last)
                 HIPCHK(hipMemsetAsync(e->glu.p, 0, (size_t)B * (Tq + layer_kernel(e, i + 1) - 1) * d * sizeof(float), s));
             resid_gemm(e, s, e->dwo.as<float>(), w.pw2_w, w.pw2_b, e->xsave.as<float>(), M, lens, Tq, mstride);
             launch_attseq_full(seq_r, e->qkv.as<float>(), e->att.as<float>(), lens, B, Tq, mstride, s);
@@ -152,6 +152,7 @@ int encode_chunk_efficient(masr_engine* e, hipStream_t s, std::vector<Stream*>& 
     CHK(e->attseq.ensure(sizeof(AttSeq) * (size_t)n * L));
     float* qp = e->qplanes.as<float>();
     HIPCHK(hipMemsetAsync(qp, 0, 3 * plane * sizeof(float), s));      // time padding rows of the new q / k / v stay zero
+    // (masr_create keeps stride_idx in [0, L): one layer halves the rate, so the step always ends on n * T2 rows)
     auto rate = [&](int l) { return l > e->stride_idx ? 2 : 1; };
     const int padmax = e->cfg.cnn_kernel - 1;
     std::vector<AttSeq> hs((size_t)n * L);

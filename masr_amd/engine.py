@@ -173,6 +173,56 @@ def _validate_cnn_kernel(use_model, enc, state_dict, streaming):
                                  f'cnn_module_kernel={have} ({key} is {list(state_dict[key].shape)})')
 
 
+def _layer_layout(use_model, enc):
+    """The layer positions a checkpoint's YAML sets, checked as masr_create checks them (include/masr_hip.h, ``reserved[5]``) and
+    returned as that call takes them: Squeezeformer ``(reduce_idx, recover_idx)`` with -1 for null, Efficient Conformer
+    ``(stride_layer_idx, len(group_layer_idx))``.  L = ``num_blocks``.
+
+    Squeezeformer: ``reduce_idx`` null or a layer in [0, L); with it set, ``recover_idx`` a layer in [reduce_idx, L).  The reference
+    fails on ``recover_idx < reduce_idx`` (an empty stack) and keeps HALF the frame rate to the end with ``recover_idx`` null or
+    >= L: the engine's output is at the input frame rate everywhere, so those are refused by name rather than run.  With
+    ``reduce_idx`` null the reference ignores ``recover_idx``, and so does this.
+    Efficient Conformer: one stride-2 layer in [0, L) and 0 .. stride_layer_idx + 1 leading grouped layers."""
+    def index(key, v):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise _lib.MasrError(f'{use_model}: encoder_conf.{key}={v!r} is not supported: a layer index (an integer)')
+        return v
+    L = index('num_blocks', enc.get('num_blocks', 12))
+    if use_model == 'squeezeformer':
+        red, rec = enc.get('reduce_idx', 5), enc.get('recover_idx', 11)
+        r = -1 if red is None else index('reduce_idx', red)
+        c = -1 if rec is None else index('recover_idx', rec)
+        if red is not None and not 0 <= r < L:
+            raise _lib.MasrError(f'squeezeformer: encoder_conf.reduce_idx={red!r} is not supported: null or a layer in '
+                                 f'[0, num_blocks = {L})')
+        if red is not None and (rec is None or not r <= c < L):
+            raise _lib.MasrError(f'squeezeformer: encoder_conf.recover_idx={rec!r} with reduce_idx={r} is not supported: a layer in '
+                                 f'[reduce_idx, num_blocks = {L}) (the reference fails on a recovery in front of the reduction; with '
+                                 f'recover_idx null or >= num_blocks its output stays at half the frame rate, which is not implemented)')
+        return r, c
+    eff = dict(enc.get('efficient_conf', {}) or {})
+    stride_idx = eff.get('stride_layer_idx', [3])
+    stride_idx = list(stride_idx) if isinstance(stride_idx, (list, tuple)) else [stride_idx]
+    groups = eff.get('group_layer_idx', [0, 1, 2, 3])
+    groups = list(groups) if isinstance(groups, (list, tuple)) else [groups]
+    stride = eff.get('stride', [2])
+    stride = list(stride) if isinstance(stride, (list, tuple)) else [stride]
+    if len(stride_idx) != 1 or stride != [2]:
+        raise _lib.MasrError(f'efficient_conformer: efficient_conf.stride_layer_idx={stride_idx!r} with stride={stride!r} is not '
+                             f'supported: only one stride-2 layer and leading grouped layers are supported')
+    s = index('stride_layer_idx', stride_idx[0])
+    if not 0 <= s < L:
+        raise _lib.MasrError(f'efficient_conformer: efficient_conf.stride_layer_idx={s} is not supported: one stride layer in '
+                             f'[0, num_blocks = {L})')
+    if groups != list(range(len(groups))):
+        raise _lib.MasrError(f'efficient_conformer: efficient_conf.group_layer_idx={groups!r} is not supported: only one stride-2 '
+                             f'layer and leading grouped layers (0, 1, ..., g - 1) are supported')
+    if len(groups) > s + 1:
+        raise _lib.MasrError(f'efficient_conformer: efficient_conf.group_layer_idx={groups!r} with stride_layer_idx={s} is not '
+                             f'supported: grouped attention after the stride layer is not implemented (at most layers 0 .. {s})')
+    return s, len(groups)
+
+
 def _validate_encoder_conf(use_model, enc, state_dict, streaming=None):
     """The kernels implement exactly the module variants the shipped YAMLs select; anything else must fail here instead of
     loading cleanly into the wrong arithmetic (e.g. ``cnn_module_norm: batch_norm`` has LayerNorm-shaped ``norm.weight``).
@@ -196,6 +246,8 @@ def _validate_encoder_conf(use_model, enc, state_dict, streaming=None):
                 raise _lib.MasrError(f'conformer: encoder_conf.input_layer={enc.get("input_layer")!r} is implemented at output_size '
                                      f'256 only (output_size 512 takes conv2d)')
         _validate_cnn_kernel(use_model, enc, state_dict, streaming)
+    if use_model in ('squeezeformer', 'efficient_conformer'):
+        _layer_layout(use_model, enc)
     if use_model in ('conformer', 'efficient_conformer'):
         # batch_norm (conformer/convolution.py:60-67, eval-mode statistics folded into scale / shift): Conformer in the full-context
         # forward only, Efficient Conformer full-context and chunked.  An absent key means layer_norm here for both families (the
@@ -355,28 +407,18 @@ class HipEngine:
                              cnn_kernel=int(enc.get('cnn_module_kernel', 31)), n_mels=n_mels,
                              vocab_size=int(vocab_size), causal=1 if streaming else 0, max_pos=max_pos,
                              device_id=device)
-            red, rec = enc.get('reduce_idx', 5), enc.get('recover_idx', 11)
-            cfg.reserved[0] = -1 if red is None else int(red)
-            cfg.reserved[1] = -1 if rec is None else int(rec)
+            cfg.reserved[0], cfg.reserved[1] = _layer_layout(use_model, enc)
         elif use_model == 'efficient_conformer':
             # configs/efficient_conformer.yml: the nested efficient_conf is swallowed by **kwargs in the reference
             # (efficient_conformer/encoder.py:54); its constructor defaults equal the shipped YAML values
             eff = dict(enc.get('efficient_conf', {}) or {})
-            stride_idx = eff.get('stride_layer_idx', [3])
-            stride_idx = stride_idx if isinstance(stride_idx, (list, tuple)) else [stride_idx]
-            groups = list(eff.get('group_layer_idx', [0, 1, 2, 3]))
-            stride = eff.get('stride', [2])
-            stride = list(stride) if isinstance(stride, (list, tuple)) else [stride]
-            if len(stride_idx) != 1 or stride != [2] or groups != list(range(len(groups))):
-                raise _lib.MasrError('efficient_conformer: only one stride-2 layer and leading grouped layers are supported')
             cfg = MasrConfig(model_kind=2, d_model=int(enc.get('output_size', 256)),
                              heads=int(enc.get('attention_heads', 4)), d_ff=int(enc.get('linear_units', 2048)),
                              num_blocks=int(enc.get('num_blocks', 12)),
                              cnn_kernel=int(enc.get('cnn_module_kernel', 15)), n_mels=n_mels,
                              vocab_size=int(vocab_size), causal=1 if streaming else 0, max_pos=max_pos,
                              device_id=device)
-            cfg.reserved[0] = int(stride_idx[0])
-            cfg.reserved[1] = len(groups)
+            cfg.reserved[0], cfg.reserved[1] = _layer_layout(use_model, enc)
             cfg.reserved[2] = int(eff.get('group_size', 3))
             cfg.reserved[4] = 1 if enc.get('cnn_module_norm', 'layer_norm') == 'batch_norm' else 0
             cfg.reserved[3] = INPUT_LAYERS[self.input_layer]

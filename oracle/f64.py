@@ -54,9 +54,10 @@ def both_chunks(family, sd, feats, windows, **kw):
 
 
 @torch.no_grad()
-def chunk_run(family, sd, feats, windows, dtype=torch.float32, required_cache_size=-16):
+def chunk_run(family, sd, feats, windows, dtype=torch.float32, required_cache_size=-16, **kw):
     """chunked streaming of one utterance (feats [1, T, n_mels]) over ``windows`` = [(first frame, frames), ...] in ``dtype``
-    -> (probabilities of all chunks concatenated [T', V], att_cache, cnn_cache); DeepSpeech2: (probs, h, c)"""
+    -> (probabilities of all chunks concatenated [T', V], att_cache, cnn_cache); DeepSpeech2: (probs, h, c).  ``kw`` goes to the
+    family's ``get_encoder_out_chunk`` (the layer layout, the kernel size)"""
     sd = cast_state_dict(sd, dtype)
     feats = torch.as_tensor(feats).to(dtype)
     m = module_of(family)
@@ -66,9 +67,9 @@ def chunk_run(family, sd, feats, windows, dtype=torch.float32, required_cache_si
     for cur, n in windows:
         x = feats[:1, cur:cur + n]
         if family == 'deepspeech2':
-            p, _, a, b = m.get_encoder_out_chunk(sd, x, torch.tensor([x.shape[1]]), a, b)
+            p, _, a, b = m.get_encoder_out_chunk(sd, x, torch.tensor([x.shape[1]]), a, b, **kw)
         else:
-            p, a, b = m.get_encoder_out_chunk(sd, x, off, required_cache_size, a, b)
+            p, a, b = m.get_encoder_out_chunk(sd, x, off, required_cache_size, a, b, **kw)
         off += p.shape[1]
         outs.append(p[0])
     return torch.cat(outs), a, b

@@ -134,7 +134,7 @@ def encoder_full(sd, feats, lens, heads=4, kernel=31, reduce_idx=5, recover_idx=
             x, pad_s = _time_reduce(sd, x, pad_s)
             pos_emb = pos_emb[:, ::2, :]
             att = None if att is None else att[:, ::2, ::2]
-        if i == recover_idx:
+        if i == recover_idx and reduce_idx is not None:        # (time_reduce is None without a reduce_idx: recover_idx is ignored, :81-88)
             rx, rpad, rpos, ratt = saved
             y = torch.repeat_interleave(x, repeats=2, dim=1)
             y = F.linear(y, sd['encoder.time_recover_layer.weight'], sd['encoder.time_recover_layer.bias'])
@@ -216,13 +216,14 @@ def get_encoder_out_chunk(sd, feats, offset, required_cache_size, att_cache, cnn
             saved = (x, pos_emb)
             x, _ = _time_reduce(sd, x, torch.ones(1, x.shape[1], dtype=torch.bool))
             pos_emb = pos_emb[:, ::2, :]
-        if i == recover_idx:
+        if i == recover_idx and reduce_idx is not None:
             rx, rpos = saved
             y = torch.repeat_interleave(x, repeats=2, dim=1)
             y = F.linear(y, sd['encoder.time_recover_layer.weight'], sd['encoder.time_recover_layer.bias'])
             x = rx + y[:, :rx.shape[1], :]
             pos_emb = rpos
-        factor = 2 if reduce_idx <= i < recover_idx else 1
+        # calculate_downsampling_factor (:226-238): 2 from reduce_idx on, 1 again from recover_idx on (null: to the last layer)
+        factor = 2 if reduce_idx is not None and reduce_idx <= i and (recover_idx is None or i < recover_idx) else 1
         ac = att_cache[i:i + 1][:, :, ::factor, :][:, :, :pos_emb.shape[1] - x.shape[1], :] if have else None
         p = f'encoder.encoders.{i}'
         a, new_att = _attention_chunk(sd, p + '.self_attn', x, pos_emb, heads, ac)

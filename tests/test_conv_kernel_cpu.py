@@ -25,8 +25,8 @@ def _create(kind, kernel, causal=1):
                           causal=causal, max_pos=5000, device_id=0)
     if kind == 1:
         cfg.reserved[0], cfg.reserved[1] = -1, -1
-    if kind == 2:
-        cfg.reserved[0], cfg.reserved[1], cfg.reserved[2] = 3, 4, 3
+    if kind == 2:                     # (two blocks: the stride layer is the last one and both are grouped, as in the shipped layout)
+        cfg.reserved[0], cfg.reserved[1], cfg.reserved[2] = 1, 2, 3
     h = ctypes.c_void_p()
     rc = _lib.lib().masr_create(ctypes.byref(cfg), ctypes.byref(h))
     msg = _lib.lib().masr_last_error().decode()
