@@ -648,7 +648,8 @@ int masr_op_attention_plain(masr_engine* e, const float* q_dev, const float* k_d
  *                        arrays; returns when the work has finished.
  *   masr_decoder_info    enabled | left blocks | right blocks | bytes of decoder weights on the device | bytes of decoder
  *                        workspace of the ACTIVE lane (0 until its first masr_rescore / masr_attention_decode /
- *                        masr_op_decoder_step; the step workspaces of the search are counted).  Null outputs are skipped. */
+ *                        masr_op_decoder_step / masr_joint_decode / masr_op_ctc_prefix_scores; the step workspaces of the
+ *                        search and the CTC prefix states of the joint search are counted).  Null outputs are skipped. */
 int masr_decoder_enable(masr_engine* e, int32_t attention_heads, int32_t linear_units, int32_t num_blocks, int32_t r_num_blocks);
 int masr_rescore(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const int32_t* hyp_dev,
                  const int32_t* hyp_lens_dev, int32_t N, int32_t Lmax, int32_t with_right, float* att_dev, float* r_att_dev,
@@ -676,7 +677,8 @@ int masr_decoder_info(masr_engine* e, int32_t* enabled, int32_t* num_blocks, int
  *            that add +0 and eos and change no result.
  *   result   per rank n (best first): tokens_dev [B, N, Lcap] = the tokens behind sos up to and excluding the first eos (eos from
  *            there on), lens_dev [B, N] their count, scores_dev [B, N] the summed log-probability.  The best hypothesis is rank
- *            0 (the highest score, an exact tie to the earlier rank).  No CTC score, no length penalty, no right decoder.
+ *            0 (the highest score, an exact tie to the earlier rank).  No CTC score, no length penalty (masr_joint_decode below
+ *            adds both), no right decoder.
  * Self-attention k | v of a position are projected once and kept per layer ([blocks][steps][B * N][2 d]); reordering the beam
  * rewrites a small ancestor table, never the cache.  The encoder k | v projection is one GEMM per layer before the loop.
  *   masr_attention_decode  enc_dev [B, Tp, d_model], enc_lens_dev [B] -> the result above; *steps_host_or_null = steps launched.
@@ -704,6 +706,54 @@ int masr_attention_decode(masr_engine* e, const float* enc_dev, const int32_t* e
 int masr_op_decoder_step(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_host, int32_t B, int32_t Tp,
                          const int32_t* prefix_host, const int32_t* prefix_lens_host, int32_t N, int32_t L, int32_t top_n,
                          int32_t* top_ids_host, float* top_logp_host, float* logp_host_or_null, void* stream);
+/* Joint CTC / attention decoding (`decoder: joint`): the search of masr_attention_decode -- its step launches, k | v cache, tie
+ * rules, step limit, early stop and end poll -- ranked by a key that adds the CTC prefix probability of every hypothesis over the
+ * utterance's valid frames and a length bonus.  Every hypothesis carries A (the sum of its attention log-probabilities), psi (the
+ * log of its CTC prefix probability) and n (its tokens other than eos); its key is
+ *     J = ((1 - ctc_weight) * A + ctc_weight * psi) + length_bonus * n        float32, in that order;
+ * with ctc_weight = 0 the psi term is left out and no CTC launch happens at all.  N = beam_size, M = ctc_candidates.
+ *   step     per live hypothesis g: the top M of its attention log-probabilities (the order and tie rule of the top N above),
+ *            psi(g . c) of those M candidates, J of each; a finished hypothesis offers itself once with its own A, psi, n and
+ *            -inf otherwise.  Per utterance the top N of the N x M keys, of bit-equal keys the SMALLER parent_rank * M +
+ *            candidate_rank first.
+ *   result   per rank: tokens, length, J in scores_dev; A in att_or_null and psi in ctc_or_null [B, N] when given (psi is 0
+ *            with ctc_weight = 0).  Hypotheses still unfinished at the limit are returned as they stand.
+ * The prefix score, over the utterance's frames t = 0 .. T - 1 (T = enc_lens[b]), lp = ln of the CTC posterior, blank = id 0:
+ *   state    r_n[t], r_b[t]: the log-probabilities of the alignments of g over frames 0 .. t that end in a non-blank / a blank.
+ *   empty    r_n = -inf, r_b[t] = sum of lp[0 .. t][blank], psi = 0.
+ *   c        neither blank nor eos; phi[t] = r_b(g)[t] when c equals the last token of g, else logaddexp(r_n(g)[t], r_b(g)[t]).
+ *            r_n'[0] = lp[0][c] when g is empty, else -inf;  r_b'[0] = -inf;  psi' = r_n'[0];  for t >= 1:
+ *            r_n'[t] = logaddexp(r_n'[t - 1], phi[t - 1]) + lp[t][c]
+ *            r_b'[t] = logaddexp(r_n'[t - 1], r_b'[t - 1]) + lp[t][blank]
+ *            psi'    = logaddexp(psi', phi[t - 1] + lp[t][c])
+ *   eos      c = vocab_size - 1 is always read as eos: psi' = logaddexp(r_n(g)[T - 1], r_b(g)[T - 1]).
+ *   blank    -inf.  A prefix longer than the frames can carry comes out as -inf by this arithmetic.
+ * All of it in float32 with logf / expf, sequential over t.  psi of a winner is the value the scorer produced for it as a
+ * candidate: it is carried through the merge, never recomputed.
+ *   masr_joint_decode    enc_dev [B, Tp, d_model], enc_lens_dev [B]; post_dev [B, Tp, vocab_size] the CTC posteriors as
+ *                        masr_ctc_probs leaves them (input_is_log = 0: probabilities, the kernels take the logarithm and read an
+ *                        entry that is not > 0 as -inf; 1: log-probabilities), an argument of its own, so a caller may pass
+ *                        posteriors that did not come from enc_dev; only frames below enc_lens[b] are read.  Stream, lane, end
+ *                        poll and the bit-for-bit independence of an utterance's result from B, its neighbours, Tp and the
+ *                        lane are masr_attention_decode's.  With ctc_weight = 0, length_bonus = 0 and ctc_candidates =
+ *                        beam_size the tokens and scores are masr_attention_decode's bit for bit.  Memory on top of that
+ *                        search: the prefix states, 2 x B x N x 2 x Tp floats in the active lane's decoder workspace.  Refused
+ *                        by name: what masr_attention_decode refuses, ctc_candidates outside beam_size .. min(64, vocab_size),
+ *                        ctc_weight outside [0, 1), a length_bonus that is not finite, ctc_weight > 0 without post_dev.
+ *   masr_op_ctc_prefix_scores  the scorer alone from HOST tables: R rows of (utterance index row_utt_host [R], prefix_host
+ *                        [R, L] with prefix_lens_host [R] in 0 .. L, cand_host [R, M] candidate ids), frames_host [B] in
+ *                        1 .. Tp, every entry validated (prefix ids in 1 .. vocab_size - 2, candidate ids in the vocabulary, M
+ *                        in 1 .. 64).  The prefixes are fed one position at a time through the advance kernel;
+ *                        psi_prefix_host [R] = psi of each prefix, psi_cand_host [R, M] = psi of each prefix extended by each
+ *                        candidate.  Needs no attention decoder.  Returns when the work has finished. */
+int masr_joint_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const float* post_dev,
+                      int32_t input_is_log, int32_t beam_size, int32_t ctc_candidates, float ctc_weight, float length_bonus,
+                      int32_t max_len, int32_t* tokens_dev, int32_t Lcap, int32_t* lens_dev, float* scores_dev, float* att_or_null,
+                      float* ctc_or_null, int32_t* steps_host_or_null, void* stream);
+int masr_op_ctc_prefix_scores(masr_engine* e, const float* post_dev, int32_t input_is_log, const int32_t* frames_host, int32_t B,
+                              int32_t Tp, const int32_t* row_utt_host, const int32_t* prefix_host, const int32_t* prefix_lens_host,
+                              int32_t R, int32_t L, const int32_t* cand_host, int32_t M, float* psi_prefix_host, float* psi_cand_host,
+                              void* stream);
 /* The N best prefixes of the LM-free host-thread search (masr_beam_search_batch's search, same pruned candidates): per utterance
  * tokens_host [B, nbest, max_len], len_host [B, nbest], score_host [B, nbest] = log probability of each prefix, count_host [B] =
  * prefixes returned (<= min(nbest, beam_size)), best first in the search's own order (score, then the smaller last character), so

@@ -12,7 +12,7 @@ LIB_DIR = os.path.join(ROOT, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libmasr_hip.so')
 SOURCES = ['gemm_f32.hip', 'ffn_reduce.hip', 'ffn_pc.hip', 'sqz_layer.hip', 'rowgemm.hip', 'rowgemm_small.hip', 'elementwise.hip', 'wide.hip',
            'attention.hip', 'lstm.hip', 'gru.hip', 'beam_gpu.hip', 'beam_nbest.hip', 'lm_scorer.cpp', 'fbank.hip', 'silero.hip', 'engine.hip', 'pool.hip',
-           'beam_search.cpp', 'stage.cpp', 'resample.cpp', 'resample.hip', 'knobs.cpp', 'decoder.hip', 'decoder_step.hip',
+           'beam_search.cpp', 'stage.cpp', 'resample.cpp', 'resample.hip', 'knobs.cpp', 'decoder.hip', 'decoder_step.hip', 'decoder_joint.hip',
            'engine_attdecoder.hip', 'ctc_align.hip', 'engine_layers.hip', 'engine_conformer.hip', 'engine_efficient.hip',
            'engine_squeezeformer.hip', 'engine_ds2.hip', 'engine_ctc.hip', 'engine_frontend.hip', 'engine_ops.hip']
 # MASR_BUILD_EXPERIMENTS=1: the measured-and-rejected kernels of earlier rounds (A/B material behind masr_debug_set keys 20 / 24 /
@@ -22,12 +22,14 @@ EXPERIMENT_SOURCES = ['gemm_bf16x3.hip', 'ffn_x3.hip', 'ffn_coop.hip', 'ffn_dual
 if EXPERIMENTS:
     SOURCES = SOURCES + EXPERIMENT_SOURCES
 HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'knobs.h'), os.path.join(CSRC, 'ffn_plan.h'), os.path.join(CSRC, 'pool_plan.h'),
-           os.path.join(CSRC, 'lm_scorer.h'), os.path.join(CSRC, 'engine_state.h'), os.path.join(CSRC, 'engine_encoder.h'),
+           os.path.join(CSRC, 'lm_scorer.h'), os.path.join(CSRC, 'engine_state.h'), os.path.join(CSRC, 'engine_encoder.h'), os.path.join(CSRC, 'step_select.h'),
            os.path.join(os.path.dirname(ROOT), 'include', 'masr_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value'] + (['-DMASR_EXPERIMENTS=1'] if EXPERIMENTS else [])
 # resample.hip reproduces the host loop of resample.cpp bit for bit: a multiply and the add behind it must round separately (no
 # fused multiply-add) and float32 denormals must survive (tests/test_gpu_resample.py pins both)
-FILE_FLAGS = {'resample.hip': ['-ffp-contract=off', '-fno-gpu-flush-denormals-to-zero']}
+# decoder_joint.hip states its key and its recursion as separately rounded float32 operations (include/masr_hip.h: "in that
+# order"; tests/ctc_prefix_ref.py and tests/joint_decode_ref.py restate them so): no fused multiply-add there either
+FILE_FLAGS = {'resample.hip': ['-ffp-contract=off', '-fno-gpu-flush-denormals-to-zero'], 'decoder_joint.hip': ['-ffp-contract=off']}
 STAMP = os.path.join(LIB_DIR, '.build_flavour')
 
 

@@ -636,6 +636,50 @@ void launch_step_init(float* score, int* done, int* active, const int* enc_lens,
 void launch_step_result(const int* tok, const float* score, const int* enc_lens, int* tokens_out, int* lens_out, float* scores_out,
                         int S, int N, int Lcap, int Tp, int V, int steps, int max_len, int max_pos, hipStream_t s);
 
+// ---- joint CTC / attention search (decoder_joint.hip; decoder: joint) ----
+// The CTC prefix state of row s: r [S][2][Tp] float32 = r_n | r_b over the frames of its utterance, two such buffers (read `cur`,
+// write `next`).  Row s belongs to utterance row_utt[s] (given: the scorer op) or s / N; blank = id 0, eos = V - 1.
+struct PrefixRows {
+    const float* post;       // [B, Tp, V] posteriors (input_is_log = 0: probabilities, the kernels take the logarithm)
+    const int* enc_lens;     // [B] valid frames (clamped to [0, Tp])
+    const int* row_utt;      // [S] or nullptr
+    const int* done;         // [B] or nullptr: rows of a finished utterance are skipped
+    int S, N, V, Tp, input_is_log;
+};
+// r <- the empty prefix: r_n = -inf, r_b[t] = sum of lp[0 .. t][blank]
+void launch_prefix_init(const PrefixRows& pr, float* r, hipStream_t s);
+// psi_out [S, M] = log CTC prefix probability of row s extended by cand [S, M] (lane m = candidate m); tok [S, Lcap] holds the
+// row's p tokens.  only_pos [S] given: a row writes at p == only_pos[row] alone.  Rows whose last token is eos are skipped.
+void launch_prefix_score(const PrefixRows& pr, const int* cand, int M, const int* tok, int Lcap, int p, const int* only_pos,
+                         const float* r_cur, float* psi_out, hipStream_t s);
+// r_next[s] <- r_cur[parent of s] extended by tok_next[s][p], parent = rank anc_next[s][p] of the row's utterance; a row that ends
+// in eos is left alone.  row_len [S] given (the scorer op): rows with p >= row_len[s] copy their own state.
+void launch_prefix_advance(const PrefixRows& pr, const int* tok_next, const int* anc_next, int Lcap, int p, const int* row_len,
+                           const float* r_cur, float* r_next, hipStream_t s);
+struct JointMerge {          // the joint merge kernel's argument
+    const float* top_v;      // [S, M] attention log-probabilities of the candidates
+    const int* top_i;        // [S, M]
+    const float* psi_cand;   // [S, M] or nullptr (ctc_weight 0)
+    const float *key_cur, *att_cur, *psi_cur;      // [S] J, A, psi
+    float *key_next, *att_next, *psi_next;
+    const int* n_cur;        // [S] tokens other than eos
+    int* n_next;
+    const int* tok_cur;      // [S, Lcap]
+    int* tok_next;
+    const int* anc_cur;      // [S, Lcap]
+    int* anc_next;
+    const int* enc_lens;     // [B]
+    int* done;               // [B] 0 / 1
+    int* active;             // [1] utterances not done
+    int N, M, Lcap, Tp, V, p, max_len, max_pos;
+    float ctc_weight, length_bonus;
+};
+// beam merge of step p + 1 by J = ((1 - ctc_weight) A + ctc_weight psi) + length_bonus n: N of the N x M candidates per utterance,
+// ties to the smaller flat index parent * M + candidate; A, psi, n, tokens and ancestors carried through the parent index
+void launch_joint_merge(const JointMerge& m, int B, hipStream_t s);
+// att [S] = [0, -inf, ...] per utterance, psi = 0, n = 0
+void launch_joint_init(float* att, float* psi, int* n, int S, int N, hipStream_t s);
+
 // ---- features ------------------------------------------------------------------------------
 size_t fbank_gain_scratch_floats(int B);   // size of gain_scratch ([B] gains + partial sums)
 // use_db: 0 = no dB normalisation, 1 = gains computed on the device, 2 = gains supplied in gain_scratch[0 .. B)

@@ -1,5 +1,7 @@
-// libmasr_hip.so -- engine: the attention decoder of the second pass, host side (kernels: decoder.hip, decoder_step.hip).
+// libmasr_hip.so -- engine: the attention decoder of the second pass, host side (kernels: decoder.hip, decoder_step.hip,
+// decoder_joint.hip).
 #include <math.h>
+#include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -527,6 +529,175 @@ int masr_op_decoder_step(masr_engine* e, const float* enc_dev, const int32_t* en
     HIPCHK(hipMemcpyAsync(top_logp_host, top_v, (size_t)S * top_n * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(top_ids_host, top_v + (size_t)S * top_n, (size_t)S * top_n * sizeof(int), hipMemcpyDeviceToHost, st));
     if (full) HIPCHK(hipMemcpyAsync(logp_host_or_null, full, (size_t)S * V * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// decoder: joint -- the search above ranked by the joint key: the step launches with the top M of every row, the CTC prefix
+// scorer over the M candidates, the joint merge, the prefix states of the N winners (kernels: decoder_joint.hip)
+// ------------------------------------------------------------------------------------------------
+int masr_joint_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const float* post_dev,
+                      int32_t input_is_log, int32_t beam_size, int32_t ctc_candidates, float ctc_weight, float length_bonus,
+                      int32_t max_len, int32_t* tokens_dev, int32_t Lcap, int32_t* lens_dev, float* scores_dev, float* att_or_null,
+                      float* ctc_or_null, int32_t* steps_host_or_null, void* stream) {
+    const std::string w("masr_joint_decode");
+    if (!enc_dev || !enc_lens_dev || !tokens_dev || !lens_dev || !scores_dev) return fail(w + ": null argument");
+    if (max_len < 0) return fail(w + ": max_len must be 0 (no limit of its own) or positive");
+    if (!(ctc_weight >= 0.f && ctc_weight < 1.f)) return fail(w + ": ctc_weight = " + std::to_string(ctc_weight) + " is outside [0, 1)");
+    if (!std::isfinite(length_bonus)) return fail(w + ": length_bonus must be finite");
+    if (ctc_weight > 0.f && !post_dev) return fail(w + ": ctc_weight > 0 needs the CTC posteriors (post_dev is null)");
+    if (beam_size >= 1 && beam_size <= 64 && (ctc_candidates < beam_size || ctc_candidates > 64))
+        return fail(w + ": ctc_candidates = " + std::to_string(ctc_candidates) + " is outside beam_size .. 64");
+    CHK(step_shape_check(e, "masr_joint_decode", B, Tp, beam_size, Lcap));
+    const int V = e->cfg.vocab_size, M = ctc_candidates;
+    if (M > V) return fail(w + ": ctc_candidates = " + std::to_string(M) + " exceeds the vocabulary of " + std::to_string(V));
+    ENTER(e);
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard call_guard(e, st);
+    StepPlan pl{};
+    pl.B = B; pl.N = beam_size; pl.S = B * beam_size; pl.Tp = Tp; pl.Lcap = Lcap; pl.max_len = max_len;
+    pl.Lrun = step_run_bound(e, Tp, Lcap, max_len);
+    CHK(step_workspaces(e, pl, M));
+    const bool ctc = ctc_weight > 0.f;
+    const size_t S = (size_t)pl.S, rows = S * 2 * Tp;
+    // att[2] | psi[2] [S], n[2] [S], the candidates' psi [S, M]
+    CHK(e->jt_tab.ensure((6 * S + S * M) * sizeof(float)));
+    float* jt = e->jt_tab.as<float>();
+    float *att[2] = {jt, jt + S}, *psi[2] = {jt + 2 * S, jt + 3 * S}, *psi_cand = jt + 6 * S;
+    int* cnt[2] = {reinterpret_cast<int*>(jt + 4 * S), reinterpret_cast<int*>(jt + 5 * S)};
+    float* r[2] = {nullptr, nullptr};
+    PrefixRows pr{};
+    pr.post = post_dev; pr.enc_lens = enc_lens_dev; pr.row_utt = nullptr; pr.done = pl.done;
+    pr.S = pl.S; pr.N = pl.N; pr.V = V; pr.Tp = Tp; pr.input_is_log = input_is_log ? 1 : 0;
+    if (ctc) {
+        CHK(e->jt_r.ensure(2 * rows * sizeof(float)));
+        r[0] = e->jt_r.as<float>();
+        r[1] = r[0] + rows;
+    }
+    const int poll = step_poll_every();
+    launch_step_init(pl.score[0], pl.done, pl.active, enc_lens_dev, B, pl.N, Tp, Lcap, max_len, e->cfg.max_pos, st);
+    launch_joint_init(att[0], psi[0], cnt[0], pl.S, pl.N, st);
+    if (ctc) launch_prefix_init(pr, r[0], st);
+    step_source_kv(e, st, enc_dev, pl);
+    float* top_v = e->st_top.as<float>();
+    const int* top_i = reinterpret_cast<const int*>(top_v + S * M);
+    int cur = 0, steps = 0;
+    for (int p = 0; p < pl.Lrun; ++p) {
+        CHK(step_forward(e, st, pl, p, pl.tok[cur], pl.anc[cur], enc_lens_dev, M, nullptr, nullptr));
+        if (ctc) launch_prefix_score(pr, top_i, M, pl.tok[cur], Lcap, p, nullptr, r[cur], psi_cand, st);
+        JointMerge m{};
+        m.top_v = top_v; m.top_i = top_i; m.psi_cand = ctc ? psi_cand : nullptr;
+        m.key_cur = pl.score[cur]; m.key_next = pl.score[cur ^ 1];
+        m.att_cur = att[cur]; m.att_next = att[cur ^ 1]; m.psi_cur = psi[cur]; m.psi_next = psi[cur ^ 1];
+        m.n_cur = cnt[cur]; m.n_next = cnt[cur ^ 1];
+        m.tok_cur = pl.tok[cur]; m.tok_next = pl.tok[cur ^ 1]; m.anc_cur = pl.anc[cur]; m.anc_next = pl.anc[cur ^ 1];
+        m.enc_lens = enc_lens_dev; m.done = pl.done; m.active = pl.active;
+        m.N = pl.N; m.M = M; m.Lcap = Lcap; m.Tp = Tp; m.V = V; m.p = p; m.max_len = max_len; m.max_pos = e->cfg.max_pos;
+        m.ctc_weight = ctc_weight; m.length_bonus = length_bonus;
+        launch_joint_merge(m, B, st);
+        if (ctc) launch_prefix_advance(pr, pl.tok[cur ^ 1], pl.anc[cur ^ 1], Lcap, p, nullptr, r[cur], r[cur ^ 1], st);
+        cur ^= 1;
+        steps = p + 1;
+        if (poll > 0 && steps % poll == 0 && steps < pl.Lrun) {
+            int active = 1;
+            HIPCHK(hipMemcpyAsync(&active, pl.active, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (active <= 0) break;
+        }
+    }
+    launch_step_result(pl.tok[cur], pl.score[cur], enc_lens_dev, tokens_dev, lens_dev, scores_dev, pl.S, pl.N, Lcap, Tp, V, steps,
+                       max_len, e->cfg.max_pos, st);
+    if (att_or_null) HIPCHK(hipMemcpyAsync(att_or_null, att[cur], S * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (ctc_or_null) HIPCHK(hipMemcpyAsync(ctc_or_null, psi[cur], S * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LAUNCHCHK();
+    if (steps_host_or_null) *steps_host_or_null = steps;
+    return 0;
+}
+
+int masr_op_ctc_prefix_scores(masr_engine* e, const float* post_dev, int32_t input_is_log, const int32_t* frames_host, int32_t B,
+                              int32_t Tp, const int32_t* row_utt_host, const int32_t* prefix_host, const int32_t* prefix_lens_host,
+                              int32_t R, int32_t L, const int32_t* cand_host, int32_t M, float* psi_prefix_host, float* psi_cand_host,
+                              void* stream) {
+    const std::string w("masr_op_ctc_prefix_scores");
+    if (!post_dev || !frames_host || !row_utt_host || !prefix_host || !prefix_lens_host || !cand_host || !psi_prefix_host ||
+        !psi_cand_host)
+        return fail(w + ": null argument");
+    if (B <= 0 || Tp <= 0) return fail(w + ": B and Tp must be positive");
+    if (R < 1 || R > 65535) return fail(w + ": R = " + std::to_string(R) + " rows is outside 1 .. 65535");
+    if (L < 1) return fail(w + ": L must be at least 1");
+    if (M < 1 || M > 64) return fail(w + ": M = " + std::to_string(M) + " candidates per row is outside 1 .. 64");
+    if (!e || !e->finalized) return fail("engine not finalized");
+    const int V = e->cfg.vocab_size;
+    for (int b = 0; b < B; ++b)
+        if (frames_host[b] < 1 || frames_host[b] > Tp)
+            return fail(w + ": utterance " + std::to_string(b) + " has " + std::to_string(frames_host[b]) + " frames, outside 1 .. Tp");
+    int maxlen = 0;
+    for (int s = 0; s < R; ++s) {
+        if (row_utt_host[s] < 0 || row_utt_host[s] >= B)
+            return fail(w + ": row " + std::to_string(s) + " names utterance " + std::to_string(row_utt_host[s]) + ", outside 0 .. B - 1");
+        if (prefix_lens_host[s] < 0 || prefix_lens_host[s] > L)
+            return fail(w + ": prefix " + std::to_string(s) + " has length " + std::to_string(prefix_lens_host[s]) + ", outside 0 .. L");
+        maxlen = std::max(maxlen, prefix_lens_host[s]);
+        for (int i = 0; i < prefix_lens_host[s]; ++i) {
+            const int t = prefix_host[(size_t)s * L + i];
+            if (t < 1 || t >= V - 1)
+                return fail(w + ": token id " + std::to_string(t) + " of prefix " + std::to_string(s) +
+                            " is outside 1 .. vocabulary - 2 (a prefix holds neither blank nor eos)");
+        }
+        for (int m = 0; m < M; ++m) {
+            const int t = cand_host[(size_t)s * M + m];
+            if (t < 0 || t >= V)
+                return fail(w + ": candidate id " + std::to_string(t) + " of row " + std::to_string(s) + " is outside the vocabulary");
+        }
+    }
+    ENTER(e);
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard call_guard(e, st);
+    // host tables: tok [R, L] | lens [R] | lens - 1 [R] | utt [R] | frames [B] | cand [R, M] | the token of every row at every
+    // position [maxlen, R]; behind them psi of the prefixes [R] and of the candidates [R, M]
+    const size_t nR = (size_t)R;
+    std::vector<int> tab(nR * L + 3 * nR + B + nR * M + (size_t)maxlen * nR, 0);
+    int *h_tok = tab.data(), *h_len = h_tok + nR * L, *h_lm1 = h_len + nR, *h_utt = h_lm1 + nR, *h_fr = h_utt + nR, *h_cand = h_fr + B,
+        *h_at = h_cand + nR * M;
+    for (int s = 0; s < R; ++s) {
+        h_len[s] = prefix_lens_host[s];
+        h_lm1[s] = prefix_lens_host[s] - 1;
+        h_utt[s] = row_utt_host[s];
+        for (int i = 0; i < prefix_lens_host[s]; ++i) {
+            h_tok[(size_t)s * L + i] = prefix_host[(size_t)s * L + i];
+            h_at[(size_t)i * nR + s] = prefix_host[(size_t)s * L + i];
+        }
+    }
+    memcpy(h_fr, frames_host, (size_t)B * sizeof(int));
+    memcpy(h_cand, cand_host, nR * M * sizeof(int));
+    const size_t rows = nR * 2 * Tp;
+    CHK(e->jt_r.ensure(2 * rows * sizeof(float)));
+    CHK(e->jt_tab.ensure((tab.size() + nR + nR * M) * sizeof(int)));
+    int* d = e->jt_tab.as<int>();
+    int *d_tok = d, *d_len = d_tok + nR * L, *d_lm1 = d_len + nR, *d_utt = d_lm1 + nR, *d_fr = d_utt + nR, *d_cand = d_fr + B,
+        *d_at = d_cand + nR * M;
+    float *d_psi = reinterpret_cast<float*>(d + tab.size()), *d_psic = d_psi + nR;
+    // (the call waits for the stream before `tab` goes)
+    HIPCHK(hipMemcpyAsync(d, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_psi, 0, nR * sizeof(float), st));            // psi of the empty prefix
+    float* r[2] = {e->jt_r.as<float>(), e->jt_r.as<float>() + rows};
+    PrefixRows pr{};
+    pr.post = post_dev; pr.enc_lens = d_fr; pr.row_utt = d_utt; pr.done = nullptr;
+    pr.S = R; pr.N = 1; pr.V = V; pr.Tp = Tp; pr.input_is_log = input_is_log ? 1 : 0;
+    launch_prefix_init(pr, r[0], st);
+    int cur = 0;
+    for (int p = 0; p <= maxlen; ++p) {
+        // a row reports the candidates' psi behind its last token, and its own psi as the extension that made it
+        launch_prefix_score(pr, d_cand, M, d_tok, L, p, d_len, r[cur], d_psic, st);
+        if (p == maxlen) break;
+        launch_prefix_score(pr, d_at + (size_t)p * nR, 1, d_tok, L, p, d_lm1, r[cur], d_psi, st);
+        launch_prefix_advance(pr, d_tok, d_tok, L, p, d_len, r[cur], r[cur ^ 1], st);     // (N = 1: every row is its own parent)
+        cur ^= 1;
+    }
+    LAUNCHCHK();
+    HIPCHK(hipMemcpyAsync(psi_prefix_host, d_psi, nR * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(psi_cand_host, d_psic, nR * M * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return 0;
 }

@@ -250,20 +250,24 @@ struct EngineWs {
     // source k | v [blocks][B * Tp][2 d], top-N values | ids, the double-buffered token / ancestor / score tables and flags, and
     // the test op's [S, V] log-probabilities
     DevBuf st_x, st_ln, st_q, st_att, st_hid, st_logits, st_cache, st_src, st_top, st_tab, st_full;
+    // joint CTC / attention search (masr_joint_decode / masr_op_ctc_prefix_scores; allocated on the lane's first such call): the
+    // CTC prefix states r_n | r_b of every hypothesis, double-buffered [2][S][2][Tp], and the double-buffered A / psi / n tables
+    // with the candidates' psi [S, M] (the scorer op keeps its host tables' device copies there)
+    DevBuf jt_r, jt_tab;
     // forced alignment (masr_ctc_align; allocated on the lane's first such call): the predecessor choice of every state and frame,
     // [B][T'][2 Lmax + 1] bytes
     DevBuf align_bp;
     size_t decoder_bytes() const {
         return dec_x.bytes + dec_ln.bytes + dec_qkv.bytes + dec_att.bytes + dec_kv.bytes + dec_hid.bytes + dec_logits.bytes +
                dec_rowlp.bytes + st_x.bytes + st_ln.bytes + st_q.bytes + st_att.bytes + st_hid.bytes + st_logits.bytes + st_cache.bytes +
-               st_src.bytes + st_top.bytes + st_tab.bytes + st_full.bytes;
+               st_src.bytes + st_top.bytes + st_tab.bytes + st_full.bytes + jt_r.bytes + jt_tab.bytes;
     }
     void release_all() {
         for (DevBuf* b : {&gx, &rnn_out, &hstate, &cstate, &ds2_lens, &qplanes, &attp, &cnnptrs, &ffpart, &fb_scratch, &x1, &x2, &x,
                           &ln, &hid, &qkv, &att, &lnpad, &glu, &dwo, &logits, &feats, &enc, &idx, &maxp, &attseq, &gain, &nframes,
                           &lens, &xsave, &xred, &xh, &x3, &sublens, &posoff, &dec_x, &dec_ln, &dec_qkv, &dec_att, &dec_kv, &dec_hid,
                           &dec_logits, &dec_rowlp, &st_x, &st_ln, &st_q, &st_att, &st_hid, &st_logits, &st_cache, &st_src, &st_top,
-                          &st_tab, &st_full, &align_bp})
+                          &st_tab, &st_full, &jt_r, &jt_tab, &align_bp})
             b->release();
         stage.release();
     }

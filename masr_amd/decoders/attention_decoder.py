@@ -13,7 +13,8 @@ passes through the CTC prefix search.
     stop : after min(encoder frames of the utterance, max_len if positive, max_pos - 1) steps, or when all N end in eos
     text : the best hypothesis' tokens behind sos up to its first eos; score: its summed log-probability
 
-Left out: the right-to-left decoder, joint CTC scoring, a length penalty and streaming sessions."""
+Left out: the right-to-left decoder and streaming sessions.  Joint CTC scoring and a length bonus are ``decoder: 'joint'``
+(decoders/joint_decoder.py)."""
 import torch
 
 from masr_amd import _lib

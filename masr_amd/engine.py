@@ -972,6 +972,54 @@ class HipEngine:
                                              _ptr(scores), C.byref(steps), _stream()))
         return tokens, lens, scores, steps.value
 
+    def joint_decode(self, enc, enc_lens, post, beam_size=10, ctc_candidates=None, ctc_weight=0.3, length_bonus=0.0, max_len=0,
+                     lcap=None, input_is_log=False):
+        """masr_joint_decode on the current stream and the active lane: the search of ``attention_decode`` ranked by
+        J = ((1 - ctc_weight) A + ctc_weight psi) + length_bonus n over ``enc`` [B, T', d] / ``enc_lens`` [B] int32 with the CTC
+        posteriors ``post`` [B, T', V] (``ctc_probs`` of the same pass, or any others; ``input_is_log=True``: log-probabilities;
+        None is accepted with ``ctc_weight`` 0) -> (tokens [B, N, Lcap] int32, lens [B, N] int32, J [B, N], A [B, N], psi [B, N]
+        float32) device tensors, best hypothesis first, and the number of steps launched.  ``ctc_candidates`` (default
+        min(2 N, 64, V)): the attention candidates per hypothesis that are CTC-scored.  The host waits only at the end polls."""
+        B, Tp, _ = enc.shape
+        N, max_len = int(beam_size), int(max_len)
+        M = min(2 * N, 64, self.vocab_size) if ctc_candidates is None else int(ctc_candidates)
+        if post is not None and (tuple(post.shape) != (B, Tp, self.vocab_size) or post.dtype != torch.float32 or not post.is_contiguous()):
+            raise ValueError(f'joint_decode: contiguous float32 posteriors [{B}, {Tp}, {self.vocab_size}] expected')
+        if lcap is None:
+            lcap = max(1, min(Tp, self.max_pos - 1, max_len if max_len > 0 else Tp))
+        tokens = torch.empty(B, max(N, 1), max(int(lcap), 1), dtype=torch.int32, device=self.device)
+        lens = torch.empty(B, max(N, 1), dtype=torch.int32, device=self.device)
+        scores, att, psi = (torch.empty(B, max(N, 1), dtype=torch.float32, device=self.device) for _ in range(3))
+        steps = C.c_int32(0)
+        check(self.lib.masr_joint_decode(self.h, _ptr(enc), _ptr(enc_lens), B, Tp, _ptr(post), 1 if input_is_log else 0, N, M,
+                                         float(ctc_weight), float(length_bonus), max_len, _ptr(tokens), int(lcap), _ptr(lens),
+                                         _ptr(scores), _ptr(att), _ptr(psi), C.byref(steps), _stream()))
+        return tokens, lens, scores, att, psi, steps.value
+
+    def ctc_prefix_scores(self, post, frames, row_utt, prefixes, prefix_lens, cands, input_is_log=False):
+        """masr_op_ctc_prefix_scores: the CTC prefix scorer driven alone from HOST tables.  ``post`` [B, T', V] on the device,
+        ``frames`` [B] valid frames, and R rows: ``row_utt`` [R] utterance of the row, ``prefixes`` [R, L] with ``prefix_lens``
+        [R] in 0 .. L (ids in 1 .. V - 2), ``cands`` [R, M] candidate ids -> (psi of every prefix [R], psi of every prefix
+        extended by every candidate [R, M]) numpy float32; returns when the work has finished."""
+        frames = np.ascontiguousarray(frames, np.int32)
+        row_utt = np.ascontiguousarray(row_utt, np.int32)
+        prefixes = np.ascontiguousarray(prefixes, np.int32)
+        prefix_lens = np.ascontiguousarray(prefix_lens, np.int32)
+        cands = np.ascontiguousarray(cands, np.int32)
+        B, Tp, V = post.shape
+        R, L = prefixes.shape
+        M = cands.shape[1]
+        if (V != self.vocab_size or post.dtype != torch.float32 or not post.is_contiguous() or frames.shape != (B,)
+                or row_utt.shape != (R,) or prefix_lens.shape != (R,) or cands.shape != (R, M)):
+            raise ValueError('ctc_prefix_scores: contiguous float32 posteriors [B, T\', vocab_size], frames [B], row_utt / '
+                             'prefix_lens [R], prefixes [R, L] and cands [R, M] expected')
+        psi, psi_c = np.zeros(R, np.float32), np.zeros((R, max(M, 1)), np.float32)
+        as_p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self.lib.masr_op_ctc_prefix_scores(self.h, _ptr(post), 1 if input_is_log else 0, as_p(frames), B, Tp, as_p(row_utt),
+                                                 as_p(prefixes), as_p(prefix_lens), R, L, as_p(cands), M, as_p(psi), as_p(psi_c),
+                                                 _stream()))
+        return psi, psi_c
+
     def op_decoder_step(self, enc, enc_lens, prefixes, prefix_lens, top_n=1, want_logp=True):
         """masr_op_decoder_step: the decode step driven alone from HOST tables, teacher forced.  ``enc`` [B, T', d] on the device,
         ``enc_lens`` [B], ``prefixes`` [B, N, L] tokens behind sos, ``prefix_lens`` [B, N] in 0 .. L -> (top ids [B, N, top_n]

@@ -50,9 +50,9 @@ class InferencePredictor:
         # input feature size of the model = AudioFeaturizer.feature_dim (audio_featurizer.py:141-154)
         pc = configs.get('preprocess_conf', {}) if configs is not None else {}
         n_mels = {'linear': 161, 'mfcc': int(pc.get('n_mfcc', 40))}.get(pc.get('feature_method', 'fbank'), int(pc.get('n_mels', 80)))
-        # decoder: attention_rescoring / attention -- the engine also loads the checkpoint's attention decoder (decoder_conf of the
+        # decoder: attention_rescoring / attention / joint -- the engine also loads the checkpoint's attention decoder (decoder_conf of the
         # YAML); any other decoder: those tensors are never touched
-        rescoring = configs is not None and configs.get('decoder', None) in ('attention_rescoring', 'attention')
+        rescoring = configs is not None and configs.get('decoder', None) in ('attention_rescoring', 'attention', 'joint')
         self.engine = HipEngine(state_dict, encoder_conf=enc_conf, streaming=streaming, n_mels=n_mels,
                                 use_model=use_model, **({'attention_decoder': True,
                                                          'decoder_conf': dict(configs.get('decoder_conf', {}) or {})} if rescoring else {}))

@@ -3,7 +3,7 @@ stream (``begin``), then featurized, encoded and decoded by the configured decod
 
 A pass is always launched deferred: ``launch`` waits for nothing and returns a zero-argument function that waits for the pass
 and returns its results; the non-deferred form is that function called at once.  Every decoder has one route (``_greedy_rows``,
-``_greedy_calls``, ``_beam_search``, ``_rescoring``, ``_attention``): it queues its work behind the encoder and returns a fetch
+``_greedy_calls``, ``_beam_search``, ``_rescoring``, ``_attention``, ``_joint``): it queues its work behind the encoder and returns a fetch
 of [(token ids or text, score)] plus, with timestamps, the function that aligns those hypotheses.  What the routes share --
 the frame counts, the aligner, the score rule, filling the results -- is written once below them.
 
@@ -59,9 +59,9 @@ def first_of_nbest(fetch):
 
 
 class OfflinePasses:
-    def __init__(self, engine, configs, vocab_list, beam=None, rescoring=None, attention=None):
+    def __init__(self, engine, configs, vocab_list, beam=None, rescoring=None, attention=None, joint=None):
         self.eng, self.configs, self.vocab = engine, configs, vocab_list
-        self.beam, self.rescoring, self.attention = beam, rescoring, attention
+        self.beam, self.rescoring, self.attention, self.joint = beam, rescoring, attention, joint
         # Pinned rings; the slot counts are the passes that may be in flight.  Staging: buffers take turns and each carries the
         # event of its last upload, so filling one never waits for the device unless that very buffer's previous copy (two
         # passes ago) is still in flight (a buffer's upload is complete long before the pass that staged it ends).
@@ -247,7 +247,7 @@ class OfflinePasses:
                                                float(n[j]) / rate, self.vocab) for j, ids in enumerate(ids_list)]
 
     def _aligner(self, ps, probs):
-        """for the decoders whose hypotheses reach the host first (beam search, rescoring, attention): the pass keeps its CTC
+        """for the decoders whose hypotheses reach the host first (beam search, rescoring, attention, joint): the pass keeps its CTC
         posteriors ``probs`` on the device; the function returned takes the pass's [(token ids, score)] once they are known, sends
         the ids up in one small copy, aligns them with ONE masr_ctc_align call on the pass's own stream and lane, waits for the one
         copy back and returns the ``'tokens'`` values"""
@@ -326,6 +326,15 @@ class OfflinePasses:
         align = self._aligner(ps, ps.eng.ctc_probs(ps.enc)) if ps.timestamps else None
         return self.attention.decode_pass(ps.eng, ps.enc, enc_lens.contiguous(), want_tokens=ps.want_ids), align
 
+    def _joint(self, ps):
+        """CTC head, then the joint search over this pass's encoder output and those posteriors, queued on the SAME stream and lane
+        (the caller selected them); the aligner reuses the same posteriors; the host waits at the search's end polls and fetches
+        the hypotheses behind an event"""
+        probs = ps.eng.ctc_probs(ps.enc)
+        enc_lens = self._enc_lens(ps)
+        align = self._aligner(ps, probs) if ps.timestamps else None
+        return self.joint.decode_pass(ps.eng, ps.enc, enc_lens.contiguous(), probs, want_tokens=ps.want_ids), align
+
     def _rescoring(self, ps):
         """first pass: CTC head, vocabulary pruning on the GPU, the n-best prefixes of the LM-free prefix search; second pass:
         both attention decoders over this pass's encoder output, queued behind it on the SAME stream and lane (the caller
@@ -393,7 +402,7 @@ class OfflinePasses:
         method = pc.get('feature_method', 'fbank')
         xs, ns, gain = self.prepare_finish(began['prep'], pc.target_dB)
         ps = _Pass(eng, began['ok'], began['n'], began['min_samples'], None, None, decode_all_frames, want_ids, defer, timestamps, nbest)
-        greedy = decoder not in ('ctc_beam_search', 'attention_rescoring', 'attention')
+        greedy = decoder not in ('ctc_beam_search', 'attention_rescoring', 'attention', 'joint')
         if greedy and method == 'fbank' and not timestamps:
             return self._greedy_rows(ps, xs, ns, gain)
         feats, frames = eng.features_batch(method, xs, ns, pc.use_dB_normalization, pc.target_dB, n_mfcc=pc.get('n_mfcc', 40),
@@ -404,7 +413,8 @@ class OfflinePasses:
         ps = ps._replace(enc=enc, nenc=None if decode_all_frames else eng.enc_frames(frames).to(torch.int32))
         if greedy:
             return self._greedy_calls(ps)
-        return {'attention': self._attention, 'attention_rescoring': self._rescoring, 'ctc_beam_search': self._beam_search}[decoder](ps)
+        return {'attention': self._attention, 'joint': self._joint, 'attention_rescoring': self._rescoring,
+                'ctc_beam_search': self._beam_search}[decoder](ps)
 
     def launch(self, began, decode_all_frames=False, as_tokens=False, defer=False, timestamps=False, nbest=None):
         """the pass ``began`` (``begin``) on the current stream and the active lane -> a zero-argument function that waits for it

@@ -86,6 +86,16 @@ class MASRPredictor:
                 raise Exception(DS2_REFUSAL)
             aconf = validate_attention_conf(self.configs.get('attention_decoder_conf', None), len(self._text_featurizer.vocab_list))
             self.attention_decoder = AttentionDecoder(vocab_list=self._text_featurizer.vocab_list, **aconf)
+        self.joint_decoder = None
+        if self.configs.decoder == 'joint':
+            # the attention search ranked jointly with the CTC prefix score, on the GPU (decoders/joint_decoder.py); the
+            # configuration is checked before anything is loaded
+            from masr_amd.decoders.joint_decoder import JointDecoder, DS2_REFUSAL, validate_joint_conf
+            if self.configs.use_model == 'deepspeech2':
+                raise Exception(DS2_REFUSAL)
+            jconf = validate_joint_conf(self.configs.get('joint_decoder_conf', None), self.configs.get('model_conf', None),
+                                        len(self._text_featurizer.vocab_list))
+            self.joint_decoder = JointDecoder(vocab_list=self._text_featurizer.vocab_list, **jconf)
         if state_dict is None and not os.path.exists(model_path):
             raise Exception("模型文件不存在，请检查{}是否存在！".format(model_path))
         self.predictor = InferencePredictor(configs=self.configs, use_model=self.configs.use_model,
@@ -93,7 +103,8 @@ class MASRPredictor:
                                             use_gpu=self.use_gpu, state_dict=state_dict)
         self._audio_featurizer.bind(self.predictor.engine)
         self._passes = OfflinePasses(self.predictor.engine, self.configs, self._text_featurizer.vocab_list,
-                                     beam=self.beam_search_decoder, rescoring=self.rescoring_decoder, attention=self.attention_decoder)
+                                     beam=self.beam_search_decoder, rescoring=self.rescoring_decoder, attention=self.attention_decoder,
+                                     joint=self.joint_decoder)
         self._deferred_turn, self._lane1_ordered = 0, False
         # warm-up like the reference (predict.py:89-92)
         warmup_audio = np.random.uniform(low=-2.0, high=2.0, size=(134240,))
@@ -108,6 +119,9 @@ class MASRPredictor:
                             "use predict / predict_batch")
         if self.configs.decoder == 'attention':
             from masr_amd.decoders.attention_decoder import DECODE_REFUSAL
+            raise Exception(DECODE_REFUSAL)
+        if self.configs.decoder == 'joint':
+            from masr_amd.decoders.joint_decoder import DECODE_REFUSAL
             raise Exception(DECODE_REFUSAL)
         if self.configs.decoder == 'ctc_beam_search':
             score, text = self.beam_search_decoder.decode_beam_search_offline(probs_split=output_data)
@@ -142,6 +156,9 @@ class MASRPredictor:
         if nbest is None:
             return None
         decoder = self.configs.decoder
+        if decoder == 'joint':
+            from masr_amd.decoders.joint_decoder import NBEST_REFUSAL
+            raise ValueError(NBEST_REFUSAL.format(nbest=nbest))
         if decoder in ('attention_rescoring', 'attention'):
             raise ValueError(f"nbest={nbest!r} with decoder={decoder!r}: nbest returns the prefixes of the CTC prefix beam search "
                              f"(decoder='ctc_beam_search'); the n-best of {decoder} -- its rescored or autoregressive hypotheses -- "
@@ -459,6 +476,9 @@ class MASRPredictor:
                 raise Exception(STREAM_REFUSAL)
         if self.configs.decoder == 'attention':
             from masr_amd.decoders.attention_decoder import STREAM_REFUSAL
+            raise Exception(STREAM_REFUSAL)
+        if self.configs.decoder == 'joint':
+            from masr_amd.decoders.joint_decoder import STREAM_REFUSAL
             raise Exception(STREAM_REFUSAL)
         self._stream_pool_for(bool(timestamps), nbest)
         self._pool.feed(self._session, audio_data, is_end, channels=channels, samp_width=samp_width, sample_rate=sample_rate)

@@ -170,6 +170,9 @@ class StreamPool:
         if cfg.decoder == 'attention':
             from masr_amd.decoders.attention_decoder import STREAM_REFUSAL
             raise Exception(STREAM_REFUSAL)
+        if cfg.decoder == 'joint':
+            from masr_amd.decoders.joint_decoder import STREAM_REFUSAL
+            raise Exception(STREAM_REFUSAL)
         if cfg.decoder not in ('ctc_greedy', 'ctc_beam_search', 'attention_rescoring'):
             raise Exception(f'unknown decoder {cfg.decoder}')
         # nbest=N (ctc_beam_search sessions): every result gains 'nbest': [{'text', 'score'}], read from the session's

@@ -1,14 +1,15 @@
 """Times one pass of ``decoder: attention`` (masr_attention_decode) beside the encoder pass it follows.
 
-    python tools/attention_decode_bench.py [--batch 32] [--seconds 10] [--beam 10] [--runs 5] [--vocab 4233] [--max-len 0] [--torch]
+    python tools/attention_decode_bench.py [--batch 32] [--seconds 10] [--beam 10] [--runs 5] [--vocab 4233] [--max-len 0] [--torch] [--joint]
 
 Synthetic Conformer checkpoint with the shipped decoder (3 + 3 blocks, 4 heads, linear_units 1024; only the left half is used),
 ``batch`` utterances of ``seconds`` s, beam ``beam``.  Per run, alternating: the encoder pass (masr_encode_full) and the search,
 each timed with events on the stream; prints medians, min / max, the steps run and the run count as one JSON line.  Synthetic
 checkpoints rarely emit eos, so the search runs to its limit (the utterance's encoder frames): the figure is the worst case of
 that length.  ``--torch``: the same search in plain torch on the device beside it (batched over the hypotheses, the whole prefix
-recomputed every step as the reference's forward_one_step does without a cache; ties as torch.topk leaves them).  The per-kernel
-split comes from a kernel trace of this script."""
+recomputed every step as the reference's forward_one_step does without a cache; ties as torch.topk leaves them).  ``--joint``: one
+pass of ``decoder: joint`` beside it on the same encoder output (the CTC head + masr_joint_decode, ``--ctc-weight`` 0.3,
+``--candidates`` 20).  The per-kernel split comes from a kernel trace of this script."""
 import argparse
 import json
 import math
@@ -79,6 +80,9 @@ def main():
     ap.add_argument('--vocab', type=int, default=4233)
     ap.add_argument('--max-len', type=int, default=0)
     ap.add_argument('--torch', action='store_true')
+    ap.add_argument('--joint', action='store_true')
+    ap.add_argument('--ctc-weight', type=float, default=0.3)
+    ap.add_argument('--candidates', type=int, default=20)
     a = ap.parse_args()
     from masr_amd.engine import HipEngine, positional_table
     from masr_amd.utils import synthetic
@@ -98,19 +102,23 @@ def main():
         t1.record()
         t1.synchronize()
         return t0.elapsed_time(t1), out
-    t_enc, t_dec, t_torch, steps = [], [], [], 0
+    t_enc, t_dec, t_torch, t_joint, steps = [], [], [], [], 0
     dsd = {k: v.to(eng.device) for k, v in sd.items() if k.startswith('decoder.left_decoder.')} if a.torch else None
     pe = positional_table(int(enc_lens.max()) + 2, 256).to(eng.device) if a.torch else None
     for k in range(a.runs + 2):
         te, enc = timed(lambda: eng.encode_full(feats, frames, -1))
         td, out = timed(lambda: eng.attention_decode(enc, enc_lens, a.beam, a.max_len))
         steps = out[3]
+        if a.joint:
+            tj, _ = timed(lambda: eng.joint_decode(enc, enc_lens, eng.ctc_probs(enc), a.beam, a.candidates, a.ctc_weight, 0.0, a.max_len))
         if a.torch:
             with torch.no_grad():
                 tt, _ = timed(lambda: torch_search(dsd, enc, enc_lens, a.beam, pe, 4, a.max_len))
         if k >= 2:                       # two warm-up rounds (workspaces, clocks)
             t_enc.append(te)
             t_dec.append(td)
+            if a.joint:
+                t_joint.append(tj)
             if a.torch:
                 t_torch.append(tt)
     stat = lambda v: {'median_ms': float(np.median(v)), 'min_ms': float(min(v)), 'max_ms': float(max(v))}
@@ -119,6 +127,8 @@ def main():
     res['ms_per_step'] = res['attention_decode_pass']['median_ms'] / max(steps, 1)
     if a.torch:
         res['torch_search'] = stat(t_torch)
+    if a.joint:
+        res['joint_decode_pass'] = dict(stat(t_joint), ctc_weight=a.ctc_weight, candidates=a.candidates)
     print(json.dumps(res))
     eng.close()
 
