@@ -648,8 +648,9 @@ int masr_op_attention_plain(masr_engine* e, const float* q_dev, const float* k_d
  *                        arrays; returns when the work has finished.
  *   masr_decoder_info    enabled | left blocks | right blocks | bytes of decoder weights on the device | bytes of decoder
  *                        workspace of the ACTIVE lane (0 until its first masr_rescore / masr_attention_decode /
- *                        masr_op_decoder_step / masr_joint_decode / masr_op_ctc_prefix_scores; the step workspaces of the
- *                        search and the CTC prefix states of the joint search are counted).  Null outputs are skipped. */
+ *                        masr_op_decoder_step / masr_joint_decode(_lm) / masr_op_ctc_prefix_scores / masr_op_lm_scores; the step
+ *                        workspaces of the search, the CTC prefix states and the LM candidate scores of the joint search are
+ *                        counted).  Null outputs are skipped. */
 int masr_decoder_enable(masr_engine* e, int32_t attention_heads, int32_t linear_units, int32_t num_blocks, int32_t r_num_blocks);
 int masr_rescore(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const int32_t* hyp_dev,
                  const int32_t* hyp_lens_dev, int32_t N, int32_t Lmax, int32_t with_right, float* att_dev, float* r_att_dev,
@@ -745,7 +746,39 @@ int masr_op_decoder_step(masr_engine* e, const float* enc_dev, const int32_t* en
  *                        1 .. Tp, every entry validated (prefix ids in 1 .. vocab_size - 2, candidate ids in the vocabulary, M
  *                        in 1 .. 64).  The prefixes are fed one position at a time through the advance kernel;
  *                        psi_prefix_host [R] = psi of each prefix, psi_cand_host [R, M] = psi of each prefix extended by each
- *                        candidate.  Needs no attention decoder.  Returns when the work has finished. */
+ *                        candidate.  Needs no attention decoder.  Returns when the work has finished.
+ * Shallow fusion with an n-gram language model (masr_lm above; `joint_decoder_conf.language_model_path` / `lm_weight`): every
+ * hypothesis carries a fourth part beside A, psi and n,
+ *     Lm(g . c) = Lm(g) + lm(g, c)        float32, the sum added in that order; Lm of the empty hypothesis is 0,
+ * and the key is
+ *     J = ((((1 - ctc_weight) * A + ctc_weight * psi) + lm_weight * Lm) + length_bonus * n)        float32, in that order.
+ *   lm(g, c) EXACTLY what masr_lm_cond_log_prob returns for the tokens of g (behind sos) followed by c: the <s>-padded window of
+ *            the last max_order - 1 tokens (the empty hypothesis: <s> alone), natural logarithm, the ARPA backoff recursion,
+ *            and -1000 (the scorer's OOV score, as it is) for a candidate or a context word the model does not know -- the same
+ *            float32 additions in the same order, so the device's value is the host's bit for bit.  Candidate vocab_size - 1
+ *            (eos) is scored as the model's </s>; every other token id is its own LM word id, as in the CTC beam search (blank
+ *            and the other tokens that are no single character are unknown words).
+ *   step     the M candidates of a hypothesis stay its top ctc_candidates by ATTENTION log-probability: the model is a partial
+ *            scorer over the same M, like the CTC scorer.  A finished hypothesis offers itself once with its own J, A, psi, Lm,
+ *            n.  Tie rules, step limit, early stop and end poll are unchanged.  Lm of a winner is the sum that ranked it as a
+ *            candidate: carried through the merge, never recomputed.
+ *   lm_weight = 0  the Lm term is left out and no LM kernel is launched, whether or not a model was passed: tokens and every
+ *            score are masr_joint_decode's bit for bit (Lm comes back 0).  A model that is passed is still validated then: a
+ *            word-based one or one of another vocabulary size is refused at lm_weight = 0 too.  With ctc_weight = 0 and
+ *            lm_weight > 0 the call is attention + LM, still with no CTC launch and no use for post_dev.
+ *   masr_joint_decode_lm  masr_joint_decode (which is this call with no model) with lm_or_null / lm_weight and lm_or_null_out
+ *                        [B, N] = Lm per rank when given.  The model's table is uploaded to the engine's device on its first
+ *                        use there, before the first launch of the call, and the host waits for that upload once.  One more
+ *                        launch per step (one wave per hypothesis, lane m = candidate m) between the step's top M and the
+ *                        merge; memory on top of masr_joint_decode: B x N x M floats.  Refused by name: everything
+ *                        masr_joint_decode refuses, an lm_weight that is not finite or is negative, lm_weight > 0 without a
+ *                        model, a word-based model (its words are spelt out of several tokens: host-thread CTC search only), a
+ *                        model loaded for a vocabulary of another size than the engine's.
+ *   masr_op_lm_scores    the LM score kernel alone from HOST tables: R rows (1 .. 65535) of prefix_host [R, L] with
+ *                        prefix_lens_host [R] in 0 .. L and cand_host [R, M] (M in 1 .. 64), every entry validated (prefix and
+ *                        candidate ids in [0, vocab_size); a candidate vocab_size - 1 is read as </s>, a prefix token
+ *                        vocab_size - 1 as its own -- unknown -- word) -> out_host [R, M] = lm(prefix, candidate).  Needs no
+ *                        attention decoder.  Returns when the work has finished. */
 int masr_joint_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const float* post_dev,
                       int32_t input_is_log, int32_t beam_size, int32_t ctc_candidates, float ctc_weight, float length_bonus,
                       int32_t max_len, int32_t* tokens_dev, int32_t Lcap, int32_t* lens_dev, float* scores_dev, float* att_or_null,
@@ -754,6 +787,13 @@ int masr_op_ctc_prefix_scores(masr_engine* e, const float* post_dev, int32_t inp
                               int32_t Tp, const int32_t* row_utt_host, const int32_t* prefix_host, const int32_t* prefix_lens_host,
                               int32_t R, int32_t L, const int32_t* cand_host, int32_t M, float* psi_prefix_host, float* psi_cand_host,
                               void* stream);
+int masr_joint_decode_lm(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const float* post_dev,
+                         int32_t input_is_log, int32_t beam_size, int32_t ctc_candidates, float ctc_weight, float length_bonus,
+                         masr_lm* lm_or_null, float lm_weight, int32_t max_len, int32_t* tokens_dev, int32_t Lcap, int32_t* lens_dev,
+                         float* scores_dev, float* att_or_null, float* ctc_or_null, float* lm_or_null_out, int32_t* steps_host_or_null,
+                         void* stream);
+int masr_op_lm_scores(masr_engine* e, masr_lm* lm, const int32_t* prefix_host, const int32_t* prefix_lens_host, const int32_t* cand_host,
+                      int32_t R, int32_t L, int32_t M, float* out_host, void* stream);
 /* The N best prefixes of the LM-free host-thread search (masr_beam_search_batch's search, same pruned candidates): per utterance
  * tokens_host [B, nbest, max_len], len_host [B, nbest], score_host [B, nbest] = log probability of each prefix, count_host [B] =
  * prefixes returned (<= min(nbest, beam_size)), best first in the search's own order (score, then the smaller last character), so

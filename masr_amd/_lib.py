@@ -130,6 +130,8 @@ SIGNATURES = {
     'masr_op_decoder_step': [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     'masr_joint_decode': [_P, _P, _P, _I, _I, _P, _I, _I, _I, _F, _F, _I, _P, _I, _P, _P, _P, _P, C.POINTER(_I), _P],
     'masr_op_ctc_prefix_scores': [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P],
+    'masr_joint_decode_lm': [_P, _P, _P, _I, _I, _P, _I, _I, _I, _F, _F, _P, _F, _I, _P, _I, _P, _P, _P, _P, _P, C.POINTER(_I), _P],
+    'masr_op_lm_scores': [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
     'masr_beam_search_batch_nbest': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
     'masr_beam_nbest_gpu': [_P, _I, _I, _I, _P, _F, _F, _P, _I, _P, _P, _P, _P],
     'masr_gbeam_nbest': [_P, _I, _I, _P, _I, _P, _P, _P, _P],

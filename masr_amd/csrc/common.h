@@ -660,8 +660,9 @@ struct JointMerge {          // the joint merge kernel's argument
     const float* top_v;      // [S, M] attention log-probabilities of the candidates
     const int* top_i;        // [S, M]
     const float* psi_cand;   // [S, M] or nullptr (ctc_weight 0)
-    const float *key_cur, *att_cur, *psi_cur;      // [S] J, A, psi
-    float *key_next, *att_next, *psi_next;
+    const float* lm_cand;    // [S, M] or nullptr (lm_weight 0): lm(g, c) of the candidates
+    const float *key_cur, *att_cur, *psi_cur, *lm_cur;      // [S] J, A, psi, Lm
+    float *key_next, *att_next, *psi_next, *lm_next;
     const int* n_cur;        // [S] tokens other than eos
     int* n_next;
     const int* tok_cur;      // [S, Lcap]
@@ -672,13 +673,20 @@ struct JointMerge {          // the joint merge kernel's argument
     int* done;               // [B] 0 / 1
     int* active;             // [1] utterances not done
     int N, M, Lcap, Tp, V, p, max_len, max_pos;
-    float ctc_weight, length_bonus;
+    float ctc_weight, lm_weight, length_bonus;
 };
-// beam merge of step p + 1 by J = ((1 - ctc_weight) A + ctc_weight psi) + length_bonus n: N of the N x M candidates per utterance,
-// ties to the smaller flat index parent * M + candidate; A, psi, n, tokens and ancestors carried through the parent index
+// beam merge of step p + 1 by J = (((1 - ctc_weight) A + ctc_weight psi) + lm_weight Lm) + length_bonus n (the psi / Lm term left
+// out where its candidate table is null): N of the N x M candidates per utterance, ties to the smaller flat index parent * M +
+// candidate; A, psi, Lm, n, tokens and ancestors carried through the parent index
 void launch_joint_merge(const JointMerge& m, int B, hipStream_t s);
-// att [S] = [0, -inf, ...] per utterance, psi = 0, n = 0
-void launch_joint_init(float* att, float* psi, int* n, int S, int N, hipStream_t s);
+// att [S] = [0, -inf, ...] per utterance, psi = 0, Lm = 0, n = 0
+void launch_joint_init(float* att, float* psi, float* lm, int* n, int S, int N, hipStream_t s);
+// lm_out [S, M] = ln P(cand [S, M] | the row's tokens) of the n-gram model `lm` (a device view), bit-equal to
+// masr_lm_cond_log_prob; one wave per row, lane m = candidate m.  tok [S, Lcap] holds p tokens per row, or row_len [S] of them
+// when that is given (the op; no row counts as finished then).  done [B] or nullptr: rows s / N of a finished utterance are
+// skipped, and so are rows whose last token is eos.  Returns non-zero for a model order outside 1 .. 5.
+int launch_joint_lm_score(const LmView& lm, const int* cand, int M, const int* tok, int Lcap, int p, const int* row_len,
+                          const int* done, int S, int N, int V, float* lm_out, hipStream_t s);
 
 // ---- features ------------------------------------------------------------------------------
 size_t fbank_gain_scratch_floats(int B);   // size of gain_scratch ([B] gains + partial sums)

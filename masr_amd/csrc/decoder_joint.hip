@@ -18,6 +18,14 @@
 // the chain that consumes it.  The advance kernel runs one wave per winner: the lanes fetch 64 frames at a time (the next 64 while
 // the chain of the current ones runs), lane 0 runs the chain out of LDS, the lanes store the 64 results.  The merge kernel is the
 // merge of decoder_step.hip over N x M keys.
+//
+// Shallow fusion with the n-gram language model (masr_joint_decode_lm / masr_op_lm_scores): every hypothesis also carries Lm, the
+// float32 running sum of lm(g, c) = ln P(c | the last max_order - 1 tokens of g, <s>-padded) -- masr_lm_cond_log_prob's value bit
+// for bit (lm_scorer.h) -- and the key becomes J = (((1 - ctc_weight) A + ctc_weight psi) + lm_weight Lm) + length_bonus n.  The LM
+// score kernel has the mapping of the prefix score kernel: one wave per hypothesis, lane m = candidate m.  The scorer state of the
+// row (its packed context, matched suffix length and backoffs) is the same for every lane -- the lanes read the same table slots,
+// one transaction per probe -- and the candidates' own n-grams are one divergent 16-byte probe per lane and order, longest n-gram
+// first (lm_cond_desc: the kernel is bound by the number of such probes, so no more are issued than the recursion needs).
 #include "common.h"
 #include "step_select.h"
 
@@ -216,8 +224,45 @@ __global__ __launch_bounds__(64) void ctc_prefix_advance_kernel(AdvanceArgs a) {
     }
 }
 
+// lm_out [S, M] = lm(row s, candidate m): the row's scorer state from the last max_order - 1 of its tokens (tok [S, Lcap]; row_len
+// [S] given: the op's prefix lengths, else every row holds p tokens), the candidate scored behind it.  eos = V - 1 is read as the
+// model's </s>, every other id is its own LM word; an unknown candidate or context word gives LM_OOV_SCORE.  Rows of a finished
+// utterance and (in the search) rows whose last token is eos are skipped.
+struct LmScoreArgs {
+    LmView lm;
+    const int* cand;         // [S, M]
+    const int* tok;          // [S, Lcap]
+    const int* row_len;      // [S] or nullptr
+    const int* done;         // [B] or nullptr
+    float* lm_out;           // [S, M]
+    int N, M, Lcap, p, V;
+};
+
+template <int ORD>
+__global__ __launch_bounds__(64) void joint_lm_score_kernel(LmScoreArgs a) {
+    const int s = blockIdx.x, lane = threadIdx.x, eos = a.V - 1;
+    if (a.done && a.done[s / a.N]) return;
+    const int* __restrict__ row = a.tok + (size_t)s * a.Lcap;
+    const int len = a.row_len ? clampi(a.row_len[s], 0, a.Lcap) : a.p;
+    if (!a.row_len && len > 0 && row[len - 1] == eos) return;        // a finished hypothesis offers itself: nothing to score
+    // the <s>-padded window of masr_lm_cond_log_prob; one address per token for the whole wave
+    unsigned long long ctx = lm_root_ctx(a.lm);
+    for (int j = len - min(len, a.lm.max_order - 1); j < len; ++j) ctx = lm_push(ctx, __builtin_amdgcn_readfirstlane(row[j]));
+    const LmState st = lm_state_of(a.lm, ctx);
+    if (lane >= a.M) return;
+    const int c = clampi(a.cand[(size_t)s * a.M + lane], 0, a.V - 1);
+    const int w = c == eos ? a.lm.eos : c;
+    float v = LM_OOV_SCORE;
+    if (!st.oov && w < a.lm.n_words && a.lm.known[w]) {
+        float uni = LM_OOV_SCORE, ubo = 0.f;
+        lm_find(a.lm, lm_key(0ull, 0, w), &uni, &ubo);       // (a known word has its unigram)
+        v = lm_cond_desc<ORD>(a.lm, st, w, uni);
+    }
+    a.lm_out[(size_t)s * a.M + lane] = v;
+}
+
 // Beam merge of step i = p + 1 by the joint key, one workgroup of 256 per utterance (step_merge_kernel over N x M candidates): a
-// finished row offers itself once with its own J, A, psi, n and -inf otherwise; the N best keys, ties to the smaller flat index
+// finished row offers itself once with its own J, A, psi, Lm, n and -inf otherwise; the N best keys, ties to the smaller flat index
 // parent * M + candidate; everything a hypothesis carries written to the `next` tables through the parent index.
 __global__ __launch_bounds__(256) void joint_merge_kernel(JointMerge a) {
     __shared__ float cand[64 * 64];
@@ -243,6 +288,8 @@ __global__ __launch_bounds__(256) void joint_merge_kernel(JointMerge a) {
                 const float n = (float)(a.n_cur[s0 + h] + (t != eos ? 1 : 0));
                 float mix = __fmul_rn(wa, att);
                 if (a.psi_cand) mix = __fadd_rn(mix, __fmul_rn(a.ctc_weight, a.psi_cand[(s0 + h) * M + k]));
+                if (a.lm_cand)
+                    mix = __fadd_rn(mix, __fmul_rn(a.lm_weight, __fadd_rn(a.lm_cur[s0 + h], a.lm_cand[(s0 + h) * M + k])));
                 key = __fadd_rn(mix, __fmul_rn(a.length_bonus, n));
             }
             cand[c] = key;
@@ -276,6 +323,7 @@ __global__ __launch_bounds__(256) void joint_merge_kernel(JointMerge a) {
                 a.key_next[s0 + k] = bv;
                 a.att_next[s0 + k] = fin ? a.att_cur[s0 + h] : __fadd_rn(a.att_cur[s0 + h], a.top_v[(s0 + h) * M + kk]);
                 a.psi_next[s0 + k] = fin ? a.psi_cur[s0 + h] : (a.psi_cand ? a.psi_cand[(s0 + h) * M + kk] : 0.f);
+                a.lm_next[s0 + k] = (fin || !a.lm_cand) ? a.lm_cur[s0 + h] : __fadd_rn(a.lm_cur[s0 + h], a.lm_cand[(s0 + h) * M + kk]);
                 a.n_next[s0 + k] = a.n_cur[s0 + h] + ((!fin && t != eos) ? 1 : 0);
                 if (t == eos) nfin += 1;
             }
@@ -288,6 +336,7 @@ __global__ __launch_bounds__(256) void joint_merge_kernel(JointMerge a) {
             a.key_next[s0 + k] = a.key_cur[s0 + k];
             a.att_next[s0 + k] = a.att_cur[s0 + k];
             a.psi_next[s0 + k] = a.psi_cur[s0 + k];
+            a.lm_next[s0 + k] = a.lm_cur[s0 + k];
             a.n_next[s0 + k] = a.n_cur[s0 + k];
         }
     }
@@ -310,11 +359,12 @@ __global__ __launch_bounds__(256) void joint_merge_kernel(JointMerge a) {
     }
 }
 
-__global__ void joint_init_kernel(float* att, float* psi, int* n, int S, int N) {
+__global__ void joint_init_kernel(float* att, float* psi, float* lm, int* n, int S, int N) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= S) return;
     att[i] = (i % N == 0) ? 0.f : -INFINITY;
     psi[i] = 0.f;
+    lm[i] = 0.f;
     n[i] = 0;
 }
 
@@ -347,8 +397,20 @@ void launch_joint_merge(const JointMerge& m, int B, hipStream_t s) {
     hipLaunchKernelGGL(joint_merge_kernel, dim3((unsigned)B), dim3(256), 0, s, m);
 }
 
-void launch_joint_init(float* att, float* psi, int* n, int S, int N, hipStream_t s) {
-    hipLaunchKernelGGL(joint_init_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, att, psi, n, S, N);
+void launch_joint_init(float* att, float* psi, float* lm, int* n, int S, int N, hipStream_t s) {
+    hipLaunchKernelGGL(joint_init_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, att, psi, lm, n, S, N);
+}
+
+int launch_joint_lm_score(const LmView& lm, const int* cand, int M, const int* tok, int Lcap, int p, const int* row_len,
+                          const int* done, int S, int N, int V, float* lm_out, hipStream_t s) {
+    if (lm.max_order < 1 || lm.max_order > 5) return 1;
+    LmScoreArgs a{};
+    a.lm = lm; a.cand = cand; a.tok = tok; a.row_len = row_len; a.done = done; a.lm_out = lm_out;
+    a.N = N; a.M = M; a.Lcap = Lcap; a.p = p; a.V = V;
+    // (the order bounds the keys a lane holds in registers: two instantiations, as the CTC search has them)
+    if (lm.max_order <= 3) hipLaunchKernelGGL(joint_lm_score_kernel<3>, dim3((unsigned)S), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(joint_lm_score_kernel<5>, dim3((unsigned)S), dim3(64), 0, s, a);
+    return 0;
 }
 
 }  // namespace masr

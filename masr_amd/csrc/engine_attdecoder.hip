@@ -535,36 +535,53 @@ int masr_op_decoder_step(masr_engine* e, const float* enc_dev, const int32_t* en
 
 // ------------------------------------------------------------------------------------------------
 // decoder: joint -- the search above ranked by the joint key: the step launches with the top M of every row, the CTC prefix
-// scorer over the M candidates, the joint merge, the prefix states of the N winners (kernels: decoder_joint.hip)
+// scorer over the M candidates, the joint merge, the prefix states of the N winners (kernels: decoder_joint.hip); with a language
+// model (masr_joint_decode_lm) the n-gram score of the same M candidates between the step and the merge
 // ------------------------------------------------------------------------------------------------
-int masr_joint_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const float* post_dev,
-                      int32_t input_is_log, int32_t beam_size, int32_t ctc_candidates, float ctc_weight, float length_bonus,
-                      int32_t max_len, int32_t* tokens_dev, int32_t Lcap, int32_t* lens_dev, float* scores_dev, float* att_or_null,
-                      float* ctc_or_null, int32_t* steps_host_or_null, void* stream) {
-    const std::string w("masr_joint_decode");
+// (lm_weight 0: no model is looked at and nothing of the LM is launched -- masr_joint_decode's launches and bits)
+static int joint_decode_impl(const char* who, masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp,
+                             const float* post_dev, int32_t input_is_log, int32_t beam_size, int32_t ctc_candidates, float ctc_weight,
+                             float length_bonus, masr_lm* lm_model, float lm_weight, int32_t max_len, int32_t* tokens_dev, int32_t Lcap,
+                             int32_t* lens_dev, float* scores_dev, float* att_or_null, float* ctc_or_null, float* lm_or_null,
+                             int32_t* steps_host_or_null, void* stream) {
+    const std::string w(who);
     if (!enc_dev || !enc_lens_dev || !tokens_dev || !lens_dev || !scores_dev) return fail(w + ": null argument");
     if (max_len < 0) return fail(w + ": max_len must be 0 (no limit of its own) or positive");
     if (!(ctc_weight >= 0.f && ctc_weight < 1.f)) return fail(w + ": ctc_weight = " + std::to_string(ctc_weight) + " is outside [0, 1)");
     if (!std::isfinite(length_bonus)) return fail(w + ": length_bonus must be finite");
+    if (!(std::isfinite(lm_weight) && lm_weight >= 0.f))
+        return fail(w + ": lm_weight = " + std::to_string(lm_weight) + " is not a finite number >= 0");
+    if (lm_weight > 0.f && !lm_model) return fail(w + ": lm_weight > 0 needs a language model (lm_or_null is null)");
+    if (lm_model && lm_word_based(lm_model))
+        return fail(w + ": word-based language models are searched on host threads (masr_beam_search_batch_lm): the joint search "
+                    "scores vocabulary tokens");
     if (ctc_weight > 0.f && !post_dev) return fail(w + ": ctc_weight > 0 needs the CTC posteriors (post_dev is null)");
     if (beam_size >= 1 && beam_size <= 64 && (ctc_candidates < beam_size || ctc_candidates > 64))
         return fail(w + ": ctc_candidates = " + std::to_string(ctc_candidates) + " is outside beam_size .. 64");
-    CHK(step_shape_check(e, "masr_joint_decode", B, Tp, beam_size, Lcap));
+    CHK(step_shape_check(e, who, B, Tp, beam_size, Lcap));
     const int V = e->cfg.vocab_size, M = ctc_candidates;
     if (M > V) return fail(w + ": ctc_candidates = " + std::to_string(M) + " exceeds the vocabulary of " + std::to_string(V));
+    if (lm_model && lm_vocab_size(lm_model) != V)
+        return fail(w + ": the language model was loaded for a vocabulary of " + std::to_string(lm_vocab_size(lm_model)) +
+                    " tokens, the engine has " + std::to_string(V));
     ENTER(e);
     hipStream_t st = (hipStream_t)stream;
     CallGuard call_guard(e, st);
+    // the table of the model on this device, before the first launch of the call (a first use uploads it and waits for that)
+    const bool fuse = lm_weight > 0.f;
+    LmView lmv{};
+    if (fuse && lm_device_view(lm_model, &lmv)) return fail(w + ": " + masr_lm_last_error());
     StepPlan pl{};
     pl.B = B; pl.N = beam_size; pl.S = B * beam_size; pl.Tp = Tp; pl.Lcap = Lcap; pl.max_len = max_len;
     pl.Lrun = step_run_bound(e, Tp, Lcap, max_len);
     CHK(step_workspaces(e, pl, M));
     const bool ctc = ctc_weight > 0.f;
     const size_t S = (size_t)pl.S, rows = S * 2 * Tp;
-    // att[2] | psi[2] [S], n[2] [S], the candidates' psi [S, M]
-    CHK(e->jt_tab.ensure((6 * S + S * M) * sizeof(float)));
+    // att[2] | psi[2] [S], n[2] [S], Lm[2] [S], the candidates' psi [S, M] and (with a model) their lm [S, M]
+    CHK(e->jt_tab.ensure((8 * S + (fuse ? 2 : 1) * S * M) * sizeof(float)));
     float* jt = e->jt_tab.as<float>();
-    float *att[2] = {jt, jt + S}, *psi[2] = {jt + 2 * S, jt + 3 * S}, *psi_cand = jt + 6 * S;
+    float *att[2] = {jt, jt + S}, *psi[2] = {jt + 2 * S, jt + 3 * S}, *lms[2] = {jt + 6 * S, jt + 7 * S}, *psi_cand = jt + 8 * S,
+          *lm_cand = psi_cand + S * M;
     int* cnt[2] = {reinterpret_cast<int*>(jt + 4 * S), reinterpret_cast<int*>(jt + 5 * S)};
     float* r[2] = {nullptr, nullptr};
     PrefixRows pr{};
@@ -577,7 +594,7 @@ int masr_joint_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_l
     }
     const int poll = step_poll_every();
     launch_step_init(pl.score[0], pl.done, pl.active, enc_lens_dev, B, pl.N, Tp, Lcap, max_len, e->cfg.max_pos, st);
-    launch_joint_init(att[0], psi[0], cnt[0], pl.S, pl.N, st);
+    launch_joint_init(att[0], psi[0], lms[0], cnt[0], pl.S, pl.N, st);
     if (ctc) launch_prefix_init(pr, r[0], st);
     step_source_kv(e, st, enc_dev, pl);
     float* top_v = e->st_top.as<float>();
@@ -586,8 +603,11 @@ int masr_joint_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_l
     for (int p = 0; p < pl.Lrun; ++p) {
         CHK(step_forward(e, st, pl, p, pl.tok[cur], pl.anc[cur], enc_lens_dev, M, nullptr, nullptr));
         if (ctc) launch_prefix_score(pr, top_i, M, pl.tok[cur], Lcap, p, nullptr, r[cur], psi_cand, st);
+        if (fuse && launch_joint_lm_score(lmv, top_i, M, pl.tok[cur], Lcap, p, nullptr, pl.done, pl.S, pl.N, V, lm_cand, st))
+            return fail(w + ": language model order " + std::to_string(lmv.max_order) + " is outside 1 .. 5");
         JointMerge m{};
-        m.top_v = top_v; m.top_i = top_i; m.psi_cand = ctc ? psi_cand : nullptr;
+        m.top_v = top_v; m.top_i = top_i; m.psi_cand = ctc ? psi_cand : nullptr; m.lm_cand = fuse ? lm_cand : nullptr;
+        m.lm_cur = lms[cur]; m.lm_next = lms[cur ^ 1]; m.lm_weight = lm_weight;
         m.key_cur = pl.score[cur]; m.key_next = pl.score[cur ^ 1];
         m.att_cur = att[cur]; m.att_next = att[cur ^ 1]; m.psi_cur = psi[cur]; m.psi_next = psi[cur ^ 1];
         m.n_cur = cnt[cur]; m.n_next = cnt[cur ^ 1];
@@ -610,8 +630,85 @@ int masr_joint_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_l
                        max_len, e->cfg.max_pos, st);
     if (att_or_null) HIPCHK(hipMemcpyAsync(att_or_null, att[cur], S * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (ctc_or_null) HIPCHK(hipMemcpyAsync(ctc_or_null, psi[cur], S * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (lm_or_null) HIPCHK(hipMemcpyAsync(lm_or_null, lms[cur], S * sizeof(float), hipMemcpyDeviceToDevice, st));
     LAUNCHCHK();
     if (steps_host_or_null) *steps_host_or_null = steps;
+    return 0;
+}
+
+int masr_joint_decode(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const float* post_dev,
+                      int32_t input_is_log, int32_t beam_size, int32_t ctc_candidates, float ctc_weight, float length_bonus,
+                      int32_t max_len, int32_t* tokens_dev, int32_t Lcap, int32_t* lens_dev, float* scores_dev, float* att_or_null,
+                      float* ctc_or_null, int32_t* steps_host_or_null, void* stream) {
+    return joint_decode_impl("masr_joint_decode", e, enc_dev, enc_lens_dev, B, Tp, post_dev, input_is_log, beam_size, ctc_candidates,
+                             ctc_weight, length_bonus, nullptr, 0.f, max_len, tokens_dev, Lcap, lens_dev, scores_dev, att_or_null,
+                             ctc_or_null, nullptr, steps_host_or_null, stream);
+}
+
+int masr_joint_decode_lm(masr_engine* e, const float* enc_dev, const int32_t* enc_lens_dev, int32_t B, int32_t Tp, const float* post_dev,
+                         int32_t input_is_log, int32_t beam_size, int32_t ctc_candidates, float ctc_weight, float length_bonus,
+                         masr_lm* lm_or_null, float lm_weight, int32_t max_len, int32_t* tokens_dev, int32_t Lcap, int32_t* lens_dev,
+                         float* scores_dev, float* att_or_null, float* ctc_or_null, float* lm_or_null_out, int32_t* steps_host_or_null,
+                         void* stream) {
+    return joint_decode_impl("masr_joint_decode_lm", e, enc_dev, enc_lens_dev, B, Tp, post_dev, input_is_log, beam_size,
+                             ctc_candidates, ctc_weight, length_bonus, lm_or_null, lm_weight, max_len, tokens_dev, Lcap, lens_dev,
+                             scores_dev, att_or_null, ctc_or_null, lm_or_null_out, steps_host_or_null, stream);
+}
+
+int masr_op_lm_scores(masr_engine* e, masr_lm* lm, const int32_t* prefix_host, const int32_t* prefix_lens_host, const int32_t* cand_host,
+                      int32_t R, int32_t L, int32_t M, float* out_host, void* stream) {
+    const std::string w("masr_op_lm_scores");
+    if (!lm || !prefix_host || !prefix_lens_host || !cand_host || !out_host) return fail(w + ": null argument");
+    if (R < 1 || R > 65535) return fail(w + ": R = " + std::to_string(R) + " rows is outside 1 .. 65535");
+    if (L < 1) return fail(w + ": L must be at least 1");
+    if (M < 1 || M > 64) return fail(w + ": M = " + std::to_string(M) + " candidates per row is outside 1 .. 64");
+    if (lm_word_based(lm))
+        return fail(w + ": word-based language models are searched on host threads (masr_beam_search_batch_lm): the joint search "
+                    "scores vocabulary tokens");
+    if (!e || !e->finalized) return fail("engine not finalized");
+    const int V = e->cfg.vocab_size;
+    if (lm_vocab_size(lm) != V)
+        return fail(w + ": the language model was loaded for a vocabulary of " + std::to_string(lm_vocab_size(lm)) +
+                    " tokens, the engine has " + std::to_string(V));
+    for (int s = 0; s < R; ++s) {
+        if (prefix_lens_host[s] < 0 || prefix_lens_host[s] > L)
+            return fail(w + ": prefix " + std::to_string(s) + " has length " + std::to_string(prefix_lens_host[s]) + ", outside 0 .. L");
+        for (int i = 0; i < prefix_lens_host[s]; ++i) {
+            const int t = prefix_host[(size_t)s * L + i];
+            if (t < 0 || t >= V)
+                return fail(w + ": token id " + std::to_string(t) + " of prefix " + std::to_string(s) + " is outside the vocabulary");
+        }
+        for (int m = 0; m < M; ++m) {
+            const int t = cand_host[(size_t)s * M + m];
+            if (t < 0 || t >= V)
+                return fail(w + ": candidate id " + std::to_string(t) + " of row " + std::to_string(s) + " is outside the vocabulary");
+        }
+    }
+    ENTER(e);
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard call_guard(e, st);
+    LmView lmv{};
+    if (lm_device_view(lm, &lmv)) return fail(w + ": " + masr_lm_last_error());
+    if (lmv.max_order < 1 || lmv.max_order > 5)          // (before anything is queued: the launcher refuses the same)
+        return fail(w + ": language model order " + std::to_string(lmv.max_order) + " is outside 1 .. 5");
+    // host table: tok [R, L] (zeros behind a prefix' length) | lens [R] | cand [R, M]; behind it on the device the scores [R, M]
+    const size_t nR = (size_t)R;
+    std::vector<int> tab(nR * L + nR + nR * M, 0);
+    int *h_tok = tab.data(), *h_len = h_tok + nR * L, *h_cand = h_len + nR;
+    for (int s = 0; s < R; ++s) {
+        h_len[s] = prefix_lens_host[s];
+        for (int i = 0; i < prefix_lens_host[s]; ++i) h_tok[(size_t)s * L + i] = prefix_host[(size_t)s * L + i];
+    }
+    memcpy(h_cand, cand_host, nR * M * sizeof(int));
+    CHK(e->jt_tab.ensure((tab.size() + nR * M) * sizeof(int)));
+    int* d = e->jt_tab.as<int>();
+    float* d_out = reinterpret_cast<float*>(d + tab.size());
+    // (the call waits for the stream before `tab` goes)
+    HIPCHK(hipMemcpyAsync(d, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    (void)launch_joint_lm_score(lmv, d + nR * L + nR, M, d, L, 0, d + nR * L, nullptr, R, 1, V, d_out, st);
+    LAUNCHCHK();
+    HIPCHK(hipMemcpyAsync(out_host, d_out, nR * M * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -77,6 +77,13 @@ int lm_device_view(masr_lm* lm, LmView* out) {
             if (dv.known) (void)hipFree(dv.known);
             return lm_fail("allocation / upload of the language model table on the device failed");
         }
+        // the copies above were issued on the null stream and the engine's lanes run on streams that do not wait for it: the host
+        // waits here, once per device, so that whatever the caller launches next -- on any stream -- finds the table in place
+        if (hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipFree(dv.table);
+            (void)hipFree(dv.known);
+            return lm_fail("allocation / upload of the language model table on the device failed");
+        }
         it = lm->dev.emplace(d, dv).first;
     }
     *out = lm->host_view();
@@ -87,6 +94,7 @@ int lm_device_view(masr_lm* lm, LmView* out) {
 LmView lm_host_view(const masr_lm* lm) { return lm->host_view(); }
 // ---- word-based scorers: the spelling dictionary and n-gram scoring over word ids (host search only) ----
 bool lm_word_based(const masr_lm* lm) { return !lm->char_based; }
+int lm_vocab_size(const masr_lm* lm) { return lm->V; }
 int lm_space_id(const masr_lm* lm) { return lm->space_id; }
 int lm_dict_next(const masr_lm* lm, int state, int token) {
     auto it = lm->dict_arc.find(((unsigned long long)state << 16) | (unsigned long long)(token & 0xFFFF));

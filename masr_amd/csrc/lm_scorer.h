@@ -38,9 +38,11 @@ struct LmView {
 };
 
 // host side, lm_scorer.cpp: the LM table in the memory of the current device (uploaded on first use there), and whether the model
-// scores words spelt out of several tokens (searched on host threads only)
+// scores words spelt out of several tokens (searched on host threads only); the size of the vocabulary the model was loaded for.
+// lm_device_view returns with the first-use upload finished: a launch that follows it on any stream reads the whole table.
 int lm_device_view(masr_lm* lm, LmView* out);
 bool lm_word_based(const masr_lm* lm);
+int lm_vocab_size(const masr_lm* lm);
 
 static constexpr float LM_OOV_SCORE = -1000.0f;   // scorer.h OOV_SCORE: returned as it is (not converted from log10)
 

@@ -996,6 +996,47 @@ class HipEngine:
                                          _ptr(scores), _ptr(att), _ptr(psi), C.byref(steps), _stream()))
         return tokens, lens, scores, att, psi, steps.value
 
+    def joint_decode_lm(self, enc, enc_lens, post, language_model=None, lm_weight=0.0, beam_size=10, ctc_candidates=None,
+                        ctc_weight=0.3, length_bonus=0.0, max_len=0, lcap=None, input_is_log=False):
+        """masr_joint_decode_lm: ``joint_decode`` with the n-gram ``language_model`` (decoders.lm_scorer.LanguageModel, or None)
+        fused into the key, J = (((1 - ctc_weight) A + ctc_weight psi) + lm_weight Lm) + length_bonus n with Lm the float32 sum
+        of the model's conditional log-probabilities of the hypothesis' tokens -> ``joint_decode``'s results with Lm [B, N]
+        float32 behind psi: (tokens, lens, J, A, psi, Lm, steps).  ``lm_weight`` 0 launches nothing of the model and returns
+        ``joint_decode``'s bits (Lm = 0)."""
+        B, Tp, _ = enc.shape
+        N, max_len = int(beam_size), int(max_len)
+        M = min(2 * N, 64, self.vocab_size) if ctc_candidates is None else int(ctc_candidates)
+        if post is not None and (tuple(post.shape) != (B, Tp, self.vocab_size) or post.dtype != torch.float32 or not post.is_contiguous()):
+            raise ValueError(f'joint_decode_lm: contiguous float32 posteriors [{B}, {Tp}, {self.vocab_size}] expected')
+        if lcap is None:
+            lcap = max(1, min(Tp, self.max_pos - 1, max_len if max_len > 0 else Tp))
+        tokens = torch.empty(B, max(N, 1), max(int(lcap), 1), dtype=torch.int32, device=self.device)
+        lens = torch.empty(B, max(N, 1), dtype=torch.int32, device=self.device)
+        scores, att, psi, lm = (torch.empty(B, max(N, 1), dtype=torch.float32, device=self.device) for _ in range(4))
+        steps = C.c_int32(0)
+        check(self.lib.masr_joint_decode_lm(self.h, _ptr(enc), _ptr(enc_lens), B, Tp, _ptr(post), 1 if input_is_log else 0, N, M,
+                                            float(ctc_weight), float(length_bonus), language_model.h if language_model is not None else None,
+                                            float(lm_weight), max_len, _ptr(tokens), int(lcap), _ptr(lens), _ptr(scores), _ptr(att),
+                                            _ptr(psi), _ptr(lm), C.byref(steps), _stream()))
+        return tokens, lens, scores, att, psi, lm, steps.value
+
+    def lm_scores(self, language_model, prefixes, prefix_lens, cands):
+        """masr_op_lm_scores: the LM score kernel of the joint search alone from HOST tables.  ``prefixes`` [R, L] token ids with
+        ``prefix_lens`` [R] in 0 .. L, ``cands`` [R, M] candidate ids (vocab_size - 1 is scored as ``</s>``) -> [R, M] numpy
+        float32, ``language_model.cond_log_prob(prefix + [candidate])`` bit for bit; returns when the work has finished."""
+        prefixes = np.ascontiguousarray(prefixes, np.int32)
+        prefix_lens = np.ascontiguousarray(prefix_lens, np.int32)
+        cands = np.ascontiguousarray(cands, np.int32)
+        if prefixes.ndim != 2 or cands.ndim != 2 or prefix_lens.shape != (prefixes.shape[0],) or cands.shape[0] != prefixes.shape[0]:
+            raise ValueError('lm_scores: prefixes [R, L], prefix_lens [R] and cands [R, M] expected')
+        R, L = prefixes.shape
+        M = cands.shape[1]
+        out = np.zeros((R, max(M, 1)), np.float32)
+        as_p = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self.lib.masr_op_lm_scores(self.h, language_model.h if language_model is not None else None, as_p(prefixes),
+                                         as_p(prefix_lens), as_p(cands), R, L, M, as_p(out), _stream()))
+        return out
+
     def ctc_prefix_scores(self, post, frames, row_utt, prefixes, prefix_lens, cands, input_is_log=False):
         """masr_op_ctc_prefix_scores: the CTC prefix scorer driven alone from HOST tables.  ``post`` [B, T', V] on the device,
         ``frames`` [B] valid frames, and R rows: ``row_utt`` [R] utterance of the row, ``prefixes`` [R, L] with ``prefix_lens``

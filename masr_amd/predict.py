@@ -90,11 +90,15 @@ class MASRPredictor:
         if self.configs.decoder == 'joint':
             # the attention search ranked jointly with the CTC prefix score, on the GPU (decoders/joint_decoder.py); the
             # configuration is checked before anything is loaded
-            from masr_amd.decoders.joint_decoder import JointDecoder, DS2_REFUSAL, validate_joint_conf
+            from masr_amd.decoders.joint_decoder import JointDecoder, DS2_REFUSAL, load_language_model, validate_joint_conf
             if self.configs.use_model == 'deepspeech2':
                 raise Exception(DS2_REFUSAL)
             jconf = validate_joint_conf(self.configs.get('joint_decoder_conf', None), self.configs.get('model_conf', None),
                                         len(self._text_featurizer.vocab_list))
+            # shallow fusion: the ARPA model of language_model_path, loaded only where lm_weight > 0 uses it
+            lm_path = jconf.pop('language_model_path', None)
+            if lm_path is not None:
+                jconf['language_model'] = load_language_model(lm_path, self._text_featurizer.vocab_list)
             self.joint_decoder = JointDecoder(vocab_list=self._text_featurizer.vocab_list, **jconf)
         if state_dict is None and not os.path.exists(model_path):
             raise Exception("模型文件不存在，请检查{}是否存在！".format(model_path))

@@ -1,6 +1,6 @@
 """Times one pass of ``decoder: attention`` (masr_attention_decode) beside the encoder pass it follows.
 
-    python tools/attention_decode_bench.py [--batch 32] [--seconds 10] [--beam 10] [--runs 5] [--vocab 4233] [--max-len 0] [--torch] [--joint]
+    python tools/attention_decode_bench.py [--batch 32] [--seconds 10] [--beam 10] [--runs 5] [--vocab 4233] [--max-len 0] [--torch] [--joint] [--lm]
 
 Synthetic Conformer checkpoint with the shipped decoder (3 + 3 blocks, 4 heads, linear_units 1024; only the left half is used),
 ``batch`` utterances of ``seconds`` s, beam ``beam``.  Per run, alternating: the encoder pass (masr_encode_full) and the search,
@@ -9,7 +9,9 @@ checkpoints rarely emit eos, so the search runs to its limit (the utterance's en
 that length.  ``--torch``: the same search in plain torch on the device beside it (batched over the hypotheses, the whole prefix
 recomputed every step as the reference's forward_one_step does without a cache; ties as torch.topk leaves them).  ``--joint``: one
 pass of ``decoder: joint`` beside it on the same encoder output (the CTC head + masr_joint_decode, ``--ctc-weight`` 0.3,
-``--candidates`` 20).  The per-kernel split comes from a kernel trace of this script."""
+``--candidates`` 20).  ``--lm`` (implies ``--joint``): one more pass beside those, masr_joint_decode_lm with a synthetic
+character ARPA model of ``--lm-order`` 3 over the vocabulary (``--lm-higher`` n-grams drawn per order above 1) at ``--lm-weight`` 0.3,
+and the same call with lm_weight 0 (which launches what masr_joint_decode launches).  The per-kernel split comes from a kernel trace of this script."""
 import argparse
 import json
 import math
@@ -83,7 +85,12 @@ def main():
     ap.add_argument('--joint', action='store_true')
     ap.add_argument('--ctc-weight', type=float, default=0.3)
     ap.add_argument('--candidates', type=int, default=20)
+    ap.add_argument('--lm', action='store_true')
+    ap.add_argument('--lm-weight', type=float, default=0.3)
+    ap.add_argument('--lm-order', type=int, default=3)
+    ap.add_argument('--lm-higher', type=int, default=20000)
     a = ap.parse_args()
+    a.joint = a.joint or a.lm
     from masr_amd.engine import HipEngine, positional_table
     from masr_amd.utils import synthetic
     dec = dict(linear_units=1024, num_blocks=3, r_num_blocks=3)
@@ -102,7 +109,14 @@ def main():
         t1.record()
         t1.synchronize()
         return t0.elapsed_time(t1), out
-    t_enc, t_dec, t_torch, t_joint, steps = [], [], [], [], 0
+    t_enc, t_dec, t_torch, t_joint, t_lm0, t_lm, steps = [], [], [], [], [], [], 0
+    lm = None
+    if a.lm:
+        import tempfile
+        from masr_amd.decoders.lm_scorer import LanguageModel, write_synthetic_arpa
+        toks = synthetic.synthetic_vocab(a.vocab)
+        with tempfile.TemporaryDirectory() as tmp:
+            lm = LanguageModel(write_synthetic_arpa(os.path.join(tmp, 'bench.arpa'), toks, order=a.lm_order, n_higher=a.lm_higher), toks)
     dsd = {k: v.to(eng.device) for k, v in sd.items() if k.startswith('decoder.left_decoder.')} if a.torch else None
     pe = positional_table(int(enc_lens.max()) + 2, 256).to(eng.device) if a.torch else None
     for k in range(a.runs + 2):
@@ -111,6 +125,11 @@ def main():
         steps = out[3]
         if a.joint:
             tj, _ = timed(lambda: eng.joint_decode(enc, enc_lens, eng.ctc_probs(enc), a.beam, a.candidates, a.ctc_weight, 0.0, a.max_len))
+        if a.lm:
+            fused = lambda w: eng.joint_decode_lm(enc, enc_lens, eng.ctc_probs(enc), lm, w, a.beam, a.candidates, a.ctc_weight, 0.0,
+                                                  a.max_len)
+            tl0, _ = timed(lambda: fused(0.0))
+            tl, _ = timed(lambda: fused(a.lm_weight))
         if a.torch:
             with torch.no_grad():
                 tt, _ = timed(lambda: torch_search(dsd, enc, enc_lens, a.beam, pe, 4, a.max_len))
@@ -119,6 +138,9 @@ def main():
             t_dec.append(td)
             if a.joint:
                 t_joint.append(tj)
+            if a.lm:
+                t_lm0.append(tl0)
+                t_lm.append(tl)
             if a.torch:
                 t_torch.append(tt)
     stat = lambda v: {'median_ms': float(np.median(v)), 'min_ms': float(min(v)), 'max_ms': float(max(v))}
@@ -129,6 +151,10 @@ def main():
         res['torch_search'] = stat(t_torch)
     if a.joint:
         res['joint_decode_pass'] = dict(stat(t_joint), ctc_weight=a.ctc_weight, candidates=a.candidates)
+    if a.lm:
+        res['joint_decode_lm_weight0_pass'] = stat(t_lm0)
+        res['joint_decode_lm_pass'] = dict(stat(t_lm), lm_weight=a.lm_weight, order=lm.max_order, n_ngrams=lm.n_ngrams)
+        res['lm_ms_per_step'] = (res['joint_decode_lm_pass']['median_ms'] - res['joint_decode_pass']['median_ms']) / max(steps, 1)
     print(json.dumps(res))
     eng.close()
 
